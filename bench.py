@@ -14,11 +14,15 @@ resident in HBM before the timed region; weights are seeded random-init (the ref
 stripped blob).  Frames shard across ranks with no data-path collective (weak scaling); the only collectives
 are the timing barrier and the MAX over ranks.
 
-Rank 0 prints ONE JSON line: metric/value (pose solves per second over the whole job), ``roofline`` for the
-correlation-lookup kernel (algorithmic bytes per launch / HIP-event time measured inside the timed region) and
-``roofline_conv`` (the fused f32-MFMA convolutions that now hold most of the step) and
+Rank 0 prints ONE JSON line: metric/value (pose solves per second over the whole job) and ms_per_step.  A plain run
+does only that: set-up, W warm-up steps, K timed steps, the line.  ``--full`` adds everything else, measured after
+the timed region (and with the lookup and the solve bracketed by HIP events inside it): ``roofline`` for the
+correlation-lookup kernel (algorithmic bytes per launch / HIP-event time), ``roofline_conv`` (the fused f32-MFMA
+convolutions that now hold most of the step), the labelled bf16x3 variant, the deployment numbers and
 ``cpu_baseline`` (the CPU oracle -- a PyTorch-CPU port of the reference path -- on a bounded sample of the
 same inputs with the same weights).
+
+``--dump-outputs DIR`` writes what the last timed step returned as DIR/<name>.npy (see write_outputs).
 """
 import argparse
 import json
@@ -73,6 +77,25 @@ def lookup_algorithmic_bytes(pairs, h8, w8, levels=4, r=4):
     return pairs * (nq * levels * ((2 * r + 2) ** 2 + (2 * r + 1) ** 2) * 4 + nq * 8)
 
 
+DUMP_SAMPLE = 1 << 20          # elements kept of a larger output (4 MiB in f32): the default step's eight outputs stay under 64 MB in all
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: every output as ``path/<name>.npy``, float64 where it is computed in f64, else float32 (masks as 0 / 1).  An output
+    of more than DUMP_SAMPLE elements is stored flattened (C order) at DUMP_SAMPLE indices drawn with a fixed seed and sorted: the same
+    elements in every run of the same shape, so that two builds can be compared output for output."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        n = t.numel()
+        if n > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        np.save(os.path.join(path, name + '.npy'), t.cpu().numpy())
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -87,7 +110,12 @@ def parse_args(argv=None):
     ap.add_argument('--raft-iters', type=int, default=12)
     ap.add_argument('--solver', default='lbfgs', choices=['lbfgs', 'gn'])
     ap.add_argument('--solver-iters', type=int, default=8)
-    ap.add_argument('--cpu-frames', type=int, default=8, help='frames timed on the CPU oracle (0 = skip)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline: HIP events around the lookup and the solve in the timed region, the rooflines, '
+                         'the bf16x3 variant, the live PMC traffic passes, the deployment numbers, the CPU baseline and (N > 1) the sequence walk')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned as DIR/<name>.npy (rank 0; large outputs as a fixed, seeded sample)')
+    ap.add_argument('--cpu-frames', type=int, default=8, help='with --full: frames timed on the CPU oracle (0 = skip)')
     ap.add_argument('--seq-frames', type=int, default=33, help='--mode sequence: frames per GPU (weak scaling); 33 = 32 pairs = two chunks of 16 at N = 1')
     ap.add_argument('--seq-chunk', type=int, default=16, help='--mode sequence: frames per RAFT pass (SequenceTracker(chunk=...)); 1 = one frame at a time')
     ap.add_argument('--fp16-features', action='store_true',
@@ -98,10 +126,10 @@ def parse_args(argv=None):
                     help='LABELLED VARIANT (reported under its own dtype, never the headline): the update block\'s 3x3 layers with >= 128 input channels, the '
                          '1x1 layers (convc1, the encoders\' and the mask head\'s output layers) and the correlation build with every f32 product as six bf16 '
                          'products of an exact 3-way split on the 16-bit matrix cores (raft.CONV_BF16X3)')
-    ap.add_argument('--no-extras', action='store_true', help='skip the batch-1 latency / tracker / Gauss-Newton lines (and the live PMC traffic passes)')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the batch-1 latency / tracker / Gauss-Newton lines (and the live PMC traffic passes)')
     ap.add_argument('--one-stream', action='store_true', help='encoders one after the other on one stream (raft.ENC_STREAMS = False): for kernel-trace profiles whose per-kernel durations must not overlap')
     ap.add_argument('--no-live-traffic', action='store_true',
-                    help='do not run the two rocprofv3 --pmc child passes after the timed region; roofline.traffic then comes from profiles/pmc_traffic.json')
+                    help='with --full: do not run the two rocprofv3 --pmc child passes after the timed region; roofline.traffic then comes from profiles/pmc_traffic.json')
     return ap.parse_args(argv)
 
 
@@ -287,6 +315,8 @@ def run_sequence(args, rank, world, dev, dist):
         dist.barrier()
         dist.destroy_process_group()
         sys.exit(3)
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, {'poses': poses, 'rel': seq['rel'], 'ok': ok})
     if rank != 0:
         return None
     return {
@@ -339,12 +369,11 @@ def run_batch(args, rank, world, dev, dist):
         lookup_events.append((e0, e1))
         return r
 
-    rpe_amd.ops.CorrPyramid.lookup = timed_lookup
     # The product enqueues the update loop as ONE launch list (raft.LOOP_OPLIST -> rpe_run_ops), so the lookup is not a Python call any
     # more: the list itself records raw HIP events around each iteration's lookup when raft.LOOKUP_EVENT_SINK hands it some.  One pair per
     # lookup launch of the timed region, created up front (no event is created, and no extra record issued, inside the timed region).
     from rpe_amd import _lib as _rpe_lib
-    raw_ev = _rpe_lib.RawEvents(2 * args.raft_iters * max(1, args.steps))
+    raw_ev = _rpe_lib.RawEvents(2 * args.raft_iters * max(1, args.steps)) if args.full else None
     raw_used = [0]
 
     def lookup_sink(iters):
@@ -366,9 +395,6 @@ def run_batch(args, rank, world, dev, dist):
         e1.record()
         solve_events.append((e0, e1))
         return r
-
-    rpe_amd.ops.pose_solve = timed_solve
-    rpe_amd.pose_head.ops.pose_solve = timed_solve
 
     # the fused convolutions (k_conv_igemm): FLOPs and HIP-event time of every launch -- in a diagnostic pass AFTER the timed region: ~300 event
     # records per step inside it cost the headline 1.5-2 % (68.3 vs 69.6 ms per step), and only the lookup's timing has to come from there
@@ -409,8 +435,6 @@ def run_batch(args, rank, world, dev, dist):
             conv_events.append((e0, e1, flop))
         return r
 
-    rpe_amd.ops.conv_fused = timed_conv            # raft.py calls it as ops.conv_fused
-
     # the Winograd 3x3 layers (k_conv_wino): EXECUTED matrix FLOPs = 16 products per 2x2 output tile and (ci, co) pair,
     # i.e. 4/9 of the direct form's; the direct-form count is kept separately as "effective"
     wino_events = []
@@ -441,7 +465,12 @@ def run_batch(args, rank, world, dev, dist):
         timed_launch.op, timed_launch.keep = launch.op, launch.keep
         return timed_launch
 
-    rpe_amd.ops.conv_wino = timed_wino
+    if args.full:                                  # the wrappers above feed --full's rooflines; a plain run calls the product as it is
+        rpe_amd.ops.CorrPyramid.lookup = timed_lookup
+        rpe_amd.ops.pose_solve = timed_solve
+        rpe_amd.pose_head.ops.pose_solve = timed_solve
+        rpe_amd.ops.conv_fused = timed_conv        # raft.py calls it as ops.conv_fused
+        rpe_amd.ops.conv_wino = timed_wino
 
     def step():
         gpu_in['mask2'].copy_(mask2_init)          # infer() mutates mask2 in place, as the reference does
@@ -460,10 +489,14 @@ def run_batch(args, rank, world, dev, dist):
     torch.cuda.synchronize()                       # persistent workspaces / launch descriptors built on first use
     for _ in range(args.warmup):
         step()
-    elapsed, out = timed_region(timed_step, args.steps, 0, dev, dist)
+    elapsed, out = timed_region(timed_step if args.full else step, args.steps, 0, dev, dist)
+    if args.dump_outputs and rank == 0:            # first: the outputs live in persistent workspaces that any further step overwrites
+        pose, depth1, depth2, (w2d, w3d), time_flow, stereo_flow2 = out
+        write_outputs(args.dump_outputs, {'pose': pose.data, 'depth1': depth1, 'depth2': depth2, 'w2d': w2d, 'w3d': w3d, 'time_flow': time_flow,
+                                          'stereo_flow2': stereo_flow2, 'mask2': gpu_in['mask2']})     # (infer() narrows mask2 in place)
 
     seq_line = None
-    if world > 1 and dist is not None and not args.no_extras:
+    if world > 1 and dist is not None and args.full and not args.no_extras:
         # The batch metric shards frames with no data-path collective; the multi-GPU number that exercises the all-gather of relative poses
         # and the prefix product is a SEQUENCE walk.  A short one (one chunk of 16 + halo per GPU, one timed walk) on every rank, after
         # the timed region, so that a scaling run's line carries it.  (N > 1 has never been run on hardware in this pool.)
@@ -482,37 +515,19 @@ def run_batch(args, rank, world, dev, dist):
         return None
     pose, _, depth2, weights, time_flow, stereo_flow2 = out
     conv_steps = 2                                 # diagnostic pass: the same step with every convolution launch bracketed by HIP events
-    timing['conv'] = True
-    enc_streams, raft_mod.ENC_STREAMS = raft_mod.ENC_STREAMS, False     # one stream: a launch's duration is its own, not two overlapping launches'
-    loop_oplist, raft_mod.LOOP_OPLIST = raft_mod.LOOP_OPLIST, False     # launch by launch from Python: the wrappers above bracket each launch with events
-    try:
-        for _ in range(conv_steps):
-            step()
-        torch.cuda.synchronize()
-    finally:
-        timing['conv'] = False
-        raft_mod.ENC_STREAMS = enc_streams
-        raft_mod.LOOP_OPLIST = loop_oplist
+    if args.full:
+        timing['conv'] = True
+        enc_streams, raft_mod.ENC_STREAMS = raft_mod.ENC_STREAMS, False     # one stream: a launch's duration is its own, not two overlapping launches'
+        loop_oplist, raft_mod.LOOP_OPLIST = raft_mod.LOOP_OPLIST, False     # launch by launch from Python: the wrappers above bracket each launch with events
+        try:
+            for _ in range(conv_steps):
+                step()
+            torch.cuda.synchronize()
+        finally:
+            timing['conv'] = False
+            raft_mod.ENC_STREAMS = enc_streams
+            raft_mod.LOOP_OPLIST = loop_oplist
     info = model.pose_head.problem.last_info.cpu()
-    lk_ms = sorted([a.elapsed_time(b) for a, b in lookup_events] + [raw_ev.elapsed_ms(i, i + 1) for i in range(0, raw_used[0], 2)])
-    lk_avg_s = sum(lk_ms) / max(1, len(lk_ms)) / 1e3
-
-    def pct(q):
-        return lk_ms[min(len(lk_ms) - 1, int(q * len(lk_ms)))] * 1e3 if lk_ms else 0.0
-    lk_med_s = pct(0.5) / 1e6
-    alg = lookup_algorithmic_bytes(2 * B, H // 8, W // 8)
-    # frac from the MEDIAN launch: a HIP-event pair also spans the launch gap in front of the kernel, and a mean over 240 launches carries
-    # the outliers of the box (round 4: 98.3 us mean in the driver's run against 93.9 us by rocprofv3); mean, p10 and p90 are reported beside it
-    achieved = alg / lk_med_s / 1e9 if lk_med_s > 0 else 0.0
-    achieved_mean = alg / lk_avg_s / 1e9 if lk_avg_s > 0 else 0.0
-    traffic = traffic_src = None                # HBM bytes per launch from separate rocprofv3 --pmc passes over THIS program
-    try:                                        # (tools/pmc_bench.sh -> profiles/pmc_traffic.json), valid for the default workload only
-        pmc = json.load(open(os.path.join(ROOT, 'profiles', 'pmc_traffic.json')))['k_corr_lookup_bench']
-        if (B, H, W) == (16, 512, 640):
-            traffic, traffic_src = pmc['traffic_bytes_per_launch'], pmc['source']
-    except (OSError, KeyError, ValueError):
-        pass
-    rounds_own = lookup_rounds(last_lookup['pyr'], last_lookup['coords'])      # roughness of the coordinates this run looked up last
     res = {
         'metric': 'stereo-pair pose solves/sec (640x512, 8 solver iters)',
         'value': world * B * args.steps / elapsed,
@@ -532,6 +547,34 @@ def run_batch(args, rank, world, dev, dist):
                                + (', conv + correlation bf16x3 (labelled variant)' if args.conv_bf16x3 else ''),
                    'frames_per_gpu': B, 'height': H, 'width': W, 'raft_iters': args.raft_iters,
                    'solver': args.solver, 'solver_iters': args.solver_iters, 'parallelism': f'frames sharded x{world}'},
+        'solver_iters_run': {'min': int(info[:, 0].min()), 'max': int(info[:, 0].max())},
+        'valid_fraction': float(gpu_in['mask2'].float().mean()),
+        'peak_hbm_gb': torch.cuda.max_memory_allocated(dev) / 1e9,
+    }
+    if args.conv_bf16x3:
+        res['conv_bf16x3_families'] = X3_FAMILIES
+    if not args.full:
+        return res
+    lk_ms = sorted([a.elapsed_time(b) for a, b in lookup_events] + [raw_ev.elapsed_ms(i, i + 1) for i in range(0, raw_used[0], 2)])
+    lk_avg_s = sum(lk_ms) / max(1, len(lk_ms)) / 1e3
+
+    def pct(q):
+        return lk_ms[min(len(lk_ms) - 1, int(q * len(lk_ms)))] * 1e3 if lk_ms else 0.0
+    lk_med_s = pct(0.5) / 1e6
+    alg = lookup_algorithmic_bytes(2 * B, H // 8, W // 8)
+    # frac from the MEDIAN launch: a HIP-event pair also spans the launch gap in front of the kernel, and a mean over 240 launches carries
+    # the GPU's outliers (round 4: a 98.3 us mean against 93.9 us by rocprofv3's kernel trace); mean, p10 and p90 are reported beside it
+    achieved = alg / lk_med_s / 1e9 if lk_med_s > 0 else 0.0
+    achieved_mean = alg / lk_avg_s / 1e9 if lk_avg_s > 0 else 0.0
+    traffic = traffic_src = None                # HBM bytes per launch from separate rocprofv3 --pmc passes over THIS program
+    try:                                        # (tools/pmc_bench.sh -> profiles/pmc_traffic.json), valid for the default workload only
+        pmc = json.load(open(os.path.join(ROOT, 'profiles', 'pmc_traffic.json')))['k_corr_lookup_bench']
+        if (B, H, W) == (16, 512, 640):
+            traffic, traffic_src = pmc['traffic_bytes_per_launch'], pmc['source']
+    except (OSError, KeyError, ValueError):
+        pass
+    rounds_own = lookup_rounds(last_lookup['pyr'], last_lookup['coords'])      # roughness of the coordinates this run looked up last
+    res.update({
         'roofline': {'kernel': 'k_corr_lookup', 'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
                      'frac': achieved / HBM_PEAK_GBS, 'peak_achievable': HBM_ACHIEVABLE_GBS, 'frac_of_achievable': achieved / HBM_ACHIEVABLE_GBS,
                      'traffic': traffic, 'algorithmic_bytes_per_launch': alg,
@@ -545,10 +588,7 @@ def run_batch(args, rank, world, dev, dist):
         'roofline_conv': conv_roofline(conv_events, conv_steps),
         'roofline_conv_winograd_1d': wino_roofline(wino1d_events, conv_steps, 'k_conv_wino1d'),
         'roofline_conv_winograd': wino_roofline(wino_events, conv_steps),
-        'solver_iters_run': {'min': int(info[:, 0].min()), 'max': int(info[:, 0].max())},
-        'valid_fraction': float(gpu_in['mask2'].float().mean()),
-        'peak_hbm_gb': torch.cuda.max_memory_allocated(dev) / 1e9,
-    }
+    })
     # the whole step against the f32 matrix peak: executed FLOPs of the matrix kernels (Winograd layers at their executed 4/9 and 2/5)
     # over the step time -- the floor the f32 formulation could reach at 100 % of the pipe (6.09 TFLOP, 38.7 ms, 0.58)
     fam = [res['roofline_conv'], res['roofline_conv_winograd'], res['roofline_conv_winograd_1d']]
@@ -557,8 +597,6 @@ def run_batch(args, rank, world, dev, dist):
     res['roofline_step'] = {'executed_tflop': ex, 'floor_ms_at_peak': ex / F32_MFMA_PEAK_TFLOPS * 1e3,
                             'frac': (ex / F32_MFMA_PEAK_TFLOPS * 1e3) / res['ms_per_step'] if res['ms_per_step'] > 0 else 0.0,
                             'counts': 'k_conv_igemm + k_conv1x1 + k_conv_wino + k_conv_wino1d (executed) + k_corr_build; stems, heads and element-wise passes not counted'}
-    if args.conv_bf16x3:
-        res['conv_bf16x3_families'] = X3_FAMILIES
     if seq_line is not None:
         res.update(seq_line)
     if world == 1 and not args.no_extras and not args.conv_bf16x3 and not args.corr_bf16x3 and not args.fp16_features:
