@@ -52,9 +52,10 @@ const char *rpe_version(void);
  * Entry points are only ever ADDED under one RPE_ABI_VERSION (they change no struct and no existing signature); RPE_ABI_MINOR counts those
  * additions, so a binding can require "version 5, minor >= m" for the newest entry point it calls -- or probe with dlsym:
  *   minor 0: the 68 entry points of round 4;  1: rpe_conv_wino_x3*, rpe_conv1x1_x3*, rpe_conv_wino1d_x3* (9, round 5);  2: rpe_run_ops and
- *   the rpe_*_args structs of the prepared launch lists, rpe_corr_lookup_conv1x1* (round 6). */
+ *   the rpe_*_args structs of the prepared launch lists, rpe_corr_lookup_conv1x1* (round 6);  3: struct rpe_surfel_map and the
+ *   rpe_surfel_* entry points of frame-to-model tracking (7). */
 #define RPE_ABI_VERSION 5
-#define RPE_ABI_MINOR 2
+#define RPE_ABI_MINOR 3
 int rpe_abi_minor(void);
 int rpe_abi_version(void);
 
@@ -577,6 +578,68 @@ int rpe_remap_nearest(const void *src, int src_is_u8, int c, int h, int w, const
  * a 1-LSB difference to a particular OpenCV build (other interpolation tables, FMA contraction in remapBilinear<float>) would go
  * unnoticed until a golden from real cv2 (oracle/gen_golden.py on a machine that has it) pins both. */
 int rpe_shift_bilinear(const void *src, int src_is_u8, int c, int h, int w, float tx, float ty, void *dst, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Surfel map of frame-to-model tracking (core/fusion/surfel_map.py; configuration/infer_scared.yaml: frame2frame False).
+ *
+ * Layout: SoA f32 with capacity cap -- opts (3,cap) world points in mm, rgb (3,cap), conf (cap), t_created (cap) -- so that
+ * [:, :n] views are the reference's (3,N) tensors.  The count n lives in a device int32 (*count); *overflow is a device int32 that a
+ * kernel ORs with 1 when it would have written past cap (it then writes nothing past cap, stores n = cap and returns normally) and
+ * with 2 when n exceeded the caller's n_bound (items past the bound were not visited).  No entry point synchronises the host: every
+ * kernel reads n from *count and is launched over n_bound, a host-side upper bound of n (the caller tracks n + h*w per fuse).
+ * Compactions (init, fuse, prune) preserve order and are deterministic (block counts -> scan -> scatter): the map's order is the
+ * reference's (boolean-mask gathers, torch.cat appends).  They read a source map and write a DIFFERENT destination map (the caller
+ * ping-pongs two buffers); fuse also updates the source's matched surfels in place before compacting.
+ * Frame inputs: depth (h,w) f32 in mm, img (3,h,w) f32, mask (h,w) u8 (nonzero = valid), confidence (h,w) f32.  kmat, kinv: device
+ * f32 3x3 row-major (kinv = torch.linalg.inv(kmat), computed once on the host as the reference does per call); poses: device f32
+ * 7-vectors [t, q] (lietorch layout).  Arithmetic follows the reference's operation order without FMA contraction: reproject
+ * p = depth * (Kinv . (x+.5, y+.5, 1)), transform R p + t, project (K p).xy / clamp((K p).z, 1e-12) (NaN stays NaN).
+ * Workspace: rpe_surfel_workspace_bytes(n_bound, h, w) bytes, any alignment of 256. */
+typedef struct rpe_surfel_map {
+    float *opts;          /* (3, cap) */
+    float *rgb;           /* (3, cap) */
+    float *conf;          /* (cap) */
+    float *t_created;     /* (cap), f32 as in the reference */
+    int64_t cap;
+    int32_t *count;       /* device: n */
+    int32_t *overflow;    /* device: 0, or the OR of 1 (cap reached) and 2 (n > n_bound) */
+} rpe_surfel_map;
+
+size_t rpe_surfel_workspace_bytes(int64_t n_bound, int h, int w);
+/* SurfelMap(frame=, kmat=, pmat=) (surfel_map.py:45-70): every pixel with mask != 0, in raster order, at pmat . reproject(depth);
+ * rgb from img, conf = confidence / conf_thr, t_created = 0.  Writes *dst->count. */
+int rpe_surfel_init(const float *depth, const float *img, const uint8_t *mask, const float *confidence, int h, int w, const float *kinv,
+                    const float *pmat, float conf_thr, const rpe_surfel_map *dst, void *workspace, void *stream);
+/* SurfelMap.fuse(frame, pose) with upscale 1 (surfel_map.py:73-158; other upscales: RPE_E_UNSUPPORTED), then the prune:
+ *  1. every surfel i < n of src: (u,v) = project(K, pose^-1 . opts_i); associated when 0 <= u < w-1 and 0 <= v < h-1, pixel
+ *     m = round(v - .5) * w + round(u - .5) (half to even, flattened in f32), |z(pose . reproject(depth)[m]) - z_i| < d_thresh and
+ *     mask[m]; then conf_i = clamp(conf_i + 1/conf_thr, 0, 1) and, with average_pts, opts_i / rgb_i = (conf_i old * old + 1/conf_thr *
+ *     frame) / (conf_i old + 1/conf_thr) -- in place in src;
+ *  2. dst = [surfels of src | every pixel with mask != 0 that no surfel associated with, raster order: world point, rgb, conf 1/conf_thr,
+ *     t_created = tick], keeping only conf >= 1 | (tick + 1 - t_created) < t_max (the prune after tick += 1).
+ * The caller's tick becomes tick + 1.  n_bound >= n of src; dst needs cap >= n + h*w to be safe. */
+int rpe_surfel_fuse(const rpe_surfel_map *src, int64_t n_bound, const float *depth, const float *img, const uint8_t *mask, int h, int w,
+                    const float *kmat, const float *kinv, const float *pose, float d_thresh, int average_pts, int upscale, float conf_thr,
+                    int tick, int t_max, const rpe_surfel_map *dst, void *workspace, void *stream);
+/* remove_surfels_by_confidence_and_time (surfel_map.py:150-158) alone: dst = the surfels of src with conf >= 1 | (tick - t_created) < t_max */
+int rpe_surfel_prune(const rpe_surfel_map *src, int64_t n_bound, int tick, int t_max, const rpe_surfel_map *dst, void *workspace, void *stream);
+/* SurfelMap.render (surfel_map.py:230-264) under extrinsics T: every surfel projects to (u,v) = project(K, T . opts_i); in the image
+ * when 0 <= u < w and 0 <= v < h; pixel (int)v * w + (int)u (.long() truncation).  Per pixel the WINNER is the surfel with the largest
+ * conf in torch.sort's order (-inf < ... < -0 == +0 < ... < +inf < NaN), ties going to the LARGEST surfel index -- what a stable
+ * argsort of conf followed by last-write-wins scattering gives (the reference's own CPU argsort is not stable and its CUDA index_put
+ * has no defined winner, so this rule is the deterministic one).  Implemented as one 64-bit atomicMax per in-image surfel on
+ * (order-preserving conf bits << 32 | index), then a resolve pass.  Outputs (empty pixels 0): img (3,h,w) = winner's rgb, depth (h,w)
+ * = winner's z -- of T . opts when depth_transformed (transform_cpy(T).render(), the tracker's pair in one launch: the identity act of
+ * the copy's render is exact), of opts itself otherwise (render(extrinsics=T) writes the untransformed z) --, confidence (h,w) = winner's
+ * conf, mask (h,w) u8 = confidence != 0.  Then SparseImgInterpolator(5, 2, 0) on depth and each colour plane
+ * (core/interpol/sparse_img_interpolation.py:19-31): NaN pixels become the 5x5 Gaussian (sigma 2, centre weight 0, normalised) of the
+ * reflect-padded plane with NaNs read as 0; other pixels are untouched.  Needs h, w >= 3. */
+int rpe_surfel_render(const rpe_surfel_map *m, int64_t n_bound, const float *kmat, const float *T, int depth_transformed, int h, int w,
+                      float *img, float *depth, float *confidence, uint8_t *mask, void *workspace, void *stream);
+/* SurfelMap.transform / transform_cpy (surfel_map.py:205-219): opts_out[:, i] = T . opts_in[:, i] for i < *count (in place allowed);
+ * in_cap / out_cap are the row strides of the two (3, cap) arrays. */
+int rpe_surfel_transform(const float *opts_in, int64_t in_cap, float *opts_out, int64_t out_cap, const int32_t *count, int64_t n_bound,
+                         const float *T, void *stream);
 
 #ifdef __cplusplus
 }

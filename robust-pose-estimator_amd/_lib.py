@@ -87,7 +87,7 @@ OP_EVENT_RECORD, OP_STREAM_WAIT = 32, 33
 OP_OF_ENTRY = {'rpe_conv_fused': OP_CONV_FUSED, 'rpe_conv_wino': OP_CONV_WINO, 'rpe_conv_wino1d': OP_CONV_WINO1D, 'rpe_conv1x1': OP_CONV1X1,
                'rpe_conv_wino_x3': OP_CONV_WINO_X3, 'rpe_conv_wino1d_x3': OP_CONV_WINO1D_X3, 'rpe_conv1x1_x3': OP_CONV1X1_X3}
 
-ABI_MINOR = 2              # RPE_ABI_MINOR: the newest additions this binding calls (rpe_run_ops)
+ABI_MINOR = 3              # RPE_ABI_MINOR: the newest additions this binding calls (rpe_surfel_*)
 ABI_VERSION = 5            # RPE_ABI_VERSION of include/rpe.h these struct mirrors were written against
 
 
@@ -95,6 +95,13 @@ class SolveOpts(_c.Structure):
     """struct rpe_solve_opts (include/rpe.h)."""
     _fields_ = [('struct_size', _i), ('history_size', _i), ('tolerance_grad', _d), ('tolerance_change', _d), ('partition_rows', _i), ('reserved', _i)]
 
+
+class SurfelMapDesc(_c.Structure):
+    """struct rpe_surfel_map (include/rpe.h)."""
+    _fields_ = [('opts', _vp), ('rgb', _vp), ('conf', _vp), ('t_created', _vp), ('cap', _i64), ('count', _vp), ('overflow', _vp)]
+
+
+_SMP = _c.POINTER(SurfelMapDesc)
 
 # name -> (restype, argtypes); mirrors include/rpe.h one to one
 SIGNATURES = {
@@ -180,6 +187,12 @@ SIGNATURES = {
     'rpe_resize_crop_mask': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     'rpe_remap_nearest': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
     'rpe_shift_bilinear': (_i, [_vp, _i, _i, _i, _i, _c.c_float, _c.c_float, _vp, _vp]),
+    'rpe_surfel_workspace_bytes': (_sz, [_i64, _i, _i]),
+    'rpe_surfel_init': (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _fl, _SMP, _vp, _vp]),
+    'rpe_surfel_fuse': (_i, [_SMP, _i64, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _fl, _i, _i, _fl, _i, _i, _SMP, _vp, _vp]),
+    'rpe_surfel_prune': (_i, [_SMP, _i64, _i, _i, _SMP, _vp, _vp]),
+    'rpe_surfel_render': (_i, [_SMP, _i64, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'rpe_surfel_transform': (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
 }
 
 _lib = None

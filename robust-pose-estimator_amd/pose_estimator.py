@@ -4,7 +4,8 @@ called once per stereo frame, as scripts/infer_trajectory.py:50-51,71-77 of the 
 Follows core/pose/pose_estimator.py:26-48 (checkpoint + config overrides, 1/depth_clipping scale),
 :50-96 (forward: failure gate ``isnan | |log| > 0.1`` -> identity, de-normalise, chain
 ``last_pose <- last_pose * rel^-1``) and :98-125 (get_pose_f2f), and core/utils/frame_class.py:5-50 (Frame).
-Frame-to-model tracking (``frame2frame: False``, SurfelMap) is out of scope.
+Frame-to-model tracking (``frame2frame: False``, :56-96,127-150 with core/fusion/surfel_map.py) is ``SurfelPoseEstimator`` below;
+``from_config`` picks the class from the config as scripts/infer_trajectory.py:50-51 would.
 """
 import time
 import warnings
@@ -49,12 +50,14 @@ class Frame:
 
 
 class PoseEstimator(torch.nn.Module):
+    _f2m = False
+
     def __init__(self, config, intrinsics, baseline, checkpoint, img_shape, init_pose=None):
         """config: the ``slam`` section of the inference YAML (configuration/infer_f2f.yaml:1-11);
         img_shape = (W, H) as in the reference; checkpoint: path, ``{'state_dict','config'}`` dict or a PoseNet."""
         super().__init__()
-        if not config.get('frame2frame', True):
-            raise NotImplementedError('frame-to-model tracking (SurfelMap) is out of scope')
+        if not config.get('frame2frame', True) and not self._f2m:
+            raise NotImplementedError('PoseEstimator tracks frame to frame; frame2frame: False is SurfelPoseEstimator (or from_config)')
         if isinstance(checkpoint, PoseNet):
             model = checkpoint
         else:
@@ -220,3 +223,74 @@ class PoseEstimator(torch.nn.Module):
         self.frame.depth = depth2 / self.scale
         self.frame.flow = stereo_flow
         return rel, self.last_frame, flow, weights
+
+
+class SurfelPoseEstimator(PoseEstimator):
+    """Frame-to-model tracker (``frame2frame: False``, configuration/infer_scared.yaml): every frame is tracked against a render of a
+    fused surfel map (surfel_map.SurfelMap on the rpe_surfel_* kernels) at the last pose, following core/pose/pose_estimator.py:
+    first frame -> stereo depth, ``mask &= valid``, map at last_pose (:56-65); every frame -> render at last_pose^-1 (transform_cpy +
+    render in one launch), PoseNet.infer against it (:127-150), the gate and chain of PoseEstimator (one host synchronisation), and on
+    success ``fuse(frame, last_pose)`` (:94-95).  Reads ``dist_thr`` and ``average_pts`` from the config.  Frames depend on the map the
+    previous frame fused, so there is no chunked or pipelined form."""
+    _f2m = True
+
+    def __init__(self, config, intrinsics, baseline, checkpoint, img_shape, init_pose=None):
+        if config.get('frame2frame', True):
+            raise ValueError('SurfelPoseEstimator is frame-to-model tracking: it needs frame2frame: False (PoseEstimator tracks frame to frame)')
+        super().__init__(config, intrinsics, baseline, checkpoint, img_shape, init_pose)
+        self.scene = None
+
+    def reset(self):
+        super().reset()
+        self.scene = None
+        return self
+
+    def submit(self, *a, **k):
+        raise RuntimeError('SurfelPoseEstimator: frame t+1 is tracked against the map frame t fused, so frames cannot be pipelined')
+
+    def forward_chunk(self, *a, **k):
+        raise RuntimeError('SurfelPoseEstimator: frame t+1 is tracked against the map frame t fused, so frames cannot be chunked')
+
+    @torch.no_grad()
+    def forward(self, limg, rimg, mask):
+        """limg, rimg: (1,3,h,w) 0..255; mask: (1,1,h,w) True = valid.  Returns (absolute pose SE3, the SurfelMap, flow, weights)."""
+        from .surfel_map import SurfelMap
+        self.last_pose = self.last_pose.to(limg.device)
+        self.last_frame = self.frame
+        self.frame = Frame(limg, rimg, mask=mask)
+        if self.scene is None:                                             # :56-65
+            depth, stereo_flow, valid = self.model.flow2depth(self.frame.img, self.frame.rimg, self.baseline * self.scale)
+            self.frame.depth = depth / self.scale
+            self.frame.mask &= valid
+            self.frame.flow = stereo_flow
+            self.scene = SurfelMap(frame=self.frame, kmat=self.intrinsics.squeeze(0), upscale=1, d_thresh=self.config['dist_thr'],
+                                   pmat=self.last_pose, average_pts=self.config['average_pts'])
+        rel_pose, ret_frame, flow, weights = self.get_pose_f2m()
+        rel, pose, ok = ops.pose_gate_chain(rel_pose.data.reshape(1, 7), self.last_pose.data, self._inv_scale, 1.0e-1)   # :81-91
+        self.t_enqueued = time.perf_counter()
+        self.success = bool(ok[0])
+        if not self.success:
+            warnings.warn('pose estimation not converged, skip.', RuntimeWarning)
+        self.last_rel_pose = SE3(rel)
+        self.last_frame = ret_frame
+        self.last_pose = SE3(pose)
+        if self.success and flow is not None:                              # :94-95
+            self.scene.fuse(self.frame, self.last_pose)
+        return self.last_pose, self.scene, flow, weights
+
+    def get_pose_f2m(self):
+        """:127-150: the map rendered at the last camera pose, PoseNet.infer of render -> frame (mask2 &= valid in place)."""
+        model_frame = self.scene.render_transformed(self.intrinsics.squeeze(0), self.last_pose.inv())[0]
+        rel, depth1, depth2, weights, flow, stereo_flow = self.model.infer(
+            model_frame.img, self.frame.img, self.intrinsics, self.baseline * self.scale, depth1=model_frame.depth * self.scale,
+            image2r=self.frame.rimg, mask1=model_frame.mask, mask2=self.frame.mask, stereo_flow1=model_frame.flow, ret_details=True)
+        self.frame.depth = depth2 / self.scale
+        self.frame.flow = stereo_flow
+        model_frame.confidence = weights[0]
+        return SE3(rel.data.reshape(1, 7)), model_frame, flow, weights
+
+
+def from_config(config, intrinsics, baseline, checkpoint, img_shape, init_pose=None):
+    """The tracker the config asks for (scripts/infer_trajectory.py:50-51): PoseEstimator for frame2frame True, SurfelPoseEstimator for False."""
+    cls = PoseEstimator if config.get('frame2frame', True) else SurfelPoseEstimator
+    return cls(config, intrinsics, baseline, checkpoint, img_shape, init_pose)

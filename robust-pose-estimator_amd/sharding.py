@@ -143,6 +143,9 @@ class SequenceTracker:
             scale = est_scale
         elif abs(scale - est_scale) > 1e-6 * est_scale:
             raise ValueError(f'SequenceTracker.track: scale {scale} != the estimator\'s depth_clipping {est_scale}')
+        if world > 1 and not self.estimator.config.get('frame2frame', True):
+            raise ValueError('SequenceTracker.track: frame-to-model tracking cannot be sharded -- every frame is tracked against the map '
+                             'all earlier frames fused')
         chain = self._chain
         if chain is None:
             from . import ops

@@ -121,3 +121,26 @@ def init_synthetic_weights(model, seed=1234, flow_bias=-0.35):
         raft = model.flow if hasattr(model, 'flow') else model
         raft.update_block.flow_head.conv2.bias.copy_(torch.tensor([flow_bias, 0.0]))
     return model
+
+
+def surfel_scene(h=32, w=48, steps=20, seed=3):
+    """Seeded frames for the surfel map (tests/golden/surfel_map.npz, tools/bench_f2m.py): K (3,3) and steps+1 tuples (img (1,3,h,w)
+    0..255, depth (1,1,h,w) in mm around 60, mask (1,1,h,w) bool ~88 % valid, confidence (1,1,h,w) in [0.5, 1.5)).  A smooth surface
+    plus 0.4 mm noise per frame; torch.Generator draws on the CPU, so every machine regenerates the same frames."""
+    g = torch.Generator().manual_seed(seed)
+    K = torch.tensor([[41.3 * w / 48, 0.0, 23.7 * w / 48], [0.0, 40.9 * w / 48, 16.2 * h / 32], [0.0, 0.0, 1.0]])
+    yy, xx = torch.meshgrid(torch.arange(h, dtype=torch.float32), torch.arange(w, dtype=torch.float32), indexing='ij')
+    base = 60.0 + 6.0 * torch.sin(xx * (48 / w) / 9.0) + 4.0 * torch.cos(yy * (32 / h) / 7.0)
+    frames = []
+    for _ in range(steps + 1):
+        depth = (base + 0.4 * torch.randn(h, w, generator=g))[None, None]
+        img = torch.rand(1, 3, h, w, generator=g) * 255.0
+        mask = torch.rand(1, 1, h, w, generator=g) > 0.12
+        conf = 0.5 + torch.rand(1, 1, h, w, generator=g)
+        frames.append((img, depth, mask, conf))
+    return K, frames
+
+
+def surfel_pose(k, scale=1.0):
+    """xi (1,6) of step k of the surfel scene's camera path (translation mm first, then rotation): SE3.exp of it is the step's pose."""
+    return torch.tensor([[0.05 * k, -0.03 * k, 0.02 * k, 0.002 * k, -0.001 * k, 0.0015 * k]]) * scale
