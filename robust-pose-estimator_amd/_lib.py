@@ -84,8 +84,17 @@ OP_CONV_FUSED, OP_CONV_WINO, OP_CONV_WINO1D, OP_CONV1X1, OP_CONV_WINO_X3, OP_CON
 OP_CORR_LOOKUP, OP_STEM_CONV, OP_FLOW_UPDATE, OP_COPY_PLANES, OP_INSTNORM_FINALIZE, OP_INSTNORM_APPLY, OP_UPSAMPLE_CONVEX, OP_CORR_BUILD = 8, 9, 10, 11, 12, 13, 14, 15
 OP_LOOKUP_CONV1X1 = 16
 OP_EVENT_RECORD, OP_STREAM_WAIT = 32, 33
-OP_OF_ENTRY = {'rpe_conv_fused': OP_CONV_FUSED, 'rpe_conv_wino': OP_CONV_WINO, 'rpe_conv_wino1d': OP_CONV_WINO1D, 'rpe_conv1x1': OP_CONV1X1,
-               'rpe_conv_wino_x3': OP_CONV_WINO_X3, 'rpe_conv_wino1d_x3': OP_CONV_WINO1D_X3, 'rpe_conv1x1_x3': OP_CONV1X1_X3}
+# kind -> (entry point, argument struct) of every op a launch list carries (csrc/oplist.hip's run_one).  An entry point with an argument
+# struct takes its fields in order, then the stream; the rpe_conv_desc kinds take the descriptor by pointer, then the stream.
+LIST_OPS = {OP_CONV_FUSED: ('rpe_conv_fused', ConvDesc), OP_CONV_WINO: ('rpe_conv_wino', ConvDesc), OP_CONV_WINO1D: ('rpe_conv_wino1d', ConvDesc),
+            OP_CONV1X1: ('rpe_conv1x1', ConvDesc), OP_CONV_WINO_X3: ('rpe_conv_wino_x3', ConvDesc),
+            OP_CONV_WINO1D_X3: ('rpe_conv_wino1d_x3', ConvDesc), OP_CONV1X1_X3: ('rpe_conv1x1_x3', ConvDesc),
+            OP_CORR_LOOKUP: ('rpe_corr_lookup', CorrLookupArgs), OP_STEM_CONV: ('rpe_stem_conv', StemConvArgs),
+            OP_FLOW_UPDATE: ('rpe_conv3x3_to2_flow', FlowUpdateArgs), OP_COPY_PLANES: ('rpe_copy_planes', CopyPlanesArgs),
+            OP_INSTNORM_FINALIZE: ('rpe_instnorm_finalize', InstnormFinalizeArgs), OP_INSTNORM_APPLY: ('rpe_instnorm_apply_ex', InstnormApplyArgs),
+            OP_UPSAMPLE_CONVEX: ('rpe_upsample_convex', UpsampleConvexArgs), OP_CORR_BUILD: ('rpe_corr_build_ex', CorrBuildArgs),
+            OP_LOOKUP_CONV1X1: ('rpe_corr_lookup_conv1x1', LookupConv1x1Args)}
+KIND_OF_ENTRY = {entry: kind for kind, (entry, _) in LIST_OPS.items()}
 
 ABI_MINOR = 3              # RPE_ABI_MINOR: the newest additions this binding calls (rpe_surfel_*)
 ABI_VERSION = 5            # RPE_ABI_VERSION of include/rpe.h these struct mirrors were written against
@@ -103,7 +112,7 @@ class SurfelMapDesc(_c.Structure):
 
 _SMP = _c.POINTER(SurfelMapDesc)
 
-# name -> (restype, argtypes); mirrors include/rpe.h one to one
+# name -> (restype, argtypes); mirrors include/rpe.h one to one (the entry points of LIST_OPS: below, from their argument structs)
 SIGNATURES = {
     'rpe_version': (_c.c_char_p, []),
     'rpe_abi_version': (_i, []),
@@ -129,11 +138,8 @@ SIGNATURES = {
     'rpe_corr_pyramid_bytes': (_sz, [_i, _i, _i, _i]),
     'rpe_corr_pyramid_bytes_ex': (_sz, [_i, _i, _i, _i, _i]),
     'rpe_corr_build': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    'rpe_corr_build_ex': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    'rpe_corr_lookup': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     'rpe_corr_lookup_conv1x1_packed_floats': (_sz, [_i, _i]),
     'rpe_corr_lookup_conv1x1_pack': (_i, [_vp, _i, _i, _vp, _vp]),
-    'rpe_corr_lookup_conv1x1': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _ll, _vp, _ll, _vp]),
     'rpe_corr_lookup_taps': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'rpe_corr_lookup_rounds': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'rpe_corr_export_level': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
@@ -143,44 +149,31 @@ SIGNATURES = {
     'rpe_instnorm_act': (_i, [_vp, _vp, _i, _i, _i, _c.c_float, _i, _vp, _vp, _vp]),
     'rpe_affine_act': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'rpe_conv3x3_to2': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
-    'rpe_conv3x3_to2_flow': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _ll, _vp, _ll, _vp]),
-    'rpe_copy_planes': (_i, [_vp, _ll, _vp, _ll, _i, _i, _i, _vp]),
-    'rpe_upsample_convex': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     'rpe_conv_packed_floats': (_sz, [_i, _i, _i, _i]),
     'rpe_conv_pack': (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     'rpe_conv1x1_packed_floats': (_sz, [_i, _i]),
     'rpe_conv1x1_pack': (_i, [_vp, _i, _i, _vp, _vp]),
-    'rpe_conv_fused': (_i, [_c.POINTER(ConvDesc), _vp]),
     'rpe_conv_direct': (_i, [_vp, _ll, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _ll, _vp]),
     'rpe_conv_wino_packed_floats': (_sz, [_i, _i]),
     'rpe_conv_wino_stats_tiles': (_i, [_i, _i]),
     'rpe_conv_wino_pack': (_i, [_vp, _i, _i, _vp, _vp]),
-    'rpe_conv_wino': (_i, [_c.POINTER(ConvDesc), _vp]),
     'rpe_conv_wino_x3_packed_bytes': (_sz, [_i, _i]),
     'rpe_conv_wino_x3_pack': (_i, [_vp, _i, _i, _vp, _vp]),
-    'rpe_conv_wino_x3': (_i, [_c.POINTER(ConvDesc), _vp]),
-    'rpe_conv1x1': (_i, [_c.POINTER(ConvDesc), _vp]),
     'rpe_conv1x1_x3_packed_bytes': (_sz, [_i, _i]),
     'rpe_conv1x1_x3_pack': (_i, [_vp, _i, _i, _vp, _vp]),
-    'rpe_conv1x1_x3': (_i, [_c.POINTER(ConvDesc), _vp]),
     'rpe_conv_wino1d_packed_floats': (_sz, [_i, _i]),
     'rpe_conv_wino1d_pack': (_i, [_vp, _i, _i, _vp, _vp]),
-    'rpe_conv_wino1d': (_i, [_c.POINTER(ConvDesc), _vp]),
     'rpe_conv_wino1d_x3_packed_bytes': (_sz, [_i, _i]),
     'rpe_conv_wino1d_x3_pack': (_i, [_vp, _i, _i, _vp, _vp]),
-    'rpe_conv_wino1d_x3': (_i, [_c.POINTER(ConvDesc), _vp]),
     'rpe_conv_stats_tiles': (_i, [_i, _i, _i, _i]),
     'rpe_conv_stats_tiles_batch': (_i, [_i, _i, _i, _i, _i]),
     'rpe_instnorm_apply': (_i, [_vp, _vp, _i, _i, _i, _i, _c.c_float, _i, _vp, _vp, _vp]),
-    'rpe_instnorm_apply_ex': (_i, [_vp, _vp, _i, _i, _i, _i, _c.c_float, _i, _vp, _vp, _vp, _vp]),
-    'rpe_instnorm_finalize': (_i, [_vp, _i, _i, _i, _i, _c.c_float, _vp, _vp]),
     'rpe_unet_params_floats': (_sz, [_i]),
     'rpe_unet_workspace_bytes': (_sz, [_i, _i, _i]),
     'rpe_unet_heads': (_i, [_vp, _vp, _vp, _vp, _ll, _ll, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'rpe_stem_tiles': (_i, [_i, _i, _i]),
     'rpe_stem_packed_floats': (_sz, [_i, _i]),
     'rpe_stem_pack': (_i, [_vp, _i, _i, _vp, _vp]),
-    'rpe_stem_conv': (_i, [_vp, _i, _i, _i, _i, _i, _c.c_float, _c.c_float, _c.c_float, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     'rpe_run_ops': (_i, [_c.POINTER(Op), _i, _c.POINTER(_vp), _i, _c.POINTER(_i)]),
     'rpe_mask_specularities': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     'rpe_resize_crop': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
@@ -194,6 +187,7 @@ SIGNATURES = {
     'rpe_surfel_render': (_i, [_SMP, _i64, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     'rpe_surfel_transform': (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
 }
+SIGNATURES.update({entry: (_i, ([_c.POINTER(ConvDesc)] if st is ConvDesc else [t for _, t in st._fields_]) + [_vp]) for entry, st in LIST_OPS.values()})
 
 _lib = None
 
@@ -264,6 +258,14 @@ class CountingLib:
                 self.list_ops += a[1]
             return fn(*a)
         return counted
+
+
+def real_lib():
+    """The loaded library itself, also while CountingLibs stand in for it: what a prepared launcher calls, whenever it runs."""
+    L = lib()
+    while isinstance(L, CountingLib):
+        L = L._real
+    return L
 
 
 _ERR = {-1: 'RPE_E_BADARG', -2: 'RPE_E_LAUNCH', -3: 'RPE_E_UNSUPPORTED'}

@@ -2,6 +2,9 @@
 caching allocator, and launch on torch's current HIP stream.  PyTorch is plumbing here (device memory and
 streams); every operation below runs in librpe_hip.so.  Tensors must live on a ROCm device -- there is no
 CPU path."""
+import ctypes
+import operator
+
 import torch
 
 from . import _lib
@@ -18,7 +21,6 @@ class OpList:
     stream tuple given to run().  Event cells: cell(i) is a void* slot holding a raw hipEvent_t handle (0 = the op is skipped)."""
 
     def __init__(self, n_cells=0):
-        import ctypes
         self._items, self._keep, self._arr = [], [], None
         self.cells = (ctypes.c_void_p * max(1, n_cells))()
         self._streams = (ctypes.c_void_p * 4)()
@@ -29,14 +31,12 @@ class OpList:
 
     def add(self, launcher, stream=0):
         kind, args = launcher.op
-        import ctypes
         self._items.append((kind, stream, ctypes.addressof(args)))
         self._keep.append(launcher)                       # (the launcher keeps the struct and every tensor it points to alive)
         self._arr = None
         return self
 
     def _cell_op(self, kind, cell, stream):
-        import ctypes
         self._items.append((kind, stream, ctypes.addressof(self.cells) + ctypes.sizeof(ctypes.c_void_p) * cell))
         self._arr = None
         return self
@@ -53,7 +53,6 @@ class OpList:
 
     def run(self, streams, start=0, stop=None):
         """Enqueue ops [start, stop) on ``streams`` (raw hipStream_t handles as ints, index = the ops' ``stream``)."""
-        import ctypes
         if self._arr is None:
             self._arr = (_lib.Op * max(1, len(self._items)))(*[_lib.Op(k, s, a) for k, s, a in self._items])
         stop = len(self._items) if stop is None else stop
@@ -105,7 +104,6 @@ class Recorder(OpList):
         return False
 
     def log(self, kind, args, keep):
-        import ctypes
         self._items.append((kind, 0, ctypes.addressof(args)))
         self._keep.append((args, keep))
         self._structs.append(args)
@@ -113,7 +111,6 @@ class Recorder(OpList):
 
     def bind(self, name, t):
         """Every pointer field of the logged argument blocks that points into ``t``'s memory -> (struct, field, offset)."""
-        import ctypes
         lo, hi = t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()
         sites = []
         for i, st in enumerate(self._structs):
@@ -123,15 +120,15 @@ class Recorder(OpList):
                     if v is not None and lo <= v < hi:
                         sites.append((st, fname, v - lo))
                         self._claimed.add((i, fname))
-        self._bound[name] = (sites, tuple(t.shape), t.dtype)
+        self._bound[name] = (sites, tuple(t.shape), t.dtype, t.device)
         return len(sites)
 
     def patch(self, tensors):
-        """Rewrite every pointer bound to ``name`` for the tensors given (same shape and dtype as at recording time, contiguous)."""
+        """Rewrite every pointer bound to ``name`` for the tensors given (same shape, dtype and device as at recording time, contiguous)."""
         for name, t in tensors.items():
-            sites, shape, dtype = self._bound[name]
-            if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous():
-                raise _lib.RpeError(f'Recorder.replay: {name} must be a contiguous {dtype} tensor of shape {shape}')
+            sites, shape, dtype, device = self._bound[name]
+            if tuple(t.shape) != shape or t.dtype != dtype or t.device != device or not t.is_contiguous():
+                raise _lib.RpeError(f'Recorder.replay: {name} must be a contiguous {dtype} tensor of shape {shape} on {device}')
             base = t.data_ptr()
             for st, fname, off in sites:
                 setattr(st, fname, base + off)
@@ -144,6 +141,44 @@ class Recorder(OpList):
 def raw_stream(stream=None):
     """The raw hipStream_t handle (int) of a torch stream (default: the current stream of the current device)."""
     return _lib.stream_ptr().value or 0 if stream is None else stream.cuda_stream
+
+
+class _Launcher:
+    """A prepared launch (``prepare=True``): calling it runs the entry point on the current stream with the CURRENT fields of its argument
+    struct, so a struct that Recorder.patch rewrote is seen here as in a launch list.  ``.op`` = (kind, struct) for OpList.add; ``.keep``
+    = what the struct points into.  ``L`` is the library whose entry point it calls."""
+
+    def __init__(self, kind, a, keep, result, L):
+        entry, struct = _lib.LIST_OPS[kind]
+        self.op, self.keep, self._result, self._entry, self._fn = (kind, a), keep, result, entry, getattr(L, entry)
+        self._args = (lambda d, ref=ctypes.byref(a): (ref,)) if struct is _lib.ConvDesc else operator.attrgetter(*(f for f, _ in struct._fields_))
+
+    def __call__(self):
+        kind, a = self.op
+        if _REC is not None:
+            _REC.log(kind, a, self.keep)
+        st = self._fn(*self._args(a), stream_ptr())
+        if st != 0:
+            check(st, self._entry)
+        return self._result
+
+
+def _launch(kind, args, keep, result, prepare=False):
+    """The launch policy of every wrapper a launch list can carry.  ``args``: the entry point's arguments without the stream, in the order
+    of its argument struct (the descriptor itself for the rpe_conv_desc kinds); ``keep``: the objects they point into.  Launches on the
+    current stream and returns ``result``, or (``prepare``) returns a _Launcher on the real library -- never on a CountingLib that stands
+    in while it is built.  While a Recorder is active, every launch is logged with its struct."""
+    entry, struct = _lib.LIST_OPS[kind]
+    desc = struct is _lib.ConvDesc
+    if not prepare and _REC is None:                  # call by call: no struct beyond the descriptor the wrapper built anyway
+        st = getattr(lib(), entry)(*((ctypes.byref(args),) if desc else args), stream_ptr())
+        if st != 0:
+            check(st, entry)
+        return result
+    launch = _Launcher(kind, args if desc else struct(*args), keep, result, _lib.real_lib() if prepare else lib())
+    return launch if prepare else launch()
+
+
 _DT = {torch.float32: 0, torch.float64: 1}
 
 
@@ -288,7 +323,6 @@ def pose_solve(flow, pcl1, pcl2, w1, w2, mask1, mask2, K, loss_weight, iters, mo
     log6 = torch.empty(n, 6, dtype=torch.float32, device=dev)
     info = torch.empty(n, 4, dtype=torch.int32, device=dev)
     ws = _workspace(n, h, w, dev)
-    import ctypes
     o = _lib.SolveOpts(ctypes.sizeof(_lib.SolveOpts), int(history_size), float(tolerance_grad), float(tolerance_change), int(partition_rows),
                        0 if persistent else 1)
     check(lib().rpe_pose_solve_ex(*[ptr(a) for a in args], n, h, w, int(mode), int(iters), ctypes.byref(o), ptr(T), ptr(vec7), ptr(log6),
@@ -380,14 +414,10 @@ class CorrPyramid:
         b, c, h8, w8 = f1.shape
         if (b, h8, w8) != (self.b, self.h8, self.w8) or f2.shape != f1.shape:
             raise _lib.RpeError('corr build: shape mismatch')
-        if self.buf.numel() < lib().rpe_corr_pyramid_bytes_ex(b, h8, w8, self.levels, 2 if fp16_features else 3 if bf16x3 else 0):
+        mode = 2 if fp16_features else 3 if bf16x3 else 0
+        if self.buf.numel() < lib().rpe_corr_pyramid_bytes_ex(b, h8, w8, self.levels, mode):
             raise _lib.RpeError('corr build: this pyramid was not sized for the requested feature mode (CorrPyramid(..., bf16x3=True))')
-        if _REC is not None:
-            _REC.log(_lib.OP_CORR_BUILD, _lib.CorrBuildArgs(f1.data_ptr(), f2.data_ptr(), b, c, h8, w8, self.levels, 2 if fp16_features else 3 if bf16x3 else 0,
-                                                            self.buf.data_ptr()), (f1, f2, self))
-        check(lib().rpe_corr_build_ex(ptr(f1), ptr(f2), b, c, h8, w8, self.levels, 2 if fp16_features else 3 if bf16x3 else 0, ptr(self.buf),
-                                      stream_ptr()), 'rpe_corr_build_ex')
-        return self
+        return _launch(_lib.OP_CORR_BUILD, (ptr(f1), ptr(f2), b, c, h8, w8, self.levels, mode, ptr(self.buf)), (f1, f2, self), self)
 
     def lookup(self, coords, out=None, prepare=False):
         """``prepare=True`` (needs ``out``): a zero-argument launcher on these buffers, with ``.op`` for an OpList."""
@@ -397,22 +427,10 @@ class CorrPyramid:
         ch = self.levels * (2 * self.radius + 1) ** 2
         if out is None:
             out = torch.empty(self.b, ch, self.h8, self.w8, dtype=torch.float32, device=co.device)
-        if prepare:
-            if co is not coords or tuple(_nchw(out, 'out').shape) != (self.b, ch, self.h8, self.w8):
-                raise _lib.RpeError('corr lookup: a prepared launch needs contiguous coords and a (b, levels*(2r+1)^2, h8, w8) out buffer')
-            a = _lib.CorrLookupArgs(self.buf.data_ptr(), co.data_ptr(), self.b, self.h8, self.w8, self.levels, self.radius, out.data_ptr())
-            fn, keep = lib().rpe_corr_lookup, (self, co, out)
-
-            def launch():
-                if _REC is not None:
-                    _REC.log(_lib.OP_CORR_LOOKUP, a, keep)
-                check(fn(a.pyramid, a.coords, a.b, a.h8, a.w8, a.levels, a.radius, a.out, stream_ptr()), 'rpe_corr_lookup')
-                return keep[2]
-            launch.keep, launch.op = keep, (_lib.OP_CORR_LOOKUP, a)
-            return launch
-        check(lib().rpe_corr_lookup(ptr(self.buf), ptr(co), self.b, self.h8, self.w8, self.levels, self.radius, ptr(out),
-                                    stream_ptr()), 'rpe_corr_lookup')
-        return out
+        if prepare and (co is not coords or tuple(_nchw(out, 'out').shape) != (self.b, ch, self.h8, self.w8)):
+            raise _lib.RpeError('corr lookup: a prepared launch needs contiguous coords and a (b, levels*(2r+1)^2, h8, w8) out buffer')
+        return _launch(_lib.OP_CORR_LOOKUP, (ptr(self.buf), ptr(co), self.b, self.h8, self.w8, self.levels, self.radius, ptr(out)), (self, co, out), out,
+                       prepare)
 
     def lookup_conv1x1(self, coords, packed, out, out2=None, relu=True, prepare=False):
         """rpe_corr_lookup_conv1x1: act(convc1(lookup(coords))) in one kernel (``packed`` = PackedLookupConv of convc1's weight), written to the
@@ -429,22 +447,9 @@ class CorrPyramid:
                 continue
             if tuple(t.shape) != (self.b, packed.cout, self.h8, self.w8):
                 raise _lib.RpeError(f'corr lookup_conv1x1: {name} must be a ({self.b},{packed.cout},{self.h8},{self.w8}) channel slice')
-            pp, bs = _chan_slice(t, name)
-            sl += [pp.value, bs]
-        a = _lib.LookupConv1x1Args(self.buf.data_ptr(), co.data_ptr(), self.b, self.h8, self.w8, self.levels, self.radius, packed.packed.data_ptr(),
-                                   packed.bias.data_ptr() if packed.bias is not None else None, int(bool(relu)), sl[0], sl[1], sl[2], sl[3])
-        fn, keep = lib().rpe_corr_lookup_conv1x1, (self, co, packed, out, out2)
-
-        def launch():
-            if _REC is not None:
-                _REC.log(_lib.OP_LOOKUP_CONV1X1, a, keep)
-            check(fn(a.pyramid, a.coords, a.b, a.h8, a.w8, a.levels, a.radius, a.packed, a.bias, a.relu, a.out, a.out_batch_stride, a.out2,
-                     a.out2_batch_stride, stream_ptr()), 'rpe_corr_lookup_conv1x1')
-            return keep[3]
-        launch.keep, launch.op = keep, (_lib.OP_LOOKUP_CONV1X1, a)
-        if prepare:
-            return launch
-        return launch()
+            sl += list(_chan_slice(t, name))
+        return _launch(_lib.OP_LOOKUP_CONV1X1, (ptr(self.buf), ptr(co), self.b, self.h8, self.w8, self.levels, self.radius, ptr(packed.packed),
+                                                ptr(packed.bias), int(bool(relu)), *sl), (self, co, packed, out, out2), out, prepare)
 
     def taps(self, coords):
         co = _dev(coords, torch.float32, 'coords')
@@ -473,18 +478,33 @@ class CorrPyramid:
         return dense
 
 
-class PackedLookupConv:
-    """convc1's (256, 324, 1, 1) weight in rpe_corr_lookup_conv1x1's layout (a lane's fragments of a 16-channel step as one 64-byte piece)."""
+class _Packed:
+    """A convolution's weight (and bias) re-laid once per weight version for the entry point ``entry`` that launches it.  A subclass states
+    what differs: the kernel shapes it takes (``kernels``, or _fits) and the error text, its size query (``size``: floats, or bytes with
+    ``in_bytes`` -- bf16 planes kept in float32 storage for the descriptor) and its pack entry point (``pack``)."""
+    kernels, in_bytes = (), False
 
     def __init__(self, weight, bias=None):
         w = _nchw(weight.detach().contiguous(), 'weight')
         self.cout, self.cin, self.kh, self.kw = w.shape
-        n = lib().rpe_corr_lookup_conv1x1_packed_floats(self.cout, self.cin) if (self.kh, self.kw) == (1, 1) else 0
+        n = getattr(lib(), self.size)(*self._dims()) if self._fits() else 0
         if n == 0:
-            raise _lib.RpeError('PackedLookupConv: needs the (256, 324, 1, 1) weight of BasicMotionEncoder.convc1')
-        self.packed = torch.empty(n, dtype=torch.float32, device=w.device)
-        check(lib().rpe_corr_lookup_conv1x1_pack(ptr(w), self.cout, self.cin, ptr(self.packed), stream_ptr()), 'rpe_corr_lookup_conv1x1_pack')
+            raise _lib.RpeError(f'{type(self).__name__}: {self.error}')
+        self.packed = torch.empty(n // 4 if self.in_bytes else n, dtype=torch.float32, device=w.device)
+        check(getattr(lib(), self.pack)(ptr(w), *self._dims(), ptr(self.packed), stream_ptr()), self.pack)
         self.bias = None if bias is None else _nchw(bias.detach().contiguous(), 'bias')
+
+    def _dims(self):
+        return self.cout, self.cin
+
+    def _fits(self):
+        return (self.kh, self.kw) in self.kernels
+
+
+class PackedLookupConv(_Packed):
+    """convc1's (256, 324, 1, 1) weight in rpe_corr_lookup_conv1x1's layout (a lane's fragments of a 16-channel step as one 64-byte piece)."""
+    kernels, error = ((1, 1),), 'needs the (256, 324, 1, 1) weight of BasicMotionEncoder.convc1'
+    size, pack, entry = 'rpe_corr_lookup_conv1x1_packed_floats', 'rpe_corr_lookup_conv1x1_pack', 'rpe_corr_lookup_conv1x1'
 
     @staticmethod
     def supported(levels, radius, w8):
@@ -590,23 +610,8 @@ def flow_update(x, weight, bias, coords, coords_out, flow_out=None, dst1=None, d
         if tuple(t.shape) != (b, 2, hh, ww):
             raise _lib.RpeError(f'flow_update: {name} must be a ({b},2,{hh},{ww}) channel slice')
         sl += list(_chan_slice(t, name))
-    args = (ptr(x), ptr(weight), ptr(bias), b, c, hh, ww, ptr(coords), ptr(coords_out), ptr(flow_out), sl[0], sl[1], sl[2], sl[3])
-    fn = lib().rpe_conv3x3_to2_flow
-    if prepare:
-        keep = (x, weight, bias, coords, coords_out, flow_out, dst1, dst2)
-        a = _lib.FlowUpdateArgs(*[v.value if hasattr(v, 'value') else v for v in args])
-
-        def launch():
-            if _REC is not None:
-                _REC.log(_lib.OP_FLOW_UPDATE, a, keep)
-            st = fn(*args, stream_ptr())
-            if st != 0:
-                check(st, 'rpe_conv3x3_to2_flow')
-            return keep[4]
-        launch.keep, launch.op = keep, (_lib.OP_FLOW_UPDATE, a)
-        return launch
-    check(fn(*args, stream_ptr()), 'rpe_conv3x3_to2_flow')
-    return coords_out
+    return _launch(_lib.OP_FLOW_UPDATE, (ptr(x), ptr(weight), ptr(bias), b, c, hh, ww, ptr(coords), ptr(coords_out), ptr(flow_out), *sl),
+                   (x, weight, bias, coords, coords_out, flow_out, dst1, dst2), coords_out, prepare)
 
 
 def copy_planes(src, dst):
@@ -616,10 +621,7 @@ def copy_planes(src, dst):
     b, c, hh, ww = src.shape
     if tuple(dst.shape) != (b, c, hh, ww):
         raise _lib.RpeError('copy_planes: shape mismatch')
-    if _REC is not None:
-        _REC.log(_lib.OP_COPY_PLANES, _lib.CopyPlanesArgs(sp.value, sbs, dp.value, dbs, b, c, hh * ww), (src, dst))
-    check(lib().rpe_copy_planes(sp, sbs, dp, dbs, b, c, hh * ww, stream_ptr()), 'rpe_copy_planes')
-    return dst
+    return _launch(_lib.OP_COPY_PLANES, (sp, sbs, dp, dbs, b, c, hh * ww), (src, dst), dst)
 
 
 def upsample_convex(flow, mask):
@@ -628,10 +630,7 @@ def upsample_convex(flow, mask):
     if tuple(mk.shape) != (b, 576, h8, w8):
         raise _lib.RpeError('upsample_convex: mask must be (b,576,h/8,w/8)')
     out = torch.empty(b, 2, 8 * h8, 8 * w8, dtype=torch.float32, device=fl.device)
-    if _REC is not None:
-        _REC.log(_lib.OP_UPSAMPLE_CONVEX, _lib.UpsampleConvexArgs(fl.data_ptr(), mk.data_ptr(), b, h8, w8, out.data_ptr()), (fl, mk, out))
-    check(lib().rpe_upsample_convex(ptr(fl), ptr(mk), b, h8, w8, ptr(out), stream_ptr()), 'rpe_upsample_convex')
-    return out
+    return _launch(_lib.OP_UPSAMPLE_CONVEX, (ptr(fl), ptr(mk), b, h8, w8, ptr(out)), (fl, mk, out), out)
 
 
 # ------------------------------------------------------------------------- fused update-block convolutions
@@ -650,16 +649,16 @@ def _chan_slice(t, name):
     return ptr(t), t.stride(0)
 
 
-class PackedConv:
+class PackedConv(_Packed):
     """Weights of one stride-1 'same' convolution re-laid for rpe_conv_fused (done once per weight version)."""
+    error = 'needs a non-empty (cout, cin, kh, kw) weight'
+    size, pack, entry = 'rpe_conv_packed_floats', 'rpe_conv_pack', 'rpe_conv_fused'
 
-    def __init__(self, weight, bias=None):
-        w = _nchw(weight.detach().contiguous(), 'weight')
-        self.cout, self.cin, self.kh, self.kw = w.shape
-        n = lib().rpe_conv_packed_floats(self.cout, self.cin, self.kh, self.kw)
-        self.packed = torch.empty(n, dtype=torch.float32, device=w.device)
-        check(lib().rpe_conv_pack(ptr(w), self.cout, self.cin, self.kh, self.kw, ptr(self.packed), stream_ptr()), 'rpe_conv_pack')
-        self.bias = None if bias is None else _nchw(bias.detach().contiguous(), 'bias')
+    def _dims(self):
+        return self.cout, self.cin, self.kh, self.kw
+
+    def _fits(self):
+        return True
 
     @staticmethod
     def supported(weight, width):
@@ -667,43 +666,28 @@ class PackedConv:
         return kh % 2 == 1 and kw in (1, 3, 5) and width % 4 == 0
 
 
-class PackedConv1x1:
+class PackedConv1x1(_Packed):
     """Weights of a 1x1 stride-1 convolution in rpe_conv1x1's layout ([co tile][16-channel step][k][128 co]); same attributes as
     PackedConv, so conv_fused(..., entry='rpe_conv1x1') builds the descriptor."""
-
-    def __init__(self, weight, bias=None):
-        w = _nchw(weight.detach().contiguous(), 'weight')
-        self.cout, self.cin, self.kh, self.kw = w.shape
-        if (self.kh, self.kw) != (1, 1):
-            raise _lib.RpeError('PackedConv1x1: weight must be (cout, cin, 1, 1)')
-        self.packed = torch.empty(lib().rpe_conv1x1_packed_floats(self.cout, self.cin), dtype=torch.float32, device=w.device)
-        check(lib().rpe_conv1x1_pack(ptr(w), self.cout, self.cin, ptr(self.packed), stream_ptr()), 'rpe_conv1x1_pack')
-        self.bias = None if bias is None else _nchw(bias.detach().contiguous(), 'bias')
+    kernels, error = ((1, 1),), 'weight must be (cout, cin, 1, 1)'
+    size, pack, entry = 'rpe_conv1x1_packed_floats', 'rpe_conv1x1_pack', 'rpe_conv1x1'
 
     @staticmethod
     def supported(h, w):
         return (h * w) % 4 == 0 and h * w >= 4
 
 
-class PackedConv1x1X3:
+class PackedConv1x1X3(_Packed):
     """Weights of a 1x1 stride-1 convolution split three ways into bf16 for rpe_conv1x1_x3 (the labelled bf16x3 variant of rpe_conv1x1;
     conv1x1 dispatches on the packing).  LINEAR / RELU only."""
-    x3 = True
-
-    def __init__(self, weight, bias=None):
-        w = _nchw(weight.detach().contiguous(), 'weight')
-        self.cout, self.cin, self.kh, self.kw = w.shape
-        if (self.kh, self.kw) != (1, 1):
-            raise _lib.RpeError('PackedConv1x1X3: weight must be (cout, cin, 1, 1)')
-        self.packed = torch.empty(lib().rpe_conv1x1_x3_packed_bytes(self.cout, self.cin) // 4, dtype=torch.float32, device=w.device)
-        check(lib().rpe_conv1x1_x3_pack(ptr(w), self.cout, self.cin, ptr(self.packed), stream_ptr()), 'rpe_conv1x1_x3_pack')
-        self.bias = None if bias is None else _nchw(bias.detach().contiguous(), 'bias')
+    kernels, error, in_bytes = ((1, 1),), 'weight must be (cout, cin, 1, 1)', True
+    size, pack, entry = 'rpe_conv1x1_x3_packed_bytes', 'rpe_conv1x1_x3_pack', 'rpe_conv1x1_x3'
 
 
 def conv1x1(x, pc, mode, out, out2=None, prepare=False):
     """rpe_conv1x1: out = act(W x + bias) for a PackedConv1x1 (LINEAR / RELU / TANH), channel-slice destinations like conv_fused
     (a PackedConv1x1X3 runs rpe_conv1x1_x3)."""
-    return conv_fused(x, pc, mode, out, out2=out2, prepare=prepare, entry='rpe_conv1x1_x3' if getattr(pc, 'x3', False) else 'rpe_conv1x1')
+    return conv_fused(x, pc, mode, out, out2=out2, prepare=prepare, entry=pc.entry)
 
 
 class Conv1x1:
@@ -715,25 +699,17 @@ class Conv1x1:
         self._w = _nchw(weight.detach().contiguous(), 'weight')
         self._b = None if bias is None else _nchw(bias.detach().contiguous(), 'bias')
         self.cout, self.cin = self._w.shape[0], self._w.shape[1]
-        self._fused = self._gemm = self._gemm_x3 = None
+        self._packings = {}
 
-    @property
-    def fused(self):
-        if self._fused is None:
-            self._fused = PackedConv(self._w, self._b)
-        return self._fused
+    def _packing(self, cls):
+        p = self._packings.get(cls)
+        if p is None:
+            p = self._packings[cls] = cls(self._w, self._b)
+        return p
 
-    @property
-    def gemm(self):
-        if self._gemm is None:
-            self._gemm = PackedConv1x1(self._w, self._b)
-        return self._gemm
-
-    @property
-    def gemm_x3(self):
-        if self._gemm_x3 is None:
-            self._gemm_x3 = PackedConv1x1X3(self._w, self._b)
-        return self._gemm_x3
+    fused = property(lambda self: self._packing(PackedConv))
+    gemm = property(lambda self: self._packing(PackedConv1x1))
+    gemm_x3 = property(lambda self: self._packing(PackedConv1x1X3))
 
     def __call__(self, x, mode, out, out2=None, prepare=False, x3=False):
         b, _, hh, ww = x.shape
@@ -792,23 +768,7 @@ def conv_fused(x, pc, mode, out, out2=None, add=None, hidden=None, zgate=None, g
     d.pre_norm = ptr(pre_norm)
     d.b, d.cin, d.cout, d.h, d.w, d.kh, d.kw, d.mode, d.gate_channels = b, cin, pc.cout, hh, ww, pc.kh, pc.kw, mode, gate_channels
     d.stride = stride
-    import ctypes
-    if _REC is not None and not prepare:
-        _REC.log(_lib.OP_OF_ENTRY[entry], d, (x, pc, out, out2, add, hidden, zgate, scale, bias, residual, stats, pre_norm))
-    if prepare:                                    # the checked descriptor, to be launched again and again on the same buffers
-        fn, ref, keep = getattr(lib(), entry), ctypes.byref(d), (d, x, pc, out, out2, add, hidden, zgate, scale, bias, residual, stats, pre_norm)
-
-        def launch():
-            if _REC is not None:
-                _REC.log(_lib.OP_OF_ENTRY[entry], d, keep)
-            st = fn(ref, stream_ptr())
-            if st != 0:
-                check(st, entry)
-            return keep[3]
-        launch.keep, launch.op = keep, (_lib.OP_OF_ENTRY[entry], d)
-        return launch
-    check(getattr(lib(), entry)(ctypes.byref(d), stream_ptr()), entry)
-    return out
+    return _launch(_lib.KIND_OF_ENTRY[entry], d, (x, pc, out, out2, add, hidden, zgate, scale, bias, residual, stats, pre_norm), out, prepare)
 
 
 def conv_direct(x, weight, bias=None, stride=1, padding=0, relu=False, out=None):
@@ -837,18 +797,10 @@ def conv_direct(x, weight, bias=None, stride=1, padding=0, relu=False, out=None)
     return out
 
 
-class PackedWino1d:
+class PackedWino1d(_Packed):
     """Weights of a 1x5 / 5x1 stride-1 convolution transformed for rpe_conv_wino1d (U = G g along the taps, once per weight version)."""
-
-    def __init__(self, weight, bias=None):
-        w = _nchw(weight.detach().contiguous(), 'weight')
-        self.cout, self.cin, self.kh, self.kw = w.shape
-        n = lib().rpe_conv_wino1d_packed_floats(self.cout, self.cin) if (self.kh, self.kw) in ((1, 5), (5, 1)) else 0
-        if n == 0:
-            raise _lib.RpeError('PackedWino1d: needs a (cout, cin % 4 == 0, 1, 5) or (.., 5, 1) weight')
-        self.packed = torch.empty(n, dtype=torch.float32, device=w.device)
-        check(lib().rpe_conv_wino1d_pack(ptr(w), self.cout, self.cin, ptr(self.packed), stream_ptr()), 'rpe_conv_wino1d_pack')
-        self.bias = None if bias is None else _nchw(bias.detach().contiguous(), 'bias')
+    kernels, error = ((1, 5), (5, 1)), 'needs a (cout, cin % 4 == 0, 1, 5) or (.., 5, 1) weight'
+    size, pack, entry = 'rpe_conv_wino1d_packed_floats', 'rpe_conv_wino1d_pack', 'rpe_conv_wino1d'
 
     @staticmethod
     def supported(weight, ww):
@@ -859,61 +811,35 @@ def conv_wino1d(x, pw, mode, out, **kw):
     """rpe_conv_wino1d: conv_fused's operation (all four epilogue modes incl. the GRU gates) for 1x5 / 5x1 stride-1 convolutions
     by Winograd F(4,5) along the filter axis: 2.5x fewer matrix FLOPs.  Same keyword arguments as conv_fused (no scale /
     residual / stats / pre_norm)."""
-    return conv_fused(x, pw, mode, out, entry='rpe_conv_wino1d_x3' if getattr(pw, 'x3', False) else 'rpe_conv_wino1d', **kw)
+    return conv_fused(x, pw, mode, out, entry=pw.entry, **kw)
 
 
-class PackedWino1dX3:
+class PackedWino1dX3(_Packed):
     """Weights of a 1x5 / 5x1 stride-1 convolution transformed and split three ways into bf16 for rpe_conv_wino1d_x3 (the labelled
     bf16x3 variant of rpe_conv_wino1d; conv_wino1d dispatches on the packing)."""
-    x3 = True
-
-    def __init__(self, weight, bias=None):
-        w = _nchw(weight.detach().contiguous(), 'weight')
-        self.cout, self.cin, self.kh, self.kw = w.shape
-        n = lib().rpe_conv_wino1d_x3_packed_bytes(self.cout, self.cin) if (self.kh, self.kw) in ((1, 5), (5, 1)) else 0
-        if n == 0:
-            raise _lib.RpeError('PackedWino1dX3: needs a (cout, cin % 16 == 0, 1, 5) or (.., 5, 1) weight')
-        self.packed = torch.empty(n // 4, dtype=torch.float32, device=w.device)
-        check(lib().rpe_conv_wino1d_x3_pack(ptr(w), self.cout, self.cin, ptr(self.packed), stream_ptr()), 'rpe_conv_wino1d_x3_pack')
-        self.bias = None if bias is None else _nchw(bias.detach().contiguous(), 'bias')
+    kernels, error, in_bytes = ((1, 5), (5, 1)), 'needs a (cout, cin % 16 == 0, 1, 5) or (.., 5, 1) weight', True
+    size, pack, entry = 'rpe_conv_wino1d_x3_packed_bytes', 'rpe_conv_wino1d_x3_pack', 'rpe_conv_wino1d_x3'
 
     @staticmethod
     def supported(weight, ww):
         return tuple(weight.shape[2:]) in ((1, 5), (5, 1)) and weight.shape[1] % 16 == 0 and ww % 4 == 0
 
 
-class PackedWino:
+class PackedWino(_Packed):
     """Weights of a 3x3 stride-1 convolution transformed for rpe_conv_wino (U = G g G^T, once per weight version)."""
-
-    def __init__(self, weight, bias=None):
-        w = _nchw(weight.detach().contiguous(), 'weight')
-        self.cout, self.cin, self.kh, self.kw = w.shape
-        n = lib().rpe_conv_wino_packed_floats(self.cout, self.cin) if (self.kh, self.kw) == (3, 3) else 0
-        if n == 0:
-            raise _lib.RpeError('PackedWino: needs a (cout, cin % 4 == 0, 3, 3) weight')
-        self.packed = torch.empty(n, dtype=torch.float32, device=w.device)
-        check(lib().rpe_conv_wino_pack(ptr(w), self.cout, self.cin, ptr(self.packed), stream_ptr()), 'rpe_conv_wino_pack')
-        self.bias = None if bias is None else _nchw(bias.detach().contiguous(), 'bias')
+    kernels, error = ((3, 3),), 'needs a (cout, cin % 4 == 0, 3, 3) weight'
+    size, pack, entry = 'rpe_conv_wino_packed_floats', 'rpe_conv_wino_pack', 'rpe_conv_wino'
 
     @staticmethod
     def supported(weight, hh, ww):
         return tuple(weight.shape[2:]) == (3, 3) and weight.shape[1] % 4 == 0 and hh % 2 == 0 and ww % 2 == 0
 
 
-class PackedWinoX3:
+class PackedWinoX3(_Packed):
     """Weights of a 3x3 stride-1 convolution for rpe_conv_wino_x3, the LABELLED bf16x3 variant of rpe_conv_wino: U = G g G^T in f32,
     then the exact three-way bf16 split.  conv_wino() takes either packing and runs the kernel that belongs to it."""
-    x3 = True
-
-    def __init__(self, weight, bias=None):
-        w = _nchw(weight.detach().contiguous(), 'weight')
-        self.cout, self.cin, self.kh, self.kw = w.shape
-        n = lib().rpe_conv_wino_x3_packed_bytes(self.cout, self.cin) if (self.kh, self.kw) == (3, 3) else 0
-        if n == 0:
-            raise _lib.RpeError('PackedWinoX3: needs a (cout, cin % 16 == 0, 3, 3) weight')
-        self.packed = torch.empty(n // 4, dtype=torch.float32, device=w.device)       # (three bf16 planes; float32 storage for the descriptor)
-        check(lib().rpe_conv_wino_x3_pack(ptr(w), self.cout, self.cin, ptr(self.packed), stream_ptr()), 'rpe_conv_wino_x3_pack')
-        self.bias = None if bias is None else _nchw(bias.detach().contiguous(), 'bias')
+    kernels, error, in_bytes = ((3, 3),), 'needs a (cout, cin % 16 == 0, 3, 3) weight', True
+    size, pack, entry = 'rpe_conv_wino_x3_packed_bytes', 'rpe_conv_wino_x3_pack', 'rpe_conv_wino_x3'
 
     @staticmethod
     def supported(weight, hh, ww):
@@ -923,7 +849,6 @@ class PackedWinoX3:
 def conv_wino(x, pw, mode, out, out2=None, scale=None, bias='packed', residual=None, stats=None, pre_norm=None, prepare=False):
     """rpe_conv_wino: out = epilogue(conv3x3(x; pw) * scale + bias) by Winograd F(2x2,3x3); tensors are channel slices of NCHW
     buffers.  ``stats`` (conv_wino_stats_buffer) / ``pre_norm`` / ``residual`` / ``scale``: the encoders' epilogues, as conv_fused."""
-    import ctypes
     d = _lib.ConvDesc()
     b, cin, hh, ww = x.shape
     if cin != pw.cin:
@@ -956,25 +881,7 @@ def conv_wino(x, pw, mode, out, out2=None, scale=None, bias='packed', residual=N
         raise _lib.RpeError(f'conv_wino: pre_norm must be a contiguous float32 ({b},{cin},2) GPU tensor')
     d.stats, d.pre_norm = ptr(stats), ptr(pre_norm)
     d.b, d.cin, d.cout, d.h, d.w, d.kh, d.kw, d.mode, d.stride = b, cin, pw.cout, hh, ww, 3, 3, mode, 1
-    if _REC is not None and not prepare:
-        _REC.log(_lib.OP_CONV_WINO_X3 if getattr(pw, 'x3', False) else _lib.OP_CONV_WINO, d, (x, pw, out, out2, scale, bias, residual, stats, pre_norm))
-    if prepare:
-        fn, ref, keep = (lib().rpe_conv_wino_x3 if getattr(pw, 'x3', False) else lib().rpe_conv_wino), ctypes.byref(d), (d, x, pw, out, out2, scale, bias, residual, stats, pre_norm)
-
-        def launch():
-            if _REC is not None:
-                _REC.log(_lib.OP_CONV_WINO_X3 if getattr(pw, 'x3', False) else _lib.OP_CONV_WINO, d, keep)
-            st = fn(ref, stream_ptr())
-            if st != 0:
-                check(st, 'rpe_conv_wino')
-            return keep[3]
-        launch.keep, launch.op = keep, (_lib.OP_CONV_WINO_X3 if getattr(pw, 'x3', False) else _lib.OP_CONV_WINO, d)
-        return launch
-    if getattr(pw, 'x3', False):
-        check(lib().rpe_conv_wino_x3(ctypes.byref(d), stream_ptr()), 'rpe_conv_wino_x3')
-    else:
-        check(lib().rpe_conv_wino(ctypes.byref(d), stream_ptr()), 'rpe_conv_wino')
-    return out
+    return _launch(_lib.KIND_OF_ENTRY[pw.entry], d, (x, pw, out, out2, scale, bias, residual, stats, pre_norm), out, prepare)
 
 
 class TileMajorStats:
@@ -1025,10 +932,7 @@ def instnorm_finalize(stats, hw, eps=1e-5, channels=None):
         raise _lib.RpeError(f'instnorm_finalize: records hold {c} channels, expected {channels}')
     t, tiles = _stats_layout(stats, b, c, 'instnorm_finalize')
     mi = torch.empty(b, c, 2, dtype=torch.float32, device=t.device)
-    if _REC is not None:
-        _REC.log(_lib.OP_INSTNORM_FINALIZE, _lib.InstnormFinalizeArgs(t.data_ptr(), tiles, b, c, hw, float(eps), mi.data_ptr()), (t, mi))
-    check(lib().rpe_instnorm_finalize(ptr(t), tiles, b, c, hw, float(eps), ptr(mi), stream_ptr()), 'rpe_instnorm_finalize')
-    return mi
+    return _launch(_lib.OP_INSTNORM_FINALIZE, (ptr(t), tiles, b, c, hw, float(eps), ptr(mi)), (t, mi), mi)
 
 
 def instnorm_apply(x, stats, eps=1e-5, relu=True, residual=None, out=None, residual_norm=None, residual_relu=True):
@@ -1052,26 +956,21 @@ def instnorm_apply(x, stats, eps=1e-5, relu=True, residual=None, out=None, resid
         raise _lib.RpeError(f'instnorm_apply: residual_norm must be a contiguous float32 ({b},{c},2) GPU tensor next to a residual')
     out = x if out is None else _nchw(out, 'out')
     flags = int(bool(relu)) | (0 if residual_relu or residual_norm is None else 2)
-    if _REC is not None:
-        dp = lambda v: v.data_ptr() if v is not None else None
-        _REC.log(_lib.OP_INSTNORM_APPLY, _lib.InstnormApplyArgs(x.data_ptr(), t.data_ptr(), tiles, b, c, hh * ww, float(eps), flags, dp(residual),
-                                                                dp(residual_norm), out.data_ptr()), (x, t, residual, residual_norm, out))
-    check(lib().rpe_instnorm_apply_ex(ptr(x), ptr(t), tiles, b, c, hh * ww, float(eps), flags, ptr(residual), ptr(residual_norm),
-                                      ptr(out), stream_ptr()), 'rpe_instnorm_apply_ex')
-    return out
+    return _launch(_lib.OP_INSTNORM_APPLY, (ptr(x), ptr(t), tiles, b, c, hh * ww, float(eps), flags, ptr(residual), ptr(residual_norm), ptr(out)),
+                   (x, t, residual, residual_norm, out), out)
 
 
-class PackedStem:
+class PackedStem(_Packed):
     """A (cout, cin, 7, 7) weight (cin 3: encoder stem, stride 2; cin 2: convf1, stride 1) in rpe_stem_conv's layout."""
+    error = 'weight must be (64k, 2|3, 7, 7)'
+    size, pack, entry = 'rpe_stem_packed_floats', 'rpe_stem_pack', 'rpe_stem_conv'
 
     def __init__(self, weight):
-        w = _nchw(weight.detach().contiguous(), 'weight')
-        self.cout, self.cin = w.shape[0], w.shape[1]
-        if tuple(w.shape[2:]) != (7, 7) or self.cin not in (2, 3) or self.cout % 64:
-            raise _lib.RpeError('PackedStem: weight must be (64k, 2|3, 7, 7)')
+        super().__init__(weight)
         self.stride = 2 if self.cin == 3 else 1
-        self.packed = torch.empty(lib().rpe_stem_packed_floats(self.cout, self.cin), dtype=torch.float32, device=w.device)
-        check(lib().rpe_stem_pack(ptr(w), self.cout, self.cin, ptr(self.packed), stream_ptr()), 'rpe_stem_pack')
+
+    def _fits(self):
+        return (self.kh, self.kw) == (7, 7) and self.cin in (2, 3) and self.cout % 64 == 0
 
 
 def stem_conv(image, ps, bias=None, scale=None, relu=True, stats=False, div=255.0, mul=2.0, sub=1.0, out=None, prepare=False):
@@ -1093,26 +992,9 @@ def stem_conv(image, ps, bias=None, scale=None, relu=True, stats=False, div=255.
         stats = True
     else:
         st = torch.empty(b, ps.cout, lib().rpe_stem_tiles(hh, ww, st_), 3, dtype=torch.float32, device=image.device) if stats else None
-    if prepare or _REC is not None:
-        dp = lambda t: t.data_ptr() if t is not None else None
-        a = _lib.StemConvArgs(dp(image), b, c, hh, ww, st_, float(div), float(mul), float(sub), dp(ps.packed), ps.cout, dp(bias), dp(scale), int(bool(relu)),
-                              dp(out), dp(st))
-        fn, keep = lib().rpe_stem_conv, (image, ps, bias, scale, out, st)
-        if not prepare:
-            _REC.log(_lib.OP_STEM_CONV, a, keep)
-
-    if prepare:
-        def launch():
-            if _REC is not None:
-                _REC.log(_lib.OP_STEM_CONV, a, keep)
-            check(fn(a.image, a.b, a.cin, a.h, a.w, a.stride, a.div, a.mul, a.sub, a.packed, a.cout, a.bias, a.scale, a.relu, a.out, a.stats, stream_ptr()),
-                  'rpe_stem_conv')
-            return keep[4]
-        launch.keep, launch.op = keep, (_lib.OP_STEM_CONV, a)
-        return launch
-    check(lib().rpe_stem_conv(ptr(image), b, c, hh, ww, st_, float(div), float(mul), float(sub), ptr(ps.packed), ps.cout, ptr(bias), ptr(scale),
-                              int(bool(relu)), ptr(out), ptr(st), stream_ptr()), 'rpe_stem_conv')
-    return (out, st) if stats else out
+    return _launch(_lib.OP_STEM_CONV, (ptr(image), b, c, hh, ww, st_, float(div), float(mul), float(sub), ptr(ps.packed), ps.cout, ptr(bias), ptr(scale),
+                                       int(bool(relu)), ptr(out), ptr(st)), (image, ps, bias, scale, out, st),
+                   (out, st) if stats and not prepare else out, prepare)
 
 
 # ------------------------------------------------------------------------------------------------- weight heads

@@ -27,6 +27,8 @@ Exact re-associations used (results identical up to float rounding):
 The RAFT architecture itself is restated from princeton-vl/RAFT (the reference's submodule is empty);
 see oracle/raft.py for the CPU restatement these kernels are tested against.
 """
+from types import SimpleNamespace
+
 import torch
 import torch.nn as nn
 
@@ -471,70 +473,23 @@ class BasicMotionEncoder(nn.Module):
         self.convf2 = nn.Conv2d(128, 64, 3, padding=1)
         self.conv = nn.Conv2d(64 + 192, 128 - 2, 3, padding=1)
 
-    def _calls(self, corr, cat_buf, hx, rhx, packed):
-        """Prepared launchers of the fused route for one buffer set (descriptors checked once; the 12 iterations reuse them)."""
-        key = (corr.data_ptr(), cat_buf.data_ptr(), hx.data_ptr(), rhx.data_ptr(), tuple(corr.shape))
-        cache = packed.setdefault('_enc_calls', {})               # one entry per workspace (a tracker alternates between batch n and 2n)
-        calls = cache.get(key)
-        if calls is None:
-            cor = packed['cor_buf'](corr)
-            flo = packed['flo_buf'](corr)
-            wino = dict(packed['wino']) if corr.shape[-1] % 2 == 0 and corr.shape[-2] % 2 == 0 else {}
-            if wino and corr.shape[-1] % 4 == 0:
-                wino.update(packed.get('wino_x3', {}))          # (CONV_BF16X3: conv_wino runs the kernel that belongs to the packing)
+    def flow_branch(self, flow, P, L):
+        """convf1 -> convf2 of the fused route (``P`` = BasicUpdateBlock.packed_convs, ``L`` = its launchers): depends on the flow only, not
+        on the correlation lookup, so it may run on a side stream beside lookup -> convc1 -> convc2."""
+        ops.stem_conv(flow, P['convf1'], bias=self.convf1.bias.detach(), relu=True, div=1.0, mul=1.0, sub=0.0, out=L.flo)   # 7x7 on 2 channels
+        L.f2()
 
-            def c3(name, x, out, out2=None):            # a 3x3 layer: Winograd when available, else the direct implicit GEMM
-                if name in wino:
-                    return ops.conv_wino(x, wino[name], ops.CONV_RELU, out, out2=out2, prepare=True)
-                return ops.conv_fused(x, packed[name], ops.CONV_RELU, out, out2=out2, prepare=True)
-            calls = (key, cor, flo,
-                     packed['convc1_1x1'](corr, ops.CONV_RELU, cor, prepare=True, x3=CONV_BF16X3),
-                     c3('convc2', cor, cat_buf[:, :192]), c3('convf2', flo, cat_buf[:, 192:]),
-                     c3('conv', cat_buf, hx[:, 128:254], rhx[:, 128:254]))
-            _bounded_put(cache, key, calls, keep=4)
-        return calls
-
-    def flow_branch_launchers(self, flow, corr, cat_buf, hx, rhx, packed):
-        """(convf1, convf2) as prepared launchers on these buffers (``flow`` must be the persistent flow buffer of the workspace)."""
-        _, cor, flo_buf, c1, c2, f2, cv_ = self._calls(corr, cat_buf, hx, rhx, packed)
-        key = (flow.data_ptr(), flo_buf.data_ptr())
-        cache = packed.setdefault('_f1_calls', {})
-        f1 = cache.get(key)
-        if f1 is None:
-            f1 = ops.stem_conv(flow, packed['convf1'], bias=self.convf1.bias.detach(), relu=True, div=1.0, mul=1.0, sub=0.0, out=flo_buf, prepare=True)
-            _bounded_put(cache, key, f1, keep=4)
-        return f1, f2
-
-    def flow_branch(self, flow, corr, cat_buf, hx, rhx, packed):
-        """convf1 -> convf2 (fused route): depends on the flow only, not on the correlation lookup, so RAFT.forward may run it on a
-        side stream beside lookup -> convc1 -> convc2."""
-        _, cor, flo_buf, c1, c2, f2, cv_ = self._calls(corr, cat_buf, hx, rhx, packed)
-        ops.stem_conv(flow, packed['convf1'], bias=self.convf1.bias.detach(), relu=True, div=1.0, mul=1.0, sub=0.0, out=flo_buf)   # 7x7 on 2 channels
-        f2()
-
-    def forward(self, flow, corr, cat_buf, hx, rhx, packed=None, flow_in_place=False, flow_branch_done=None):
-        """Writes relu(conv(cat[cor, flo])) (126 ch) and flow (2 ch) into channels [128,256) of hx and rhx.
-        ``packed`` (BasicUpdateBlock.packed_convs) selects the fused HIP convolutions (conv + bias + ReLU + cat in
-        one kernel each); otherwise the generic convolution (ops.conv_direct) runs without bias and rpe_bias_act does the rest.
-        ``flow_branch_done``: an event recorded behind flow_branch() on another stream (it then is not run here)."""
+    def forward(self, flow, corr, cat_buf, hx, rhx):
+        """The generic route (no packed_convs): writes relu(conv(cat[cor, flo])) (126 ch) and flow (2 ch) into channels [128,256) of hx and
+        rhx -- the generic convolution (ops.conv_direct) without bias, rpe_bias_act for the rest."""
         def cv(m, x):
             return ops.conv_direct(x, m.weight, None, m.stride, m.padding)
-        if packed is not None:
-            _, cor, flo_buf, c1, c2, f2, cv_ = self._calls(corr, cat_buf, hx, rhx, packed)
-            c1(); c2()
-            if flow_branch_done is None:
-                self.flow_branch(flow, corr, cat_buf, hx, rhx, packed)
-            else:
-                torch.cuda.current_stream().wait_event(flow_branch_done)
-            cv_()
-        else:
-            cor = ops.bias_act(cv(self.convc1, corr), self.convc1.bias)
-            ops.bias_act(cv(self.convc2, cor), self.convc2.bias, out=cat_buf, out_offset=0)
-            flo = ops.bias_act(cv(self.convf1, flow), self.convf1.bias)
-            ops.bias_act(cv(self.convf2, flo), self.convf2.bias, out=cat_buf, out_offset=192)
-            ops.bias_act(cv(self.conv, cat_buf), self.conv.bias, out=hx, out_offset=128, out2=rhx, out2_offset=128)
-        if not flow_in_place:                                   # (the fused flow head has already written flow behind the motion features)
-            ops.bias_act(flow, None, relu=False, out=hx, out_offset=254, out2=rhx, out2_offset=254)
+        cor = ops.bias_act(cv(self.convc1, corr), self.convc1.bias)
+        ops.bias_act(cv(self.convc2, cor), self.convc2.bias, out=cat_buf, out_offset=0)
+        flo = ops.bias_act(cv(self.convf1, flow), self.convf1.bias)
+        ops.bias_act(cv(self.convf2, flo), self.convf2.bias, out=cat_buf, out_offset=192)
+        ops.bias_act(cv(self.conv, cat_buf), self.conv.bias, out=hx, out_offset=128, out2=rhx, out2_offset=128)
+        ops.bias_act(flow, None, relu=False, out=hx, out_offset=254, out2=rhx, out2_offset=254)
 
 
 class BasicUpdateBlock(nn.Module):
@@ -625,58 +580,75 @@ class BasicUpdateBlock(nn.Module):
             self._packed = (key, P)
         return self._packed[1]
 
-    def gru_launchers(self, hx, rhx, z_buf, ctx, flow, coords1, in_place, P):
-        """Prepared launchers of the GRU, FlowHead.conv1 and (``in_place``) the flow head's output layer with the coords / flow bookkeeping,
-        on these buffers (descriptors checked once; every iteration of every pass on the same workspace reuses them)."""
+    def launchers(self, ws, pyr=None):
+        """Prepared launchers of the fused route's update on workspace ``ws`` (RAFT._workspace), built once and cached in ``ws`` until the
+        packed weights change (every iteration of every pass on the workspace reuses them): c1, c2, f1, f2, cv (the motion encoder's convc1,
+        convc2, convf1, convf2, conv; flo = convf1's output) and gru (the four GRU convolutions, FlowHead.conv1 and the flow head's output
+        layer, which updates ws['coords1'] in place and writes flow = coords1 - grid into ws['flow'] and behind the motion features of hx /
+        rhx).  With the pyramid ``pyr`` (the launch list's route) also lookup on coords1 and lookup_c1: lookup -> convc1 -> ReLU as one
+        launch where that pays (LOOKUP_FUSED), else None."""
+        hx, rhx, z_buf, cat_buf, corr, coords1, flow, ctx = (ws[k] for k in ('hx', 'rhx', 'z', 'cat', 'corr', 'coords1', 'flow', 'ctx'))
+        P = self.packed_convs(hx.shape[-1])
+        key = (id(P), None if pyr is None else (pyr.buf.data_ptr(), LOOKUP_FUSED, LOOKUP_FUSED_MAX_WGS))
+        cached = ws.get('_launchers')
+        if cached is not None and cached[0] == key:
+            return cached[2]
         c = self.hidden_dim
-        fh = self.flow_head
+        e, fh = self.encoder, self.flow_head
+        cor, flo, fh_buf = P['cor_buf'](corr), P['flo_buf'](corr), P['fh_buf'](hx)
+        wino = dict(P['wino']) if hx.shape[-1] % 2 == 0 and hx.shape[-2] % 2 == 0 else {}
+        if wino and hx.shape[-1] % 4 == 0:
+            wino.update(P['wino_x3'])                      # (CONV_BF16X3: conv_wino runs the kernel that belongs to the packing)
+
+        def c3(name, x, out, out2=None):                    # a 3x3 layer: Winograd when available, else the direct implicit GEMM
+            if name in wino:
+                return ops.conv_wino(x, wino[name], ops.CONV_RELU, out, out2=out2, prepare=True)
+            return ops.conv_fused(x, P[name], ops.CONV_RELU, out, out2=out2, prepare=True)
         # each GRU half = two implicit-GEMM convolutions whose epilogues are the gates:
         #   z = s(convz hx + ctx), r*h -> rhx ;  h <- (1-z) h + z tanh(convq rhx + ctx)   (in place on hx[:, :c])
-        key = (hx.data_ptr(), rhx.data_ptr(), z_buf.data_ptr(), tuple(ctx[k].data_ptr() for k in ('zr1', 'q1', 'zr2', 'q2')), tuple(hx.shape),
-               (coords1.data_ptr(), flow.data_ptr()) if in_place else None)
-        cache = P.setdefault('_gru_calls', {})
-        calls = cache.get(key)
-        if calls is None:
-            seq = []
-            gconv = ops.conv_wino1d if isinstance(P['zr1'], (ops.PackedWino1d, ops.PackedWino1dX3)) else ops.conv_fused
-            for zr, q in (('zr1', 'q1'), ('zr2', 'q2')):
-                seq.append(gconv(hx, P[zr], ops.CONV_GATE_ZR, z_buf, out2=rhx[:, :c], add=ctx[zr], hidden=hx[:, :c], gate_channels=c,
-                                 prepare=True))
-                seq.append(gconv(rhx, P[q], ops.CONV_GATE_H, hx[:, :c], add=ctx[q], hidden=hx[:, :c], zgate=z_buf, prepare=True))
-            if 'fh1' in P['wino'] and hx.shape[-1] % 2 == 0 and hx.shape[-2] % 2 == 0:
-                pfh = P['wino_x3']['fh1'] if 'fh1' in P.get('wino_x3', {}) and hx.shape[-1] % 4 == 0 else P['wino']['fh1']
-                seq.append(ops.conv_wino(hx[:, :c], pfh, ops.CONV_RELU, P['fh_buf'](hx), prepare=True))
-            else:
-                seq.append(ops.conv_fused(hx[:, :c], P['fh1'], ops.CONV_RELU, P['fh_buf'](hx), prepare=True))
-            if in_place:
-                seq.append(ops.flow_update(P['fh_buf'](hx), fh.conv2.weight, fh.conv2.bias.detach(), coords1, coords1, flow_out=flow,
-                                           dst1=hx[:, 2 * c - 2:], dst2=rhx[:, 2 * c - 2:], prepare=True))
-            calls = (key, seq)
-            _bounded_put(cache, key, calls, keep=4)
-        return calls[1]
+        gconv = ops.conv_wino1d if isinstance(P['zr1'], (ops.PackedWino1d, ops.PackedWino1dX3)) else ops.conv_fused
+        gru = []
+        for zr, q in (('zr1', 'q1'), ('zr2', 'q2')):
+            gru.append(gconv(hx, P[zr], ops.CONV_GATE_ZR, z_buf, out2=rhx[:, :c], add=ctx[zr], hidden=hx[:, :c], gate_channels=c, prepare=True))
+            gru.append(gconv(rhx, P[q], ops.CONV_GATE_H, hx[:, :c], add=ctx[q], hidden=hx[:, :c], zgate=z_buf, prepare=True))
+        gru.append(c3('fh1', hx[:, :c], fh_buf))
+        gru.append(ops.flow_update(fh_buf, fh.conv2.weight, fh.conv2.bias.detach(), coords1, coords1, flow_out=flow, dst1=hx[:, 2 * c - 2:],
+                                   dst2=rhx[:, 2 * c - 2:], prepare=True))
+        L = SimpleNamespace(flo=flo, c1=P['convc1_1x1'](corr, ops.CONV_RELU, cor, prepare=True, x3=CONV_BF16X3), c2=c3('convc2', cor, cat_buf[:, :192]),
+                            f1=ops.stem_conv(flow, P['convf1'], bias=e.convf1.bias.detach(), relu=True, div=1.0, mul=1.0, sub=0.0, out=flo, prepare=True),
+                            f2=c3('convf2', flo, cat_buf[:, 192:]), cv=c3('conv', cat_buf, hx[:, 128:254], rhx[:, 128:254]), gru=gru)
+        if pyr is not None:
+            L.lookup, L.lookup_c1 = pyr.lookup(coords1, out=corr, prepare=True), None
+            n_wgs = hx.shape[0] * -(-(hx.shape[2] * -(-hx.shape[3] // 8)) // 8)
+            if LOOKUP_FUSED and not CONV_BF16X3 and n_wgs <= LOOKUP_FUSED_MAX_WGS and ops.PackedLookupConv.supported(pyr.levels, pyr.radius, pyr.w8):
+                if 'convc1_lookup' not in P:
+                    P['convc1_lookup'] = ops.PackedLookupConv(e.convc1.weight, e.convc1.bias)
+                L.lookup_c1 = pyr.lookup_conv1x1(coords1, P['convc1_lookup'], cor, relu=True, prepare=True)
+        ws['_launchers'] = (key, P, L)                      # (holding P: no other dict can take its id while the entry lives)
+        return L
 
-    def step(self, hx, rhx, z_buf, cat_buf, h_buf, ctx, corr, flow, coords1, in_place=False, flow_branch_done=None):
-        """One update.  hx = (h | motion | flow), rhx = (r*h | motion | flow), both (b,256,h,w); ctx = context_terms().
-        Returns coords1 + delta_flow; the new hidden state is left in hx[:, :128] (h_buf is written by the generic
-        path only: the fused flow head reads the slice directly).  ``in_place`` (fused route only): ``coords1`` and ``flow`` are
-        persistent buffers; the flow head's output layer updates coords1 in place and writes flow = coords1 - grid into ``flow``
-        and behind the motion features of hx / rhx, so the loop runs without subtract / copy launches."""
+    def step(self, ws, ctx, flow, coords1, h_buf, flow_branch_done=None):
+        """One update on workspace ``ws``: hx = (h | motion | flow), rhx = (r*h | motion | flow), both (b,256,h,w); ctx = context_terms();
+        the new hidden state is left in hx[:, :128].  Fused route (packed_convs): the workspace's launchers, ``coords1`` and ``flow`` are its
+        persistent buffers and the flow head's output layer updates them in place (no subtract / copy launches); ``flow_branch_done``: an
+        event recorded behind flow_branch() on another stream (it then is not run here).  Generic route: returns coords1 + delta_flow and
+        writes h_buf (the fused flow head reads the slice directly)."""
         c = self.hidden_dim
+        hx, rhx, z_buf, cat_buf, corr = (ws[k] for k in ('hx', 'rhx', 'z', 'cat', 'corr'))
         P = self.packed_convs(hx.shape[-1])
-        if in_place and P is None:
-            raise RuntimeError('in_place update needs the fused route')
-        self.encoder(flow, corr, cat_buf, hx, rhx, packed=P, flow_in_place=in_place, flow_branch_done=flow_branch_done)
-        fh = self.flow_head
         if P is not None:
-            calls = (None, self.gru_launchers(hx, rhx, z_buf, ctx, flow, coords1, in_place, P))
-            if in_place:
-                for launch in calls[1]:
-                    launch()
-                return coords1
-            for launch in calls[1][:-1]:
+            L = self.launchers(ws)
+            L.c1(); L.c2()
+            if flow_branch_done is None:
+                self.encoder.flow_branch(flow, P, L)
+            else:
+                torch.cuda.current_stream().wait_event(flow_branch_done)
+            L.cv()
+            for launch in L.gru:
                 launch()
-            t = calls[1][-1]()
-            return ops.conv3x3_to2(t, fh.conv2.weight, fh.conv2.bias, add=coords1)  # coords1 + delta_flow
+            return coords1
+        self.encoder(flow, corr, cat_buf, hx, rhx)
+        fh = self.flow_head
         W = self.gate_weights()
         # horizontal half: z = s(convz1 hx), r = s(convr1 hx), q = tanh(convq1 [r*h, x]), h = (1-z) h + z q
         zr = ops.conv_direct(hx, W['zr1'][0], None, 1, (0, 2))
@@ -787,23 +759,12 @@ class RAFT(nn.Module):
         per (weights, pyramid, workspace, iters, streams) and replayed by one rpe_run_ops call per pass.  Cells 0 / 1: the fork / join
         events; cells 2 + 2k, 3 + 2k: timing events around iteration k's lookup (LOOKUP_EVENT_SINK; empty = skipped).
         Returns (list, marks) with marks[k] = first op of iteration k, marks[iters] = the end."""
-        ub = self.update_block
-        hx, rhx, z_buf, cat_buf, corr, coords1, flow = (ws[k] for k in ('hx', 'rhx', 'z', 'cat', 'corr', 'coords1', 'flow'))
-        P = ub.packed_convs(hx.shape[-1])
-        key = (id(P), pyr.buf.data_ptr(), iters, None if side is None else side[0].cuda_stream, LOOKUP_FUSED, LOOKUP_FUSED_MAX_WGS)
+        L = self.update_block.launchers(ws, pyr)
+        key = (id(L), iters, None if side is None else side[0].cuda_stream)
         cached = ws.get('_program')
         if cached is not None and cached[0] == key:
             return cached[1], cached[2]
-        _, _, _, c1, c2, _, cv_ = ub.encoder._calls(corr, cat_buf, hx, rhx, P)
-        f1, f2 = ub.encoder.flow_branch_launchers(flow, corr, cat_buf, hx, rhx, P)
-        seq = ub.gru_launchers(hx, rhx, z_buf, ws['ctx'], flow, coords1, True, P)
-        lk = pyr.lookup(coords1, out=corr, prepare=True)
-        n_wgs = hx.shape[0] * -(-(hx.shape[2] * -(-hx.shape[3] // 8)) // 8)
-        if LOOKUP_FUSED and not CONV_BF16X3 and n_wgs <= LOOKUP_FUSED_MAX_WGS and ops.PackedLookupConv.supported(pyr.levels, pyr.radius, pyr.w8):
-            cor = P['cor_buf'](corr)
-            if 'convc1_lookup' not in P:
-                P['convc1_lookup'] = ops.PackedLookupConv(ub.encoder.convc1.weight, ub.encoder.convc1.bias)
-            lk, c1 = pyr.lookup_conv1x1(coords1, P['convc1_lookup'], cor, relu=True, prepare=True), None      # one launch for lookup -> convc1 -> ReLU
+        lk, c1 = (L.lookup, L.c1) if L.lookup_c1 is None else (L.lookup_c1, None)
         prog = ops.OpList(n_cells=2 + 2 * iters)
         if side is not None:
             for cell, ev in ((0, side[1]), (1, side[2])):
@@ -813,20 +774,20 @@ class RAFT(nn.Module):
         for itr in range(iters):
             marks.append(prog.mark())
             if side is not None:                                  # the flow branch needs only the flow: beside lookup -> convc1 -> convc2
-                prog.record(0, 0).wait(0, 1).add(f1, 1).add(f2, 1).record(1, 1)
+                prog.record(0, 0).wait(0, 1).add(L.f1, 1).add(L.f2, 1).record(1, 1)
             prog.record(2 + 2 * itr, 0).add(lk).record(3 + 2 * itr, 0)
             if c1 is not None:
                 prog.add(c1)
-            prog.add(c2)
+            prog.add(L.c2)
             if side is not None:
                 prog.wait(1, 0)
             else:
-                prog.add(f1).add(f2)
-            prog.add(cv_)
-            for launch in seq:
+                prog.add(L.f1).add(L.f2)
+            prog.add(L.cv)
+            for launch in L.gru:
                 prog.add(launch)
         marks.append(prog.mark())
-        prog.keep = (P, pyr, side)
+        prog.keep = (L, side)                                 # (holding L: no other launcher set can take its id while the program lives)
         prog.armed = False
         ws['_program'] = (key, prog, marks)
         return prog, marks
@@ -972,7 +933,9 @@ class RAFT(nn.Module):
         if cnet is None:
             cnet = self.encode_context(image1)                # (tanh(net) | relu(inp))
         c = self.hidden_dim
-        fused = self.update_block.packed_convs(w8) is not None
+        ub = self.update_block
+        P = ub.packed_convs(w8)
+        fused = P is not None
         if fused and FRAME_OPLISTS and LOOP_OPLIST and not all_flows and N <= FRAME_OPLISTS_MAX_IMAGES and LOOKUP_EVENT_SINK is None:
             r = self._forward_recorded(fmap1, fmap2, cnet, iters, upsample)
             if r is not None:
@@ -980,7 +943,7 @@ class RAFT(nn.Module):
         pyr = self._pyramid(N, h8, w8, dev)
         ws = self._workspace(N, h8, w8, dev)
         ctx = self._begin(pyr, ws, fmap1, fmap2, cnet, fused)
-        hx, rhx, z_buf, cat_buf, corr = ws['hx'], ws['rhx'], ws['z'], ws['cat'], ws['corr']   # hx = (h | motion | flow)
+        hx, corr = ws['hx'], ws['corr']                     # hx = (h | motion | flow)
         h_buf = torch.empty(N, c, h8, w8, device=dev)         # returned to the caller: fresh
         inp = cnet[:, c:]
         coords0 = ws['coords0']
@@ -1011,14 +974,12 @@ class RAFT(nn.Module):
                 ev_flow.record()
                 with torch.cuda.stream(stream):
                     stream.wait_event(ev_flow)
-                    self.update_block.encoder.flow_branch(flow, corr, cat_buf, hx, rhx, self.update_block.packed_convs(w8))
+                    ub.encoder.flow_branch(flow, P, ub.launchers(ws))
                     done.record()
             pyr.lookup(coords1, out=corr)
-            if fused:
-                self.update_block.step(hx, rhx, z_buf, cat_buf, h_buf, ctx, corr, flow, coords1, in_place=True, flow_branch_done=done)
-            else:
+            if not fused:
                 flow = coords1 - coords0
-                coords1 = self.update_block.step(hx, rhx, z_buf, cat_buf, h_buf, ctx, corr, flow, coords1)
+            coords1 = ub.step(ws, ctx, flow, coords1, h_buf, flow_branch_done=done)
             if all_flows or itr == iters - 1:
                 lowres = flow if fused else coords1 - coords0
                 if upsample:
