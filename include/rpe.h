@@ -53,9 +53,10 @@ const char *rpe_version(void);
  * additions, so a binding can require "version 5, minor >= m" for the newest entry point it calls -- or probe with dlsym:
  *   minor 0: the 68 entry points of round 4;  1: rpe_conv_wino_x3*, rpe_conv1x1_x3*, rpe_conv_wino1d_x3* (9, round 5);  2: rpe_run_ops and
  *   the rpe_*_args structs of the prepared launch lists, rpe_corr_lookup_conv1x1* (round 6);  3: struct rpe_surfel_map and the
- *   rpe_surfel_* entry points of frame-to-model tracking (7). */
+ *   rpe_surfel_* entry points of frame-to-model tracking (7);  4: rpe_surfel_*_many (K maps per launch, RPE_SURFEL_MAX_MAPS) and
+ *   rpe_pose_gate_chain_rows, for tracking several sequences frame to model in one batch (8). */
 #define RPE_ABI_VERSION 5
-#define RPE_ABI_MINOR 3
+#define RPE_ABI_MINOR 4
 int rpe_abi_minor(void);
 int rpe_abi_version(void);
 
@@ -80,6 +81,10 @@ int rpe_se3_chain(const void *rel, const void *init, void *out, int64_t m, doubl
  * 1 where the row passed (may be NULL).  Same arithmetic as rpe_se3_log / _inv / _mul step by step: bit-identical poses.            */
 int rpe_pose_gate_chain(const void *rel, const void *init, void *rel_out, void *abs_out, int32_t *ok, int64_t m, double scale,
                         double thr, int dtype, void *stream);
+/* rpe_pose_gate_chain for m INDEPENDENT rows (m sequences tracked side by side): row k is gated and chained onto ITS OWN init row,
+ * init (m,7) (may be NULL = identity for every row), and gives the bits a rpe_pose_gate_chain call with m = 1 gives for it.          */
+int rpe_pose_gate_chain_rows(const void *rel, const void *init, void *rel_out, void *abs_out, int32_t *ok, int64_t m, double scale,
+                             double thr, int dtype, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Pose layer -- replaces DPoseSE3Head.objective / .solve (core/pose/pose_head.py:12-79) together with
@@ -640,6 +645,34 @@ int rpe_surfel_render(const rpe_surfel_map *m, int64_t n_bound, const float *kma
  * in_cap / out_cap are the row strides of the two (3, cap) arrays. */
 int rpe_surfel_transform(const float *opts_in, int64_t in_cap, float *opts_out, int64_t out_cap, const int32_t *count, int64_t n_bound,
                          const float *T, void *stream);
+
+/* K maps per call (ABI minor 4): several sequences tracked frame to model in one batch.  Map k of a call gets bit for bit what the
+ * single-map entry point gives it alone -- count, order, t_created, overflow word, render outputs, render tie winners -- but each
+ * stage is ONE launch over all K maps (a compaction's scan: one workgroup per map).  maps / dst / src are HOST arrays of K
+ * descriptors, n_bounds HOST int64 arrays, kmat / kinv of the fuse and init HOST arrays of K device pointers (each map's own 3x3);
+ * batched frame inputs are device tensors of K (or `batch`) rows: depth / mask / confidence (.,1,h,w), img (.,3,h,w), poses (.,7).
+ * 0 <= K <= RPE_SURFEL_MAX_MAPS (K = 0: nothing to do, RPE_OK); the maps of one call must not share storage.  The per-map argument
+ * table goes into the head of the workspace with small kernel launches (no host copy, no allocation, no synchronisation: the calls
+ * can be captured into a graph).  Workspace: rpe_surfel_workspace_bytes_many(K, n_bounds, h, w) bytes (>= the sum of the single-map
+ * sizes; 0 on bad arguments), 256-aligned; render and fuse need the K n_bounds of the call, init K zeros. */
+#define RPE_SURFEL_MAX_MAPS 64
+size_t rpe_surfel_workspace_bytes_many(int nmaps, const int64_t *n_bounds, int h, int w);
+/* rpe_surfel_init for K frames: map dst[k] from row k of depth / img / mask / confidence at pmat row k, with kinv[k]. */
+int rpe_surfel_init_many(int nmaps, const float *depth, const float *img, const uint8_t *mask, const float *confidence, int h, int w,
+                         const float *const *kinv, const float *pmat, float conf_thr, const rpe_surfel_map *dst, void *workspace,
+                         void *stream);
+/* rpe_surfel_render of map k with n_bounds[k], kmat row k (K,3,3) and T row k (K,7), into row k of img (K,3,h,w), depth /
+ * confidence (K,1,h,w) and mask (K,1,h,w) u8: the rows of one batch, no concatenation.  One splat and one resolve launch. */
+int rpe_surfel_render_many(int nmaps, const rpe_surfel_map *maps, const int64_t *n_bounds, const float *kmat, const float *T,
+                           int depth_transformed, int h, int w, float *img, float *depth, float *confidence, uint8_t *mask, void *workspace,
+                           void *stream);
+/* rpe_surfel_fuse of map k (src[k] -> dst[k], n_bounds[k], ticks[k], kmat[k], kinv[k]) with frame row rows[k] (0 <= rows[k] < batch) of
+ * depth / img / mask and of pose (batch,7): a caller fuses the subset of its maps whose frame passed the gate.  d_thresh, average_pts,
+ * upscale, conf_thr and t_max are shared.  Update, block counts, scan and scatter: one launch each. */
+int rpe_surfel_fuse_many(int nmaps, const rpe_surfel_map *src, const int64_t *n_bounds, const rpe_surfel_map *dst, const int32_t *ticks,
+                         const int32_t *rows, int batch, const float *depth, const float *img, const uint8_t *mask, int h, int w,
+                         const float *const *kmat, const float *const *kinv, const float *pose, float d_thresh, int average_pts, int upscale,
+                         float conf_thr, int t_max, void *workspace, void *stream);
 
 #ifdef __cplusplus
 }

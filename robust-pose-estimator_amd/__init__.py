@@ -11,7 +11,7 @@ Layout:
                       up-sampling in HIP)
   pose_head.py        DPoseSE3Head / DeclarativeLayerLie mirrors on rpe_pose_solve
   pose_net.py         PoseNet.infer / flow2depth mirror
-  pose_estimator.py   frame-to-frame tracker mirror (+ Frame), SurfelPoseEstimator (frame to model), from_config
+  pose_estimator.py   frame-to-frame tracker mirror (+ Frame), SurfelPoseEstimator (frame to model), MultiSurfelPoseEstimator (K sequences), from_config
   surfel_map.py       SurfelMap mirror on the rpe_surfel_* kernels
   sharding.py         one-process-per-GPU sequence sharding, RCCL all-gather of relative poses
   synth.py            seeded synthetic stereo inputs for tests and bench

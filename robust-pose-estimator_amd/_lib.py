@@ -96,7 +96,9 @@ LIST_OPS = {OP_CONV_FUSED: ('rpe_conv_fused', ConvDesc), OP_CONV_WINO: ('rpe_con
             OP_LOOKUP_CONV1X1: ('rpe_corr_lookup_conv1x1', LookupConv1x1Args)}
 KIND_OF_ENTRY = {entry: kind for kind, (entry, _) in LIST_OPS.items()}
 
-ABI_MINOR = 3              # RPE_ABI_MINOR: the newest additions this binding calls (rpe_surfel_*)
+ABI_MINOR = 3              # RPE_ABI_MINOR of the single-map surfel entry points (rpe_surfel_*)
+ABI_MINOR_MANY = 4         # RPE_ABI_MINOR of rpe_surfel_*_many and rpe_pose_gate_chain_rows: the newest additions this binding calls
+SURFEL_MAX_MAPS = 64       # RPE_SURFEL_MAX_MAPS: maps per rpe_surfel_*_many call
 ABI_VERSION = 5            # RPE_ABI_VERSION of include/rpe.h these struct mirrors were written against
 
 
@@ -111,6 +113,7 @@ class SurfelMapDesc(_c.Structure):
 
 
 _SMP = _c.POINTER(SurfelMapDesc)
+_P64, _P32, _PVP = _c.POINTER(_i64), _c.POINTER(_c.c_int32), _c.POINTER(_vp)
 
 # name -> (restype, argtypes); mirrors include/rpe.h one to one (the entry points of LIST_OPS: below, from their argument structs)
 SIGNATURES = {
@@ -124,6 +127,7 @@ SIGNATURES = {
     'rpe_se3_act': (_i, [_vp, _vp, _vp, _i64, _i64, _i, _vp]),
     'rpe_se3_chain': (_i, [_vp, _vp, _vp, _i64, _d, _i, _vp]),
     'rpe_pose_gate_chain': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _d, _d, _i, _vp]),
+    'rpe_pose_gate_chain_rows': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _d, _d, _i, _vp]),
     'rpe_pose_workspace_bytes': (_sz, [_i, _i, _i]),
     'rpe_pose_reduce': (_i, [_vp] * 10 + [_i, _i, _i, _i, _vp, _vp, _vp]),
     'rpe_pose_solve': (_i, [_vp] * 9 + [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -186,6 +190,11 @@ SIGNATURES = {
     'rpe_surfel_prune': (_i, [_SMP, _i64, _i, _i, _SMP, _vp, _vp]),
     'rpe_surfel_render': (_i, [_SMP, _i64, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     'rpe_surfel_transform': (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
+    'rpe_surfel_workspace_bytes_many': (_sz, [_i, _P64, _i, _i]),
+    'rpe_surfel_init_many': (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _PVP, _vp, _fl, _SMP, _vp, _vp]),
+    'rpe_surfel_render_many': (_i, [_i, _SMP, _P64, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'rpe_surfel_fuse_many': (_i, [_i, _SMP, _P64, _SMP, _P32, _P32, _i, _vp, _vp, _vp, _i, _i, _PVP, _PVP, _vp, _fl, _i, _i, _fl, _i, _vp,
+                                  _vp]),
 }
 SIGNATURES.update({entry: (_i, ([_c.POINTER(ConvDesc)] if st is ConvDesc else [t for _, t in st._fields_]) + [_vp]) for entry, st in LIST_OPS.values()})
 
@@ -221,8 +230,9 @@ def lib():
             fn.argtypes = args
         if L.rpe_abi_version() != ABI_VERSION:
             raise RpeError(f'{LIB_PATH} has ABI version {L.rpe_abi_version()}, this binding expects {ABI_VERSION} (struct layouts of include/rpe.h): rebuild')
-        if L.rpe_abi_minor() < ABI_MINOR:
-            raise RpeError(f'{LIB_PATH} has ABI minor {L.rpe_abi_minor()}, this binding calls entry points added in minor {ABI_MINOR}: rebuild')
+        if L.rpe_abi_minor() < max(ABI_MINOR, ABI_MINOR_MANY):
+            raise RpeError(f'{LIB_PATH} has ABI minor {L.rpe_abi_minor()}, this binding calls entry points added in minor '
+                           f'{max(ABI_MINOR, ABI_MINOR_MANY)}: rebuild')
         _lib = L
     return _lib
 

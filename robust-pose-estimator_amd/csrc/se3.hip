@@ -60,27 +60,36 @@ template <typename S> __global__ void k_chain(const S* rel, const S* init, S* ou
 // failure gate isnan(rel) | any(|log(rel)| > thr) -> identity, then the chain of k_chain.  The same device functions in the same
 // order as rpe_se3_log / _inv / _mul give (the dozen element-wise launches and two host synchronisations per frame this replaces
 // computed exactly that), so the poses are bit-identical to the step-by-step form.
+// One row of it: gate rel row k, store it (and its flag), chain it onto P.
+template <typename S> __device__ __forceinline__ void gate_step(const S* rel, S* rel_out, S* abs_out, int32_t* ok, int64_t k, S s, S thr, Pose<S>& P) {
+    const S* rv = rel + k * 7;
+    bool bad = false;
+#pragma unroll
+    for (int e = 0; e < 7; ++e) bad = bad || rv[e] != rv[e];
+    Pose<S> r = pose_load(rv);
+    V3<S> tau, phi;
+    op_log(r, tau, phi);
+    const S lg[6] = {tau.x, tau.y, tau.z, phi.x, phi.y, phi.z};
+#pragma unroll
+    for (int e = 0; e < 6; ++e) bad = bad || (lg[e] < 0 ? -lg[e] : lg[e]) > thr;        // (NaN compares false, like torch.abs(log) > thr)
+    if (bad) r = pose_identity<S>();
+    if (rel_out) pose_store(rel_out + k * 7, r);
+    if (ok) ok[k] = bad ? 0 : 1;
+    r.t = scale(r.t, s);                       // SE3.scale: translation * s (pose_estimator.py:90)
+    P = op_mul(P, op_inv(r));                  // pose_estimator.py:91
+    pose_store(abs_out + k * 7, P);
+}
 template <typename S> __global__ void k_gate_chain(const S* rel, const S* init, S* rel_out, S* abs_out, int32_t* ok, int64_t m, S s, S thr) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
     Pose<S> P = init ? pose_load(init) : pose_identity<S>();
-    for (int64_t k = 0; k < m; ++k) {
-        const S* rv = rel + k * 7;
-        bool bad = false;
-#pragma unroll
-        for (int e = 0; e < 7; ++e) bad = bad || rv[e] != rv[e];
-        Pose<S> r = pose_load(rv);
-        V3<S> tau, phi;
-        op_log(r, tau, phi);
-        const S lg[6] = {tau.x, tau.y, tau.z, phi.x, phi.y, phi.z};
-#pragma unroll
-        for (int e = 0; e < 6; ++e) bad = bad || (lg[e] < 0 ? -lg[e] : lg[e]) > thr;        // (NaN compares false, like torch.abs(log) > thr)
-        if (bad) r = pose_identity<S>();
-        if (rel_out) pose_store(rel_out + k * 7, r);
-        if (ok) ok[k] = bad ? 0 : 1;
-        r.t = scale(r.t, s);                       // SE3.scale: translation * s (pose_estimator.py:90)
-        P = op_mul(P, op_inv(r));                  // pose_estimator.py:91
-        pose_store(abs_out + k * 7, P);
-    }
+    for (int64_t k = 0; k < m; ++k) gate_step(rel, rel_out, abs_out, ok, k, s, thr, P);
+}
+// m independent sequences: row k onto init row k, one thread per row (each row is the m = 1 case of k_gate_chain)
+template <typename S> __global__ void k_gate_chain_rows(const S* rel, const S* init, S* rel_out, S* abs_out, int32_t* ok, int64_t m, S s, S thr) {
+    const int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (k >= m) return;
+    Pose<S> P = init ? pose_load(init + k * 7) : pose_identity<S>();
+    gate_step(rel, rel_out, abs_out, ok, k, s, thr, P);
 }
 
 extern "C" {
@@ -157,6 +166,19 @@ int rpe_pose_gate_chain(const void* rel, const void* init, void* rel_out, void* 
                                              (float*)abs_out, ok, m, (float)s, (float)thr);
     else if (dtype == RPE_F64) hipLaunchKernelGGL(k_gate_chain<double>, dim3(1), dim3(64), 0, st, (const double*)rel, (const double*)init, (double*)rel_out,
                                                   (double*)abs_out, ok, m, s, thr);
+    else return RPE_E_BADARG;
+    return rpe_check_launch();
+}
+int rpe_pose_gate_chain_rows(const void* rel, const void* init, void* rel_out, void* abs_out, int32_t* ok, int64_t m, double s, double thr,
+                             int dtype, void* stream) {
+    if (!rel || !abs_out || m < 0) return RPE_E_BADARG;
+    if (m == 0) return RPE_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const int blocks = ceil_div(m, 64);
+    if (dtype == RPE_F32) hipLaunchKernelGGL(k_gate_chain_rows<float>, dim3(blocks), dim3(64), 0, st, (const float*)rel, (const float*)init,
+                                             (float*)rel_out, (float*)abs_out, ok, m, (float)s, (float)thr);
+    else if (dtype == RPE_F64) hipLaunchKernelGGL(k_gate_chain_rows<double>, dim3(blocks), dim3(64), 0, st, (const double*)rel, (const double*)init,
+                                                  (double*)rel_out, (double*)abs_out, ok, m, s, thr);
     else return RPE_E_BADARG;
     return rpe_check_launch();
 }

@@ -11,6 +11,8 @@
 //   reproject  p = depth * (Kinv . (x + .5, y + .5, 1))          pinhole_transforms.py:79-87 (Kinv: torch.linalg.inv on the host)
 //   transform  R p + t, R p = p + w uv + v x uv, uv = 2 v x p    lietorch act (homogeneous w = 1 is exact)
 //   project    (K . p).xy / clamp((K . p).z, 1e-12)              pinhole_transforms.py:90-100 (clamp keeps NaN)
+#include <string.h>
+
 #include "rpe_common.h"
 #include "se3_device.h"
 
@@ -101,10 +103,12 @@ __device__ __forceinline__ bool keep_item(const CompactArgs &a, int64_t i, int64
     return prune_keep(a, new_conf(a, p), a.t_new);
 }
 
-__global__ void __launch_bounds__(kThreads) k_compact_count(CompactArgs a) {
+// The kernel bodies below take the block index within their map (blk): the single-map kernels pass blockIdx.x, the batched ones
+// (rpe_surfel_*_many) the block's offset inside its map's segment of the grid, so both run the same code per map.
+__device__ __forceinline__ void compact_count(const CompactArgs &a, int blk) {
     __shared__ int wsum[kThreads / RPE_WAVE];
     const int64_t n = src_count(a);
-    const int64_t base = (int64_t)blockIdx.x * kTile + threadIdx.x * kItems;
+    const int64_t base = (int64_t)blk * kTile + threadIdx.x * kItems;
     int c = 0;
 #pragma unroll
     for (int k = 0; k < kItems; ++k) c += keep_item(a, base + k, n);
@@ -114,13 +118,13 @@ __global__ void __launch_bounds__(kThreads) k_compact_count(CompactArgs a) {
     if (threadIdx.x == 0) {
         int s = 0;
         for (int k = 0; k < kThreads / RPE_WAVE; ++k) s += wsum[k];
-        a.block_counts[blockIdx.x] = s;
+        a.block_counts[blk] = s;
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0 && n > a.n_bound) atomicOr(a.dst.overflow, 2);      // the host bound was wrong: items lost
+    if (blk == 0 && threadIdx.x == 0 && n > a.n_bound) atomicOr(a.dst.overflow, 2);      // the host bound was wrong: items lost
 }
 
 // One block: exclusive scan of the block counts in place (sequential per thread, then across threads), total -> *dst.count.
-__global__ void __launch_bounds__(1024) k_compact_scan(CompactArgs a, int nblocks) {
+__device__ __forceinline__ void compact_scan(const CompactArgs &a, int nblocks) {
     __shared__ int64_t part[1024];
     const int t = threadIdx.x;
     const int per = (nblocks + 1023) / 1024;
@@ -140,10 +144,10 @@ __global__ void __launch_bounds__(1024) k_compact_scan(CompactArgs a, int nblock
     for (int b = lo; b < hi; ++b) { int64_t v = a.block_counts[b]; a.block_counts[b] = (int)min(run, (int64_t)INT32_MAX); run += v; }
 }
 
-__global__ void __launch_bounds__(kThreads) k_compact_scatter(CompactArgs a) {
+__device__ __forceinline__ void compact_scatter(const CompactArgs &a, int blk) {
     __shared__ int wsum[kThreads / RPE_WAVE];
     const int64_t n = src_count(a);
-    const int64_t base = (int64_t)blockIdx.x * kTile + threadIdx.x * kItems;
+    const int64_t base = (int64_t)blk * kTile + threadIdx.x * kItems;
     bool keep[kItems];
     int c = 0;
 #pragma unroll
@@ -160,7 +164,7 @@ __global__ void __launch_bounds__(kThreads) k_compact_scatter(CompactArgs a) {
     __syncthreads();
     int before = 0;
     for (int k = 0; k < wave; ++k) before += wsum[k];
-    int64_t j = (int64_t)a.block_counts[blockIdx.x] + before + inc - c;
+    int64_t j = (int64_t)a.block_counts[blk] + before + inc - c;
     const int hw = a.h * a.w;
     Pose<float> P;
     if (hw) P = pose_load(a.pose);
@@ -193,6 +197,10 @@ __global__ void __launch_bounds__(kThreads) k_compact_scatter(CompactArgs a) {
     }
 }
 
+__global__ void __launch_bounds__(kThreads) k_compact_count(CompactArgs a) { compact_count(a, blockIdx.x); }
+__global__ void __launch_bounds__(1024) k_compact_scan(CompactArgs a, int nblocks) { compact_scan(a, nblocks); }
+__global__ void __launch_bounds__(kThreads) k_compact_scatter(CompactArgs a) { compact_scatter(a, blockIdx.x); }
+
 int compact(CompactArgs a, int64_t items_bound, hipStream_t st) {
     const int64_t nb64 = (items_bound + kTile - 1) / kTile;
     if (nb64 > INT32_MAX / 2) return RPE_E_BADARG;
@@ -215,8 +223,8 @@ struct FuseArgs {
     int average;
 };
 
-__global__ void __launch_bounds__(kThreads) k_fuse_update(FuseArgs a, int64_t n_bound) {
-    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+__device__ __forceinline__ void fuse_update(const FuseArgs &a, int64_t n_bound, int blk) {
+    const int64_t i = (int64_t)blk * kThreads + threadIdx.x;
     if (i >= n_bound || i >= (int64_t)*a.m.count) return;
     const int64_t cap = a.m.cap;
     const Pose<float> P = pose_load(a.pose);
@@ -246,6 +254,8 @@ __global__ void __launch_bounds__(kThreads) k_fuse_update(FuseArgs a, int64_t n_
     a.matched[pix] = 1;                                              // :131-132 (every writer stores 1)
 }
 
+__global__ void __launch_bounds__(kThreads) k_fuse_update(FuseArgs a, int64_t n_bound) { fuse_update(a, n_bound, blockIdx.x); }
+
 // ------------------------------------------------------------------------------------------ render (surfel_map.py:230-264)
 struct RenderArgs {
     MapPtrs m;
@@ -259,8 +269,8 @@ struct RenderArgs {
     float gk[25];                // SparseImgInterpolator(5, 2, 0) kernel
 };
 
-__global__ void __launch_bounds__(kThreads) k_render_splat(RenderArgs a) {
-    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+__device__ __forceinline__ void render_splat(const RenderArgs &a, int blk) {
+    const int64_t i = (int64_t)blk * kThreads + threadIdx.x;
     if (i >= a.n_bound || i >= (int64_t)*a.m.count) return;
     float u, v;
     project(a.kmat, se3_act(pose_load(a.T), load_pt(a.m.opts, a.m.cap, i)), u, v);
@@ -270,6 +280,8 @@ __global__ void __launch_bounds__(kThreads) k_render_splat(RenderArgs a) {
     const unsigned long long key = ((unsigned long long)conf_key(a.m.conf[i]) << 32) | (unsigned long long)(uint32_t)i;
     atomicMax(a.keys + pix, key);
 }
+
+__global__ void __launch_bounds__(kThreads) k_render_splat(RenderArgs a) { render_splat(a, blockIdx.x); }
 
 // value of plane c (0..2 colour, 3 depth) at pixel pix before interpolation; NaN -> 0 (the interpolator's prior) when zero_nan
 __device__ __forceinline__ float rendered(const RenderArgs &a, int pix, int c, const Pose<float> &T) {
@@ -283,8 +295,8 @@ __device__ __forceinline__ float rendered(const RenderArgs &a, int pix, int c, c
 
 __device__ __forceinline__ int reflect(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * (n - 1) - i : i); }
 
-__global__ void __launch_bounds__(kThreads) k_render_resolve(RenderArgs a) {
-    const int pix = blockIdx.x * kThreads + threadIdx.x;
+__device__ __forceinline__ void render_resolve(const RenderArgs &a, int blk) {
+    const int pix = blk * kThreads + threadIdx.x;
     const int hw = a.h * a.w;
     if (pix >= hw) return;
     const Pose<float> T = pose_load(a.T);
@@ -310,6 +322,8 @@ __global__ void __launch_bounds__(kThreads) k_render_resolve(RenderArgs a) {
     }
 }
 
+__global__ void __launch_bounds__(kThreads) k_render_resolve(RenderArgs a) { render_resolve(a, blockIdx.x); }
+
 // ------------------------------------------------------------------------------------------ transform (surfel_map.py:205-219)
 __global__ void __launch_bounds__(kThreads) k_transform(const float *in, int64_t in_cap, float *out, int64_t out_cap, const int32_t *count,
                                                         int64_t n_bound, const float *T) {
@@ -333,6 +347,125 @@ void gauss_kernel(float *g) {
         for (int c = 0; c < 5; ++c) g[r * 5 + c] = (r == 2 && c == 2) ? 0.f : g1[r] * g1[c];
     for (int k = 0; k < 25; ++k) s += g[k];
     for (int k = 0; k < 25; ++k) g[k] /= s;
+}
+
+// ------------------------------------------------------------------------------------------ K maps per launch (rpe_surfel_*_many)
+// Each stage of the single-map calls becomes one launch over all maps.  The maps' argument structs (the single-map kernels' own:
+// CompactArgs, FuseArgs, RenderArgs) and the prefix of their block counts form a table at the head of the workspace, written there by
+// k_put launches that carry it by value: no host-to-device copy, so the calls stay graph-capturable.  A block of a per-surfel or
+// compaction kernel finds its map by binary search in the prefix and runs the single-map body with its block index inside the map's
+// segment of the grid: every map gets exactly the arithmetic, the counts and the order of the single-map call.
+constexpr int kMaxMaps = RPE_SURFEL_MAX_MAPS;
+
+struct ManyHead {
+    int nmaps;
+    int off_a[kMaxMaps + 1];     // per-surfel kernels (render splat, fuse update): prefix of the maps' block counts
+    int off_b[kMaxMaps + 1];     // compactions: prefix of the maps' block counts = the maps' segments of block_counts
+    int64_t bound[kMaxMaps];     // fuse update: n_bound of each map
+};
+
+constexpr size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
+constexpr size_t cmax(size_t a, size_t b) { return a > b ? a : b; }
+constexpr size_t kStageBytes = align16(sizeof(ManyHead)) + kMaxMaps * cmax(align16(sizeof(RenderArgs)), align16(sizeof(FuseArgs)) + align16(sizeof(CompactArgs))) + 64;
+constexpr size_t kTableBytes = (kStageBytes + 255) & ~(size_t)255;                  // the workspace's head; the single-map layouts follow
+
+// host image of the table; arrays are appended after the head at 16-byte alignment
+struct Staging {
+    alignas(16) unsigned char bytes[kStageBytes];
+    size_t used = align16(sizeof(ManyHead));
+    Staging() { memset(bytes, 0, used); }
+    ManyHead &head() { return *reinterpret_cast<ManyHead *>(bytes); }
+    template <typename T> size_t add(int n) {
+        const size_t at = align16(used);
+        used = at + sizeof(T) * (size_t)n;
+        return at;
+    }
+    template <typename T> T *at(size_t off) { return reinterpret_cast<T *>(bytes + off); }
+};
+
+constexpr int kPutWords = 256;                                 // 2 KiB of kernel arguments per k_put launch
+struct PutChunk { uint64_t w[kPutWords]; };
+
+__global__ void __launch_bounds__(kPutWords) k_put(uint64_t *dst, PutChunk c, int nwords) {
+    if ((int)threadIdx.x < nwords) dst[threadIdx.x] = c.w[threadIdx.x];
+}
+
+int put_table(const Staging &s, void *workspace, hipStream_t st) {
+    const size_t words = (s.used + 7) / 8;
+    const uint64_t *src = reinterpret_cast<const uint64_t *>(s.bytes);
+    for (size_t w0 = 0; w0 < words; w0 += kPutWords) {
+        PutChunk c;
+        const int nw = (int)(words - w0 < (size_t)kPutWords ? words - w0 : kPutWords);
+        memcpy(c.w, src + w0, sizeof(uint64_t) * nw);
+        hipLaunchKernelGGL(k_put, dim3(1), dim3(kPutWords), 0, st, (uint64_t *)workspace + w0, c, nw);
+    }
+    return rpe_check_launch();
+}
+
+// the map whose segment [off[k], off[k+1]) holds block b (empty segments are skipped)
+__device__ __forceinline__ int find_map(const int *off, int nmaps, int b) {
+    int lo = 0, hi = nmaps - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (off[mid + 1] <= b) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+__global__ void __launch_bounds__(kThreads) k_render_splat_many(const ManyHead *h, const RenderArgs *r) {
+    const int k = find_map(h->off_a, h->nmaps, blockIdx.x);
+    render_splat(r[k], blockIdx.x - h->off_a[k]);
+}
+__global__ void __launch_bounds__(kThreads) k_render_resolve_many(const RenderArgs *r) { render_resolve(r[blockIdx.y], blockIdx.x); }
+__global__ void __launch_bounds__(kThreads) k_fuse_update_many(const ManyHead *h, const FuseArgs *f) {
+    const int k = find_map(h->off_a, h->nmaps, blockIdx.x);
+    fuse_update(f[k], h->bound[k], blockIdx.x - h->off_a[k]);
+}
+__global__ void __launch_bounds__(kThreads) k_compact_count_many(const ManyHead *h, const CompactArgs *c) {
+    const int k = find_map(h->off_b, h->nmaps, blockIdx.x);
+    compact_count(c[k], blockIdx.x - h->off_b[k]);
+}
+// one workgroup per map segment
+__global__ void __launch_bounds__(1024) k_compact_scan_many(const ManyHead *h, const CompactArgs *c) {
+    compact_scan(c[blockIdx.x], h->off_b[blockIdx.x + 1] - h->off_b[blockIdx.x]);
+}
+__global__ void __launch_bounds__(kThreads) k_compact_scatter_many(const ManyHead *h, const CompactArgs *c) {
+    const int k = find_map(h->off_b, h->nmaps, blockIdx.x);
+    compact_scatter(c[k], blockIdx.x - h->off_b[k]);
+}
+
+// the compaction blocks of a map with items_bound items (compact()'s count); false when the grid would be too large
+bool compact_blocks(int64_t items_bound, int64_t &total, int &nb) {
+    const int64_t nb64 = (items_bound + kTile - 1) / kTile;
+    nb = (int)(nb64 > 0 ? (nb64 < INT32_MAX / 2 ? nb64 : INT32_MAX / 2) : 1);
+    total += nb;
+    return nb64 <= INT32_MAX / 2 && total <= INT32_MAX / 2;
+}
+
+int compact_many(Staging &s, size_t cmp_at, void *workspace, hipStream_t st) {
+    const ManyHead &hd = s.head();
+    const int nmaps = hd.nmaps, total = hd.off_b[nmaps];
+    const ManyHead *h = (const ManyHead *)workspace;
+    const CompactArgs *c = (const CompactArgs *)((char *)workspace + cmp_at);
+    hipLaunchKernelGGL(k_compact_count_many, dim3(total), dim3(kThreads), 0, st, h, c);
+    hipLaunchKernelGGL(k_compact_scan_many, dim3(nmaps), dim3(1024), 0, st, h, c);
+    hipLaunchKernelGGL(k_compact_scatter_many, dim3(total), dim3(kThreads), 0, st, h, c);
+    return rpe_check_launch();
+}
+
+// no two of the n maps share storage (the batched kernels of one launch would race on it)
+bool maps_disjoint(const rpe_surfel_map *a, const rpe_surfel_map *b, int n) {
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) {
+            const rpe_surfel_map *x[2] = {&a[i], b ? &b[i] : nullptr}, *y[2] = {&a[j], b ? &b[j] : nullptr};
+            for (int p = 0; p < 2; ++p)
+                for (int q = 0; q < 2; ++q) {
+                    if (!x[p] || !y[q] || (i == j && p == q)) continue;
+                    if (x[p]->opts == y[q]->opts || x[p]->count == y[q]->count) return false;
+                }
+        }
+    return true;
 }
 
 }  // namespace
@@ -426,6 +559,150 @@ int rpe_surfel_transform(const float *opts_in, int64_t in_cap, float *opts_out, 
     if (n_bound == 0) return RPE_OK;
     hipLaunchKernelGGL(k_transform, dim3(ceil_div(n_bound, kThreads)), dim3(kThreads), 0, (hipStream_t)stream, opts_in, in_cap, opts_out,
                        out_cap, count, n_bound, T);
+    return rpe_check_launch();
+}
+
+size_t rpe_surfel_workspace_bytes_many(int nmaps, const int64_t *n_bounds, int h, int w) {
+    if (nmaps <= 0 || nmaps > kMaxMaps || !n_bounds) return 0;
+    size_t s = kTableBytes;
+    for (int k = 0; k < nmaps; ++k) {
+        const size_t b = rpe_surfel_workspace_bytes(n_bounds[k], h, w);
+        if (!b) return 0;
+        s += b;
+    }
+    return s;
+}
+
+int rpe_surfel_init_many(int nmaps, const float *depth, const float *img, const uint8_t *mask, const float *confidence, int h, int w,
+                         const float *const *kinv, const float *pmat, float conf_thr, const rpe_surfel_map *dst, void *workspace,
+                         void *stream) {
+    if (nmaps < 0 || nmaps > kMaxMaps) return RPE_E_BADARG;
+    if (nmaps == 0) return RPE_OK;
+    if (!depth || !img || !mask || !confidence || !kinv || !pmat || !dst || !workspace || h <= 0 || w <= 0) return RPE_E_BADARG;
+    if ((int64_t)h * w > INT32_MAX / 2) return RPE_E_BADARG;
+    for (int k = 0; k < nmaps; ++k)
+        if (!kinv[k] || !map_ok(&dst[k])) return RPE_E_BADARG;
+    if (!maps_disjoint(dst, nullptr, nmaps)) return RPE_E_BADARG;
+    const int64_t hw = (int64_t)h * w;
+    Staging s;
+    ManyHead &hd = s.head();
+    hd.nmaps = nmaps;
+    const size_t cmp_at = s.add<CompactArgs>(nmaps);
+    CompactArgs *c = s.at<CompactArgs>(cmp_at);
+    int *block_counts = (int *)((char *)workspace + kTableBytes);
+    int64_t total = 0;
+    hd.off_b[0] = 0;
+    for (int k = 0; k < nmaps; ++k) {
+        int nb;
+        if (!compact_blocks(hw, total, nb)) return RPE_E_BADARG;
+        hd.off_b[k + 1] = (int)total;
+        CompactArgs a = {};
+        a.dst = map_ptrs(&dst[k]);
+        a.depth = depth + k * hw; a.img = img + 3 * k * hw; a.confidence = confidence + k * hw; a.mask = mask + k * hw; a.matched = nullptr;
+        a.h = h; a.w = w; a.kinv = kinv[k]; a.pose = pmat + 7 * k; a.conf_thr = conf_thr; a.t_new = 0.f; a.prune = 0;
+        a.block_counts = block_counts + hd.off_b[k];
+        c[k] = a;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (put_table(s, workspace, st) != RPE_OK) return RPE_E_LAUNCH;
+    return compact_many(s, cmp_at, workspace, st);
+}
+
+int rpe_surfel_fuse_many(int nmaps, const rpe_surfel_map *src, const int64_t *n_bounds, const rpe_surfel_map *dst, const int32_t *ticks,
+                         const int32_t *rows, int batch, const float *depth, const float *img, const uint8_t *mask, int h, int w,
+                         const float *const *kmat, const float *const *kinv, const float *pose, float d_thresh, int average_pts, int upscale,
+                         float conf_thr, int t_max, void *workspace, void *stream) {
+    if (nmaps < 0 || nmaps > kMaxMaps) return RPE_E_BADARG;
+    if (nmaps == 0) return RPE_OK;
+    if (!src || !n_bounds || !dst || !ticks || !rows || !depth || !img || !mask || !kmat || !kinv || !pose || !workspace || batch <= 0 ||
+        h <= 0 || w <= 0 || (int64_t)h * w > INT32_MAX / 2)
+        return RPE_E_BADARG;
+    for (int k = 0; k < nmaps; ++k)
+        if (!map_ok(&src[k]) || !map_ok(&dst[k]) || n_bounds[k] < 0 || n_bounds[k] > src[k].cap || rows[k] < 0 || rows[k] >= batch ||
+            !kmat[k] || !kinv[k])
+            return RPE_E_BADARG;
+    if (!maps_disjoint(src, dst, nmaps)) return RPE_E_BADARG;
+    if (upscale != 1) return RPE_E_UNSUPPORTED;
+    const int64_t hw = (int64_t)h * w;
+    Staging s;
+    ManyHead &hd = s.head();
+    hd.nmaps = nmaps;
+    const size_t upd_at = s.add<FuseArgs>(nmaps), cmp_at = s.add<CompactArgs>(nmaps);
+    FuseArgs *f = s.at<FuseArgs>(upd_at);
+    CompactArgs *c = s.at<CompactArgs>(cmp_at);
+    uint8_t *matched = (uint8_t *)workspace + kTableBytes;
+    int *block_counts = (int *)(matched + align256((size_t)(nmaps * hw)));
+    const float ccor = 1.0f / conf_thr;                              // torch.ones_like(depth) / conf_thr
+    int64_t total_a = 0, total_b = 0;
+    hd.off_a[0] = hd.off_b[0] = 0;
+    for (int k = 0; k < nmaps; ++k) {
+        const int64_t r = rows[k], nbd = n_bounds[k];
+        total_a += ceil_div(nbd, kThreads);
+        int nb;
+        if (total_a > INT32_MAX / 2 || !compact_blocks(nbd + hw, total_b, nb)) return RPE_E_BADARG;
+        hd.off_a[k + 1] = (int)total_a;
+        hd.off_b[k + 1] = (int)total_b;
+        hd.bound[k] = nbd;
+        FuseArgs u = {};
+        u.m = map_ptrs(&src[k]);
+        u.depth = depth + r * hw; u.img = img + 3 * r * hw; u.mask = mask + r * hw; u.matched = matched + k * hw; u.h = h; u.w = w;
+        u.kmat = kmat[k]; u.kinv = kinv[k]; u.pose = pose + 7 * r; u.d_thresh = d_thresh; u.ccor = ccor; u.average = average_pts;
+        f[k] = u;
+        CompactArgs a = {};
+        a.src = map_ptrs(&src[k]); a.dst = map_ptrs(&dst[k]); a.n_bound = nbd;
+        a.depth = u.depth; a.img = u.img; a.confidence = nullptr; a.mask = u.mask; a.matched = u.matched;
+        a.h = h; a.w = w; a.kinv = kinv[k]; a.pose = u.pose; a.conf_thr = conf_thr; a.t_new = (float)ticks[k];
+        a.prune = 1; a.tick = (float)(ticks[k] + 1); a.t_max = (float)t_max;          // :147 tick += 1, then :150-158
+        a.block_counts = block_counts + hd.off_b[k];
+        c[k] = a;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (put_table(s, workspace, st) != RPE_OK) return RPE_E_LAUNCH;
+    if (hipMemsetAsync(matched, 0, (size_t)(nmaps * hw), st) != hipSuccess) return RPE_E_LAUNCH;
+    if (total_a > 0)
+        hipLaunchKernelGGL(k_fuse_update_many, dim3((int)total_a), dim3(kThreads), 0, st, (const ManyHead *)workspace,
+                           (const FuseArgs *)((char *)workspace + upd_at));
+    return compact_many(s, cmp_at, workspace, st);
+}
+
+int rpe_surfel_render_many(int nmaps, const rpe_surfel_map *maps, const int64_t *n_bounds, const float *kmat, const float *T,
+                           int depth_transformed, int h, int w, float *img, float *depth, float *confidence, uint8_t *mask, void *workspace,
+                           void *stream) {
+    if (nmaps < 0 || nmaps > kMaxMaps) return RPE_E_BADARG;
+    if (nmaps == 0) return RPE_OK;
+    if (!maps || !n_bounds || !kmat || !T || !img || !depth || !confidence || !mask || !workspace || h < 3 || w < 3 ||
+        (int64_t)h * w > INT32_MAX / 2)
+        return RPE_E_BADARG;
+    for (int k = 0; k < nmaps; ++k)
+        if (!map_ok(&maps[k]) || n_bounds[k] < 0 || n_bounds[k] > maps[k].cap) return RPE_E_BADARG;
+    const int64_t hw = (int64_t)h * w;
+    Staging s;
+    ManyHead &hd = s.head();
+    hd.nmaps = nmaps;
+    const size_t ren_at = s.add<RenderArgs>(nmaps);
+    RenderArgs *r = s.at<RenderArgs>(ren_at);
+    unsigned long long *keys = (unsigned long long *)((char *)workspace + kTableBytes);
+    float gk[25];
+    gauss_kernel(gk);
+    int64_t total = 0;
+    hd.off_a[0] = 0;
+    for (int k = 0; k < nmaps; ++k) {
+        total += ceil_div(n_bounds[k], kThreads);
+        if (total > INT32_MAX / 2) return RPE_E_BADARG;
+        hd.off_a[k + 1] = (int)total;
+        RenderArgs a = {};
+        a.m = map_ptrs(&maps[k]); a.n_bound = n_bounds[k]; a.kmat = kmat + 9 * k; a.T = T + 7 * k; a.depth_transformed = depth_transformed ? 1 : 0;
+        a.h = h; a.w = w; a.keys = keys + k * hw;
+        a.img = img + 3 * k * hw; a.depth = depth + k * hw; a.confidence = confidence + k * hw; a.mask = mask + k * hw;
+        memcpy(a.gk, gk, sizeof(gk));
+        r[k] = a;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (put_table(s, workspace, st) != RPE_OK) return RPE_E_LAUNCH;
+    if (hipMemsetAsync(keys, 0, (size_t)(nmaps * hw) * sizeof(unsigned long long), st) != hipSuccess) return RPE_E_LAUNCH;
+    const RenderArgs *rd = (const RenderArgs *)((char *)workspace + ren_at);
+    if (total > 0) hipLaunchKernelGGL(k_render_splat_many, dim3((int)total), dim3(kThreads), 0, st, (const ManyHead *)workspace, rd);
+    hipLaunchKernelGGL(k_render_resolve_many, dim3(ceil_div(hw, kThreads), nmaps), dim3(kThreads), 0, st, rd);
     return rpe_check_launch();
 }
 

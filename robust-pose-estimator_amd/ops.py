@@ -270,6 +270,20 @@ def pose_gate_chain(rel, init, scale, thr=0.1):
     return rel_out, abs_out, ok
 
 
+def pose_gate_chain_rows(rel, init, scale, thr=0.1):
+    """rpe_pose_gate_chain_rows: the gate and chain of ``pose_gate_chain`` for m independent sequences in one launch, row k of rel (m,7)
+    onto row k of init (m,7).  Row k's bits are those of ``pose_gate_chain(rel[k], init[k], ...)``.  Returns (rel_out, abs_out, ok)."""
+    rel = _dev(rel.reshape(-1, 7), None, 'rel')
+    init = _dev(init.reshape(-1, 7), rel.dtype, 'init') if init is not None else None
+    if init is not None and init.shape[0] != rel.shape[0]:
+        raise _lib.RpeError(f'pose_gate_chain_rows: {rel.shape[0]} relative poses, {init.shape[0]} initial poses')
+    rel_out, abs_out = torch.empty_like(rel), torch.empty_like(rel)
+    ok = torch.empty(rel.shape[0], dtype=torch.int32, device=rel.device)
+    check(lib().rpe_pose_gate_chain_rows(ptr(rel), ptr(init), ptr(rel_out), ptr(abs_out), ptr(ok), rel.shape[0], float(scale), float(thr),
+                                         _DT[rel.dtype], stream_ptr()), 'rpe_pose_gate_chain_rows')
+    return rel_out, abs_out, ok
+
+
 # ------------------------------------------------------------------------------------------------- pose layer
 def _pose_inputs(flow, pcl1, pcl2, w1, w2, mask1, mask2, K, loss_weight):
     f32 = torch.float32

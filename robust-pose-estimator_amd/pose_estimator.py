@@ -290,6 +290,133 @@ class SurfelPoseEstimator(PoseEstimator):
         return SE3(rel.data.reshape(1, 7)), model_frame, flow, weights
 
 
+class MultiSurfelPoseEstimator(PoseEstimator):
+    """K independent frame-to-model sequences advanced in lockstep (e.g. the (start, end) scenarios of the reference's
+    scripts/benchmark_test.py): ``forward(limgs, rimgs, masks, rows)`` moves every listed sequence on by one frame with one batched
+    network pass, one render and one fuse launch chain over all maps, and ONE host synchronisation for all success flags.  Sequence k
+    gets bit for bit what a ``SurfelPoseEstimator`` fed its frames alone gets -- poses, success flags and map -- whichever rows share
+    the batch: every kernel computes a row independently of its batch, the solve runs with ``partition_rows = 1`` (its launch-per-
+    evaluation route when the rows do not all fit on the chip at once, bit-identical) and the map kernels are the single-map ones.
+    intrinsics (K,3,3), baselines (K,), init_poses (K,7) (SE3 or tensor; default identity).  State per sequence: ``last_pose[k]``,
+    ``success[k]``, ``scenes[k]`` (None until its first frame)."""
+    _f2m = True
+
+    def __init__(self, config, intrinsics, baselines, checkpoint, img_shape, init_poses=None):
+        from ._lib import SURFEL_MAX_MAPS
+        if config.get('frame2frame', True):
+            raise ValueError('MultiSurfelPoseEstimator is frame-to-model tracking (frame2frame: False); frame-to-frame tracking already '
+                             'batches the frames of one sequence: PoseEstimator.forward_chunk')
+        intrinsics = torch.as_tensor(intrinsics)
+        baselines = torch.as_tensor(baselines)
+        if intrinsics.ndim != 3 or tuple(intrinsics.shape[1:]) != (3, 3):
+            raise ValueError(f'MultiSurfelPoseEstimator: intrinsics must be (K,3,3), got {tuple(intrinsics.shape)}')
+        n = intrinsics.shape[0]
+        if baselines.shape != (n,):
+            raise ValueError(f'MultiSurfelPoseEstimator: {n} intrinsics need baselines of shape ({n},), got {tuple(baselines.shape)}')
+        if init_poses is not None:
+            init_poses = (init_poses.data if hasattr(init_poses, 'data') and not isinstance(init_poses, torch.Tensor) else init_poses)
+            if tuple(init_poses.shape) != (n, 7):
+                raise ValueError(f'MultiSurfelPoseEstimator: {n} sequences need init_poses of shape ({n}, 7), got {tuple(init_poses.shape)}')
+        if not 1 <= n <= SURFEL_MAX_MAPS:
+            raise ValueError(f'MultiSurfelPoseEstimator: 1 to {SURFEL_MAX_MAPS} sequences (RPE_SURFEL_MAX_MAPS), got {n}')
+        super().__init__(config, intrinsics[0], 0.0, checkpoint, img_shape)
+        self.intrinsics = intrinsics.float()                              # (K,3,3): the buffer PoseEstimator registered, per sequence
+        self.baseline = baselines.float()                                 # (K,): torch.tensor(b).float() of each single tracker
+        self.n_seq = n
+        self._init_poses = None if init_poses is None else init_poses.float()
+        self.reset()
+
+    def _init_pose_of(self, k):
+        return SE3.Identity(1) if self._init_poses is None else SE3(self._init_poses[k:k + 1])
+
+    def reset(self, rows=None):
+        """Forget sequences ``rows`` (default: all): each restarts at its initial pose with no map."""
+        if rows is None:
+            self.last_pose = [None] * self.n_seq
+            self.success = [True] * self.n_seq
+            self.scenes = [None] * self.n_seq
+            rows = range(self.n_seq)
+        for k in rows:
+            self.last_pose[k] = self._init_pose_of(k)
+            self.success[k] = True
+            self.scenes[k] = None
+        return self
+
+    def submit(self, *a, **k):
+        raise RuntimeError('MultiSurfelPoseEstimator: frame t+1 is tracked against the map frame t fused, so frames cannot be pipelined')
+
+    def forward_chunk(self, *a, **k):
+        raise RuntimeError('MultiSurfelPoseEstimator: frame t+1 is tracked against the map frame t fused, so frames cannot be chunked; '
+                           'it batches sequences instead (forward with rows=)')
+
+    @torch.no_grad()
+    def forward(self, limgs, rimgs, masks, rows=None):
+        """One frame of each sequence in ``rows`` (default: all, in order): limgs, rimgs (R,3,h,w) 0..255, masks (R,1,h,w) True = valid,
+        row j of the inputs belonging to sequence rows[j].  Returns (absolute poses SE3 (R,7), success (R,) bool on the host, the R
+        maps, flow (R,2,h,w), weights)."""
+        from . import surfel_map
+        rows = list(range(self.n_seq)) if rows is None else [int(k) for k in rows]
+        R = len(rows)
+        if R == 0 or len(set(rows)) != R or any(k < 0 or k >= self.n_seq for k in rows):
+            raise ValueError(f'MultiSurfelPoseEstimator.forward: rows must be distinct sequence indices in [0, {self.n_seq}), got {rows}')
+        if limgs.shape[0] != R or rimgs.shape[0] != R or masks.shape[0] != R:
+            raise ValueError(f'MultiSurfelPoseEstimator.forward: {R} rows need {R} images and masks, got {limgs.shape[0]}, '
+                             f'{rimgs.shape[0]}, {masks.shape[0]}')
+        dev = limgs.device
+        limgs, rimgs = limgs.contiguous(), rimgs.contiguous()
+        masks = masks.bool()                                               # (a bool mask is the caller's tensor, as Frame keeps it)
+        for k in rows:
+            self.last_pose[k] = self.last_pose[k].to(dev)
+        every = rows == list(range(self.n_seq))                            # (device slices, not an index tensor: no blocking host copy)
+        K = self.intrinsics if every else torch.cat([self.intrinsics[k:k + 1] for k in rows])
+        baseline = (self.baseline if every else torch.cat([self.baseline[k:k + 1] for k in rows])) * self.scale
+        new = [j for j, k in enumerate(rows) if self.scenes[k] is None]
+        if new:                                                            # :56-65 for every sequence that starts here
+            sub = new if len(new) < R else None
+            pick = (lambda t: torch.cat([t[j:j + 1] for j in sub])) if sub is not None else (lambda t: t)
+            depth, stereo_flow, valid = self.model.flow2depth(pick(limgs), pick(rimgs), pick(baseline))
+            if sub is None:
+                masks &= valid
+                m_new = masks
+            else:
+                m_new = pick(masks) & valid
+                for i, j in enumerate(sub):
+                    masks[j:j + 1] = m_new[i:i + 1]
+            pm = torch.cat([self.last_pose[rows[j]].data.reshape(1, 7) for j in new])
+            maps = surfel_map.init_many(Frame(pick(limgs), pick(rimgs), depth=depth / self.scale, mask=m_new), pick(K), pm, upscale=1,
+                                        d_thresh=self.config['dist_thr'], average_pts=self.config['average_pts'])
+            for j, m in zip(new, maps):
+                self.scenes[rows[j]] = m
+        # :127-150 for every row: the maps rendered at the last camera poses, straight into the network's input rows
+        last = torch.cat([self.last_pose[k].data.reshape(1, 7) for k in rows])
+        model = surfel_map.render_many([self.scenes[k] for k in rows], K, ops.se3_inv(last))
+        problem = getattr(getattr(self.model, 'pose_head', None), 'problem', None)
+        keep = problem.partition_rows if problem is not None else None
+        if problem is not None:
+            problem.partition_rows = 1                                     # a row's solve as if alone (PoseNet.infer_chunk does the same)
+        try:
+            rel, depth1, depth2, weights, flow, stereo_flow = self.model.infer(
+                model.img, limgs, K, baseline, depth1=model.depth * self.scale, image2r=rimgs, mask1=model.mask, mask2=masks,
+                stereo_flow1=model.flow, ret_details=True)
+        finally:
+            if problem is not None:
+                problem.partition_rows = keep
+        rel_g, pose, ok = ops.pose_gate_chain_rows(rel.data.reshape(R, 7), last, self._inv_scale, 1.0e-1)     # :81-91, row by row
+        self.t_enqueued = time.perf_counter()
+        okh = ok.cpu().bool()                                              # the lockstep frame's one host synchronisation
+        for j, k in enumerate(rows):
+            self.success[k] = bool(okh[j])
+            if not self.success[k]:
+                warnings.warn('pose estimation not converged, skip.', RuntimeWarning)
+            self.last_pose[k] = SE3(pose[j:j + 1])
+        self.last_rel_poses = rel_g
+        passed = [j for j in range(R) if okh[j]]
+        if passed:                                                         # :94-95
+            surfel_map.fuse_many([self.scenes[rows[j]] for j in passed], Frame(limgs, rimgs, depth=depth2 / self.scale, mask=masks),
+                                 pose, rows=passed)
+        return SE3(pose), okh, [self.scenes[k] for k in rows], flow, weights
+
+
 def from_config(config, intrinsics, baseline, checkpoint, img_shape, init_pose=None):
     """The tracker the config asks for (scripts/infer_trajectory.py:50-51): PoseEstimator for frame2frame True, SurfelPoseEstimator for False."""
     cls = PoseEstimator if config.get('frame2frame', True) else SurfelPoseEstimator

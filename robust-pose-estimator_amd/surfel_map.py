@@ -10,11 +10,16 @@ overflow).  The compactions of fuse / prune read one buffer and write the other 
 an upper bound of the count (+ h*w per fuse); only when that bound would pass the capacity does it read the true count (one host
 synchronisation) and, if needed, grow both buffers geometrically.  The ``opts`` / ``rgb`` / ``conf`` / ``t_created`` properties are
 ``[:, :n]`` views and read the count (a synchronisation): they are for callers, not for the per-frame path.
+
+``init_many`` / ``render_many`` / ``fuse_many`` run the same operations over K maps (several sequences tracked side by side) with one
+launch per stage; every map stays a full SurfelMap and ends bit for bit as the single-map call leaves it.
 """
+import ctypes
+
 import numpy as np
 import torch
 
-from ._lib import RpeError, SurfelMapDesc, check, lib, ptr, stream_ptr
+from ._lib import SURFEL_MAX_MAPS, RpeError, SurfelMapDesc, check, lib, ptr, stream_ptr
 from .se3 import SE3
 
 _ROWS = 8
@@ -46,14 +51,7 @@ def write_ply(pts, rgb, path):
 class SurfelMap:
     def __init__(self, frame=None, kmat=None, pmat=None, d_thresh=100.0, average_pts=True, upscale=1, conf_thr=7, t_max=15,
                  depth_scale=1.0, opts=None, rgb=None, conf=None, img_shape=None, ignore_mask=False, capacity=None):
-        if upscale != 1:
-            raise NotImplementedError('SurfelMap: only upscale == 1 is supported (super-sampled fusion is not built)')
-        if kmat is None:
-            raise RpeError('SurfelMap: kmat is required')
-        self.pmat = SE3.Identity(1) if pmat is None else pmat
-        self.conf_thr, self.t_max, self.upscale, self.d_thresh = conf_thr, t_max, upscale, d_thresh
-        self.depth_scale, self.average_points = depth_scale, average_pts
-        self.tick = 0
+        self._configure(kmat, pmat, d_thresh, average_pts, upscale, conf_thr, t_max, depth_scale)
         if opts is not None:
             if rgb is None:
                 raise RpeError('SurfelMap: opts= needs rgb=')
@@ -88,6 +86,16 @@ class SurfelMap:
             check(lib().rpe_surfel_init(ptr(depth), ptr(img), ptr(mask), ptr(confidence), h, w, ptr(self._kinv), ptr(pm), float(conf_thr),
                                         self._desc(self._cur), ptr(ws), stream_ptr()), 'rpe_surfel_init')
             self._n_ub = h * w
+
+    def _configure(self, kmat, pmat, d_thresh, average_pts, upscale, conf_thr, t_max, depth_scale):
+        if upscale != 1:
+            raise NotImplementedError('SurfelMap: only upscale == 1 is supported (super-sampled fusion is not built)')
+        if kmat is None:
+            raise RpeError('SurfelMap: kmat is required')
+        self.pmat = SE3.Identity(1) if pmat is None else pmat
+        self.conf_thr, self.t_max, self.upscale, self.d_thresh = conf_thr, t_max, upscale, d_thresh
+        self.depth_scale, self.average_points = depth_scale, average_pts
+        self.tick = 0
 
     # ------------------------------------------------------------------------------------------------ storage
     def _setup(self, kmat, dev, cap):
@@ -268,3 +276,137 @@ class SurfelMap:
         self.device = dev
         return self
 
+
+# ---------------------------------------------------------------------------------------------------- K maps per launch
+# Several sequences tracked side by side (pose_estimator.MultiSurfelPoseEstimator): the rpe_surfel_*_many entry points run each stage
+# once over all maps, and map k ends bit for bit as the single-map method leaves it.  Each map stays a full SurfelMap.
+
+def _descs(descs):
+    return (SurfelMapDesc * len(descs))(*descs)
+
+
+def _ws_many(n_bounds, h, w, dev):
+    nb = (ctypes.c_int64 * len(n_bounds))(*n_bounds)
+    size = int(lib().rpe_surfel_workspace_bytes_many(len(n_bounds), nb, h, w))
+    if size <= 0:
+        raise RpeError(f'rpe_surfel_workspace_bytes_many: bad arguments ({len(n_bounds)} maps, {h}x{w})')
+    return nb, torch.empty(size, dtype=torch.uint8, device=dev)
+
+
+def _check_count(maps, what):
+    if len(maps) > SURFEL_MAX_MAPS:
+        raise RpeError(f'{what}: {len(maps)} maps, at most {SURFEL_MAX_MAPS} per call (RPE_SURFEL_MAX_MAPS)')
+
+
+def _check_rows(frames, n, h, w, what, names=('img', 'depth', 'mask')):
+    for name, c in (('img', 3), ('depth', 1), ('mask', 1), ('confidence', 1)):
+        if name in names and getattr(frames, name).numel() != n * c * h * w:
+            raise RpeError(f'{what}: frames.{name} {tuple(getattr(frames, name).shape)} is not ({n},{c},{h},{w})')
+
+
+@torch.no_grad()
+def init_many(frames, kmats, pmats, d_thresh=100.0, average_pts=True, upscale=1, conf_thr=7, t_max=15, depth_scale=1.0, ignore_mask=False,
+              capacity=None):
+    """``[SurfelMap(frame=row k of frames, kmat=kmats[k], pmat=SE3(pmats[k]), ...) for k]`` with one launch per stage: frames is a Frame
+    of K rows, kmats (K,3,3), pmats (K,7) (SE3 or tensor).  Returns the K maps."""
+    n = frames.img.shape[0]
+    h, w = (int(v) for v in frames.shape)
+    dev = frames.depth.device
+    pm = (pmats.data if isinstance(pmats, SE3) else pmats).reshape(n, 7)
+    maps = []
+    for k in range(n):
+        m = SurfelMap.__new__(SurfelMap)
+        m._configure(kmats[k], SE3(pm[k:k + 1]), d_thresh, average_pts, upscale, conf_thr, t_max, depth_scale)
+        m.img_shape = (h, w)
+        m._setup(kmats[k], dev, max(h * w, capacity or 0, 1))
+        m._n_ub = h * w
+        maps.append(m)
+    if n == 0:
+        return maps
+    _check_count(maps, 'init_many')
+    _check_rows(frames, n, h, w, 'init_many', ('img', 'depth', 'mask', 'confidence'))
+    mask = torch.ones((n, 1, h, w), dtype=torch.bool, device=dev) if ignore_mask else frames.mask.reshape(n, 1, h, w).bool().contiguous()
+    depth, img = _f32(frames.depth, 'depth', dev), _f32(frames.img, 'img', dev)
+    confidence = _f32(frames.confidence, 'confidence', dev)
+    pmf = pm.to(device=dev, dtype=torch.float32).contiguous()
+    kinv = (ctypes.c_void_p * n)(*[m._kinv.data_ptr() for m in maps])
+    _, ws = _ws_many([0] * n, h, w, dev)
+    check(lib().rpe_surfel_init_many(n, ptr(depth), ptr(img), ptr(mask), ptr(confidence), h, w, kinv, ptr(pmf), float(conf_thr),
+                                     _descs([m._desc(m._cur) for m in maps]), ptr(ws), stream_ptr()), 'rpe_surfel_init_many')
+    return maps
+
+
+@torch.no_grad()
+def render_many(maps, Ks, Ts, out=None, depth_transformed=True):
+    """``maps[k].render_transformed(Ks[k], Ts[k])`` for every k in one splat and one resolve launch (``depth_transformed=False``:
+    ``render(Ks[k], Ts[k])``).  Ks (K,3,3), Ts (K,7) (SE3 or tensor); the maps share one image shape.  The outputs are the rows of
+    batch tensors -- img (K,3,h,w), depth / confidence (K,1,h,w), mask (K,1,h,w) bool -- or of ``out`` = (img, depth, confidence, mask)
+    when given.  Returns a Frame of K rows."""
+    from .pose_estimator import Frame
+    n = len(maps)
+    if n == 0:
+        raise RpeError('render_many: no maps')
+    _check_count(maps, 'render_many')
+    shapes = {m.img_shape for m in maps}
+    if len(shapes) != 1 or None in shapes:
+        raise RpeError(f'render_many: the maps must share one image shape, got {sorted(map(str, shapes))}')
+    h, w = shapes.pop()
+    dev = maps[0].device
+    K = Ks.reshape(n, 3, 3).to(device=dev, dtype=torch.float32).contiguous()
+    T = (Ts.data if isinstance(Ts, SE3) else Ts).reshape(n, 7).to(device=dev, dtype=torch.float32).contiguous()
+    if out is None:
+        out = (torch.empty(n, 3, h, w, device=dev), torch.empty(n, 1, h, w, device=dev), torch.empty(n, 1, h, w, device=dev),
+               torch.empty(n, 1, h, w, dtype=torch.bool, device=dev))
+    img, depth, confidence, mask = out
+    for t, c, dt in ((img, 3, torch.float32), (depth, 1, torch.float32), (confidence, 1, torch.float32), (mask, 1, torch.bool)):
+        if tuple(t.shape) != (n, c, h, w) or t.dtype != dt or not t.is_contiguous() or t.device != dev:
+            raise RpeError(f'render_many: output {tuple(t.shape)} {t.dtype} must be a contiguous ({n},{c},{h},{w}) {dt} tensor on {dev}')
+    nb, ws = _ws_many([m._n_ub for m in maps], h, w, dev)
+    check(lib().rpe_surfel_render_many(n, _descs([m._desc(m._cur) for m in maps]), nb, ptr(K), ptr(T), int(bool(depth_transformed)), h, w,
+                                       ptr(img), ptr(depth), ptr(confidence), ptr(mask), ptr(ws), stream_ptr()), 'rpe_surfel_render_many')
+    return Frame(img, depth=depth, mask=mask, confidence=confidence)
+
+
+@torch.no_grad()
+def fuse_many(maps, frames, poses, rows=None):
+    """``maps[j].fuse(row rows[j] of frames, row rows[j] of poses)`` for every j, one launch per stage (update, block counts, scan,
+    scatter): frames is a Frame of B rows, poses (B,7) (SE3 or tensor), rows defaults to 0..len(maps)-1.  The maps may differ in size
+    and capacity but share d_thresh, average_pts, conf_thr and t_max; each first grows as its own fuse would (``_grow_for``), then
+    flips its ping-pong buffer and advances its tick."""
+    n = len(maps)
+    if n == 0:
+        return
+    _check_count(maps, 'fuse_many')
+    rows = list(range(n)) if rows is None else [int(r) for r in rows]
+    B = frames.img.shape[0]
+    h, w = (int(v) for v in frames.shape)
+    if len(rows) != n or any(r < 0 or r >= B for r in rows):
+        raise RpeError(f'fuse_many: {n} maps need {n} frame rows in [0, {B}), got {rows}')
+    _check_rows(frames, B, h, w, 'fuse_many')
+    if len({id(m) for m in maps}) != n:
+        raise RpeError('fuse_many: a map is listed twice')
+    m0 = maps[0]
+    opts = (m0.d_thresh, bool(m0.average_points), m0.upscale, m0.conf_thr, m0.t_max)
+    if any((m.d_thresh, bool(m.average_points), m.upscale, m.conf_thr, m.t_max) != opts for m in maps):
+        raise RpeError('fuse_many: the maps must share d_thresh, average_pts, upscale, conf_thr and t_max')
+    dev = m0.device
+    for m in maps:
+        m.img_shape = (h, w)
+        m._grow_for(h * w)
+    depth, img = _f32(frames.depth, 'depth', dev), _f32(frames.img, 'img', dev)
+    mask = frames.mask.reshape(B, 1, h, w).bool().contiguous()
+    P = (poses.data if isinstance(poses, SE3) else poses).reshape(B, 7).to(device=dev, dtype=torch.float32).contiguous()
+    src = _descs([m._desc(m._cur) for m in maps])
+    dst = _descs([m._desc(1 - m._cur) for m in maps])
+    nb, ws = _ws_many([m._n_ub for m in maps], h, w, dev)
+    ticks = (ctypes.c_int32 * n)(*[int(m.tick) for m in maps])
+    rws = (ctypes.c_int32 * n)(*rows)
+    kmat = (ctypes.c_void_p * n)(*[m.kmat.data_ptr() for m in maps])
+    kinv = (ctypes.c_void_p * n)(*[m._kinv.data_ptr() for m in maps])
+    check(lib().rpe_surfel_fuse_many(n, src, nb, dst, ticks, rws, B, ptr(depth), ptr(img), ptr(mask), h, w, kmat, kinv, ptr(P),
+                                     float(m0.d_thresh), int(bool(m0.average_points)), int(m0.upscale), float(m0.conf_thr), int(m0.t_max),
+                                     ptr(ws), stream_ptr()), 'rpe_surfel_fuse_many')
+    for m in maps:
+        m._cur = 1 - m._cur
+        m._n_ub += h * w
+        m.tick += 1

@@ -51,6 +51,38 @@ def track_sequence(estimator, frames, start_stamp=0, chunk=1):
     return traj
 
 
+def track_sequences(estimator, sequences, start_stamps=None):
+    """``track_sequence`` for K sequences at once on a MultiSurfelPoseEstimator: ``sequences[k]`` yields (limg, rimg, mask, stamp) of
+    sequence k (row k of the estimator).  Every lockstep step takes the next frame of each sequence that has one and advances those
+    rows in one ``estimator.forward`` call; a sequence that ends leaves the batch.  With the estimator's init_poses the K runs can be
+    the (start, end) scenarios of one recording (scripts/benchmark_test.py).  Returns the K trajectories in track_sequence's format,
+    each bit for bit the one a SurfelPoseEstimator run of that sequence alone gives."""
+    import torch
+    n = len(sequences)
+    if n > estimator.n_seq:
+        raise ValueError(f'track_sequences: {n} sequences for an estimator of {estimator.n_seq}')
+    stamps = [0] * n if start_stamps is None else list(start_stamps)
+    if len(stamps) != n:
+        raise ValueError(f'track_sequences: {n} sequences, {len(stamps)} start stamps')
+    trajs = [[{'camera-pose': estimator.last_pose[k].vec().reshape(7).detach().cpu(), 'timestamp': stamps[k]}] for k in range(n)]
+    its = [iter(s) for s in sequences]
+    live = list(range(n))
+    while live:
+        items = []
+        for k in live:
+            item = next(its[k], None)
+            if item is not None:
+                items.append((k, item))
+        live = [k for k, _ in items]
+        if not live:
+            break
+        poses = estimator(torch.cat([it[0] for _, it in items]), torch.cat([it[1] for _, it in items]),
+                          torch.cat([it[2] for _, it in items]), rows=live)[0].vec().reshape(-1, 7)
+        for row, (k, it) in zip(poses.detach().cpu(), items):
+            trajs[k].append({'camera-pose': row.reshape(7), 'timestamp': it[3]})
+    return trajs
+
+
 def save_trajectory(trajectory, path):
     """trajectory.py:17-23 -- ``stamp tx ty tz qx qy qz qw`` per line, translation mm -> m."""
     fn = os.path.join(path, 'trajectory.freiburg')
