@@ -54,7 +54,8 @@ const char *rpe_version(void);
  *   minor 0: the 68 entry points of round 4;  1: rpe_conv_wino_x3*, rpe_conv1x1_x3*, rpe_conv_wino1d_x3* (9, round 5);  2: rpe_run_ops and
  *   the rpe_*_args structs of the prepared launch lists, rpe_corr_lookup_conv1x1* (round 6);  3: struct rpe_surfel_map and the
  *   rpe_surfel_* entry points of frame-to-model tracking (7);  4: rpe_surfel_*_many (K maps per launch, RPE_SURFEL_MAX_MAPS) and
- *   rpe_pose_gate_chain_rows, for tracking several sequences frame to model in one batch (8). */
+ *   rpe_pose_gate_chain_rows, for tracking several sequences frame to model in one batch (8).  rpe_conv_wino24* and RPE_OP_CONV_WINO24
+ *   (Winograd F(2x4,3x3)) were added without a new minor: probe for them with dlsym. */
 #define RPE_ABI_VERSION 5
 #define RPE_ABI_MINOR 4
 int rpe_abi_minor(void);
@@ -375,6 +376,15 @@ size_t rpe_conv_wino_packed_floats(int cout, int cin);
 int rpe_conv_wino_stats_tiles(int h, int w);
 int rpe_conv_wino_pack(const float *weight, int cout, int cin, float *packed, void *stream);
 int rpe_conv_wino(const rpe_conv_desc *desc, void *stream);
+/* The same convolution as Winograd F(2x4,3x3): F(2,3) along H, F(4,3) along W at the points {0, 1, -1, 1/2, -2}; 1/3 product per output
+ * against F(2x2)'s 4/9, at about a serial direct f32 sum's error (csrc/conv_wino24.hip; the layers of rpe_conv_wino).  Same descriptor
+ * fields, epilogues and moment records (rpe_conv_wino_stats_tiles, (b, T, cout, 3)).  Needs cin % 4 == 0, even h, w % 4 == 0 and
+ * 16-byte aligned x / out / out2 / residual planes (batch strides % 4 == 0); anything else -> RPE_E_UNSUPPORTED (the caller uses
+ * rpe_conv_wino).  desc->packed must come from rpe_conv_wino24_pack (rpe_conv_wino24_packed_floats floats, 0 = unsupported shape;
+ * 16-byte aligned). */
+size_t rpe_conv_wino24_packed_floats(int cout, int cin);
+int rpe_conv_wino24_pack(const float *weight, int cout, int cin, float *packed, void *stream);
+int rpe_conv_wino24(const rpe_conv_desc *desc, void *stream);
 /* LABELLED VARIANT of rpe_conv_wino (never in a headline number; bench.py --conv-bf16x3): the same convolution, descriptor fields,
  * epilogues and moment records, with every f32 product of the Winograd domain evaluated as six bf16 products of an exact three-way
  * split (x = hi + mid + lo) on the 16-bit matrix cores, f32 accumulation: f32-equivalent error (tests/test_gpu_conv_x3.py holds it to
@@ -491,6 +501,7 @@ int rpe_instnorm_finalize(const float *partials, int tiles, int b, int c, int hw
 #define RPE_OP_UPSAMPLE_CONVEX 14  /*       const rpe_upsample_convex_args *               */
 #define RPE_OP_CORR_BUILD 15       /*       const rpe_corr_build_args * -> rpe_corr_build_ex */
 #define RPE_OP_LOOKUP_CONV1X1 16    /*       const rpe_lookup_conv1x1_args * -> rpe_corr_lookup_conv1x1 */
+#define RPE_OP_CONV_WINO24 17      /*       const rpe_conv_desc *  -> rpe_conv_wino24      */
 #define RPE_OP_EVENT_RECORD 32     /*       void *const * (address of a hipEvent_t handle; NULL handle = no-op) */
 #define RPE_OP_STREAM_WAIT 33      /*       void *const * (the same)                       */
 typedef struct rpe_op {

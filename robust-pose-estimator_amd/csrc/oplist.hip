@@ -27,6 +27,7 @@ static int run_one(const rpe_op& op, void* const* streams, int n_streams) {
     switch (op.kind) {
     case RPE_OP_CONV_FUSED: return rpe_conv_fused(as<rpe_conv_desc>(op), st);
     case RPE_OP_CONV_WINO: return rpe_conv_wino(as<rpe_conv_desc>(op), st);
+    case RPE_OP_CONV_WINO24: return rpe_conv_wino24(as<rpe_conv_desc>(op), st);
     case RPE_OP_CONV_WINO1D: return rpe_conv_wino1d(as<rpe_conv_desc>(op), st);
     case RPE_OP_CONV1X1: return rpe_conv1x1(as<rpe_conv_desc>(op), st);
     case RPE_OP_CONV_WINO_X3: return rpe_conv_wino_x3(as<rpe_conv_desc>(op), st);

@@ -849,6 +849,17 @@ class PackedWino(_Packed):
         return tuple(weight.shape[2:]) == (3, 3) and weight.shape[1] % 4 == 0 and hh % 2 == 0 and ww % 2 == 0
 
 
+class PackedWino24(_Packed):
+    """Weights of a 3x3 stride-1 convolution for rpe_conv_wino24, Winograd F(2x4,3x3) (U = Gy g Gx^T in f64, rounded once).  conv_wino()
+    runs the kernel that belongs to the packing; maps it refuses (``supported``) take PackedWino's F(2x2)."""
+    kernels, error = ((3, 3),), 'needs a (cout, cin % 4 == 0, 3, 3) weight'
+    size, pack, entry = 'rpe_conv_wino24_packed_floats', 'rpe_conv_wino24_pack', 'rpe_conv_wino24'
+
+    @staticmethod
+    def supported(weight, hh, ww):
+        return tuple(weight.shape[2:]) == (3, 3) and weight.shape[1] % 4 == 0 and hh % 2 == 0 and ww % 4 == 0
+
+
 class PackedWinoX3(_Packed):
     """Weights of a 3x3 stride-1 convolution for rpe_conv_wino_x3, the LABELLED bf16x3 variant of rpe_conv_wino: U = G g G^T in f32,
     then the exact three-way bf16 split.  conv_wino() takes either packing and runs the kernel that belongs to it."""
@@ -861,8 +872,9 @@ class PackedWinoX3(_Packed):
 
 
 def conv_wino(x, pw, mode, out, out2=None, scale=None, bias='packed', residual=None, stats=None, pre_norm=None, prepare=False):
-    """rpe_conv_wino: out = epilogue(conv3x3(x; pw) * scale + bias) by Winograd F(2x2,3x3); tensors are channel slices of NCHW
-    buffers.  ``stats`` (conv_wino_stats_buffer) / ``pre_norm`` / ``residual`` / ``scale``: the encoders' epilogues, as conv_fused."""
+    """rpe_conv_wino: out = epilogue(conv3x3(x; pw) * scale + bias) by Winograd F(2x2,3x3) -- F(2x4,3x3) with a PackedWino24, the
+    labelled bf16x3 variant with a PackedWinoX3; tensors are channel slices of NCHW buffers.  ``stats`` (conv_wino_stats_buffer) /
+    ``pre_norm`` / ``residual`` / ``scale``: the encoders' epilogues, as conv_fused."""
     d = _lib.ConvDesc()
     b, cin, hh, ww = x.shape
     if cin != pw.cin:

@@ -36,6 +36,8 @@ from . import ops
 
 # Module-level route constants (no environment switches in the product: tools/ and bench.py's labelled experiments set these attributes)
 WINOGRAD = True          # 3x3 layers as F(2x2,3x3), the GRU's 1x5 / 5x1 as F(4,5); False = the direct implicit GEMM (A/B measurements)
+WINO_2X4 = True          # under WINOGRAD, 3x3 layers on maps with w % 4 == 0 as F(2x4,3x3) (rpe_conv_wino24: a quarter fewer products);
+                         # False = F(2x2) everywhere (A/B measurements)
 CORR_BF16X3 = False      # EXPERIMENT: correlation products as six bf16 products of an exact 3-way split (bench.py --corr-bf16x3)
 CONV_BF16X3 = False      # LABELLED VARIANT (bench.py --conv-bf16x3; never the headline): the update block's 3x3 layers with >= 128 input
 #                          channels (convc2, conv, FlowHead.conv1, the mask head's 3x3) through rpe_conv_wino_x3 -- Winograd products as six
@@ -188,15 +190,17 @@ def _packed(conv):
 
 
 def _wino(conv, x):
-    """PackedWino of a 3x3 stride-1 convolution when rpe_conv_wino can run it on this input (cached on the module), else None."""
+    """PackedWino24 / PackedWino of a 3x3 stride-1 convolution when rpe_conv_wino24 / rpe_conv_wino can run it on this input (cached on
+    the module), else None."""
     if not WINOGRAD or conv.stride != (1, 1) or conv.kernel_size != (3, 3) or conv.padding != (1, 1):
         return None
     if not ops.PackedWino.supported(conv.weight, x.shape[-2], x.shape[-1]) or conv.in_channels > 128 or not x.is_contiguous():
         return None
-    key = (conv.weight._version, conv.weight.data_ptr())
+    kind = ops.PackedWino24 if WINO_2X4 and ops.PackedWino24.supported(conv.weight, x.shape[-2], x.shape[-1]) else ops.PackedWino
+    key = (conv.weight._version, conv.weight.data_ptr(), kind)
     cached = getattr(conv, '_rpe_wino', None)
     if cached is None or cached[0] != key:
-        conv._rpe_wino = cached = (key, ops.PackedWino(conv.weight, None))
+        conv._rpe_wino = cached = (key, kind(conv.weight, None))
     return cached[1]
 
 
@@ -402,7 +406,7 @@ class BasicEncoder(nn.Module):
                 self._recorded = _Recorded()
             if '_key_tensors' not in self.__dict__:
                 self.__dict__['_key_tensors'] = _key_sources(self)
-            key = (tuple(tuple(im.shape) for im in images), first.device.index, ops.raw_stream(), split_act, WINOGRAD, CONV_BF16X3, self.training,
+            key = (tuple(tuple(im.shape) for im in images), first.device.index, ops.raw_stream(), split_act, WINOGRAD, WINO_2X4, CONV_BF16X3, self.training,
                    _tensor_key(self.__dict__['_key_tensors']))
             rec = self._recorded.get(key)
             if rec is not None:
@@ -548,13 +552,16 @@ class BasicUpdateBlock(nn.Module):
         keymods = mods + (e.convf1,)
         # (the convolutions' own weight / bias attributes: walking module.parameters() costs ~100 us a call, and this runs 26 times a frame)
         ps = [t for m in keymods for t in (m.weight, m.bias) if t is not None]
-        key = tuple(p._version for p in ps) + tuple(p.data_ptr() for p in ps) + (id(self.gate_weights()), CONV_BF16X3, X3_GRU)
+        key = tuple(p._version for p in ps) + tuple(p.data_ptr() for p in ps) + (id(self.gate_weights()), CONV_BF16X3, X3_GRU, WINO_2X4)
         if getattr(self, '_packed', None) is None or self._packed[0] != key:
             W = self.gate_weights()
             P = {n: ops.PackedConv(m.weight, m.bias) for n, m in zip(('convc1', 'convc2', 'convf2', 'conv', 'fh1'), mods)}
             # the four 3x3 layers also in Winograd form (rpe_conv_wino: 2.25x fewer matrix FLOPs); used on even maps
             P['wino'] = {n: ops.PackedWino(m.weight, m.bias) for n, m in zip(('convc2', 'convf2', 'conv', 'fh1'), mods[1:])
                          if ops.PackedWino.supported(m.weight, 2, 2)} if WINOGRAD else {}
+            # and as F(2x4,3x3) (rpe_conv_wino24: a quarter fewer products), used on maps with w % 4 == 0; not under the labelled variant
+            P['wino24'] = {n: ops.PackedWino24(m.weight, m.bias) for n, m in zip(('convc2', 'convf2', 'conv', 'fh1'), mods[1:])
+                           if ops.PackedWino24.supported(m.weight, 2, 4)} if (WINOGRAD and WINO_2X4 and not CONV_BF16X3) else {}
             # the labelled bf16x3 variant's packings of the same layers (used on maps rpe_conv_wino_x3 accepts: even h, w % 4 == 0)
             P['wino_x3'] = {n: ops.PackedWinoX3(m.weight, m.bias) for n, m in zip(('convc2', 'convf2', 'conv', 'fh1'), mods[1:])
                             if n != 'convf2' and m.in_channels >= X3_MIN_CIN and ops.PackedWinoX3.supported(m.weight, 2, 4)} if (WINOGRAD and CONV_BF16X3) else {}
@@ -598,6 +605,7 @@ class BasicUpdateBlock(nn.Module):
         cor, flo, fh_buf = P['cor_buf'](corr), P['flo_buf'](corr), P['fh_buf'](hx)
         wino = dict(P['wino']) if hx.shape[-1] % 2 == 0 and hx.shape[-2] % 2 == 0 else {}
         if wino and hx.shape[-1] % 4 == 0:
+            wino.update(P['wino24'])
             wino.update(P['wino_x3'])                      # (CONV_BF16X3: conv_wino runs the kernel that belongs to the packing)
 
         def c3(name, x, out, out2=None):                    # a 3x3 layer: Winograd when available, else the direct implicit GEMM
@@ -671,10 +679,11 @@ class BasicUpdateBlock(nn.Module):
         mp = (c1.weight, c1.bias, c2.weight, c2.bias)
         hh, ww = net.shape[-2:]
         x3 = CONV_BF16X3 and c1.in_channels >= X3_MIN_CIN and ops.PackedWinoX3.supported(c1.weight, hh, ww)
-        key = tuple(p._version for p in mp) + tuple(p.data_ptr() for p in mp) + (x3,)
+        w24 = WINO_2X4 and not CONV_BF16X3 and ops.PackedWino24.supported(c1.weight, hh, ww)
+        key = tuple(p._version for p in mp) + tuple(p.data_ptr() for p in mp) + (x3, w24)
         cached = getattr(self, '_mask_packed', None)
         if cached is None or cached[0] != key:
-            pw = (ops.PackedWinoX3 if x3 else ops.PackedWino)(c1.weight, c1.bias) if WINOGRAD and c1.weight.is_cuda else None
+            pw = (ops.PackedWinoX3 if x3 else ops.PackedWino24 if w24 else ops.PackedWino)(c1.weight, c1.bias) if WINOGRAD and c1.weight.is_cuda else None
             w2, b2 = (0.25 * c2.weight).detach(), (0.25 * c2.bias).detach()
             self._mask_packed = cached = (key, pw, w2, b2, ops.Conv1x1(w2, b2) if c2.weight.is_cuda else None)
         _, pw, w2, b2, p2 = cached
@@ -882,7 +891,7 @@ class RAFT(nn.Module):
             self.__dict__['_key_tensors'] = _key_sources(self.update_block)
         pyr = self._pyramid(N, h8, w8, dev)
         ws = self._workspace(N, h8, w8, dev)
-        key = (N, h8, w8, dev.index, ops.raw_stream(), iters, upsample, self.mixed_precision, WINOGRAD, CORR_BF16X3, CONV_BF16X3, X3_GRU, SIDE_STREAM,
+        key = (N, h8, w8, dev.index, ops.raw_stream(), iters, upsample, self.mixed_precision, WINOGRAD, WINO_2X4, CORR_BF16X3, CONV_BF16X3, X3_GRU, SIDE_STREAM,
                pyr.buf.data_ptr(), ws['hx'].data_ptr(), _tensor_key(self.__dict__['_key_tensors']))
         side = self._side_stream(dev) if SIDE_STREAM and N * h8 * w8 <= SIDE_STREAM_MAX else None
         entry = self._recorded.get(key)
