@@ -55,7 +55,8 @@ const char *rpe_version(void);
  *   the rpe_*_args structs of the prepared launch lists, rpe_corr_lookup_conv1x1* (round 6);  3: struct rpe_surfel_map and the
  *   rpe_surfel_* entry points of frame-to-model tracking (7);  4: rpe_surfel_*_many (K maps per launch, RPE_SURFEL_MAX_MAPS) and
  *   rpe_pose_gate_chain_rows, for tracking several sequences frame to model in one batch (8).  rpe_conv_wino24* and RPE_OP_CONV_WINO24
- *   (Winograd F(2x4,3x3)) were added without a new minor: probe for them with dlsym. */
+ *   (Winograd F(2x4,3x3)) were added without a new minor: probe for them with dlsym.  So were rpe_flow_forward_interpolate, rpe_flow_seed
+ *   and RPE_OP_FLOW_SEED (warm start of the update loop); the next RPE_ABI_MINOR bump counts them and rpe_conv_wino24*. */
 #define RPE_ABI_VERSION 5
 #define RPE_ABI_MINOR 4
 int rpe_abi_minor(void);
@@ -314,6 +315,20 @@ int rpe_conv3x3_to2(const float *x, const float *weight, const float *bias, int 
 int rpe_conv3x3_to2_flow(const float *x, const float *weight, const float *bias, int b, int c, int h, int w,
                          const float *coords, float *coords_out, float *flow_out, float *dst1, long long dst1_batch_stride,
                          float *dst2, long long dst2_batch_stride, void *stream);
+/* Warm start of the update loop from a previous flow (upstream RAFT.forward(..., flow_init): coords1 = coords0 + flow_init, and
+ * core/RAFT/core/utils/utils.py::forward_interpolate).
+ * rpe_flow_forward_interpolate: flow, out (b,2,h,w) f32, out must not overlap flow.  Per batch row, each source pixel (x0, y0) lands at
+ * x1 = x0 + dx, y1 = y0 + dy (f64); it is valid iff 0 < x1 < w and 0 < y1 < h (strict, as upstream's mask).  Output point (x, y) takes the
+ * (dx, dy) of the nearest valid point, distance (x - x1)^2 + (y - y1)^2 in f64 (two rounded squares, then their rounded sum, no fused
+ * multiply-add), ties to the lowest source index y0 * w + x0 (upstream's scipy griddata(method='nearest') leaves ties undefined).  A row
+ * without a valid point gives zeros (upstream's scipy raises).  Outputs are copies of input values; a row's result does not depend on the
+ * batch or the launch (no atomics); no allocation, no synchronisation.  b <= 65535.
+ * rpe_flow_seed: the front of a warm pass -- coords_out = pixel grid + flow_init (one f32 addition), flow_out = flow_init, and flow_init
+ * into the two-plane channel slices dst1 / dst2 (pointer to the first plane in batch item 0 + batch stride in floats); every output may
+ * be NULL.  flow_init (b,2,h,w). */
+int rpe_flow_forward_interpolate(const float *flow, int b, int h, int w, float *out, void *stream);
+int rpe_flow_seed(const float *flow_init, int b, int h, int w, float *coords_out, float *flow_out, float *dst1, long long dst1_batch_stride,
+                  float *dst2, long long dst2_batch_stride, void *stream);
 /* flow (b,2,h8,w8), mask (b,576,h8,w8) raw logits already scaled by .25 -> out (b,2,8*h8,8*w8). */
 int rpe_upsample_convex(const float *flow, const float *mask, int b, int h8, int w8, float *out, void *stream);
 
@@ -502,6 +517,7 @@ int rpe_instnorm_finalize(const float *partials, int tiles, int b, int c, int hw
 #define RPE_OP_CORR_BUILD 15       /*       const rpe_corr_build_args * -> rpe_corr_build_ex */
 #define RPE_OP_LOOKUP_CONV1X1 16    /*       const rpe_lookup_conv1x1_args * -> rpe_corr_lookup_conv1x1 */
 #define RPE_OP_CONV_WINO24 17      /*       const rpe_conv_desc *  -> rpe_conv_wino24      */
+#define RPE_OP_FLOW_SEED 18        /*       const rpe_flow_seed_args * -> rpe_flow_seed    */
 #define RPE_OP_EVENT_RECORD 32     /*       void *const * (address of a hipEvent_t handle; NULL handle = no-op) */
 #define RPE_OP_STREAM_WAIT 33      /*       void *const * (the same)                       */
 typedef struct rpe_op {
@@ -523,6 +539,9 @@ typedef struct rpe_flow_update_args {
     const float *x, *weight, *bias; int b, c, h, w; const float *coords; float *coords_out, *flow_out, *dst1; long long dst1_batch_stride;
     float *dst2; long long dst2_batch_stride;
 } rpe_flow_update_args;
+typedef struct rpe_flow_seed_args {
+    const float *flow_init; int b, h, w; float *coords_out, *flow_out, *dst1; long long dst1_batch_stride; float *dst2; long long dst2_batch_stride;
+} rpe_flow_seed_args;
 typedef struct rpe_copy_planes_args { const float *src; long long src_batch_stride; float *dst; long long dst_batch_stride; int b, c, hw; } rpe_copy_planes_args;
 typedef struct rpe_instnorm_finalize_args { const float *partials; int tiles, b, c, hw; float eps; float *mean_inv; } rpe_instnorm_finalize_args;
 typedef struct rpe_instnorm_apply_args {

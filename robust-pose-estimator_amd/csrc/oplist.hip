@@ -16,6 +16,7 @@ static_assert(sizeof(rpe_instnorm_finalize_args) == 40, "rpe_instnorm_finalize_a
 static_assert(sizeof(rpe_instnorm_apply_args) == 64, "rpe_instnorm_apply_args: layout changed -- update _lib.py and RPE_ABI_VERSION");
 static_assert(sizeof(rpe_upsample_convex_args) == 40, "rpe_upsample_convex_args: layout changed -- update _lib.py and RPE_ABI_VERSION");
 static_assert(sizeof(rpe_lookup_conv1x1_args) == 96, "rpe_lookup_conv1x1_args: layout changed -- update _lib.py and RPE_ABI_VERSION");
+static_assert(sizeof(rpe_flow_seed_args) == 72, "rpe_flow_seed_args: layout changed -- update _lib.py and RPE_ABI_VERSION");
 static_assert(sizeof(rpe_solve_opts) == 32, "rpe_solve_opts: layout changed -- update _lib.py and RPE_ABI_VERSION");
 
 template <typename A>
@@ -71,6 +72,11 @@ static int run_one(const rpe_op& op, void* const* streams, int n_streams) {
     case RPE_OP_UPSAMPLE_CONVEX: {
         const auto* a = as<rpe_upsample_convex_args>(op);
         return rpe_upsample_convex(a->flow, a->mask, a->b, a->h8, a->w8, a->out, st);
+    }
+    case RPE_OP_FLOW_SEED: {
+        const auto* a = as<rpe_flow_seed_args>(op);
+        return rpe_flow_seed(a->flow_init, a->b, a->h, a->w, a->coords_out, a->flow_out, a->dst1, a->dst1_batch_stride, a->dst2,
+                             a->dst2_batch_stride, st);
     }
     case RPE_OP_EVENT_RECORD: {
         hipEvent_t ev = (hipEvent_t) * static_cast<void* const*>(op.args);

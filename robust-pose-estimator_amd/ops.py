@@ -638,6 +638,52 @@ def copy_planes(src, dst):
     return _launch(_lib.OP_COPY_PLANES, (sp, sbs, dp, dbs, b, c, hh * ww), (src, dst), dst)
 
 
+def forward_interpolate(flow, out=None):
+    """Upstream RAFT's forward_interpolate (core/RAFT/core/utils/utils.py) of a 1/8 flow (N,2,h,w) f32, row by row on the GPU
+    (rpe_flow_forward_interpolate): each pixel's flow is pushed forward along itself, and every grid point takes the flow of the nearest
+    landing point strictly inside the map (ties to the lowest source index; a row with no such point gives zeros, where upstream's scipy
+    raises).  Bit-exact copies of input values; ``out`` must not overlap ``flow``.  No allocation when ``out`` is given, no synchronisation."""
+    fl = _dev(flow, torch.float32, 'flow')
+    if fl.dim() != 4 or fl.shape[1] != 2:
+        raise _lib.RpeError(f'forward_interpolate: flow must be (N,2,h,w), got {tuple(fl.shape)}')
+    n, _, hh, ww = fl.shape
+    if out is None:
+        out = torch.empty_like(fl)
+    elif tuple(out.shape) != tuple(fl.shape) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != fl.device:
+        raise _lib.RpeError(f'forward_interpolate: out must be a contiguous float32 tensor of shape {tuple(fl.shape)} on {fl.device}')
+    if _overlap_span(fl, out):
+        raise _lib.RpeError('forward_interpolate: out must not overlap flow')
+    check(lib().rpe_flow_forward_interpolate(ptr(fl), n, hh, ww, ptr(out), stream_ptr()), 'rpe_flow_forward_interpolate')
+    return out
+
+
+def _overlap_span(a, b):
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+def flow_seed(flow_init, coords_out=None, flow_out=None, dst1=None, dst2=None, prepare=False):
+    """rpe_flow_seed, the front of a warm update loop: coords_out = pixel grid + flow_init, flow_out = flow_init, and flow_init into the
+    two-channel slices ``dst1`` / ``dst2`` (e.g. hx[:, 254:256]); flow_init (b,2,h,w) contiguous.  ``prepare=True`` returns a launcher."""
+    fi = _nchw(flow_init, 'flow_init')
+    b, c, hh, ww = fi.shape
+    if c != 2:
+        raise _lib.RpeError(f'flow_seed: flow_init must be (b,2,h,w), got {tuple(fi.shape)}')
+    for name, t in (('coords_out', coords_out), ('flow_out', flow_out)):
+        if t is not None and tuple(_nchw(t, name).shape) != (b, 2, hh, ww):
+            raise _lib.RpeError(f'flow_seed: {name} must be ({b},2,{hh},{ww})')
+    sl = []
+    for name, t in (('dst1', dst1), ('dst2', dst2)):
+        if t is None:
+            sl += [None, 0]
+            continue
+        if tuple(t.shape) != (b, 2, hh, ww):
+            raise _lib.RpeError(f'flow_seed: {name} must be a ({b},2,{hh},{ww}) channel slice')
+        sl += list(_chan_slice(t, name))
+    return _launch(_lib.OP_FLOW_SEED, (ptr(fi), b, hh, ww, ptr(coords_out), ptr(flow_out), *sl), (fi, coords_out, flow_out, dst1, dst2),
+                   coords_out, prepare)
+
+
 def upsample_convex(flow, mask):
     fl, mk = _dev(flow, torch.float32, 'flow'), _dev(mask, torch.float32, 'mask')
     b, _, h8, w8 = fl.shape

@@ -88,6 +88,11 @@ class PoseEstimator(torch.nn.Module):
         self._enc_cache = None
         self._pending = []                                            # submit() / result(): frames whose encoders are already on the side stream
         self._prefetch_stream = None
+        # warm start (``warm_start: True``): the temporal RAFT pass of frame t starts from ops.forward_interpolate of frame t-1's temporal
+        # 1/8 flow (upstream RAFT's video warm start).  Cold after the first frame, after reset() and after a frame the gate rejected.
+        self.warm_start = bool(config.get('warm_start', False))
+        self._flow_low = None                                         # the last accepted temporal pass's 1/8 flow (1,2,h/8,w/8), or None
+        self._low_pass = None                                         # ... of the pass in flight, until the gate has seen it
 
     @property
     def device(self):
@@ -99,7 +104,14 @@ class PoseEstimator(torch.nn.Module):
         self.frame = self.last_frame = None
         self._enc_cache = None
         self._pending = []
+        self._flow_low = None
         return self
+
+    def _flow_init(self):
+        """The temporal pass's flow_init / ret_lowres keywords of PoseNet.infer: {} without warm start."""
+        if not self.warm_start:
+            return {}
+        return dict(ret_lowres=True, flow_init=None if self._flow_low is None else ops.forward_interpolate(self._flow_low))
 
     @torch.no_grad()
     def submit(self, limg, rimg, mask):
@@ -161,12 +173,14 @@ class PoseEstimator(torch.nn.Module):
         # :81-91 in one launch (ops.pose_gate_chain): the gate isnan | |log| > 0.1 -> identity, de-normalisation of the depth scaling and
         # last_pose <- last_pose * rel^-1, with ONE host synchronisation (the success flag) instead of a dozen element-wise launches and two
         rel, pose, ok = ops.pose_gate_chain(rel_pose.data.reshape(1, 7), self.last_pose.data, self._inv_scale, 1.0e-1)
+        low, self._low_pass = self._low_pass, None
         if self._pending:
             self._start_encoders(self._pending[0])            # (submit / result) the next frame's encoders, before the host waits for this one
         self.t_enqueued = time.perf_counter()             # everything of this frame has been handed to the runtime; what follows waits for the GPU
         self.success = bool(ok[0])
         if not self.success:
             warnings.warn('pose estimation not converged, skip.', RuntimeWarning)                 # :82
+        self._flow_low = low if self.success else None                # (a rejected frame: the next pair spans two frames, start it cold)
         self.last_rel_pose = SE3(rel)
         self.last_frame = ret_frame
         self.last_pose = SE3(pose)
@@ -179,6 +193,9 @@ class PoseEstimator(torch.nn.Module):
         relative poses, same gate decisions, same chained poses, same Frame left behind.  Returns the (c,7) absolute poses;
         ``last_rel_poses`` (c,7) gated relative poses and ``successes`` (c,) bool are left on the estimator, the gate is evaluated on
         the device with ONE host synchronisation per chunk (for the warnings) instead of two per frame."""
+        if self.warm_start:
+            raise ValueError('forward_chunk computes a chunk\'s temporal flows in one RAFT pass, so frame t cannot start from frame t-1\'s '
+                             'flow: warm_start needs forward (or submit / result) frame by frame')
         if self.frame is None:
             raise RuntimeError('forward_chunk: call forward() on the first frame of the sequence (it has no predecessor to pair with)')
         c = limgs.shape[0]
@@ -205,6 +222,7 @@ class PoseEstimator(torch.nn.Module):
 
     def get_pose_f2f(self, enc=None):
         flow = None
+        self._low_pass = None
         if self.last_frame is None:
             rel = SE3.IdentityLike(self.last_pose)
             depth, stereo_flow, valid, cache = self.model.flow2depth(self.frame.img, self.frame.rimg,
@@ -217,7 +235,10 @@ class PoseEstimator(torch.nn.Module):
             self.last_frame.img, self.frame.img, self.intrinsics, self.baseline * self.scale,
             depth1=self.last_frame.depth * self.scale, image2r=self.frame.rimg, mask1=self.last_frame.mask,
             mask2=self.frame.mask, stereo_flow1=self.last_frame.flow, ret_details=True,
-            cache1=self._enc_cache, ret_cache=True, **({'enc2': enc} if enc is not None and self._enc_cache is not None else {}))
+            cache1=self._enc_cache, ret_cache=True, **({'enc2': enc} if enc is not None and self._enc_cache is not None else {}),
+            **self._flow_init())
+        if self.warm_start:
+            self._low_pass = cache.pop('time_flow_low')
         self._enc_cache = cache if self.reuse_features else None
         rel = SE3(rel.data.reshape(1, 7))
         self.frame.depth = depth2 / self.scale
@@ -271,6 +292,7 @@ class SurfelPoseEstimator(PoseEstimator):
         self.success = bool(ok[0])
         if not self.success:
             warnings.warn('pose estimation not converged, skip.', RuntimeWarning)
+        self._flow_low = self._low_pass if self.success else None
         self.last_rel_pose = SE3(rel)
         self.last_frame = ret_frame
         self.last_pose = SE3(pose)
@@ -281,9 +303,13 @@ class SurfelPoseEstimator(PoseEstimator):
     def get_pose_f2m(self):
         """:127-150: the map rendered at the last camera pose, PoseNet.infer of render -> frame (mask2 &= valid in place)."""
         model_frame = self.scene.render_transformed(self.intrinsics.squeeze(0), self.last_pose.inv())[0]
-        rel, depth1, depth2, weights, flow, stereo_flow = self.model.infer(
+        warm = self._flow_init()                                           # (warm start: the previous render -> frame flow, pushed forward)
+        r = self.model.infer(
             model_frame.img, self.frame.img, self.intrinsics, self.baseline * self.scale, depth1=model_frame.depth * self.scale,
-            image2r=self.frame.rimg, mask1=model_frame.mask, mask2=self.frame.mask, stereo_flow1=model_frame.flow, ret_details=True)
+            image2r=self.frame.rimg, mask1=model_frame.mask, mask2=self.frame.mask, stereo_flow1=model_frame.flow, ret_details=True,
+            **(dict(warm, ret_cache=True) if warm else {}))
+        rel, depth1, depth2, weights, flow, stereo_flow = r[:6]
+        self._low_pass = r[6]['time_flow_low'] if warm else None
         self.frame.depth = depth2 / self.scale
         self.frame.flow = stereo_flow
         model_frame.confidence = weights[0]
@@ -335,11 +361,13 @@ class MultiSurfelPoseEstimator(PoseEstimator):
             self.last_pose = [None] * self.n_seq
             self.success = [True] * self.n_seq
             self.scenes = [None] * self.n_seq
+            self._flow_lows = [None] * self.n_seq                         # warm start: each sequence's last accepted temporal 1/8 flow
             rows = range(self.n_seq)
         for k in rows:
             self.last_pose[k] = self._init_pose_of(k)
             self.success[k] = True
             self.scenes[k] = None
+            self._flow_lows[k] = None                                      # (warm start: the sequence's next pass is cold)
         return self
 
     def submit(self, *a, **k):
@@ -394,21 +422,35 @@ class MultiSurfelPoseEstimator(PoseEstimator):
         keep = problem.partition_rows if problem is not None else None
         if problem is not None:
             problem.partition_rows = 1                                     # a row's solve as if alone (PoseNet.infer_chunk does the same)
+        warm = {}
+        if self.warm_start:
+            # per sequence: forward_interpolate of its last accepted render -> frame flow, or zeros (= the cold pass, bit for bit) for a
+            # sequence without one; one launch over the R rows (a row's result does not depend on its batch)
+            prev = [self._flow_lows[k] for k in rows]
+            have = [p for p in prev if p is not None]
+            warm['ret_lowres'], warm['ret_cache'] = True, True
+            if have:
+                zero = torch.zeros_like(have[0])
+                warm['flow_init'] = ops.forward_interpolate(torch.cat([zero if p is None else p for p in prev]))
         try:
-            rel, depth1, depth2, weights, flow, stereo_flow = self.model.infer(
+            r = self.model.infer(
                 model.img, limgs, K, baseline, depth1=model.depth * self.scale, image2r=rimgs, mask1=model.mask, mask2=masks,
-                stereo_flow1=model.flow, ret_details=True)
+                stereo_flow1=model.flow, ret_details=True, **warm)
+            rel, depth1, depth2, weights, flow, stereo_flow = r[:6]
         finally:
             if problem is not None:
                 problem.partition_rows = keep
         rel_g, pose, ok = ops.pose_gate_chain_rows(rel.data.reshape(R, 7), last, self._inv_scale, 1.0e-1)     # :81-91, row by row
         self.t_enqueued = time.perf_counter()
         okh = ok.cpu().bool()                                              # the lockstep frame's one host synchronisation
+        low = r[6]['time_flow_low'] if warm else None
         for j, k in enumerate(rows):
             self.success[k] = bool(okh[j])
             if not self.success[k]:
                 warnings.warn('pose estimation not converged, skip.', RuntimeWarning)
             self.last_pose[k] = SE3(pose[j:j + 1])
+            if warm:
+                self._flow_lows[k] = low[j:j + 1] if self.success[k] else None
         self.last_rel_poses = rel_g
         passed = [j for j in range(R) if okh[j]]
         if passed:                                                         # :94-95

@@ -109,10 +109,14 @@ class PoseNet(nn.Module):
         return self.flow.encode_features(feature_images), self.flow.encode_context(context_images)
 
     @torch.no_grad()
-    def stages(self, image1l, image2l, intrinsics, baseline, depth1, image2r, mask1, mask2, stereo_flow1, cache1=None, heads=True, enc2=None):
+    def stages(self, image1l, image2l, intrinsics, baseline, depth1, image2r, mask1, mask2, stereo_flow1, cache1=None, heads=True, enc2=None,
+               flow_init=None, ret_lowres=False):
         """Every stage of infer() before the solve.  ``cache1`` = {'fmap','cnet'} of image1l from the previous call
         (streaming: frame t's image2l is frame t+1's image1l), so only the two new images are encoded -- or not even those when
-        ``enc2`` = encode_frame(image2l, image2r) was computed ahead of the call (needs cache1)."""
+        ``enc2`` = encode_frame(image2l, image2r) was computed ahead of the call (needs cache1).
+        ``flow_init`` (n,2,h/8,w/8): warm start of the n TEMPORAL pairs (RAFT.forward's flow_init); the n stereo pairs of the same RAFT
+        batch start from zero, so depth and stereo flow are bit-identical to a cold pass.  ``ret_lowres``: the temporal pairs' last 1/8 flow
+        (n,2,h/8,w/8) is added as 'time_flow_low' to the result and to its 'cache2'."""
         n = image1l.shape[0]
         intrinsics = intrinsics.expand(n, 3, 3).contiguous()
         baseline = baseline.expand(n).contiguous()
@@ -129,7 +133,13 @@ class PoseNet(nn.Module):
             f2l = f[:n]
             fmaps = (torch.cat((cache1['fmap'], f2l), dim=0), f)
             cn = torch.cat((cache1['cnet'], c2l), dim=0)
-        flow_predictions, hidden, context = self.flow(None, None, upsample=True, fmaps=fmaps, cnet=cn)
+        kw = {}
+        if flow_init is not None:
+            kw['flow_init'] = torch.cat((flow_init, torch.zeros_like(flow_init)), dim=0)      # (temporal | stereo) rows of the RAFT batch
+        if ret_lowres:
+            kw['ret_lowres'] = True
+        r = self.flow(None, None, upsample=True, fmaps=fmaps, cnet=cn, **kw)
+        flow_predictions, hidden, context = r[:3]
         time_flow = flow_predictions[-1][:n].contiguous()
         stereo_flow2 = flow_predictions[-1][n:].contiguous()
         hidden, context = hidden[:n], context[:n]
@@ -149,14 +159,21 @@ class PoseNet(nn.Module):
             w3d = torch.ones_like(g['depth2'])
         g.update(time_flow=time_flow, stereo_flow2=stereo_flow2, hidden=hidden, context=context, w2d=w2d, w3d=w3d,
                  intrinsics=intrinsics, cache2=dict(fmap=f2l, cnet=c2l))
+        if ret_lowres:
+            g['time_flow_low'] = g['cache2']['time_flow_low'] = r[3][:n]
         return g
 
     @torch.no_grad()
     def infer(self, image1l, image2l, intrinsics, baseline, depth1, image2r, mask1, mask2, stereo_flow1,
-              ret_details=False, cache1=None, ret_cache=False, enc2=None):
+              ret_details=False, cache1=None, ret_cache=False, enc2=None, flow_init=None, ret_lowres=False):
+        """``flow_init`` / ``ret_lowres``: see stages (warm start of the temporal pairs; the temporal 1/8 flow comes back as the returned
+        cache's 'time_flow_low', so ret_lowres needs ret_cache)."""
         if enc2 is not None and cache1 is None:
             raise ValueError('infer: enc2 (the new frame encoded ahead of the call) needs cache1 (the previous frame\'s encoder outputs)')
-        s = self.stages(image1l, image2l, intrinsics, baseline, depth1, image2r, mask1, mask2, stereo_flow1, cache1, enc2=enc2)
+        if ret_lowres and not ret_cache:
+            raise ValueError("infer: ret_lowres returns the temporal 1/8 flow in the cache dict ('time_flow_low'): it needs ret_cache=True")
+        s = self.stages(image1l, image2l, intrinsics, baseline, depth1, image2r, mask1, mask2, stereo_flow1, cache1, enc2=enc2,
+                        flow_init=flow_init, ret_lowres=ret_lowres)
         mask2.copy_(s['mask2'])                               # `mask2 &= valid` mutates the caller's tensor (:77)
         n = image1l.shape[0]
         lw = self.loss_weight.detach()[None, :].repeat(n, 1)

@@ -836,30 +836,34 @@ class RAFT(nn.Module):
         cn.record_stream(cur)                                 # allocated on the side stream, consumed (and freed) on the caller's
         return f, cn
 
-    def _begin(self, pyr, ws, fmap1, fmap2, cnet, fused):
+    def _begin(self, pyr, ws, fmap1, fmap2, cnet, fused, flow_init=None):
         """Everything of a pass in front of the update loop: the correlation pyramid, h <- tanh half of the context encoder's output, the
         GRU's four loop-invariant context terms, and (fused route) coords1 <- grid, flow <- 0 in the workspace's persistent buffers,
-        which the flow head's output layer then updates in place."""
+        which the flow head's output layer then updates in place.  ``flow_init`` (warm start): coords1 <- grid + flow_init and flow_init
+        as the flow the first iteration's motion encoder sees, in ONE launch (rpe_flow_seed) instead of the four plane copies."""
         c = self.hidden_dim
         pyr.build(fmap1.float(), fmap2.float(), fp16_features=self.mixed_precision, bf16x3=(CORR_BF16X3 or CONV_BF16X3) and not self.mixed_precision)
         hx, rhx = ws['hx'], ws['rhx']
         ops.copy_planes(cnet[:, :c], hx[:, :c])
         ctx = self.update_block.context_terms(cnet[:, c:], out=ws['ctx'] if fused else None)      # (fused: written into the persistent buffers)
-        if fused:
+        if fused and flow_init is not None:
+            ops.flow_seed(flow_init, coords_out=ws['coords1'], flow_out=ws['flow'], dst1=hx[:, 2 * c - 2:], dst2=rhx[:, 2 * c - 2:])
+        elif fused:
             ops.copy_planes(ws['coords0'], ws['coords1'])
             ops.copy_planes(ws['zero2'], ws['flow'])
             ops.copy_planes(ws['zero2'], hx[:, 2 * c - 2:])
             ops.copy_planes(ws['zero2'], rhx[:, 2 * c - 2:])
         return ctx
 
-    def _finish(self, ws, upsample):
-        """Behind the loop of the fused route: the returned prediction (mask head + convex x8 up-sampling, or a copy of the 1/8 flow) and
-        the returned hidden state, both fresh tensors."""
+    def _finish(self, ws, upsample, ret_lowres=False):
+        """Behind the loop of the fused route: the returned prediction (mask head + convex x8 up-sampling, or a copy of the 1/8 flow), the
+        returned hidden state and (``ret_lowres``) a copy of the last 1/8 flow, all fresh tensors (the last one None when not asked for)."""
         c = self.hidden_dim
         hx, flow = ws['hx'], ws['flow']
         pred = ops.upsample_convex(flow, self.update_block.up_mask(hx[:, :c])) if upsample else ops.copy_planes(flow, torch.empty_like(flow))
         h_buf = ops.copy_planes(hx[:, :c], torch.empty(hx.shape[0], c, hx.shape[2], hx.shape[3], device=hx.device))
-        return pred, h_buf
+        low = ops.copy_planes(flow, torch.empty_like(flow)) if ret_lowres else None
+        return pred, h_buf, low
 
     def _run_loop(self, pyr, ws, iters, side):
         prog, marks = self._loop_program(pyr, ws, iters, side)
@@ -874,16 +878,17 @@ class RAFT(nn.Module):
         streams = (ops.raw_stream(),) if side is None else (ops.raw_stream(), side[0].cuda_stream)
         return prog, marks, streams
 
-    def _forward_recorded(self, fmap1, fmap2, cnet, iters, upsample):
+    def _forward_recorded(self, fmap1, fmap2, cnet, iters, upsample, flow_init=None, ret_lowres=False):
         """forward() for a small pass on given encoder outputs (sequential tracking: one or two flow pairs per frame) as THREE calls into
-        the library: the recorded front (_begin), the loop's launch list, the recorded tail (_finish).  None = this pass cannot be
-        recorded (the caller goes on call by call)."""
+        the library: the recorded front (_begin; a warm pass's seeding launch included, flow_init bound like the encoder outputs), the
+        loop's launch list, the recorded tail (_finish).  None = this pass cannot be recorded (the caller goes on call by call)."""
         N, _, h8, w8 = fmap1.shape
         dev = fmap1.device
         c = self.hidden_dim
-        ts = (fmap1, fmap2, cnet)
+        ts = (fmap1, fmap2, cnet) + (() if flow_init is None else (flow_init,))
         if not all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == dev for t in ts) or _overlap(ts) \
-                or tuple(cnet.shape) != (N, 2 * c, h8, w8) or dev.index != torch.cuda.current_device():
+                or tuple(cnet.shape) != (N, 2 * c, h8, w8) or dev.index != torch.cuda.current_device() \
+                or (flow_init is not None and tuple(flow_init.shape) != (N, 2, h8, w8)):
             return None                                               # (the call-by-call route raises what needs raising)
         if getattr(self, '_recorded', None) is None:
             self._recorded = _Recorded()
@@ -893,40 +898,52 @@ class RAFT(nn.Module):
         ws = self._workspace(N, h8, w8, dev)
         key = (N, h8, w8, dev.index, ops.raw_stream(), iters, upsample, self.mixed_precision, WINOGRAD, WINO_2X4, CORR_BF16X3, CONV_BF16X3, X3_GRU, SIDE_STREAM,
                pyr.buf.data_ptr(), ws['hx'].data_ptr(), _tensor_key(self.__dict__['_key_tensors']))
+        if flow_init is not None or ret_lowres:                       # (a cold pass keeps the key it always had)
+            key += ('warm' if flow_init is not None else 'cold', ret_lowres)
+        ins = {'f1': fmap1, 'f2': fmap2, 'cnet': cnet}
+        if flow_init is not None:
+            ins['finit'] = flow_init
         side = self._side_stream(dev) if SIDE_STREAM and N * h8 * w8 <= SIDE_STREAM_MAX else None
         entry = self._recorded.get(key)
         if entry is not None:
             pre, post = entry.pre, entry
-            pre.replay({'f1': fmap1, 'f2': fmap2, 'cnet': cnet})
+            pre.replay(ins)
             prog, _, streams = self._run_loop(pyr, ws, iters, side)
             prog.run(streams)
             pred, h_buf = torch.empty(post.pred_shape, device=dev), torch.empty(N, c, h8, w8, device=dev)
-            post.replay({'pred': pred, 'h': h_buf})
-            return [pred], h_buf, cnet[:, c:]
+            outs = {'pred': pred, 'h': h_buf}
+            if ret_lowres:
+                outs['low'] = low = torch.empty(N, 2, h8, w8, device=dev)
+            post.replay(outs)
+            return ([pred], h_buf, cnet[:, c:], low) if ret_lowres else ([pred], h_buf, cnet[:, c:])
         if not self._recorded.wanted(key):
             return None
         prog, _, streams = self._run_loop(pyr, ws, iters, side)      # (built outside the recordings: its launchers must hold the real entry points)
         pre = ops.Recorder()
         with pre:
-            self._begin(pyr, ws, fmap1, fmap2, cnet, True)
+            self._begin(pyr, ws, fmap1, fmap2, cnet, True, flow_init)
         prog.run(streams)
         post = ops.Recorder()
         with post:
-            pred, h_buf = self._finish(ws, upsample)
+            pred, h_buf, low = self._finish(ws, upsample, ret_lowres)
         if pre.complete and post.complete:
-            ok = pre.bind('f1', fmap1) > 0 and pre.bind('f2', fmap2) > 0 and pre.bind('cnet', cnet) > 0 and post.bind('pred', pred) > 0 and post.bind('h', h_buf) > 0
+            outs = {'pred': pred, 'h': h_buf, **({'low': low} if ret_lowres else {})}
+            ok = all(pre.bind(k, t) > 0 for k, t in ins.items()) and all(post.bind(k, t) > 0 for k, t in outs.items())
             pre.complete = post.complete = ok
         post.complete = post.complete and pre.complete
         post.pre, post.pred_shape = pre, tuple(pred.shape)
         self._recorded.put(key, post)
-        return [pred], h_buf, cnet[:, c:]
+        return ([pred], h_buf, cnet[:, c:], low) if ret_lowres else ([pred], h_buf, cnet[:, c:])
 
     @torch.no_grad()
-    def forward(self, image1, image2, upsample=True, iters=None, all_flows=False, fmaps=None, cnet=None):
+    def forward(self, image1, image2, upsample=True, iters=None, all_flows=False, fmaps=None, cnet=None, flow_init=None, ret_lowres=False):
         """image1, image2: (N,3,H,W) in 0..255.  Inference only (the reference freezes RAFT, train.yaml:51).
         ``fmaps`` / ``cnet`` accept encoder outputs computed elsewhere (both encoders normalise per sample -- instance
         norm / frozen batch norm -- so a caller may encode every distinct image once and reuse it); with both given the
-        images may be None.  ``cnet`` is encode_context's output: (tanh(net) | relu(inp))."""
+        images may be None.  ``cnet`` is encode_context's output: (tanh(net) | relu(inp)).
+        ``flow_init`` (N,2,H/8,W/8) f32: warm start as upstream RAFT's (coords1 = coords0 + flow_init; the first iteration's motion encoder
+        sees flow = flow_init), e.g. ops.forward_interpolate of the previous frame's 1/8 flow; all zeros gives the cold pass bit for bit.
+        ``ret_lowres``: a 4th return element, the last iteration's 1/8 flow as a fresh tensor."""
         iters = self.iters if iters is None else iters
         if image1 is None:                                    # encoder outputs given: the images are not needed again
             (N, _, h8, w8), dev = fmaps[0].shape, fmaps[0].device
@@ -942,16 +959,21 @@ class RAFT(nn.Module):
         if cnet is None:
             cnet = self.encode_context(image1)                # (tanh(net) | relu(inp))
         c = self.hidden_dim
+        if flow_init is not None:
+            if tuple(flow_init.shape) != (N, 2, h8, w8) or flow_init.dtype != torch.float32 or flow_init.device != dev:
+                raise ValueError(f'RAFT.forward: flow_init must be a float32 ({N},2,{h8},{w8}) tensor on {dev}, got '
+                                 f'{flow_init.dtype} {tuple(flow_init.shape)} on {flow_init.device}')
+            flow_init = flow_init.contiguous()
         ub = self.update_block
         P = ub.packed_convs(w8)
         fused = P is not None
         if fused and FRAME_OPLISTS and LOOP_OPLIST and not all_flows and N <= FRAME_OPLISTS_MAX_IMAGES and LOOKUP_EVENT_SINK is None:
-            r = self._forward_recorded(fmap1, fmap2, cnet, iters, upsample)
+            r = self._forward_recorded(fmap1, fmap2, cnet, iters, upsample, flow_init, ret_lowres)
             if r is not None:
                 return r
         pyr = self._pyramid(N, h8, w8, dev)
         ws = self._workspace(N, h8, w8, dev)
-        ctx = self._begin(pyr, ws, fmap1, fmap2, cnet, fused)
+        ctx = self._begin(pyr, ws, fmap1, fmap2, cnet, fused, flow_init)
         hx, corr = ws['hx'], ws['corr']                     # hx = (h | motion | flow)
         h_buf = torch.empty(N, c, h8, w8, device=dev)         # returned to the caller: fresh
         inp = cnet[:, c:]
@@ -959,6 +981,8 @@ class RAFT(nn.Module):
         flow_predictions = []
         if fused:
             coords1, flow = ws['coords1'], ws['flow']
+        elif flow_init is not None:
+            coords1 = ops.flow_seed(flow_init, coords_out=torch.empty_like(coords0))          # coords0 + flow_init
         else:
             coords1 = coords0.clone()
         side = self._side_stream(dev) if fused and SIDE_STREAM and N * h8 * w8 <= SIDE_STREAM_MAX else None
@@ -987,7 +1011,7 @@ class RAFT(nn.Module):
                     done.record()
             pyr.lookup(coords1, out=corr)
             if not fused:
-                flow = coords1 - coords0
+                flow = flow_init if itr == 0 and flow_init is not None else coords1 - coords0
             coords1 = ub.step(ws, ctx, flow, coords1, h_buf, flow_branch_done=done)
             if all_flows or itr == iters - 1:
                 lowres = flow if fused else coords1 - coords0
@@ -996,4 +1020,6 @@ class RAFT(nn.Module):
                 else:
                     flow_predictions.append(ops.copy_planes(lowres, torch.empty_like(lowres)) if fused else lowres)
         ops.copy_planes(hx[:, :c], h_buf)
+        if ret_lowres:
+            return flow_predictions, h_buf, inp, ops.copy_planes(flow, torch.empty_like(flow)) if fused else coords1 - coords0
         return flow_predictions, h_buf, inp

@@ -102,7 +102,13 @@ class SequenceTracker:
             self._est = self.make_estimator()
         return self._est
 
+    def _refuse_warm_start(self):
+        if getattr(self.estimator, 'warm_start', False):
+            raise ValueError('SequenceTracker: warm_start seeds frame t\'s flow with frame t-1\'s, which a block walk (chunked passes, blocks '
+                             'restarted at their halo frame) cannot honour: track the sequence frame by frame (trajectory.track_sequence)')
+
     def run_block(self, first_pair, last_pair):
+        self._refuse_warm_start()
         est = self.estimator
         est.reset()
         rels, oks = [], []
@@ -138,6 +144,7 @@ class SequenceTracker:
 
     def track(self, n_frames, rank=0, world=1, group=None, scale=None):
         """``scale`` defaults to the depth-clipping distance of the estimator this tracker builds."""
+        self._refuse_warm_start()
         est_scale = float(self.estimator.config['depth_clipping'][1])     # the distance PoseEstimator normalises by (pose_estimator.py:40-43)
         if scale is None:
             scale = est_scale

@@ -26,8 +26,11 @@ def track_sequence(estimator, frames, start_stamp=0, chunk=1):
     """The loop of infer_trajectory.py:70-91.  ``frames`` yields (limg, rimg, mask, stamp) already on the device.
     Returns [{'camera-pose': (7,) tensor (mm), 'timestamp': stamp}], starting with the initial pose.
     ``chunk`` > 1: frames are handed to ``estimator.forward_chunk`` in groups of ``chunk`` (one RAFT pass per group; the same
-    trajectory bit for bit, about twice the frames per second at 16); the sequence's first frame always goes through ``forward``."""
+    trajectory bit for bit, about twice the frames per second at 16); the sequence's first frame always goes through ``forward``.
+    An estimator with ``warm_start`` needs ``chunk`` = 1 (a chunk's temporal flows come from one pass)."""
     import torch
+    if chunk > 1 and getattr(estimator, 'warm_start', False):
+        raise ValueError('track_sequence: warm_start starts frame t from frame t-1\'s flow, which a chunked pass cannot: use chunk=1')
     traj = [{'camera-pose': estimator.last_pose.vec().reshape(7).detach().cpu(), 'timestamp': start_stamp}]
     pending = []
 
