@@ -146,6 +146,11 @@ typedef struct rpe_solve_opts {
     int reserved;                /* flags; 0 = defaults.  RPE_SOLVE_LAUNCH_PER_EVALUATION (bit 0): one launch per evaluation even where the whole
                                   * solve would run as one persistent launch (identical results; for A/B measurements) */
 } rpe_solve_opts;
+/* Concurrent solves.  The one persistent launch is chosen when ITS grid fits the device's resident workgroups; its workgroups then wait
+ * for their row's tail without giving up their slots.  Persistent solves running at the same time (on several streams, in this process or
+ * in another) whose grids TOGETHER exceed the device can each hold part of a row with no row of either complete, and starve each other
+ * until the wait's bound gives up -- with a wrong pose and a normal stop code.  A caller that runs several solves at once passes
+ * RPE_SOLVE_LAUNCH_PER_EVALUATION (bit-identical results), unless it keeps their combined grids within the device. */
 #define RPE_SOLVE_LAUNCH_PER_EVALUATION 1
 int rpe_pose_solve_ex(const float *flow, const float *pcl1, const float *pcl2, const float *w1, const float *w2,
                       const uint8_t *mask1, const uint8_t *mask2, const float *K, const float *loss_weight,

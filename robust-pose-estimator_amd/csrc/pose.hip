@@ -205,16 +205,20 @@ template <bool COH>
 __device__ bool reduce_tail(const PoseArgs& A, RowUniform* uni, RowState* states, const double* partials, int row, int nblk, const TailArgs& Z, double* line);
 
 #define EPOCH_STOPPED (1 << 30)
+// s_waitcnt simm16 (gfx9 family): vmcnt = 0, expcnt (7) and lgkmcnt (15) left free -- waits until every vector memory operation of the
+// wave, stores included, has been acknowledged
+#define RPE_WAIT_VMCNT0 0x0f70
 // a workgroup-uniform double from LDS, moved to scalar registers
 __device__ __forceinline__ double lds_uniform(const double* p) {
     const double v = *p;
     return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
 }
 
-// Waiting never deadlocks: a workgroup only ever waits for workgroups of ITS OWN ROW, a row's workgroups are contiguous in dispatch order,
-// and a row whose workgroups are all resident runs to its end and leaves -- so whatever else shares the device (another solve on another
-// stream), some row is always complete and progressing, and the slots it frees go to the rows that are not.  (The host still only asks
-// for one launch when the whole grid fits: the partition is sized so that nothing waits for a slot.)
+// Waiting: a workgroup only ever waits for workgroups of ITS OWN ROW, a row's workgroups are contiguous in dispatch order, and a row whose
+// workgroups are all resident runs to its end and leaves -- so beside kernels that end by themselves (another stream's encoders), some row
+// is always complete and progressing, and the slots it frees go to the rows that are not.  (The host still only asks for one launch when
+// the whole grid fits: the partition is sized so that nothing waits for a slot.)  NOT beside another persistent solve: two of them whose
+// grids together exceed the device can each hold part of a row with no row of either complete (include/rpe.h, rpe_solve_opts).
 // TAIL: the launch belongs to a solve: the row's last workgroup runs the update, and the launch runs Z.evals evaluations -- between
 // evaluations a row's workgroups wait for the row's tail (an epoch word per row), so there is no launch boundary, no dispatch of 768
 // workgroups and no drained chip between them.  Z.evals > 1 needs every workgroup of the grid resident at once (the host checks; else it
@@ -282,7 +286,7 @@ __global__ __launch_bounds__(RED_THREADS, HESS ? 2 : 3) void k_pose_reduce(PoseA
             // arrives WITH the epoch, not a round trip later.
             if (threadIdx.x < 64) {
                 double v = 0.0;
-                // (bounded: ~4 M polls = seconds.  It never gets there -- see "Waiting never deadlocks" above --, but a kernel that can spin
+                // (bounded: ~4 M polls = seconds.  A lone solve never gets there -- see "Waiting" above --, but a kernel that can spin
                 // for ever takes the whole device with it if an assumption about the dispatcher ever fails; past the bound the workgroup goes on
                 // with what it has read, and the solve ends with a wrong pose instead of not at all)
                 for (int spin = 0; spin < (1 << 22); ++spin) {
@@ -349,8 +353,12 @@ __global__ __launch_bounds__(RED_THREADS, HESS ? 2 : 3) void k_pose_reduce(PoseA
             else prow[threadIdx.x] = s;
         }
         if constexpr (TAIL) {
-            // the row's last workgroup to get here runs the update.  The barrier waits for this workgroup's stores above (they have reached
-            // the device's point of coherence when they are acknowledged); then one ticket per workgroup.
+            // the row's last workgroup to get here runs the update.  A device-scope store has reached the device's point of coherence once
+            // it is acknowledged, and only the storing wave's own vmcnt(0) waits for that: the barrier does not (a workgroup-scope fence
+            // adds no vmcnt wait on gfx950).  So every wave waits for its stores, THEN the barrier, then one ticket per workgroup -- the
+            // row's last workgroup, on any XCD, reads every partial row acknowledged.  (A release on the ticket instead brings back the
+            // L2 write-back above.)
+            __builtin_amdgcn_s_waitcnt(RPE_WAIT_VMCNT0);
             __syncthreads();
             if (threadIdx.x == 0) is_last = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nblk - 1;
             __syncthreads();
@@ -360,9 +368,11 @@ __global__ __launch_bounds__(RED_THREADS, HESS ? 2 : 3) void k_pose_reduce(PoseA
             if (threadIdx.x == 0) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // for the next evaluation
             const bool stopped = reduce_tail<PERSIST>(A, uni, states, partials, row, nblk, Z, line);
             if constexpr (PERSIST) {
-                // the tail's device-scope stores (pose line data, state) are acknowledged when this barrier lets the workgroup through; then
-                // the two epoch words of the pose line
+                // the tail's device-scope stores (pose line data, state, history, the ticket reset) are acknowledged before the epoch words
+                // of the pose line go out: each wave waits for its own stores (vmcnt(0)), the barrier then waits for every wave
+                __builtin_amdgcn_s_waitcnt(RPE_WAIT_VMCNT0);
                 __syncthreads();
+                asm volatile("; rpe publish: epoch");                // (anchor for tests/test_pose_publish_isa.py; emits nothing)
                 if (threadIdx.x < 2) __hip_atomic_store((long long*)line + 8 * threadIdx.x, (long long)((it + 1) | (stopped ? EPOCH_STOPPED : 0)), __ATOMIC_RELAXED,
                                                         __HIP_MEMORY_SCOPE_AGENT);
 #ifdef RPE_POSE_PROBE

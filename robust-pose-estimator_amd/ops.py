@@ -329,7 +329,8 @@ def pose_solve(flow, pcl1, pcl2, w1, w2, mask1, mask2, K, loss_weight, iters, mo
     """Device-resident solve.  Returns (T f64 (n,7), vec7 f32 (n,7), log6 f32 (n,6), info int32 (n,4)).
     ``partition_rows=1``: every row's float64 sums are grouped as if it were solved alone (rpe_solve_opts), i.e. the result of a
     row does not depend on the batch it is in, bit for bit.  ``persistent=False`` (RPE_SOLVE_LAUNCH_PER_EVALUATION): one launch per
-    evaluation instead of one for the whole solve -- the same bits, for A/B measurements."""
+    evaluation instead of one for the whole solve -- the same bits, for A/B measurements, and for several solves at once whose grids
+    together exceed the device (include/rpe.h, rpe_solve_opts: concurrent one-launch solves can starve each other)."""
     args, n, h, w = _pose_inputs(flow, pcl1, pcl2, w1, w2, mask1, mask2, K, loss_weight)
     dev = args[0].device
     T = torch.empty(n, 7, dtype=torch.float64, device=dev)
