@@ -8,7 +8,10 @@ source is not under /root/reference, so this restates its published algorithm:
                    the Jacobian as ``[I | -[X]x]``, scripts/train_posenet.py:46-47 slices ``[:, :3]``
                    as translation).
   * exp / log    : unit-quaternion exponential with Taylor guards at ``theta^2 < EPS`` (EPS = 1e-6),
-                   translation through the SO(3) left Jacobian / its inverse.
+                   translation through the SO(3) left Jacobian / its inverse.  Two departures from lietorch's
+                   formulas, both checked against float64 truth in tests/test_se3_cpu.py: the left Jacobian's
+                   coefficients are computed without cancellation, and the logarithm next to a rotation by pi
+                   keeps the angle's distance from pi.
   * mul / inv/act: ``(t1 + R1 t2, q1 q2)``, ``(-R^T t, q*)``, ``R p + t`` with the rotation applied
                    as ``p + w*uv + v x uv``, ``uv = 2 v x p``.
   * LieGroupParameter: tangent-zero tensor subclass whose ``add_`` is the left retraction
@@ -26,6 +29,7 @@ import math
 import torch
 
 EPS = 1e-6
+C2_SERIES_F32 = 1e-2          # float32: theta^2 below which the left Jacobian's c2 is its series (three terms)
 
 
 # ----------------------------------------------------------------------------- quaternion helpers
@@ -90,7 +94,10 @@ def so3_log(q):
     w_small = w.abs() < EPS
     safe_w = torch.where(w_small, torch.ones_like(w), w)
     taylor = 2.0 / safe_w - (2.0 / 3.0) * sq_n / (safe_w * safe_w * safe_w)
-    pi_branch = torch.where(w > 0, math.pi / n, -math.pi / n)
+    # |w| < EPS, a rotation within 2e-6 rad of pi: 2 atan(n / w) = +-(pi - 2 atan(|w| / n)), and atan(x) = x to 1e-18 there (lietorch
+    # returns pi itself, 2e-6 rad off in float64)
+    near_pi = (math.pi - 2.0 * w.abs() / n) / n
+    pi_branch = torch.where(w > 0, near_pi, -near_pi)
     reg = 2.0 * torch.atan(n / safe_w) / n
     coef = torch.where(small, taylor, torch.where(w_small, pi_branch, reg))
     return coef * v
@@ -101,8 +108,13 @@ def so3_left_jacobian(phi):
     small = theta_sq < EPS
     safe_sq = torch.where(small, torch.ones_like(theta_sq), theta_sq)
     theta = torch.sqrt(safe_sq)
-    c1 = torch.where(small, 0.5 - theta_sq / 24.0, (1.0 - torch.cos(theta)) / safe_sq)
+    # not lietorch's (1 - cos(theta)) / theta^2 and (theta - sin(theta)) / theta^3: just above the guard both subtractions cancel (see
+    # csrc/se3_device.h, left_jacobian_mul, which this mirrors)
+    sinc_half = torch.sin(0.5 * theta) / (0.5 * theta)
+    c1 = torch.where(small, 0.5 - theta_sq / 24.0, 0.5 * sinc_half * sinc_half)
     c2 = torch.where(small, 1.0 / 6.0 - theta_sq / 120.0, (theta - torch.sin(theta)) / (safe_sq * theta))
+    if phi.dtype == torch.float32:
+        c2 = torch.where(~small & (theta_sq < C2_SERIES_F32), 1.0 / 6.0 - theta_sq / 120.0 + theta_sq * theta_sq / 5040.0, c2)
     Phi = hat(phi)
     eye = torch.eye(3, dtype=phi.dtype, device=phi.device).expand(Phi.shape)
     return eye + c1[..., None] * Phi + c2[..., None] * (Phi @ Phi)

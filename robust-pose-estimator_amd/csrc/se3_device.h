@@ -1,13 +1,17 @@
 // SE(3) device functions, templated on float/double.
 //
-// Restates the published lietorch algorithm (princeton-vl/lietorch include/so3.h, se3.h; not on disk,
-// unpinned dependency of the reference, README.md:37): unit-quaternion exp/log with Taylor guards at
-// theta^2 < 1e-6, translation through the SO(3) left Jacobian.  Pose layout [tx ty tz qx qy qz qw],
-// tangent [tau phi].  Mirrors oracle/se3.py operation for operation.
+// Follows the published lietorch algorithm (princeton-vl/lietorch include/so3.h, se3.h; not on disk, unpinned dependency of the
+// reference, README.md:37): unit-quaternion exp/log with Taylor guards at theta^2 < 1e-6, translation through the SO(3) left Jacobian.
+// Pose layout [tx ty tz qx qy qz qw], tangent [tau phi].  Mirrors oracle/se3.py operation for operation.
+// It departs from lietorch's formulas in two places, both pinned against float64 truth by tests/test_gpu_se3.py:
+//   left_jacobian_mul : c1 and c2 without cancellation.  lietorch's form gave float32 se3_exp a translation error of 1.3e-4 at 1 mrad
+//                       (tau ~ N(0,1)), this one 2.7e-7, as at every other angle.
+//   so3_log           : for |qw| < 1e-6 the angle keeps its distance 2 |qw| / |qv| from pi (lietorch returns pi, 2e-6 rad off).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #define RPE_SE3_EPS 1e-6
+#define RPE_SE3_C2_SERIES_F32 1e-2          // float32: theta^2 below which the left Jacobian's c2 is its series
 
 template <typename S> struct V3 { S x, y, z; };
 
@@ -66,7 +70,10 @@ template <typename S> __device__ __forceinline__ V3<S> so3_log(const V3<S>& qv, 
     } else {
         S n = sqrt(sq);
         S aw = qw < 0 ? -qw : qw;
-        if (aw < (S)RPE_SE3_EPS) coef = qw > 0 ? PI / n : -PI / n;
+        if (aw < (S)RPE_SE3_EPS) {                 // within 2e-6 rad of pi: 2 atan(n / qw) = +-(pi - 2 atan(aw / n)), atan(x) = x to 1e-18
+            S a = (PI - (S)2.0 * aw / n) / n;
+            coef = qw > 0 ? a : -a;
+        }
         else coef = (S)2.0 * atan(n / qw) / n;
     }
     return scale(qv, coef);
@@ -86,9 +93,17 @@ template <typename S> __device__ __forceinline__ V3<S> left_jacobian_mul(const V
         c1 = (S)0.5 - th2 / (S)24.0;
         c2 = (S)1.0 / (S)6.0 - th2 / (S)120.0;
     } else {
+        // c1 = (1 - cos th) / th^2 as lietorch writes it cancels: at th = 1e-3 cos th = 1 - 5e-7 and the float32 difference keeps
+        // two digits.  1 - cos th = 2 sin^2(th / 2) has no subtraction.
         S th = sqrt(th2);
-        c1 = ((S)1.0 - cos(th)) / th2;
-        c2 = (th - sin(th)) / (th2 * th);
+        S half = (S)0.5 * th;
+        S sh = sin(half) / half;
+        c1 = (S)0.5 * sh * sh;
+        // c2 = (th - sin th) / th^3 cancels the same way; it is multiplied by th^2, so it matters in float32 only, where the series
+        // takes over up to th^2 = 1e-2 (its next term is th^6 / 362880 < 3e-12; there the difference keeps four digits of a term that
+        // is 2e-3 of the result)
+        if (sizeof(S) == 4 && th2 < (S)RPE_SE3_C2_SERIES_F32) c2 = (S)1.0 / (S)6.0 - th2 / (S)120.0 + th2 * th2 / (S)5040.0;
+        else c2 = (th - sin(th)) / (th2 * th);
     }
     return apply_poly(phi, c1, c2, v);
 }
