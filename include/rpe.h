@@ -56,7 +56,8 @@ const char *rpe_version(void);
  *   rpe_surfel_* entry points of frame-to-model tracking (7);  4: rpe_surfel_*_many (K maps per launch, RPE_SURFEL_MAX_MAPS) and
  *   rpe_pose_gate_chain_rows, for tracking several sequences frame to model in one batch (8).  rpe_conv_wino24* and RPE_OP_CONV_WINO24
  *   (Winograd F(2x4,3x3)) were added without a new minor: probe for them with dlsym.  So were rpe_flow_forward_interpolate, rpe_flow_seed
- *   and RPE_OP_FLOW_SEED (warm start of the update loop); the next RPE_ABI_MINOR bump counts them and rpe_conv_wino24*. */
+ *   and RPE_OP_FLOW_SEED (warm start of the update loop), and rpe_ingest_stereo (the one-call input side); the next RPE_ABI_MINOR bump
+ *   counts them and rpe_conv_wino24*. */
 #define RPE_ABI_VERSION 5
 #define RPE_ABI_MINOR 4
 int rpe_abi_minor(void);
@@ -618,6 +619,28 @@ int rpe_remap_nearest(const void *src, int src_is_u8, int c, int h, int w, const
  * a 1-LSB difference to a particular OpenCV build (other interpolation tables, FMA contraction in remapBilinear<float>) would go
  * unnoticed until a golden from real cv2 (oracle/gen_golden.py on a machine that has it) pins both. */
 int rpe_shift_bilinear(const void *src, int src_is_u8, int c, int h, int w, float tx, float ty, void *dst, void *stream);
+
+/* The whole input side in one call: n decoded stereo frames -> the tracker's inputs, bit for bit what the chain
+ * rpe_mask_specularities (left image) -> rpe_resize_crop (both images) + rpe_resize_crop_mask -> rpe_remap_nearest (both images) or
+ * rpe_shift_bilinear (right image) gives frame by frame (dataset/video_dataset.py:55-66; the mask is not rectified there either),
+ * without its intermediates: one launch reads the frames and writes limg, rimg (n,3,out_h,out_w) f32 0..255 and mask (n,1,out_h,out_w)
+ * u8, nothing else.
+ * frames: uint8 HWC.  right == NULL: stacked (n,2h,w,3), the left eye in the upper half (StereoVideoDataset._split_stereo_img);
+ * else frames is the left eye (n,h,w,3) and right the other one.  bgr != 0: the channels are stored B,G,R (as a decoder hands them
+ * over) and are swapped on load.  user_mask: NULL or (n,h,w) u8, non-zero = valid (rpe_mask_specularities' mask argument).
+ * sum_threshold and (resized_h, resized_w, top, left, out_h, out_w) as rpe_mask_specularities / rpe_resize_crop take them.
+ * rect_mode: RPE_INGEST_RECT_NONE; RPE_INGEST_RECT_MAPS with the four (out_h,out_w) f32 maps of rpe_remap_nearest (left x, y, right
+ * x, y); RPE_INGEST_RECT_SHIFT with rpe_shift_bilinear's (tx, ty) for the right image.  Maps and shift are ignored in other modes.
+ * out_w % 4 == 0 (16-byte stores) needs limg / rimg 16-byte and mask 4-byte aligned: RPE_E_BADARG otherwise.  RPE_E_UNSUPPORTED for
+ * a reduction so strong (beyond about 8:1 per axis) that a 64x16 output tile's source footprint does not fit 64 KiB of LDS, n > 65535
+ * is RPE_E_BADARG.  Frames whose base is not 4-byte aligned are read byte by byte (slower, same result). */
+#define RPE_INGEST_RECT_NONE 0
+#define RPE_INGEST_RECT_MAPS 1
+#define RPE_INGEST_RECT_SHIFT 2
+int rpe_ingest_stereo(const uint8_t *frames, const uint8_t *right, int n, int h, int w, int bgr, const uint8_t *user_mask,
+                      int sum_threshold, int resized_h, int resized_w, int top, int left, int out_h, int out_w, int rect_mode,
+                      const float *lmapx, const float *lmapy, const float *rmapx, const float *rmapy, float tx, float ty,
+                      float *limg, float *rimg, uint8_t *mask, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------------------------
  * Surfel map of frame-to-model tracking (core/fusion/surfel_map.py; configuration/infer_scared.yaml: frame2frame False).

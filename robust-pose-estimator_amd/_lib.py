@@ -104,7 +104,7 @@ KIND_OF_ENTRY = {entry: kind for kind, (entry, _) in LIST_OPS.items()}
 
 ABI_MINOR = 3              # RPE_ABI_MINOR of the single-map surfel entry points (rpe_surfel_*)
 ABI_MINOR_MANY = 4         # RPE_ABI_MINOR of rpe_surfel_*_many and rpe_pose_gate_chain_rows: the newest additions this binding calls
-                           # (rpe_conv_wino24*, rpe_flow_forward_interpolate and rpe_flow_seed came later under the same minor:
+                           # (rpe_conv_wino24*, rpe_flow_forward_interpolate, rpe_flow_seed and rpe_ingest_stereo came later under the same minor:
                            # loading binds every SIGNATURES entry, so a library without them fails there)
 SURFEL_MAX_MAPS = 64       # RPE_SURFEL_MAX_MAPS: maps per rpe_surfel_*_many call
 ABI_VERSION = 5            # RPE_ABI_VERSION of include/rpe.h these struct mirrors were written against
@@ -195,6 +195,8 @@ SIGNATURES = {
     'rpe_resize_crop_mask': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     'rpe_remap_nearest': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
     'rpe_shift_bilinear': (_i, [_vp, _i, _i, _i, _i, _c.c_float, _c.c_float, _vp, _vp]),
+    'rpe_ingest_stereo': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _c.c_float, _c.c_float,
+                               _vp, _vp, _vp, _vp]),
     'rpe_surfel_workspace_bytes': (_sz, [_i64, _i, _i]),
     'rpe_surfel_init': (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _fl, _SMP, _vp, _vp]),
     'rpe_surfel_fuse': (_i, [_SMP, _i64, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _fl, _i, _i, _fl, _i, _i, _SMP, _vp, _vp]),

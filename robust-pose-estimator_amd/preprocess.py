@@ -3,6 +3,9 @@
   mask_specularities(img, mask=None, spec_thr=0.96)   dataset/stereo_dataset.py:12-16
   ResizeStereo(size)(left, right, mask)               dataset/transforms.py:20-39
 
+  ingest_stereo(frames_u8, size, rectifier, ...)       all of the above plus StereoRectifier in ONE library call (rpe_ingest_stereo)
+  HostFrameIngest(size, rectifier, depth=2, ...)       the same fed from host frames: pinned staging ring, own stream, events
+
 Images may be passed as the reference passes them (float32 (3,H,W) tensors) or as decoded (uint8 (H,W,3)), which fuses
 the `.permute(2,0,1).float()` of dataset/stereo_dataset.py:35-37 into the resize.  Everything runs in librpe_hip.so
 (rpe_mask_specularities, rpe_resize_crop, rpe_resize_crop_mask); tensors must be on the GPU.
@@ -380,3 +383,244 @@ class StereoRectifier:
         fs = yaml.load(text, Loader=_L)
         return {'lkmat': fs['M1'], 'rkmat': fs['M2'], 'ld': fs['D1'], 'rd': fs['D2'], 'T': fs['T'], 'R': fs['R'],
                 'img_size': (int(fs['Camera.width']), int(fs['Camera.height']))}
+
+
+# ------------------------------------------------------------------------------------------------- one-call ingest
+# scripts/infer_trajectory.py:57,71-77 + dataset/video_dataset.py:40-68 / dataset/stereo_dataset.py:27-41 per frame: colour order,
+# split, mask_specularities on the full-size left image, ResizeStereo, StereoRectifier, host-to-device copy.  rpe_ingest_stereo does
+# everything after the copy in one launch, bit for bit what the chain of the functions above gives.
+RECT_NONE, RECT_MAPS, RECT_SHIFT = 0, 1, 2          # RPE_INGEST_RECT_* of include/rpe.h
+
+
+def ingest_geometry(h, w, size):
+    """(resized_h, resized_w, top, left, out_h, out_w) of ResizeStereo(size) on an (h, w) image; size = (W, H) as there.  Same
+    arithmetic as ResizeStereo.__call__ / _resize_with_crop, same refusal."""
+    th, tw = int(size[1]), int(size[0])
+    scale = max(th / h, tw / w)
+    rh, rw = int(scale * h), int(scale * w)
+    if rh < th or rw < tw:
+        raise _lib.RpeError('ResizeStereo: resized image smaller than the crop (torchvision would zero-pad; not supported)')
+    return rh, rw, int(round((rh - th) / 2.0)), int(round((rw - tw) / 2.0)), th, tw
+
+
+def _rect_args(rectifier, oh, ow):
+    """(mode, four map tensors or Nones, tx, ty) of rpe_ingest_stereo for a StereoRectifier (or None)."""
+    if rectifier is None:
+        return RECT_NONE, (None,) * 4, 0.0, 0.0
+    if rectifier.mode == 'pseudo':                                # StereoRectifier.__call__ -> shift_bilinear
+        lk, rk = rectifier.cal['lkmat'], rectifier.cal['rkmat']
+        return RECT_SHIFT, (None,) * 4, float(np.float32(lk[0][-1] - rk[0][-1])), float(np.float32(lk[1][-1] - rk[1][-1]))
+    m = rectifier._gpu_maps
+    if m is None:
+        raise _lib.RpeError('StereoRectifier: no GPU (the HIP path has no CPU fallback)')
+    maps = tuple(m[k] for k in ('lmap1', 'lmap2', 'rmap1', 'rmap2'))
+    for t in maps:
+        if tuple(t.shape) != (oh, ow) or t.dtype != torch.float32 or not t.is_contiguous():
+            raise _lib.RpeError(f'ingest_stereo: the rectifier\'s maps are {tuple(t.shape)}, the resized image is {(oh, ow)} '
+                                '(construct StereoRectifier with img_size_new = size)')
+    return RECT_MAPS, maps, 0.0, 0.0
+
+
+def _ingest_launch(left, right, n, h, w, bgr, um, thr, geom, rect):
+    """One rpe_ingest_stereo call on torch's current stream into fresh outputs.  left: (n,2h,w,3) with right None, or two (n,h,w,3)."""
+    rh, rw, top, lft, oh, ow = geom
+    mode, maps, tx, ty = rect
+    limg = torch.empty(n, 3, oh, ow, dtype=torch.float32, device=left.device)
+    rimg = torch.empty_like(limg)
+    mask = torch.empty(n, 1, oh, ow, dtype=torch.uint8, device=left.device)
+    check(lib().rpe_ingest_stereo(ptr(left), ptr(right), n, h, w, int(bool(bgr)), ptr(um), thr, rh, rw, top, lft, oh, ow, mode,
+                                  ptr(maps[0]), ptr(maps[1]), ptr(maps[2]), ptr(maps[3]), tx, ty, ptr(limg), ptr(rimg), ptr(mask),
+                                  stream_ptr()), 'rpe_ingest_stereo')
+    return limg, rimg, mask.view(torch.bool)
+
+
+def _frame_dims(shape, stacked):
+    """(n, h, w) per eye of a frame tensor's shape: (n,2h,w,3) / (2h,w,3) stacked, (n,h,w,3) / (h,w,3) per eye."""
+    if len(shape) == 3:
+        shape = (1,) + tuple(shape)
+    if len(shape) != 4 or shape[3] != 3 or (stacked and shape[1] % 2):
+        raise _lib.RpeError(f'ingest: frames must be uint8 ([n,] {"2H" if stacked else "H"}, W, 3), got {tuple(shape)}')
+    return shape[0], shape[1] // 2 if stacked else shape[1], shape[2]
+
+
+def ingest_stereo(frames_u8, size, rectifier=None, user_mask=None, stacked=True, bgr=False, spec_thr=0.96):
+    """Decoded stereo frames on the device -> (limg, rimg, mask) as the trackers take them, in one library call.
+
+    frames_u8: stacked=True: uint8 (n,2H,W,3) or (2H,W,3), left eye in the upper half (the video route); stacked=False: a pair
+    (left, right) of (n,H,W,3) / (H,W,3) tensors (the StereoDataset route).  bgr: channels as cv2 decodes them.  user_mask: (n,H,W) /
+    (H,W) bool or uint8, True = valid.  size = (W, H) of the network input as ResizeStereo takes it; rectifier: a StereoRectifier built
+    for that size, or None.  Returns limg, rimg (n,3,h,w) float32 0..255 and mask (n,1,h,w) bool: for every n what
+    mask_specularities -> ResizeStereo -> StereoRectifier give for that frame, bit for bit."""
+    left, right = (frames_u8, None) if stacked else frames_u8
+    left = _gpu(left, 'frames')
+    right = None if right is None else _gpu(right, 'right frames')
+    if left.dtype != torch.uint8 or (right is not None and (right.dtype != torch.uint8 or right.shape != left.shape)):
+        raise _lib.RpeError('ingest_stereo: frames must be uint8 (and both eyes of one shape)')
+    n, h, w = _frame_dims(left.shape, stacked)
+    um = None
+    if user_mask is not None:
+        um = _gpu(user_mask, 'user_mask')
+        um = um.view(torch.uint8) if um.dtype == torch.bool else um
+        if um.dtype != torch.uint8 or um.numel() != n * h * w or tuple(um.shape[-2:]) != (h, w):
+            raise _lib.RpeError('ingest_stereo: user_mask must be ([n,] H, W) bool/uint8')
+    geom = ingest_geometry(h, w, size)
+    return _ingest_launch(left, right, n, h, w, bgr, um, math.ceil(3 * 255 * spec_thr), geom, _rect_args(rectifier, geom[4], geom[5]))
+
+
+class HostFrameIngest:
+    """Streaming form of ``ingest_stereo`` for frames that arrive on the host (a decoder's output): host-to-device copy and ingest run
+    on this object's own stream, beside whatever the caller's stream is doing (the previous frame's update loop).
+
+        ingest = HostFrameIngest((640, 512), rectifier, depth=2, bgr=True)
+        ingest.push(frame)                      # host uint8 (2H,W,3) torch tensor or numpy array (stacked=False: a (left, right) pair)
+        limg, rimg, mask = ingest.pop()         # oldest pushed frame; the caller's current stream waits for it, the host does not
+        for limg, rimg, mask, stamp in ingest.stream(source): ...        # source yields (frame, stamp) or (frame, user_mask, stamp)
+
+    Lifetimes:
+    * Staging.  Each of the ``depth`` slots owns a pinned host buffer and a device buffer for one push (``chunk`` frames of one push
+      in ``stream``).  A frame that is not already pinned is copied into the slot's host buffer by the CPU; a pinned torch tensor is
+      read by the copy directly, so the caller keeps it unchanged until that frame has been popped and consumed.  A slot's host
+      buffer is rewritten only after the event recorded behind the copy that read it (the host waits there, and only when the ring is
+      full: it was recorded ``depth`` pushes ago); its device buffer is rewritten by the next copy into it, which the stream orders
+      behind the ingest that read it.  No other host synchronisation per frame.
+    * Outputs are FRESH tensors per push: the trackers keep Frame.img / Frame.mask across calls and write into the mask in place, so
+      no output may alias a later frame's.  They are allocated on the ingest stream; ``pop`` makes the caller's current stream wait for
+      the ingest's event and calls ``record_stream`` on them, as PoseEstimator.result does for the encoder outputs, so the caching
+      allocator does not hand their memory out again while the caller's stream still reads them."""
+
+    def __init__(self, size, rectifier=None, depth=2, stacked=True, bgr=False, spec_thr=0.96, device='cuda'):
+        if not torch.cuda.is_available():
+            raise _lib.RpeError('HostFrameIngest: no GPU (the HIP path has no CPU fallback)')
+        if depth < 1:
+            raise ValueError('HostFrameIngest: depth >= 1')
+        self.size, self.rectifier, self.depth, self.stacked, self.bgr = size, rectifier, int(depth), stacked, bgr
+        self.thr = math.ceil(3 * 255 * spec_thr)
+        self.device = torch.device(device, torch.cuda.current_device()) if torch.device(device).index is None else torch.device(device)
+        self._stream = torch.cuda.Stream(device=self.device)
+        self._stream.wait_stream(torch.cuda.current_stream(self.device))      # the rectifier's maps were uploaded there
+        self._slots = [None] * self.depth
+        self._next = 0
+        self._ready = []                                     # [(limg, rimg, mask, event)] in push order
+        self._geom = self._rect = self._dims = None
+
+    def _slot(self, n, h, w, masked):
+        """The next slot of the ring, with buffers for n frames (and masks), free for the host to write."""
+        k, self._next = self._next, (self._next + 1) % self.depth
+        rows = 2 * h if self.stacked else h
+        sl = self._slots[k]
+        if sl is None or sl['host'][0].shape[0] < n or tuple(sl['host'][0].shape[1:]) != (rows, w, 3):
+            if sl is not None:
+                sl['copied'].synchronize()
+            eyes = 1 if self.stacked else 2
+            with torch.cuda.stream(self._stream):
+                sl = {'host': [torch.empty(n, rows, w, 3, dtype=torch.uint8).pin_memory() for _ in range(eyes)],
+                      'dev': [torch.empty(n, rows, w, 3, dtype=torch.uint8, device=self.device) for _ in range(eyes)],
+                      'mhost': None, 'mdev': None, 'copied': torch.cuda.Event()}
+            self._slots[k] = sl
+        else:
+            sl['copied'].synchronize()                       # returns at once unless the ring is full and the copy still pending
+        if masked and (sl['mhost'] is None or sl['mhost'].shape[0] < n):
+            with torch.cuda.stream(self._stream):
+                sl['mhost'] = torch.empty(n, h, w, dtype=torch.uint8).pin_memory()
+                sl['mdev'] = torch.empty(n, h, w, dtype=torch.uint8, device=self.device)
+        return sl
+
+    @staticmethod
+    def _host(t, what):
+        t = torch.from_numpy(np.ascontiguousarray(t)) if isinstance(t, np.ndarray) else t
+        if not isinstance(t, torch.Tensor) or t.is_cuda:
+            raise _lib.RpeError(f'HostFrameIngest: {what} must be a host torch tensor or numpy array (device tensors: ingest_stereo)')
+        t = t.view(torch.uint8) if t.dtype == torch.bool else t
+        if t.dtype != torch.uint8:
+            raise _lib.RpeError(f'HostFrameIngest: {what} must be uint8')
+        return t.contiguous()
+
+    def push(self, frame, user_mask=None):
+        """Enqueue one host frame: copy and ingest go onto the ingest stream, nothing waits for them."""
+        self._push_many([frame], None if user_mask is None else [user_mask])
+
+    def _push_many(self, frames, masks):
+        n = len(frames)
+        eyes = [[self._host(f, 'frame')] for f in frames] if self.stacked else [[self._host(e, 'frame') for e in f] for f in frames]
+        _, h, w = _frame_dims(eyes[0][0].shape, self.stacked)
+        for f in eyes:
+            for e in f:
+                if e.dim() != 3 or e.shape != eyes[0][0].shape:
+                    raise _lib.RpeError('HostFrameIngest: every frame of a push must be one uint8 (H,W,3) image of the same size')
+        if self._dims != (h, w):
+            self._geom = ingest_geometry(h, w, self.size)
+            self._rect = _rect_args(self.rectifier, self._geom[4], self._geom[5])
+            self._dims = (h, w)
+        sl = self._slot(n, h, w, masks is not None)
+        with torch.cuda.stream(self._stream):
+            pinned = [all(e.is_pinned() for e in f) for f in eyes]
+            for j, f in enumerate(eyes):
+                for e, host, dev in zip(f, sl['host'], sl['dev']):
+                    if pinned[j]:
+                        dev[j].copy_(e, non_blocking=True)   # read by the copy directly
+                    else:
+                        host[j].copy_(e)                     # CPU copy into the pinned slot
+            for host, dev in zip(sl['host'], sl['dev']):
+                if not any(pinned):
+                    dev[:n].copy_(host[:n], non_blocking=True)
+                else:
+                    for j in range(n):
+                        if not pinned[j]:
+                            dev[j].copy_(host[j], non_blocking=True)
+            um = None
+            if masks is not None:
+                for j, m in enumerate(masks):
+                    m = self._host(m, 'user_mask')
+                    if tuple(m.shape) != (h, w):
+                        raise _lib.RpeError('HostFrameIngest: user_mask must be (H,W) bool/uint8')
+                    sl['mhost'][j].copy_(m)
+                sl['mdev'][:n].copy_(sl['mhost'][:n], non_blocking=True)
+                um = sl['mdev']
+            sl['copied'].record(self._stream)
+            out = _ingest_launch(sl['dev'][0], None if self.stacked else sl['dev'][1], n, h, w, self.bgr, um, self.thr, self._geom, self._rect)
+            done = torch.cuda.Event()
+            done.record(self._stream)
+        self._ready.append(out + (done,))
+
+    def __len__(self):
+        return len(self._ready)
+
+    def pop(self):
+        """(limg, rimg, mask) of the oldest push; the caller's current stream waits for its ingest, the host does not."""
+        if not self._ready:
+            raise RuntimeError('HostFrameIngest.pop() without a pushed frame')
+        limg, rimg, mask, done = self._ready.pop(0)
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_event(done)
+        for t in (limg, rimg, mask):
+            t.record_stream(cur)
+        return limg, rimg, mask
+
+    def stream(self, source, chunk=1):
+        """Generator over ``source`` -- an iterable of (frame, stamp) or (frame, user_mask, stamp) -- that keeps ``depth`` pushes in
+        flight and yields (limg, rimg, mask, stamp) per frame, track_sequence's format.  chunk = c: c frames per copy and per ingest
+        call (n = c); the items yielded are the same (rows of the chunk's outputs)."""
+        it = iter(source)
+        stamps = []
+
+        def fill():
+            items = []
+            for item in it:
+                items.append(item)
+                if len(items) >= chunk:
+                    break
+            if not items:
+                return False
+            masked = len(items[0]) == 3
+            self._push_many([i[0] for i in items], [i[1] for i in items] if masked else None)
+            stamps.append([i[-1] for i in items])
+            return True
+        for _ in range(self.depth):
+            if not fill():
+                break
+        while stamps:
+            limg, rimg, mask = self.pop()
+            st = stamps.pop(0)
+            fill()                                           # the next copy is queued before the consumer queues this frame's work
+            for j, s in enumerate(st):
+                yield limg[j:j + 1], rimg[j:j + 1], mask[j:j + 1], s

@@ -54,6 +54,35 @@ def track_sequence(estimator, frames, start_stamp=0, chunk=1):
     return traj
 
 
+def track_host_frames(estimator, source, ingest, start_stamp=0, pipelined=True):
+    """``track_sequence`` from frames on the host.  ``source`` yields (frame, stamp) or (frame, user_mask, stamp) with ``frame`` a decoded
+    uint8 host frame, ``ingest`` is a preprocess.HostFrameIngest: its stream copies and prepares frame t+1 (and t+2, with depth 2) while
+    the tracker works on frame t.  ``pipelined``: the frames go through ``estimator.submit`` / ``result``, so frame t+1's encoders too
+    run beside frame t's update loop; an estimator that refuses ``submit`` (the surfel trackers: frame t+1 is tracked against the map
+    frame t fused) is driven through ``forward`` as with pipelined=False -- copy and ingest still overlap.  Same kernels on the same
+    inputs: the trajectory is that of ``track_sequence`` on the prepared frames, bit for bit."""
+    traj = [{'camera-pose': estimator.last_pose.vec().reshape(7).detach().cpu(), 'timestamp': start_stamp}]
+    waiting = []                                                   # stamps of the submitted frames
+
+    def collect(pose, stamp):
+        traj.append({'camera-pose': pose.vec().reshape(7).detach().cpu(), 'timestamp': stamp})
+    for limg, rimg, mask, stamp in ingest.stream(source):
+        if pipelined:
+            try:
+                estimator.submit(limg, rimg, mask)
+            except RuntimeError:                                   # refused before anything was queued
+                pipelined = False
+        if not pipelined:
+            collect(estimator(limg, rimg, mask)[0], stamp)
+            continue
+        waiting.append(stamp)
+        if len(waiting) > 1:                                       # frame t+1 is queued: now frame t
+            collect(estimator.result()[0], waiting.pop(0))
+    while waiting:
+        collect(estimator.result()[0], waiting.pop(0))
+    return traj
+
+
 def track_sequences(estimator, sequences, start_stamps=None):
     """``track_sequence`` for K sequences at once on a MultiSurfelPoseEstimator: ``sequences[k]`` yields (limg, rimg, mask, stamp) of
     sequence k (row k of the estimator).  Every lockstep step takes the next frame of each sequence that has one and advances those
