@@ -56,8 +56,8 @@ const char *rpe_version(void);
  *   rpe_surfel_* entry points of frame-to-model tracking (7);  4: rpe_surfel_*_many (K maps per launch, RPE_SURFEL_MAX_MAPS) and
  *   rpe_pose_gate_chain_rows, for tracking several sequences frame to model in one batch (8).  rpe_conv_wino24* and RPE_OP_CONV_WINO24
  *   (Winograd F(2x4,3x3)) were added without a new minor: probe for them with dlsym.  So were rpe_flow_forward_interpolate, rpe_flow_seed
- *   and RPE_OP_FLOW_SEED (warm start of the update loop), and rpe_ingest_stereo (the one-call input side); the next RPE_ABI_MINOR bump
- *   counts them and rpe_conv_wino24*. */
+ *   and RPE_OP_FLOW_SEED (warm start of the update loop), rpe_ingest_stereo (the one-call input side) and rpe_pose_quality /
+ *   rpe_pose_quality_workspace_bytes (the solve-quality report); the next RPE_ABI_MINOR bump counts them and rpe_conv_wino24*. */
 #define RPE_ABI_VERSION 5
 #define RPE_ABI_MINOR 4
 int rpe_abi_minor(void);
@@ -157,6 +157,38 @@ int rpe_pose_solve_ex(const float *flow, const float *pcl1, const float *pcl2, c
                       const uint8_t *mask1, const uint8_t *mask2, const float *K, const float *loss_weight,
                       int n, int h, int w, int mode, int iters, const rpe_solve_opts *opts, double *T_out, float *vec7,
                       float *log6, int32_t *info, void *workspace, void *stream);
+
+/* Solve-quality report (opt-in; not part of any solve): everything a consumer of the pose needs to judge HOW WELL a frame was solved,
+ * evaluated in float64 at a given pose T (n,7) f64 -- normally the pose rpe_pose_solve* returned.  Inputs as rpe_pose_reduce; the gates are
+ * those of the objective (core/pose/pose_head.py:12-58): the reprojection term keeps a pixel unless its weighted residual is NaN / Inf, its
+ * flow target leaves the image or mask1 is false; the 3-D term keeps mask1 & mask2; depth is clamped at 1e-12 -- handled exactly as
+ * rpe_pose_reduce handles them.  out (n,64) f64 per row:
+ *   [0]      n2d   pixels the reprojection term keeps
+ *   [1]      n3d   pixels the 3-D term keeps
+ *   [2] [3]  sum of w1 over the kept 2-D pixels, sum of w2 over the kept 3-D pixels
+ *   [4] [5]  sum w1 (ex^2 + ey^2), sum w2 |e3|^2 over the kept pixels (= loss2d (hw)^2, loss3d hw)
+ *   [6] [7]  unweighted RMS of the kept residuals: sqrt(sum (ex^2 + ey^2) / n2d) in pixels, sqrt(sum |e3|^2 / n3d) in the solve's
+ *            (normalised) units; 0 / 0 gives NaN
+ *   [8]      f = lw[1] loss2d + lw[0] loss3d
+ *   [9]      max |g|, g unclipped
+ *   [10..15] g = df/dxi (left perturbation, xi = (tau, phi))
+ *   [16..51] C (6x6, row-major), see below
+ *   [52]     pd: 1 if the Cholesky factorisation of H succeeded and m > 6 and f is finite, else 0; when 0, C is all NaN
+ *   [53]     m = 2 n2d + 3 n3d, the number of scalar residuals
+ *   [54..63] zero, reserved
+ * C = (2 f / (m - 6)) H^-1 with H the Gauss-Newton Hessian of rpe_pose_reduce (H = 2 J^T W J, f = sum W r^2): the usual
+ * sigma^2 (J^T W J)^-1 with sigma^2 = f / (m - 6), i.e. the FORMAL covariance of the weighted least-squares fit in the left tangent
+ * (tau, phi) of T.  It is invariant to a common scale of the weights and says how well the data constrain the pose under the fit's own
+ * noise model; how it is calibrated against true pose error depends on the trained weight heads and cannot be measured with the seeded
+ * weights this repository ships -- treat it as a relative measure between frames until it has been calibrated on real weights.
+ * A NaN residual that the gate removes still reaches g (0 * NaN, as in the reference's autograd), not f, H or C.
+ * Two launches on `stream`: a streaming pass whose workgroups write partial sums, and one workgroup per row that adds them in index order,
+ * factors and inverts H.  The pixel partition depends on (h, w) only, so a row's 64 slots do not depend on the batch, bit for bit.
+ * workspace: rpe_pose_quality_workspace_bytes(n, h, w) bytes.  Status codes as rpe_pose_reduce. */
+size_t rpe_pose_quality_workspace_bytes(int n, int h, int w);
+int rpe_pose_quality(const float *flow, const float *pcl1, const float *pcl2, const float *w1, const float *w2,
+                     const uint8_t *mask1, const uint8_t *mask2, const float *K, const float *loss_weight,
+                     const double *T, int n, int h, int w, double *out, void *workspace, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Backward of the declarative pose layer (training): replaces DeclarativeNodeLie.gradient /

@@ -141,6 +141,8 @@ SIGNATURES = {
     'rpe_pose_solve': (_i, [_vp] * 9 + [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     'rpe_pose_solve_opts': (_i, [_vp] * 9 + [_i, _i, _i, _i, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     'rpe_pose_solve_ex': (_i, [_vp] * 9 + [_i, _i, _i, _i, _i, _c.POINTER(SolveOpts), _vp, _vp, _vp, _vp, _vp, _vp]),
+    'rpe_pose_quality_workspace_bytes': (_sz, [_i, _i, _i]),
+    'rpe_pose_quality': (_i, [_vp] * 10 + [_i, _i, _i, _vp, _vp, _vp]),
     'rpe_pose_backward_workspace_bytes': (_sz, [_i, _i, _i]),
     'rpe_pose_backward_moments': (_i, [_vp] * 10 + [_i, _i, _i, _vp, _vp, _vp]),
     'rpe_pose_backward_grads': (_i, [_vp] * 11 + [_i, _i, _i] + [_vp] * 6),

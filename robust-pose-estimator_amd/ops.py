@@ -345,6 +345,28 @@ def pose_solve(flow, pcl1, pcl2, w1, w2, mask1, mask2, K, loss_weight, iters, mo
     return T, vec7, log6, info
 
 
+QUALITY_SLOTS = 64
+
+
+def pose_quality(flow, pcl1, pcl2, w1, w2, mask1, mask2, K, loss_weight, T):
+    """rpe_pose_quality: the solve-quality report at T (n,7) f64 -> (n,64) f64 (slot table: include/rpe.h; ``quality_fields`` names
+    them).  Two launches on the current stream, no host synchronisation; a row's slots do not depend on its batch, bit for bit."""
+    args, n, h, w = _pose_inputs(flow, pcl1, pcl2, w1, w2, mask1, mask2, K, loss_weight)
+    T = _dev(T.reshape(n, 7), torch.float64, 'T')
+    out = torch.empty(n, QUALITY_SLOTS, dtype=torch.float64, device=T.device)
+    ws = torch.empty(lib().rpe_pose_quality_workspace_bytes(n, h, w), dtype=torch.uint8, device=T.device)
+    check(lib().rpe_pose_quality(*[ptr(a) for a in args], ptr(T), n, h, w, ptr(out), ptr(ws), stream_ptr()), 'rpe_pose_quality')
+    return out
+
+
+def quality_fields(out):
+    """Named views of rpe_pose_quality's (n,64) rows: cov (n,6,6), pd, n2d, n3d, sum_w1, sum_w2, sse2d, sse3d, rms2d_px, rms3d, f,
+    grad_max, g (n,6), m.  Views only: works on the device and on the host, copies nothing."""
+    return dict(cov=out[:, 16:52].reshape(-1, 6, 6), pd=out[:, 52], n2d=out[:, 0], n3d=out[:, 1], sum_w1=out[:, 2], sum_w2=out[:, 3],
+                sse2d=out[:, 4], sse3d=out[:, 5], rms2d_px=out[:, 6], rms3d=out[:, 7], f=out[:, 8], grad_max=out[:, 9], g=out[:, 10:16],
+                m=out[:, 53])
+
+
 def pose_backward_moments(flow, pcl1, pcl2, w1, w2, mask1, mask2, K, loss_weight, T):
     """At pose T (n,7) f64: (g2u (n,6), g3u (n,6), H (n,6,6)) -- unit-loss-weight tangent gradients of the two terms
     and the symmetrised fYY of the reference's backward (declerative_node_lie.py:40-51)."""

@@ -49,6 +49,35 @@ class Frame:
         return self
 
 
+QUALITY_F64 = ('pd', 'n2d', 'n3d', 'rms2d_px', 'rms3d', 'f', 'grad_max')
+QUALITY_I32 = ('n_iter', 'func_evals', 'stop_reason')
+
+
+def blank_quality(n, device):
+    """The report of n frames that had no solve (a sequence's first frame): NaN covariance, RMS, f and gradient, pd = 0, zero counts."""
+    nan = float('nan')
+    q = dict(cov=torch.full((n, 6, 6), nan, dtype=torch.float64, device=device))
+    for k in QUALITY_F64:
+        q[k] = torch.full((n,), 0.0 if k in ('pd', 'n2d', 'n3d') else nan, dtype=torch.float64, device=device)
+    for k in QUALITY_I32:
+        q[k] = torch.zeros(n, dtype=torch.int32, device=device)
+    return q
+
+
+def denormalise_quality(q, inv_scale):
+    """PoseNet.infer's quality dict (the solve's normalised depth units) in the units of the pose the tracker returns
+    (core/pose/pose_estimator.py:90 scales the translation by 1 / scale): rows and columns 0..2 of ``cov`` and ``rms3d`` times 1 / scale
+    (millimetres); counts, ``rms2d_px`` and the solver's bookkeeping have no unit; ``f`` and ``grad_max`` stay the solver's own numbers.
+    Device arithmetic only."""
+    out = dict(q)
+    cov = q['cov'].clone()
+    cov[:, :3, :] *= inv_scale
+    cov[:, :, :3] *= inv_scale
+    out['cov'] = cov
+    out['rms3d'] = q['rms3d'] * inv_scale
+    return out
+
+
 class PoseEstimator(torch.nn.Module):
     _f2m = False
 
@@ -93,6 +122,12 @@ class PoseEstimator(torch.nn.Module):
         self.warm_start = bool(config.get('warm_start', False))
         self._flow_low = None                                         # the last accepted temporal pass's 1/8 flow (1,2,h/8,w/8), or None
         self._low_pass = None                                         # ... of the pass in flight, until the gate has seen it
+        # ``report_quality: True``: every call leaves ``last_quality`` -- PoseNet.infer's solve-quality report (covariance of the relative
+        # pose's left tangent, counts, RMS residuals, the solver's stop reason ...), de-normalised like the pose, one row per frame, as device
+        # tensors -- whether or not the gate accepts the frame.  Two more launches per frame and no host synchronisation; off, nothing changes.
+        self.report_quality = bool(config.get('report_quality', False))
+        self.last_quality = None
+        self._q_pass = None                                           # the report of the pass in flight
 
     @property
     def device(self):
@@ -105,7 +140,16 @@ class PoseEstimator(torch.nn.Module):
         self._enc_cache = None
         self._pending = []
         self._flow_low = None
+        self.last_quality = self._q_pass = None
         return self
+
+    def _set_quality(self, q, n, device):
+        """``last_quality`` from a pass's report ``q`` (None: n frames without a solve)."""
+        if self.report_quality:
+            self.last_quality = blank_quality(n, device) if q is None else denormalise_quality(q, self._inv_scale)
+
+    def _quality_kw(self):
+        return {'ret_quality': True} if self.report_quality else {}
 
     def _flow_init(self):
         """The temporal pass's flow_init / ret_lowres keywords of PoseNet.infer: {} without warm start."""
@@ -173,6 +217,7 @@ class PoseEstimator(torch.nn.Module):
         # :81-91 in one launch (ops.pose_gate_chain): the gate isnan | |log| > 0.1 -> identity, de-normalisation of the depth scaling and
         # last_pose <- last_pose * rel^-1, with ONE host synchronisation (the success flag) instead of a dozen element-wise launches and two
         rel, pose, ok = ops.pose_gate_chain(rel_pose.data.reshape(1, 7), self.last_pose.data, self._inv_scale, 1.0e-1)
+        self._set_quality(self._q_pass, 1, limg.device)
         low, self._low_pass = self._low_pass, None
         if self._pending:
             self._start_encoders(self._pending[0])            # (submit / result) the next frame's encoders, before the host waits for this one
@@ -202,9 +247,12 @@ class PoseEstimator(torch.nn.Module):
         prev = self.frame
         masks = masks.bool().contiguous()
         self.last_pose = self.last_pose.to(limgs.device)
-        vec7, depth2, weights, flow, stereo_flow, cache = self.model.infer_chunk(
+        r = self.model.infer_chunk(
             prev.img, limgs, rimgs, self.intrinsics, self.baseline * self.scale, depth0=prev.depth * self.scale, mask0=prev.mask,
-            masks=masks, stereo_flow0=prev.flow, cache0=self._enc_cache, depth_roundtrip=self.scale)
+            masks=masks, stereo_flow0=prev.flow, cache0=self._enc_cache, depth_roundtrip=self.scale, **self._quality_kw())
+        vec7, depth2, weights, flow, stereo_flow, cache = r[:6]
+        if self.report_quality:
+            self._set_quality(r[6], c, limgs.device)
         self._enc_cache = cache if self.reuse_features else None
         rel, poses, ok = ops.pose_gate_chain(vec7.reshape(c, 7), self.last_pose.data, self._inv_scale, 1.0e-1)   # :81-91, every frame
         bad = ok == 0
@@ -222,7 +270,7 @@ class PoseEstimator(torch.nn.Module):
 
     def get_pose_f2f(self, enc=None):
         flow = None
-        self._low_pass = None
+        self._low_pass = self._q_pass = None
         if self.last_frame is None:
             rel = SE3.IdentityLike(self.last_pose)
             depth, stereo_flow, valid, cache = self.model.flow2depth(self.frame.img, self.frame.rimg,
@@ -231,12 +279,16 @@ class PoseEstimator(torch.nn.Module):
             self.frame.depth = depth / self.scale
             self.frame.flow = stereo_flow
             return rel, None, None, None
-        rel, depth1, depth2, weights, flow, stereo_flow, cache = self.model.infer(
+        r = self.model.infer(
             self.last_frame.img, self.frame.img, self.intrinsics, self.baseline * self.scale,
             depth1=self.last_frame.depth * self.scale, image2r=self.frame.rimg, mask1=self.last_frame.mask,
             mask2=self.frame.mask, stereo_flow1=self.last_frame.flow, ret_details=True,
             cache1=self._enc_cache, ret_cache=True, **({'enc2': enc} if enc is not None and self._enc_cache is not None else {}),
-            **self._flow_init())
+            **self._flow_init(), **self._quality_kw())
+        rel, depth1, depth2, weights, flow, stereo_flow = r[:6]
+        cache = r[-1]
+        if self.report_quality:
+            self._q_pass = r[6]
         if self.warm_start:
             self._low_pass = cache.pop('time_flow_low')
         self._enc_cache = cache if self.reuse_features else None
@@ -288,6 +340,7 @@ class SurfelPoseEstimator(PoseEstimator):
                                    pmat=self.last_pose, average_pts=self.config['average_pts'])
         rel_pose, ret_frame, flow, weights = self.get_pose_f2m()
         rel, pose, ok = ops.pose_gate_chain(rel_pose.data.reshape(1, 7), self.last_pose.data, self._inv_scale, 1.0e-1)   # :81-91
+        self._set_quality(self._q_pass, 1, limg.device)
         self.t_enqueued = time.perf_counter()
         self.success = bool(ok[0])
         if not self.success:
@@ -307,9 +360,10 @@ class SurfelPoseEstimator(PoseEstimator):
         r = self.model.infer(
             model_frame.img, self.frame.img, self.intrinsics, self.baseline * self.scale, depth1=model_frame.depth * self.scale,
             image2r=self.frame.rimg, mask1=model_frame.mask, mask2=self.frame.mask, stereo_flow1=model_frame.flow, ret_details=True,
-            **(dict(warm, ret_cache=True) if warm else {}))
+            **(dict(warm, ret_cache=True) if warm else {}), **self._quality_kw())
         rel, depth1, depth2, weights, flow, stereo_flow = r[:6]
-        self._low_pass = r[6]['time_flow_low'] if warm else None
+        self._low_pass = r[-1]['time_flow_low'] if warm else None
+        self._q_pass = r[6] if self.report_quality else None
         self.frame.depth = depth2 / self.scale
         self.frame.flow = stereo_flow
         model_frame.confidence = weights[0]
@@ -435,15 +489,17 @@ class MultiSurfelPoseEstimator(PoseEstimator):
         try:
             r = self.model.infer(
                 model.img, limgs, K, baseline, depth1=model.depth * self.scale, image2r=rimgs, mask1=model.mask, mask2=masks,
-                stereo_flow1=model.flow, ret_details=True, **warm)
+                stereo_flow1=model.flow, ret_details=True, **warm, **self._quality_kw())
             rel, depth1, depth2, weights, flow, stereo_flow = r[:6]
         finally:
             if problem is not None:
                 problem.partition_rows = keep
         rel_g, pose, ok = ops.pose_gate_chain_rows(rel.data.reshape(R, 7), last, self._inv_scale, 1.0e-1)     # :81-91, row by row
+        if self.report_quality:
+            self._set_quality(r[6], R, dev)                                # row j belongs to sequence rows[j]
         self.t_enqueued = time.perf_counter()
         okh = ok.cpu().bool()                                              # the lockstep frame's one host synchronisation
-        low = r[6]['time_flow_low'] if warm else None
+        low = r[-1]['time_flow_low'] if warm else None
         for j, k in enumerate(rows):
             self.success[k] = bool(okh[j])
             if not self.success[k]:

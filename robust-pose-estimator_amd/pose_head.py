@@ -34,7 +34,8 @@ class DPoseSE3Head:
         self.lbgfs_iters = lbgfs_iters
         self.solver = solver
         self.losses = []
-        self.last_info = None
+        self.last_info = None          # info (n,4) int32 of the last solve [n_iter, func_evals, stop_reason, 0], on the device
+        self.last_T = None             # its float64 pose (n,7), on the device (the layer's outputs are float32)
         # 1: every row is reduced with the block partition it would get alone (rpe_solve_opts.partition_rows), so a row's pose does not
         # depend on the batch it is solved in, bit for bit; 0: the partition follows the batch (one resident round of workgroups)
         self.partition_rows = 0
@@ -53,8 +54,17 @@ class DPoseSE3Head:
     def solve(self, *xs):
         xs = [x.detach() if isinstance(x, torch.Tensor) else x for x in xs]
         T, vec7, log6, info = ops.pose_solve(*xs, iters=self.lbgfs_iters, mode=self.mode, partition_rows=self.partition_rows)
-        self.last_info = info
+        self.last_info, self.last_T = info, T
         return SE3(T[:, None]), (vec7, log6)
+
+    def quality(self, *xs, T=None):
+        """The solve-quality report (ops.pose_quality, (n,64) f64 on the device) of the layer's inputs ``xs`` at pose ``T`` (SE3 or
+        (n,[1,]7) tensor; default: the float64 pose of the last solve).  Opt-in: nothing calls it unless asked to."""
+        T = self.last_T if T is None else (T.data if isinstance(T, SE3) else T)
+        if T is None:
+            raise ValueError('DPoseSE3Head.quality: no pose given and nothing solved yet')
+        xs = [x.detach() if isinstance(x, torch.Tensor) else x for x in xs]
+        return ops.pose_quality(*xs, T.detach().reshape(xs[0].shape[0], 7).double())
 
     def gradient(self, *xs, y, v, needs=None, eps=1e-3):
         """DeclarativeNodeLie.gradient (declerative_node_lie.py:13-82) at the layer's float32 output pose ``y`` (n,7) for

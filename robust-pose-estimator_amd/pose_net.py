@@ -165,29 +165,46 @@ class PoseNet(nn.Module):
 
     @torch.no_grad()
     def infer(self, image1l, image2l, intrinsics, baseline, depth1, image2r, mask1, mask2, stereo_flow1,
-              ret_details=False, cache1=None, ret_cache=False, enc2=None, flow_init=None, ret_lowres=False):
+              ret_details=False, cache1=None, ret_cache=False, enc2=None, flow_init=None, ret_lowres=False, ret_quality=False):
         """``flow_init`` / ``ret_lowres``: see stages (warm start of the temporal pairs; the temporal 1/8 flow comes back as the returned
-        cache's 'time_flow_low', so ret_lowres needs ret_cache)."""
+        cache's 'time_flow_low', so ret_lowres needs ret_cache).
+        ``ret_quality`` (needs ret_details): the details gain, behind stereo_flow2, the solve-quality report of the n rows as a dict of
+        device tensors (``_quality``): two more launches, no host synchronisation; everything else is unchanged bit for bit."""
         if enc2 is not None and cache1 is None:
             raise ValueError('infer: enc2 (the new frame encoded ahead of the call) needs cache1 (the previous frame\'s encoder outputs)')
         if ret_lowres and not ret_cache:
             raise ValueError("infer: ret_lowres returns the temporal 1/8 flow in the cache dict ('time_flow_low'): it needs ret_cache=True")
+        if ret_quality and not ret_details:
+            raise ValueError('infer: ret_quality adds the quality report to the details: it needs ret_details=True')
         s = self.stages(image1l, image2l, intrinsics, baseline, depth1, image2r, mask1, mask2, stereo_flow1, cache1, enc2=enc2,
                         flow_init=flow_init, ret_lowres=ret_lowres)
         mask2.copy_(s['mask2'])                               # `mask2 &= valid` mutates the caller's tensor (:77)
         n = image1l.shape[0]
         lw = self.loss_weight.detach()[None, :].repeat(n, 1)
-        vec7, _ = self.pose_head(s['time_flow'], s['pcl1'], s['pcl2w'], s['w2d'], s['w3d'], mask1.bool(), s['mask2w'],
-                                 s['intrinsics'], lw)
+        inputs = (s['time_flow'], s['pcl1'], s['pcl2w'], s['w2d'], s['w3d'], mask1.bool(), s['mask2w'], s['intrinsics'], lw)
+        vec7, _ = self.pose_head(*inputs)
         pose = SE3(vec7[:, 0]) if n > 1 else SE3(vec7)[0]     # reference returns SE3(pose_se3)[0] for its n == 1
         out = (pose, depth1, s['depth2'], (s['w2d'], s['w3d']), s['time_flow'], s['stereo_flow2']) if ret_details else pose
+        if ret_quality:
+            out = (*out, self._quality(inputs))
         if ret_cache:
             return (*out, s['cache2']) if ret_details else (out, s['cache2'])
         return out
 
+    def _quality(self, inputs):
+        """The report of the solve that has just run on ``inputs``, at its float64 pose: cov (n,6,6), pd, n2d, n3d, rms2d_px, rms3d, f,
+        grad_max (f64; ops.quality_fields) and n_iter, func_evals, stop_reason (int32, the solve's info).  Device tensors, in the
+        solve's normalised units."""
+        problem = self.pose_head.problem
+        q = ops.quality_fields(problem.quality(*inputs))
+        info = problem.last_info
+        d = {k: q[k] for k in ('cov', 'pd', 'n2d', 'n3d', 'rms2d_px', 'rms3d', 'f', 'grad_max')}
+        d.update(n_iter=info[:, 0], func_evals=info[:, 1], stop_reason=info[:, 2])
+        return d
+
     @torch.no_grad()
     def infer_chunk(self, image0l, imagesl, imagesr, intrinsics, baseline, depth0, mask0, masks, stereo_flow0, cache0=None,
-                    depth_roundtrip=None):
+                    depth_roundtrip=None, ret_quality=False):
         """c consecutive calls of ``infer`` as ONE pass: frame t of the chunk is ``infer(image1l = frame t-1, image2l = frame t, ...)``
         with frame -1 = (image0l, depth0, mask0, stereo_flow0) and, for t > 0, depth1 / mask1 / stereo_flow1 = the depth2 / mask2 /
         stereo_flow2 that call t-1 produced (core/pose/pose_estimator.py:113-122 feeds them back through its Frame) -- a shift by one
@@ -198,7 +215,7 @@ class PoseNet(nn.Module):
         consecutive calls (it stores depth / scale and hands over depth * scale, pose_estimator.py:107,116,121).
         Every kernel on the way computes a row independently of its batch (tests), and the solve runs with partition_rows = 1, so the
         result is BIT-IDENTICAL to the c single calls.  Returns (vec7 (c,7) f32, depth2 (c,1,h,w), (w2d, w3d), time_flow (c,2,h,w),
-        stereo_flow2 (c,2,h,w), cache of the last frame)."""
+        stereo_flow2 (c,2,h,w), cache of the last frame[, the quality dict of ``infer`` with one row per frame, with ``ret_quality``])."""
         c = imagesl.shape[0]
         intrinsics = intrinsics.expand(c, 3, 3).contiguous()
         baseline = baseline.expand(c).contiguous()
@@ -239,10 +256,12 @@ class PoseNet(nn.Module):
         problem = self.pose_head.problem
         keep, problem.partition_rows = problem.partition_rows, 1
         try:
-            vec7, _ = self.pose_head(time_flow, g['pcl1'], g['pcl2w'], w2d, w3d, mask1, g['mask2w'], intrinsics, lw)
+            inputs = (time_flow, g['pcl1'], g['pcl2w'], w2d, w3d, mask1, g['mask2w'], intrinsics, lw)
+            vec7, _ = self.pose_head(*inputs)
         finally:
             problem.partition_rows = keep
-        return vec7[:, 0], g['depth2'], (w2d, w3d), time_flow, stereo_flow2, dict(fmap=fl[c - 1:], cnet=cn[c - 1:])
+        out = (vec7[:, 0], g['depth2'], (w2d, w3d), time_flow, stereo_flow2, dict(fmap=fl[c - 1:], cnet=cn[c - 1:]))
+        return (*out, self._quality(inputs)) if ret_quality else out
 
     def init_from_raft(self, raft_ckp):
         state = torch.load(raft_ckp, map_location='cpu')

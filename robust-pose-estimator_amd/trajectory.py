@@ -22,16 +22,53 @@ def pose_matrices(vec7):
     return M
 
 
-def track_sequence(estimator, frames, start_stamp=0, chunk=1):
+class _QualityLog:
+    """The ``quality=True`` side of the tracking loops: keeps each call's ``estimator.last_quality`` (device tensors, nothing waits) and
+    attaches one row per trajectory item in ONE copy to the host at the end of the run.  The initial pose, which no frame produced,
+    gets the report of a frame without a solve (NaN covariance, pd = 0), like a sequence's first frame."""
+
+    def __init__(self, estimator, quality):
+        self.on = bool(quality)
+        if self.on and not getattr(estimator, 'report_quality', False):
+            raise ValueError("quality=True needs an estimator built with report_quality: True in its config")
+        self.estimator, self.parts, self.owners = estimator, [], []
+
+    def start(self, items):
+        """``items``: the trajectory items of the initial poses."""
+        if self.on:
+            from .pose_estimator import blank_quality
+            self.add(items, blank_quality(len(items), self.estimator.device))
+
+    def add(self, items, q=None):
+        """``items``: the trajectory items the estimator's last call produced, in the row order of its ``last_quality``."""
+        if self.on:
+            self.parts.append(self.estimator.last_quality if q is None else q)
+            self.owners.extend(items)
+
+    def finish(self):
+        if not self.on or not self.parts:
+            return
+        import torch
+        host = {k: torch.cat([p[k] for p in self.parts]).cpu() for k in self.parts[0]}
+        for j, item in enumerate(self.owners):
+            item['quality'] = {k: v[j] for k, v in host.items()}
+
+
+def track_sequence(estimator, frames, start_stamp=0, chunk=1, quality=False):
     """The loop of infer_trajectory.py:70-91.  ``frames`` yields (limg, rimg, mask, stamp) already on the device.
     Returns [{'camera-pose': (7,) tensor (mm), 'timestamp': stamp}], starting with the initial pose.
     ``chunk`` > 1: frames are handed to ``estimator.forward_chunk`` in groups of ``chunk`` (one RAFT pass per group; the same
     trajectory bit for bit, about twice the frames per second at 16); the sequence's first frame always goes through ``forward``.
-    An estimator with ``warm_start`` needs ``chunk`` = 1 (a chunk's temporal flows come from one pass)."""
+    An estimator with ``warm_start`` needs ``chunk`` = 1 (a chunk's temporal flows come from one pass).
+    ``quality`` (an estimator with ``report_quality: True``): every item gains 'quality', the frame's row of ``estimator.last_quality``
+    as host tensors (cov (6,6) of the relative pose's left tangent in mm / rad, pd, n2d, n3d, rms2d_px, rms3d in mm, f, grad_max, n_iter,
+    func_evals, stop_reason), copied to the host once, after the last frame; ``save_quality`` writes them."""
     import torch
     if chunk > 1 and getattr(estimator, 'warm_start', False):
         raise ValueError('track_sequence: warm_start starts frame t from frame t-1\'s flow, which a chunked pass cannot: use chunk=1')
+    qlog = _QualityLog(estimator, quality)
     traj = [{'camera-pose': estimator.last_pose.vec().reshape(7).detach().cpu(), 'timestamp': start_stamp}]
+    qlog.start(traj)
     pending = []
 
     def flush():
@@ -45,27 +82,32 @@ def track_sequence(estimator, frames, start_stamp=0, chunk=1):
                                             torch.cat([p[2] for p in pending]))[0]
         for row, (_, _, _, stamp) in zip(poses.detach().cpu(), pending):
             traj.append({'camera-pose': row.reshape(7), 'timestamp': stamp})
+        qlog.add(traj[-len(pending):])
         pending.clear()
     for item in frames:
         pending.append(item)
         if chunk <= 1 or estimator.frame is None or len(pending) >= chunk:
             flush()
     flush()
+    qlog.finish()
     return traj
 
 
-def track_host_frames(estimator, source, ingest, start_stamp=0, pipelined=True):
+def track_host_frames(estimator, source, ingest, start_stamp=0, pipelined=True, quality=False):
     """``track_sequence`` from frames on the host.  ``source`` yields (frame, stamp) or (frame, user_mask, stamp) with ``frame`` a decoded
     uint8 host frame, ``ingest`` is a preprocess.HostFrameIngest: its stream copies and prepares frame t+1 (and t+2, with depth 2) while
     the tracker works on frame t.  ``pipelined``: the frames go through ``estimator.submit`` / ``result``, so frame t+1's encoders too
     run beside frame t's update loop; an estimator that refuses ``submit`` (the surfel trackers: frame t+1 is tracked against the map
     frame t fused) is driven through ``forward`` as with pipelined=False -- copy and ingest still overlap.  Same kernels on the same
-    inputs: the trajectory is that of ``track_sequence`` on the prepared frames, bit for bit."""
+    inputs: the trajectory is that of ``track_sequence`` on the prepared frames, bit for bit.  ``quality``: as ``track_sequence``."""
+    qlog = _QualityLog(estimator, quality)
     traj = [{'camera-pose': estimator.last_pose.vec().reshape(7).detach().cpu(), 'timestamp': start_stamp}]
+    qlog.start(traj)
     waiting = []                                                   # stamps of the submitted frames
 
     def collect(pose, stamp):
         traj.append({'camera-pose': pose.vec().reshape(7).detach().cpu(), 'timestamp': stamp})
+        qlog.add(traj[-1:])
     for limg, rimg, mask, stamp in ingest.stream(source):
         if pipelined:
             try:
@@ -80,16 +122,18 @@ def track_host_frames(estimator, source, ingest, start_stamp=0, pipelined=True):
             collect(estimator.result()[0], waiting.pop(0))
     while waiting:
         collect(estimator.result()[0], waiting.pop(0))
+    qlog.finish()
     return traj
 
 
-def track_sequences(estimator, sequences, start_stamps=None):
+def track_sequences(estimator, sequences, start_stamps=None, quality=False):
     """``track_sequence`` for K sequences at once on a MultiSurfelPoseEstimator: ``sequences[k]`` yields (limg, rimg, mask, stamp) of
     sequence k (row k of the estimator).  Every lockstep step takes the next frame of each sequence that has one and advances those
     rows in one ``estimator.forward`` call; a sequence that ends leaves the batch.  With the estimator's init_poses the K runs can be
     the (start, end) scenarios of one recording (scripts/benchmark_test.py).  Returns the K trajectories in track_sequence's format,
-    each bit for bit the one a SurfelPoseEstimator run of that sequence alone gives."""
+    each bit for bit the one a SurfelPoseEstimator run of that sequence alone gives.  ``quality``: as ``track_sequence``."""
     import torch
+    qlog = _QualityLog(estimator, quality)
     n = len(sequences)
     if n > estimator.n_seq:
         raise ValueError(f'track_sequences: {n} sequences for an estimator of {estimator.n_seq}')
@@ -97,6 +141,7 @@ def track_sequences(estimator, sequences, start_stamps=None):
     if len(stamps) != n:
         raise ValueError(f'track_sequences: {n} sequences, {len(stamps)} start stamps')
     trajs = [[{'camera-pose': estimator.last_pose[k].vec().reshape(7).detach().cpu(), 'timestamp': stamps[k]}] for k in range(n)]
+    qlog.start([t[0] for t in trajs])
     its = [iter(s) for s in sequences]
     live = list(range(n))
     while live:
@@ -112,6 +157,8 @@ def track_sequences(estimator, sequences, start_stamps=None):
                           torch.cat([it[2] for _, it in items]), rows=live)[0].vec().reshape(-1, 7)
         for row, (k, it) in zip(poses.detach().cpu(), items):
             trajs[k].append({'camera-pose': row.reshape(7), 'timestamp': it[3]})
+        qlog.add([trajs[k][-1] for k, _ in items])
+    qlog.finish()
     return trajs
 
 
@@ -123,6 +170,57 @@ def save_trajectory(trajectory, path):
             v = np.asarray(tr['camera-pose'], dtype=np.float64).reshape(7)
             f.write(f"{tr['timestamp']} {v[0] / 1000.0} {v[1] / 1000.0} {v[2] / 1000.0} {v[3]} {v[4]} {v[5]} {v[6]}\n")
     return fn
+
+
+_TRIU = [(i, j) for i in range(6) for j in range(i, 6)]
+QUALITY_COLUMNS = ('stamp', 'pd', 'stop_reason', 'n_iter', 'n2d', 'n3d', 'rms2d_px', 'rms3d_mm') + tuple(f'cov{i}{j}' for i, j in _TRIU)
+
+
+def save_quality(trajectory, path):
+    """``trajectory.quality.txt`` beside ``trajectory.freiburg``: per item that carries 'quality' (track_sequence(..., quality=True)) one line
+    ``stamp pd stop_reason n_iter n2d n3d rms2d_px rms3d_mm`` + the 21 upper-triangle entries of ``cov`` (row-major; left tangent
+    (tau, phi) of the frame's relative pose, mm and rad).  Floats are written with repr, so ``read_quality`` returns them bit for bit."""
+    fn = os.path.join(path, 'trajectory.quality.txt')
+    with open(fn, 'w') as f:
+        f.write('# ' + ' '.join(QUALITY_COLUMNS) + '\n')
+        for tr in trajectory:
+            q = tr.get('quality')
+            if q is None:
+                continue
+            cov = np.asarray(q['cov'], dtype=np.float64).reshape(6, 6)
+            ints = [int(q[k]) for k in ('pd', 'stop_reason', 'n_iter', 'n2d', 'n3d')]
+            floats = [float(q['rms2d_px']), float(q['rms3d'])] + [float(cov[i, j]) for i, j in _TRIU]
+            f.write(' '.join([str(tr['timestamp'])] + [str(v) for v in ints] + [repr(v) for v in floats]) + '\n')
+    return fn
+
+
+def read_quality(path):
+    """Reads ``save_quality``'s file -> dict: 'timestamp' (list; int where the text is one, else float), pd, stop_reason, n_iter, n2d, n3d
+    (int64 (m,)), rms2d_px, rms3d_mm (float64 (m,)) and cov (m,6,6) float64, symmetric."""
+    with open(path) as f:
+        rows = [ln.split() for ln in f.read().split('\n') if ln.strip() and not ln.startswith('#')]
+    for r in rows:
+        if len(r) != len(QUALITY_COLUMNS):
+            raise ValueError(f'{path}: a line has {len(r)} fields, expected {len(QUALITY_COLUMNS)}')
+
+    def stamp(t):
+        try:
+            return int(t)
+        except ValueError:
+            return float(t)
+    m = len(rows)
+    out = {'timestamp': [stamp(r[0]) for r in rows]}
+    for c, k in enumerate(('pd', 'stop_reason', 'n_iter', 'n2d', 'n3d')):
+        out[k] = np.asarray([int(r[1 + c]) for r in rows], dtype=np.int64).reshape(m)
+    out['rms2d_px'] = np.asarray([float(r[6]) for r in rows], dtype=np.float64).reshape(m)
+    out['rms3d_mm'] = np.asarray([float(r[7]) for r in rows], dtype=np.float64).reshape(m)
+    cov = np.zeros((m, 6, 6))
+    for c, (i, j) in enumerate(_TRIU):
+        col = np.asarray([float(r[8 + c]) for r in rows], dtype=np.float64).reshape(m)
+        cov[:, i, j] = col
+        cov[:, j, i] = col
+    out['cov'] = cov
+    return out
 
 
 def read_freiburg(path, ret_stamps=False, no_stamp=False):
