@@ -10,6 +10,7 @@ Frame-to-model tracking (``frame2frame: False``, :56-96,127-150 with core/fusion
 import time
 import warnings
 from collections import OrderedDict
+from types import SimpleNamespace
 
 import torch
 
@@ -76,6 +77,12 @@ def denormalise_quality(q, inv_scale):
     out['cov'] = cov
     out['rms3d'] = q['rms3d'] * inv_scale
     return out
+
+
+def _warn_skipped(n=1):
+    """One warning per frame the gate rejected (core/pose/pose_estimator.py:82)."""
+    for _ in range(n):
+        warnings.warn('pose estimation not converged, skip.', RuntimeWarning)
 
 
 class PoseEstimator(torch.nn.Module):
@@ -214,22 +221,38 @@ class PoseEstimator(torch.nn.Module):
         self.last_frame = self.frame
         self.frame = Frame(limg, rimg, mask=mask)
         rel_pose, ret_frame, flow, weights = self.get_pose_f2f(_enc)
-        # :81-91 in one launch (ops.pose_gate_chain): the gate isnan | |log| > 0.1 -> identity, de-normalisation of the depth scaling and
-        # last_pose <- last_pose * rel^-1, with ONE host synchronisation (the success flag) instead of a dozen element-wise launches and two
+        self._gate_and_chain(rel_pose, ret_frame)
+        return self.last_pose, None, flow, weights
+
+    def _pass(self, f1, limg, rimg, mask, intrinsics, baseline, **kw):
+        """A tracker's ``model.infer`` from frame 1 ``f1`` (the previous Frame, or the rendered model frame(s)) to the stereo frame(s)
+        (limg, rimg, mask).  ``kw``: what differs between the trackers (cache1 / enc2 / ret_cache, the warm start's flow_init / ret_lowres,
+        rows_alone), handed on as given; the quality keyword is added under ``report_quality``.  The ONE place that knows the positions in
+        infer's tuple: the details, then the quality dict if asked for, then the cache dict if asked for, whose 'time_flow_low' (the
+        temporal 1/8 flow of ret_lowres) is taken out of it.  Returns the parts by name; what was not asked for is None."""
+        r = self.model.infer(f1.img, limg, intrinsics, baseline, depth1=f1.depth * self.scale, image2r=rimg, mask1=f1.mask, mask2=mask,
+                             stereo_flow1=f1.flow, ret_details=True, **kw, **self._quality_kw())
+        cache = r[-1] if kw.get('ret_cache') else None
+        return SimpleNamespace(rel=r[0], depth2=r[2], weights=r[3], flow=r[4], stereo_flow=r[5], quality=r[6] if self.report_quality else None,
+                               cache=cache, flow_low=cache.pop('time_flow_low') if kw.get('ret_lowres') else None)
+
+    def _gate_and_chain(self, rel_pose, ret_frame):
+        """The tail of a frame behind its network pass, core/pose/pose_estimator.py:81-91 in one launch (ops.pose_gate_chain): the gate
+        isnan | |log| > 0.1 -> identity, de-normalisation of the depth scaling and last_pose <- last_pose * rel^-1, with ONE host
+        synchronisation (the success flag) instead of a dozen element-wise launches and two."""
         rel, pose, ok = ops.pose_gate_chain(rel_pose.data.reshape(1, 7), self.last_pose.data, self._inv_scale, 1.0e-1)
-        self._set_quality(self._q_pass, 1, limg.device)
+        self._set_quality(self._q_pass, 1, self.frame.device)
         low, self._low_pass = self._low_pass, None
         if self._pending:
             self._start_encoders(self._pending[0])            # (submit / result) the next frame's encoders, before the host waits for this one
         self.t_enqueued = time.perf_counter()             # everything of this frame has been handed to the runtime; what follows waits for the GPU
         self.success = bool(ok[0])
         if not self.success:
-            warnings.warn('pose estimation not converged, skip.', RuntimeWarning)                 # :82
+            _warn_skipped()
         self._flow_low = low if self.success else None                # (a rejected frame: the next pair spans two frames, start it cold)
         self.last_rel_pose = SE3(rel)
         self.last_frame = ret_frame
         self.last_pose = SE3(pose)
-        return self.last_pose, None, flow, weights
 
     @torch.no_grad()
     def forward_chunk(self, limgs, rimgs, masks):
@@ -247,18 +270,15 @@ class PoseEstimator(torch.nn.Module):
         prev = self.frame
         masks = masks.bool().contiguous()
         self.last_pose = self.last_pose.to(limgs.device)
-        r = self.model.infer_chunk(
+        vec7, depth2, weights, flow, stereo_flow, cache, *q = self.model.infer_chunk(
             prev.img, limgs, rimgs, self.intrinsics, self.baseline * self.scale, depth0=prev.depth * self.scale, mask0=prev.mask,
             masks=masks, stereo_flow0=prev.flow, cache0=self._enc_cache, depth_roundtrip=self.scale, **self._quality_kw())
-        vec7, depth2, weights, flow, stereo_flow, cache = r[:6]
-        if self.report_quality:
-            self._set_quality(r[6], c, limgs.device)
+        self._set_quality(q[0] if q else None, c, limgs.device)
         self._enc_cache = cache if self.reuse_features else None
         rel, poses, ok = ops.pose_gate_chain(vec7.reshape(c, 7), self.last_pose.data, self._inv_scale, 1.0e-1)   # :81-91, every frame
         bad = ok == 0
         n_bad = int(bad.sum())                                             # the chunk's one host synchronisation
-        for _ in range(n_bad):
-            warnings.warn('pose estimation not converged, skip.', RuntimeWarning)
+        _warn_skipped(n_bad)
         self.successes = ~bad
         self.success = not bool(bad[-1]) if n_bad else True
         self.last_rel_poses = rel
@@ -279,23 +299,14 @@ class PoseEstimator(torch.nn.Module):
             self.frame.depth = depth / self.scale
             self.frame.flow = stereo_flow
             return rel, None, None, None
-        r = self.model.infer(
-            self.last_frame.img, self.frame.img, self.intrinsics, self.baseline * self.scale,
-            depth1=self.last_frame.depth * self.scale, image2r=self.frame.rimg, mask1=self.last_frame.mask,
-            mask2=self.frame.mask, stereo_flow1=self.last_frame.flow, ret_details=True,
-            cache1=self._enc_cache, ret_cache=True, **({'enc2': enc} if enc is not None and self._enc_cache is not None else {}),
-            **self._flow_init(), **self._quality_kw())
-        rel, depth1, depth2, weights, flow, stereo_flow = r[:6]
-        cache = r[-1]
-        if self.report_quality:
-            self._q_pass = r[6]
-        if self.warm_start:
-            self._low_pass = cache.pop('time_flow_low')
-        self._enc_cache = cache if self.reuse_features else None
-        rel = SE3(rel.data.reshape(1, 7))
-        self.frame.depth = depth2 / self.scale
-        self.frame.flow = stereo_flow
-        return rel, self.last_frame, flow, weights
+        p = self._pass(self.last_frame, self.frame.img, self.frame.rimg, self.frame.mask, self.intrinsics, self.baseline * self.scale,
+                       cache1=self._enc_cache, ret_cache=True, **({'enc2': enc} if enc is not None and self._enc_cache is not None else {}),
+                       **self._flow_init())
+        self._q_pass, self._low_pass = p.quality, p.flow_low
+        self._enc_cache = p.cache if self.reuse_features else None
+        self.frame.depth = p.depth2 / self.scale
+        self.frame.flow = p.stereo_flow
+        return SE3(p.rel.data.reshape(1, 7)), self.last_frame, p.flow, p.weights
 
 
 class SurfelPoseEstimator(PoseEstimator):
@@ -339,16 +350,7 @@ class SurfelPoseEstimator(PoseEstimator):
             self.scene = SurfelMap(frame=self.frame, kmat=self.intrinsics.squeeze(0), upscale=1, d_thresh=self.config['dist_thr'],
                                    pmat=self.last_pose, average_pts=self.config['average_pts'])
         rel_pose, ret_frame, flow, weights = self.get_pose_f2m()
-        rel, pose, ok = ops.pose_gate_chain(rel_pose.data.reshape(1, 7), self.last_pose.data, self._inv_scale, 1.0e-1)   # :81-91
-        self._set_quality(self._q_pass, 1, limg.device)
-        self.t_enqueued = time.perf_counter()
-        self.success = bool(ok[0])
-        if not self.success:
-            warnings.warn('pose estimation not converged, skip.', RuntimeWarning)
-        self._flow_low = self._low_pass if self.success else None
-        self.last_rel_pose = SE3(rel)
-        self.last_frame = ret_frame
-        self.last_pose = SE3(pose)
+        self._gate_and_chain(rel_pose, ret_frame)
         if self.success and flow is not None:                              # :94-95
             self.scene.fuse(self.frame, self.last_pose)
         return self.last_pose, self.scene, flow, weights
@@ -357,17 +359,13 @@ class SurfelPoseEstimator(PoseEstimator):
         """:127-150: the map rendered at the last camera pose, PoseNet.infer of render -> frame (mask2 &= valid in place)."""
         model_frame = self.scene.render_transformed(self.intrinsics.squeeze(0), self.last_pose.inv())[0]
         warm = self._flow_init()                                           # (warm start: the previous render -> frame flow, pushed forward)
-        r = self.model.infer(
-            model_frame.img, self.frame.img, self.intrinsics, self.baseline * self.scale, depth1=model_frame.depth * self.scale,
-            image2r=self.frame.rimg, mask1=model_frame.mask, mask2=self.frame.mask, stereo_flow1=model_frame.flow, ret_details=True,
-            **(dict(warm, ret_cache=True) if warm else {}), **self._quality_kw())
-        rel, depth1, depth2, weights, flow, stereo_flow = r[:6]
-        self._low_pass = r[-1]['time_flow_low'] if warm else None
-        self._q_pass = r[6] if self.report_quality else None
-        self.frame.depth = depth2 / self.scale
-        self.frame.flow = stereo_flow
-        model_frame.confidence = weights[0]
-        return SE3(rel.data.reshape(1, 7)), model_frame, flow, weights
+        p = self._pass(model_frame, self.frame.img, self.frame.rimg, self.frame.mask, self.intrinsics, self.baseline * self.scale,
+                       **(dict(warm, ret_cache=True) if warm else {}))
+        self._q_pass, self._low_pass = p.quality, p.flow_low
+        self.frame.depth = p.depth2 / self.scale
+        self.frame.flow = p.stereo_flow
+        model_frame.confidence = p.weights[0]
+        return SE3(p.rel.data.reshape(1, 7)), model_frame, p.flow, p.weights
 
 
 class MultiSurfelPoseEstimator(PoseEstimator):
@@ -472,10 +470,6 @@ class MultiSurfelPoseEstimator(PoseEstimator):
         # :127-150 for every row: the maps rendered at the last camera poses, straight into the network's input rows
         last = torch.cat([self.last_pose[k].data.reshape(1, 7) for k in rows])
         model = surfel_map.render_many([self.scenes[k] for k in rows], K, ops.se3_inv(last))
-        problem = getattr(getattr(self.model, 'pose_head', None), 'problem', None)
-        keep = problem.partition_rows if problem is not None else None
-        if problem is not None:
-            problem.partition_rows = 1                                     # a row's solve as if alone (PoseNet.infer_chunk does the same)
         warm = {}
         if self.warm_start:
             # per sequence: forward_interpolate of its last accepted render -> frame flow, or zeros (= the cold pass, bit for bit) for a
@@ -486,33 +480,24 @@ class MultiSurfelPoseEstimator(PoseEstimator):
             if have:
                 zero = torch.zeros_like(have[0])
                 warm['flow_init'] = ops.forward_interpolate(torch.cat([zero if p is None else p for p in prev]))
-        try:
-            r = self.model.infer(
-                model.img, limgs, K, baseline, depth1=model.depth * self.scale, image2r=rimgs, mask1=model.mask, mask2=masks,
-                stereo_flow1=model.flow, ret_details=True, **warm, **self._quality_kw())
-            rel, depth1, depth2, weights, flow, stereo_flow = r[:6]
-        finally:
-            if problem is not None:
-                problem.partition_rows = keep
-        rel_g, pose, ok = ops.pose_gate_chain_rows(rel.data.reshape(R, 7), last, self._inv_scale, 1.0e-1)     # :81-91, row by row
+        p = self._pass(model, limgs, rimgs, masks, K, baseline, rows_alone=True, **warm)   # (a row's solve as if alone, as PoseNet.infer_chunk)
+        rel_g, pose, ok = ops.pose_gate_chain_rows(p.rel.data.reshape(R, 7), last, self._inv_scale, 1.0e-1)     # :81-91, row by row
         if self.report_quality:
-            self._set_quality(r[6], R, dev)                                # row j belongs to sequence rows[j]
+            self._set_quality(p.quality, R, dev)                           # row j belongs to sequence rows[j]
         self.t_enqueued = time.perf_counter()
         okh = ok.cpu().bool()                                              # the lockstep frame's one host synchronisation
-        low = r[-1]['time_flow_low'] if warm else None
+        _warn_skipped(R - int(okh.sum()))
         for j, k in enumerate(rows):
             self.success[k] = bool(okh[j])
-            if not self.success[k]:
-                warnings.warn('pose estimation not converged, skip.', RuntimeWarning)
             self.last_pose[k] = SE3(pose[j:j + 1])
             if warm:
-                self._flow_lows[k] = low[j:j + 1] if self.success[k] else None
+                self._flow_lows[k] = p.flow_low[j:j + 1] if self.success[k] else None
         self.last_rel_poses = rel_g
         passed = [j for j in range(R) if okh[j]]
         if passed:                                                         # :94-95
-            surfel_map.fuse_many([self.scenes[rows[j]] for j in passed], Frame(limgs, rimgs, depth=depth2 / self.scale, mask=masks),
+            surfel_map.fuse_many([self.scenes[rows[j]] for j in passed], Frame(limgs, rimgs, depth=p.depth2 / self.scale, mask=masks),
                                  pose, rows=passed)
-        return SE3(pose), okh, [self.scenes[k] for k in rows], flow, weights
+        return SE3(pose), okh, [self.scenes[k] for k in rows], p.flow, p.weights
 
 
 def from_config(config, intrinsics, baseline, checkpoint, img_shape, init_pose=None):

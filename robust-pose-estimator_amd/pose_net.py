@@ -108,6 +108,30 @@ class PoseNet(nn.Module):
             return both(feature_images, context_images)
         return self.flow.encode_features(feature_images), self.flow.encode_context(context_images)
 
+    def _heads(self, g, hidden, context):
+        """(w2d, w3d) of a pass from ops.depth_backproject_warp's ``g`` and RAFT's hidden / context maps: both heads + resize + sigmoid as
+        one hand-written kernel chain (csrc/unet.hip, no concatenations) when they are in eval mode and FUSED_HEADS is set, the modules
+        otherwise, ones without ``use_weights``."""
+        if not self.use_weights:
+            return torch.ones_like(g['depth2']), torch.ones_like(g['depth2'])
+        if FUSED_HEADS and not (self.weight_head_2d.training or self.weight_head_3d.training):
+            return ops.unet_heads(g['inp1'], g['inp2'], hidden, context, pack_params(self.weight_head_2d[0]),
+                                  pack_params(self.weight_head_3d[0]), self.config['image_shape'])
+        return (self.weight_head_2d(torch.cat((g['inp1'], hidden, context), dim=1)),
+                self.weight_head_3d(torch.cat((g['inp1'], g['inp2'], hidden, context), dim=1)))
+
+    def _solve(self, inputs, rows_alone=False):
+        """vec7 (n,1,7) of ``self.pose_head(*inputs)``.  ``rows_alone``: with ``partition_rows = 1`` for this solve, so that a row's float64
+        sums are grouped as if it were solved alone and its result does not depend on the rows it shares the batch with."""
+        problem = self.pose_head.problem
+        keep = problem.partition_rows
+        if rows_alone:
+            problem.partition_rows = 1
+        try:
+            return self.pose_head(*inputs)[0]
+        finally:
+            problem.partition_rows = keep
+
     @torch.no_grad()
     def stages(self, image1l, image2l, intrinsics, baseline, depth1, image2r, mask1, mask2, stereo_flow1, cache1=None, heads=True, enc2=None,
                flow_init=None, ret_lowres=False):
@@ -145,18 +169,7 @@ class PoseNet(nn.Module):
         hidden, context = hidden[:n], context[:n]
         g = ops.depth_backproject_warp(stereo_flow2, time_flow, baseline, intrinsics, depth1, image1l, image2l,
                                        stereo_flow1, mask2)
-        if not heads:
-            w2d = w3d = None
-        elif self.use_weights and FUSED_HEADS and not (self.weight_head_2d.training or self.weight_head_3d.training):
-            # both heads + resize + sigmoid as one hand-written kernel chain (csrc/unet.hip), no concatenations
-            w2d, w3d = ops.unet_heads(g['inp1'], g['inp2'], hidden, context, pack_params(self.weight_head_2d[0]),
-                                      pack_params(self.weight_head_3d[0]), self.config['image_shape'])
-        elif self.use_weights:
-            w2d = self.weight_head_2d(torch.cat((g['inp1'], hidden, context), dim=1))
-            w3d = self.weight_head_3d(torch.cat((g['inp1'], g['inp2'], hidden, context), dim=1))
-        else:
-            w2d = torch.ones_like(g['depth2'])
-            w3d = torch.ones_like(g['depth2'])
+        w2d, w3d = self._heads(g, hidden, context) if heads else (None, None)
         g.update(time_flow=time_flow, stereo_flow2=stereo_flow2, hidden=hidden, context=context, w2d=w2d, w3d=w3d,
                  intrinsics=intrinsics, cache2=dict(fmap=f2l, cnet=c2l))
         if ret_lowres:
@@ -165,11 +178,12 @@ class PoseNet(nn.Module):
 
     @torch.no_grad()
     def infer(self, image1l, image2l, intrinsics, baseline, depth1, image2r, mask1, mask2, stereo_flow1,
-              ret_details=False, cache1=None, ret_cache=False, enc2=None, flow_init=None, ret_lowres=False, ret_quality=False):
+              ret_details=False, cache1=None, ret_cache=False, enc2=None, flow_init=None, ret_lowres=False, ret_quality=False, rows_alone=False):
         """``flow_init`` / ``ret_lowres``: see stages (warm start of the temporal pairs; the temporal 1/8 flow comes back as the returned
         cache's 'time_flow_low', so ret_lowres needs ret_cache).
         ``ret_quality`` (needs ret_details): the details gain, behind stereo_flow2, the solve-quality report of the n rows as a dict of
-        device tensors (``_quality``): two more launches, no host synchronisation; everything else is unchanged bit for bit."""
+        device tensors (``_quality``): two more launches, no host synchronisation; everything else is unchanged bit for bit.
+        ``rows_alone``: every row's solve as if it were alone in the batch (``_solve``), for callers that batch independent sequences."""
         if enc2 is not None and cache1 is None:
             raise ValueError('infer: enc2 (the new frame encoded ahead of the call) needs cache1 (the previous frame\'s encoder outputs)')
         if ret_lowres and not ret_cache:
@@ -182,7 +196,7 @@ class PoseNet(nn.Module):
         n = image1l.shape[0]
         lw = self.loss_weight.detach()[None, :].repeat(n, 1)
         inputs = (s['time_flow'], s['pcl1'], s['pcl2w'], s['w2d'], s['w3d'], mask1.bool(), s['mask2w'], s['intrinsics'], lw)
-        vec7, _ = self.pose_head(*inputs)
+        vec7 = self._solve(inputs, rows_alone)
         pose = SE3(vec7[:, 0]) if n > 1 else SE3(vec7)[0]     # reference returns SE3(pose_se3)[0] for its n == 1
         out = (pose, depth1, s['depth2'], (s['w2d'], s['w3d']), s['time_flow'], s['stereo_flow2']) if ret_details else pose
         if ret_quality:
@@ -243,23 +257,14 @@ class PoseNet(nn.Module):
         image1l = torch.cat((image0l, imagesl[:c - 1]), dim=0)
         g = ops.depth_backproject_warp(stereo_flow2, time_flow, baseline, intrinsics, depth1, image1l, imagesl, stereo_flow1, masks)
         if self.use_weights and not FUSED_HEADS:
-            # the A/B switch selects the module route in stages(); here it would silently break forward_chunk == c forward calls
+            # the A/B switch selects the module route in _heads(); here it would silently break forward_chunk == c forward calls
             raise RuntimeError('infer_chunk runs the fused weight heads only: set pose_net.FUSED_HEADS = True (or walk the frames with infer)')
-        if self.use_weights and not (self.weight_head_2d.training or self.weight_head_3d.training):
-            w2d, w3d = ops.unet_heads(g['inp1'], g['inp2'], hidden, context, pack_params(self.weight_head_2d[0]),
-                                      pack_params(self.weight_head_3d[0]), self.config['image_shape'])
-        elif self.use_weights:
+        if self.use_weights and (self.weight_head_2d.training or self.weight_head_3d.training):
             raise RuntimeError('infer_chunk: the weight heads must be in eval mode')
-        else:
-            w2d, w3d = torch.ones_like(g['depth2']), torch.ones_like(g['depth2'])
+        w2d, w3d = self._heads(g, hidden, context)
         lw = self.loss_weight.detach()[None, :].repeat(c, 1)
-        problem = self.pose_head.problem
-        keep, problem.partition_rows = problem.partition_rows, 1
-        try:
-            inputs = (time_flow, g['pcl1'], g['pcl2w'], w2d, w3d, mask1, g['mask2w'], intrinsics, lw)
-            vec7, _ = self.pose_head(*inputs)
-        finally:
-            problem.partition_rows = keep
+        inputs = (time_flow, g['pcl1'], g['pcl2w'], w2d, w3d, mask1, g['mask2w'], intrinsics, lw)
+        vec7 = self._solve(inputs, rows_alone=True)
         out = (vec7[:, 0], g['depth2'], (w2d, w3d), time_flow, stereo_flow2, dict(fmap=fl[c - 1:], cnet=cn[c - 1:]))
         return (*out, self._quality(inputs)) if ret_quality else out
 

@@ -120,41 +120,24 @@ class ResidualBlock(nn.Module):
         if x_norm is not None and not (fused_in and self.takes_raw_input(x)):
             raise RuntimeError('ResidualBlock: x_norm needs the fused stride-1 Winograd route')
         if fused_in:
-            b, _, hh, ww = x.shape
             st = self.conv1.stride[0]
-            w1 = _wino(self.conv1, x)
-            raw1 = torch.empty(b, self.conv1.out_channels, hh // st, ww // st, device=x.device)
-            if w1 is not None:                                 # stride 1: Winograd, moments per 16x8-pixel patch
-                stats1 = ops.conv_wino_stats_buffer(b, self.conv1.out_channels, hh, ww, x.device)
-                ops.conv_wino(x, w1, ops.CONV_LINEAR, raw1, bias=self.conv1.bias.detach(), stats=stats1, pre_norm=x_norm)
-            else:
-                stats1 = ops.conv_stats_buffer(b, self.conv1.out_channels, hh, ww, x.device, stride=st)
-                ops.conv_fused(x, _packed(self.conv1), ops.CONV_LINEAR, raw1, bias=self.conv1.bias.detach(), stats=stats1, stride=st)
-            mi = ops.instnorm_finalize(stats1, (hh // st) * (ww // st), eps=self.norm1.eps, channels=self.conv1.out_channels)
+            hw = (x.shape[-2] // st) * (x.shape[-1] // st)
+            raw1, stats1 = _encoder_conv(self.conv1, x, pre_norm=x_norm, moments=True)   # (stride 1: Winograd, moments per 16x8-pixel patch)
+            mi = ops.instnorm_finalize(stats1, hw, eps=self.norm1.eps, channels=self.conv1.out_channels)
             res_relu = True
             if self.downsample is not None:
                 sc = self.downsample[0]
                 if _fusable(sc, x):
                     # the shortcut norm3(conv1x1 x) never exists as a tensor either: its raw convolution output and (mean, 1/std) go to
                     # the block's last pass, which normalises it on the fly (bit-identical to a pass of its own, tested)
-                    stats_sc = ops.conv_stats_buffer(b, sc.out_channels, hh, ww, x.device, stride=st)
-                    x = ops.conv_fused(x, _packed(sc), ops.CONV_LINEAR, torch.empty(b, sc.out_channels, hh // st, ww // st, device=x.device),
-                                       bias=sc.bias.detach(), stats=stats_sc, stride=st)
-                    x_norm = ops.instnorm_finalize(stats_sc, (hh // st) * (ww // st), eps=self.norm3.eps, channels=sc.out_channels)
+                    x, stats_sc = _encoder_conv(sc, x, moments=True)
+                    x_norm = ops.instnorm_finalize(stats_sc, hw, eps=self.norm3.eps, channels=sc.out_channels)
                     res_relu = False
                 else:
                     x = conv_norm_act(sc, self.norm3, x, relu=False)
-            ho, wo = raw1.shape[-2:]
-            w2 = _wino(self.conv2, raw1)
-            raw2 = torch.empty(b, self.conv2.out_channels, ho, wo, device=x.device)
-            if w2 is not None:
-                stats2 = ops.conv_wino_stats_buffer(b, self.conv2.out_channels, ho, wo, x.device)
-                ops.conv_wino(raw1, w2, ops.CONV_LINEAR, raw2, bias=self.conv2.bias.detach(), stats=stats2, pre_norm=mi)
-            else:
-                stats2 = ops.conv_stats_buffer(b, self.conv2.out_channels, ho, wo, x.device)
-                ops.conv_fused(raw1, _packed(self.conv2), ops.CONV_LINEAR, raw2, bias=self.conv2.bias.detach(), stats=stats2, pre_norm=mi)
+            raw2, stats2 = _encoder_conv(self.conv2, raw1, pre_norm=mi, moments=True)
             if isinstance(stats2, ops.TileMajorStats):            # merge the Winograd kernel's records once (a small launch), then stream
-                stats2 = ops.instnorm_finalize(stats2, ho * wo, eps=self.norm2.eps, channels=self.conv2.out_channels)
+                stats2 = ops.instnorm_finalize(stats2, hw, eps=self.norm2.eps, channels=self.conv2.out_channels)
             return ops.instnorm_apply(raw2, stats2, eps=self.norm2.eps, relu=True, residual=x, residual_norm=x_norm, residual_relu=res_relu)
         y = conv_norm_act(self.conv1, self.norm1, x, relu=True)
         if self.downsample is not None:
@@ -180,13 +163,18 @@ def _bn_affine(conv, norm):
     return cached[1], cached[2]
 
 
+def _cached(module, attr, key, make):
+    """``make()`` kept on ``module`` as ``attr`` until ``key`` (the versions and addresses of what it was made from) changes."""
+    cached = getattr(module, attr, None)
+    if cached is None or cached[0] != key:
+        cached = (key, make())
+        setattr(module, attr, cached)
+    return cached[1]
+
+
 def _packed(conv):
     """PackedConv of a module's weight (no bias), cached on the module until the weight changes."""
-    key = (conv.weight._version, conv.weight.data_ptr())
-    cached = getattr(conv, '_rpe_packed', None)
-    if cached is None or cached[0] != key:
-        conv._rpe_packed = cached = (key, ops.PackedConv(conv.weight, None))
-    return cached[1]
+    return _cached(conv, '_rpe_packed', (conv.weight._version, conv.weight.data_ptr()), lambda: ops.PackedConv(conv.weight, None))
 
 
 def _wino(conv, x):
@@ -197,11 +185,7 @@ def _wino(conv, x):
     if not ops.PackedWino.supported(conv.weight, x.shape[-2], x.shape[-1]) or conv.in_channels > 128 or not x.is_contiguous():
         return None
     kind = ops.PackedWino24 if WINO_2X4 and ops.PackedWino24.supported(conv.weight, x.shape[-2], x.shape[-1]) else ops.PackedWino
-    key = (conv.weight._version, conv.weight.data_ptr(), kind)
-    cached = getattr(conv, '_rpe_wino', None)
-    if cached is None or cached[0] != key:
-        conv._rpe_wino = cached = (key, kind(conv.weight, None))
-    return cached[1]
+    return _cached(conv, '_rpe_wino', (conv.weight._version, conv.weight.data_ptr(), kind), lambda: kind(conv.weight, None))
 
 
 def _fusable(conv, x):
@@ -221,35 +205,40 @@ def conv_norm_act(conv, norm, x, relu, residual=None):
     the 1x1 stride-2 shortcut -- run on the fused HIP implicit GEMM when the map width is a multiple of 4 (folded batch
     norm / ReLU / residual inside its epilogue; for instance norm the epilogue leaves per-tile partial sums and one more
     read+write pass normalises); shapes those kernels refuse run on the generic kernel (ops.conv_direct) + a stand-alone epilogue pass."""
-    b, _, hh, ww = x.shape
     fused = _fusable(conv, x)
-    stride = conv.stride[0] if fused else 1
     if isinstance(norm, nn.BatchNorm2d):
         if norm.training:
             raise RuntimeError('the RAFT encoders run with frozen batch norm (RAFT.freeze_bn, pose_net.py:22)')
         scale, shift = _bn_affine(conv, norm)
-        pw = _wino(conv, x) if fused else None
-        if pw is not None:                                     # cnet's stride-1 3x3 layers: Winograd with the folded batch norm in the epilogue
-            out = torch.empty(b, conv.out_channels, hh, ww, device=x.device)
-            return ops.conv_wino(x, pw, ops.CONV_RELU if relu else ops.CONV_LINEAR, out, scale=scale, bias=shift, residual=residual)
-        if fused:
-            out = torch.empty(b, conv.out_channels, hh // stride, ww // stride, device=x.device)
-            return ops.conv_fused(x, _packed(conv), ops.CONV_RELU if relu else ops.CONV_LINEAR, out, scale=scale, bias=shift, residual=residual,
-                                  stride=stride)
+        if fused:                                              # (cnet's stride-1 3x3 layers: Winograd with the folded batch norm in the epilogue)
+            return _encoder_conv(conv, x, ops.CONV_RELU if relu else ops.CONV_LINEAR, affine=(scale, shift), residual=residual)[0]
         return ops.affine_act(ops.conv_direct(x, conv.weight, None, conv.stride, conv.padding), scale, shift, relu=relu, residual=residual)
     if isinstance(norm, nn.InstanceNorm2d):
-        pw = _wino(conv, x) if fused else None
-        if pw is not None:
-            stats = ops.conv_wino_stats_buffer(b, conv.out_channels, hh, ww, x.device)
-            pre = ops.conv_wino(x, pw, ops.CONV_LINEAR, torch.empty(b, conv.out_channels, hh, ww, device=x.device), bias=conv.bias.detach(), stats=stats)
-            return ops.instnorm_apply(pre, stats, eps=norm.eps, relu=relu, residual=residual)
         if fused:
-            stats = ops.conv_stats_buffer(b, conv.out_channels, hh, ww, x.device, stride=stride)
-            pre = ops.conv_fused(x, _packed(conv), ops.CONV_LINEAR, torch.empty(b, conv.out_channels, hh // stride, ww // stride, device=x.device),
-                                 bias=conv.bias.detach(), stats=stats, stride=stride)
+            pre, stats = _encoder_conv(conv, x, moments=True)
             return ops.instnorm_apply(pre, stats, eps=norm.eps, relu=relu, residual=residual)
         return ops.instnorm_act(ops.conv_direct(x, conv.weight, None, conv.stride, conv.padding), conv.bias, eps=norm.eps, relu=relu, residual=residual)
     raise NotImplementedError(type(norm))
+
+
+def _encoder_conv(conv, x, mode=ops.CONV_LINEAR, affine=None, residual=None, pre_norm=None, moments=False):
+    """An encoder convolution that _fusable accepts, on the route its input allows: Winograd (rpe_conv_wino*) when _wino has a packing for
+    it, else the fused implicit GEMM (rpe_conv_fused, which also takes stride 2 and the 1x1 shortcut).  The epilogue adds the conv bias, or
+    with ``affine`` = (scale, shift) applies the folded batch norm; ``mode`` (LINEAR / RELU), ``residual`` and ``pre_norm`` as ops.conv_fused.
+    Returns (the output, the per-tile moments for instnorm_finalize / instnorm_apply in the layout of the kernel that ran -- TileMajorStats
+    from Winograd, channel-major records from the implicit GEMM -- when ``moments``, else None)."""
+    b, _, hh, ww = x.shape
+    st, cout = conv.stride[0], conv.out_channels
+    scale, bias = affine if affine is not None else (None, conv.bias.detach())
+    pw = _wino(conv, x)
+    out = torch.empty(b, cout, hh // st, ww // st, device=x.device)
+    if pw is not None:
+        stats = ops.conv_wino_stats_buffer(b, cout, hh, ww, x.device) if moments else None
+        ops.conv_wino(x, pw, mode, out, scale=scale, bias=bias, residual=residual, stats=stats, pre_norm=pre_norm)
+    else:
+        stats = ops.conv_stats_buffer(b, cout, hh, ww, x.device, stride=st) if moments else None
+        ops.conv_fused(x, _packed(conv), mode, out, scale=scale, bias=bias, residual=residual, stats=stats, stride=st, pre_norm=pre_norm)
+    return out, stats
 
 
 def _key_sources(module):
@@ -329,10 +318,8 @@ class BasicEncoder(nn.Module):
     def _stem_pack(self):
         """conv1 + norm1 + ReLU run on the RAW 0..255 image: the normalisation 2*(x/255)-1 happens while the kernel stages its
         input patch (rpe_stem_conv)."""
-        key = (self.conv1.weight._version, self.conv1.weight.data_ptr())
-        if getattr(self, '_stem_packed', None) is None or self._stem_packed[0] != key:
-            self._stem_packed = (key, ops.PackedStem(self.conv1.weight))
-        return self._stem_packed[1]
+        w = self.conv1.weight
+        return _cached(self, '_stem_packed', (w._version, w.data_ptr()), lambda: ops.PackedStem(w))
 
     def _stem_many(self, images):
         """The stem over several image batches, written into batch slices of ONE output (no torch.cat of the inputs)."""

@@ -247,3 +247,53 @@ def test_library_calls_per_frame_are_unchanged_when_off_and_one_more_when_on(seq
     assert 'rpe_pose_quality' not in off.names
     assert on.calls == off.calls + 1 and on.list_ops == off.list_ops
     assert collections.Counter(on.names) - collections.Counter(off.names) == collections.Counter({'rpe_pose_quality': 1})
+
+
+def test_warm_start_and_quality_together_in_the_three_trackers(seq):
+    """``warm_start`` and ``report_quality`` at once, four frames: the K = 2 MultiSurfelPoseEstimator against a SurfelPoseEstimator per
+    sequence -- poses, success flags, the kept 1/8 flows and every field of last_quality bit for bit, row for row (NaNs in the same
+    places) --, and PoseEstimator.forward against submit / result on sequence 0."""
+    from rpe_amd import pose_estimator, synth
+    model, K, (L, R, M) = seq
+    fr = synth.stereo_frames(22, 4, H, W)
+    Ls, Rs, Ms = (L, fr['image2l'].to(DEV)), (R, fr['image2r'].to(DEV)), (M, fr['mask2'].to(DEV))
+    Ks = (K, fr['K'][0])
+    both = dict(warm_start=True, report_quality=True)
+
+    def same_low(a, b):
+        return (a is None) == (b is None) and (a is None or _same(a, b))
+
+    def left(est, P):
+        return dict(pose=P.data.clone(), rel=est.last_rel_pose.data.clone(), ok=est.success, quality=_clone(est.last_quality),
+                    low=None if est._flow_low is None else est._flow_low.clone())
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore')
+        single = []
+        for k in range(2):
+            est = pose_estimator.SurfelPoseEstimator(dict(F2M, **both), Ks[k], BF, model, (W, H)).to(DEV)
+            single.append([left(est, est(Ls[k][t:t + 1], Rs[k][t:t + 1], Ms[k][t:t + 1].clone())[0]) for t in range(4)])
+        multi = pose_estimator.MultiSurfelPoseEstimator(dict(F2M, **both), torch.stack(Ks), torch.tensor([BF, BF]), model, (W, H)).to(DEV)
+        for t in range(4):
+            P, ok, _, _, _ = multi(*(torch.cat([x[k][t:t + 1] for k in range(2)]).clone() for x in (Ls, Rs, Ms)))
+            for k in range(2):
+                a = single[k][t]
+                assert _same(P.data[k:k + 1], a['pose']) and bool(ok[k]) == a['ok'] and _same(multi.last_rel_poses[k:k + 1], a['rel']), (k, t)
+                assert same_low(multi._flow_lows[k], a['low']), (k, t)
+                for key in KEYS:
+                    assert _same(multi.last_quality[key][k:k + 1], a['quality'][key]), (k, t, key)
+        est = pose_estimator.PoseEstimator(dict(F2F, **both), K, BF, model, (W, H)).to(DEV)
+        walked = [left(est, est(*_frame(seq, t))[0]) for t in range(4)]
+        est.reset()
+        est.submit(*_frame(seq, 0))
+        piped = []
+        for t in range(4):
+            if t + 1 < 4:
+                est.submit(*_frame(seq, t + 1))
+            piped.append(left(est, est.result()[0]))
+    for t, (a, b) in enumerate(zip(walked, piped)):
+        assert _same(a['pose'], b['pose']) and _same(a['rel'], b['rel']) and a['ok'] == b['ok'] and same_low(a['low'], b['low']), t
+        assert sorted(a['quality']) == sorted(KEYS) and all(_same(a['quality'][key], b['quality'][key]) for key in KEYS), t
+    # both options did something: a first frame without a solve, later ones with one, and passes that started from a kept flow
+    assert float(walked[0]['quality']['pd'][0]) == 0.0 and bool(torch.isnan(walked[0]['quality']['cov']).all()) and walked[0]['low'] is None
+    assert any(float(r['quality']['pd'][0]) == 1.0 for r in walked[1:]) and any(r['low'] is not None for r in walked[1:3])
+    assert any(r['low'] is not None for run in single for r in run[:3])

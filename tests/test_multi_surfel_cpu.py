@@ -146,3 +146,25 @@ def test_multi_estimator_construction_and_refusals(tmp_path):
         est(img, img, torch.ones(2, 1, H, W, dtype=torch.bool), rows=[0, 0])
     with pytest.raises(ValueError, match='rows'):
         est(img, img, torch.ones(2, 1, H, W, dtype=torch.bool), rows=[0, 3])
+
+
+def test_solve_rows_alone_sets_partition_rows_1_and_restores_it():
+    """PoseNet._solve on a stand-in pose head (no GPU, no library): ``rows_alone`` solves with partition_rows = 1 and puts the value
+    back, also when the solve raises; without it the value is left alone."""
+    from types import SimpleNamespace
+    from rpe_amd.pose_net import PoseNet
+    problem = SimpleNamespace(partition_rows=7)
+    seen = []
+
+    def head(*inputs):
+        seen.append(problem.partition_rows)
+        if inputs[0] == 'raise':
+            raise RuntimeError('solve failed')
+        return inputs, None
+    net = SimpleNamespace(pose_head=head)
+    head.problem = problem
+    assert PoseNet._solve(net, ('a', 'b'), rows_alone=True) == ('a', 'b') and seen == [1] and problem.partition_rows == 7
+    with pytest.raises(RuntimeError, match='solve failed'):
+        PoseNet._solve(net, ('raise',), rows_alone=True)
+    assert seen == [1, 1] and problem.partition_rows == 7
+    assert PoseNet._solve(net, ('c',)) == ('c',) and seen == [1, 1, 7] and problem.partition_rows == 7
