@@ -18,7 +18,7 @@
 // input crosses L2->LDS once per dy instead of once per tap.  Both tiles are double buffered; one barrier per step.
 // Zero padding: rows (y+dy outside the map) are zero-filled by the loader (whole float4s, W % 4 == 0); columns
 // (x+dx outside the row) are masked per lane when the B operand is read.
-#include "rpe_common.h"
+#include "conv_host.h"
 #include <type_traits>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -723,7 +723,6 @@ __global__ void k_conv_pack(const float* __restrict__ w, float* __restrict__ wp,
     wp[e] = (co < cout && ci < cin) ? w[(((size_t)co * cin + ci) * kh + dy) * kw + dx] : 0.0f;
 }
 
-static inline int conv_cop(int cout) { return (cout + 127) / 128 * 128; }
 // Stride-1 launches use 64(co) x 256(px) tiles when cout is 64 / 96 / 192-like (cout % 128 in 1..96), else 128 x 128.
 // ONE definition: the launcher, rpe_conv_stats_tiles and the statistics consumers must agree on the pixel-tile width.
 static inline bool conv_wide(int cout) { return (cout % 128) != 0 && (cout % 128) <= 96; }
@@ -734,29 +733,24 @@ extern "C" size_t rpe_conv_packed_floats(int cout, int cin, int kh, int kw) {
     if (cout <= 0 || cin <= 0 || kh <= 0 || kw <= 0) return 0;
     // one zero step of padding: the kernel fetches the weights of step s+1 unconditionally (a load under a branch spoils
     // the compiler's s_waitcnt placement on every path)
-    return ((size_t)((cin + CK - 1) / CK) * kh * kw + 1) * CK * conv_cop(cout);
+    return ((size_t)((cin + CK - 1) / CK) * kh * kw + 1) * CK * round_up(cout, 128);
 }
 
 extern "C" int rpe_conv_pack(const float* weight, int cout, int cin, int kh, int kw, float* packed, void* stream) {
-    if (!weight || !packed || cout <= 0 || cin <= 0 || kh <= 0 || kw <= 0) return RPE_E_BADARG;
-    const long long total = (long long)rpe_conv_packed_floats(cout, cin, kh, kw);
-    hipLaunchKernelGGL(k_conv_pack, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, weight, packed, cout, cin, kh, kw,
-                       conv_cop(cout), total);
-    return rpe_check_launch();
+    if (kh <= 0 || kw <= 0) return RPE_E_BADARG;
+    return launch_pack(k_conv_pack, weight, packed, cout, cin, 1, (long long)rpe_conv_packed_floats(cout, cin, kh, kw), stream, kh, kw, round_up(cout, 128));
 }
 
 static_assert(sizeof(rpe_conv_desc) == 200, "rpe_conv_desc layout is part of the ABI (ctypes mirror in _lib.py)");
-static inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 extern "C" int rpe_conv_fused(const rpe_conv_desc* d, void* stream) {
-    if (!d || !d->x || !d->packed || !d->out || d->b <= 0 || d->cin <= 0 || d->cout <= 0 || d->h <= 0 || d->w <= 0) return RPE_E_BADARG;
+    if (!conv_desc_present(d)) return RPE_E_BADARG;
     if (d->kh < 1 || !(d->kh & 1) || (d->kw != 1 && d->kw != 3 && d->kw != 5)) return RPE_E_UNSUPPORTED;
-    if ((d->w & 3) || !al16(d->x) || (d->x_batch_stride & 3)) return RPE_E_UNSUPPORTED;     // 16-B input loads
+    if ((d->w & 3) || !aligned16(d->x, d->x_batch_stride)) return RPE_E_UNSUPPORTED;     // 16-B input loads
     if (d->mode < RPE_CONV_LINEAR || d->mode > RPE_CONV_TANH) return RPE_E_BADARG;
-    if (d->mode == RPE_CONV_TANH && (d->scale || d->residual || d->stats || d->pre_norm || (d->stride != 0 && d->stride != 1) ||
+    if (d->mode == RPE_CONV_TANH && (!conv_no_encoder_epilogue(d) || !stride_is_1(d) ||
                                      ((d->cout % 64) != 0 && (d->cout % 64) <= 32 && d->kw == 3))) return RPE_E_UNSUPPORTED;   // plain epilogue only
-    if (d->mode == RPE_CONV_GATE_ZR && (!d->out2 || !d->hidden || d->gate_channels <= 0 || d->cout != 2 * d->gate_channels)) return RPE_E_BADARG;
-    if (d->mode == RPE_CONV_GATE_H && (!d->hidden || !d->zgate)) return RPE_E_BADARG;
+    if (!conv_gate_args_ok(d)) return RPE_E_BADARG;
     if ((d->mode == RPE_CONV_GATE_ZR || d->mode == RPE_CONV_GATE_H) && (d->scale || d->residual || d->stats)) return RPE_E_BADARG;
     const int stride = d->stride ? d->stride : 1;
     if (stride != 1 && stride != 2) return RPE_E_UNSUPPORTED;
@@ -764,13 +758,9 @@ extern "C" int rpe_conv_fused(const rpe_conv_desc* d, void* stream) {
     if (stride == 2 && ((d->h & 1) || (d->w & 1) || d->mode > RPE_CONV_RELU || !((d->kh == 3 && d->kw == 3) || (d->kh == 1 && d->kw == 1))))
         return RPE_E_UNSUPPORTED;                    // stride 2: 3x3 (pad 1) or 1x1 (pad 0) on even maps
     ConvP P;
-    P.x = d->x; P.xbs = d->x_batch_stride; P.wp = d->packed;
-    P.cin = d->cin; P.cout = d->cout; P.coP = conv_cop(d->cout); P.kh = d->kh;
-    P.Hin = d->h; P.Win = d->w; P.H = d->h / stride; P.W = d->w / stride; P.hw = P.H * P.W;
-    P.bias = d->bias; P.add = d->add; P.abs_ = d->add_batch_stride; P.mode = d->mode;
-    P.out = d->out; P.obs = d->out_batch_stride; P.out2 = d->out2; P.o2bs = d->out2_batch_stride;
-    P.h = d->hidden; P.hbs = d->hidden_batch_stride; P.z = d->zgate; P.zbs = d->zgate_batch_stride; P.cgate = d->gate_channels;
-    P.scale = d->scale; P.res = d->residual; P.rbs = d->residual_batch_stride; P.stats = d->stats; P.pre = d->pre_norm;
+    fill_common(P, d, round_up(d->cout, 128)); fill_gate(P, d); fill_encoder(P, d);
+    P.kh = d->kh; P.Hin = d->h; P.Win = d->w; P.H = d->h / stride; P.W = d->w / stride; P.hw = P.H * P.W;
+    P.h = d->hidden; P.hbs = d->hidden_batch_stride;
     hipStream_t s = (hipStream_t)stream;
     if (stride == 2) {
         // 128 x 128 tiles, or 64 x 64 for launches that would leave most CUs with at most one workgroup (sequential tracking's 2-3 image
@@ -829,7 +819,7 @@ extern "C" int rpe_conv_stats_tiles_batch(int cout, int h, int w, int stride, in
 extern "C" int rpe_instnorm_apply_ex(const float* x, const float* partials, int tiles, int b, int c, int hw, float eps, int relu,
                                      const float* residual, const float* residual_mean_inv, float* out, void* stream) {
     if (!x || !partials || !out || b <= 0 || c <= 0 || hw <= 0 || (residual_mean_inv && !residual)) return RPE_E_BADARG;
-    if ((hw & 3) || !al16(x) || !al16(out) || (residual && !al16(residual))) return RPE_E_UNSUPPORTED;
+    if ((hw & 3) || !aligned16(x, 0) || !aligned16(out, 0) || !aligned16(residual, 0)) return RPE_E_UNSUPPORTED;
     int split = 1;                                   // tiles == 0 (moments given): slices of >= 16 KB, at most 16 per plane
 #ifndef INA_MAXSPLIT
 #define INA_MAXSPLIT 16

@@ -219,30 +219,25 @@ __global__ void k_conv1x1_pack(const float* __restrict__ w, float* __restrict__ 
 
 extern "C" size_t rpe_conv1x1_packed_floats(int cout, int cin) {
     if (cout <= 0 || cin <= 0) return 0;
-    return (size_t)((cout + 127) / 128) * ((cin + G1_K - 1) / G1_K) * G1_TILE;
+    return (size_t)(round_up(cout, 128) / 128) * ceil_div(cin, G1_K) * G1_TILE;
 }
 
-extern "C" int rpe_conv1x1_pack(const float* weight, int cout, int cin, float* packed, void* stream) {
-    if (!weight || !packed || cout <= 0 || cin <= 0) return RPE_E_BADARG;
-    const long long total = (long long)rpe_conv1x1_packed_floats(cout, cin);
-    hipLaunchKernelGGL(k_conv1x1_pack, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, weight, packed, cout, cin,
-                       (cin + G1_K - 1) / G1_K, total);
-    return rpe_check_launch();
+extern "C" int rpe_conv1x1_pack(const float* weight, int cout, int cin, float* packed, void* stream) {        // (any cin: a ragged last step is zero-filled)
+    return launch_pack(k_conv1x1_pack, weight, packed, cout, cin, 1, (long long)rpe_conv1x1_packed_floats(cout, cin), stream, ceil_div(cin, G1_K));
 }
 
 extern "C" int rpe_conv1x1(const rpe_conv_desc* d, void* stream) {
-    if (!d || !d->x || !d->packed || !d->out || d->b <= 0 || d->cin <= 0 || d->cout <= 0 || d->h <= 0 || d->w <= 0) return RPE_E_BADARG;
-    if (d->kh != 1 || d->kw != 1 || (d->stride != 0 && d->stride != 1)) return RPE_E_UNSUPPORTED;
-    if (d->mode != RPE_CONV_LINEAR && d->mode != RPE_CONV_RELU && d->mode != RPE_CONV_TANH) return RPE_E_UNSUPPORTED;
-    if (d->add || d->hidden || d->zgate || d->scale || d->residual || d->stats || d->pre_norm) return RPE_E_UNSUPPORTED;
+    if (!conv_desc_present(d)) return RPE_E_BADARG;
+    if (d->kh != 1 || d->kw != 1 || !stride_is_1(d)) return RPE_E_UNSUPPORTED;
+    if (!conv_linear_or_relu(d) && d->mode != RPE_CONV_TANH) return RPE_E_UNSUPPORTED;
+    if (!conv_plain_only(d) || !conv_no_encoder_epilogue(d)) return RPE_E_UNSUPPORTED;
     const long long hw = (long long)d->h * d->w;
-    // 16-byte DMA pieces: plane size and the input slice's base / batch stride; 32-bit byte offsets inside a 16-channel step
-    if ((hw & 3) || hw < 4 || (((uintptr_t)d->x) & 15) || (d->x_batch_stride & 3) || (((uintptr_t)d->packed) & 15)) return RPE_E_UNSUPPORTED;
-    if (hw * 16 * 4 + G1_BIAS >= (1ll << 32)) return RPE_E_UNSUPPORTED;
+    // 16-byte DMA pieces: plane size and the input slice's base / batch stride (the epilogue stores single floats: any destination)
+    if ((hw & 3) || hw < 4 || !aligned16(d->x, d->x_batch_stride) || !aligned16(d->packed, 0)) return RPE_E_UNSUPPORTED;
+    if (hw * 16 * 4 + G1_BIAS >= (1ll << 32)) return RPE_E_UNSUPPORTED;                        // 32-bit byte offsets inside a 16-channel step
     G1P P;
-    P.x = d->x; P.xbs = d->x_batch_stride; P.wp = d->packed; P.cin = d->cin; P.cout = d->cout; P.coP = (d->cout + 127) / 128 * 128;
-    P.hw = (int)hw; P.bias = d->bias; P.out = d->out; P.obs = d->out_batch_stride; P.out2 = d->out2; P.o2bs = d->out2_batch_stride;
-    P.mode = d->mode;
+    fill_common(P, d, round_up(d->cout, 128));
+    P.hw = (int)hw;
     const dim3 grid(ceil_div(hw, G1_N) * (P.coP / 128), 1, d->b);
 #define G1_LAUNCH(M_) do { if (d->out2) hipLaunchKernelGGL((k_conv1x1<M_, true>), grid, dim3(256), 0, (hipStream_t)stream, P); \
                            else hipLaunchKernelGGL((k_conv1x1<M_, false>), grid, dim3(256), 0, (hipStream_t)stream, P); } while (0)

@@ -281,43 +281,33 @@ __global__ void k_conv1x1_pack_x3(const float* __restrict__ w, unsigned short* _
     const int nct = coP / G3_CO;
     const int co = (int)(rest % nct) * G3_CO + cb * 32 + co32, ci = (int)(rest / nct) * G3K + kh * 8 + ci8;
     const float v = (co < cout && ci < cin) ? w[(size_t)co * cin + ci] : 0.0f;
-    auto bf16_rne = [](float f) { unsigned b = __builtin_bit_cast(unsigned, f); b += 0x7FFFu + ((b >> 16) & 1u); return b & 0xFFFF0000u; };
-    const unsigned u = bf16_rne(v);
-    const float r1 = v - __builtin_bit_cast(float, u);
-    const unsigned u1 = bf16_rne(r1);
-    const float r2 = r1 - __builtin_bit_cast(float, u1);
-    unsigned short* d = wp + (rest * 4 + cb) * (3 * 512) + kh * 256 + co32 * 8 + ci8;
-    d[0] = (unsigned short)(u >> 16); d[512] = (unsigned short)(u1 >> 16); d[1024] = (unsigned short)(bf16_rne(r2) >> 16);
+    store_bf16x3(wp + (rest * 4 + cb) * (3 * 512) + kh * 256 + co32 * 8 + ci8, v);
 }
-
-static inline int g3_cop(int cout) { return (cout + G3_CO - 1) / G3_CO * G3_CO; }
 
 extern "C" size_t rpe_conv1x1_x3_packed_bytes(int cout, int cin) {
     if (cout <= 0 || cin <= 0) return 0;
-    return (size_t)((cin + G3K - 1) / G3K) * (g3_cop(cout) / G3_CO) * G3_A_STEP;
+    return (size_t)ceil_div(cin, G3K) * (round_up(cout, G3_CO) / G3_CO) * G3_A_STEP;
 }
 
-extern "C" int rpe_conv1x1_x3_pack(const float* weight, int cout, int cin, void* packed, void* stream) {
-    if (!weight || !packed || cout <= 0 || cin <= 0) return RPE_E_BADARG;
-    const long long total = (long long)((cin + G3K - 1) / G3K * G3K) * g3_cop(cout);
-    hipLaunchKernelGGL(k_conv1x1_pack_x3, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, weight, (unsigned short*)packed, cout, cin, g3_cop(cout), total);
-    return rpe_check_launch();
+extern "C" int rpe_conv1x1_x3_pack(const float* weight, int cout, int cin, void* packed, void* stream) {      // (any cin: a ragged last step is zero-filled)
+    const int coP = round_up(cout, G3_CO);
+    return launch_pack(k_conv1x1_pack_x3, weight, (unsigned short*)packed, cout, cin, 1, (long long)round_up(cin, G3K) * coP, stream, coP);
 }
 
 extern "C" int rpe_conv1x1_x3(const rpe_conv_desc* d, void* stream) {
-    if (!d || !d->x || !d->packed || !d->out || d->b <= 0 || d->cin <= 0 || d->cout <= 0 || d->h <= 0 || d->w <= 0) return RPE_E_BADARG;
-    if (d->kh != 1 || d->kw != 1 || (d->stride != 0 && d->stride != 1)) return RPE_E_UNSUPPORTED;
-    if (d->mode != RPE_CONV_LINEAR && d->mode != RPE_CONV_RELU) return RPE_E_UNSUPPORTED;
-    if (d->add || d->hidden || d->zgate || d->scale || d->residual || d->stats || d->pre_norm) return RPE_E_UNSUPPORTED;
+    if (!conv_desc_present(d)) return RPE_E_BADARG;
+    if (d->kh != 1 || d->kw != 1 || !stride_is_1(d)) return RPE_E_UNSUPPORTED;
+    if (!conv_linear_or_relu(d)) return RPE_E_UNSUPPORTED;                                      // (no tanh epilogue, unlike rpe_conv1x1)
+    if (!conv_plain_only(d) || !conv_no_encoder_epilogue(d)) return RPE_E_UNSUPPORTED;
     const long long hw = (long long)d->h * d->w;
-    if ((hw & 3) || hw < 4 || (((uintptr_t)d->x) & 15) || (d->x_batch_stride & 3) || (((uintptr_t)d->packed) & 15)) return RPE_E_UNSUPPORTED;
-    // the epilogue stores 16-byte pieces: destination slices aligned like the input
-    if ((((uintptr_t)d->out) & 15) || (d->out_batch_stride & 3) || (d->out2 && ((((uintptr_t)d->out2) & 15) || (d->out2_batch_stride & 3)))) return RPE_E_UNSUPPORTED;
+    // 16-byte DMA pieces as rpe_conv1x1, and the epilogue stores 16-byte pieces: destination slices aligned like the input
+    if ((hw & 3) || hw < 4 || !aligned16(d->x, d->x_batch_stride) || !aligned16(d->packed, 0)) return RPE_E_UNSUPPORTED;
+    if (!aligned16(d->out, d->out_batch_stride) || !aligned16(d->out2, d->out2_batch_stride)) return RPE_E_UNSUPPORTED;
     // 32-bit byte offsets: inside a group of four channel planes, or -- a ragged last step (cin % 16 != 0) addresses up to 16 planes from one base -- sixteen
     if (hw * 4 * ((d->cin & (G3K - 1)) ? 16 : 4) >= (1ll << 31)) return RPE_E_UNSUPPORTED;
     G1X3P P;
-    P.x = d->x; P.xbs = d->x_batch_stride; P.wp = (const unsigned short*)d->packed; P.cin = d->cin; P.cout = d->cout; P.coP = g3_cop(d->cout);
-    P.hw = (int)hw; P.bias = d->bias; P.out = d->out; P.obs = d->out_batch_stride; P.out2 = d->out2; P.o2bs = d->out2_batch_stride; P.mode = d->mode;
+    fill_common(P, d, round_up(d->cout, G3_CO));
+    P.hw = (int)hw;
     hipLaunchKernelGGL(k_conv1x1_x3, dim3(ceil_div((int)hw, 256), P.coP / G3_CO, d->b), dim3(256), 0, (hipStream_t)stream, P);
     return rpe_check_launch();
 }

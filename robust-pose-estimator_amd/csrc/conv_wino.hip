@@ -585,35 +585,16 @@ __global__ void k_wino_pack(const float* __restrict__ w, float* __restrict__ wp,
     const long long rest = e >> 12;
     const int ncot = coP / WB_CO;
     const int co = (int)(rest % ncot) * WB_CO + col, ci = (int)(rest / ncot) * WK + cil;
-    float v = 0.0f;
-    if (co < cout && ci < cin) {
-        const float* g = w + ((size_t)co * cin + ci) * 9;
-        const int xi = pos >> 2, nu = pos & 3;
-        // row xi of G applied to the columns of g, then row nu of G applied to the result
-        float col[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float g0 = g[0 * 3 + c], g1 = g[1 * 3 + c], g2 = g[2 * 3 + c];
-            col[c] = xi == 0 ? g0 : xi == 1 ? 0.5f * ((g0 + g1) + g2) : xi == 2 ? 0.5f * ((g0 - g1) + g2) : g2;
-        }
-        v = nu == 0 ? col[0] : nu == 1 ? 0.5f * ((col[0] + col[1]) + col[2]) : nu == 2 ? 0.5f * ((col[0] - col[1]) + col[2]) : col[2];
-    }
-    wp[e] = v;
+    wp[e] = (co < cout && ci < cin) ? wino_u3x3(w + ((size_t)co * cin + ci) * 9, pos >> 2, pos & 3) : 0.0f;
 }
-
-static inline int wino_cop(int cout) { return (cout + WB_CO - 1) / WB_CO * WB_CO; }
 
 extern "C" size_t rpe_conv_wino_packed_floats(int cout, int cin) {
     if (cout <= 0 || cin <= 0 || cin % WK) return 0;
-    return (size_t)(cin / WK) * 16 * WK * wino_cop(cout);
+    return (size_t)(cin / WK) * 16 * WK * round_up(cout, WB_CO);
 }
 
 extern "C" int rpe_conv_wino_pack(const float* weight, int cout, int cin, float* packed, void* stream) {
-    if (!weight || !packed || cout <= 0 || cin <= 0) return RPE_E_BADARG;
-    if (cin % WK) return RPE_E_UNSUPPORTED;
-    const long long total = (long long)rpe_conv_wino_packed_floats(cout, cin);
-    hipLaunchKernelGGL(k_wino_pack, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, weight, packed, cout, cin, wino_cop(cout), total);
-    return rpe_check_launch();
+    return launch_pack(k_wino_pack, weight, packed, cout, cin, WK, (long long)rpe_conv_wino_packed_floats(cout, cin), stream, round_up(cout, WB_CO));
 }
 
 extern "C" int rpe_conv_wino_stats_tiles(int h, int w) {
@@ -621,65 +602,38 @@ extern "C" int rpe_conv_wino_stats_tiles(int h, int w) {
 }
 
 extern "C" int rpe_conv_wino(const rpe_conv_desc* d, void* stream) {
-    if (!d || !d->x || !d->packed || !d->out || d->b <= 0 || d->cin <= 0 || d->cout <= 0 || d->h <= 0 || d->w <= 0) return RPE_E_BADARG;
-    if (d->kh != 3 || d->kw != 3 || (d->stride != 0 && d->stride != 1) || (d->cin % WK) || (d->h & 1) || (d->w & 1)) return RPE_E_UNSUPPORTED;
-    if (d->mode != RPE_CONV_LINEAR && d->mode != RPE_CONV_RELU) return RPE_E_UNSUPPORTED;
-    if (d->add || d->hidden || d->zgate) return RPE_E_UNSUPPORTED;
-    const bool enc = d->scale || d->residual || d->stats || d->pre_norm;
-    if ((d->pre_norm && d->cin > 128) || (d->residual && ((((uintptr_t)d->residual) & 7) || (d->residual_batch_stride & 1)))) return RPE_E_UNSUPPORTED;
-    if ((((uintptr_t)d->packed) & 15) || (((uintptr_t)d->out) & 7) || (d->out_batch_stride & 1) ||
-        (d->out2 && ((((uintptr_t)d->out2) & 7) || (d->out2_batch_stride & 1)))) return RPE_E_UNSUPPORTED;
+    if (!conv_desc_present(d)) return RPE_E_BADARG;
+    // tiles of 2 x 2 outputs: even maps (the only 3x3 Winograd kernel that takes w % 4 == 2)
+    if (d->kh != 3 || d->kw != 3 || !stride_is_1(d) || (d->cin % WK) || (d->h & 1) || (d->w & 1)) return RPE_E_UNSUPPORTED;
+    if (!conv_linear_or_relu(d) || !conv_plain_only(d)) return RPE_E_UNSUPPORTED;
+    if (d->pre_norm && d->cin > 128) return RPE_E_UNSUPPORTED;                                  // LDS room for 128 (mean, 1/std) pairs of the input
+    // the epilogue moves a tile row (two floats) per lane: 8-byte destinations and residual; the input may lie anywhere (see quads)
+    if (!aligned16(d->packed, 0) || !aligned8(d->out, d->out_batch_stride) || !aligned8(d->out2, d->out2_batch_stride) ||
+        !aligned8(d->residual, d->residual_batch_stride)) return RPE_E_UNSUPPORTED;
     WinoP P;
-    P.x = d->x; P.xbs = d->x_batch_stride; P.wp = d->packed; P.cin = d->cin; P.cout = d->cout; P.coP = wino_cop(d->cout);
-    P.H = d->h; P.W = d->w; P.bias = d->bias; P.out = d->out; P.obs = d->out_batch_stride; P.out2 = d->out2; P.o2bs = d->out2_batch_stride;
-    P.mode = d->mode;
-    auto a16 = [](const void* p, long long bs) { return !p || ((((uintptr_t)p) & 15) == 0 && (bs & 3) == 0); };
-    P.v4 = (d->w & 3) == 0 && a16(d->out, d->out_batch_stride) && a16(d->out2, d->out2_batch_stride) && a16(d->residual, d->residual_batch_stride);
-    P.scale = d->scale; P.res = d->residual; P.rbs = d->residual_batch_stride; P.stats = d->stats; P.pre = d->pre_norm;
-    // 64-channel tiles; a remainder of at most 32 channels (cout = 96) runs as one 32-channel tile instead of a half-empty 64
-    const int rem = d->cout % WB_CO, tail32 = rem > 0 && rem <= 32;
-    const int n64 = tail32 ? d->cout / WB_CO : P.coP / WB_CO;
-    const unsigned gx = ceil_div(d->w, 2 * WB_TX) * ceil_div(d->h, 2 * WB_TY);
-    hipStream_t s = (hipStream_t)stream;
-    P.co_base = 0;
-    // epilogue shape: 0 plain, 1 scale / residual (cnet), 2 moments (fnet), 3 anything else
-    const int epi = !enc ? 0 : (d->stats && !d->scale && !d->residual) ? 2 : !d->stats ? 1 : 3;
+    fill_common(P, d, round_up(d->cout, WB_CO)); fill_encoder(P, d);
+    P.H = d->h; P.W = d->w; P.co_base = 0;
+    P.v4 = (d->w & 3) == 0 && aligned16(d->out, d->out_batch_stride) && aligned16(d->out2, d->out2_batch_stride) && aligned16(d->residual, d->residual_batch_stride);
 #ifndef WINO_RAWQ
 #define WINO_RAWQ 1
 #endif
     // the raw patch as 16-byte quads: rows of whole quads, planes and batch items 16-byte aligned, at least one whole quad per row
-    const bool quads = WINO_RAWQ && (d->w & 3) == 0 && d->w >= 4 && ((d->h * d->w) & 3) == 0 && (((uintptr_t)d->x) & 15) == 0 && (d->x_batch_stride & 3) == 0;
-    auto launch = [&](auto cbc, dim3 grid) {
-        constexpr int CBv = decltype(cbc)::value;
-#define WINO_LAUNCH(E, PR, Q) hipLaunchKernelGGL((k_conv_wino<E, PR, CBv, Q>), grid, dim3(256), 0, s, P)
-        if (d->pre_norm && quads) { if (epi == 2) WINO_LAUNCH(2, true, true); else WINO_LAUNCH(3, true, true); }
-        else if (d->pre_norm) { if (epi == 2) WINO_LAUNCH(2, true, false); else WINO_LAUNCH(3, true, false); }
-        else if (quads) {
-            if (epi == 0) WINO_LAUNCH(0, false, true);
-            else if (epi == 1) WINO_LAUNCH(1, false, true);
-            else if (epi == 2) WINO_LAUNCH(2, false, true);
-            else WINO_LAUNCH(3, false, true);
-        }
-        else if (epi == 0) WINO_LAUNCH(0, false, false);
-        else if (epi == 1) WINO_LAUNCH(1, false, false);
-        else if (epi == 2) WINO_LAUNCH(2, false, false);
-        else WINO_LAUNCH(3, false, false);
-#undef WINO_LAUNCH
+    const bool quads = WINO_RAWQ && (d->w & 3) == 0 && d->w >= 4 && ((d->h * d->w) & 3) == 0 && aligned16(d->x, d->x_batch_stride);
+    const int epi = wino_epilogue_class(d);
+    const unsigned gx = ceil_div(d->w, 2 * WB_TX) * ceil_div(d->h, 2 * WB_TY);
+    auto launch = [&](auto cb, int tiles) {
+        dispatch_epi_pre(epi, d->pre_norm != nullptr, [&](auto e, auto pre) {
+            constexpr int E = decltype(e)::value, CB = decltype(cb)::value;
+            constexpr bool PRE = decltype(pre)::value;
+            const dim3 grid(gx, tiles, d->b);
+            if (quads) hipLaunchKernelGGL((k_conv_wino<E, PRE, CB, true>), grid, dim3(256), 0, (hipStream_t)stream, P);
+            else hipLaunchKernelGGL((k_conv_wino<E, PRE, CB, false>), grid, dim3(256), 0, (hipStream_t)stream, P);
+        });
     };
     // Small launches (sequential tracking: batch 1-2) would leave every CU with at most one workgroup = one wave per SIMD, whose
     // K loop is a chain of DMA latencies: 32-channel tiles double the workgroups (two per CU hide each other's stalls).  At full
     // occupancy the 64-channel tile is 15-17 % faster (one weight fragment feeds two matrix instructions), so only below the threshold.
-#ifndef WINO_SMALL_WG
-#define WINO_SMALL_WG 512LL                       /* (tools/build_variant.sh -DWINO_SMALL_WG=... for A/B runs) */
-#endif
-    if ((long long)gx * ceil_div(d->cout, WB_CO) * d->b < WINO_SMALL_WG) {
-        launch(std::integral_constant<int, 1>{}, dim3(gx, ceil_div(d->cout, 32), d->b));
-        return rpe_check_launch();
-    }
-    if (n64 > 0) launch(std::integral_constant<int, 2>{}, dim3(gx, n64, d->b));
-    if (tail32) {
-        P.co_base = n64 * WB_CO;
-        launch(std::integral_constant<int, 1>{}, dim3(gx, 1, d->b));
-    }
+    if ((long long)gx * ceil_div(d->cout, WB_CO) * d->b < WINO_SMALL_WG) launch(std::integral_constant<int, 1>{}, ceil_div(d->cout, 32));
+    else launch_tiles64(P, launch);
     return rpe_check_launch();
 }

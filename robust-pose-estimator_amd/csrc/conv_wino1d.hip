@@ -387,57 +387,31 @@ __global__ void k_wino1d_pack(const float* __restrict__ w, float* __restrict__ w
     const long long rest = e >> 11;
     const int ncot = coP / W1_CO;
     const int co = (int)(rest % ncot) * W1_CO + col, ci = (int)(rest / ncot) * W1_K + cil;
-    double v = 0.0;
-    if (co < cout && ci < cin) {
-        const float* g = w + ((size_t)co * cin + ci) * 5;
-        // G = the evaluation matrix at {0, 1, -1, 2, -2, 1/2, -1/2, inf}, rows scaled to match the dyadic B^T used by the kernel
-        const double G[8][5] = {{1.0, 0.0, 0.0, 0.0, 0.0},
-                                {-2.0 / 9.0, -2.0 / 9.0, -2.0 / 9.0, -2.0 / 9.0, -2.0 / 9.0},
-                                {-2.0 / 9.0, 2.0 / 9.0, -2.0 / 9.0, 2.0 / 9.0, -2.0 / 9.0},
-                                {1.0 / 90.0, 1.0 / 45.0, 2.0 / 45.0, 4.0 / 45.0, 8.0 / 45.0},
-                                {1.0 / 90.0, -1.0 / 45.0, 2.0 / 45.0, -4.0 / 45.0, 8.0 / 45.0},
-                                {32.0 / 45.0, 16.0 / 45.0, 8.0 / 45.0, 4.0 / 45.0, 2.0 / 45.0},
-                                {32.0 / 45.0, -16.0 / 45.0, 8.0 / 45.0, -4.0 / 45.0, 2.0 / 45.0},
-                                {0.0, 0.0, 0.0, 0.0, 1.0}};
-#pragma unroll
-        for (int k = 0; k < 5; ++k) v += G[pos][k] * (double)g[k];
-    }
-    wp[e] = (float)v;
+    wp[e] = (co < cout && ci < cin) ? (float)wino1d_u(w + ((size_t)co * cin + ci) * 5, pos) : 0.0f;
 }
-
-static inline int w1_cop(int cout) { return (cout + W1_CO - 1) / W1_CO * W1_CO; }
 
 extern "C" size_t rpe_conv_wino1d_packed_floats(int cout, int cin) {
     if (cout <= 0 || cin <= 0 || cin % W1_K) return 0;
-    return (size_t)(cin / W1_K) * W1_K * W1_ROW * w1_cop(cout);
+    return (size_t)(cin / W1_K) * W1_K * W1_ROW * round_up(cout, W1_CO);
 }
 
 extern "C" int rpe_conv_wino1d_pack(const float* weight, int cout, int cin, float* packed, void* stream) {
-    if (!weight || !packed || cout <= 0 || cin <= 0) return RPE_E_BADARG;
-    if (cin % W1_K) return RPE_E_UNSUPPORTED;
-    const long long total = (long long)rpe_conv_wino1d_packed_floats(cout, cin);
-    hipLaunchKernelGGL(k_wino1d_pack, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, weight, packed, cout, cin, w1_cop(cout), total);
-    return rpe_check_launch();
+    return launch_pack(k_wino1d_pack, weight, packed, cout, cin, W1_K, (long long)rpe_conv_wino1d_packed_floats(cout, cin), stream, round_up(cout, W1_CO));
 }
 
 extern "C" int rpe_conv_wino1d(const rpe_conv_desc* d, void* stream) {
-    if (!d || !d->x || !d->packed || !d->out || d->b <= 0 || d->cin <= 0 || d->cout <= 0 || d->h <= 0 || d->w <= 0) return RPE_E_BADARG;
+    if (!conv_desc_present(d)) return RPE_E_BADARG;
     const bool vert = d->kh == 5 && d->kw == 1, horiz = d->kh == 1 && d->kw == 5;
-    if (!(vert || horiz) || (d->stride != 0 && d->stride != 1) || (d->cin % W1_K) || (d->w & 3)) return RPE_E_UNSUPPORTED;
-    if (d->mode < RPE_CONV_LINEAR || d->mode > RPE_CONV_GATE_H) return RPE_E_BADARG;
-    if (d->mode == RPE_CONV_GATE_ZR && (!d->out2 || !d->hidden || d->gate_channels <= 0 || d->cout != 2 * d->gate_channels)) return RPE_E_BADARG;
-    if (d->mode == RPE_CONV_GATE_H && (!d->hidden || !d->zgate)) return RPE_E_BADARG;
-    if (d->scale || d->residual || d->stats || d->pre_norm) return RPE_E_UNSUPPORTED;
+    if (!(vert || horiz) || !stride_is_1(d) || (d->cin % W1_K) || (d->w & 3)) return RPE_E_UNSUPPORTED;
+    if (d->mode < RPE_CONV_LINEAR || d->mode > RPE_CONV_GATE_H || !conv_gate_args_ok(d)) return RPE_E_BADARG;
+    if (!conv_no_encoder_epilogue(d)) return RPE_E_UNSUPPORTED;
     // 16-byte accesses: the input quads of the LDS-DMA and the four pixels a lane handles in every tensor of the epilogue
-    auto a16 = [](const void* p, long long bs) { return !p || ((((uintptr_t)p) & 15) == 0 && (bs & 3) == 0); };
-    if (!a16(d->x, d->x_batch_stride) || !a16(d->packed, 0)) return RPE_E_UNSUPPORTED;
-    if ((!a16(d->out, d->out_batch_stride) || !a16(d->out2, d->out2_batch_stride) || !a16(d->add, d->add_batch_stride) ||
-                  !a16(d->hidden, d->hidden_batch_stride) || !a16(d->zgate, d->zgate_batch_stride))) return RPE_E_UNSUPPORTED;
+    if (!aligned16(d->x, d->x_batch_stride) || !aligned16(d->packed, 0) || !aligned16(d->out, d->out_batch_stride) ||
+        !aligned16(d->out2, d->out2_batch_stride) || !aligned16(d->add, d->add_batch_stride) || !aligned16(d->hidden, d->hidden_batch_stride) ||
+        !aligned16(d->zgate, d->zgate_batch_stride)) return RPE_E_UNSUPPORTED;
     W1P P;
-    P.x = d->x; P.xbs = d->x_batch_stride; P.wp = d->packed; P.cin = d->cin; P.cout = d->cout; P.coP = w1_cop(d->cout);
-    P.H = d->h; P.W = d->w; P.bias = d->bias; P.add = d->add; P.abs_ = d->add_batch_stride;
-    P.out = d->out; P.obs = d->out_batch_stride; P.out2 = d->out2; P.o2bs = d->out2_batch_stride;
-    P.hid = d->hidden; P.hbs = d->hidden_batch_stride; P.z = d->zgate; P.zbs = d->zgate_batch_stride; P.cgate = d->gate_channels; P.mode = d->mode;
+    fill_common(P, d, round_up(d->cout, W1_CO)); fill_gate(P, d);
+    P.H = d->h; P.W = d->w; P.hid = d->hidden; P.hbs = d->hidden_batch_stride;
     // Small launches (sequential tracking: 80-320 workgroups of 64 channels) leave most CUs with one workgroup whose K loop is a chain
     // of DMA latencies: 32-channel tiles double the workgroups.  Measured (whole pass, 640x512): batch 1 8.43 -> 7.87 ms, 4 frame pairs
     // 21.9 -> 21.1 ms, 8 pairs equal, 16 pairs (q convolutions: 1 280 workgroups = 2.5 rounds of the 512 slots) 70.96 -> 71.62 ms --

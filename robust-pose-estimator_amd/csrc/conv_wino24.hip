@@ -466,60 +466,36 @@ __global__ void k_wino24_pack(const float* __restrict__ w, float* __restrict__ w
     wp[e] = v;
 }
 
-static inline int wino24_cop(int cout) { return (cout + W4_CO - 1) / W4_CO * W4_CO; }
-
 extern "C" size_t rpe_conv_wino24_packed_floats(int cout, int cin) {
     if (cout <= 0 || cin <= 0 || cin % W4K) return 0;
-    return (size_t)(cin / W4K) * W4K * W4_NP * wino24_cop(cout);
+    return (size_t)(cin / W4K) * W4K * W4_NP * round_up(cout, W4_CO);
 }
 
 extern "C" int rpe_conv_wino24_pack(const float* weight, int cout, int cin, float* packed, void* stream) {
-    if (!weight || !packed || cout <= 0 || cin <= 0) return RPE_E_BADARG;
-    if (cin % W4K) return RPE_E_UNSUPPORTED;
-    const long long total = (long long)rpe_conv_wino24_packed_floats(cout, cin);
-    hipLaunchKernelGGL(k_wino24_pack, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, weight, packed, cout, cin, wino24_cop(cout), total);
-    return rpe_check_launch();
+    return launch_pack(k_wino24_pack, weight, packed, cout, cin, W4K, (long long)rpe_conv_wino24_packed_floats(cout, cin), stream, round_up(cout, W4_CO));
 }
 
 extern "C" int rpe_conv_wino24(const rpe_conv_desc* d, void* stream) {
-    if (!d || !d->x || !d->packed || !d->out || d->b <= 0 || d->cin <= 0 || d->cout <= 0 || d->h <= 0 || d->w <= 0) return RPE_E_BADARG;
-    if (d->kh != 3 || d->kw != 3 || (d->stride != 0 && d->stride != 1) || (d->cin % W4K) || (d->h & 1) || (d->w & 3)) return RPE_E_UNSUPPORTED;
-    if (d->mode != RPE_CONV_LINEAR && d->mode != RPE_CONV_RELU) return RPE_E_UNSUPPORTED;
-    if (d->add || d->hidden || d->zgate) return RPE_E_UNSUPPORTED;
-    if (d->pre_norm && d->cin > 128) return RPE_E_UNSUPPORTED;
-    auto a16 = [](const void* p, long long bs) { return !p || ((((uintptr_t)p) & 15) == 0 && (bs & 3) == 0); };
-    if (!a16(d->x, d->x_batch_stride) || !a16(d->out, d->out_batch_stride) || !a16(d->out2, d->out2_batch_stride) ||
-        !a16(d->residual, d->residual_batch_stride) || (((uintptr_t)d->packed) & 15)) return RPE_E_UNSUPPORTED;
+    if (!conv_desc_present(d)) return RPE_E_BADARG;
+    // tiles of 2 x 4 outputs, and every map row moved as 16-byte quads
+    if (d->kh != 3 || d->kw != 3 || !stride_is_1(d) || (d->cin % W4K) || (d->h & 1) || (d->w & 3)) return RPE_E_UNSUPPORTED;
+    if (!conv_linear_or_relu(d) || !conv_plain_only(d)) return RPE_E_UNSUPPORTED;
+    if (d->pre_norm && d->cin > 128) return RPE_E_UNSUPPORTED;                                  // LDS room for 128 (mean, 1/std) pairs of the input
+    if (!aligned16(d->x, d->x_batch_stride) || !aligned16(d->out, d->out_batch_stride) || !aligned16(d->out2, d->out2_batch_stride) ||
+        !aligned16(d->residual, d->residual_batch_stride) || !aligned16(d->packed, 0)) return RPE_E_UNSUPPORTED;
     Wino24P P;
-    P.x = d->x; P.xbs = d->x_batch_stride; P.wp = d->packed; P.cin = d->cin; P.cout = d->cout; P.coP = wino24_cop(d->cout);
-    P.H = d->h; P.W = d->w; P.bias = d->bias; P.out = d->out; P.obs = d->out_batch_stride; P.out2 = d->out2; P.o2bs = d->out2_batch_stride;
-    P.mode = d->mode; P.scale = d->scale; P.res = d->residual; P.rbs = d->residual_batch_stride; P.stats = d->stats; P.pre = d->pre_norm;
-    const bool enc = d->scale || d->residual || d->stats || d->pre_norm;
-    const int epi = !enc ? 0 : (d->stats && !d->scale && !d->residual) ? 2 : !d->stats ? 1 : 3;
-    const int rem = d->cout % W4_CO, tail32 = rem > 0 && rem <= 32;
-    const int n64 = tail32 ? d->cout / W4_CO : P.coP / W4_CO;
+    fill_common(P, d, round_up(d->cout, W4_CO)); fill_encoder(P, d);
+    P.H = d->h; P.W = d->w; P.co_base = 0;
+    const int epi = wino_epilogue_class(d);
     const unsigned gx = ceil_div(d->w, 16) * ceil_div(d->h, 8);
-    hipStream_t s = (hipStream_t)stream;
-    auto launch = [&](auto cbc, dim3 grid) {
-        constexpr int CBv = decltype(cbc)::value;
-#define W24_LAUNCH(E, PR) hipLaunchKernelGGL((k_conv_wino24<E, PR, CBv>), grid, dim3(256), 0, s, P)
-        if (d->pre_norm) { if (epi == 2) W24_LAUNCH(2, true); else W24_LAUNCH(3, true); }
-        else if (epi == 0) W24_LAUNCH(0, false);
-        else if (epi == 1) W24_LAUNCH(1, false);
-        else if (epi == 2) W24_LAUNCH(2, false);
-        else W24_LAUNCH(3, false);
-#undef W24_LAUNCH
+    auto launch = [&](auto cb, int tiles) {
+        dispatch_epi_pre(epi, d->pre_norm != nullptr, [&](auto e, auto pre) {
+            hipLaunchKernelGGL((k_conv_wino24<decltype(e)::value, decltype(pre)::value, decltype(cb)::value>), dim3(gx, tiles, d->b), dim3(256), 0,
+                               (hipStream_t)stream, P);
+        });
     };
-    P.co_base = 0;
     // small launches (sequential tracking): 32-channel tiles, as rpe_conv_wino (same threshold, same workgroup count)
-    if ((long long)gx * ceil_div(d->cout, W4_CO) * d->b < 512LL) {
-        launch(std::integral_constant<int, 1>{}, dim3(gx, ceil_div(d->cout, 32), d->b));
-        return rpe_check_launch();
-    }
-    if (n64 > 0) launch(std::integral_constant<int, 2>{}, dim3(gx, n64, d->b));
-    if (tail32) {
-        P.co_base = n64 * W4_CO;
-        launch(std::integral_constant<int, 1>{}, dim3(gx, 1, d->b));
-    }
+    if ((long long)gx * ceil_div(d->cout, W4_CO) * d->b < WINO_SMALL_WG) launch(std::integral_constant<int, 1>{}, ceil_div(d->cout, 32));
+    else launch_tiles64(P, launch);
     return rpe_check_launch();
 }

@@ -609,77 +609,40 @@ __global__ void k_wino_pack_x3(const float* __restrict__ w, unsigned short* __re
     const long long rest = e >> 14;
     const int nct = coP / X_CO;
     const int co = (int)(rest % nct) * X_CO + cb * 32 + co32, ci = (int)(rest / nct) * XK + ci16;
-    float v = 0.0f;
-    if (co < cout && ci < cin) {
-        const float* g = w + ((size_t)co * cin + ci) * 9;
-        float col[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float g0 = g[0 * 3 + c], g1 = g[1 * 3 + c], g2 = g[2 * 3 + c];
-            col[c] = xi == 0 ? g0 : xi == 1 ? 0.5f * ((g0 + g1) + g2) : xi == 2 ? 0.5f * ((g0 - g1) + g2) : g2;
-        }
-        v = nu == 0 ? col[0] : nu == 1 ? 0.5f * ((col[0] + col[1]) + col[2]) : nu == 2 ? 0.5f * ((col[0] - col[1]) + col[2]) : col[2];
-    }
-    // round-to-nearest-even bf16 parts: hi = bf16(v), mid = bf16(v - hi), lo = bf16(v - hi - mid), the residuals exact in f32
-    auto bf16_rne = [](float f) { unsigned b = __builtin_bit_cast(unsigned, f); b += 0x7FFFu + ((b >> 16) & 1u); return b & 0xFFFF0000u; };
-    const unsigned u = bf16_rne(v);
-    const float r1 = v - __builtin_bit_cast(float, u);
-    const unsigned u1 = bf16_rne(r1);
-    const float r2 = r1 - __builtin_bit_cast(float, u1);
-    unsigned short* d = wp + (e >> 9) * (3 * 512) + co32 * 16 + ci16;
-    d[0] = (unsigned short)(u >> 16); d[512] = (unsigned short)(u1 >> 16); d[1024] = (unsigned short)(bf16_rne(r2) >> 16);
+    const float v = (co < cout && ci < cin) ? wino_u3x3(w + ((size_t)co * cin + ci) * 9, xi, nu) : 0.0f;
+    store_bf16x3(wp + (e >> 9) * (3 * 512) + co32 * 16 + ci16, v);
 }
-
-static inline int x3_cop(int cout) { return (cout + X_CO - 1) / X_CO * X_CO; }
 
 extern "C" size_t rpe_conv_wino_x3_packed_bytes(int cout, int cin) {
     if (cout <= 0 || cin <= 0 || cin % XK) return 0;
-    return (size_t)(cin / XK) * (x3_cop(cout) / X_CO) * 4 * X_U_WAVE;
+    return (size_t)(cin / XK) * (round_up(cout, X_CO) / X_CO) * 4 * X_U_WAVE;
 }
 
 extern "C" int rpe_conv_wino_x3_pack(const float* weight, int cout, int cin, void* packed, void* stream) {
-    if (!weight || !packed || cout <= 0 || cin <= 0) return RPE_E_BADARG;
-    if (cin % XK) return RPE_E_UNSUPPORTED;
-    const long long total = (long long)cin * x3_cop(cout) * 16;
-    hipLaunchKernelGGL(k_wino_pack_x3, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, weight, (unsigned short*)packed, cout, cin, x3_cop(cout), total);
-    return rpe_check_launch();
+    const int coP = round_up(cout, X_CO);
+    return launch_pack(k_wino_pack_x3, weight, (unsigned short*)packed, cout, cin, XK, (long long)cin * coP * 16, stream, coP);
 }
 
 extern "C" int rpe_conv_wino_x3(const rpe_conv_desc* d, void* stream) {
-    if (!d || !d->x || !d->packed || !d->out || d->b <= 0 || d->cin <= 0 || d->cout <= 0 || d->h <= 0 || d->w <= 0) return RPE_E_BADARG;
-    if (d->kh != 3 || d->kw != 3 || (d->stride != 0 && d->stride != 1) || (d->cin % XK) || (d->h & 1) || (d->w & 3)) return RPE_E_UNSUPPORTED;
-    if (d->mode != RPE_CONV_LINEAR && d->mode != RPE_CONV_RELU) return RPE_E_UNSUPPORTED;
-    if (d->add || d->hidden || d->zgate) return RPE_E_UNSUPPORTED;
-    if (d->pre_norm && d->cin > 128) return RPE_E_UNSUPPORTED;
-    auto a16 = [](const void* p, long long bs) { return !p || ((((uintptr_t)p) & 15) == 0 && (bs & 3) == 0); };
-    if (!a16(d->x, d->x_batch_stride) || ((d->h * d->w) & 3) || !a16(d->out, d->out_batch_stride) || !a16(d->out2, d->out2_batch_stride) ||
-        !a16(d->residual, d->residual_batch_stride) || (((uintptr_t)d->packed) & 15)) return RPE_E_UNSUPPORTED;
+    if (!conv_desc_present(d)) return RPE_E_BADARG;
+    if (d->kh != 3 || d->kw != 3 || !stride_is_1(d) || (d->cin % XK) || (d->h & 1) || (d->w & 3)) return RPE_E_UNSUPPORTED;
+    if (!conv_linear_or_relu(d) || !conv_plain_only(d)) return RPE_E_UNSUPPORTED;
+    if (d->pre_norm && d->cin > 128) return RPE_E_UNSUPPORTED;                                  // LDS room for 128 (mean, 1/std) pairs of the input
+    // the raw patch arrives as 16-byte quads: every channel plane starts on a 16-byte boundary, (h * w) % 4 == 0 (w % 4 == 0 above already
+    // gives it, which is why the f32 kernels with that rule do not repeat it; stated here as what the quad addressing relies on)
+    if (!aligned16(d->x, d->x_batch_stride) || ((d->h * d->w) & 3) || !aligned16(d->out, d->out_batch_stride) || !aligned16(d->out2, d->out2_batch_stride) ||
+        !aligned16(d->residual, d->residual_batch_stride) || !aligned16(d->packed, 0)) return RPE_E_UNSUPPORTED;
     WinoX3P P;
-    P.x = d->x; P.xbs = d->x_batch_stride; P.wp = (const unsigned short*)d->packed; P.cin = d->cin; P.cout = d->cout; P.coP = x3_cop(d->cout);
-    P.H = d->h; P.W = d->w; P.bias = d->bias; P.out = d->out; P.obs = d->out_batch_stride; P.out2 = d->out2; P.o2bs = d->out2_batch_stride;
-    P.mode = d->mode; P.scale = d->scale; P.res = d->residual; P.rbs = d->residual_batch_stride; P.stats = d->stats; P.pre = d->pre_norm;
-    P.nrec = rpe_conv_wino_stats_tiles(d->h, d->w);
-    const bool enc = d->scale || d->residual || d->stats || d->pre_norm;
-    const int epi = !enc ? 0 : (d->stats && !d->scale && !d->residual) ? 2 : !d->stats ? 1 : 3;
-    const int rem = d->cout % X_CO, tail32 = rem > 0 && rem <= 32;
-    const int n64 = tail32 ? d->cout / X_CO : P.coP / X_CO;
+    fill_common(P, d, round_up(d->cout, X_CO)); fill_encoder(P, d);
+    P.H = d->h; P.W = d->w; P.nrec = rpe_conv_wino_stats_tiles(d->h, d->w);
+    const int epi = wino_epilogue_class(d);
     const unsigned gx = ceil_div(d->w, 16) * ceil_div(d->h, 16);
-    hipStream_t s = (hipStream_t)stream;
-    auto launch = [&](auto cbc, dim3 grid) {
-        constexpr int CBv = decltype(cbc)::value;
-#define X3_LAUNCH(E, PR) hipLaunchKernelGGL((k_conv_wino_x3<E, PR, CBv>), grid, dim3(256), 0, s, P)
-        if (d->pre_norm) { if (epi == 2) X3_LAUNCH(2, true); else X3_LAUNCH(3, true); }
-        else if (epi == 0) X3_LAUNCH(0, false);
-        else if (epi == 1) X3_LAUNCH(1, false);
-        else if (epi == 2) X3_LAUNCH(2, false);
-        else X3_LAUNCH(3, false);
-#undef X3_LAUNCH
-    };
-    P.co_base = 0;
-    if (n64 > 0) launch(std::integral_constant<int, 2>{}, dim3(gx, d->b, n64));
-    if (tail32) {
-        P.co_base = n64 * X_CO;
-        launch(std::integral_constant<int, 1>{}, dim3(gx, d->b, 1));
-    }
+    // no small-launch class; the tiles go along grid z
+    launch_tiles64(P, [&](auto cb, int tiles) {
+        dispatch_epi_pre(epi, d->pre_norm != nullptr, [&](auto e, auto pre) {
+            hipLaunchKernelGGL((k_conv_wino_x3<decltype(e)::value, decltype(pre)::value, decltype(cb)::value>), dim3(gx, d->b, tiles), dim3(256), 0,
+                               (hipStream_t)stream, P);
+        });
+    });
     return rpe_check_launch();
 }

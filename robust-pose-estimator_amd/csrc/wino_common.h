@@ -1,6 +1,8 @@
-// Shared pieces of the Winograd convolution kernels (conv_wino.hip: F(2x2,3x3); conv_wino1d.hip: F(4,5) along one axis).
+// Device pieces shared by the matrix-core convolution kernels -- the Winograd ones (conv_wino.hip, conv_wino24.hip, conv_wino_x3.hip: 3x3;
+// conv_wino1d.hip, conv_wino1d_x3.hip: F(4,5) along one axis) and the 1x1 GEMMs (conv1x1.hip, conv1x1_x3.hip): LDS-DMA requests, a row sum,
+// and what their weight packers share.  The entry points' host side is conv_host.h.
 #pragma once
-#include "rpe_common.h"
+#include "conv_host.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -74,3 +76,41 @@ __device__ __forceinline__ unsigned lds_addr_of(const void* p) {
     return (unsigned)(size_t)(__attribute__((address_space(3))) const void*)p;
 }
 
+// ---- weight packing
+// row `row` of G = [1 0 0; .5 .5 .5; .5 -.5 .5; 0 0 1] (F(2x2,3x3)) applied to (g0, g1, g2), in f32 with this parenthesisation
+__device__ __forceinline__ float wino_g3(int row, float g0, float g1, float g2) {
+    return row == 0 ? g0 : row == 1 ? 0.5f * ((g0 + g1) + g2) : row == 2 ? 0.5f * ((g0 - g1) + g2) : g2;
+}
+// element (xi, nu) of U = G g G^T for one 3x3 filter g: row xi of G applied to the columns of g, then row nu of G applied to the result
+__device__ __forceinline__ float wino_u3x3(const float* g, int xi, int nu) {
+    float col[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) col[c] = wino_g3(xi, g[0 * 3 + c], g[1 * 3 + c], g[2 * 3 + c]);
+    return wino_g3(nu, col[0], col[1], col[2]);
+}
+// element pos of U = G g for one 5-tap filter g, in f64: G = the F(4,5) evaluation matrix at {0, 1, -1, 2, -2, 1/2, -1/2, inf}, rows scaled
+// to match the dyadic B^T used by the kernels
+__device__ __forceinline__ double wino1d_u(const float* g, int pos) {
+    const double G[8][5] = {{1.0, 0.0, 0.0, 0.0, 0.0},
+                            {-2.0 / 9.0, -2.0 / 9.0, -2.0 / 9.0, -2.0 / 9.0, -2.0 / 9.0},
+                            {-2.0 / 9.0, 2.0 / 9.0, -2.0 / 9.0, 2.0 / 9.0, -2.0 / 9.0},
+                            {1.0 / 90.0, 1.0 / 45.0, 2.0 / 45.0, 4.0 / 45.0, 8.0 / 45.0},
+                            {1.0 / 90.0, -1.0 / 45.0, 2.0 / 45.0, -4.0 / 45.0, 8.0 / 45.0},
+                            {32.0 / 45.0, 16.0 / 45.0, 8.0 / 45.0, 4.0 / 45.0, 2.0 / 45.0},
+                            {32.0 / 45.0, -16.0 / 45.0, 8.0 / 45.0, -4.0 / 45.0, 2.0 / 45.0},
+                            {0.0, 0.0, 0.0, 0.0, 1.0}};
+    double v = 0.0;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) v += G[pos][k] * (double)g[k];
+    return v;
+}
+// the exact three-way bf16 split of a finite v: hi = bf16(v), mid = bf16(v - hi), lo = bf16(v - hi - mid), round-to-nearest-even parts,
+// the residuals exact in f32; the three planes of a fragment lie 512 elements apart
+__device__ __forceinline__ void store_bf16x3(unsigned short* d, float v) {
+    auto bf16_rne = [](float f) { unsigned b = __builtin_bit_cast(unsigned, f); b += 0x7FFFu + ((b >> 16) & 1u); return b & 0xFFFF0000u; };
+    const unsigned u = bf16_rne(v);
+    const float r1 = v - __builtin_bit_cast(float, u);
+    const unsigned u1 = bf16_rne(r1);
+    const float r2 = r1 - __builtin_bit_cast(float, u1);
+    d[0] = (unsigned short)(u >> 16); d[512] = (unsigned short)(u1 >> 16); d[1024] = (unsigned short)(bf16_rne(r2) >> 16);
+}

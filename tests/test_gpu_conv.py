@@ -558,7 +558,8 @@ def test_stem_statistics_survive_large_means(rpe):
 
 
 @pytest.mark.parametrize('cin,cout,h,w,b', [(256, 192, 64, 80, 2), (128, 64, 64, 80, 1), (256, 126, 44, 48, 2), (128, 256, 32, 40, 1),
-                                            (8, 20, 6, 10, 3), (64, 64, 128, 160, 1)])
+                                            (8, 20, 6, 10, 3), (64, 64, 128, 160, 1),
+                                            (16, 96, 64, 64, 8)])     # 32 patches x 2 tiles x 8 = 512 workgroups: a 64-channel tile + the 32-channel tail launch
 def test_winograd_3x3_matches_f64(rpe, cin, cout, h, w, b):
     """rpe_conv_wino (F(2x2,3x3) on the f32 matrix cores; the update block's convc2 / convf2 / conv / FlowHead.conv1 shapes, a
     ragged one and the 1280x1024 grid) against the f64 convolution: same bar as the direct kernel, times 3 for the transforms.

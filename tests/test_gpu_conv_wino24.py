@@ -19,7 +19,8 @@ def _tol(x, w):
 
 
 @pytest.mark.parametrize('cin,cout,h,w,b', [(256, 192, 64, 80, 2), (128, 64, 64, 80, 1), (256, 126, 44, 48, 2), (128, 256, 32, 40, 1),
-                                            (8, 20, 6, 12, 3), (64, 64, 128, 160, 1), (64, 96, 20, 36, 9)])
+                                            (8, 20, 6, 12, 3), (64, 64, 128, 160, 1), (64, 96, 20, 36, 9),
+                                            (16, 96, 64, 64, 8)])     # 32 patches x 2 tiles x 8 = 512 workgroups: a 64-channel tile + the 32-channel tail launch
 def test_wino24_matches_f64(rpe, cin, cout, h, w, b):
     """Bias + ReLU into channel slices with a second output; linear; the prepared launcher: F(2x2)'s bar."""
     from rpe_amd import ops
