@@ -602,6 +602,37 @@ int rpe_unet_heads(const float *inp1, const float *inp2, const float *hidden, co
                    long long context_batch_stride, const float *params2d, const float *params3d, int b, int h8, int w8, int H, int W,
                    float *out2d, float *out3d, void *workspace, void *stream);
 
+/* ---- Training route of ONE TinyUNet head (csrc/unet_train.hip): what F.conv2d / F.batch_norm / F.max_pool2d / F.conv_transpose2d /
+ * F.interpolate and their backward kernels do under autograd while the reference trains the heads (scripts/train_posenet.py),
+ * as hand-written kernels, one per operation.  f32 NCHW; every reduction in a fixed order (no float atomics): bit-reproducible.
+ *   input: the channel concatenation of nsrc <= 4 maps (n, src_channels[k], h8, w8), never materialised: src[k] points at channel 0 of
+ *     row 0, src_batch_strides[k] is the distance between rows in floats (so a channel slice of a wider tensor is fine); every
+ *     src_channels[k] must be a multiple of 8 (RPE_E_UNSUPPORTED otherwise).  src, src_channels, src_batch_strides, params,
+ *     running_mean, running_var, num_batches_tracked, momentum and eps are HOST arrays (of device pointers / of values).
+ *   params: the 36 parameter tensors in torch's own layouts, in the order documented in csrc/unet_train_host.h (per encoder stage
+ *     conv1.weight, conv1.bias, norm.weight, norm.bias, conv2.weight, conv2.bias; per decoder stage upconv.weight, upconv.bias,
+ *     conv1.weight, conv1.bias, norm.weight, norm.bias, conv2.weight, conv2.bias; head.weight, head.bias).
+ *   norms (3 encoder, then 2 decoder): bit k of train_mask set = batch statistics (biased variance) and running_mean[k] / running_var[k]
+ *     (momentum[k], unbiased variance) and *num_batches_tracked[k] (int64; the array or an entry may be NULL) updated exactly once, as
+ *     F.batch_norm(training=True) does; bit clear = the running statistics are used and left alone.
+ *   out (n,1,out_h,out_w): the head map resized bilinearly (align_corners=False), through a sigmoid if `sigmoid` is set.
+ *   workspace: rpe_unet_train_workspace_bytes(n, cin, h8, w8, out_h, out_w) bytes (cin = sum of src_channels; 0 = unsupported size);
+ *     the forward leaves the saved activations in it, rpe_unet_train_backward must get the same, untouched workspace and the same
+ *     src / params / train_mask / sizes.  It writes the parameter gradients back to back in the params order into grad_params
+ *     (rpe_unet_train_grad_floats(cin) floats; tensor k starts at rpe_unet_train_grad_offset(cin, k), k = 36 gives the total) and the
+ *     gradient of the concatenated input (n,cin,h8,w8) into grad_input unless that is NULL.  `out` (the forward's output) is read
+ *     only with `sigmoid`.  The 1/8 grid must be at least 44x44, otherwise RPE_E_UNSUPPORTED. */
+size_t rpe_unet_train_workspace_bytes(int n, int cin, int h8, int w8, int out_h, int out_w);
+size_t rpe_unet_train_grad_floats(int cin);
+size_t rpe_unet_train_grad_offset(int cin, int index);
+int rpe_unet_train_forward(const float *const *src, const int *src_channels, const long long *src_batch_strides, int nsrc,
+                           const float *const *params, float *const *running_mean, float *const *running_var,
+                           long long *const *num_batches_tracked, const float *momentum, const float *eps, int train_mask,
+                           int n, int h8, int w8, int out_h, int out_w, int sigmoid, float *out, void *workspace, void *stream);
+int rpe_unet_train_backward(const float *grad_out, const float *out, const float *const *src, const int *src_channels,
+                            const long long *src_batch_strides, int nsrc, const float *const *params, int train_mask, int n, int h8, int w8,
+                            int out_h, int out_w, int sigmoid, float *grad_params, float *grad_input, void *workspace, void *stream);
+
 /* ---- 7x7 convolutions of few input channels as patch-staged implicit GEMMs (csrc/stem.hip):
  *   cin = 3, stride 2: the encoders' first layer (core/RAFT/core/extractor.py BasicEncoder.conv1/norm1/relu1) on the RAW
  *                      0..255 image with RAFT.forward's normalisation image = 2 * (image / 255) - 1 (core/RAFT/core/raft.py)

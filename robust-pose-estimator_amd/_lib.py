@@ -188,6 +188,12 @@ SIGNATURES = {
     'rpe_unet_params_floats': (_sz, [_i]),
     'rpe_unet_workspace_bytes': (_sz, [_i, _i, _i]),
     'rpe_unet_heads': (_i, [_vp, _vp, _vp, _vp, _ll, _ll, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'rpe_unet_train_workspace_bytes': (_sz, [_i, _i, _i, _i, _i, _i]),
+    'rpe_unet_train_grad_floats': (_sz, [_i]),
+    'rpe_unet_train_grad_offset': (_sz, [_i, _i]),
+    'rpe_unet_train_forward': (_i, [_PVP, _c.POINTER(_i), _c.POINTER(_ll), _i, _PVP, _PVP, _PVP, _PVP, _c.POINTER(_fl), _c.POINTER(_fl), _i,
+                                    _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'rpe_unet_train_backward': (_i, [_vp, _vp, _PVP, _c.POINTER(_i), _c.POINTER(_ll), _i, _PVP, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'rpe_stem_tiles': (_i, [_i, _i, _i]),
     'rpe_stem_packed_floats': (_sz, [_i, _i]),
     'rpe_stem_pack': (_i, [_vp, _i, _i, _vp, _vp]),
@@ -273,7 +279,7 @@ class CountingLib:
 
     def __getattr__(self, name):
         fn = getattr(self._real, name)
-        if not name.startswith('rpe_') or any(k in name for k in ('_bytes', '_floats', '_tiles', 'version')):        # (size queries launch nothing)
+        if not name.startswith('rpe_') or any(k in name for k in ('_bytes', '_floats', '_tiles', '_offset', 'version')):        # (size queries launch nothing)
             return fn
 
         def counted(*a):

@@ -1114,3 +1114,86 @@ def unet_heads(inp1, inp2, hidden, context, params2d, params3d, out_size):
     check(lib().rpe_unet_heads(ptr(i1), ptr(i2), hp, cp, hbs, cbs, ptr(params2d), ptr(params3d), b, h8, w8, H, W, ptr(o2), ptr(o3), ptr(ws),
                                stream_ptr()), 'rpe_unet_heads')
     return o2, o3
+
+
+# ------------------------------------------------------------------------------------------------- weight heads, training route
+UNET_TRAIN_NPARAM, UNET_TRAIN_NNORM = 36, 5          # UT_NPARAM, UT_NNORM of csrc/unet_train_host.h
+
+
+class UNetTrainCtx:
+    """What unet_train_backward needs from unet_train_forward: the workspace with the saved activations, the argument arrays (and the
+    tensors behind their pointers, kept alive) and the sizes."""
+    __slots__ = ('ws', 'src', 'src_c', 'src_bs', 'nsrc', 'params', 'train_mask', 'n', 'cin', 'h8', 'w8', 'out_size', 'sigmoid', 'keep')
+
+
+def _ptr_array(tensors):
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() if t is not None else None for t in tensors])
+
+
+def unet_train_forward(parts, params, norms, out_size, sigmoid=False):
+    """One TinyUNet head in training form (rpe_unet_train_forward, csrc/unet_train.hip) -> (out (n,1,H,W), ctx for unet_train_backward).
+    parts: 1..4 maps (n,c_k,h/8,w/8) whose channel concatenation is the head's input (each may be a channel slice of a wider buffer);
+    params: the 36 parameter tensors in the order of csrc/unet_train_host.h; norms: 5 tuples (running_mean, running_var,
+    num_batches_tracked or None, momentum, eps, training) -- encoder stages, then decoder stages.  Norms in training mode use the batch
+    statistics and have their running statistics updated in place, as F.batch_norm(training=True) does."""
+    if not 1 <= len(parts) <= 4 or len(params) != UNET_TRAIN_NPARAM or len(norms) != UNET_TRAIN_NNORM:
+        raise _lib.RpeError('unet_train_forward: expected 1..4 input parts, 36 parameter tensors and 5 norms')
+    sl = [_chan_slice(t, f'parts[{k}]') for k, t in enumerate(parts)]
+    n, _, h8, w8 = parts[0].shape
+    if any(tuple(t.shape[2:]) != (h8, w8) or t.shape[0] != n for t in parts):
+        raise _lib.RpeError('unet_train_forward: the input parts must share batch and map size')
+    cin = sum(t.shape[1] for t in parts)
+    L = lib()
+    for k, t in enumerate(params):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+                and t.numel() == L.rpe_unet_train_grad_offset(cin, k + 1) - L.rpe_unet_train_grad_offset(cin, k)):
+            raise _lib.RpeError(f'unet_train_forward: params[{k}] must be the contiguous float32 GPU tensor of TinyUNet({cin}) in the documented order')
+    mask = 0
+    for k, (rm, rv, nbt, momentum, eps, training) in enumerate(norms):
+        if rm is None or rv is None or momentum is None:
+            raise _lib.RpeError('unet_train_forward: the norms must track running statistics with a fixed momentum')
+        if not all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in (rm, rv)) or \
+                (nbt is not None and not (nbt.is_cuda and nbt.dtype == torch.int64)):
+            raise _lib.RpeError('unet_train_forward: running statistics must be float32 GPU tensors (num_batches_tracked int64)')
+        mask |= int(bool(training)) << k
+    H, W = out_size
+    nws = L.rpe_unet_train_workspace_bytes(n, cin, h8, w8, H, W)
+    if nws == 0:
+        raise _lib.RpeError('unet_train_forward: unsupported size (the 1/8 grid must be at least 44x44, the channel counts multiples of 8)')
+    c = UNetTrainCtx()
+    c.ws = torch.empty(nws, dtype=torch.uint8, device=parts[0].device)
+    c.src = (ctypes.c_void_p * len(parts))(*[p.value for p, _ in sl])
+    c.src_c = (ctypes.c_int * len(parts))(*[t.shape[1] for t in parts])
+    c.src_bs = (ctypes.c_longlong * len(parts))(*[bs for _, bs in sl])
+    c.nsrc, c.params, c.train_mask = len(parts), _ptr_array(params), mask
+    c.n, c.cin, c.h8, c.w8, c.out_size, c.sigmoid = n, cin, h8, w8, (H, W), int(bool(sigmoid))
+    c.keep = (tuple(parts), tuple(params))
+    out = torch.empty(n, 1, H, W, dtype=torch.float32, device=parts[0].device)
+    rms, rvs, nbts = (_ptr_array([nm[k] for nm in norms]) for k in range(3))
+    mom = (ctypes.c_float * UNET_TRAIN_NNORM)(*[float(nm[3]) for nm in norms])
+    eps = (ctypes.c_float * UNET_TRAIN_NNORM)(*[float(nm[4]) for nm in norms])
+    check(L.rpe_unet_train_forward(c.src, c.src_c, c.src_bs, c.nsrc, c.params, rms, rvs, nbts, mom, eps, mask, n, h8, w8, H, W, c.sigmoid,
+                                   ptr(out), ptr(c.ws), stream_ptr()), 'rpe_unet_train_forward')
+    return out, c
+
+
+def unet_train_backward(grad_out, out, ctx, input_grad=False):
+    """Backward of unet_train_forward (rpe_unet_train_backward) -> (the parameter gradients as one blob in the params order: tensor k
+    at ``unet_train_grad_offsets(cin)[k]``, gradient of the concatenated input (n,cin,h/8,w/8) or None)."""
+    c = ctx
+    H, W = c.out_size
+    g = _nchw(grad_out, 'grad_out')
+    if tuple(g.shape) != (c.n, 1, H, W) or tuple(_nchw(out, 'out').shape) != (c.n, 1, H, W):
+        raise _lib.RpeError('unet_train_backward: grad_out and out must be (n,1,H,W)')
+    L = lib()
+    blob = torch.empty(L.rpe_unet_train_grad_floats(c.cin), dtype=torch.float32, device=g.device)
+    gin = torch.empty(c.n, c.cin, c.h8, c.w8, dtype=torch.float32, device=g.device) if input_grad else None
+    check(L.rpe_unet_train_backward(ptr(g), ptr(out), c.src, c.src_c, c.src_bs, c.nsrc, c.params, c.train_mask, c.n, c.h8, c.w8, H, W, c.sigmoid,
+                                    ptr(blob), ptr(gin), ptr(c.ws), stream_ptr()), 'rpe_unet_train_backward')
+    return blob, gin
+
+
+def unet_train_grad_offsets(cin):
+    """First float of each of the 36 parameter gradients in unet_train_backward's blob, and the blob's size as the 37th entry."""
+    L = lib()
+    return [L.rpe_unet_train_grad_offset(cin, k) for k in range(UNET_TRAIN_NPARAM + 1)]

@@ -4,8 +4,8 @@ reference's argument meaning (core/pose/pose_net.py:14-27,60-85,102-135) and par
 unchanged: ``flow.*``, ``weight_head_2d.0.*``, ``weight_head_3d.0.*``, ``loss_weight``).
 
 Per call: one batch-2n RAFT pass (hand-written HIP throughout: raft.py), one fused HIP pass for depth + back-projection +
-the four warps + both 1/8 stacks, both TinyUNet heads as one HIP kernel chain (csrc/unet.hip; PyTorch-ROCm ops only when
-they train), and the device-resident SE(3) solve.  ``infer`` is generalised from the reference's hard-coded single frame
+the four warps + both 1/8 stacks, both TinyUNet heads as one HIP kernel chain (csrc/unet.hip; when they train: PyTorch-ROCm ops, or
+the kernels of csrc/unet_train.hip with config['train_heads_hip']), and the device-resident SE(3) solve.  ``infer`` is generalised from the reference's hard-coded single frame
 (``flow_predictions[-1][0]`` / ``[1]``, :66-67) to n frames by splitting the RAFT batch in halves.
 """
 import torch
@@ -34,6 +34,11 @@ class PoseNet(nn.Module):
                                                           solver=config.get('solver', 'lbfgs')))
         self.weight_head_2d = nn.Sequential(TinyUNet(in_channels=128 + 128 + 8, output_size=(H, W)), nn.Sigmoid())
         self.weight_head_3d = nn.Sequential(TinyUNet(in_channels=128 + 128 + 8 + 8, output_size=(H, W)), nn.Sigmoid())
+        # config['train_heads_hip']: forward() (the training forward) runs the two heads, forward and backward, on the hand-written
+        # training kernels instead of PyTorch-ROCm ops; only these two heads are switched, and inference is unaffected
+        self.train_heads_hip = bool(config.get('train_heads_hip', False))
+        if self.train_heads_hip:
+            self.weight_head_2d[0].train_hip = self.weight_head_3d[0].train_hip = True
 
     def train(self, mode=True):
         super().train(mode)
@@ -77,7 +82,12 @@ class PoseNet(nn.Module):
             mask1 = (mask1.bool() & valid1) if mask1 is not None else valid1
             mask2 = mask2.bool().clone() if mask2 is not None else torch.ones_like(valid1)
             s = self.stages(image1l, image2l, intrinsics, baseline, depth1, image2r, mask1, mask2, stereo_flow1, heads=False)
-        if self.use_weights:
+        if self.use_weights and self.train_heads_hip:
+            # the heads' training route on hand-written kernels (csrc/unet_train.hip): the parts are read where they are (no torch.cat),
+            # the Sigmoid modules' work is fused into the resize
+            w2d = self.weight_head_2d[0].forward_train_hip((s['inp1'], s['hidden'], s['context']), sigmoid=True)
+            w3d = self.weight_head_3d[0].forward_train_hip((s['inp1'], s['inp2'], s['hidden'], s['context']), sigmoid=True)
+        elif self.use_weights:
             w2d = self.weight_head_2d(torch.cat((s['inp1'], s['hidden'], s['context']), dim=1))
             w3d = self.weight_head_3d(torch.cat((s['inp1'], s['inp2'], s['hidden'], s['context']), dim=1))
         else:

@@ -8,8 +8,10 @@ with its parameter names (``encoder.enc_blocks.i.conv1/norm/conv2``, ``decoder.u
 the preceding conv bias, into one per-channel affine map applied by ``rpe_affine_act``:
     encoder stage : conv1 (no bias) -> [affine + ReLU]                 -> conv2            (conv-norm-relu-conv, :15-16)
     decoder stage : conv1 (no bias) -> [bias + ReLU] -> [affine]       -> conv2            (conv-relu-norm-conv, :18-20)
-Training (gradients enabled, or norms in train mode): the same architecture on plain differentiable PyTorch-ROCm ops, batch norm in the module's
-train/eval state -- the heads are what the reference trains (scripts/train_posenet.py:97-136)."""
+Training (gradients enabled, or norms in train mode), batch norm in the module's train/eval state -- the heads are what the reference
+trains (scripts/train_posenet.py:97-136) -- has two routes: by default the same architecture on plain differentiable PyTorch-ROCm ops
+(``forward_train``); with ``TRAIN_HIP`` set (or ``TinyUNet.train_hip`` on one head) ``forward_train_hip``: forward and backward as
+hand-written kernels, one per operation (csrc/unet_train.hip, ``_UNetTrainFn``), deterministic and without library kernels."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -17,6 +19,7 @@ import torch.nn.functional as F
 from . import ops
 
 WIDTHS = (16, 32, 64)
+TRAIN_HIP = False       # the training route on the hand-written kernels (csrc/unet_train.hip) for every TinyUNet whose own train_hip is None
 
 
 class _Stage(nn.Module):
@@ -83,7 +86,55 @@ def pack_params(net):
     return blob
 
 
+def train_params(net):
+    """The 36 parameters in the order rpe_unet_train_forward reads them and rpe_unet_train_backward writes their gradients
+    (csrc/unet_train_host.h), fetched from the modules' current attributes."""
+    out = []
+    for st in net.encoder.enc_blocks:
+        out += [st.conv1.weight, st.conv1.bias, st.norm.weight, st.norm.bias, st.conv2.weight, st.conv2.bias]
+    for upc, st in zip(net.decoder.upconvs, net.decoder.dec_blocks):
+        out += [upc.weight, upc.bias, st.conv1.weight, st.conv1.bias, st.norm.weight, st.norm.bias, st.conv2.weight, st.conv2.bias]
+    return out + [net.head.weight, net.head.bias]
+
+
+class _UNetTrainFn(torch.autograd.Function):
+    """forward_train as one autograd node on the kernels of csrc/unet_train.hip: forward keeps the workspace with the saved
+    activations, backward runs the backward chain and hands the blob's slices to the parameters (and the input parts)."""
+
+    @staticmethod
+    def forward(ctx, net, nparts, sigmoid, *tensors):
+        parts, params = tensors[:nparts], tensors[nparts:]
+        # (num_batches_tracked is left alone, as by forward_train: F.batch_norm updates the running statistics, the count is nn.BatchNorm2d's)
+        norms = [(n.running_mean, n.running_var, None, n.momentum, n.eps, n.training)
+                 for n in (st.norm for st in list(net.encoder.enc_blocks) + list(net.decoder.dec_blocks))]
+        out, ctx.call = ops.unet_train_forward([p.detach() for p in parts], [p.detach() for p in params], norms, net.out_sz, sigmoid)
+        ctx.nparts, ctx.shapes = nparts, [p.shape for p in params]
+        ctx.save_for_backward(out, *tensors)          # (the backward reads parts and parameters again: autograd checks their versions)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        out = ctx.saved_tensors[0]
+        call, nparts = ctx.call, ctx.nparts
+        need = ctx.needs_input_grad[3:]
+        blob, gin = ops.unet_train_backward(grad_out.contiguous(), out, call, input_grad=any(need[:nparts]))
+        grads = [None] * len(need)
+        if gin is not None:
+            c0 = 0
+            for k in range(nparts):
+                ck = call.src_c[k]
+                grads[k] = gin[:, c0:c0 + ck] if need[k] else None
+                c0 += ck
+        off = ops.unet_train_grad_offsets(call.cin)
+        for k, shape in enumerate(ctx.shapes):
+            if need[nparts + k]:
+                grads[nparts + k] = blob[off[k]:off[k + 1]].view(shape)
+        return (None, None, None, *grads)
+
+
 class TinyUNet(nn.Module):
+    train_hip = None        # this head's training route: True / False, or None = the module constant TRAIN_HIP
+
     def __init__(self, in_channels, output_size):
         super().__init__()
         down = (in_channels,) + WIDTHS
@@ -105,9 +156,24 @@ class TinyUNet(nn.Module):
         self._check_size(x)
         batch_stats = any(st.norm.training for st in list(self.encoder.enc_blocks) + list(self.decoder.dec_blocks))
         if batch_stats or (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))):
+            if TRAIN_HIP if self.train_hip is None else self.train_hip:
+                return self.forward_train_hip((x,))
             return self.forward_train(x)
         with torch.no_grad():
             return self.forward_infer(x)
+
+    def forward_train_hip(self, parts, sigmoid=False):
+        """``forward_train`` of the channel concatenation of ``parts`` (never materialised; each (n,c_k,h/8,w/8) with c_k a multiple
+        of 8, possibly a channel slice of a wider buffer) on the hand-written training kernels (csrc/unet_train.hip), differentiable
+        with respect to every parameter and every part; ``sigmoid`` fuses the nn.Sigmoid PoseNet puts behind the head.  Norms follow
+        their module's train / eval state and have their running statistics updated as F.batch_norm does.
+        The parameter pointers are read from the modules on every call, so an optimiser (or anything else) that writes the parameters
+        through ``.data`` is seen by the next forward -- unlike a recorded pass, nothing here is packed or cached.  Between a forward and
+        its backward they must stay as they are: the backward reads them again, and autograd refuses an in-place change it can see
+        (a write through ``.data`` it cannot see would pair new weights with the saved activations)."""
+        parts = tuple(p if p.stride(3) == 1 and p.stride(2) == p.shape[3] and p.stride(1) == p.shape[2] * p.shape[3] else p.contiguous() for p in parts)
+        self._check_size(parts[0])
+        return _UNetTrainFn.apply(self, len(parts), bool(sigmoid), *parts, *train_params(self))
 
     def forward_train(self, x):
         """core/unet/unet.py:7-77 on differentiable torch ops (encoder: conv-norm-relu-conv + max-pool; decoder: up-conv,
