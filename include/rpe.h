@@ -57,7 +57,8 @@ const char *rpe_version(void);
  *   rpe_pose_gate_chain_rows, for tracking several sequences frame to model in one batch (8).  rpe_conv_wino24* and RPE_OP_CONV_WINO24
  *   (Winograd F(2x4,3x3)) were added without a new minor: probe for them with dlsym.  So were rpe_flow_forward_interpolate, rpe_flow_seed
  *   and RPE_OP_FLOW_SEED (warm start of the update loop), rpe_ingest_stereo (the one-call input side) and rpe_pose_quality /
- *   rpe_pose_quality_workspace_bytes (the solve-quality report); the next RPE_ABI_MINOR bump counts them and rpe_conv_wino24*. */
+ *   rpe_pose_quality_workspace_bytes (the solve-quality report), and rpe_conv_fused_m96 with RPE_OP_CONV_FUSED_M96 (the 96-row tile class
+ *   of the stride-2 3x3 layers); the next RPE_ABI_MINOR bump counts them and rpe_conv_wino24*. */
 #define RPE_ABI_VERSION 5
 #define RPE_ABI_MINOR 4
 int rpe_abi_minor(void);
@@ -417,6 +418,12 @@ size_t rpe_conv_packed_floats(int cout, int cin, int kh, int kw);
 /* weight (cout, cin, kh, kw) contiguous -> packed (tap-major 16-channel steps, output channels padded to 128) */
 int rpe_conv_pack(const float *weight, int cout, int cin, int kh, int kw, float *packed, void *stream);
 int rpe_conv_fused(const rpe_conv_desc *desc, void *stream);
+/* rpe_conv_fused with one more tile class: a stride-2 3x3 launch of 96 output channels without residual / add / out2 runs 96(co) x
+ * 128(px) tiles in which no wave idles (csrc/conv_s2.hip) instead of 128-row tiles a quarter of whose rows do not exist -- whatever the
+ * launch size, so the caller picks this entry point for launches that fill the chip (rpe_conv_fused turns to 64 x 64 tiles below 512
+ * workgroups).  Bit-identical to rpe_conv_fused, the statistics records included; every other descriptor runs exactly as
+ * rpe_conv_fused (same rules, same codes). */
+int rpe_conv_fused_m96(const rpe_conv_desc *desc, void *stream);
 /* The same operation for 3x3 stride-1 convolutions with LINEAR / RELU epilogues (even h and w, cin % 4 == 0) as Winograd
  * F(2x2,3x3) on the f32 matrix cores: 2.25x fewer matrix FLOPs than the direct form (csrc/conv_wino.hip; the update block's
  * convc2, convf2, conv and FlowHead.conv1, core/RAFT/core/update.py, and the encoders' residual blocks,
@@ -556,6 +563,7 @@ int rpe_instnorm_finalize(const float *partials, int tiles, int b, int c, int hw
 #define RPE_OP_LOOKUP_CONV1X1 16    /*       const rpe_lookup_conv1x1_args * -> rpe_corr_lookup_conv1x1 */
 #define RPE_OP_CONV_WINO24 17      /*       const rpe_conv_desc *  -> rpe_conv_wino24      */
 #define RPE_OP_FLOW_SEED 18        /*       const rpe_flow_seed_args * -> rpe_flow_seed    */
+#define RPE_OP_CONV_FUSED_M96 19   /*       const rpe_conv_desc *  -> rpe_conv_fused_m96   */
 #define RPE_OP_EVENT_RECORD 32     /*       void *const * (address of a hipEvent_t handle; NULL handle = no-op) */
 #define RPE_OP_STREAM_WAIT 33      /*       void *const * (the same)                       */
 typedef struct rpe_op {

@@ -87,7 +87,7 @@ class FlowSeedArgs(_c.Structure):
 # RPE_OP_* of include/rpe.h
 OP_CONV_FUSED, OP_CONV_WINO, OP_CONV_WINO1D, OP_CONV1X1, OP_CONV_WINO_X3, OP_CONV_WINO1D_X3, OP_CONV1X1_X3 = 1, 2, 3, 4, 5, 6, 7
 OP_CORR_LOOKUP, OP_STEM_CONV, OP_FLOW_UPDATE, OP_COPY_PLANES, OP_INSTNORM_FINALIZE, OP_INSTNORM_APPLY, OP_UPSAMPLE_CONVEX, OP_CORR_BUILD = 8, 9, 10, 11, 12, 13, 14, 15
-OP_LOOKUP_CONV1X1, OP_CONV_WINO24, OP_FLOW_SEED = 16, 17, 18
+OP_LOOKUP_CONV1X1, OP_CONV_WINO24, OP_FLOW_SEED, OP_CONV_FUSED_M96 = 16, 17, 18, 19
 OP_EVENT_RECORD, OP_STREAM_WAIT = 32, 33
 # kind -> (entry point, argument struct) of every op a launch list carries (csrc/oplist.hip's run_one).  An entry point with an argument
 # struct takes its fields in order, then the stream; the rpe_conv_desc kinds take the descriptor by pointer, then the stream.
@@ -99,12 +99,12 @@ LIST_OPS = {OP_CONV_FUSED: ('rpe_conv_fused', ConvDesc), OP_CONV_WINO: ('rpe_con
             OP_INSTNORM_FINALIZE: ('rpe_instnorm_finalize', InstnormFinalizeArgs), OP_INSTNORM_APPLY: ('rpe_instnorm_apply_ex', InstnormApplyArgs),
             OP_UPSAMPLE_CONVEX: ('rpe_upsample_convex', UpsampleConvexArgs), OP_CORR_BUILD: ('rpe_corr_build_ex', CorrBuildArgs),
             OP_LOOKUP_CONV1X1: ('rpe_corr_lookup_conv1x1', LookupConv1x1Args), OP_CONV_WINO24: ('rpe_conv_wino24', ConvDesc),
-            OP_FLOW_SEED: ('rpe_flow_seed', FlowSeedArgs)}
+            OP_FLOW_SEED: ('rpe_flow_seed', FlowSeedArgs), OP_CONV_FUSED_M96: ('rpe_conv_fused_m96', ConvDesc)}
 KIND_OF_ENTRY = {entry: kind for kind, (entry, _) in LIST_OPS.items()}
 
 ABI_MINOR = 3              # RPE_ABI_MINOR of the single-map surfel entry points (rpe_surfel_*)
 ABI_MINOR_MANY = 4         # RPE_ABI_MINOR of rpe_surfel_*_many and rpe_pose_gate_chain_rows: the newest additions this binding calls
-                           # (rpe_conv_wino24*, rpe_flow_forward_interpolate, rpe_flow_seed and rpe_ingest_stereo came later under the same minor:
+                           # (rpe_conv_wino24*, rpe_flow_forward_interpolate, rpe_flow_seed, rpe_ingest_stereo and rpe_conv_fused_m96 came later under the same minor:
                            # loading binds every SIGNATURES entry, so a library without them fails there)
 SURFEL_MAX_MAPS = 64       # RPE_SURFEL_MAX_MAPS: maps per rpe_surfel_*_many call
 ABI_VERSION = 5            # RPE_ABI_VERSION of include/rpe.h these struct mirrors were written against

@@ -19,42 +19,8 @@
 // Zero padding: rows (y+dy outside the map) are zero-filled by the loader (whole float4s, W % 4 == 0); columns
 // (x+dx outside the row) are masked per lane when the B operand is read.
 #include "conv_host.h"
+#include "conv_igemm.h"
 #include <type_traits>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-#define CK 16
-#define SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)     /* nothing is scheduled across this point */
-
-struct ConvP {
-    const float* x; long long xbs;            // first input channel of the slice; batch stride (floats)
-    const float* wp;                          // packed weights [step][16][coP]
-    int cin, cout, coP, H, W, hw, kh;         // H, W, hw: OUTPUT map
-    int Hin, Win;                             // input map (= H, W unless stride 2)
-    const float* bias;                        // [cout] or null
-    const float* add; long long abs_;         // (b, cout, hw) pre-activation addend or null
-    int mode;
-    float* out; long long obs;                // channel 0 of the destination slice; batch stride
-    float* out2; long long o2bs;              // second destination (RPE_CONV_RELU/LINEAR: copy; GATE_ZR: r*h)
-    const float* h; long long hbs;            // hidden state, channels [0, c)
-    const float* z; long long zbs;            // update gate (GATE_H)
-    int cgate;
-    const float* scale;                       // [cout] or null: v = acc * scale + ...
-    const float* res; long long rbs;          // residual added after the activation, then ReLU again (encoder blocks)
-    float* stats;                             // [b][cout][tiles_n][2] partial (sum, sum of squares) of v, or null
-    const float* pre;                         // [b][cin][2] (mean, 1/std) or null: the input is normalised + ReLU'd as it is staged
-};
-
-
-// Sum over each 32-lane half of the wave with DPP moves (VALU rate, no LDS traffic): quad butterflies, row half-mirror,
-// row mirror, then lane 15 of each even 16-lane row is broadcast into the odd row.  Lanes 31 and 63 hold the totals.
-__device__ __forceinline__ float half_wave_sum(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));   // row_half_mirror
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));   // row_mirror
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x142, 0xA, 0xF, true));   // row_bcast:15 into rows 1, 3
-    return v;
-}
 
 // LDS layouts are K-contiguous: As[m][KS], Bs[4 + n][KS] with KS = 20 floats (16 used): a lane fetches the 8 k-values
 // it feeds to 8 consecutive MFMAs with two ds_read_b128 (rows 80 B apart: 16 consecutive rows tile the 64 banks
@@ -743,7 +709,9 @@ extern "C" int rpe_conv_pack(const float* weight, int cout, int cin, int kh, int
 
 static_assert(sizeof(rpe_conv_desc) == 200, "rpe_conv_desc layout is part of the ABI (ctypes mirror in _lib.py)");
 
-extern "C" int rpe_conv_fused(const rpe_conv_desc* d, void* stream) {
+// m96: stride-2 3x3 launches of 96 output channels run the 96-row tile class (conv_s2.hip; bit-identical, statistics records included)
+// when their epilogue is one it has; every other descriptor takes the route below either way.
+static int conv_fused(const rpe_conv_desc* d, void* stream, bool m96) {
     if (!conv_desc_present(d)) return RPE_E_BADARG;
     if (d->kh < 1 || !(d->kh & 1) || (d->kw != 1 && d->kw != 3 && d->kw != 5)) return RPE_E_UNSUPPORTED;
     if ((d->w & 3) || !aligned16(d->x, d->x_batch_stride)) return RPE_E_UNSUPPORTED;     // 16-B input loads
@@ -769,6 +737,8 @@ extern "C" int rpe_conv_fused(const rpe_conv_desc* d, void* stream) {
         const int t128 = ceil_div(P.hw, 128), t64 = ceil_div(P.hw, 64);
         const bool small = conv_s2_small(d->cout, P.hw, d->b);
         if (d->stats && d->stats_tiles != 0 && d->stats_tiles != ceil_div(P.hw, 32)) return RPE_E_BADARG;
+        // (whatever the launch size: the caller asks for this class where the launch fills the chip, raft.S2_M96_MIN_WGS)
+        if (m96 && d->kw == 3 && d->cout == 96 && !d->residual && !d->add && !d->out2) return conv_s2_m96_launch(P, d->b, s);
         if (small) {
             dim3 g2(t64, ceil_div(d->cout, 64), d->b);
             if (d->kw == 3) hipLaunchKernelGGL((k_conv_igemm<3, 2, true, 1, false, true>), g2, dim3(256), 0, s, P);
@@ -803,6 +773,9 @@ extern "C" int rpe_conv_fused(const rpe_conv_desc* d, void* stream) {
 #undef LAUNCH
     return rpe_check_launch();
 }
+
+extern "C" int rpe_conv_fused(const rpe_conv_desc* d, void* stream) { return conv_fused(d, stream, false); }
+extern "C" int rpe_conv_fused_m96(const rpe_conv_desc* d, void* stream) { return conv_fused(d, stream, true); }
 
 extern "C" int rpe_conv_stats_tiles(int cout, int h, int w, int stride) {
     if (cout <= 0 || h <= 0 || w <= 0 || (stride != 1 && stride != 2)) return 0;

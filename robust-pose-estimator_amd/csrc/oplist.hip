@@ -27,6 +27,7 @@ static int run_one(const rpe_op& op, void* const* streams, int n_streams) {
     void* st = streams[op.stream];
     switch (op.kind) {
     case RPE_OP_CONV_FUSED: return rpe_conv_fused(as<rpe_conv_desc>(op), st);
+    case RPE_OP_CONV_FUSED_M96: return rpe_conv_fused_m96(as<rpe_conv_desc>(op), st);
     case RPE_OP_CONV_WINO: return rpe_conv_wino(as<rpe_conv_desc>(op), st);
     case RPE_OP_CONV_WINO24: return rpe_conv_wino24(as<rpe_conv_desc>(op), st);
     case RPE_OP_CONV_WINO1D: return rpe_conv_wino1d(as<rpe_conv_desc>(op), st);

@@ -38,6 +38,9 @@ from . import ops
 WINOGRAD = True          # 3x3 layers as F(2x2,3x3), the GRU's 1x5 / 5x1 as F(4,5); False = the direct implicit GEMM (A/B measurements)
 WINO_2X4 = True          # under WINOGRAD, 3x3 layers on maps with w % 4 == 0 as F(2x4,3x3) (rpe_conv_wino24: a quarter fewer products);
                          # False = F(2x2) everywhere (A/B measurements)
+S2_M96 = True            # the stride-2 3x3 layers of 96 output channels on 96-row tiles (rpe_conv_fused_m96: no idle wave; bit-identical);
+                         # False = rpe_conv_fused's 128-row tiles (A/B measurements)
+S2_M96_MIN_WGS = 512     # ... for launches of at least this many 128-pixel workgroups: below, rpe_conv_fused's 64 x 64 tiles fill the chip better
 CORR_BF16X3 = False      # EXPERIMENT: correlation products as six bf16 products of an exact 3-way split (bench.py --corr-bf16x3)
 CONV_BF16X3 = False      # LABELLED VARIANT (bench.py --conv-bf16x3; never the headline): the update block's 3x3 layers with >= 128 input
 #                          channels (convc2, conv, FlowHead.conv1, the mask head's 3x3) through rpe_conv_wino_x3 -- Winograd products as six
@@ -237,7 +240,9 @@ def _encoder_conv(conv, x, mode=ops.CONV_LINEAR, affine=None, residual=None, pre
         ops.conv_wino(x, pw, mode, out, scale=scale, bias=bias, residual=residual, stats=stats, pre_norm=pre_norm)
     else:
         stats = ops.conv_stats_buffer(b, cout, hh, ww, x.device, stride=st) if moments else None
-        ops.conv_fused(x, _packed(conv), mode, out, scale=scale, bias=bias, residual=residual, stats=stats, stride=st, pre_norm=pre_norm)
+        m96 = S2_M96 and st == 2 and conv.kernel_size == (3, 3) and cout == 96 and b * -(-(hh // 2) * (ww // 2) // 128) >= S2_M96_MIN_WGS
+        ops.conv_fused(x, _packed(conv), mode, out, scale=scale, bias=bias, residual=residual, stats=stats, stride=st, pre_norm=pre_norm,
+                       entry='rpe_conv_fused_m96' if m96 else 'rpe_conv_fused')
     return out, stats
 
 
@@ -393,7 +398,7 @@ class BasicEncoder(nn.Module):
                 self._recorded = _Recorded()
             if '_key_tensors' not in self.__dict__:
                 self.__dict__['_key_tensors'] = _key_sources(self)
-            key = (tuple(tuple(im.shape) for im in images), first.device.index, ops.raw_stream(), split_act, WINOGRAD, WINO_2X4, CONV_BF16X3, self.training,
+            key = (tuple(tuple(im.shape) for im in images), first.device.index, ops.raw_stream(), split_act, WINOGRAD, WINO_2X4, S2_M96, S2_M96_MIN_WGS, CONV_BF16X3, self.training,
                    _tensor_key(self.__dict__['_key_tensors']))
             rec = self._recorded.get(key)
             if rec is not None:
