@@ -58,7 +58,8 @@ const char *rpe_version(void);
  *   (Winograd F(2x4,3x3)) were added without a new minor: probe for them with dlsym.  So were rpe_flow_forward_interpolate, rpe_flow_seed
  *   and RPE_OP_FLOW_SEED (warm start of the update loop), rpe_ingest_stereo (the one-call input side) and rpe_pose_quality /
  *   rpe_pose_quality_workspace_bytes (the solve-quality report), and rpe_conv_fused_m96 with RPE_OP_CONV_FUSED_M96 (the 96-row tile class
- *   of the stride-2 3x3 layers); the next RPE_ABI_MINOR bump counts them and rpe_conv_wino24*. */
+ *   of the stride-2 3x3 layers), and rpe_corr_alt_bytes / rpe_corr_alt_prepare / rpe_corr_alt_lookup with RPE_OP_CORR_ALT_PREPARE /
+ *   RPE_OP_CORR_ALT_LOOKUP (correlation without the all-pairs volume); the next RPE_ABI_MINOR bump counts them and rpe_conv_wino24*. */
 #define RPE_ABI_VERSION 5
 #define RPE_ABI_MINOR 4
 int rpe_abi_minor(void);
@@ -303,6 +304,23 @@ int rpe_corr_lookup_rounds(const float *coords, int b, int h8, int w8, int level
 /* Copy one level of the pyramid out as a dense (b*h8*w8, h8>>l, w8>>l) f32 tensor (tests only). */
 int rpe_corr_export_level(const void *pyramid, int b, int h8, int w8, int levels, int level, float *dense,
                           void *stream);
+
+/* ---- Correlation WITHOUT the all-pairs volume (upstream RAFT's alternate_corr; csrc/corr_alt.hip).  The window of every query is
+ * recomputed from the two feature maps at every lookup; what is kept between lookups is a scratch of pixel-major feature maps:
+ * fmap1 / sqrt(c) and fmap2 with its levels - 1 pooled copies (2x2 mean, stride 2, sizes floored) -- pooling fmap2 and pooling the
+ * correlation over its target axes are the same linear map.  f32 only; c as rpe_corr_build takes it (a multiple of 16, <= 256).
+ * rpe_corr_alt_bytes: bytes of the scratch; 0 for exactly the (b, h8, w8, levels) for which rpe_corr_pyramid_bytes_ex(.., RPE_F32) is 0
+ * (and for a c the route does not take).  At most b c h8 w8 4 (1 + 4/3) bytes plus RPE_CORR_ALT_PAD bytes per level. */
+#define RPE_CORR_ALT_PAD 512
+size_t rpe_corr_alt_bytes(int b, int c, int h8, int w8, int levels);
+/* Once per pass: fmap1, fmap2 (b,c,h8,w8) f32 -> scratch (rpe_corr_alt_bytes bytes, 16-byte aligned). */
+int rpe_corr_alt_prepare(const float *fmap1, const float *fmap2, int b, int c, int h8, int w8, int levels, void *scratch, void *stream);
+/* rpe_corr_lookup's contract on that scratch: coords (b,2,h8,w8) -> out (b, levels*(2r+1)^2, h8, w8) f32, the same channel order
+ * (transposed window), zero for taps outside the level's map, integer taps and fractions from the arithmetic of rpe_corr_lookup_taps.
+ * A query's values depend on its own coordinate and the feature maps of its pair only -- bit for bit, whatever its neighbours' flow
+ * and whichever batch it is part of.  radius must be 4. */
+int rpe_corr_alt_lookup(const void *scratch, const float *coords, int b, int c, int h8, int w8, int levels, int radius, float *out,
+                        void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * RAFT update block, element-wise halves of SepConvGRU (core/RAFT/core/update.py) fused around the
@@ -564,6 +582,8 @@ int rpe_instnorm_finalize(const float *partials, int tiles, int b, int c, int hw
 #define RPE_OP_CONV_WINO24 17      /*       const rpe_conv_desc *  -> rpe_conv_wino24      */
 #define RPE_OP_FLOW_SEED 18        /*       const rpe_flow_seed_args * -> rpe_flow_seed    */
 #define RPE_OP_CONV_FUSED_M96 19   /*       const rpe_conv_desc *  -> rpe_conv_fused_m96   */
+#define RPE_OP_CORR_ALT_PREPARE 20 /*       const rpe_corr_alt_prepare_args *              */
+#define RPE_OP_CORR_ALT_LOOKUP 21  /*       const rpe_corr_alt_lookup_args *               */
 #define RPE_OP_EVENT_RECORD 32     /*       void *const * (address of a hipEvent_t handle; NULL handle = no-op) */
 #define RPE_OP_STREAM_WAIT 33      /*       void *const * (the same)                       */
 typedef struct rpe_op {
@@ -577,6 +597,8 @@ typedef struct rpe_lookup_conv1x1_args {
     long long out_batch_stride; float *out2; long long out2_batch_stride;
 } rpe_lookup_conv1x1_args;
 typedef struct rpe_corr_build_args { const float *fmap1, *fmap2; int b, c, h8, w8, levels, feature_dtype; void *pyramid; } rpe_corr_build_args;
+typedef struct rpe_corr_alt_prepare_args { const float *fmap1, *fmap2; int b, c, h8, w8, levels; void *scratch; } rpe_corr_alt_prepare_args;
+typedef struct rpe_corr_alt_lookup_args { const void *scratch; const float *coords; int b, c, h8, w8, levels, radius; float *out; } rpe_corr_alt_lookup_args;
 typedef struct rpe_stem_conv_args {
     const float *image; int b, cin, h, w, stride; float div, mul, sub; const float *packed; int cout; const float *bias, *scale; int relu;
     float *out, *stats;

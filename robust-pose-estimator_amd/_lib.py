@@ -52,6 +52,14 @@ class CorrBuildArgs(_c.Structure):
     _fields_ = [('fmap1', _vp), ('fmap2', _vp), ('b', _i), ('c', _i), ('h8', _i), ('w8', _i), ('levels', _i), ('feature_dtype', _i), ('pyramid', _vp)]
 
 
+class CorrAltPrepareArgs(_c.Structure):
+    _fields_ = [('fmap1', _vp), ('fmap2', _vp), ('b', _i), ('c', _i), ('h8', _i), ('w8', _i), ('levels', _i), ('scratch', _vp)]
+
+
+class CorrAltLookupArgs(_c.Structure):
+    _fields_ = [('scratch', _vp), ('coords', _vp), ('b', _i), ('c', _i), ('h8', _i), ('w8', _i), ('levels', _i), ('radius', _i), ('out', _vp)]
+
+
 class StemConvArgs(_c.Structure):
     _fields_ = [('image', _vp), ('b', _i), ('cin', _i), ('h', _i), ('w', _i), ('stride', _i), ('div', _fl), ('mul', _fl), ('sub', _fl), ('packed', _vp),
                 ('cout', _i), ('bias', _vp), ('scale', _vp), ('relu', _i), ('out', _vp), ('stats', _vp)]
@@ -88,6 +96,7 @@ class FlowSeedArgs(_c.Structure):
 OP_CONV_FUSED, OP_CONV_WINO, OP_CONV_WINO1D, OP_CONV1X1, OP_CONV_WINO_X3, OP_CONV_WINO1D_X3, OP_CONV1X1_X3 = 1, 2, 3, 4, 5, 6, 7
 OP_CORR_LOOKUP, OP_STEM_CONV, OP_FLOW_UPDATE, OP_COPY_PLANES, OP_INSTNORM_FINALIZE, OP_INSTNORM_APPLY, OP_UPSAMPLE_CONVEX, OP_CORR_BUILD = 8, 9, 10, 11, 12, 13, 14, 15
 OP_LOOKUP_CONV1X1, OP_CONV_WINO24, OP_FLOW_SEED, OP_CONV_FUSED_M96 = 16, 17, 18, 19
+OP_CORR_ALT_PREPARE, OP_CORR_ALT_LOOKUP = 20, 21
 OP_EVENT_RECORD, OP_STREAM_WAIT = 32, 33
 # kind -> (entry point, argument struct) of every op a launch list carries (csrc/oplist.hip's run_one).  An entry point with an argument
 # struct takes its fields in order, then the stream; the rpe_conv_desc kinds take the descriptor by pointer, then the stream.
@@ -99,12 +108,13 @@ LIST_OPS = {OP_CONV_FUSED: ('rpe_conv_fused', ConvDesc), OP_CONV_WINO: ('rpe_con
             OP_INSTNORM_FINALIZE: ('rpe_instnorm_finalize', InstnormFinalizeArgs), OP_INSTNORM_APPLY: ('rpe_instnorm_apply_ex', InstnormApplyArgs),
             OP_UPSAMPLE_CONVEX: ('rpe_upsample_convex', UpsampleConvexArgs), OP_CORR_BUILD: ('rpe_corr_build_ex', CorrBuildArgs),
             OP_LOOKUP_CONV1X1: ('rpe_corr_lookup_conv1x1', LookupConv1x1Args), OP_CONV_WINO24: ('rpe_conv_wino24', ConvDesc),
-            OP_FLOW_SEED: ('rpe_flow_seed', FlowSeedArgs), OP_CONV_FUSED_M96: ('rpe_conv_fused_m96', ConvDesc)}
+            OP_FLOW_SEED: ('rpe_flow_seed', FlowSeedArgs), OP_CONV_FUSED_M96: ('rpe_conv_fused_m96', ConvDesc),
+            OP_CORR_ALT_PREPARE: ('rpe_corr_alt_prepare', CorrAltPrepareArgs), OP_CORR_ALT_LOOKUP: ('rpe_corr_alt_lookup', CorrAltLookupArgs)}
 KIND_OF_ENTRY = {entry: kind for kind, (entry, _) in LIST_OPS.items()}
 
 ABI_MINOR = 3              # RPE_ABI_MINOR of the single-map surfel entry points (rpe_surfel_*)
 ABI_MINOR_MANY = 4         # RPE_ABI_MINOR of rpe_surfel_*_many and rpe_pose_gate_chain_rows: the newest additions this binding calls
-                           # (rpe_conv_wino24*, rpe_flow_forward_interpolate, rpe_flow_seed, rpe_ingest_stereo and rpe_conv_fused_m96 came later under the same minor:
+                           # (rpe_conv_wino24*, rpe_flow_forward_interpolate, rpe_flow_seed, rpe_ingest_stereo, rpe_conv_fused_m96 and rpe_corr_alt_* came later under the same minor:
                            # loading binds every SIGNATURES entry, so a library without them fails there)
 SURFEL_MAX_MAPS = 64       # RPE_SURFEL_MAX_MAPS: maps per rpe_surfel_*_many call
 ABI_VERSION = 5            # RPE_ABI_VERSION of include/rpe.h these struct mirrors were written against
@@ -152,6 +162,7 @@ SIGNATURES = {
     'rpe_flow_forward_interpolate': (_i, [_vp, _i, _i, _i, _vp, _vp]),
     'rpe_corr_pyramid_bytes': (_sz, [_i, _i, _i, _i]),
     'rpe_corr_pyramid_bytes_ex': (_sz, [_i, _i, _i, _i, _i]),
+    'rpe_corr_alt_bytes': (_sz, [_i, _i, _i, _i, _i]),
     'rpe_corr_build': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     'rpe_corr_lookup_conv1x1_packed_floats': (_sz, [_i, _i]),
     'rpe_corr_lookup_conv1x1_pack': (_i, [_vp, _i, _i, _vp, _vp]),

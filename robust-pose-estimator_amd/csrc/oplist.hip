@@ -9,6 +9,8 @@ static_assert(sizeof(rpe_op) == 16, "rpe_op: layout changed -- update _lib.py an
 static_assert(sizeof(rpe_conv_desc) == 200, "rpe_conv_desc: layout changed -- update _lib.py and RPE_ABI_VERSION");
 static_assert(sizeof(rpe_corr_lookup_args) == 48, "rpe_corr_lookup_args: layout changed -- update _lib.py and RPE_ABI_VERSION");
 static_assert(sizeof(rpe_corr_build_args) == 48, "rpe_corr_build_args: layout changed -- update _lib.py and RPE_ABI_VERSION");
+static_assert(sizeof(rpe_corr_alt_prepare_args) == 48, "rpe_corr_alt_prepare_args: layout changed -- update _lib.py and RPE_ABI_VERSION");
+static_assert(sizeof(rpe_corr_alt_lookup_args) == 48, "rpe_corr_alt_lookup_args: layout changed -- update _lib.py and RPE_ABI_VERSION");
 static_assert(sizeof(rpe_stem_conv_args) == 96, "rpe_stem_conv_args: layout changed -- update _lib.py and RPE_ABI_VERSION");
 static_assert(sizeof(rpe_flow_update_args) == 96, "rpe_flow_update_args: layout changed -- update _lib.py and RPE_ABI_VERSION");
 static_assert(sizeof(rpe_copy_planes_args) == 48, "rpe_copy_planes_args: layout changed -- update _lib.py and RPE_ABI_VERSION");
@@ -47,6 +49,14 @@ static int run_one(const rpe_op& op, void* const* streams, int n_streams) {
     case RPE_OP_CORR_BUILD: {
         const auto* a = as<rpe_corr_build_args>(op);
         return rpe_corr_build_ex(a->fmap1, a->fmap2, a->b, a->c, a->h8, a->w8, a->levels, a->feature_dtype, a->pyramid, st);
+    }
+    case RPE_OP_CORR_ALT_PREPARE: {
+        const auto* a = as<rpe_corr_alt_prepare_args>(op);
+        return rpe_corr_alt_prepare(a->fmap1, a->fmap2, a->b, a->c, a->h8, a->w8, a->levels, a->scratch, st);
+    }
+    case RPE_OP_CORR_ALT_LOOKUP: {
+        const auto* a = as<rpe_corr_alt_lookup_args>(op);
+        return rpe_corr_alt_lookup(a->scratch, a->coords, a->b, a->c, a->h8, a->w8, a->levels, a->radius, a->out, st);
     }
     case RPE_OP_STEM_CONV: {
         const auto* a = as<rpe_stem_conv_args>(op);

@@ -515,6 +515,40 @@ class CorrPyramid:
         return dense
 
 
+class AltCorr:
+    """The correlation of a batch of pairs WITHOUT the all-pairs volume (upstream RAFT's ``alternate_corr``; csrc/corr_alt.hip): the
+    device buffer holds fmap1 / sqrt(c) and fmap2 with its pooled copies, pixel-major, and every lookup recomputes its windows from
+    them.  f32 only.  Same build / lookup interface as CorrPyramid (what RAFT's loop calls); ``nbytes`` = the size of the buffer."""
+
+    def __init__(self, b, c, h8, w8, levels=4, radius=4, device='cuda'):
+        self.b, self.c, self.h8, self.w8, self.levels, self.radius = b, c, h8, w8, levels, radius
+        self.nbytes = lib().rpe_corr_alt_bytes(b, c, h8, w8, levels)
+        if self.nbytes == 0 or radius != 4:
+            raise _lib.RpeError('rpe_corr_alt_bytes: unsupported geometry')
+        self.buf = torch.empty(self.nbytes, dtype=torch.uint8, device=device)
+
+    def build(self, fmap1, fmap2):
+        f1, f2 = _dev(fmap1, torch.float32, 'fmap1'), _dev(fmap2, torch.float32, 'fmap2')
+        if tuple(f1.shape) != (self.b, self.c, self.h8, self.w8) or f2.shape != f1.shape:
+            raise _lib.RpeError('corr alt build: shape mismatch')
+        return _launch(_lib.OP_CORR_ALT_PREPARE, (ptr(f1), ptr(f2), self.b, self.c, self.h8, self.w8, self.levels, ptr(self.buf)), (f1, f2, self), self)
+
+    def lookup(self, coords, out=None, prepare=False):
+        """``prepare=True`` (needs ``out``): a zero-argument launcher on these buffers, with ``.op`` for an OpList."""
+        co = _dev(coords, torch.float32, 'coords')
+        if tuple(co.shape) != (self.b, 2, self.h8, self.w8):
+            raise _lib.RpeError('corr alt lookup: coords shape mismatch')
+        ch = self.levels * (2 * self.radius + 1) ** 2
+        if out is None:
+            out = torch.empty(self.b, ch, self.h8, self.w8, dtype=torch.float32, device=co.device)
+        if prepare and co is not coords:
+            raise _lib.RpeError('corr alt lookup: a prepared launch needs contiguous coords and a (b, levels*(2r+1)^2, h8, w8) out buffer')
+        if tuple(_nchw(out, 'out').shape) != (self.b, ch, self.h8, self.w8):
+            raise _lib.RpeError('corr alt lookup: out must be a contiguous (b, levels*(2r+1)^2, h8, w8) buffer')
+        return _launch(_lib.OP_CORR_ALT_LOOKUP, (ptr(self.buf), ptr(co), self.b, self.c, self.h8, self.w8, self.levels, self.radius, ptr(out)),
+                       (self, co, out), out, prepare)
+
+
 class _Packed:
     """A convolution's weight (and bias) re-laid once per weight version for the entry point ``entry`` that launches it.  A subclass states
     what differs: the kernel shapes it takes (``kernels``, or _fits) and the error text, its size query (``size``: floats, or bytes with

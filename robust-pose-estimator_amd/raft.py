@@ -588,7 +588,8 @@ class BasicUpdateBlock(nn.Module):
         launch where that pays (LOOKUP_FUSED), else None."""
         hx, rhx, z_buf, cat_buf, corr, coords1, flow, ctx = (ws[k] for k in ('hx', 'rhx', 'z', 'cat', 'corr', 'coords1', 'flow', 'ctx'))
         P = self.packed_convs(hx.shape[-1])
-        key = (id(P), None if pyr is None else (pyr.buf.data_ptr(), LOOKUP_FUSED, LOOKUP_FUSED_MAX_WGS))
+        alt = isinstance(pyr, ops.AltCorr)                  # (alternate_corr: lookup into the cor buffer, then convc1 -- LOOKUP_FUSED does not apply)
+        key = (id(P), None if pyr is None else (pyr.buf.data_ptr(), LOOKUP_FUSED, LOOKUP_FUSED_MAX_WGS) + ((alt,) if alt else ()))
         cached = ws.get('_launchers')
         if cached is not None and cached[0] == key:
             return cached[2]
@@ -620,7 +621,7 @@ class BasicUpdateBlock(nn.Module):
         if pyr is not None:
             L.lookup, L.lookup_c1 = pyr.lookup(coords1, out=corr, prepare=True), None
             n_wgs = hx.shape[0] * -(-(hx.shape[2] * -(-hx.shape[3] // 8)) // 8)
-            if LOOKUP_FUSED and not CONV_BF16X3 and n_wgs <= LOOKUP_FUSED_MAX_WGS and ops.PackedLookupConv.supported(pyr.levels, pyr.radius, pyr.w8):
+            if not alt and LOOKUP_FUSED and not CONV_BF16X3 and n_wgs <= LOOKUP_FUSED_MAX_WGS and ops.PackedLookupConv.supported(pyr.levels, pyr.radius, pyr.w8):
                 if 'convc1_lookup' not in P:
                     P['convc1_lookup'] = ops.PackedLookupConv(e.convc1.weight, e.convc1.bias)
                 L.lookup_c1 = pyr.lookup_conv1x1(coords1, P['convc1_lookup'], cor, relu=True, prepare=True)
@@ -703,6 +704,10 @@ class RAFT(nn.Module):
         # correlation (BASELINE config 5 "fp16 features").  Here the encoders stay f32 and the feature maps are rounded to
         # fp16 where the correlation consumes them (16-bit matrix cores, f32 accumulation, f32 pyramid).
         self.mixed_precision = bool(config.get('mixed_precision', False))
+        # upstream RAFT's ``alternate_corr``: no all-pairs volume; every iteration recomputes its correlation windows from the feature maps
+        # (ops.AltCorr, csrc/corr_alt.hip).  Opt-in, f32 only.
+        self.alternate_corr = bool(config.get('alternate_corr', False))
+        self._check_alternate_corr()
         self.iters = int(config.get('iters', 12))
         self.hidden_dim = self.context_dim = 128
         self.corr_levels, self.corr_radius = 4, 4
@@ -725,8 +730,20 @@ class RAFT(nn.Module):
                 self._side = s = (torch.cuda.Stream(device=device), torch.cuda.Event(), torch.cuda.Event())
         return s
 
+    def _check_alternate_corr(self):
+        """The on-the-fly correlation is f32 only: refused together with fp16 features or a bf16x3 variant (at construction, and at every
+        pass for the module-level switches)."""
+        if self.alternate_corr and (self.mixed_precision or CORR_BF16X3 or CONV_BF16X3):
+            raise ops._lib.RpeError('RAFT: alternate_corr is f32 only -- not with mixed_precision, CORR_BF16X3 or CONV_BF16X3')
+
     def _pyramid(self, b, h8, w8, device):
         p = self._pyr
+        if self.alternate_corr:
+            self._check_alternate_corr()
+            c = self.fnet.conv2.out_channels
+            if not isinstance(p, ops.AltCorr) or (p.b, p.c, p.h8, p.w8) != (b, c, h8, w8) or p.buf.device != device:
+                self._pyr = p = ops.AltCorr(b, c, h8, w8, self.corr_levels, self.corr_radius, device=device)
+            return p
         x3 = CORR_BF16X3 or CONV_BF16X3
         if p is None or (p.b, p.h8, p.w8) != (b, h8, w8) or p.buf.device != device or getattr(p, 'x3', False) != x3:
             self._pyr = ops.CorrPyramid(b, h8, w8, self.corr_levels, self.corr_radius, device=device, bf16x3=x3)
@@ -834,7 +851,10 @@ class RAFT(nn.Module):
         which the flow head's output layer then updates in place.  ``flow_init`` (warm start): coords1 <- grid + flow_init and flow_init
         as the flow the first iteration's motion encoder sees, in ONE launch (rpe_flow_seed) instead of the four plane copies."""
         c = self.hidden_dim
-        pyr.build(fmap1.float(), fmap2.float(), fp16_features=self.mixed_precision, bf16x3=(CORR_BF16X3 or CONV_BF16X3) and not self.mixed_precision)
+        if self.alternate_corr:
+            pyr.build(fmap1.float(), fmap2.float())
+        else:
+            pyr.build(fmap1.float(), fmap2.float(), fp16_features=self.mixed_precision, bf16x3=(CORR_BF16X3 or CONV_BF16X3) and not self.mixed_precision)
         hx, rhx = ws['hx'], ws['rhx']
         ops.copy_planes(cnet[:, :c], hx[:, :c])
         ctx = self.update_block.context_terms(cnet[:, c:], out=ws['ctx'] if fused else None)      # (fused: written into the persistent buffers)
@@ -888,7 +908,7 @@ class RAFT(nn.Module):
             self.__dict__['_key_tensors'] = _key_sources(self.update_block)
         pyr = self._pyramid(N, h8, w8, dev)
         ws = self._workspace(N, h8, w8, dev)
-        key = (N, h8, w8, dev.index, ops.raw_stream(), iters, upsample, self.mixed_precision, WINOGRAD, WINO_2X4, CORR_BF16X3, CONV_BF16X3, X3_GRU, SIDE_STREAM,
+        key = (N, h8, w8, dev.index, ops.raw_stream(), iters, upsample, self.mixed_precision, self.alternate_corr, WINOGRAD, WINO_2X4, CORR_BF16X3, CONV_BF16X3, X3_GRU, SIDE_STREAM,
                pyr.buf.data_ptr(), ws['hx'].data_ptr(), _tensor_key(self.__dict__['_key_tensors']))
         if flow_init is not None or ret_lowres:                       # (a cold pass keeps the key it always had)
             key += ('warm' if flow_init is not None else 'cold', ret_lowres)

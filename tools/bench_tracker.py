@@ -2,7 +2,8 @@
 """Sequential tracking throughput (the reference's real use: one stereo frame at a time, batch 1):
 PoseEstimator over a synthetic sequence, with and without streaming encoder-feature reuse.
 ``--quality``: instead, ``report_quality`` off and on (reuse_features on), alternating in this process: median frames/s of REPS runs each,
-their spread, and the difference per frame."""
+their spread, and the difference per frame.
+``--alternate-corr``: instead, RAFT's ``alternate_corr`` off and on (reuse_features on), each model warmed up, then one timed run each."""
 import os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -28,6 +29,18 @@ def run(slam):
     torch.cuda.synchronize()
     return time.perf_counter() - t
 
+
+if '--alternate-corr' in sys.argv:
+    base = dict(frame2frame=True, depth_clipping=[1, 250], lbgfs_iters=20, conf_weighing=True, reuse_features=True)
+    model_on = pose_net.PoseNet(dict(cfg, alternate_corr=True)).eval().to(dev)
+    model_on.load_state_dict(model.state_dict())
+    models = {False: model, True: model_on}
+    for on in (False, True):
+        model = models[on]
+        run(base)                                                             # warm-up
+        dt = min(run(base) for _ in range(3))
+        print(f'alternate_corr={on}: {F / dt:.1f} frames/s ({1e3 * dt / F:.2f} ms/frame; best of 3 runs of {F} frames), 640x512, 12 GRU iters, L-BFGS 20')
+    sys.exit(0)
 
 if '--quality' in sys.argv:
     import statistics
