@@ -37,6 +37,16 @@ __device__ __forceinline__ float rn_div(float a, float b) {
     return a / b;
 }
 
+// Maximum of a 2x2 pooling window by torch.max_pool2d's rule: the window in row-major order, a value replaces the running maximum if
+// it is larger or NaN -- so one NaN makes the result NaN (fmaxf drops it); on finite values it is the maximum.
+__device__ __forceinline__ float pool_max4(float a, float b, float c, float d) {
+    float m = a;
+    if (b > m || b != b) m = b;
+    if (c > m || c != c) m = c;
+    if (d > m || d != d) m = d;
+    return m;
+}
+
 // Running (count, mean, M2 = sum of squared deviations) in f64 with the parallel-variance merge (Chan et al.): how the
 // convolution epilogues' per-wave / per-tile instance-norm statistics are combined without cancellation.
 struct StatAcc {

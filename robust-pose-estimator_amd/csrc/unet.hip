@@ -158,7 +158,7 @@ __global__ void k_u_pool(const float* __restrict__ in, float* __restrict__ out, 
     const int x = (int)(e % wo), y = (int)((e / wo) % ho);
     const long long pl = e / ((long long)wo * ho);
     const float* s = in + pl * h * w + (size_t)(2 * y) * w + 2 * x;
-    out[e] = fmaxf(fmaxf(s[0], s[1]), fmaxf(s[w], s[w + 1]));
+    out[e] = pool_max4(s[0], s[1], s[w], s[w + 1]);
 }
 
 struct UUpHead { const float* in; const float* w; const float* bias; float* out; };   // w [cin][4][cout]

@@ -75,7 +75,7 @@ __global__ __launch_bounds__(256) void k_t_conv3(TConvP P) {
 #pragma unroll
     for (int j = 0; j < TCT; ++j) {
         float v = (float)(acc[j] + (P.bias ? (double)P.bias[co0 + j] : 0.0));
-        if (P.relu) v = v > 0.0f ? v : 0.0f;
+        if (P.relu) v = (v > 0.0f || v != v) ? v : 0.0f;               // NaN stays NaN, as in torch.relu
         o[(size_t)j * npix] = v;
     }
 }
@@ -249,7 +249,7 @@ __global__ void k_t_bn_apply(const float* __restrict__ x, const float* __restric
     if (e >= total) return;
     const int c = (int)((e / hw) % C);
     float v = fmaf(rn_mul(rn_sub(x[e], mean[c]), invstd[c]), gamma[c], beta[c]);
-    if (relu) v = v > 0.0f ? v : 0.0f;
+    if (relu) v = (v > 0.0f || v != v) ? v : 0.0f;                       // NaN stays NaN, as in torch.relu
     out[e] = v;
 }
 
@@ -305,7 +305,7 @@ __global__ void k_t_pool(const float* __restrict__ in, float* __restrict__ out, 
     const int x = (int)(e % wo), y = (int)((e / wo) % ho);
     const long long pl = e / ((long long)wo * ho);
     const float* s = in + pl * h * w + (size_t)(2 * y) * w + 2 * x;
-    out[e] = fmaxf(fmaxf(s[0], s[1]), fmaxf(s[w], s[w + 1]));
+    out[e] = pool_max4(s[0], s[1], s[w], s[w + 1]);
 }
 
 // routing, as a gather: thread = pixel of the pooled map's input; it takes its window's gradient if it is the window's first maximum in
