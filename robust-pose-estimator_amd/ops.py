@@ -199,6 +199,19 @@ def _dev(t, dtype=None, name='tensor'):
     return t if t.is_contiguous() else t.contiguous()
 
 
+def _is_f32(t, shape=None, numel=None):
+    return isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() \
+        and (shape is None or tuple(t.shape) == tuple(shape)) and (numel is None or t.numel() == numel)
+
+
+def _f32(t, name, shape=None, numel=None):
+    """``t`` if it is a contiguous float32 GPU tensor [of this shape / of this many elements]; ``name`` = 'wrapper: argument'."""
+    if not _is_f32(t, shape, numel):
+        what = f' of shape {tuple(shape)}' if shape is not None else f' of {numel} elements' if numel is not None else ''
+        raise _lib.RpeError(f'{name} must be a contiguous float32 GPU tensor{what}')
+    return t
+
+
 def _mask(t, name):
     t = _dev(t, None, name)
     if t.dtype == torch.bool:
@@ -477,14 +490,7 @@ class CorrPyramid:
             raise _lib.RpeError('corr lookup_conv1x1: coords must be a contiguous (b,2,h8,w8) tensor')
         if not PackedLookupConv.supported(self.levels, self.radius, self.w8):
             raise _lib.RpeError('corr lookup_conv1x1: needs 4 levels, radius 4 and w8 % 8 == 0 (use lookup + conv1x1)')
-        sl = []
-        for name, t in (('out', out), ('out2', out2)):
-            if t is None:
-                sl += [None, 0]
-                continue
-            if tuple(t.shape) != (self.b, packed.cout, self.h8, self.w8):
-                raise _lib.RpeError(f'corr lookup_conv1x1: {name} must be a ({self.b},{packed.cout},{self.h8},{self.w8}) channel slice')
-            sl += list(_chan_slice(t, name))
+        sl = _opt_slices('corr lookup_conv1x1', self.b, packed.cout, self.h8, self.w8, out=out, out2=out2)
         return _launch(_lib.OP_LOOKUP_CONV1X1, (ptr(self.buf), ptr(co), self.b, self.h8, self.w8, self.levels, self.radius, ptr(packed.packed),
                                                 ptr(packed.bias), int(bool(relu)), *sl), (self, co, packed, out, out2), out, prepare)
 
@@ -665,22 +671,15 @@ def conv3x3_to2(x, weight, bias, add=None, out=None):
 def flow_update(x, weight, bias, coords, coords_out, flow_out=None, dst1=None, dst2=None, prepare=False):
     """rpe_conv3x3_to2_flow: coords_out = conv3x3(x; weight (2,c,3,3)) + bias + coords, and flow = coords_out - pixel grid written to
     ``flow_out`` (b,2,h,w) and into the two-channel slices ``dst1`` / ``dst2`` (e.g. hx[:, 254:256]).  ``prepare=True`` returns a launcher."""
-    _nchw(x, 'x')
+    _nchw(x, 'flow_update: x')
     b, c, hh, ww = x.shape
-    weight = _nchw(weight.detach() if weight.requires_grad else weight, 'weight')
+    weight = _nchw(weight.detach() if weight.requires_grad else weight, 'flow_update: weight')
     if tuple(weight.shape) != (2, c, 3, 3):
         raise _lib.RpeError('flow_update: weight must be (2,c,3,3)')
     for name, t in (('coords', coords), ('coords_out', coords_out), ('flow_out', flow_out)):
-        if t is not None and tuple(_nchw(t, name).shape) != (b, 2, hh, ww):
+        if t is not None and tuple(_nchw(t, f'flow_update: {name}').shape) != (b, 2, hh, ww):
             raise _lib.RpeError(f'flow_update: {name} must be ({b},2,{hh},{ww})')
-    sl = []
-    for name, t in (('dst1', dst1), ('dst2', dst2)):
-        if t is None:
-            sl += [None, 0]
-            continue
-        if tuple(t.shape) != (b, 2, hh, ww):
-            raise _lib.RpeError(f'flow_update: {name} must be a ({b},2,{hh},{ww}) channel slice')
-        sl += list(_chan_slice(t, name))
+    sl = _opt_slices('flow_update', b, 2, hh, ww, dst1=dst1, dst2=dst2)
     return _launch(_lib.OP_FLOW_UPDATE, (ptr(x), ptr(weight), ptr(bias), b, c, hh, ww, ptr(coords), ptr(coords_out), ptr(flow_out), *sl),
                    (x, weight, bias, coords, coords_out, flow_out, dst1, dst2), coords_out, prepare)
 
@@ -722,21 +721,14 @@ def _overlap_span(a, b):
 def flow_seed(flow_init, coords_out=None, flow_out=None, dst1=None, dst2=None, prepare=False):
     """rpe_flow_seed, the front of a warm update loop: coords_out = pixel grid + flow_init, flow_out = flow_init, and flow_init into the
     two-channel slices ``dst1`` / ``dst2`` (e.g. hx[:, 254:256]); flow_init (b,2,h,w) contiguous.  ``prepare=True`` returns a launcher."""
-    fi = _nchw(flow_init, 'flow_init')
+    fi = _nchw(flow_init, 'flow_seed: flow_init')
     b, c, hh, ww = fi.shape
     if c != 2:
         raise _lib.RpeError(f'flow_seed: flow_init must be (b,2,h,w), got {tuple(fi.shape)}')
     for name, t in (('coords_out', coords_out), ('flow_out', flow_out)):
-        if t is not None and tuple(_nchw(t, name).shape) != (b, 2, hh, ww):
+        if t is not None and tuple(_nchw(t, f'flow_seed: {name}').shape) != (b, 2, hh, ww):
             raise _lib.RpeError(f'flow_seed: {name} must be ({b},2,{hh},{ww})')
-    sl = []
-    for name, t in (('dst1', dst1), ('dst2', dst2)):
-        if t is None:
-            sl += [None, 0]
-            continue
-        if tuple(t.shape) != (b, 2, hh, ww):
-            raise _lib.RpeError(f'flow_seed: {name} must be a ({b},2,{hh},{ww}) channel slice')
-        sl += list(_chan_slice(t, name))
+    sl = _opt_slices('flow_seed', b, 2, hh, ww, dst1=dst1, dst2=dst2)
     return _launch(_lib.OP_FLOW_SEED, (ptr(fi), b, hh, ww, ptr(coords_out), ptr(flow_out), *sl), (fi, coords_out, flow_out, dst1, dst2),
                    coords_out, prepare)
 
@@ -764,6 +756,19 @@ def _chan_slice(t, name):
         raise _lib.RpeError(f'{name}: expected a channel slice of a contiguous NCHW buffer')
     _on_current_device(t, name)
     return ptr(t), t.stride(0)
+
+
+def _opt_slices(who, b, c, hh, ww, **named):
+    """The flat [pointer, batch stride, ...] of optional (b,c,hh,ww) channel slices; [None, 0] for one that is not given."""
+    sl = []
+    for name, t in named.items():
+        if t is None:
+            sl += [None, 0]
+        elif tuple(t.shape) != (b, c, hh, ww):
+            raise _lib.RpeError(f'{who}: {name} must be a ({b},{c},{hh},{ww}) channel slice')
+        else:
+            sl += _chan_slice(t, f'{who}: {name}')
+    return sl
 
 
 class PackedConv(_Packed):
@@ -841,51 +846,71 @@ class Conv1x1:
         return conv_fused(x, self.fused, mode, out, out2=out2, prepare=prepare)
 
 
+# The slice rules of an epilogue: descriptor field -> ('min' | 'exact', channels: 'cout' | 'gate' (gate_channels), required); a field
+# without a rule is optional and may have any number of channels
+_PLAIN_RULES = dict(add=('exact', 'cout', False), out=('min', 'cout', True), out2=('min', 'cout', False), residual=('exact', 'cout', False))
+_FUSED_RULES = {CONV_GATE_ZR: dict(add=('exact', 'cout', False), out=('min', 'gate', True), out2=('min', 'gate', True), hidden=('min', 'gate', True)),
+                CONV_GATE_H: dict(add=('exact', 'cout', False), out=('min', 'cout', True), hidden=('min', 'cout', True), zgate=('min', 'cout', True))}
+_WINO_RULES = dict(out=('min', 'cout', True), out2=('min', 'cout', False), residual=('min', 'cout', False))
+_FUSED_MODES = (CONV_LINEAR, CONV_RELU, CONV_GATE_ZR, CONV_GATE_H, CONV_TANH)
+
+
 def conv_fused(x, pc, mode, out, out2=None, add=None, hidden=None, zgate=None, gate_channels=0, scale=None, bias='packed',
                residual=None, stats=None, stride=1, pre_norm=None, prepare=False, entry='rpe_conv_fused'):
     """rpe_conv_fused: out = epilogue(conv(x; pc) * scale + add + bias).  All tensors are channel slices of NCHW buffers.
     ``bias`` defaults to the one packed with the weights; ``stats`` (from conv_stats_buffer) collects the per-tile moments
     instnorm_apply needs.  ``prepare=True`` returns a zero-argument launcher instead of launching: the GRU loop runs the same
     nine convolutions on the same buffers twelve times, and at batch 1 the Python argument checking costs more than the kernels."""
+    d, bias, stats = _conv_desc('conv_fused', x, pc, mode, dict(add=add, out=out, out2=out2, hidden=hidden, zgate=zgate, residual=residual),
+                                _FUSED_RULES.get(mode, _PLAIN_RULES), scale, bias, stats, pre_norm, modes=_FUSED_MODES, tile_major=False,
+                                kernel=(pc.kh, pc.kw), stride=stride, gate_channels=gate_channels)
+    return _launch(_lib.KIND_OF_ENTRY[entry], d, (x, pc, out, out2, add, hidden, zgate, scale, bias, residual, stats, pre_norm), out, prepare)
+
+
+def _conv_desc(who, x, pc, mode, slices, rules, scale, bias, stats, pre_norm, *, modes, tile_major, kernel, stride=1, gate_channels=0):
+    """The ConvDesc of conv_fused / conv_wino after the checks they share -> (descriptor, the bias and the stats tensor it points to).
+    ``slices``: descriptor field -> channel slice on the output map or None, checked against ``rules`` (as _PLAIN_RULES); ``modes``: the epilogues the kernel has; ``tile_major``: the layout of ``stats`` (conv_wino's TileMajorStats, or
+    conv_stats_buffer's channel-major tensor); ``kernel`` = (kh, kw)."""
     d = _lib.ConvDesc()
     b, cin, hh, ww = x.shape
+    cout = pc.cout
     if cin != pc.cin:
-        raise _lib.RpeError(f'conv_fused: input has {cin} channels, weights expect {pc.cin}')
-    d.x, d.x_batch_stride = _chan_slice(x, 'x')
+        raise _lib.RpeError(f'{who}: input has {cin} channels, weights expect {pc.cin}')
+    if mode not in modes:
+        raise _lib.RpeError(f'{who}: mode {mode} is not an epilogue of this kernel' + (' (LINEAR / RELU only)' if len(modes) == 2 else ''))
+    d.x, d.x_batch_stride = _chan_slice(x, f'{who}: x')
     bias = pc.bias if isinstance(bias, str) else bias
     for name, t in (('bias', bias), ('scale', scale)):
-        if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != pc.cout):
-            raise _lib.RpeError(f'conv_fused: {name} must be a contiguous float32 GPU vector of cout elements')
+        if t is not None:
+            _f32(t, f'{who}: {name}', numel=cout)
     d.packed, d.bias, d.scale = ptr(pc.packed), ptr(bias), ptr(scale)
-    for name, t, want_c in (('add', add, pc.cout), ('out', out, None), ('out2', out2, None), ('hidden', hidden, None), ('zgate', zgate, None),
-                            ('residual', residual, pc.cout)):
+    for name, t in slices.items():
+        rule, kind, required = rules.get(name, ('min', None, False))
+        channels = {'cout': cout, 'gate': gate_channels, None: 0}[kind]
         if t is None:
-            setattr(d, name, None); setattr(d, name + '_batch_stride', 0)
-            continue
-        if t.shape[0] != b or tuple(t.shape[2:]) != (hh // stride, ww // stride) or (want_c is not None and t.shape[1] != want_c):
-            raise _lib.RpeError(f'conv_fused: {name} has shape {tuple(t.shape)}')
-        p, s = _chan_slice(t, name)
+            if required:
+                raise _lib.RpeError(f'{who}: this epilogue needs {name}')
+            continue                                          # (a fresh descriptor holds NULL and stride 0)
+        if t.shape[0] != b or tuple(t.shape[2:]) != (hh // stride, ww // stride) or (rule == 'exact' and t.shape[1] != channels):
+            raise _lib.RpeError(f'{who}: {name} has shape {tuple(t.shape)}')
+        if t.shape[1] < channels:
+            raise _lib.RpeError(f'{who}: {name} has too few channels ({t.shape[1]}, the epilogue writes or reads {channels})')
+        p, s = _chan_slice(t, f'{who}: {name}')
         setattr(d, name, p); setattr(d, name + '_batch_stride', s)
-    need = {CONV_LINEAR: pc.cout, CONV_RELU: pc.cout, CONV_GATE_ZR: gate_channels, CONV_GATE_H: pc.cout, CONV_TANH: pc.cout}[mode]
-    if out.shape[1] < need or (mode == CONV_GATE_ZR and (out2 is None or out2.shape[1] < gate_channels or hidden.shape[1] < gate_channels)):
-        raise _lib.RpeError('conv_fused: destination slice has too few channels')
-    if mode == CONV_GATE_H and (hidden is None or zgate is None or hidden.shape[1] < pc.cout or zgate.shape[1] < pc.cout):
-        raise _lib.RpeError('conv_fused: GATE_H needs hidden and zgate with cout channels')
-    if mode in (CONV_LINEAR, CONV_RELU, CONV_TANH) and out2 is not None and out2.shape[1] < pc.cout:
-        raise _lib.RpeError('conv_fused: out2 slice has too few channels')
     if stats is not None:
-        tiles = lib().rpe_conv_stats_tiles(pc.cout, hh, ww, stride)
-        if not (stats.is_cuda and stats.dtype == torch.float32 and stats.is_contiguous() and tuple(stats.shape) == (b, pc.cout, tiles, 3)):
-            raise _lib.RpeError(f'conv_fused: stats must be a contiguous float32 ({b},{pc.cout},{tiles},3) GPU tensor (conv_stats_buffer)')
-        d.stats_tiles = tiles
-    d.stats = ptr(stats)
-    if pre_norm is not None and not (pre_norm.is_cuda and pre_norm.dtype == torch.float32 and pre_norm.is_contiguous()
-                                     and tuple(pre_norm.shape) == (b, cin, 2)):
-        raise _lib.RpeError(f'conv_fused: pre_norm must be a contiguous float32 ({b},{cin},2) GPU tensor')
-    d.pre_norm = ptr(pre_norm)
-    d.b, d.cin, d.cout, d.h, d.w, d.kh, d.kw, d.mode, d.gate_channels = b, cin, pc.cout, hh, ww, pc.kh, pc.kw, mode, gate_channels
-    d.stride = stride
-    return _launch(_lib.KIND_OF_ENTRY[entry], d, (x, pc, out, out2, add, hidden, zgate, scale, bias, residual, stats, pre_norm), out, prepare)
+        if isinstance(stats, TileMajorStats) != tile_major:
+            raise _lib.RpeError(f'{who}: stats must come from ' + ('conv_wino_stats_buffer (tile-major records)' if tile_major else
+                                                                  'conv_stats_buffer (a channel-major tensor)'))
+        if tile_major:
+            stats = _f32(stats.tensor, f'{who}: stats', (b, lib().rpe_conv_wino_stats_tiles(hh, ww), cout, 3))
+        else:
+            d.stats_tiles = lib().rpe_conv_stats_tiles(cout, hh, ww, stride)
+            _f32(stats, f'{who}: stats', (b, cout, d.stats_tiles, 3))
+    if pre_norm is not None:
+        _f32(pre_norm, f'{who}: pre_norm', (b, cin, 2))
+    d.stats, d.pre_norm = ptr(stats), ptr(pre_norm)
+    d.b, d.cin, d.cout, d.h, d.w, (d.kh, d.kw), d.mode, d.gate_channels, d.stride = b, cin, cout, hh, ww, kernel, mode, gate_channels, stride
+    return d, bias, stats
 
 
 def conv_direct(x, weight, bias=None, stride=1, padding=0, relu=False, out=None):
@@ -902,8 +927,7 @@ def conv_direct(x, weight, bias=None, stride=1, padding=0, relu=False, out=None)
     ho, wo = (hh + 2 * ph - kh) // st + 1, (ww + 2 * pw - kw) // st + 1
     if bias is not None:
         bias = bias.detach()
-        if not (bias.is_cuda and bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == cout):
-            raise _lib.RpeError('conv_direct: bias must be a contiguous float32 GPU vector of cout elements')
+        _f32(bias, 'conv_direct: bias', numel=cout)
     if out is None:
         out = torch.empty(b, cout, ho, wo, dtype=torch.float32, device=x.device)
     elif tuple(out.shape) != (b, cout, ho, wo):
@@ -978,38 +1002,8 @@ def conv_wino(x, pw, mode, out, out2=None, scale=None, bias='packed', residual=N
     """rpe_conv_wino: out = epilogue(conv3x3(x; pw) * scale + bias) by Winograd F(2x2,3x3) -- F(2x4,3x3) with a PackedWino24, the
     labelled bf16x3 variant with a PackedWinoX3; tensors are channel slices of NCHW buffers.  ``stats`` (conv_wino_stats_buffer) /
     ``pre_norm`` / ``residual`` / ``scale``: the encoders' epilogues, as conv_fused."""
-    d = _lib.ConvDesc()
-    b, cin, hh, ww = x.shape
-    if cin != pw.cin:
-        raise _lib.RpeError(f'conv_wino: input has {cin} channels, weights expect {pw.cin}')
-    if mode not in (CONV_LINEAR, CONV_RELU):
-        raise _lib.RpeError('conv_wino: LINEAR / RELU epilogues only')
-    d.x, d.x_batch_stride = _chan_slice(x, 'x')
-    bias = pw.bias if isinstance(bias, str) else bias
-    for name, t in (('bias', bias), ('scale', scale)):
-        if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != pw.cout):
-            raise _lib.RpeError(f'conv_wino: {name} must be a contiguous float32 GPU vector of cout elements')
-    d.packed, d.bias, d.scale = ptr(pw.packed), ptr(bias), ptr(scale)
-    for name, t in (('out', out), ('out2', out2), ('residual', residual)):
-        if t is None:
-            setattr(d, name, None); setattr(d, name + '_batch_stride', 0)
-            continue
-        if t.shape[0] != b or tuple(t.shape[2:]) != (hh, ww) or t.shape[1] < pw.cout:
-            raise _lib.RpeError(f'conv_wino: {name} has shape {tuple(t.shape)}')
-        p, s = _chan_slice(t, name)
-        setattr(d, name, p); setattr(d, name + '_batch_stride', s)
-    if stats is not None:
-        tiles = lib().rpe_conv_wino_stats_tiles(hh, ww)
-        if not isinstance(stats, TileMajorStats):
-            raise _lib.RpeError('conv_wino: stats must come from conv_wino_stats_buffer (tile-major records)')
-        stats = stats.tensor
-        if not (stats.is_cuda and stats.dtype == torch.float32 and stats.is_contiguous() and tuple(stats.shape) == (b, tiles, pw.cout, 3)):
-            raise _lib.RpeError(f'conv_wino: stats must be a contiguous float32 ({b},{tiles},{pw.cout},3) GPU tensor (conv_wino_stats_buffer)')
-    if pre_norm is not None and not (pre_norm.is_cuda and pre_norm.dtype == torch.float32 and pre_norm.is_contiguous()
-                                     and tuple(pre_norm.shape) == (b, cin, 2)):
-        raise _lib.RpeError(f'conv_wino: pre_norm must be a contiguous float32 ({b},{cin},2) GPU tensor')
-    d.stats, d.pre_norm = ptr(stats), ptr(pre_norm)
-    d.b, d.cin, d.cout, d.h, d.w, d.kh, d.kw, d.mode, d.stride = b, cin, pw.cout, hh, ww, 3, 3, mode, 1
+    d, bias, stats = _conv_desc('conv_wino', x, pw, mode, dict(out=out, out2=out2, residual=residual), _WINO_RULES, scale, bias, stats, pre_norm,
+                                modes=(CONV_LINEAR, CONV_RELU), tile_major=True, kernel=(3, 3))
     return _launch(_lib.KIND_OF_ENTRY[pw.entry], d, (x, pw, out, out2, scale, bias, residual, stats, pre_norm), out, prepare)
 
 
@@ -1038,7 +1032,7 @@ def _stats_layout(stats, b, c, who):
     """(tensor, signed tile count for the C ABI: negative = tile-major) after validating the records' shape against (b, c)."""
     tile_major = isinstance(stats, TileMajorStats)
     t = stats.tensor if tile_major else stats
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 4 and t.shape[3] == 3):
+    if not (_is_f32(t) and t.dim() == 4 and t.shape[3] == 3):
         raise _lib.RpeError(f'{who}: stats must be a contiguous float32 4-D GPU tensor of (count, mean, M2) records')
     want = (b, t.shape[1], c) if tile_major else (b, c, t.shape[2])
     if tuple(t.shape[:3]) != want or t.shape[1 if tile_major else 2] < 1:
@@ -1070,20 +1064,19 @@ def instnorm_apply(x, stats, eps=1e-5, relu=True, residual=None, out=None, resid
     pure stream with several workgroups per plane, the faster form behind large maps (the records are merged once, not per workgroup).
     ``residual_norm`` (b,c,2) from instnorm_finalize: the residual is a RAW convolution output, normalised (+ ReLU'd unless
     ``residual_relu=False``: a stride-2 block's shortcut has none) on the fly."""
-    _nchw(x, 'x')
+    _nchw(x, 'instnorm_apply: x')
     b, c, hh, ww = x.shape
     if isinstance(stats, torch.Tensor) and stats.dim() == 3:              # (mean, 1/std) pairs of instnorm_finalize: a pure streaming pass
-        if not (stats.is_cuda and stats.dtype == torch.float32 and stats.is_contiguous() and tuple(stats.shape) == (b, c, 2)):
-            raise _lib.RpeError(f'instnorm_apply: precomputed moments must be a contiguous float32 ({b},{c},2) GPU tensor (instnorm_finalize)')
-        t, tiles = stats, 0
+        t, tiles = _f32(stats, 'instnorm_apply: stats (the moments of instnorm_finalize)', (b, c, 2)), 0
     else:
         t, tiles = _stats_layout(stats, b, c, 'instnorm_apply')
-    if residual is not None and _nchw(residual, 'residual').shape != x.shape:
+    if residual is not None and _nchw(residual, 'instnorm_apply: residual').shape != x.shape:
         raise _lib.RpeError('instnorm_apply: residual must have the shape of x')
-    if residual_norm is not None and (residual is None or not (residual_norm.is_cuda and residual_norm.dtype == torch.float32
-                                                               and residual_norm.is_contiguous() and tuple(residual_norm.shape) == (b, c, 2))):
-        raise _lib.RpeError(f'instnorm_apply: residual_norm must be a contiguous float32 ({b},{c},2) GPU tensor next to a residual')
-    out = x if out is None else _nchw(out, 'out')
+    if residual_norm is not None:
+        if residual is None:
+            raise _lib.RpeError('instnorm_apply: residual_norm needs a residual')
+        _f32(residual_norm, 'instnorm_apply: residual_norm', (b, c, 2))
+    out = x if out is None else _nchw(out, 'instnorm_apply: out')
     flags = int(bool(relu)) | (0 if residual_relu or residual_norm is None else 2)
     return _launch(_lib.OP_INSTNORM_APPLY, (ptr(x), ptr(t), tiles, b, c, hh * ww, float(eps), flags, ptr(residual), ptr(residual_norm), ptr(out)),
                    (x, t, residual, residual_norm, out), out)
@@ -1105,20 +1098,17 @@ class PackedStem(_Packed):
 def stem_conv(image, ps, bias=None, scale=None, relu=True, stats=False, div=255.0, mul=2.0, sub=1.0, out=None, prepare=False):
     """conv7x7(mul * (image / div) - sub) * scale + bias [ReLU]; stride and channel counts come from ``ps``.
     Returns out, or (out, stats).  ``prepare=True`` (needs ``out``; stats = a caller-owned buffer or False): a launcher with ``.op``."""
-    _nchw(image, 'image')
+    _nchw(image, 'stem_conv: image')
     b, c, hh, ww = image.shape
     if c != ps.cin:
         raise _lib.RpeError(f'stem_conv: image must have {ps.cin} channels')
     st_ = ps.stride
     if out is None:
         out = torch.empty(b, ps.cout, hh // st_, ww // st_, dtype=torch.float32, device=image.device)
-    elif tuple(_nchw(out, 'out').shape) != (b, ps.cout, hh // st_, ww // st_):
+    elif tuple(_nchw(out, 'stem_conv: out').shape) != (b, ps.cout, hh // st_, ww // st_):
         raise _lib.RpeError('stem_conv: out has the wrong shape')
     if isinstance(stats, torch.Tensor):             # a caller-owned (batch slice of a) statistics buffer
-        st = stats
-        if not (st.is_cuda and st.dtype == torch.float32 and st.is_contiguous() and tuple(st.shape) == (b, ps.cout, lib().rpe_stem_tiles(hh, ww, st_), 3)):
-            raise _lib.RpeError('stem_conv: stats buffer has the wrong shape')
-        stats = True
+        st, stats = _f32(stats, 'stem_conv: stats', (b, ps.cout, lib().rpe_stem_tiles(hh, ww, st_), 3)), True
     else:
         st = torch.empty(b, ps.cout, lib().rpe_stem_tiles(hh, ww, st_), 3, dtype=torch.float32, device=image.device) if stats else None
     return _launch(_lib.OP_STEM_CONV, (ptr(image), b, c, hh, ww, st_, float(div), float(mul), float(sub), ptr(ps.packed), ps.cout, ptr(bias), ptr(scale),
@@ -1137,8 +1127,7 @@ def unet_heads(inp1, inp2, hidden, context, params2d, params3d, out_size):
             tuple(context.shape) != (b, 128, h8, w8):
         raise _lib.RpeError('unet_heads: inp1, inp2 must be (b,8,h/8,w/8), hidden and context (b,128,h/8,w/8)')
     for name, t, cin in (('params2d', params2d, 264), ('params3d', params3d, 272)):
-        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == lib().rpe_unet_params_floats(cin)):
-            raise _lib.RpeError(f'unet_heads: {name} must be the packed float32 parameter blob of TinyUNet({cin})')
+        _f32(t, f'unet_heads: {name} (the packed parameter blob of TinyUNet({cin}))', numel=lib().rpe_unet_params_floats(cin))
     nws = lib().rpe_unet_workspace_bytes(b, h8, w8)
     if nws == 0:
         raise _lib.RpeError('unet_heads: the 1/8 grid is too small for the valid convolutions (needs >= 44x44)')
@@ -1179,16 +1168,16 @@ def unet_train_forward(parts, params, norms, out_size, sigmoid=False):
     cin = sum(t.shape[1] for t in parts)
     L = lib()
     for k, t in enumerate(params):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
-                and t.numel() == L.rpe_unet_train_grad_offset(cin, k + 1) - L.rpe_unet_train_grad_offset(cin, k)):
-            raise _lib.RpeError(f'unet_train_forward: params[{k}] must be the contiguous float32 GPU tensor of TinyUNet({cin}) in the documented order')
+        _f32(t, f'unet_train_forward: params[{k}] (of TinyUNet({cin}), in the documented order)',
+             numel=L.rpe_unet_train_grad_offset(cin, k + 1) - L.rpe_unet_train_grad_offset(cin, k))
     mask = 0
     for k, (rm, rv, nbt, momentum, eps, training) in enumerate(norms):
         if rm is None or rv is None or momentum is None:
             raise _lib.RpeError('unet_train_forward: the norms must track running statistics with a fixed momentum')
-        if not all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in (rm, rv)) or \
-                (nbt is not None and not (nbt.is_cuda and nbt.dtype == torch.int64)):
-            raise _lib.RpeError('unet_train_forward: running statistics must be float32 GPU tensors (num_batches_tracked int64)')
+        for what, t in (('running_mean', rm), ('running_var', rv)):
+            _f32(t, f'unet_train_forward: norms[{k}] {what}')
+        if nbt is not None and not (nbt.is_cuda and nbt.dtype == torch.int64):
+            raise _lib.RpeError(f'unet_train_forward: norms[{k}] num_batches_tracked must be an int64 GPU tensor')
         mask |= int(bool(training)) << k
     H, W = out_size
     nws = L.rpe_unet_train_workspace_bytes(n, cin, h8, w8, H, W)

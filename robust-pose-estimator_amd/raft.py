@@ -27,6 +27,7 @@ Exact re-associations used (results identical up to float rounding):
 The RAFT architecture itself is restated from princeton-vl/RAFT (the reference's submodule is empty);
 see oracle/raft.py for the CPU restatement these kernels are tested against.
 """
+import operator
 from types import SimpleNamespace
 
 import torch
@@ -82,6 +83,17 @@ FRAME_OPLISTS_MAX_IMAGES = 4                                      # images per e
 ENC_STREAMS = True                                                 # RAFT.encode_both: the context encoder on the side stream beside the feature encoder
 ENC_STREAMS_MIN = 8                                                # ... for at least this many context images (below: the fork / join costs more than it hides)
 SIDE_STREAM_MAX = 8 * 5120                                     # queries per pass (batch * h/8 * w/8) up to which the side stream is used
+# Every constant above that selects a packing, a kernel, a tile class or a stream: _switches() is part of every key of what is built or
+# recorded under them, so a switch flipped on a live model (tests, bench.py's A/B runs) is honoured by all of it at the next pass.
+# (LOOP_OPLIST, LOOKUP_EVENT_SINK, FRAME_OPLISTS and FRAME_OPLISTS_MAX_IMAGES choose how launches are dispatched, not what is cached.)
+ROUTE_SWITCHES = ('WINOGRAD', 'WINO_2X4', 'S2_M96', 'S2_M96_MIN_WGS', 'CORR_BF16X3', 'CONV_BF16X3', 'X3_MIN_CIN', 'X3_GRU', 'SIDE_STREAM', 'SIDE_STREAM_MAX',
+                  'LOOKUP_FUSED', 'LOOKUP_FUSED_MAX_WGS', 'ENC_STREAMS', 'ENC_STREAMS_MIN')
+_switch_values = operator.itemgetter(*ROUTE_SWITCHES)
+
+
+def _switches():
+    """The current values of ROUTE_SWITCHES (read from the module at every call: they are plain attributes that callers assign)."""
+    return _switch_values(globals())
 
 
 def _norm(kind, ch):
@@ -155,29 +167,33 @@ def _bounded_put(cache, key, value, keep=2):
     cache[key] = value
 
 
+def _wkey(*tensors):
+    """Cache key of what is made from ``tensors`` (None = absent, and stays None in its place): an in-place update bumps the version,
+    .to() / .float() move the data, and a replaced Parameter is another tensor."""
+    return tuple(None if t is None else (t._version, t.data_ptr()) for t in tensors)
+
+
+def _cached(owner, attr, key, make, with_key=False):
+    """``make()`` kept on ``owner`` -- a module (as attribute ``attr``) or a workspace dict (as entry ``attr``) -- until ``key`` changes.
+    ``with_key``: returns (key, value), for a caller whose own cache depends on this one and therefore keys on its key."""
+    d = owner if isinstance(owner, dict) else owner.__dict__
+    cached = d.get(attr)
+    if cached is None or cached[0] != key:
+        d[attr] = cached = (key, make())
+    return cached if with_key else cached[1]
+
+
 def _bn_affine(conv, norm):
     """Eval-mode BatchNorm2d folded with the conv bias: y = conv_nobias(x) * scale + shift (cached per module)."""
-    key = tuple(t._version for t in (conv.bias, norm.weight, norm.bias, norm.running_mean, norm.running_var)) + (norm.weight.data_ptr(),)
-    cached = getattr(norm, '_rpe_affine', None)
-    if cached is None or cached[0] != key:
+    def fold():
         scale = (norm.weight / torch.sqrt(norm.running_var + norm.eps)).detach().float().contiguous()
-        shift = ((conv.bias - norm.running_mean) * scale + norm.bias).detach().float().contiguous()
-        norm._rpe_affine = cached = (key, scale, shift)
-    return cached[1], cached[2]
-
-
-def _cached(module, attr, key, make):
-    """``make()`` kept on ``module`` as ``attr`` until ``key`` (the versions and addresses of what it was made from) changes."""
-    cached = getattr(module, attr, None)
-    if cached is None or cached[0] != key:
-        cached = (key, make())
-        setattr(module, attr, cached)
-    return cached[1]
+        return scale, ((conv.bias - norm.running_mean) * scale + norm.bias).detach().float().contiguous()
+    return _cached(norm, '_rpe_affine', _wkey(conv.bias, norm.weight, norm.bias, norm.running_mean, norm.running_var), fold)
 
 
 def _packed(conv):
     """PackedConv of a module's weight (no bias), cached on the module until the weight changes."""
-    return _cached(conv, '_rpe_packed', (conv.weight._version, conv.weight.data_ptr()), lambda: ops.PackedConv(conv.weight, None))
+    return _cached(conv, '_rpe_packed', _wkey(conv.weight), lambda: ops.PackedConv(conv.weight, None))
 
 
 def _wino(conv, x):
@@ -188,7 +204,7 @@ def _wino(conv, x):
     if not ops.PackedWino.supported(conv.weight, x.shape[-2], x.shape[-1]) or conv.in_channels > 128 or not x.is_contiguous():
         return None
     kind = ops.PackedWino24 if WINO_2X4 and ops.PackedWino24.supported(conv.weight, x.shape[-2], x.shape[-1]) else ops.PackedWino
-    return _cached(conv, '_rpe_wino', (conv.weight._version, conv.weight.data_ptr(), kind), lambda: kind(conv.weight, None))
+    return _cached(conv, '_rpe_wino', (_wkey(conv.weight), kind), lambda: kind(conv.weight, None))
 
 
 def _fusable(conv, x):
@@ -246,20 +262,16 @@ def _encoder_conv(conv, x, mode=ops.CONV_LINEAR, affine=None, residual=None, pre
     return out, stats
 
 
-def _key_sources(module):
-    """(dict, name) of every parameter / buffer slot below ``module``: the slots are read afresh for every key (a Parameter object that is
-    REPLACED shows up, not only one that is updated in place), the walk over the module tree is done once."""
-    src = []
-    for m in module.modules():
-        src += [(m._parameters, n) for n in m._parameters] + [(m._buffers, n) for n in m._buffers]
-    return src
-
-
-def _tensor_key(sources):
-    """Versions and addresses of the tensors in the slots of _key_sources (in-place updates bump the version, .to() / .float() move the
-    data, an assignment puts another tensor into the slot)."""
-    ts = [d[n] for d, n in sources]
-    return tuple((t._version, t.data_ptr()) for t in ts if t is not None)
+def _recording(owner, root):
+    """The set-up of a module that records its small passes: (``owner``'s cache of recorded passes, the _wkey of every parameter and
+    buffer below ``root``).  The (dict, name) slots are collected once and read afresh for every key, so a Parameter object that is
+    REPLACED shows up, not only one that is updated in place."""
+    d = owner.__dict__
+    if d.get('_recorded') is None:
+        d['_recorded'] = _Recorded()
+    if '_key_tensors' not in d:
+        d['_key_tensors'] = [(slots, n) for m in root.modules() for slots in (m._parameters, m._buffers) for n in slots]
+    return d['_recorded'], _wkey(*[slots[n] for slots, n in d['_key_tensors']])
 
 
 def _overlap(tensors):
@@ -324,7 +336,7 @@ class BasicEncoder(nn.Module):
         """conv1 + norm1 + ReLU run on the RAW 0..255 image: the normalisation 2*(x/255)-1 happens while the kernel stages its
         input patch (rpe_stem_conv)."""
         w = self.conv1.weight
-        return _cached(self, '_stem_packed', (w._version, w.data_ptr()), lambda: ops.PackedStem(w))
+        return _cached(self, '_stem_packed', _wkey(w), lambda: ops.PackedStem(w))
 
     def _stem_many(self, images):
         """The stem over several image batches, written into batch slices of ONE output (no torch.cat of the inputs)."""
@@ -360,17 +372,15 @@ class BasicEncoder(nn.Module):
         b, _, hh, ww = x.shape
         half = m.out_channels // 2
         if ww % 4 == 0 and x.is_contiguous():
-            key = (m.weight._version, m.weight.data_ptr(), m.bias._version)
-            cached = getattr(self, '_final_packed', None)
-            if cached is None or cached[0] != key:
+            def pack():
                 w, bv = m.weight.detach(), m.bias.detach()
-                self._final_packed = cached = (key, ops.Conv1x1(w, bv), ops.Conv1x1(w[:half].contiguous(), bv[:half].contiguous()),
-                                               ops.Conv1x1(w[half:].contiguous(), bv[half:].contiguous()))
+                return ops.Conv1x1(w, bv), ops.Conv1x1(w[:half].contiguous(), bv[:half].contiguous()), ops.Conv1x1(w[half:].contiguous(), bv[half:].contiguous())
+            whole, lo, hi = _cached(self, '_final_packed', _wkey(m.weight, m.bias), pack)
             out = torch.empty(b, m.out_channels, hh, ww, device=x.device)
             if not split_act:
-                return cached[1](x, ops.CONV_LINEAR, out, x3=CONV_BF16X3)
-            cached[2](x, ops.CONV_TANH, out[:, :half])
-            cached[3](x, ops.CONV_RELU, out[:, half:], x3=CONV_BF16X3)
+                return whole(x, ops.CONV_LINEAR, out, x3=CONV_BF16X3)
+            lo(x, ops.CONV_TANH, out[:, :half])
+            hi(x, ops.CONV_RELU, out[:, half:], x3=CONV_BF16X3)
             return out
         y = ops.conv_direct(x, m.weight, m.bias, 1, 0)           # (maps whose rows are not whole 16-byte quads)
         if split_act:
@@ -394,18 +404,14 @@ class BasicEncoder(nn.Module):
         if FRAME_OPLISTS and raw255 and first.is_cuda and first.device.index == torch.cuda.current_device() and not torch.is_grad_enabled() \
                 and sum(im.shape[0] for im in images) <= FRAME_OPLISTS_MAX_IMAGES \
                 and all(im.is_contiguous() and im.dtype == torch.float32 and im.device == first.device for im in images) and not _overlap(images):
-            if getattr(self, '_recorded', None) is None:
-                self._recorded = _Recorded()
-            if '_key_tensors' not in self.__dict__:
-                self.__dict__['_key_tensors'] = _key_sources(self)
-            key = (tuple(tuple(im.shape) for im in images), first.device.index, ops.raw_stream(), split_act, WINOGRAD, WINO_2X4, S2_M96, S2_M96_MIN_WGS, CONV_BF16X3, self.training,
-                   _tensor_key(self.__dict__['_key_tensors']))
-            rec = self._recorded.get(key)
+            recorded, wkey = _recording(self, self)
+            key = (tuple(tuple(im.shape) for im in images), first.device.index, ops.raw_stream(), split_act, _switches(), self.training, wkey)
+            rec = recorded.get(key)
             if rec is not None:
                 out = torch.empty(rec.out_shape, device=first.device)
                 rec.replay({**{i: im for i, im in enumerate(images)}, 'out': out})
                 return out
-            if self._recorded.wanted(key):
+            if recorded.wanted(key):
                 rec = ops.Recorder()
                 with rec:
                     out = self._forward(x, raw255, split_act)
@@ -414,7 +420,7 @@ class BasicEncoder(nn.Module):
                         rec.complete = rec.complete and rec.bind(i, im) > 0
                     rec.complete = rec.complete and rec.bind('out', out) > 0
                     rec.out_shape = tuple(out.shape)
-                self._recorded.put(key, rec)
+                recorded.put(key, rec)
                 return out
         return self._forward(x, raw255, split_act)
 
@@ -497,29 +503,27 @@ class BasicUpdateBlock(nn.Module):
         self.flow_head = FlowHead(hidden_dim, hidden_dim=256)
         self.mask = nn.Sequential(nn.Conv2d(128, 256, 3, padding=1), nn.ReLU(inplace=True),
                                   nn.Conv2d(256, 64 * 9, 1, padding=0))
-        self._stacked = None
 
-    def gate_weights(self):
+    def gate_weights(self, with_key=False):
         """GRU conv weights re-arranged once (cached until a parameter changes):
           * convz|convr stacked on the output-channel axis (they read the same input),
           * input channels split into the loop-varying part [h | motion | flow] (256 ch) and the context part
             `inp` (128 ch, identical in every GRU iteration).
         Returns dict name -> (w_var, w_ctx, bias) for 'zr1', 'q1', 'zr2', 'q2'."""
-        g = self.gru
-        gp = [t for m in (g.convz1, g.convr1, g.convq1, g.convz2, g.convr2, g.convq2) for t in (m.weight, m.bias)]
-        key = tuple(p._version for p in gp) + tuple(p.data_ptr() for p in gp)
-        if self._stacked is None or self._stacked[0] != key:
-            c = self.hidden_dim
+        g, c = self.gru, self.hidden_dim
 
-            def split(w):                      # (out, 384, kh, kw) -> varying (out,256,..), context (out,128,..)
-                return torch.cat((w[:, :c], w[:, 2 * c:]), 1).detach().contiguous(), w[:, c:2 * c].detach().contiguous()
+        def split(w):                          # (out, 384, kh, kw) -> varying (out,256,..), context (out,128,..)
+            return torch.cat((w[:, :c], w[:, 2 * c:]), 1).detach().contiguous(), w[:, c:2 * c].detach().contiguous()
+
+        def stack():
             W = {}
             for name, convs in (('zr1', (g.convz1, g.convr1)), ('q1', (g.convq1,)), ('zr2', (g.convz2, g.convr2)), ('q2', (g.convq2,))):
                 w = torch.cat([m.weight for m in convs], 0)
                 bvec = torch.cat([m.bias for m in convs], 0).detach().contiguous()
                 W[name] = (*split(w), bvec)
-            self._stacked = (key, W)
-        return self._stacked[1]
+            return W
+        key = _wkey(*[t for m in (g.convz1, g.convr1, g.convq1, g.convz2, g.convr2, g.convq2) for t in (m.weight, m.bias)])
+        return _cached(self, '_stacked', key, stack, with_key)
 
     def context_terms(self, inp, out=None):
         """conv(inp; context channels) + bias of the four GRU convolutions: loop-invariant, computed once per pass.
@@ -534,65 +538,66 @@ class BasicUpdateBlock(nn.Module):
         pads = {'zr1': (0, 2), 'q1': (0, 2), 'zr2': (2, 0), 'q2': (2, 0)}
         return {k: ops.conv_direct(inp, W[k][1], W[k][2], 1, pads[k]) for k in W}
 
-    def packed_convs(self, width):
-        """Weights of the update block's convolutions in rpe_conv_fused's layout (cached until a parameter changes), or
-        None when the fused kernels do not apply (map width not a multiple of 4)."""
+    def packed_convs(self, width, with_key=False):
+        """Weights of the update block's convolutions in rpe_conv_fused's layout (cached until a parameter, the stacked gate weights or a
+        route switch changes), or None when the fused kernels do not apply (map width not a multiple of 4)."""
         if width % 4 != 0:
-            return None
+            return (None, None) if with_key else None
         e, fh = self.encoder, self.flow_head
         mods = (e.convc1, e.convc2, e.convf2, e.conv, fh.conv1)
-        keymods = mods + (e.convf1,)
+        gate_key, W = self.gate_weights(with_key=True)
         # (the convolutions' own weight / bias attributes: walking module.parameters() costs ~100 us a call, and this runs 26 times a frame)
-        ps = [t for m in keymods for t in (m.weight, m.bias) if t is not None]
-        key = tuple(p._version for p in ps) + tuple(p.data_ptr() for p in ps) + (id(self.gate_weights()), CONV_BF16X3, X3_GRU, WINO_2X4)
-        if getattr(self, '_packed', None) is None or self._packed[0] != key:
-            W = self.gate_weights()
-            P = {n: ops.PackedConv(m.weight, m.bias) for n, m in zip(('convc1', 'convc2', 'convf2', 'conv', 'fh1'), mods)}
-            # the four 3x3 layers also in Winograd form (rpe_conv_wino: 2.25x fewer matrix FLOPs); used on even maps
-            P['wino'] = {n: ops.PackedWino(m.weight, m.bias) for n, m in zip(('convc2', 'convf2', 'conv', 'fh1'), mods[1:])
-                         if ops.PackedWino.supported(m.weight, 2, 2)} if WINOGRAD else {}
-            # and as F(2x4,3x3) (rpe_conv_wino24: a quarter fewer products), used on maps with w % 4 == 0; not under the labelled variant
-            P['wino24'] = {n: ops.PackedWino24(m.weight, m.bias) for n, m in zip(('convc2', 'convf2', 'conv', 'fh1'), mods[1:])
-                           if ops.PackedWino24.supported(m.weight, 2, 4)} if (WINOGRAD and WINO_2X4 and not CONV_BF16X3) else {}
-            # the labelled bf16x3 variant's packings of the same layers (used on maps rpe_conv_wino_x3 accepts: even h, w % 4 == 0)
-            P['wino_x3'] = {n: ops.PackedWinoX3(m.weight, m.bias) for n, m in zip(('convc2', 'convf2', 'conv', 'fh1'), mods[1:])
-                            if n != 'convf2' and m.in_channels >= X3_MIN_CIN and ops.PackedWinoX3.supported(m.weight, 2, 4)} if (WINOGRAD and CONV_BF16X3) else {}
-            P['convf1'] = ops.PackedStem(e.convf1.weight)
-            P['convc1_1x1'] = ops.Conv1x1(e.convc1.weight, e.convc1.bias)
-            for n in ('zr1', 'q1', 'zr2', 'q2'):
-                # the loop-varying 256 channels: Winograd F(4,5) along the filter axis (rpe_conv_wino1d: 2.5x fewer matrix FLOPs), else the
-                # direct implicit GEMM; bias is part of the context term (context_terms)
-                # (under CONV_BF16X3 with X3_GRU: the labelled variant's packing -- rpe_conv_wino1d_x3; packed_convs only runs for widths it accepts)
-                P[n] = (ops.PackedWino1dX3 if CONV_BF16X3 and X3_GRU and ops.PackedWino1dX3.supported(W[n][0], 4) else ops.PackedWino1d)(W[n][0]) if WINOGRAD \
-                    else ops.PackedConv(W[n][0])
-                P['ctx_' + n] = (ops.PackedWino1d if WINOGRAD else ops.PackedConv)(W[n][1], W[n][2])
-            scratch = {}
+        key = (_wkey(*[t for m in mods + (e.convf1,) for t in (m.weight, m.bias)]), gate_key, _switches())
+        return _cached(self, '_packed', key, lambda: self._pack_convs(mods, W), with_key)
 
-            def buf(name, like, c):                            # scratch for intermediate activations, one set per workspace (``like`` is one of
-                k = (name, like.data_ptr(), like.shape[0], c, like.shape[2], like.shape[3], like.device)   # RAFT._workspace's buffers)
-                if k not in scratch:
-                    _bounded_put(scratch, k, torch.empty(like.shape[0], c, like.shape[2], like.shape[3], device=like.device), keep=12)
-                return scratch[k]
-            P['cor_buf'] = lambda like: buf('cor', like, 256)
-            P['fh_buf'] = lambda like: buf('fh', like, 256)
-            P['flo_buf'] = lambda like: buf('flo', like, 128)
-            self._packed = (key, P)
-        return self._packed[1]
+    def _pack_convs(self, mods, W):
+        """packed_convs' dict for the layers ``mods`` and the stacked gate weights ``W``, under the current route switches."""
+        e = self.encoder
+        P = {n: ops.PackedConv(m.weight, m.bias) for n, m in zip(('convc1', 'convc2', 'convf2', 'conv', 'fh1'), mods)}
+        # the four 3x3 layers also in Winograd form (rpe_conv_wino: 2.25x fewer matrix FLOPs); used on even maps
+        P['wino'] = {n: ops.PackedWino(m.weight, m.bias) for n, m in zip(('convc2', 'convf2', 'conv', 'fh1'), mods[1:])
+                     if ops.PackedWino.supported(m.weight, 2, 2)} if WINOGRAD else {}
+        # and as F(2x4,3x3) (rpe_conv_wino24: a quarter fewer products), used on maps with w % 4 == 0; not under the labelled variant
+        P['wino24'] = {n: ops.PackedWino24(m.weight, m.bias) for n, m in zip(('convc2', 'convf2', 'conv', 'fh1'), mods[1:])
+                       if ops.PackedWino24.supported(m.weight, 2, 4)} if (WINOGRAD and WINO_2X4 and not CONV_BF16X3) else {}
+        # the labelled bf16x3 variant's packings of the same layers (used on maps rpe_conv_wino_x3 accepts: even h, w % 4 == 0)
+        P['wino_x3'] = {n: ops.PackedWinoX3(m.weight, m.bias) for n, m in zip(('convc2', 'convf2', 'conv', 'fh1'), mods[1:])
+                        if n != 'convf2' and m.in_channels >= X3_MIN_CIN and ops.PackedWinoX3.supported(m.weight, 2, 4)} if (WINOGRAD and CONV_BF16X3) else {}
+        P['convf1'] = ops.PackedStem(e.convf1.weight)
+        P['convc1_1x1'] = ops.Conv1x1(e.convc1.weight, e.convc1.bias)
+        for n in ('zr1', 'q1', 'zr2', 'q2'):
+            # the loop-varying 256 channels: Winograd F(4,5) along the filter axis (rpe_conv_wino1d: 2.5x fewer matrix FLOPs), else the
+            # direct implicit GEMM; bias is part of the context term (context_terms)
+            # (under CONV_BF16X3 with X3_GRU: the labelled variant's packing -- rpe_conv_wino1d_x3; packed_convs only runs for widths it accepts)
+            P[n] = (ops.PackedWino1dX3 if CONV_BF16X3 and X3_GRU and ops.PackedWino1dX3.supported(W[n][0], 4) else ops.PackedWino1d)(W[n][0]) if WINOGRAD \
+                else ops.PackedConv(W[n][0])
+            P['ctx_' + n] = (ops.PackedWino1d if WINOGRAD else ops.PackedConv)(W[n][1], W[n][2])
+        scratch = {}
 
-    def launchers(self, ws, pyr=None):
+        def buf(name, like, c):                            # scratch for intermediate activations, one set per workspace (``like`` is one of
+            k = (name, like.data_ptr(), like.shape[0], c, like.shape[2], like.shape[3], like.device)   # RAFT._workspace's buffers)
+            if k not in scratch:
+                _bounded_put(scratch, k, torch.empty(like.shape[0], c, like.shape[2], like.shape[3], device=like.device), keep=12)
+            return scratch[k]
+        P['cor_buf'] = lambda like: buf('cor', like, 256)
+        P['fh_buf'] = lambda like: buf('fh', like, 256)
+        P['flo_buf'] = lambda like: buf('flo', like, 128)
+        return P
+
+    def launchers(self, ws, pyr=None, with_key=False):
         """Prepared launchers of the fused route's update on workspace ``ws`` (RAFT._workspace), built once and cached in ``ws`` until the
         packed weights change (every iteration of every pass on the workspace reuses them): c1, c2, f1, f2, cv (the motion encoder's convc1,
         convc2, convf1, convf2, conv; flo = convf1's output) and gru (the four GRU convolutions, FlowHead.conv1 and the flow head's output
         layer, which updates ws['coords1'] in place and writes flow = coords1 - grid into ws['flow'] and behind the motion features of hx /
         rhx).  With the pyramid ``pyr`` (the launch list's route) also lookup on coords1 and lookup_c1: lookup -> convc1 -> ReLU as one
         launch where that pays (LOOKUP_FUSED), else None."""
-        hx, rhx, z_buf, cat_buf, corr, coords1, flow, ctx = (ws[k] for k in ('hx', 'rhx', 'z', 'cat', 'corr', 'coords1', 'flow', 'ctx'))
-        P = self.packed_convs(hx.shape[-1])
+        packed_key, P = self.packed_convs(ws['hx'].shape[-1], with_key=True)
         alt = isinstance(pyr, ops.AltCorr)                  # (alternate_corr: lookup into the cor buffer, then convc1 -- LOOKUP_FUSED does not apply)
-        key = (id(P), None if pyr is None else (pyr.buf.data_ptr(), LOOKUP_FUSED, LOOKUP_FUSED_MAX_WGS) + ((alt,) if alt else ()))
-        cached = ws.get('_launchers')
-        if cached is not None and cached[0] == key:
-            return cached[2]
+        key = (packed_key, None if pyr is None else (pyr.buf.data_ptr(), alt))
+        return _cached(ws, '_launchers', key, lambda: self._make_launchers(ws, P, pyr, alt), with_key)
+
+    def _make_launchers(self, ws, P, pyr, alt):
+        hx, rhx, z_buf, cat_buf, corr, coords1, flow, ctx = (ws[k] for k in ('hx', 'rhx', 'z', 'cat', 'corr', 'coords1', 'flow', 'ctx'))
         c = self.hidden_dim
         e, fh = self.encoder, self.flow_head
         cor, flo, fh_buf = P['cor_buf'](corr), P['flo_buf'](corr), P['fh_buf'](hx)
@@ -622,10 +627,9 @@ class BasicUpdateBlock(nn.Module):
             L.lookup, L.lookup_c1 = pyr.lookup(coords1, out=corr, prepare=True), None
             n_wgs = hx.shape[0] * -(-(hx.shape[2] * -(-hx.shape[3] // 8)) // 8)
             if not alt and LOOKUP_FUSED and not CONV_BF16X3 and n_wgs <= LOOKUP_FUSED_MAX_WGS and ops.PackedLookupConv.supported(pyr.levels, pyr.radius, pyr.w8):
-                if 'convc1_lookup' not in P:
-                    P['convc1_lookup'] = ops.PackedLookupConv(e.convc1.weight, e.convc1.bias)
-                L.lookup_c1 = pyr.lookup_conv1x1(coords1, P['convc1_lookup'], cor, relu=True, prepare=True)
-        ws['_launchers'] = (key, P, L)                      # (holding P: no other dict can take its id while the entry lives)
+                # (convc1 in the fused kernel's layout: made when a pass first takes this route, kept while convc1 stays as it is)
+                pl = _cached(self, '_lookup_packed', _wkey(e.convc1.weight, e.convc1.bias), lambda: ops.PackedLookupConv(e.convc1.weight, e.convc1.bias))
+                L.lookup_c1 = pyr.lookup_conv1x1(coords1, pl, cor, relu=True, prepare=True)
         return L
 
     def step(self, ws, ctx, flow, coords1, h_buf, flow_branch_done=None):
@@ -673,13 +677,12 @@ class BasicUpdateBlock(nn.Module):
         hh, ww = net.shape[-2:]
         x3 = CONV_BF16X3 and c1.in_channels >= X3_MIN_CIN and ops.PackedWinoX3.supported(c1.weight, hh, ww)
         w24 = WINO_2X4 and not CONV_BF16X3 and ops.PackedWino24.supported(c1.weight, hh, ww)
-        key = tuple(p._version for p in mp) + tuple(p.data_ptr() for p in mp) + (x3, w24)
-        cached = getattr(self, '_mask_packed', None)
-        if cached is None or cached[0] != key:
+
+        def pack():
             pw = (ops.PackedWinoX3 if x3 else ops.PackedWino24 if w24 else ops.PackedWino)(c1.weight, c1.bias) if WINOGRAD and c1.weight.is_cuda else None
             w2, b2 = (0.25 * c2.weight).detach(), (0.25 * c2.bias).detach()
-            self._mask_packed = cached = (key, pw, w2, b2, ops.Conv1x1(w2, b2) if c2.weight.is_cuda else None)
-        _, pw, w2, b2, p2 = cached
+            return pw, w2, b2, ops.Conv1x1(w2, b2) if c2.weight.is_cuda else None
+        pw, w2, b2, p2 = _cached(self, '_mask_packed', (_wkey(*mp), x3, w24, _switches()), pack)
         if pw is not None and not torch.is_grad_enabled() and hh % 2 == 0 and ww % 2 == 0:      # (net may be a channel slice: hx[:, :128])
             t = ops.conv_wino(net, pw, ops.CONV_RELU, torch.empty(net.shape[0], c1.out_channels, hh, ww, device=net.device))
         else:
@@ -777,11 +780,11 @@ class RAFT(nn.Module):
         per (weights, pyramid, workspace, iters, streams) and replayed by one rpe_run_ops call per pass.  Cells 0 / 1: the fork / join
         events; cells 2 + 2k, 3 + 2k: timing events around iteration k's lookup (LOOKUP_EVENT_SINK; empty = skipped).
         Returns (list, marks) with marks[k] = first op of iteration k, marks[iters] = the end."""
-        L = self.update_block.launchers(ws, pyr)
-        key = (id(L), iters, None if side is None else side[0].cuda_stream)
-        cached = ws.get('_program')
-        if cached is not None and cached[0] == key:
-            return cached[1], cached[2]
+        launchers_key, L = self.update_block.launchers(ws, pyr, with_key=True)
+        key = (launchers_key, iters, None if side is None else side[0].cuda_stream)
+        return _cached(ws, '_program', key, lambda: self._make_loop_program(L, iters, side))
+
+    def _make_loop_program(self, L, iters, side):
         lk, c1 = (L.lookup, L.c1) if L.lookup_c1 is None else (L.lookup_c1, None)
         prog = ops.OpList(n_cells=2 + 2 * iters)
         if side is not None:
@@ -805,9 +808,8 @@ class RAFT(nn.Module):
             for launch in L.gru:
                 prog.add(launch)
         marks.append(prog.mark())
-        prog.keep = (L, side)                                 # (holding L: no other launcher set can take its id while the program lives)
+        prog.keep = side                                      # (the fork / join events of cells 0 / 1)
         prog.armed = False
-        ws['_program'] = (key, prog, marks)
         return prog, marks
 
     @torch.no_grad()
@@ -867,12 +869,18 @@ class RAFT(nn.Module):
             ops.copy_planes(ws['zero2'], rhx[:, 2 * c - 2:])
         return ctx
 
+    def _prediction(self, flow, hx, upsample):
+        """What forward() returns for the 1/8 ``flow``: mask head on the hidden state + convex x8 up-sampling, or a copy of the flow."""
+        if upsample:
+            return ops.upsample_convex(flow, self.update_block.up_mask(hx[:, :self.hidden_dim]))
+        return ops.copy_planes(flow, torch.empty_like(flow))
+
     def _finish(self, ws, upsample, ret_lowres=False):
         """Behind the loop of the fused route: the returned prediction (mask head + convex x8 up-sampling, or a copy of the 1/8 flow), the
         returned hidden state and (``ret_lowres``) a copy of the last 1/8 flow, all fresh tensors (the last one None when not asked for)."""
         c = self.hidden_dim
         hx, flow = ws['hx'], ws['flow']
-        pred = ops.upsample_convex(flow, self.update_block.up_mask(hx[:, :c])) if upsample else ops.copy_planes(flow, torch.empty_like(flow))
+        pred = self._prediction(flow, hx, upsample)
         h_buf = ops.copy_planes(hx[:, :c], torch.empty(hx.shape[0], c, hx.shape[2], hx.shape[3], device=hx.device))
         low = ops.copy_planes(flow, torch.empty_like(flow)) if ret_lowres else None
         return pred, h_buf, low
@@ -898,25 +906,22 @@ class RAFT(nn.Module):
         dev = fmap1.device
         c = self.hidden_dim
         ts = (fmap1, fmap2, cnet) + (() if flow_init is None else (flow_init,))
-        if not all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == dev for t in ts) or _overlap(ts) \
+        if not all(ops._is_f32(t) and t.device == dev for t in ts) or _overlap(ts) \
                 or tuple(cnet.shape) != (N, 2 * c, h8, w8) or dev.index != torch.cuda.current_device() \
                 or (flow_init is not None and tuple(flow_init.shape) != (N, 2, h8, w8)):
             return None                                               # (the call-by-call route raises what needs raising)
-        if getattr(self, '_recorded', None) is None:
-            self._recorded = _Recorded()
-        if '_key_tensors' not in self.__dict__:
-            self.__dict__['_key_tensors'] = _key_sources(self.update_block)
+        recorded, wkey = _recording(self, self.update_block)
         pyr = self._pyramid(N, h8, w8, dev)
         ws = self._workspace(N, h8, w8, dev)
-        key = (N, h8, w8, dev.index, ops.raw_stream(), iters, upsample, self.mixed_precision, self.alternate_corr, WINOGRAD, WINO_2X4, CORR_BF16X3, CONV_BF16X3, X3_GRU, SIDE_STREAM,
-               pyr.buf.data_ptr(), ws['hx'].data_ptr(), _tensor_key(self.__dict__['_key_tensors']))
+        key = (N, h8, w8, dev.index, ops.raw_stream(), iters, upsample, self.mixed_precision, self.alternate_corr, _switches(),
+               pyr.buf.data_ptr(), ws['hx'].data_ptr(), wkey)
         if flow_init is not None or ret_lowres:                       # (a cold pass keeps the key it always had)
             key += ('warm' if flow_init is not None else 'cold', ret_lowres)
         ins = {'f1': fmap1, 'f2': fmap2, 'cnet': cnet}
         if flow_init is not None:
             ins['finit'] = flow_init
         side = self._side_stream(dev) if SIDE_STREAM and N * h8 * w8 <= SIDE_STREAM_MAX else None
-        entry = self._recorded.get(key)
+        entry = recorded.get(key)
         if entry is not None:
             pre, post = entry.pre, entry
             pre.replay(ins)
@@ -928,7 +933,7 @@ class RAFT(nn.Module):
                 outs['low'] = low = torch.empty(N, 2, h8, w8, device=dev)
             post.replay(outs)
             return ([pred], h_buf, cnet[:, c:], low) if ret_lowres else ([pred], h_buf, cnet[:, c:])
-        if not self._recorded.wanted(key):
+        if not recorded.wanted(key):
             return None
         prog, _, streams = self._run_loop(pyr, ws, iters, side)      # (built outside the recordings: its launchers must hold the real entry points)
         pre = ops.Recorder()
@@ -944,7 +949,7 @@ class RAFT(nn.Module):
             pre.complete = post.complete = ok
         post.complete = post.complete and pre.complete
         post.pre, post.pred_shape = pre, tuple(pred.shape)
-        self._recorded.put(key, post)
+        recorded.put(key, post)
         return ([pred], h_buf, cnet[:, c:], low) if ret_lowres else ([pred], h_buf, cnet[:, c:])
 
     @torch.no_grad()
@@ -1005,10 +1010,8 @@ class RAFT(nn.Module):
             for itr in range(iters if all_flows else 0):
                 prog.run(streams, marks[itr], marks[itr + 1])
                 if itr < iters - 1:
-                    flow_predictions.append(ops.upsample_convex(flow, self.update_block.up_mask(hx[:, :c])) if upsample
-                                            else ops.copy_planes(flow, torch.empty_like(flow)))
-            flow_predictions.append(ops.upsample_convex(flow, self.update_block.up_mask(hx[:, :c])) if upsample
-                                    else ops.copy_planes(flow, torch.empty_like(flow)))
+                    flow_predictions.append(self._prediction(flow, hx, upsample))
+            flow_predictions.append(self._prediction(flow, hx, upsample))
             iters = 0                                             # (the launch-by-launch loop below is the other route)
         for itr in range(iters):
             done = None
@@ -1027,10 +1030,7 @@ class RAFT(nn.Module):
             coords1 = ub.step(ws, ctx, flow, coords1, h_buf, flow_branch_done=done)
             if all_flows or itr == iters - 1:
                 lowres = flow if fused else coords1 - coords0
-                if upsample:
-                    flow_predictions.append(ops.upsample_convex(lowres, self.update_block.up_mask(hx[:, :c])))
-                else:
-                    flow_predictions.append(ops.copy_planes(lowres, torch.empty_like(lowres)) if fused else lowres)
+                flow_predictions.append(self._prediction(lowres, hx, upsample) if upsample or fused else lowres)
         ops.copy_planes(hx[:, :c], h_buf)
         if ret_lowres:
             return flow_predictions, h_buf, inp, ops.copy_planes(flow, torch.empty_like(flow)) if fused else coords1 - coords0
