@@ -59,7 +59,10 @@ const char *rpe_version(void);
  *   and RPE_OP_FLOW_SEED (warm start of the update loop), rpe_ingest_stereo (the one-call input side) and rpe_pose_quality /
  *   rpe_pose_quality_workspace_bytes (the solve-quality report), and rpe_conv_fused_m96 with RPE_OP_CONV_FUSED_M96 (the 96-row tile class
  *   of the stride-2 3x3 layers), and rpe_corr_alt_bytes / rpe_corr_alt_prepare / rpe_corr_alt_lookup with RPE_OP_CORR_ALT_PREPARE /
- *   RPE_OP_CORR_ALT_LOOKUP (correlation without the all-pairs volume); the next RPE_ABI_MINOR bump counts them and rpe_conv_wino24*. */
+ *   RPE_OP_CORR_ALT_LOOKUP (correlation without the all-pairs volume), and the entry points of the update loop on zero-padded maps:
+ *   rpe_conv_wino_v, rpe_conv_wino24_v, rpe_conv_wino1d_v, rpe_conv1x1_v (struct rpe_conv_desc_v), rpe_stem_conv_v, rpe_conv3x3_to2_flow_v,
+ *   rpe_corr_lookup_ex, rpe_corr_alt_lookup_ex, rpe_upsample_convex_ex, rpe_copy_rect with RPE_OP_* kinds 22-31; the next RPE_ABI_MINOR bump
+ *   counts them and rpe_conv_wino24*. */
 #define RPE_ABI_VERSION 5
 #define RPE_ABI_MINOR 4
 int rpe_abi_minor(void);
@@ -273,6 +276,12 @@ int rpe_corr_build_ex(const float *fmap1, const float *fmap2, int b, int c, int 
  * window).  radius must be 4, levels <= 4. */
 int rpe_corr_lookup(const void *pyramid, const float *coords, int b, int h8, int w8, int levels, int radius,
                     float *out, void *stream);
+/* The same lookup with coords and out living in LARGER maps: coords is the top-left h8 x w8 of (b, 2, map_h, map_w), out the top-left
+ * h8 x w8 of (b, levels*(2r+1)^2, map_h, map_w); nothing outside that rectangle is read or written, so a zero-filled out keeps its zero
+ * padding.  The pyramid, the taps and every value are those of rpe_corr_lookup on the true (h8, w8): bit-identical inside the rectangle.
+ * map_h < h8 or map_w < w8 -> RPE_E_BADARG.  (The update loop on maps padded to the tuned kernels' sizes, core/RAFT/core/raft.py's loop.) */
+int rpe_corr_lookup_ex(const void *pyramid, const float *coords, int b, int h8, int w8, int levels, int radius, int map_h, int map_w,
+                       float *out, void *stream);
 /* The lookup FUSED into the convolution that consumes it: out (b, 256, h8, w8) = act(convc1(lookup(coords))) without the 324-channel
  * tensor ever reaching memory -- BasicMotionEncoder.forward's first layer (upstream core/RAFT/core/update.py: cor = F.relu(self.convc1(corr)),
  * 1x1, 324 -> 256; the reference's call site is core/pose/pose_net.py:65).  A workgroup looks the four levels of 64 queries up into LDS
@@ -321,6 +330,9 @@ int rpe_corr_alt_prepare(const float *fmap1, const float *fmap2, int b, int c, i
  * and whichever batch it is part of.  radius must be 4. */
 int rpe_corr_alt_lookup(const void *scratch, const float *coords, int b, int c, int h8, int w8, int levels, int radius, float *out,
                         void *stream);
+/* rpe_corr_alt_lookup with coords and out in (map_h, map_w) maps, as rpe_corr_lookup_ex. */
+int rpe_corr_alt_lookup_ex(const void *scratch, const float *coords, int b, int c, int h8, int w8, int levels, int radius, int map_h, int map_w,
+                           float *out, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * RAFT update block, element-wise halves of SepConvGRU (core/RAFT/core/update.py) fused around the
@@ -388,6 +400,20 @@ int rpe_flow_seed(const float *flow_init, int b, int h, int w, float *coords_out
                   float *dst2, long long dst2_batch_stride, void *stream);
 /* flow (b,2,h8,w8), mask (b,576,h8,w8) raw logits already scaled by .25 -> out (b,2,8*h8,8*w8). */
 int rpe_upsample_convex(const float *flow, const float *mask, int b, int h8, int w8, float *out, void *stream);
+/* The same with flow (b,2,map_h,map_w) and mask (b,576,map_h,map_w) in larger maps whose top-left h8 x w8 is read (a zero padding beyond it
+ * is F.unfold's own zero border); out stays the true-size (b,2,8*h8,8*w8).  map_h < h8 or map_w < w8 -> RPE_E_BADARG. */
+int rpe_upsample_convex_ex(const float *flow, const float *mask, int b, int h8, int w8, int map_h, int map_w, float *out, void *stream);
+/* rpe_conv3x3_to2_flow on a zero-padded map whose real content is h_valid x w_valid: outside that extent coords_out is the pixel grid and
+ * the flow written to flow_out / dst1 / dst2 is exactly zero (not conv + bias); inside it the results are those of rpe_conv3x3_to2_flow,
+ * bit for bit.  h_valid > h or w_valid > w (or < 1) -> RPE_E_BADARG. */
+int rpe_conv3x3_to2_flow_v(const float *x, const float *weight, const float *bias, int b, int c, int h, int w,
+                           const float *coords, float *coords_out, float *flow_out, float *dst1, long long dst1_batch_stride,
+                           float *dst2, long long dst2_batch_stride, int h_valid, int w_valid, void *stream);
+/* dst[:, :, :h, :w] = src[:, :, :h, :w] for (b, c) stacks of maps with their own row pitch, plane stride and batch stride (floats): the way
+ * into and out of a padded workspace (core/RAFT/core/raft.py: net, inp, flow_init in; the hidden state and the 1/8 flow out).  A pitch below
+ * w or a plane stride below (h - 1) pitch + w -> RPE_E_BADARG. */
+int rpe_copy_rect(const float *src, long long src_batch_stride, long long src_plane_stride, int src_pitch, float *dst,
+                  long long dst_batch_stride, long long dst_plane_stride, int dst_pitch, int b, int c, int h, int w, void *stream);
 
 /* ---- update-block convolutions (core/RAFT/core/update.py: BasicMotionEncoder convc1/convc2/convf2/conv, SepConvGRU
  * convz|convr/convq of both halves, FlowHead.conv1) as implicit GEMMs on the f32 matrix cores with their epilogues
@@ -431,6 +457,19 @@ typedef struct rpe_conv_desc {
     int stats_tiles;                                     /* records per (b, cout) plane of `stats`: 0 or rpe_conv_stats_tiles(cout,h,w,stride)
                                                           * (checked when non-zero; it selects nothing) */
 } rpe_conv_desc;
+/* A descriptor with a VALID EXTENT beside the map extent (rpe_conv_*_v): d.h x d.w is a zero-padded workspace map whose real content is the
+ * top-left h_valid x w_valid.  The kernels read the whole map (its padding is zero, i.e. the convolution's own border) and their epilogues
+ * store ZERO, not the computed value, at every output with y >= h_valid or x >= w_valid -- relu(bias), and for the GRU gates sigmoid(.) and
+ * tanh(.) of the bias and the context term, would otherwise leak into the padding the next layer reads.  Inside the extent the result is
+ * that of the plain entry point on the same map, bit for bit; h_valid == d.h and w_valid == d.w IS the plain entry point's launch.
+ * h_valid > d.h or w_valid > d.w (or < 1), or a NULL pointer -> RPE_E_BADARG.  Supported: what the update loop uses -- rpe_conv_wino_v /
+ * rpe_conv_wino24_v with the plain epilogue (bias, ReLU, out2; w % 4 == 0), rpe_conv_wino1d_v with every mode, rpe_conv1x1_v; anything
+ * else the plain entry point takes -> RPE_E_UNSUPPORTED.  (core/RAFT/core/update.py's layers at any img_size, infer_f2f.yaml:13.) */
+typedef struct rpe_conv_desc_v { rpe_conv_desc d; int h_valid, w_valid; } rpe_conv_desc_v;
+int rpe_conv_wino_v(const rpe_conv_desc_v *desc, void *stream);
+int rpe_conv_wino24_v(const rpe_conv_desc_v *desc, void *stream);
+int rpe_conv_wino1d_v(const rpe_conv_desc_v *desc, void *stream);
+int rpe_conv1x1_v(const rpe_conv_desc_v *desc, void *stream);
 /* number of floats of the packed form of a (cout, cin, kh, kw) weight tensor (0 on bad arguments) */
 size_t rpe_conv_packed_floats(int cout, int cin, int kh, int kw);
 /* weight (cout, cin, kh, kw) contiguous -> packed (tap-major 16-channel steps, output channels padded to 128) */
@@ -584,6 +623,16 @@ int rpe_instnorm_finalize(const float *partials, int tiles, int b, int c, int hw
 #define RPE_OP_CONV_FUSED_M96 19   /*       const rpe_conv_desc *  -> rpe_conv_fused_m96   */
 #define RPE_OP_CORR_ALT_PREPARE 20 /*       const rpe_corr_alt_prepare_args *              */
 #define RPE_OP_CORR_ALT_LOOKUP 21  /*       const rpe_corr_alt_lookup_args *               */
+#define RPE_OP_CONV_WINO_V 22      /*       const rpe_conv_desc_v * -> rpe_conv_wino_v     */
+#define RPE_OP_CONV_WINO24_V 23    /*       const rpe_conv_desc_v * -> rpe_conv_wino24_v   */
+#define RPE_OP_CONV_WINO1D_V 24    /*       const rpe_conv_desc_v * -> rpe_conv_wino1d_v   */
+#define RPE_OP_CONV1X1_V 25        /*       const rpe_conv_desc_v * -> rpe_conv1x1_v       */
+#define RPE_OP_STEM_CONV_V 26      /*       const rpe_stem_conv_v_args *                   */
+#define RPE_OP_FLOW_UPDATE_V 27    /*       const rpe_flow_update_v_args * -> rpe_conv3x3_to2_flow_v */
+#define RPE_OP_CORR_LOOKUP_EX 28   /*       const rpe_corr_lookup_ex_args *                */
+#define RPE_OP_CORR_ALT_LOOKUP_EX 29 /*     const rpe_corr_alt_lookup_ex_args *            */
+#define RPE_OP_UPSAMPLE_CONVEX_EX 30 /*     const rpe_upsample_convex_ex_args *            */
+#define RPE_OP_COPY_RECT 31        /*       const rpe_copy_rect_args *                     */
 #define RPE_OP_EVENT_RECORD 32     /*       void *const * (address of a hipEvent_t handle; NULL handle = no-op) */
 #define RPE_OP_STREAM_WAIT 33      /*       void *const * (the same)                       */
 typedef struct rpe_op {
@@ -616,6 +665,23 @@ typedef struct rpe_instnorm_apply_args {
     const float *x, *partials; int tiles, b, c, hw; float eps; int relu; const float *residual, *residual_mean_inv; float *out;
 } rpe_instnorm_apply_args;
 typedef struct rpe_upsample_convex_args { const float *flow, *mask; int b, h8, w8; float *out; } rpe_upsample_convex_args;
+typedef struct rpe_corr_lookup_ex_args { const void *pyramid; const float *coords; int b, h8, w8, levels, radius, map_h, map_w; float *out; } rpe_corr_lookup_ex_args;
+typedef struct rpe_corr_alt_lookup_ex_args {
+    const void *scratch; const float *coords; int b, c, h8, w8, levels, radius, map_h, map_w; float *out;
+} rpe_corr_alt_lookup_ex_args;
+typedef struct rpe_stem_conv_v_args {
+    const float *image; int b, cin, h, w, stride; float div, mul, sub; const float *packed; int cout; const float *bias, *scale; int relu;
+    float *out, *stats; int h_valid, w_valid;
+} rpe_stem_conv_v_args;
+typedef struct rpe_flow_update_v_args {
+    const float *x, *weight, *bias; int b, c, h, w; const float *coords; float *coords_out, *flow_out, *dst1; long long dst1_batch_stride;
+    float *dst2; long long dst2_batch_stride; int h_valid, w_valid;
+} rpe_flow_update_v_args;
+typedef struct rpe_upsample_convex_ex_args { const float *flow, *mask; int b, h8, w8, map_h, map_w; float *out; } rpe_upsample_convex_ex_args;
+typedef struct rpe_copy_rect_args {
+    const float *src; long long src_batch_stride, src_plane_stride; int src_pitch; float *dst; long long dst_batch_stride, dst_plane_stride;
+    int dst_pitch, b, c, h, w;
+} rpe_copy_rect_args;
 /* streams: n_streams hipStream_t handles (NULL = the default stream).  failed_op may be NULL. */
 int rpe_run_ops(const rpe_op *ops, int n_ops, void *const *streams, int n_streams, int *failed_op);
 
@@ -678,6 +744,11 @@ int rpe_stem_pack(const float *weight, int cout, int cin, float *packed, void *s
 int rpe_stem_conv(const float *image, int b, int cin, int h, int w, int stride, float div, float mul, float sub,
                   const float *packed, int cout, const float *bias, const float *scale, int relu, float *out,
                   float *stats, void *stream);
+/* rpe_stem_conv with a valid extent of the OUTPUT map (cin = 2, stride 1, no stats: convf1 on a zero-padded flow map): outputs with
+ * y >= h_valid or x >= w_valid are stored as zero, not relu(bias); inside, rpe_stem_conv's bits.  An extent beyond the map -> RPE_E_BADARG. */
+int rpe_stem_conv_v(const float *image, int b, int cin, int h, int w, int stride, float div, float mul, float sub,
+                    const float *packed, int cout, const float *bias, const float *scale, int relu, float *out,
+                    float *stats, int h_valid, int w_valid, void *stream);
 
 /* ---- input side: what the reference's datasets do on the CPU before a frame reaches
  * PoseEstimator (dataset/stereo_dataset.py:12-16,35-40, dataset/video_dataset.py:59-63, dataset/transforms.py:20-39).

@@ -31,6 +31,17 @@ class ConvDesc(_c.Structure):
                 ('gate_channels', _i), ('stride', _i), ('stats_tiles', _i)]
 
 
+class ConvDescV(ConvDesc):
+    """struct rpe_conv_desc_v (include/rpe.h): an rpe_conv_desc, then the valid extent of its map.  A subclass, so the code that fills a
+    ConvDesc fills this one too and a pointer to it passes where the binding declares a descriptor pointer (the rpe_conv_*_v kinds)."""
+    _fields_ = [('h_valid', _i), ('w_valid', _i)]
+
+
+def struct_fields(st):
+    """Every (name, type) of a ctypes structure, inherited ones first (``_fields_`` of a subclass names its own only)."""
+    return [f for cls in reversed(type(st).__mro__) for f in cls.__dict__.get('_fields_', ())]
+
+
 class Op(_c.Structure):
     """struct rpe_op (include/rpe.h, prepared launch lists)."""
     _fields_ = [('kind', _i), ('stream', _i), ('args', _vp)]
@@ -92,11 +103,39 @@ class FlowSeedArgs(_c.Structure):
                 ('dst2', _vp), ('dst2_batch_stride', _ll)]
 
 
+class CorrLookupExArgs(_c.Structure):
+    _fields_ = [('pyramid', _vp), ('coords', _vp), ('b', _i), ('h8', _i), ('w8', _i), ('levels', _i), ('radius', _i), ('map_h', _i), ('map_w', _i), ('out', _vp)]
+
+
+class CorrAltLookupExArgs(_c.Structure):
+    _fields_ = [('scratch', _vp), ('coords', _vp), ('b', _i), ('c', _i), ('h8', _i), ('w8', _i), ('levels', _i), ('radius', _i), ('map_h', _i), ('map_w', _i),
+                ('out', _vp)]
+
+
+class StemConvVArgs(_c.Structure):
+    _fields_ = StemConvArgs._fields_ + [('h_valid', _i), ('w_valid', _i)]
+
+
+class FlowUpdateVArgs(_c.Structure):
+    _fields_ = FlowUpdateArgs._fields_ + [('h_valid', _i), ('w_valid', _i)]
+
+
+class UpsampleConvexExArgs(_c.Structure):
+    _fields_ = [('flow', _vp), ('mask', _vp), ('b', _i), ('h8', _i), ('w8', _i), ('map_h', _i), ('map_w', _i), ('out', _vp)]
+
+
+class CopyRectArgs(_c.Structure):
+    _fields_ = [('src', _vp), ('src_batch_stride', _ll), ('src_plane_stride', _ll), ('src_pitch', _i), ('dst', _vp), ('dst_batch_stride', _ll),
+                ('dst_plane_stride', _ll), ('dst_pitch', _i), ('b', _i), ('c', _i), ('h', _i), ('w', _i)]
+
+
 # RPE_OP_* of include/rpe.h
 OP_CONV_FUSED, OP_CONV_WINO, OP_CONV_WINO1D, OP_CONV1X1, OP_CONV_WINO_X3, OP_CONV_WINO1D_X3, OP_CONV1X1_X3 = 1, 2, 3, 4, 5, 6, 7
 OP_CORR_LOOKUP, OP_STEM_CONV, OP_FLOW_UPDATE, OP_COPY_PLANES, OP_INSTNORM_FINALIZE, OP_INSTNORM_APPLY, OP_UPSAMPLE_CONVEX, OP_CORR_BUILD = 8, 9, 10, 11, 12, 13, 14, 15
 OP_LOOKUP_CONV1X1, OP_CONV_WINO24, OP_FLOW_SEED, OP_CONV_FUSED_M96 = 16, 17, 18, 19
 OP_CORR_ALT_PREPARE, OP_CORR_ALT_LOOKUP = 20, 21
+OP_CONV_WINO_V, OP_CONV_WINO24_V, OP_CONV_WINO1D_V, OP_CONV1X1_V, OP_STEM_CONV_V, OP_FLOW_UPDATE_V = 22, 23, 24, 25, 26, 27
+OP_CORR_LOOKUP_EX, OP_CORR_ALT_LOOKUP_EX, OP_UPSAMPLE_CONVEX_EX, OP_COPY_RECT = 28, 29, 30, 31
 OP_EVENT_RECORD, OP_STREAM_WAIT = 32, 33
 # kind -> (entry point, argument struct) of every op a launch list carries (csrc/oplist.hip's run_one).  An entry point with an argument
 # struct takes its fields in order, then the stream; the rpe_conv_desc kinds take the descriptor by pointer, then the stream.
@@ -109,12 +148,19 @@ LIST_OPS = {OP_CONV_FUSED: ('rpe_conv_fused', ConvDesc), OP_CONV_WINO: ('rpe_con
             OP_UPSAMPLE_CONVEX: ('rpe_upsample_convex', UpsampleConvexArgs), OP_CORR_BUILD: ('rpe_corr_build_ex', CorrBuildArgs),
             OP_LOOKUP_CONV1X1: ('rpe_corr_lookup_conv1x1', LookupConv1x1Args), OP_CONV_WINO24: ('rpe_conv_wino24', ConvDesc),
             OP_FLOW_SEED: ('rpe_flow_seed', FlowSeedArgs), OP_CONV_FUSED_M96: ('rpe_conv_fused_m96', ConvDesc),
-            OP_CORR_ALT_PREPARE: ('rpe_corr_alt_prepare', CorrAltPrepareArgs), OP_CORR_ALT_LOOKUP: ('rpe_corr_alt_lookup', CorrAltLookupArgs)}
+            OP_CORR_ALT_PREPARE: ('rpe_corr_alt_prepare', CorrAltPrepareArgs), OP_CORR_ALT_LOOKUP: ('rpe_corr_alt_lookup', CorrAltLookupArgs),
+            # the update loop on zero-padded maps (RAFT's pad_maps): valid extents and pitches
+            # (the _v convolutions take a ConvDescV, passed as the ConvDesc it starts with)
+            OP_CONV_WINO_V: ('rpe_conv_wino_v', ConvDesc), OP_CONV_WINO24_V: ('rpe_conv_wino24_v', ConvDesc),
+            OP_CONV_WINO1D_V: ('rpe_conv_wino1d_v', ConvDesc), OP_CONV1X1_V: ('rpe_conv1x1_v', ConvDesc),
+            OP_STEM_CONV_V: ('rpe_stem_conv_v', StemConvVArgs), OP_FLOW_UPDATE_V: ('rpe_conv3x3_to2_flow_v', FlowUpdateVArgs),
+            OP_CORR_LOOKUP_EX: ('rpe_corr_lookup_ex', CorrLookupExArgs), OP_CORR_ALT_LOOKUP_EX: ('rpe_corr_alt_lookup_ex', CorrAltLookupExArgs),
+            OP_UPSAMPLE_CONVEX_EX: ('rpe_upsample_convex_ex', UpsampleConvexExArgs), OP_COPY_RECT: ('rpe_copy_rect', CopyRectArgs)}
 KIND_OF_ENTRY = {entry: kind for kind, (entry, _) in LIST_OPS.items()}
 
 ABI_MINOR = 3              # RPE_ABI_MINOR of the single-map surfel entry points (rpe_surfel_*)
 ABI_MINOR_MANY = 4         # RPE_ABI_MINOR of rpe_surfel_*_many and rpe_pose_gate_chain_rows: the newest additions this binding calls
-                           # (rpe_conv_wino24*, rpe_flow_forward_interpolate, rpe_flow_seed, rpe_ingest_stereo, rpe_conv_fused_m96 and rpe_corr_alt_* came later under the same minor:
+                           # (rpe_conv_wino24*, rpe_flow_forward_interpolate, rpe_flow_seed, rpe_ingest_stereo, rpe_conv_fused_m96, rpe_corr_alt_* and the padded loop's rpe_conv_*_v / rpe_*_ex / rpe_copy_rect came later under the same minor:
                            # loading binds every SIGNATURES entry, so a library without them fails there)
 SURFEL_MAX_MAPS = 64       # RPE_SURFEL_MAX_MAPS: maps per rpe_surfel_*_many call
 ABI_VERSION = 5            # RPE_ABI_VERSION of include/rpe.h these struct mirrors were written against

@@ -31,6 +31,7 @@ struct G1P {
     const float* bias;
     float* out; long long obs; float* out2; long long o2bs;
     int mode;
+    int W, Hv, Wv;                               // VALID instantiation: row length of the map and its valid extent
 };
 
 // two 1 KB chunks with their own per-lane offsets: global base + v_j + 1024 j -> LDS lds_addr + 1024 j + lane * 16 (the caller
@@ -57,7 +58,9 @@ __device__ __forceinline__ void store_sv(float* base, unsigned voff, float v) {
 // (by its workgroup count) never shows in the result (tests/test_gpu_conv.py::test_conv1x1_routes_agree_bitwise).
 __host__ __device__ __forceinline__ int g1_chan(int rho) { return (rho >> 1) + 8 * (rho & 1); }
 
-template <int MODE, bool OUT2>
+// VALID (rpe_conv1x1_v): pixels outside the valid extent Hv x Wv of the (h, W) map are stored as zero, not as act(bias) -- the map is a
+// zero-padded workspace and the 3x3 layer behind this one reads its padding as the convolution's zero border.
+template <int MODE, bool OUT2, bool VALID = false>
 __global__ __launch_bounds__(256, G1_OCC) void k_conv1x1(G1P P) {
     __shared__ __attribute__((aligned(16))) float As[3][G1_TILE];             // [k][co], as packed in global memory
     __shared__ __attribute__((aligned(16))) float Bs[3][G1_TILE];             // [k][pixel]
@@ -185,6 +188,7 @@ __global__ __launch_bounds__(256, G1_OCC) void k_conv1x1(G1P P) {
     for (int j = 0; j < 2; ++j) {
         const int px = px0 + wn * 64 + j * 32 + l31;
         const bool pok = px < hw;
+        const bool pvalid = !VALID || (px / P.W < P.Hv && px % P.W < P.Wv);
         const unsigned loff = ((unsigned)(4 * lh) * (unsigned)hw + (unsigned)px) * 4u;   // this lane's part: its row group of 4 and its pixel
 #pragma unroll
         for (int i = 0; i < 2; ++i)
@@ -194,6 +198,7 @@ __global__ __launch_bounds__(256, G1_OCC) void k_conv1x1(G1P P) {
                 float v = acc[i][j][r] + bsl[i * 32 + (r & 3) + 8 * (r >> 2)];
                 if (MODE == RPE_CONV_RELU) v = v < 0.0f ? 0.0f : v;           // NaN stays NaN, like torch.relu
                 else if (MODE == RPE_CONV_TANH) v = tanh_f(v);
+                if (VALID) v = pvalid ? v : 0.0f;
 #ifdef G1_NO_STORE
                 if (pok && row_u + 4 * lh < cout && v == 1234.5f) {
 #else
@@ -226,7 +231,7 @@ extern "C" int rpe_conv1x1_pack(const float* weight, int cout, int cin, float* p
     return launch_pack(k_conv1x1_pack, weight, packed, cout, cin, 1, (long long)rpe_conv1x1_packed_floats(cout, cin), stream, ceil_div(cin, G1_K));
 }
 
-extern "C" int rpe_conv1x1(const rpe_conv_desc* d, void* stream) {
+static int conv1x1_launch(const rpe_conv_desc* d, int hv, int wv, void* stream) {
     if (!conv_desc_present(d)) return RPE_E_BADARG;
     if (d->kh != 1 || d->kw != 1 || !stride_is_1(d)) return RPE_E_UNSUPPORTED;
     if (!conv_linear_or_relu(d) && d->mode != RPE_CONV_TANH) return RPE_E_UNSUPPORTED;
@@ -237,13 +242,23 @@ extern "C" int rpe_conv1x1(const rpe_conv_desc* d, void* stream) {
     if (hw * 16 * 4 + G1_BIAS >= (1ll << 32)) return RPE_E_UNSUPPORTED;                        // 32-bit byte offsets inside a 16-channel step
     G1P P;
     fill_common(P, d, round_up(d->cout, 128));
-    P.hw = (int)hw;
+    P.hw = (int)hw; P.W = d->w; P.Hv = hv; P.Wv = wv;
+    const bool valid = hv != d->h || wv != d->w;
     const dim3 grid(ceil_div(hw, G1_N) * (P.coP / 128), 1, d->b);
-#define G1_LAUNCH(M_) do { if (d->out2) hipLaunchKernelGGL((k_conv1x1<M_, true>), grid, dim3(256), 0, (hipStream_t)stream, P); \
+#define G1_LAUNCH(M_) do { if (valid && d->out2) hipLaunchKernelGGL((k_conv1x1<M_, true, true>), grid, dim3(256), 0, (hipStream_t)stream, P); \
+                           else if (valid) hipLaunchKernelGGL((k_conv1x1<M_, false, true>), grid, dim3(256), 0, (hipStream_t)stream, P); \
+                           else if (d->out2) hipLaunchKernelGGL((k_conv1x1<M_, true>), grid, dim3(256), 0, (hipStream_t)stream, P); \
                            else hipLaunchKernelGGL((k_conv1x1<M_, false>), grid, dim3(256), 0, (hipStream_t)stream, P); } while (0)
     if (d->mode == RPE_CONV_RELU) G1_LAUNCH(RPE_CONV_RELU);
     else if (d->mode == RPE_CONV_TANH) G1_LAUNCH(RPE_CONV_TANH);
     else G1_LAUNCH(RPE_CONV_LINEAR);
 #undef G1_LAUNCH
     return rpe_check_launch();
+}
+
+extern "C" int rpe_conv1x1(const rpe_conv_desc* d, void* stream) { return conv1x1_launch(d, d ? d->h : 0, d ? d->w : 0, stream); }
+
+extern "C" int rpe_conv1x1_v(const rpe_conv_desc_v* dv, void* stream) {
+    if (!dv || !conv_valid_extent_ok(dv)) return RPE_E_BADARG;
+    return conv1x1_launch(&dv->d, dv->h_valid, dv->w_valid, stream);
 }

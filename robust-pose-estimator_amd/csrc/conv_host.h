@@ -21,6 +21,10 @@ static inline bool conv_gate_args_ok(const rpe_conv_desc* d) {
     if (d->mode == RPE_CONV_GATE_ZR) return d->out2 && d->hidden && d->gate_channels > 0 && d->cout == 2 * d->gate_channels;
     return d->mode != RPE_CONV_GATE_H || (d->hidden && d->zgate);
 }
+// rpe_conv_*_v: the valid extent lies inside the map (equal to it = the plain entry point's launch)
+static inline bool conv_valid_extent_ok(const rpe_conv_desc_v* dv) {
+    return dv->h_valid > 0 && dv->w_valid > 0 && dv->h_valid <= dv->d.h && dv->w_valid <= dv->d.w;
+}
 static inline bool stride_is_1(const rpe_conv_desc* d) { return d->stride == 0 || d->stride == 1; }                                // 0 = unset
 static inline int round_up(int n, int tile) { return (n + tile - 1) / tile * tile; }
 

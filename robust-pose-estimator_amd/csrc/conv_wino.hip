@@ -49,6 +49,7 @@ struct WinoP {
     const float* scale; const float* res; long long rbs; float* stats; const float* pre;
     int co_base;                                  // first output channel of this launch (a trailing 32-channel tile is its own launch)
     int v4;                                       // W % 4 == 0 and out / out2 / residual 16-byte aligned: the epilogue moves 16 bytes per lane
+    int Hv, Wv;                                   // valid extent (VALID instantiation): outputs with y >= Hv or x >= Wv are stored as zero
 };
 
 // three 256-B chunks of gathered dwords: global base + v_j + 256 j  ->  LDS lds_addr + 256 j + lane * 4   (the caller folds the
@@ -84,7 +85,10 @@ extern "C" int rpe_debug_wino_timing(unsigned long long* out8) { return hipMemcp
 // (MI355X, batch 32): convc2 586 -> 570 us, encoder layer 1 / 2 1390 -> 1351 / 798 -> 772 us.  Needs W % 4 == 0 and 16-byte aligned
 // planes (quads are then wholly inside or wholly outside the map); other shapes keep the dword gather (RQ = false).  (Tried: the
 // same reads at 4-byte alignment without the shift -- correct, and 1.7x slower for the whole kernel: misaligned ds_read_b64.)
-template <int EPI, bool PRE, int CB, bool RQ>
+// VALID (rpe_conv_wino_v, plain epilogue with 16-byte stores only): the map is a zero-padded workspace whose real content is Hv x Wv; what the
+// kernel computes outside that extent (relu(bias), sums over the border) is replaced by zero in the store, so the padding stays the
+// convolution's own zero border for the next layer.  The loaders and the matrix phase are untouched.
+template <int EPI, bool PRE, int CB, bool RQ, bool VALID = false>
 __global__ __launch_bounds__(256, 2) void k_conv_wino(WinoP P) {
     constexpr bool HAS_AFFINE = EPI == 1 || EPI == 3, HAS_STATS = EPI == 2 || EPI == 3;
     constexpr int TCO = 32 * CB, UT_STEP = WK * TCO * 16;
@@ -540,6 +544,11 @@ __global__ __launch_bounds__(256, 2) void k_conv_wino(WinoP P) {
 #pragma unroll
                         for (int e = 0; e < 4; ++e) q[e] = q[e] < 0.0f ? 0.0f : q[e];
                     }
+                    if (VALID) {                                             // selects, not products: a NaN outside the extent leaves as zero
+                        const int ry = oy + (odd ? 1 : 0), rx = ox - (odd ? 2 : 0);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) q[e] = (ry < P.Hv && rx + e < P.Wv) ? q[e] : 0.0f;
+                    }
                     *(f32x4*)(ob + e4) = q;
                     if (ob2) *(f32x4*)(ob2 + e4) = q;
                 }
@@ -601,7 +610,7 @@ extern "C" int rpe_conv_wino_stats_tiles(int h, int w) {
     return (h > 0 && w > 0) ? 2 * ceil_div(w, 2 * WB_TX) * ceil_div(h, 2 * WB_TY) : 0;      // two records (tile halves) per 16x8 patch
 }
 
-extern "C" int rpe_conv_wino(const rpe_conv_desc* d, void* stream) {
+static int conv_wino_launch(const rpe_conv_desc* d, int hv, int wv, void* stream) {
     if (!conv_desc_present(d)) return RPE_E_BADARG;
     // tiles of 2 x 2 outputs: even maps (the only 3x3 Winograd kernel that takes w % 4 == 2)
     if (d->kh != 3 || d->kw != 3 || !stride_is_1(d) || (d->cin % WK) || (d->h & 1) || (d->w & 1)) return RPE_E_UNSUPPORTED;
@@ -621,7 +630,17 @@ extern "C" int rpe_conv_wino(const rpe_conv_desc* d, void* stream) {
     const bool quads = WINO_RAWQ && (d->w & 3) == 0 && d->w >= 4 && ((d->h * d->w) & 3) == 0 && aligned16(d->x, d->x_batch_stride);
     const int epi = wino_epilogue_class(d);
     const unsigned gx = ceil_div(d->w, 2 * WB_TX) * ceil_div(d->h, 2 * WB_TY);
+    const bool valid = hv != d->h || wv != d->w;               // a valid extent smaller than the map: the plain epilogue's 16-byte stores only
+    if (valid && (epi != 0 || !P.v4)) return RPE_E_UNSUPPORTED;
+    P.Hv = hv; P.Wv = wv;
     auto launch = [&](auto cb, int tiles) {
+        if (valid) {
+            constexpr int CB = decltype(cb)::value;
+            const dim3 grid(gx, tiles, d->b);
+            if (quads) hipLaunchKernelGGL((k_conv_wino<0, false, CB, true, true>), grid, dim3(256), 0, (hipStream_t)stream, P);
+            else hipLaunchKernelGGL((k_conv_wino<0, false, CB, false, true>), grid, dim3(256), 0, (hipStream_t)stream, P);
+            return;
+        }
         dispatch_epi_pre(epi, d->pre_norm != nullptr, [&](auto e, auto pre) {
             constexpr int E = decltype(e)::value, CB = decltype(cb)::value;
             constexpr bool PRE = decltype(pre)::value;
@@ -636,4 +655,11 @@ extern "C" int rpe_conv_wino(const rpe_conv_desc* d, void* stream) {
     if ((long long)gx * ceil_div(d->cout, WB_CO) * d->b < WINO_SMALL_WG) launch(std::integral_constant<int, 1>{}, ceil_div(d->cout, 32));
     else launch_tiles64(P, launch);
     return rpe_check_launch();
+}
+
+extern "C" int rpe_conv_wino(const rpe_conv_desc* d, void* stream) { return conv_wino_launch(d, d ? d->h : 0, d ? d->w : 0, stream); }
+
+extern "C" int rpe_conv_wino_v(const rpe_conv_desc_v* dv, void* stream) {
+    if (!dv || !conv_valid_extent_ok(dv)) return RPE_E_BADARG;
+    return conv_wino_launch(&dv->d, dv->h_valid, dv->w_valid, stream);
 }

@@ -36,13 +36,17 @@ struct W1P {
     float* out; long long obs; float* out2; long long o2bs;
     const float* hid; long long hbs; const float* z; long long zbs;
     int cgate, mode;
+    int Hv, Wv;                                  // valid extent (VALID instantiation): every epilogue stores zero at y >= Hv or x >= Wv
 };
 
 __device__ __forceinline__ int row_swap(int r) { return ((r >> 2) ^ (r >> 3)) & 1; }
 
 // CB = 16-channel blocks per wave: 2 -> 64 output channels per workgroup; 1 -> 32 (wave = 16 channels x 32 tiles): twice the
 // workgroups for launches that do not fill the chip (sequential tracking).  Same products and summation order: bit-identical outputs.
-template <bool VERT, int CB>
+// VALID (rpe_conv_wino1d_v): the map is a zero-padded workspace whose real content is Hv x Wv.  Zero inputs do not give zero gates --
+// sigmoid(bias + ctx), tanh(bias + ctx) -- so every epilogue SELECTS zero for the pixels outside the extent before it stores (z, r * h,
+// the new h, and the linear / ReLU outputs alike): the padding of (h | x) and (r*h | x) stays the convolution's own zero border.
+template <bool VERT, int CB, bool VALID = false>
 __global__ __launch_bounds__(256, 2) void k_conv_wino1d(W1P P) {
     constexpr int TCO = 32 * CB, UT_STEP = W1_K * TCO * W1_ROW;
     __shared__ __attribute__((aligned(16))) float Us[3][UT_STEP];             // [ci][co][8 positions], as packed in global memory
@@ -304,7 +308,12 @@ __global__ __launch_bounds__(256, 2) void k_conv_wino1d(W1P P) {
             const bool pok = FAST || ((oy < H) & (ox < W));
             const size_t pxo = (size_t)oy * W + ox;
             auto st4 = [&](float* p, size_t e, const float (&v)[4]) {
-                if (pok) *(f32x4*)(p + e) = (f32x4){v[0], v[1], v[2], v[3]};
+                f32x4 q4 = {v[0], v[1], v[2], v[3]};
+                if (VALID && !FAST) {                                             // (FAST: the patch lies inside the valid extent)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) q4[i] = (oy < P.Hv && ox + i < P.Wv) ? q4[i] : 0.0f;
+                }
+                if (pok) *(f32x4*)(p + e) = q4;
             };
 #pragma unroll
             for (int q = 0; q < RU; ++q) {
@@ -366,7 +375,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_wino1d(W1P P) {
     {
         typedef std::integral_constant<int, RPE_CONV_GATE_ZR> ZR; typedef std::integral_constant<int, RPE_CONV_GATE_H> GH; typedef std::integral_constant<int, -1> RT;
         typedef std::integral_constant<bool, true> Yes; typedef std::integral_constant<bool, false> No;
-        const bool inside = (y0 + 16 <= H) & (x0 + 16 <= W) & (co0 + TCO <= P.cout);
+        const bool inside = (y0 + 16 <= (VALID ? P.Hv : H)) & (x0 + 16 <= (VALID ? P.Wv : W)) & (co0 + TCO <= P.cout);
         if (mode == RPE_CONV_GATE_ZR) { if (inside && (cg % TCO) == 0) epilogue(ZR{}, Yes{}); else epilogue(ZR{}, No{}); }
         // (GATE_H in full launches keeps the masked shape: measured at batch 32, the q convolutions are 3-6 % SLOWER with the unmasked one
         // (272 vs 265 us, 245 vs 235) and 5 % faster at batch 2 -- with two workgroups per CU an epilogue that issues its 64 KB of loads
@@ -399,7 +408,7 @@ extern "C" int rpe_conv_wino1d_pack(const float* weight, int cout, int cin, floa
     return launch_pack(k_wino1d_pack, weight, packed, cout, cin, W1_K, (long long)rpe_conv_wino1d_packed_floats(cout, cin), stream, round_up(cout, W1_CO));
 }
 
-extern "C" int rpe_conv_wino1d(const rpe_conv_desc* d, void* stream) {
+static int conv_wino1d_launch(const rpe_conv_desc* d, int hv, int wv, void* stream) {
     if (!conv_desc_present(d)) return RPE_E_BADARG;
     const bool vert = d->kh == 5 && d->kw == 1, horiz = d->kh == 1 && d->kw == 5;
     if (!(vert || horiz) || !stride_is_1(d) || (d->cin % W1_K) || (d->w & 3)) return RPE_E_UNSUPPORTED;
@@ -412,6 +421,8 @@ extern "C" int rpe_conv_wino1d(const rpe_conv_desc* d, void* stream) {
     W1P P;
     fill_common(P, d, round_up(d->cout, W1_CO)); fill_gate(P, d);
     P.H = d->h; P.W = d->w; P.hid = d->hidden; P.hbs = d->hidden_batch_stride;
+    P.Hv = hv; P.Wv = wv;
+    const bool valid = hv != d->h || wv != d->w;
     // Small launches (sequential tracking: 80-320 workgroups of 64 channels) leave most CUs with one workgroup whose K loop is a chain
     // of DMA latencies: 32-channel tiles double the workgroups.  Measured (whole pass, 640x512): batch 1 8.43 -> 7.87 ms, 4 frame pairs
     // 21.9 -> 21.1 ms, 8 pairs equal, 16 pairs (q convolutions: 1 280 workgroups = 2.5 rounds of the 512 slots) 70.96 -> 71.62 ms --
@@ -423,12 +434,23 @@ extern "C" int rpe_conv_wino1d(const rpe_conv_desc* d, void* stream) {
     const unsigned gx = ceil_div(d->w, 16) * ceil_div(d->h, 16);
     if ((long long)gx * (P.coP / W1_CO) * d->b < small_wg) {
         const dim3 grid(gx, ceil_div(d->cout, 32), d->b);
-        if (vert) hipLaunchKernelGGL((k_conv_wino1d<true, 1>), grid, dim3(256), 0, (hipStream_t)stream, P);
+        if (valid && vert) hipLaunchKernelGGL((k_conv_wino1d<true, 1, true>), grid, dim3(256), 0, (hipStream_t)stream, P);
+        else if (valid) hipLaunchKernelGGL((k_conv_wino1d<false, 1, true>), grid, dim3(256), 0, (hipStream_t)stream, P);
+        else if (vert) hipLaunchKernelGGL((k_conv_wino1d<true, 1>), grid, dim3(256), 0, (hipStream_t)stream, P);
         else hipLaunchKernelGGL((k_conv_wino1d<false, 1>), grid, dim3(256), 0, (hipStream_t)stream, P);
         return rpe_check_launch();
     }
     const dim3 grid(gx, P.coP / W1_CO, d->b);
-    if (vert) hipLaunchKernelGGL((k_conv_wino1d<true, 2>), grid, dim3(256), 0, (hipStream_t)stream, P);
+    if (valid && vert) hipLaunchKernelGGL((k_conv_wino1d<true, 2, true>), grid, dim3(256), 0, (hipStream_t)stream, P);
+    else if (valid) hipLaunchKernelGGL((k_conv_wino1d<false, 2, true>), grid, dim3(256), 0, (hipStream_t)stream, P);
+    else if (vert) hipLaunchKernelGGL((k_conv_wino1d<true, 2>), grid, dim3(256), 0, (hipStream_t)stream, P);
     else hipLaunchKernelGGL((k_conv_wino1d<false, 2>), grid, dim3(256), 0, (hipStream_t)stream, P);
     return rpe_check_launch();
+}
+
+extern "C" int rpe_conv_wino1d(const rpe_conv_desc* d, void* stream) { return conv_wino1d_launch(d, d ? d->h : 0, d ? d->w : 0, stream); }
+
+extern "C" int rpe_conv_wino1d_v(const rpe_conv_desc_v* dv, void* stream) {
+    if (!dv || !conv_valid_extent_ok(dv)) return RPE_E_BADARG;
+    return conv_wino1d_launch(&dv->d, dv->h_valid, dv->w_valid, stream);
 }

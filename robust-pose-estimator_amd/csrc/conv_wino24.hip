@@ -41,6 +41,7 @@ struct Wino24P {
     int mode;
     const float* scale; const float* res; long long rbs; float* stats; const float* pre;
     int co_base;
+    int Hv, Wv;                                   // valid extent (VALID instantiation, see conv_wino.hip): zero is stored outside it
 };
 
 // three 1 KB chunks: global base + voff + 1024 j  ->  LDS lds_addr + 1024 j + lane * 16
@@ -69,7 +70,7 @@ __host__ __device__ constexpr int w4_phys(int slot, int row) { return (slot + ((
 
 // EPI as conv_wino.hip: 0 bias / ReLU / out2; 1 + scale and residual; 2 + moments; 3 all at run time.  Needs W % 4 == 0, even H and
 // 16-byte aligned planes (the host checks).
-template <int EPI, bool PRE, int CB>
+template <int EPI, bool PRE, int CB, bool VALID = false>
 __global__ __launch_bounds__(256, 2) void k_conv_wino24(Wino24P P) {
     constexpr bool HAS_AFFINE = EPI == 1 || EPI == 3, HAS_STATS = EPI == 2 || EPI == 3;
     constexpr int NW = 4, TCO = 32 * CB, UT_STEP = W4K * TCO * W4_NP;
@@ -419,6 +420,10 @@ __global__ __launch_bounds__(256, 2) void k_conv_wino24(Wino24P P) {
 #pragma unroll
                         for (int e = 0; e < 4; ++e) q[e] = q[e] < 0.0f ? 0.0f : q[e];
                     }
+                    if (VALID) {                                     // selects: a NaN outside the extent leaves as zero
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) q[e] = (oy + i < P.Hv && ox + e < P.Wv) ? q[e] : 0.0f;
+                    }
                     const size_t e4 = (size_t)co * hw + (size_t)(oy + i) * W + ox;
                     *(f32x4*)(ob + e4) = q;
                     if (ob2) *(f32x4*)(ob2 + e4) = q;
@@ -475,7 +480,7 @@ extern "C" int rpe_conv_wino24_pack(const float* weight, int cout, int cin, floa
     return launch_pack(k_wino24_pack, weight, packed, cout, cin, W4K, (long long)rpe_conv_wino24_packed_floats(cout, cin), stream, round_up(cout, W4_CO));
 }
 
-extern "C" int rpe_conv_wino24(const rpe_conv_desc* d, void* stream) {
+static int conv_wino24_launch(const rpe_conv_desc* d, int hv, int wv, void* stream) {
     if (!conv_desc_present(d)) return RPE_E_BADARG;
     // tiles of 2 x 4 outputs, and every map row moved as 16-byte quads
     if (d->kh != 3 || d->kw != 3 || !stride_is_1(d) || (d->cin % W4K) || (d->h & 1) || (d->w & 3)) return RPE_E_UNSUPPORTED;
@@ -488,7 +493,14 @@ extern "C" int rpe_conv_wino24(const rpe_conv_desc* d, void* stream) {
     P.H = d->h; P.W = d->w; P.co_base = 0;
     const int epi = wino_epilogue_class(d);
     const unsigned gx = ceil_div(d->w, 16) * ceil_div(d->h, 8);
+    const bool valid = hv != d->h || wv != d->w;               // a valid extent smaller than the map: the plain epilogue only
+    if (valid && epi != 0) return RPE_E_UNSUPPORTED;
+    P.Hv = hv; P.Wv = wv;
     auto launch = [&](auto cb, int tiles) {
+        if (valid) {
+            hipLaunchKernelGGL((k_conv_wino24<0, false, decltype(cb)::value, true>), dim3(gx, tiles, d->b), dim3(256), 0, (hipStream_t)stream, P);
+            return;
+        }
         dispatch_epi_pre(epi, d->pre_norm != nullptr, [&](auto e, auto pre) {
             hipLaunchKernelGGL((k_conv_wino24<decltype(e)::value, decltype(pre)::value, decltype(cb)::value>), dim3(gx, tiles, d->b), dim3(256), 0,
                                (hipStream_t)stream, P);
@@ -498,4 +510,11 @@ extern "C" int rpe_conv_wino24(const rpe_conv_desc* d, void* stream) {
     if ((long long)gx * ceil_div(d->cout, W4_CO) * d->b < WINO_SMALL_WG) launch(std::integral_constant<int, 1>{}, ceil_div(d->cout, 32));
     else launch_tiles64(P, launch);
     return rpe_check_launch();
+}
+
+extern "C" int rpe_conv_wino24(const rpe_conv_desc* d, void* stream) { return conv_wino24_launch(d, d ? d->h : 0, d ? d->w : 0, stream); }
+
+extern "C" int rpe_conv_wino24_v(const rpe_conv_desc_v* dv, void* stream) {
+    if (!dv || !conv_valid_extent_ok(dv)) return RPE_E_BADARG;
+    return conv_wino24_launch(&dv->d, dv->h_valid, dv->w_valid, stream);
 }

@@ -792,18 +792,22 @@ struct NoGate { __device__ __forceinline__ void operator()() const {} };
 // kernel waits there until the matrix waves are done with the tile rows this level overwrites).
 template <bool DEEP, typename Gate = NoGate>
 __device__ __forceinline__ void lookup_wave(const float* __restrict__ pyr, const float* __restrict__ coords, char* outb, unsigned nq4, int tile_q,
-                                            float* wstage, const PyrGeom& G, int wave_g0, int l, int bz, Gate gate = Gate()) {
+                                            float* wstage, const PyrGeom& G, int wave_g0, int l, int bz, Gate gate = Gate(), int map_h = 0,
+                                            int map_w = 0) {
+    // map_w > 0 (rpe_corr_lookup_ex): coords and the output are the top-left h8 x w8 of (map_h, map_w) maps -- the update loop's padded
+    // workspace; nq4 is then the byte size of such a plane.  The pyramid and every tap keep the true (h8, w8).
     const int nq = G.h8 * G.w8;
     const int lane = threadIdx.x & 63;
     const int grp = lane >> 3, k = lane & 7;
     const int Gi = wave_g0 + grp;
     const int qy = Gi / G.gx, qx = (Gi % G.gx) * GQ + k;
     const bool qok = Gi < G.ngroups && qx < G.w8;
-    const int q = qok ? qy * G.w8 + qx : 0;
+    const int q = qok ? qy * (map_w > 0 ? map_w : G.w8) + qx : 0;    // (offset of the query in its coords / output plane)
     const int hl = G.h[l], wl = G.w[l], wp = G.wp[l], sk = G.sk[l];
     const float inv = 1.0f / (float)(1 << l);
-    const float cx = coords[((size_t)bz * 2 + 0) * nq + q] * inv;     // coords / 2**i  (exact)
-    const float cy = coords[((size_t)bz * 2 + 1) * nq + q] * inv;
+    const size_t cplane = map_w > 0 ? (size_t)map_h * map_w : (size_t)nq;
+    const float cx = coords[((size_t)bz * 2 + 0) * cplane + q] * inv;     // coords / 2**i  (exact)
+    const float cy = coords[((size_t)bz * 2 + 1) * cplane + q] * inv;
     TapAxis X, Y;
     make_taps(cx, wl, X);
     make_taps(cy, hl, Y);
@@ -897,6 +901,19 @@ __global__ __launch_bounds__(64 * LK_WAVES, LK_MINW) void k_corr_lookup(const fl
     const int wave_g0 = (bx * LK_WAVES + wv) * 8;                     // first group of this wave
     if (wave_g0 >= G.ngroups) return;                                 // (whole wave; there is no workgroup barrier below)
     lookup_wave<false>(pyr, coords, (char*)(out + (size_t)bz * G.levels * WIN * WIN * nq), (unsigned)nq * 4, -1, stage + wv * LK_WAVE_FLOATS, G, wave_g0, l, bz);
+}
+
+// The same into (and with coords from) the top-left h8 x w8 of (map_h, map_w) maps: rpe_corr_lookup_ex
+__global__ __launch_bounds__(64 * LK_WAVES, LK_MINW) void k_corr_lookup_ex(const float* __restrict__ pyr, const float* __restrict__ coords,
+                                                                         float* __restrict__ out, PyrGeom G, int map_h, int map_w) {
+    __shared__ __attribute__((aligned(16))) float stage[LK_WAVES * LK_WAVE_FLOATS];
+    const int bx = blockIdx.x, l = blockIdx.y, bz = blockIdx.z;
+    const int wv = threadIdx.x >> 6;
+    const int wave_g0 = (bx * LK_WAVES + wv) * 8;
+    if (wave_g0 >= G.ngroups) return;
+    const size_t mp = (size_t)map_h * map_w;
+    lookup_wave<false>(pyr, coords, (char*)(out + (size_t)bz * G.levels * WIN * WIN * mp), (unsigned)mp * 4, -1, stage + wv * LK_WAVE_FLOATS, G, wave_g0, l, bz,
+                       NoGate(), map_h, map_w);
 }
 
 // ------------------------------------------------------------------------------------------------ lookup fused into convc1
@@ -1262,6 +1279,16 @@ extern "C" int rpe_corr_lookup(const void* pyramid, const float* coords, int b, 
     if (!pyramid || !coords || !out || radius != RADIUS || !make_geom(b, h8, w8, levels, G)) return RPE_E_BADARG;
     hipLaunchKernelGGL(k_corr_lookup, dim3(ceil_div(G.ngroups, 8 * LK_WAVES), levels, b), dim3(64 * LK_WAVES), 0, (hipStream_t)stream,
                        (const float*)pyramid, coords, out, G);
+    return rpe_check_launch();
+}
+
+extern "C" int rpe_corr_lookup_ex(const void* pyramid, const float* coords, int b, int h8, int w8, int levels, int radius, int map_h, int map_w,
+                                  float* out, void* stream) {
+    PyrGeom G;
+    if (!pyramid || !coords || !out || radius != RADIUS || map_h < h8 || map_w < w8 || !make_geom(b, h8, w8, levels, G)) return RPE_E_BADARG;
+    if ((long long)map_h * map_w * levels * WIN * WIN * 4 >= (1ll << 32)) return RPE_E_UNSUPPORTED;      // 32-bit byte offsets within a batch item
+    hipLaunchKernelGGL(k_corr_lookup_ex, dim3(ceil_div(G.ngroups, 8 * LK_WAVES), levels, b), dim3(64 * LK_WAVES), 0, (hipStream_t)stream,
+                       (const float*)pyramid, coords, out, G, map_h, map_w);
     return rpe_check_launch();
 }
 

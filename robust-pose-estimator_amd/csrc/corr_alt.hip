@@ -163,8 +163,10 @@ __device__ __forceinline__ void alt_products(const float* const (&a)[2], const f
             for (int r = 0; r < 16; ++r) prod[(m * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * ALT_PP + col[n] + l31] = acc[m][n][r];
 }
 
+// map_h x map_w: the maps coords and out live in, of which the top-left h8 x w8 is read / written (rpe_corr_alt_lookup_ex: the update loop's
+// padded workspace; = h8 x w8 for dense tensors).  The feature maps and every tap keep the true (h8, w8).
 __global__ __launch_bounds__(256, 1) void k_alt_lookup(const float* __restrict__ scratch, const float* __restrict__ coords, float* __restrict__ out, AltGeom G,
-                                                       int tiles_x) {
+                                                       int tiles_x, int map_h, int map_w) {
     __shared__ float prod[64 * ALT_PP];
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int l31 = lane & 31, lh = lane >> 5;
@@ -177,10 +179,11 @@ __global__ __launch_bounds__(256, 1) void k_alt_lookup(const float* __restrict__
     // every wave holds the 64 queries of the tile, lane = query, and plans the rounds for itself: same inputs, same instructions, same plan
     const int qy = ty0 + (lane >> 3), qx = tx0 + (lane & 7);
     const bool qok = qy < G.h8 && qx < G.w8;
-    const int q = qok ? qy * G.w8 + qx : ty0 * G.w8 + tx0;            // (the tile's first query always exists)
+    const int q = qok ? qy * map_w + qx : ty0 * map_w + tx0;          // (the tile's first query always exists)
+    const size_t mp = (size_t)map_h * map_w;
     const float inv = 1.0f / (float)(1 << l);
-    const float cx = coords[((size_t)bz * 2 + 0) * nq + q] * inv;     // coords / 2**l  (exact)
-    const float cy = coords[((size_t)bz * 2 + 1) * nq + q] * inv;
+    const float cx = coords[((size_t)bz * 2 + 0) * mp + q] * inv;     // coords / 2**l  (exact)
+    const float cy = coords[((size_t)bz * 2 + 1) * mp + q] * inv;
     TapAxis X, Y;
     make_taps(cx, wl, X);
     make_taps(cy, hl, Y);
@@ -199,7 +202,7 @@ __global__ __launch_bounds__(256, 1) void k_alt_lookup(const float* __restrict__
         const bool ok = ay < G.h8 && ax < G.w8;
         a[m] = f1 + (size_t)(ok ? ay * G.w8 + ax : ty0 * G.w8 + tx0) * c + 4 * lh;
     }
-    float* obase = out + ((size_t)bz * G.levels + l) * (WIN * WIN) * nq + q;
+    float* obase = out + ((size_t)bz * G.levels + l) * (WIN * WIN) * mp + q;
 
     const int big = 0x3fffffff;
     bool pending = !empty;
@@ -263,7 +266,7 @@ __global__ __launch_bounds__(256, 1) void k_alt_lookup(const float* __restrict__
                 }
 #pragma unroll
                 for (int i = 0; i < WIN; ++i)                             // channel i * 9 + j: x offset i - r, y offset j - r
-                    obase[(size_t)(i * WIN + j) * nq] = hc[0][i] * Y.a0[j] + hc[1][i] * Y.a1[j] + hc[2][i] * Y.a2[j];
+                    obase[(size_t)(i * WIN + j) * mp] = hc[0][i] * Y.a0[j] + hc[1][i] * Y.a1[j] + hc[2][i] * Y.a2[j];
             }
         }
         pending = pending && !fits;
@@ -278,6 +281,18 @@ extern "C" int rpe_corr_alt_lookup(const void* scratch, const float* coords, int
     if (!scratch || !coords || !out || radius != RADIUS || (((uintptr_t)scratch) & 15) || !alt_geom(b, c, h8, w8, levels, G)) return RPE_E_BADARG;
     if (b > 65535) return RPE_E_UNSUPPORTED;
     const int tiles_x = ceil_div(w8, ALT_TQ), tiles_y = ceil_div(h8, ALT_TQ);
-    hipLaunchKernelGGL(k_alt_lookup, dim3(tiles_x * tiles_y, levels, b), dim3(256), 0, (hipStream_t)stream, (const float*)scratch, coords, out, G, tiles_x);
+    hipLaunchKernelGGL(k_alt_lookup, dim3(tiles_x * tiles_y, levels, b), dim3(256), 0, (hipStream_t)stream, (const float*)scratch, coords, out, G, tiles_x, h8, w8);
+    return rpe_check_launch();
+}
+
+extern "C" int rpe_corr_alt_lookup_ex(const void* scratch, const float* coords, int b, int c, int h8, int w8, int levels, int radius, int map_h, int map_w,
+                                      float* out, void* stream) {
+    AltGeom G;
+    if (!scratch || !coords || !out || radius != RADIUS || map_h < h8 || map_w < w8 || (((uintptr_t)scratch) & 15) || !alt_geom(b, c, h8, w8, levels, G))
+        return RPE_E_BADARG;
+    if (b > 65535) return RPE_E_UNSUPPORTED;
+    const int tiles_x = ceil_div(w8, ALT_TQ), tiles_y = ceil_div(h8, ALT_TQ);
+    hipLaunchKernelGGL(k_alt_lookup, dim3(tiles_x * tiles_y, levels, b), dim3(256), 0, (hipStream_t)stream, (const float*)scratch, coords, out, G, tiles_x,
+                       map_h, map_w);
     return rpe_check_launch();
 }

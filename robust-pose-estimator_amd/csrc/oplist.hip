@@ -19,6 +19,13 @@ static_assert(sizeof(rpe_instnorm_apply_args) == 64, "rpe_instnorm_apply_args: l
 static_assert(sizeof(rpe_upsample_convex_args) == 40, "rpe_upsample_convex_args: layout changed -- update _lib.py and RPE_ABI_VERSION");
 static_assert(sizeof(rpe_lookup_conv1x1_args) == 96, "rpe_lookup_conv1x1_args: layout changed -- update _lib.py and RPE_ABI_VERSION");
 static_assert(sizeof(rpe_flow_seed_args) == 72, "rpe_flow_seed_args: layout changed -- update _lib.py and RPE_ABI_VERSION");
+static_assert(sizeof(rpe_conv_desc_v) == 208, "rpe_conv_desc_v: layout changed -- update _lib.py and RPE_ABI_VERSION");
+static_assert(sizeof(rpe_corr_lookup_ex_args) == 56, "rpe_corr_lookup_ex_args: layout changed -- update _lib.py and RPE_ABI_VERSION");
+static_assert(sizeof(rpe_corr_alt_lookup_ex_args) == 56, "rpe_corr_alt_lookup_ex_args: layout changed -- update _lib.py and RPE_ABI_VERSION");
+static_assert(sizeof(rpe_stem_conv_v_args) == 104, "rpe_stem_conv_v_args: layout changed -- update _lib.py and RPE_ABI_VERSION");
+static_assert(sizeof(rpe_flow_update_v_args) == 104, "rpe_flow_update_v_args: layout changed -- update _lib.py and RPE_ABI_VERSION");
+static_assert(sizeof(rpe_upsample_convex_ex_args) == 48, "rpe_upsample_convex_ex_args: layout changed -- update _lib.py and RPE_ABI_VERSION");
+static_assert(sizeof(rpe_copy_rect_args) == 80, "rpe_copy_rect_args: layout changed -- update _lib.py and RPE_ABI_VERSION");
 static_assert(sizeof(rpe_solve_opts) == 32, "rpe_solve_opts: layout changed -- update _lib.py and RPE_ABI_VERSION");
 
 template <typename A>
@@ -88,6 +95,37 @@ static int run_one(const rpe_op& op, void* const* streams, int n_streams) {
         const auto* a = as<rpe_flow_seed_args>(op);
         return rpe_flow_seed(a->flow_init, a->b, a->h, a->w, a->coords_out, a->flow_out, a->dst1, a->dst1_batch_stride, a->dst2,
                              a->dst2_batch_stride, st);
+    }
+    case RPE_OP_CONV_WINO_V: return rpe_conv_wino_v(as<rpe_conv_desc_v>(op), st);
+    case RPE_OP_CONV_WINO24_V: return rpe_conv_wino24_v(as<rpe_conv_desc_v>(op), st);
+    case RPE_OP_CONV_WINO1D_V: return rpe_conv_wino1d_v(as<rpe_conv_desc_v>(op), st);
+    case RPE_OP_CONV1X1_V: return rpe_conv1x1_v(as<rpe_conv_desc_v>(op), st);
+    case RPE_OP_STEM_CONV_V: {
+        const auto* a = as<rpe_stem_conv_v_args>(op);
+        return rpe_stem_conv_v(a->image, a->b, a->cin, a->h, a->w, a->stride, a->div, a->mul, a->sub, a->packed, a->cout, a->bias, a->scale, a->relu,
+                               a->out, a->stats, a->h_valid, a->w_valid, st);
+    }
+    case RPE_OP_FLOW_UPDATE_V: {
+        const auto* a = as<rpe_flow_update_v_args>(op);
+        return rpe_conv3x3_to2_flow_v(a->x, a->weight, a->bias, a->b, a->c, a->h, a->w, a->coords, a->coords_out, a->flow_out, a->dst1,
+                                      a->dst1_batch_stride, a->dst2, a->dst2_batch_stride, a->h_valid, a->w_valid, st);
+    }
+    case RPE_OP_CORR_LOOKUP_EX: {
+        const auto* a = as<rpe_corr_lookup_ex_args>(op);
+        return rpe_corr_lookup_ex(a->pyramid, a->coords, a->b, a->h8, a->w8, a->levels, a->radius, a->map_h, a->map_w, a->out, st);
+    }
+    case RPE_OP_CORR_ALT_LOOKUP_EX: {
+        const auto* a = as<rpe_corr_alt_lookup_ex_args>(op);
+        return rpe_corr_alt_lookup_ex(a->scratch, a->coords, a->b, a->c, a->h8, a->w8, a->levels, a->radius, a->map_h, a->map_w, a->out, st);
+    }
+    case RPE_OP_UPSAMPLE_CONVEX_EX: {
+        const auto* a = as<rpe_upsample_convex_ex_args>(op);
+        return rpe_upsample_convex_ex(a->flow, a->mask, a->b, a->h8, a->w8, a->map_h, a->map_w, a->out, st);
+    }
+    case RPE_OP_COPY_RECT: {
+        const auto* a = as<rpe_copy_rect_args>(op);
+        return rpe_copy_rect(a->src, a->src_batch_stride, a->src_plane_stride, a->src_pitch, a->dst, a->dst_batch_stride, a->dst_plane_stride,
+                             a->dst_pitch, a->b, a->c, a->h, a->w, st);
     }
     case RPE_OP_EVENT_RECORD: {
         hipEvent_t ev = (hipEvent_t) * static_cast<void* const*>(op.args);

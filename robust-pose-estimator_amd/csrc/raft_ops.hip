@@ -196,9 +196,13 @@ struct FlowDst { float* p[3]; long long bs[3]; };
                                               // more slices, the shorter each chain).  The four-pixel kernel below uses the SAME
                                               // slices, tap order and explicit fused multiply-adds: which of the two a launch takes
                                               // (by its size) never shows in the result
+// VALID (rpe_conv3x3_to2_flow_v; both kernels): the map is a zero-padded workspace whose real content is hv x wv.  Outside that extent the
+// result is replaced by the pixel grid itself, so coords_out stays coords0 there and the flow written to the three destinations is
+// exactly zero -- the padding of the flow planes the motion encoder reads stays the convolution's own zero border.
+template <bool VALID = false>
 __global__ __launch_bounds__(64 * TO1_WAVES) void k_conv3x3_to2(const float* __restrict__ x, const float* __restrict__ wgt,
                                                      const float* __restrict__ bias, int C, int h, int w,
-                                                     const float* __restrict__ add, float* __restrict__ out, FlowDst F) {
+                                                     const float* __restrict__ add, float* __restrict__ out, FlowDst F, int vh = 0, int vw = 0) {
     __shared__ float part[TO1_WAVES][2][64];
     const int bz = blockIdx.y;
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);     // wave-uniform: weights by scalar loads
@@ -261,6 +265,7 @@ __global__ __launch_bounds__(64 * TO1_WAVES) void k_conv3x3_to2(const float* __r
         const size_t o = (size_t)bz * 2 * hw + p;
         a0 += bias ? bias[0] : 0.0f; a1 += bias ? bias[1] : 0.0f;
         if (add) { a0 += add[o]; a1 += add[o + hw]; }
+        if (VALID && !(py < vh && px < vw)) { a0 = (float)px; a1 = (float)py; }
         out[o] = a0; out[o + hw] = a1;
         const float f0 = a0 - (float)px, f1 = a1 - (float)py;
 #pragma unroll
@@ -275,9 +280,10 @@ __global__ __launch_bounds__(64 * TO1_WAVES) void k_conv3x3_to2(const float* __r
 // what lies outside the map by SELECTS after the loads -- no conditional loads (those compile to a branch around every load), and no
 // products with zero (0 * Inf = NaN, where torch's zero padding contributes nothing).
 #define TO2_WAVES TO1_WAVES                   // the same channel slices as the one-pixel kernel (bit-identical partial sums)
+template <bool VALID = false>
 __global__ __launch_bounds__(64 * TO2_WAVES) void k_conv3x3_to2_x4(const float* __restrict__ x, const float* __restrict__ wgt,
                                                         const float* __restrict__ bias, int C, int h, int w,
-                                                        const float* __restrict__ add, float* __restrict__ out, FlowDst F) {
+                                                        const float* __restrict__ add, float* __restrict__ out, FlowDst F, int vh = 0, int vw = 0) {
     __shared__ float part[TO2_WAVES][8][64];
     const int bz = blockIdx.y;
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform: weights by scalar loads
@@ -372,8 +378,12 @@ __global__ __launch_bounds__(64 * TO2_WAVES) void k_conv3x3_to2_x4(const float* 
             }
             const size_t idx = ((size_t)bz * 2 + o) * hw + (size_t)py * w + x0;
             if (add) { const float4 ad = *(const float4*)(add + idx); r4[0] += ad.x; r4[1] += ad.y; r4[2] += ad.z; r4[3] += ad.w; }
-            *(float4*)(out + idx) = make_float4(r4[0], r4[1], r4[2], r4[3]);
             const float g0 = o == 0 ? (float)x0 : (float)py, gs = o == 0 ? 1.0f : 0.0f;      // coords0: x along the row, y constant
+            if (VALID) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) r4[e] = (py < vh && x0 + e < vw) ? r4[e] : g0 + (float)e * gs;
+            }
+            *(float4*)(out + idx) = make_float4(r4[0], r4[1], r4[2], r4[3]);
             const float4 fl = make_float4(r4[0] - g0, r4[1] - (g0 + gs), r4[2] - (g0 + 2.0f * gs), r4[3] - (g0 + 3.0f * gs));
 #pragma unroll
             for (int i = 0; i < 3; ++i)
@@ -383,22 +393,25 @@ __global__ __launch_bounds__(64 * TO2_WAVES) void k_conv3x3_to2_x4(const float* 
 }
 
 // One thread per 1/8-resolution cell and sub-pixel row; loops over the row's 8 sub-pixels.  Mask channel = k*64 + i*8 + j.
+// flow and mask live in (mh, mw) maps of which the top-left h8 x w8 is read (rpe_upsample_convex_ex: the zero-padded workspace of the update
+// loop; mh = h8, mw = w8 for dense tensors); the output is the true-size (8 h8, 8 w8) flow.
 __global__ __launch_bounds__(256) void k_upsample_convex(const float* __restrict__ flow, const float* __restrict__ mask, int h8,
-                                                         int w8, float* __restrict__ out) {
+                                                         int w8, float* __restrict__ out, int mh, int mw) {
     const int bz = blockIdx.y;
     const int nq = h8 * w8;
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= nq) return;
     const int y = q / w8, x = q - y * w8;
+    const size_t mp = (size_t)mh * mw;                          // plane of the input maps
     float fx[9], fy[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) {                              // F.unfold(8*flow, 3, padding=1): zero padded
         const int yy = y + k / 3 - 1, xx = x + k % 3 - 1;
         const bool ok = yy >= 0 && yy < h8 && xx >= 0 && xx < w8;
-        fx[k] = ok ? 8.0f * flow[((size_t)bz * 2 + 0) * nq + (size_t)yy * w8 + xx] : 0.0f;
-        fy[k] = ok ? 8.0f * flow[((size_t)bz * 2 + 1) * nq + (size_t)yy * w8 + xx] : 0.0f;
+        fx[k] = ok ? 8.0f * flow[((size_t)bz * 2 + 0) * mp + (size_t)yy * mw + xx] : 0.0f;
+        fy[k] = ok ? 8.0f * flow[((size_t)bz * 2 + 1) * mp + (size_t)yy * mw + xx] : 0.0f;
     }
-    const float* mb = mask + (size_t)bz * 576 * nq + q;
+    const float* mb = mask + (size_t)bz * 576 * mp + (size_t)y * mw + x;
     const int W = 8 * w8;
     float* ox = out + ((size_t)bz * 2 + 0) * 64 * nq;
     float* oy = out + ((size_t)bz * 2 + 1) * 64 * nq;
@@ -410,7 +423,7 @@ __global__ __launch_bounds__(256) void k_upsample_convex(const float* __restrict
         for (int j = 0; j < 8; ++j) {
             float m[9], mx = -INFINITY;
 #pragma unroll
-            for (int k = 0; k < 9; ++k) { m[k] = mb[(size_t)(k * 64 + i * 8 + j) * nq]; mx = fmaxf(mx, m[k]); }
+            for (int k = 0; k < 9; ++k) { m[k] = mb[(size_t)(k * 64 + i * 8 + j) * mp]; mx = fmaxf(mx, m[k]); }
             float sum = 0.0f;
 #pragma unroll
             for (int k = 0; k < 9; ++k) { m[k] = expf(m[k] - mx); sum += m[k]; }
@@ -447,17 +460,25 @@ extern "C" int rpe_affine_act(const float* x, const float* scale, const float* s
 }
 
 static int launch_to2(const float* x, const float* weight, const float* bias, int b, int c, int h, int w, const float* add, float* out,
-                      const FlowDst& F, void* stream) {
+                      const FlowDst& F, void* stream, int hv = 0, int wv = 0) {
     if (!x || !weight || !out || b <= 0 || c <= 0 || h <= 0 || w <= 0) return RPE_E_BADARG;
     bool fvec = true;
     for (int i = 0; i < 3; ++i) fvec = fvec && (!F.p[i] || (vec_ok(F.p[i]) && (F.bs[i] & 3) == 0));
     // (the four-pixel kernel has a quarter of the workgroups: small launches -- one frame of sequential tracking -- keep the one-pixel one)
-    if ((w & 3) == 0 && vec_ok(x) && vec_ok(out) && (!add || vec_ok(add)) && fvec && (long long)ceil_div((size_t)h * w / 4, 64) * b >= 256)
-        hipLaunchKernelGGL(k_conv3x3_to2_x4, dim3(ceil_div((size_t)h * w / 4, 64), b), dim3(64 * TO2_WAVES), 0, (hipStream_t)stream, x, weight, bias,
-                           c, h, w, add, out, F);
+    const bool x4 = (w & 3) == 0 && vec_ok(x) && vec_ok(out) && (!add || vec_ok(add)) && fvec && (long long)ceil_div((size_t)h * w / 4, 64) * b >= 256;
+    if (hv > 0 && (hv != h || wv != w)) {                       // a valid extent smaller than the map
+        if (x4) hipLaunchKernelGGL(k_conv3x3_to2_x4<true>, dim3(ceil_div((size_t)h * w / 4, 64), b), dim3(64 * TO2_WAVES), 0, (hipStream_t)stream, x, weight,
+                                   bias, c, h, w, add, out, F, hv, wv);
+        else hipLaunchKernelGGL(k_conv3x3_to2<true>, dim3(ceil_div((size_t)h * w, 64), b), dim3(64 * TO1_WAVES), 0, (hipStream_t)stream, x, weight, bias,
+                                c, h, w, add, out, F, hv, wv);
+        return rpe_check_launch();
+    }
+    if (x4)
+        hipLaunchKernelGGL(k_conv3x3_to2_x4<false>, dim3(ceil_div((size_t)h * w / 4, 64), b), dim3(64 * TO2_WAVES), 0, (hipStream_t)stream, x, weight, bias,
+                           c, h, w, add, out, F, 0, 0);
     else
-        hipLaunchKernelGGL(k_conv3x3_to2, dim3(ceil_div((size_t)h * w, 64), b), dim3(64 * TO1_WAVES), 0, (hipStream_t)stream, x, weight, bias,
-                           c, h, w, add, out, F);
+        hipLaunchKernelGGL(k_conv3x3_to2<false>, dim3(ceil_div((size_t)h * w, 64), b), dim3(64 * TO1_WAVES), 0, (hipStream_t)stream, x, weight, bias,
+                           c, h, w, add, out, F, 0, 0);
     return rpe_check_launch();
 }
 
@@ -521,6 +542,45 @@ extern "C" int rpe_gru_gates_h(const float* z, const float* q_pre, const float* 
 
 extern "C" int rpe_upsample_convex(const float* flow, const float* mask, int b, int h8, int w8, float* out, void* stream) {
     if (!flow || !mask || !out || b <= 0 || h8 <= 0 || w8 <= 0) return RPE_E_BADARG;
-    hipLaunchKernelGGL(k_upsample_convex, dim3(ceil_div((size_t)h8 * w8, 256), b, 8), dim3(256), 0, (hipStream_t)stream, flow, mask, h8, w8, out);
+    hipLaunchKernelGGL(k_upsample_convex, dim3(ceil_div((size_t)h8 * w8, 256), b, 8), dim3(256), 0, (hipStream_t)stream, flow, mask, h8, w8, out, h8, w8);
+    return rpe_check_launch();
+}
+
+extern "C" int rpe_upsample_convex_ex(const float* flow, const float* mask, int b, int h8, int w8, int map_h, int map_w, float* out, void* stream) {
+    if (!flow || !mask || !out || b <= 0 || h8 <= 0 || w8 <= 0 || map_h < h8 || map_w < w8) return RPE_E_BADARG;
+    hipLaunchKernelGGL(k_upsample_convex, dim3(ceil_div((size_t)h8 * w8, 256), b, 8), dim3(256), 0, (hipStream_t)stream, flow, mask, h8, w8, out, map_h, map_w);
+    return rpe_check_launch();
+}
+
+extern "C" int rpe_conv3x3_to2_flow_v(const float* x, const float* weight, const float* bias, int b, int c, int h, int w,
+                                      const float* coords, float* coords_out, float* flow_out, float* dst1, long long dst1_batch_stride,
+                                      float* dst2, long long dst2_batch_stride, int h_valid, int w_valid, void* stream) {
+    if (!coords || h_valid <= 0 || w_valid <= 0 || h_valid > h || w_valid > w) return RPE_E_BADARG;
+    FlowDst F = {{flow_out, dst1, dst2}, {2LL * h * w, dst1_batch_stride, dst2_batch_stride}};
+    return launch_to2(x, weight, bias, b, c, h, w, coords, coords_out, F, stream, h_valid, w_valid);
+}
+
+// The h x w top-left rectangle of every plane of a (b, c) stack of maps into another stack with its own row pitch, plane and batch
+// strides (floats): the update loop's way into and out of its zero-padded workspace (net, inp, flow_init in; hidden state and 1/8 flow out).
+__global__ __launch_bounds__(256) void k_copy_rect(const float* __restrict__ src, long long sbs, long long sps, int spitch, float* __restrict__ dst,
+                                                   long long dbs, long long dps, int dpitch, int c, int h, int w) {
+    const size_t per = (size_t)c * h * w;
+    const float* s = src + (size_t)blockIdx.y * sbs;
+    float* d = dst + (size_t)blockIdx.y * dbs;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < per; i += (size_t)gridDim.x * blockDim.x) {
+        const int x = (int)(i % w), y = (int)((i / w) % h);
+        const size_t ch = i / ((size_t)w * h);
+        d[ch * dps + (size_t)y * dpitch + x] = s[ch * sps + (size_t)y * spitch + x];
+    }
+}
+
+extern "C" int rpe_copy_rect(const float* src, long long src_batch_stride, long long src_plane_stride, int src_pitch, float* dst,
+                             long long dst_batch_stride, long long dst_plane_stride, int dst_pitch, int b, int c, int h, int w, void* stream) {
+    if (!src || !dst || b <= 0 || c <= 0 || h <= 0 || w <= 0 || b > 65535) return RPE_E_BADARG;
+    if (src_pitch < w || dst_pitch < w || src_plane_stride < (long long)(h - 1) * src_pitch + w || dst_plane_stride < (long long)(h - 1) * dst_pitch + w)
+        return RPE_E_BADARG;
+    const size_t per = (size_t)c * h * w;
+    hipLaunchKernelGGL(k_copy_rect, dim3(min(ceil_div(per, 256), 2048), b), dim3(256), 0, (hipStream_t)stream, src, src_batch_stride, src_plane_stride,
+                       src_pitch, dst, dst_batch_stride, dst_plane_stride, dst_pitch, c, h, w);
     return rpe_check_launch();
 }

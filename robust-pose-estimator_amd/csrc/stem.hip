@@ -32,6 +32,7 @@ struct StemP {
     const float* bias; const float* scale;      // v = acc * scale[co] + bias[co]   (scale may be null)
     int relu, snp;                              // snp: patches per workgroup (weights are staged once for all of them)
     float* out; float* stats;                   // (b,cout,Ho,Wo); [b][cout][tiles][3] (n, mean, M2) or null
+    int Hv, Wv;                                 // valid extent of the output map (VALID instantiation): zero is stored outside it
 };
 
 __device__ __forceinline__ float half_wave_sum_s(float v) {
@@ -45,7 +46,7 @@ __device__ __forceinline__ float half_wave_sum_s(float v) {
 
 // Epilogue of one patch for one wave.  sb[co][2] = (scale | 1, bias | 0) of the workgroup's channels; element offsets within the
 // (batch item, channel tile) block are 32-bit (the launcher checks the size).
-template <int COB, bool STATS, bool INSIDE>
+template <int COB, bool STATS, bool INSIDE, bool VALID = false>
 __device__ __forceinline__ void stem_epilogue(f32x16 (&acc)[COB][2], const StemP& P, float* __restrict__ ob, const float* sb, float* red,
                                               int x0, int y0, int wv, int l31, int lh) {
     const unsigned hw = (unsigned)(P.Ho * P.Wo);
@@ -54,6 +55,7 @@ __device__ __forceinline__ void stem_epilogue(f32x16 (&acc)[COB][2], const StemP
     const unsigned lane_off = (unsigned)(ya * P.Wo + x) + (unsigned)(4 * lh) * hw, wo = (unsigned)P.Wo;
     const bool relu = P.relu != 0;
     const float* sbl = sb + 8 * lh;
+    const bool in0 = !VALID || ((ya < P.Hv) & (x < P.Wv)), in1 = !VALID || ((ya + 1 < P.Hv) & (x < P.Wv));   // (VALID: inside the valid extent)
 #pragma unroll
     for (int i = 0; i < COB; ++i)
 #pragma unroll
@@ -69,6 +71,7 @@ __device__ __forceinline__ void stem_epilogue(f32x16 (&acc)[COB][2], const StemP
                 if (l31 == 31) { float* rd = red + ((wv * 64) + cc + 4 * lh) * 3; rd[0] = ssum; rd[1] = ssq; rd[2] = piv; }
             }
             if (relu) { v0 = v0 < 0.0f ? 0.0f : v0; v1 = v1 < 0.0f ? 0.0f : v1; }
+            if (VALID) { v0 = in0 ? v0 : 0.0f; v1 = in1 ? v1 : 0.0f; }
             const unsigned e = lane_off + (unsigned)cc * hw;
             if (ok0) ob[e] = v0;
             if (ok1) ob[e + wo] = v1;
@@ -79,7 +82,8 @@ __device__ __forceinline__ void stem_epilogue(f32x16 (&acc)[COB][2], const StemP
 // convf1 of one frame pair: 80 workgroups of 64 channels on 256 CUs, each a chain of weight staging -> patch staging -> 224 matrix
 // instructions per wave): twice the workgroups, half the weights to stage and half the matrix instructions each.  Same products in
 // the same order: bit-identical outputs.
-template <int CIN, int STRIDE, int COB>
+// VALID (rpe_stem_conv_v, convf1 on a zero-padded flow map): outputs outside the valid extent Hv x Wv are stored as zero, not relu(bias).
+template <int CIN, int STRIDE, int COB, bool VALID = false>
 __global__ __launch_bounds__(256, 2) void k_stem7x7(StemP P) {
     typedef StemGeo<CIN, STRIDE> G;
     constexpr int TCO = 32 * COB;
@@ -171,7 +175,8 @@ __global__ __launch_bounds__(256, 2) void k_stem7x7(StemP P) {
         const size_t hw = (size_t)P.Ho * P.Wo;
         float* ob = P.out + ((size_t)bz * P.cout + cbase) * hw;
         const bool inside = (y0 + SPY <= P.Ho) & (x0 + SPX <= P.Wo);
-        if (P.stats) { if (inside) stem_epilogue<COB, true, true>(acc, P, ob, &sb[0][0], &red[0][0][0], x0, y0, wv, l31, lh);
+        if (VALID) stem_epilogue<COB, false, false, true>(acc, P, ob, &sb[0][0], &red[0][0][0], x0, y0, wv, l31, lh);
+        else if (P.stats) { if (inside) stem_epilogue<COB, true, true>(acc, P, ob, &sb[0][0], &red[0][0][0], x0, y0, wv, l31, lh);
                        else stem_epilogue<COB, true, false>(acc, P, ob, &sb[0][0], &red[0][0][0], x0, y0, wv, l31, lh); }
         else { if (inside) stem_epilogue<COB, false, true>(acc, P, ob, &sb[0][0], &red[0][0][0], x0, y0, wv, l31, lh);
                else stem_epilogue<COB, false, false>(acc, P, ob, &sb[0][0], &red[0][0][0], x0, y0, wv, l31, lh); }
@@ -218,14 +223,16 @@ extern "C" int rpe_stem_pack(const float* weight, int cout, int cin, float* pack
     return rpe_check_launch();
 }
 
-extern "C" int rpe_stem_conv(const float* image, int b, int cin, int h, int w, int stride, float div, float mul, float sub, const float* packed,
-                             int cout, const float* bias, const float* scale, int relu, float* out, float* stats, void* stream) {
+static int stem_conv_launch(const float* image, int b, int cin, int h, int w, int stride, float div, float mul, float sub, const float* packed,
+                            int cout, const float* bias, const float* scale, int relu, float* out, float* stats, int hv, int wv, void* stream) {
     if (!image || !packed || !out || b <= 0 || h <= 0 || w <= 0) return RPE_E_BADARG;
     if (!stem_ok(cin, stride, cout) || (stride == 2 && ((h & 1) || (w & 1))) || (((uintptr_t)packed) & 15)) return RPE_E_UNSUPPORTED;
     if ((long long)(h / stride) * (w / stride) * 65 * 4 >= (1ll << 32)) return RPE_E_UNSUPPORTED;      // 32-bit offsets within a 64-channel output block
     StemP P;
     P.x = image; P.H = h; P.W = w; P.Ho = h / stride; P.Wo = w / stride; P.cout = cout; P.div = div; P.mul = mul; P.sub = sub; P.wk = packed;
-    P.bias = bias; P.scale = scale; P.relu = relu; P.out = out; P.stats = stats;
+    P.bias = bias; P.scale = scale; P.relu = relu; P.out = out; P.stats = stats; P.Hv = hv; P.Wv = wv;
+    const bool valid = hv != P.Ho || wv != P.Wo;               // a valid extent smaller than the output map: convf1 without moments only
+    if (valid && (cin != 2 || stats)) return RPE_E_UNSUPPORTED;
     // several patches per workgroup share one staging of the weights -- when the launch still fills the chip that way
     // (bench: 15 360 stem patches; one frame of sequential tracking: 640)
     const long long patches = (long long)rpe_stem_tiles(h, w, stride) * (cout / 64) * b;
@@ -235,12 +242,28 @@ extern "C" int rpe_stem_conv(const float* image, int b, int cin, int h, int w, i
 #endif
     if (patches < STEM_SMALL_PATCHES) {            // fewer workgroups than CUs: 32-channel workgroups (same arithmetic, bit-identical)
         dim3 g1(rpe_stem_tiles(h, w, stride), cout / 32, b);
-        if (cin == 3) hipLaunchKernelGGL((k_stem7x7<3, 2, 1>), g1, dim3(256), 0, (hipStream_t)stream, P);
+        if (valid) hipLaunchKernelGGL((k_stem7x7<2, 1, 1, true>), g1, dim3(256), 0, (hipStream_t)stream, P);
+        else if (cin == 3) hipLaunchKernelGGL((k_stem7x7<3, 2, 1>), g1, dim3(256), 0, (hipStream_t)stream, P);
         else hipLaunchKernelGGL((k_stem7x7<2, 1, 1>), g1, dim3(256), 0, (hipStream_t)stream, P);
         return rpe_check_launch();
     }
     dim3 grid(ceil_div(rpe_stem_tiles(h, w, stride), P.snp), cout / 64, b);
-    if (cin == 3) hipLaunchKernelGGL((k_stem7x7<3, 2, 2>), grid, dim3(256), 0, (hipStream_t)stream, P);
+    if (valid) hipLaunchKernelGGL((k_stem7x7<2, 1, 2, true>), grid, dim3(256), 0, (hipStream_t)stream, P);
+    else if (cin == 3) hipLaunchKernelGGL((k_stem7x7<3, 2, 2>), grid, dim3(256), 0, (hipStream_t)stream, P);
     else hipLaunchKernelGGL((k_stem7x7<2, 1, 2>), grid, dim3(256), 0, (hipStream_t)stream, P);
     return rpe_check_launch();
+}
+
+extern "C" int rpe_stem_conv(const float* image, int b, int cin, int h, int w, int stride, float div, float mul, float sub, const float* packed,
+                             int cout, const float* bias, const float* scale, int relu, float* out, float* stats, void* stream) {
+    const int st = stride == 2 ? 2 : 1;
+    return stem_conv_launch(image, b, cin, h, w, stride, div, mul, sub, packed, cout, bias, scale, relu, out, stats, h / st, w / st, stream);
+}
+
+extern "C" int rpe_stem_conv_v(const float* image, int b, int cin, int h, int w, int stride, float div, float mul, float sub, const float* packed,
+                               int cout, const float* bias, const float* scale, int relu, float* out, float* stats, int h_valid, int w_valid,
+                               void* stream) {
+    const int st = stride == 2 ? 2 : 1;
+    if (h_valid <= 0 || w_valid <= 0 || h_valid > h / st || w_valid > w / st) return RPE_E_BADARG;
+    return stem_conv_launch(image, b, cin, h, w, stride, div, mul, sub, packed, cout, bias, scale, relu, out, stats, h_valid, w_valid, stream);
 }

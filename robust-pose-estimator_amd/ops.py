@@ -114,7 +114,7 @@ class Recorder(OpList):
         lo, hi = t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()
         sites = []
         for i, st in enumerate(self._structs):
-            for fname, ftype in st._fields_:
+            for fname, ftype in _lib.struct_fields(st):
                 if ftype is ctypes.c_void_p and (i, fname) not in self._claimed:
                     v = getattr(st, fname)
                     if v is not None and lo <= v < hi:
@@ -469,12 +469,17 @@ class CorrPyramid:
             raise _lib.RpeError('corr build: this pyramid was not sized for the requested feature mode (CorrPyramid(..., bf16x3=True))')
         return _launch(_lib.OP_CORR_BUILD, (ptr(f1), ptr(f2), b, c, h8, w8, self.levels, mode, ptr(self.buf)), (f1, f2, self), self)
 
-    def lookup(self, coords, out=None, prepare=False):
-        """``prepare=True`` (needs ``out``): a zero-argument launcher on these buffers, with ``.op`` for an OpList."""
+    def lookup(self, coords, out=None, prepare=False, map_size=None):
+        """``prepare=True`` (needs ``out``): a zero-argument launcher on these buffers, with ``.op`` for an OpList.
+        ``map_size`` = (mh, mw) (needs ``out``): coords (b,2,mh,mw) and out (b,ch,mh,mw) are larger maps whose top-left h8 x w8 is read /
+        written (rpe_corr_lookup_ex: the padded workspace of RAFT's pad_maps route); the rest of ``out`` is left alone."""
         co = _dev(coords, torch.float32, 'coords')
+        ch = self.levels * (2 * self.radius + 1) ** 2
+        if map_size is not None:
+            return _lookup_ex(self, _lib.OP_CORR_LOOKUP_EX, (ptr(self.buf), ptr(co), self.b, self.h8, self.w8, self.levels, self.radius), coords, co, out, ch,
+                              map_size, prepare)
         if tuple(co.shape) != (self.b, 2, self.h8, self.w8):
             raise _lib.RpeError('corr lookup: coords shape mismatch')
-        ch = self.levels * (2 * self.radius + 1) ** 2
         if out is None:
             out = torch.empty(self.b, ch, self.h8, self.w8, dtype=torch.float32, device=co.device)
         if prepare and (co is not coords or tuple(_nchw(out, 'out').shape) != (self.b, ch, self.h8, self.w8)):
@@ -539,12 +544,16 @@ class AltCorr:
             raise _lib.RpeError('corr alt build: shape mismatch')
         return _launch(_lib.OP_CORR_ALT_PREPARE, (ptr(f1), ptr(f2), self.b, self.c, self.h8, self.w8, self.levels, ptr(self.buf)), (f1, f2, self), self)
 
-    def lookup(self, coords, out=None, prepare=False):
-        """``prepare=True`` (needs ``out``): a zero-argument launcher on these buffers, with ``.op`` for an OpList."""
+    def lookup(self, coords, out=None, prepare=False, map_size=None):
+        """``prepare=True`` (needs ``out``): a zero-argument launcher on these buffers, with ``.op`` for an OpList.  ``map_size``: as
+        CorrPyramid.lookup (rpe_corr_alt_lookup_ex)."""
         co = _dev(coords, torch.float32, 'coords')
+        ch = self.levels * (2 * self.radius + 1) ** 2
+        if map_size is not None:
+            return _lookup_ex(self, _lib.OP_CORR_ALT_LOOKUP_EX, (ptr(self.buf), ptr(co), self.b, self.c, self.h8, self.w8, self.levels, self.radius), coords, co,
+                              out, ch, map_size, prepare)
         if tuple(co.shape) != (self.b, 2, self.h8, self.w8):
             raise _lib.RpeError('corr alt lookup: coords shape mismatch')
-        ch = self.levels * (2 * self.radius + 1) ** 2
         if out is None:
             out = torch.empty(self.b, ch, self.h8, self.w8, dtype=torch.float32, device=co.device)
         if prepare and co is not coords:
@@ -553,6 +562,16 @@ class AltCorr:
             raise _lib.RpeError('corr alt lookup: out must be a contiguous (b, levels*(2r+1)^2, h8, w8) buffer')
         return _launch(_lib.OP_CORR_ALT_LOOKUP, (ptr(self.buf), ptr(co), self.b, self.c, self.h8, self.w8, self.levels, self.radius, ptr(out)),
                        (self, co, out), out, prepare)
+
+
+def _lookup_ex(corr, kind, head, coords, co, out, ch, map_size, prepare):
+    """The pitched lookup of CorrPyramid / AltCorr: ``head`` = the entry point's arguments up to the radius."""
+    mh, mw = map_size
+    if mh < corr.h8 or mw < corr.w8 or co is not coords or tuple(co.shape) != (corr.b, 2, mh, mw):
+        raise _lib.RpeError(f'corr lookup: with map_size coords must be a contiguous ({corr.b},2,{mh},{mw}) tensor, the map at least ({corr.h8},{corr.w8})')
+    if out is None or tuple(_nchw(out, 'out').shape) != (corr.b, ch, mh, mw):
+        raise _lib.RpeError(f'corr lookup: with map_size out must be a contiguous ({corr.b},{ch},{mh},{mw}) buffer')
+    return _launch(kind, (*head, mh, mw, ptr(out)), (corr, co, out), out, prepare)
 
 
 class _Packed:
@@ -668,9 +687,11 @@ def conv3x3_to2(x, weight, bias, add=None, out=None):
     return out
 
 
-def flow_update(x, weight, bias, coords, coords_out, flow_out=None, dst1=None, dst2=None, prepare=False):
+def flow_update(x, weight, bias, coords, coords_out, flow_out=None, dst1=None, dst2=None, prepare=False, valid=None):
     """rpe_conv3x3_to2_flow: coords_out = conv3x3(x; weight (2,c,3,3)) + bias + coords, and flow = coords_out - pixel grid written to
-    ``flow_out`` (b,2,h,w) and into the two-channel slices ``dst1`` / ``dst2`` (e.g. hx[:, 254:256]).  ``prepare=True`` returns a launcher."""
+    ``flow_out`` (b,2,h,w) and into the two-channel slices ``dst1`` / ``dst2`` (e.g. hx[:, 254:256]).  ``prepare=True`` returns a launcher.
+    ``valid`` = (hv, wv): the maps are zero-padded and hold hv x wv of content (rpe_conv3x3_to2_flow_v): outside it coords_out is the pixel
+    grid and the flow exactly zero."""
     _nchw(x, 'flow_update: x')
     b, c, hh, ww = x.shape
     weight = _nchw(weight.detach() if weight.requires_grad else weight, 'flow_update: weight')
@@ -680,8 +701,35 @@ def flow_update(x, weight, bias, coords, coords_out, flow_out=None, dst1=None, d
         if t is not None and tuple(_nchw(t, f'flow_update: {name}').shape) != (b, 2, hh, ww):
             raise _lib.RpeError(f'flow_update: {name} must be ({b},2,{hh},{ww})')
     sl = _opt_slices('flow_update', b, 2, hh, ww, dst1=dst1, dst2=dst2)
-    return _launch(_lib.OP_FLOW_UPDATE, (ptr(x), ptr(weight), ptr(bias), b, c, hh, ww, ptr(coords), ptr(coords_out), ptr(flow_out), *sl),
-                   (x, weight, bias, coords, coords_out, flow_out, dst1, dst2), coords_out, prepare)
+    args = (ptr(x), ptr(weight), ptr(bias), b, c, hh, ww, ptr(coords), ptr(coords_out), ptr(flow_out), *sl)
+    keep = (x, weight, bias, coords, coords_out, flow_out, dst1, dst2)
+    if valid is not None:
+        return _launch(_lib.OP_FLOW_UPDATE_V, (*args, *_valid_extent('flow_update', valid, hh, ww)), keep, coords_out, prepare)
+    return _launch(_lib.OP_FLOW_UPDATE, args, keep, coords_out, prepare)
+
+
+def _valid_extent(who, valid, hh, ww):
+    """(hv, wv) of a ``valid=`` argument, checked against the map: the library refuses an extent beyond it too (RPE_E_BADARG)."""
+    hv, wv = (int(v) for v in valid)
+    if not (0 < hv <= hh and 0 < wv <= ww):
+        raise _lib.RpeError(f'{who}: valid extent ({hv},{wv}) does not lie inside the ({hh},{ww}) map')
+    return hv, wv
+
+
+def copy_rect(src, dst, hh, ww):
+    """dst[:, :, :hh, :ww] = src[:, :, :hh, :ww] (rpe_copy_rect) for 4-D float32 tensors with unit stride along x and any row pitch, plane and
+    batch stride -- contiguous maps, channel slices, and both against maps of another size: into and out of a padded workspace."""
+    for name, t in (('src', src), ('dst', dst)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.stride(3) == 1):
+            raise _lib.RpeError(f'copy_rect: {name} must be a float32 NCHW GPU tensor with unit stride along x')
+        _on_current_device(t, f'copy_rect: {name}')
+        if t.shape[2] < hh or t.shape[3] < ww:
+            raise _lib.RpeError(f'copy_rect: {name} {tuple(t.shape)} is smaller than the ({hh},{ww}) rectangle')
+    b, c = src.shape[:2]
+    if tuple(dst.shape[:2]) != (b, c):
+        raise _lib.RpeError('copy_rect: batch / channel mismatch')
+    return _launch(_lib.OP_COPY_RECT, (ptr(src), src.stride(0), src.stride(1), src.stride(2), ptr(dst), dst.stride(0), dst.stride(1), dst.stride(2), b, c, hh, ww),
+                   (src, dst), dst)
 
 
 def copy_planes(src, dst):
@@ -733,9 +781,16 @@ def flow_seed(flow_init, coords_out=None, flow_out=None, dst1=None, dst2=None, p
                    coords_out, prepare)
 
 
-def upsample_convex(flow, mask):
+def upsample_convex(flow, mask, size=None):
+    """``size`` = (h8, w8): flow and mask are larger (zero-padded) maps whose top-left h8 x w8 is up-sampled (rpe_upsample_convex_ex)."""
     fl, mk = _dev(flow, torch.float32, 'flow'), _dev(mask, torch.float32, 'mask')
     b, _, h8, w8 = fl.shape
+    if size is not None:
+        mh, mw, (h8, w8) = h8, w8, size
+        if tuple(mk.shape) != (b, 576, mh, mw) or not (0 < h8 <= mh and 0 < w8 <= mw):
+            raise _lib.RpeError('upsample_convex: mask must be (b,576,mh,mw) like the flow map, size within it')
+        out = torch.empty(b, 2, 8 * h8, 8 * w8, dtype=torch.float32, device=fl.device)
+        return _launch(_lib.OP_UPSAMPLE_CONVEX_EX, (ptr(fl), ptr(mk), b, h8, w8, mh, mw, ptr(out)), (fl, mk, out), out)
     if tuple(mk.shape) != (b, 576, h8, w8):
         raise _lib.RpeError('upsample_convex: mask must be (b,576,h/8,w/8)')
     out = torch.empty(b, 2, 8 * h8, 8 * w8, dtype=torch.float32, device=fl.device)
@@ -806,10 +861,10 @@ class PackedConv1x1X3(_Packed):
     size, pack, entry = 'rpe_conv1x1_x3_packed_bytes', 'rpe_conv1x1_x3_pack', 'rpe_conv1x1_x3'
 
 
-def conv1x1(x, pc, mode, out, out2=None, prepare=False):
+def conv1x1(x, pc, mode, out, out2=None, prepare=False, valid=None):
     """rpe_conv1x1: out = act(W x + bias) for a PackedConv1x1 (LINEAR / RELU / TANH), channel-slice destinations like conv_fused
     (a PackedConv1x1X3 runs rpe_conv1x1_x3)."""
-    return conv_fused(x, pc, mode, out, out2=out2, prepare=prepare, entry=pc.entry)
+    return conv_fused(x, pc, mode, out, out2=out2, prepare=prepare, entry=pc.entry, valid=valid)
 
 
 class Conv1x1:
@@ -833,7 +888,7 @@ class Conv1x1:
     gemm = property(lambda self: self._packing(PackedConv1x1))
     gemm_x3 = property(lambda self: self._packing(PackedConv1x1X3))
 
-    def __call__(self, x, mode, out, out2=None, prepare=False, x3=False):
+    def __call__(self, x, mode, out, out2=None, prepare=False, x3=False, valid=None):
         b, _, hh, ww = x.shape
         # rpe_conv1x1's own preconditions (16-byte DMA pieces): plane size, base and batch stride of the input slice
         aligned = PackedConv1x1.supported(hh, ww) and x.data_ptr() % 16 == 0 and x.stride(0) % 4 == 0
@@ -841,6 +896,10 @@ class Conv1x1:
         if aligned and x3 and mode in (CONV_LINEAR, CONV_RELU):     # the labelled bf16x3 variant (raft.CONV_BF16X3): at EVERY launch size, so that a
             #                                                            row's bits do not depend on the batch it is launched in
             return conv1x1(x, self.gemm_x3, mode, out, out2=out2, prepare=prepare)
+        if valid is not None:                                 # a valid extent inside a padded map: rpe_conv1x1_v at every launch size (same bits as either)
+            if not aligned or x3:
+                raise _lib.RpeError('Conv1x1: a valid extent needs the f32 GEMM route (16-byte aligned input slice, h * w % 4 == 0, no bf16x3)')
+            return conv1x1(x, self.gemm, mode, out, out2=out2, prepare=prepare, valid=valid)
         if big:
             return conv1x1(x, self.gemm, mode, out, out2=out2, prepare=prepare)
         return conv_fused(x, self.fused, mode, out, out2=out2, prepare=prepare)
@@ -856,23 +915,36 @@ _FUSED_MODES = (CONV_LINEAR, CONV_RELU, CONV_GATE_ZR, CONV_GATE_H, CONV_TANH)
 
 
 def conv_fused(x, pc, mode, out, out2=None, add=None, hidden=None, zgate=None, gate_channels=0, scale=None, bias='packed',
-               residual=None, stats=None, stride=1, pre_norm=None, prepare=False, entry='rpe_conv_fused'):
+               residual=None, stats=None, stride=1, pre_norm=None, prepare=False, entry='rpe_conv_fused', valid=None):
     """rpe_conv_fused: out = epilogue(conv(x; pc) * scale + add + bias).  All tensors are channel slices of NCHW buffers.
     ``bias`` defaults to the one packed with the weights; ``stats`` (from conv_stats_buffer) collects the per-tile moments
     instnorm_apply needs.  ``prepare=True`` returns a zero-argument launcher instead of launching: the GRU loop runs the same
-    nine convolutions on the same buffers twelve times, and at batch 1 the Python argument checking costs more than the kernels."""
+    nine convolutions on the same buffers twelve times, and at batch 1 the Python argument checking costs more than the kernels.
+    ``valid`` = (hv, wv): the entry point's ``_v`` form (rpe_conv_wino1d_v, rpe_conv1x1_v): the map is zero-padded, the epilogue stores zero
+    outside its hv x wv of content."""
     d, bias, stats = _conv_desc('conv_fused', x, pc, mode, dict(add=add, out=out, out2=out2, hidden=hidden, zgate=zgate, residual=residual),
                                 _FUSED_RULES.get(mode, _PLAIN_RULES), scale, bias, stats, pre_norm, modes=_FUSED_MODES, tile_major=False,
-                                kernel=(pc.kh, pc.kw), stride=stride, gate_channels=gate_channels)
-    return _launch(_lib.KIND_OF_ENTRY[entry], d, (x, pc, out, out2, add, hidden, zgate, scale, bias, residual, stats, pre_norm), out, prepare)
+                                kernel=(pc.kh, pc.kw), stride=stride, gate_channels=gate_channels, valid=valid)
+    return _launch(_kind(entry, valid), d, (x, pc, out, out2, add, hidden, zgate, scale, bias, residual, stats, pre_norm), out, prepare)
 
 
-def _conv_desc(who, x, pc, mode, slices, rules, scale, bias, stats, pre_norm, *, modes, tile_major, kernel, stride=1, gate_channels=0):
+def _kind(entry, valid):
+    """The launch-list kind of ``entry``, or of its valid-extent form ``entry + '_v'`` (an entry point without one raises)."""
+    if valid is None:
+        return _lib.KIND_OF_ENTRY[entry]
+    if entry + '_v' not in _lib.KIND_OF_ENTRY:
+        raise _lib.RpeError(f'{entry} has no valid-extent form')
+    return _lib.KIND_OF_ENTRY[entry + '_v']
+
+
+def _conv_desc(who, x, pc, mode, slices, rules, scale, bias, stats, pre_norm, *, modes, tile_major, kernel, stride=1, gate_channels=0, valid=None):
     """The ConvDesc of conv_fused / conv_wino after the checks they share -> (descriptor, the bias and the stats tensor it points to).
     ``slices``: descriptor field -> channel slice on the output map or None, checked against ``rules`` (as _PLAIN_RULES); ``modes``: the epilogues the kernel has; ``tile_major``: the layout of ``stats`` (conv_wino's TileMajorStats, or
     conv_stats_buffer's channel-major tensor); ``kernel`` = (kh, kw)."""
-    d = _lib.ConvDesc()
+    d = _lib.ConvDesc() if valid is None else _lib.ConvDescV()
     b, cin, hh, ww = x.shape
+    if valid is not None:
+        d.h_valid, d.w_valid = _valid_extent(who, valid, hh // stride, ww // stride)
     cout = pc.cout
     if cin != pc.cin:
         raise _lib.RpeError(f'{who}: input has {cin} channels, weights expect {pc.cin}')
@@ -998,13 +1070,13 @@ class PackedWinoX3(_Packed):
         return tuple(weight.shape[2:]) == (3, 3) and weight.shape[1] % 16 == 0 and hh % 2 == 0 and ww % 4 == 0
 
 
-def conv_wino(x, pw, mode, out, out2=None, scale=None, bias='packed', residual=None, stats=None, pre_norm=None, prepare=False):
+def conv_wino(x, pw, mode, out, out2=None, scale=None, bias='packed', residual=None, stats=None, pre_norm=None, prepare=False, valid=None):
     """rpe_conv_wino: out = epilogue(conv3x3(x; pw) * scale + bias) by Winograd F(2x2,3x3) -- F(2x4,3x3) with a PackedWino24, the
     labelled bf16x3 variant with a PackedWinoX3; tensors are channel slices of NCHW buffers.  ``stats`` (conv_wino_stats_buffer) /
     ``pre_norm`` / ``residual`` / ``scale``: the encoders' epilogues, as conv_fused."""
     d, bias, stats = _conv_desc('conv_wino', x, pw, mode, dict(out=out, out2=out2, residual=residual), _WINO_RULES, scale, bias, stats, pre_norm,
-                                modes=(CONV_LINEAR, CONV_RELU), tile_major=True, kernel=(3, 3))
-    return _launch(_lib.KIND_OF_ENTRY[pw.entry], d, (x, pw, out, out2, scale, bias, residual, stats, pre_norm), out, prepare)
+                                modes=(CONV_LINEAR, CONV_RELU), tile_major=True, kernel=(3, 3), valid=valid)
+    return _launch(_kind(pw.entry, valid), d, (x, pw, out, out2, scale, bias, residual, stats, pre_norm), out, prepare)
 
 
 class TileMajorStats:
@@ -1095,7 +1167,7 @@ class PackedStem(_Packed):
         return (self.kh, self.kw) == (7, 7) and self.cin in (2, 3) and self.cout % 64 == 0
 
 
-def stem_conv(image, ps, bias=None, scale=None, relu=True, stats=False, div=255.0, mul=2.0, sub=1.0, out=None, prepare=False):
+def stem_conv(image, ps, bias=None, scale=None, relu=True, stats=False, div=255.0, mul=2.0, sub=1.0, out=None, prepare=False, valid=None):
     """conv7x7(mul * (image / div) - sub) * scale + bias [ReLU]; stride and channel counts come from ``ps``.
     Returns out, or (out, stats).  ``prepare=True`` (needs ``out``; stats = a caller-owned buffer or False): a launcher with ``.op``."""
     _nchw(image, 'stem_conv: image')
@@ -1111,8 +1183,10 @@ def stem_conv(image, ps, bias=None, scale=None, relu=True, stats=False, div=255.
         st, stats = _f32(stats, 'stem_conv: stats', (b, ps.cout, lib().rpe_stem_tiles(hh, ww, st_), 3)), True
     else:
         st = torch.empty(b, ps.cout, lib().rpe_stem_tiles(hh, ww, st_), 3, dtype=torch.float32, device=image.device) if stats else None
-    return _launch(_lib.OP_STEM_CONV, (ptr(image), b, c, hh, ww, st_, float(div), float(mul), float(sub), ptr(ps.packed), ps.cout, ptr(bias), ptr(scale),
-                                       int(bool(relu)), ptr(out), ptr(st)), (image, ps, bias, scale, out, st),
+    args = (ptr(image), b, c, hh, ww, st_, float(div), float(mul), float(sub), ptr(ps.packed), ps.cout, ptr(bias), ptr(scale), int(bool(relu)), ptr(out), ptr(st))
+    if valid is not None:                           # (rpe_stem_conv_v: zero outside the valid extent of the output map)
+        return _launch(_lib.OP_STEM_CONV_V, (*args, *_valid_extent('stem_conv', valid, hh // st_, ww // st_)), (image, ps, bias, scale, out, st), out, prepare)
+    return _launch(_lib.OP_STEM_CONV, args, (image, ps, bias, scale, out, st),
                    (out, st) if stats and not prepare else out, prepare)
 
 

@@ -13,6 +13,8 @@ What runs where (MI355X-first split), all hand-written HIP 
     tanh | ReLU split in the epilogue) and the mask head's 1x1 on the implicit GEMM
   * flow-head output layer with the coords / flow bookkeeping of the loop, convex up-sampling, norm / bias passes, slice copies
     (csrc/raft_ops.hip)
+  * opt-in (config ``pad_maps``): at such map sizes the UPDATE LOOP on the tuned kernels over zero-padded maps (padded_size; the kernels' valid-extent
+    entry points rpe_conv_*_v keep the padding zero); the encoders stay on the generic route below
   * map sizes the tuned kernels refuse (odd maps, rows that are not whole 16-byte quads: image widths that are not a multiple of 32,
     heights not a multiple of 16): the same layers on the generic implicit GEMM (csrc/conv_direct.hip) with the stand-alone epilogue
     kernels -- robust, slower; no launch of a pass goes to a library at any size
@@ -57,6 +59,9 @@ X3_GRU = False           # under CONV_BF16X3, also the SepConvGRU's 1x5 / 5x1 la
 # batch 1-2 (sequential tracking) 9.22 -> 9.08 ms per frame pair, 110.2 -> 111.9 frames/s; batch 32: 72.49 vs 72.41 ms per step (every
 # launch fills the chip on its own), so it is used for small passes only.
 SIDE_STREAM = True
+# RAFT's ``pad_maps`` for models built without the config key (tools/bench_pad_maps.py, A/B runs): at 1/8 maps the tuned kernels refuse, the
+# update loop runs on maps zero-padded to the next size they take (padded_size).  Opt-in; no effect on maps they take as they are.
+PAD_MAPS = False
 # The update loop as ONE call into the library (ops.OpList -> rpe_run_ops): the 12 iterations' ~130-180 launches and stream fork / joins are
 # enqueued by a C loop over prepared argument blocks instead of one Python-dispatched ctypes call each (bit-identical: the same entry
 # points with the same arguments).  False = launch by launch from Python (bench.py's per-convolution diagnostic pass, A/B runs).
@@ -87,13 +92,21 @@ SIDE_STREAM_MAX = 8 * 5120                                     # queries per pas
 # recorded under them, so a switch flipped on a live model (tests, bench.py's A/B runs) is honoured by all of it at the next pass.
 # (LOOP_OPLIST, LOOKUP_EVENT_SINK, FRAME_OPLISTS and FRAME_OPLISTS_MAX_IMAGES choose how launches are dispatched, not what is cached.)
 ROUTE_SWITCHES = ('WINOGRAD', 'WINO_2X4', 'S2_M96', 'S2_M96_MIN_WGS', 'CORR_BF16X3', 'CONV_BF16X3', 'X3_MIN_CIN', 'X3_GRU', 'SIDE_STREAM', 'SIDE_STREAM_MAX',
-                  'LOOKUP_FUSED', 'LOOKUP_FUSED_MAX_WGS', 'ENC_STREAMS', 'ENC_STREAMS_MIN')
+                  'LOOKUP_FUSED', 'LOOKUP_FUSED_MAX_WGS', 'ENC_STREAMS', 'ENC_STREAMS_MIN', 'PAD_MAPS')
 _switch_values = operator.itemgetter(*ROUTE_SWITCHES)
 
 
 def _switches():
     """The current values of ROUTE_SWITCHES (read from the module at every call: they are plain attributes that callers assign)."""
     return _switch_values(globals())
+
+
+def padded_size(h8, w8):
+    """The map the update loop's tuned kernels run (h8, w8) on under ``pad_maps``: the next size they take -- rows rounded up to an even count
+    (the 2-row tiles of rpe_conv_wino / rpe_conv_wino24), row length to a multiple of 4 (whole 16-byte quads; F(2x4,3x3) needs no more than
+    that, so a multiple of 8 buys nothing).  The identity on sizes they take as they are: (11,13) -> (12,16), (45,44) -> (46,44),
+    (135,240) -> (136,240), (64,80) -> (64,80)."""
+    return h8 + (h8 & 1), (w8 + 3) // 4 * 4
 
 
 def _norm(kind, ch):
@@ -478,7 +491,7 @@ class BasicMotionEncoder(nn.Module):
     def flow_branch(self, flow, P, L):
         """convf1 -> convf2 of the fused route (``P`` = BasicUpdateBlock.packed_convs, ``L`` = its launchers): depends on the flow only, not
         on the correlation lookup, so it may run on a side stream beside lookup -> convc1 -> convc2."""
-        ops.stem_conv(flow, P['convf1'], bias=self.convf1.bias.detach(), relu=True, div=1.0, mul=1.0, sub=0.0, out=L.flo)   # 7x7 on 2 channels
+        ops.stem_conv(flow, P['convf1'], bias=self.convf1.bias.detach(), relu=True, div=1.0, mul=1.0, sub=0.0, out=L.flo, **L.vk)   # 7x7 on 2 channels
         L.f2()
 
     def forward(self, flow, corr, cat_buf, hx, rhx):
@@ -593,7 +606,7 @@ class BasicUpdateBlock(nn.Module):
         launch where that pays (LOOKUP_FUSED), else None."""
         packed_key, P = self.packed_convs(ws['hx'].shape[-1], with_key=True)
         alt = isinstance(pyr, ops.AltCorr)                  # (alternate_corr: lookup into the cor buffer, then convc1 -- LOOKUP_FUSED does not apply)
-        key = (packed_key, None if pyr is None else (pyr.buf.data_ptr(), alt))
+        key = (packed_key, None if pyr is None else (pyr.buf.data_ptr(), alt), ws.get('valid'))
         return _cached(ws, '_launchers', key, lambda: self._make_launchers(ws, P, pyr, alt), with_key)
 
     def _make_launchers(self, ws, P, pyr, alt):
@@ -601,6 +614,10 @@ class BasicUpdateBlock(nn.Module):
         c = self.hidden_dim
         e, fh = self.encoder, self.flow_head
         cor, flo, fh_buf = P['cor_buf'](corr), P['flo_buf'](corr), P['fh_buf'](hx)
+        # pad_maps: the buffers are zero-padded maps with ``valid`` = (h8, w8) of content; every launch below then takes its entry point's
+        # valid-extent form, whose epilogue stores zero in the padding (None = the maps are the content: the plain entry points)
+        valid = ws.get('valid')
+        vk = {} if valid is None else dict(valid=valid)   # (flag off: every call below is the call it always was)
         wino = dict(P['wino']) if hx.shape[-1] % 2 == 0 and hx.shape[-2] % 2 == 0 else {}
         if wino and hx.shape[-1] % 4 == 0:
             wino.update(P['wino24'])
@@ -608,25 +625,28 @@ class BasicUpdateBlock(nn.Module):
 
         def c3(name, x, out, out2=None):                    # a 3x3 layer: Winograd when available, else the direct implicit GEMM
             if name in wino:
-                return ops.conv_wino(x, wino[name], ops.CONV_RELU, out, out2=out2, prepare=True)
+                return ops.conv_wino(x, wino[name], ops.CONV_RELU, out, out2=out2, prepare=True, **vk)
+            if valid is not None:
+                raise ops._lib.RpeError('RAFT: pad_maps runs the 3x3 layers on the Winograd kernels (WINOGRAD)')
             return ops.conv_fused(x, P[name], ops.CONV_RELU, out, out2=out2, prepare=True)
         # each GRU half = two implicit-GEMM convolutions whose epilogues are the gates:
         #   z = s(convz hx + ctx), r*h -> rhx ;  h <- (1-z) h + z tanh(convq rhx + ctx)   (in place on hx[:, :c])
         gconv = ops.conv_wino1d if isinstance(P['zr1'], (ops.PackedWino1d, ops.PackedWino1dX3)) else ops.conv_fused
         gru = []
         for zr, q in (('zr1', 'q1'), ('zr2', 'q2')):
-            gru.append(gconv(hx, P[zr], ops.CONV_GATE_ZR, z_buf, out2=rhx[:, :c], add=ctx[zr], hidden=hx[:, :c], gate_channels=c, prepare=True))
-            gru.append(gconv(rhx, P[q], ops.CONV_GATE_H, hx[:, :c], add=ctx[q], hidden=hx[:, :c], zgate=z_buf, prepare=True))
+            gru.append(gconv(hx, P[zr], ops.CONV_GATE_ZR, z_buf, out2=rhx[:, :c], add=ctx[zr], hidden=hx[:, :c], gate_channels=c, prepare=True, **vk))
+            gru.append(gconv(rhx, P[q], ops.CONV_GATE_H, hx[:, :c], add=ctx[q], hidden=hx[:, :c], zgate=z_buf, prepare=True, **vk))
         gru.append(c3('fh1', hx[:, :c], fh_buf))
         gru.append(ops.flow_update(fh_buf, fh.conv2.weight, fh.conv2.bias.detach(), coords1, coords1, flow_out=flow, dst1=hx[:, 2 * c - 2:],
-                                   dst2=rhx[:, 2 * c - 2:], prepare=True))
-        L = SimpleNamespace(flo=flo, c1=P['convc1_1x1'](corr, ops.CONV_RELU, cor, prepare=True, x3=CONV_BF16X3), c2=c3('convc2', cor, cat_buf[:, :192]),
-                            f1=ops.stem_conv(flow, P['convf1'], bias=e.convf1.bias.detach(), relu=True, div=1.0, mul=1.0, sub=0.0, out=flo, prepare=True),
+                                   dst2=rhx[:, 2 * c - 2:], prepare=True, **vk))
+        L = SimpleNamespace(flo=flo, vk=vk, c1=P['convc1_1x1'](corr, ops.CONV_RELU, cor, prepare=True, x3=CONV_BF16X3, **vk), c2=c3('convc2', cor, cat_buf[:, :192]),
+                            f1=ops.stem_conv(flow, P['convf1'], bias=e.convf1.bias.detach(), relu=True, div=1.0, mul=1.0, sub=0.0, out=flo, prepare=True, **vk),
                             f2=c3('convf2', flo, cat_buf[:, 192:]), cv=c3('conv', cat_buf, hx[:, 128:254], rhx[:, 128:254]), gru=gru)
         if pyr is not None:
-            L.lookup, L.lookup_c1 = pyr.lookup(coords1, out=corr, prepare=True), None
+            # (pad_maps: the pyramid and the taps keep the true (h8, w8); coords and the 324 channels live in the padded maps)
+            L.lookup, L.lookup_c1 = pyr.lookup(coords1, out=corr, prepare=True, **({} if valid is None else dict(map_size=tuple(hx.shape[-2:])))), None
             n_wgs = hx.shape[0] * -(-(hx.shape[2] * -(-hx.shape[3] // 8)) // 8)
-            if not alt and LOOKUP_FUSED and not CONV_BF16X3 and n_wgs <= LOOKUP_FUSED_MAX_WGS and ops.PackedLookupConv.supported(pyr.levels, pyr.radius, pyr.w8):
+            if valid is None and not alt and LOOKUP_FUSED and not CONV_BF16X3 and n_wgs <= LOOKUP_FUSED_MAX_WGS and ops.PackedLookupConv.supported(pyr.levels, pyr.radius, pyr.w8):
                 # (convc1 in the fused kernel's layout: made when a pass first takes this route, kept while convc1 stays as it is)
                 pl = _cached(self, '_lookup_packed', _wkey(e.convc1.weight, e.convc1.bias), lambda: ops.PackedLookupConv(e.convc1.weight, e.convc1.bias))
                 L.lookup_c1 = pyr.lookup_conv1x1(coords1, pl, cor, relu=True, prepare=True)
@@ -683,7 +703,7 @@ class BasicUpdateBlock(nn.Module):
             w2, b2 = (0.25 * c2.weight).detach(), (0.25 * c2.bias).detach()
             return pw, w2, b2, ops.Conv1x1(w2, b2) if c2.weight.is_cuda else None
         pw, w2, b2, p2 = _cached(self, '_mask_packed', (_wkey(*mp), x3, w24, _switches()), pack)
-        if pw is not None and not torch.is_grad_enabled() and hh % 2 == 0 and ww % 2 == 0:      # (net may be a channel slice: hx[:, :128])
+        if pw is not None and not torch.is_grad_enabled() and hh % 2 == 0 and ww % 2 == 0:      # (net may be a channel slice: hx[:, :128]; pad_maps: of a padded map)
             t = ops.conv_wino(net, pw, ops.CONV_RELU, torch.empty(net.shape[0], c1.out_channels, hh, ww, device=net.device))
         else:
             t = ops.conv_direct(net, c1.weight, c1.bias, 1, 1, relu=True)
@@ -711,6 +731,10 @@ class RAFT(nn.Module):
         # (ops.AltCorr, csrc/corr_alt.hip).  Opt-in, f32 only.
         self.alternate_corr = bool(config.get('alternate_corr', False))
         self._check_alternate_corr()
+        # ``pad_maps`` (opt-in): at 1/8 maps the tuned kernels refuse -- odd heights, rows that are not whole 16-byte quads -- the update loop runs
+        # on maps zero-padded to padded_size(h8, w8) instead of on the generic convolution; the encoders keep the generic route there.
+        self.pad_maps = bool(config.get('pad_maps', False))
+        self._check_pad_maps()
         self.iters = int(config.get('iters', 12))
         self.hidden_dim = self.context_dim = 128
         self.corr_levels, self.corr_radius = 4, 4
@@ -739,6 +763,20 @@ class RAFT(nn.Module):
         if self.alternate_corr and (self.mixed_precision or CORR_BF16X3 or CONV_BF16X3):
             raise ops._lib.RpeError('RAFT: alternate_corr is f32 only -- not with mixed_precision, CORR_BF16X3 or CONV_BF16X3')
 
+    def _check_pad_maps(self):
+        """The valid-extent entry points exist for the f32 Winograd / GEMM kernels only: pad_maps is refused together with the bf16x3 variant of
+        the convolutions and without WINOGRAD (at construction, and at every pass for the module-level switches)."""
+        if (self.pad_maps or PAD_MAPS) and (CONV_BF16X3 or not WINOGRAD):
+            raise ops._lib.RpeError('RAFT: pad_maps runs on the f32 Winograd kernels -- not with CONV_BF16X3 (X3_GRU), not without WINOGRAD')
+
+    def _padded(self, h8, w8):
+        """padded_size(h8, w8) when this pass runs its update loop on padded maps, else None (flag off, or a map the kernels take as it is)."""
+        if not (self.pad_maps or PAD_MAPS):
+            return None
+        self._check_pad_maps()
+        hp, wp = padded_size(h8, w8)
+        return None if (hp, wp) == (h8, w8) else (hp, wp)
+
     def _pyramid(self, b, h8, w8, device):
         p = self._pyr
         if self.alternate_corr:
@@ -753,25 +791,32 @@ class RAFT(nn.Module):
             self._pyr.x3 = x3
         return self._pyr
 
-    def _workspace(self, n, h8, w8, device):
+    def _workspace(self, n, h8, w8, device, padded=None):
         """Activation buffers that live INSIDE a forward pass -- (h | motion | flow), (r*h | motion | flow), z, the motion
         encoder's concat buffer, the lookup output and the four context terms -- allocated once per (batch, map, device):
         the prepared launch descriptors of the GRU loop are keyed on these addresses, so they are built once and hit on
         every later pass (and nothing from a previous pass stays pinned besides this one set).  Single-stream use, like
-        the rest of the module; tensors handed back to the caller (flows, hidden, context) are always fresh."""
-        key = (n, h8, w8, str(device))
+        the rest of the module; tensors handed back to the caller (flows, hidden, context) are always fresh.
+        ``padded`` = (hp, wp) (pad_maps): every buffer is a ZERO-FILLED (hp, wp) map of which (h8, w8) is content (``valid``), plus padded
+        copies of the context features and of a warm start's flow_init.  Invariant: whatever a tuned kernel reads as a convolution input is
+        exactly zero outside the content at every launch -- the lookup and the copies in write the content only, every convolution of the
+        loop stores zero outside it (the valid-extent entry points)."""
+        key = (n, h8, w8, str(device), padded)
         if self._ws is None:
             self._ws = {}
         if key not in self._ws:
             if len(self._ws) >= 2:                             # a tracker alternates between two shapes at most (batch n / 2n)
                 self._ws.pop(next(iter(self._ws)))
             c = self.hidden_dim
-            e = lambda ch: torch.empty(n, ch, h8, w8, device=device)
+            mh, mw = (h8, w8) if padded is None else padded
+            e = lambda ch: (torch.empty if padded is None else torch.zeros)(n, ch, mh, mw, device=device)
             self._ws[key] = dict(hx=e(2 * c), rhx=e(2 * c), z=e(c), cat=e(2 * c),
                                  corr=e(self.corr_levels * (2 * self.corr_radius + 1) ** 2),
                                  ctx=dict(zr1=e(2 * c), q1=e(c), zr2=e(2 * c), q2=e(c)),
-                                 coords0=coords_grid(n, h8, w8, device), coords1=e(2), flow=e(2),
-                                 zero2=torch.zeros(n, 2, h8, w8, device=device))
+                                 coords0=coords_grid(n, mh, mw, device), coords1=e(2), flow=e(2),
+                                 zero2=torch.zeros(n, 2, mh, mw, device=device), valid=None if padded is None else (h8, w8))
+            if padded is not None:
+                self._ws[key].update(inp=e(c), finit=e(2))
         return self._ws[key]
 
     def _loop_program(self, pyr, ws, iters, side):
@@ -858,8 +903,18 @@ class RAFT(nn.Module):
         else:
             pyr.build(fmap1.float(), fmap2.float(), fp16_features=self.mixed_precision, bf16x3=(CORR_BF16X3 or CONV_BF16X3) and not self.mixed_precision)
         hx, rhx = ws['hx'], ws['rhx']
-        ops.copy_planes(cnet[:, :c], hx[:, :c])
-        ctx = self.update_block.context_terms(cnet[:, c:], out=ws['ctx'] if fused else None)      # (fused: written into the persistent buffers)
+        if ws['valid'] is not None:
+            # pad_maps: net, inp and flow_init go into the zero-padded maps by one strided copy each; the context terms are computed on the
+            # padded inp (their padding holds the bias, which only the gate epilogues add -- and those store zero there)
+            h8, w8 = ws['valid']
+            ops.copy_rect(cnet[:, :c], hx[:, :c], h8, w8)
+            ops.copy_rect(cnet[:, c:], ws['inp'], h8, w8)
+            ctx = self.update_block.context_terms(ws['inp'], out=ws['ctx'])
+            if flow_init is not None:
+                flow_init = ops.copy_rect(flow_init, ws['finit'], h8, w8)       # (coords1's padding becomes the grid, the flow's stays zero)
+        else:
+            ops.copy_planes(cnet[:, :c], hx[:, :c])
+            ctx = self.update_block.context_terms(cnet[:, c:], out=ws['ctx'] if fused else None)      # (fused: written into the persistent buffers)
         if fused and flow_init is not None:
             ops.flow_seed(flow_init, coords_out=ws['coords1'], flow_out=ws['flow'], dst1=hx[:, 2 * c - 2:], dst2=rhx[:, 2 * c - 2:])
         elif fused:
@@ -871,6 +926,11 @@ class RAFT(nn.Module):
 
     def _prediction(self, flow, hx, upsample):
         """What forward() returns for the 1/8 ``flow``: mask head on the hidden state + convex x8 up-sampling, or a copy of the flow."""
+        valid = None if self._ws is None else next((w['valid'] for w in self._ws.values() if w['hx'] is hx), None)
+        if valid is not None:                                     # pad_maps: the heads read the padded maps and write the true-size flow
+            if upsample:
+                return ops.upsample_convex(flow, self.update_block.up_mask(hx[:, :self.hidden_dim]), size=valid)
+            return ops.copy_rect(flow, torch.empty(flow.shape[0], 2, *valid, device=flow.device), *valid)
         if upsample:
             return ops.upsample_convex(flow, self.update_block.up_mask(hx[:, :self.hidden_dim]))
         return ops.copy_planes(flow, torch.empty_like(flow))
@@ -881,6 +941,9 @@ class RAFT(nn.Module):
         c = self.hidden_dim
         hx, flow = ws['hx'], ws['flow']
         pred = self._prediction(flow, hx, upsample)
+        if ws['valid'] is not None:                               # pad_maps: hidden state and 1/8 flow come out cropped and contiguous
+            fresh = lambda ch: torch.empty(hx.shape[0], ch, *ws['valid'], device=hx.device)
+            return pred, ops.copy_rect(hx[:, :c], fresh(c), *ws['valid']), ops.copy_rect(flow, fresh(2), *ws['valid']) if ret_lowres else None
         h_buf = ops.copy_planes(hx[:, :c], torch.empty(hx.shape[0], c, hx.shape[2], hx.shape[3], device=hx.device))
         low = ops.copy_planes(flow, torch.empty_like(flow)) if ret_lowres else None
         return pred, h_buf, low
@@ -912,8 +975,8 @@ class RAFT(nn.Module):
             return None                                               # (the call-by-call route raises what needs raising)
         recorded, wkey = _recording(self, self.update_block)
         pyr = self._pyramid(N, h8, w8, dev)
-        ws = self._workspace(N, h8, w8, dev)
-        key = (N, h8, w8, dev.index, ops.raw_stream(), iters, upsample, self.mixed_precision, self.alternate_corr, _switches(),
+        ws = self._workspace(N, h8, w8, dev, self._padded(h8, w8))
+        key = (N, h8, w8, dev.index, ops.raw_stream(), iters, upsample, self.mixed_precision, self.alternate_corr, self.pad_maps, _switches(),
                pyr.buf.data_ptr(), ws['hx'].data_ptr(), wkey)
         if flow_init is not None or ret_lowres:                       # (a cold pass keeps the key it always had)
             key += ('warm' if flow_init is not None else 'cold', ret_lowres)
@@ -982,14 +1045,15 @@ class RAFT(nn.Module):
                                  f'{flow_init.dtype} {tuple(flow_init.shape)} on {flow_init.device}')
             flow_init = flow_init.contiguous()
         ub = self.update_block
-        P = ub.packed_convs(w8)
+        padded = self._padded(h8, w8)                          # pad_maps: the loop's maps, when the tuned kernels refuse (h8, w8)
+        P = ub.packed_convs(w8 if padded is None else padded[1])
         fused = P is not None
         if fused and FRAME_OPLISTS and LOOP_OPLIST and not all_flows and N <= FRAME_OPLISTS_MAX_IMAGES and LOOKUP_EVENT_SINK is None:
             r = self._forward_recorded(fmap1, fmap2, cnet, iters, upsample, flow_init, ret_lowres)
             if r is not None:
                 return r
         pyr = self._pyramid(N, h8, w8, dev)
-        ws = self._workspace(N, h8, w8, dev)
+        ws = self._workspace(N, h8, w8, dev, padded)
         ctx = self._begin(pyr, ws, fmap1, fmap2, cnet, fused, flow_init)
         hx, corr = ws['hx'], ws['corr']                     # hx = (h | motion | flow)
         h_buf = torch.empty(N, c, h8, w8, device=dev)         # returned to the caller: fresh
@@ -1024,13 +1088,16 @@ class RAFT(nn.Module):
                     stream.wait_event(ev_flow)
                     ub.encoder.flow_branch(flow, P, ub.launchers(ws))
                     done.record()
-            pyr.lookup(coords1, out=corr)
+            pyr.lookup(coords1, out=corr, **({} if padded is None else dict(map_size=padded)))
             if not fused:
                 flow = flow_init if itr == 0 and flow_init is not None else coords1 - coords0
             coords1 = ub.step(ws, ctx, flow, coords1, h_buf, flow_branch_done=done)
             if all_flows or itr == iters - 1:
                 lowres = flow if fused else coords1 - coords0
                 flow_predictions.append(self._prediction(lowres, hx, upsample) if upsample or fused else lowres)
+        if padded is not None:
+            ops.copy_rect(hx[:, :c], h_buf, h8, w8)
+            return (flow_predictions, h_buf, inp) + ((ops.copy_rect(flow, torch.empty(N, 2, h8, w8, device=dev), h8, w8),) if ret_lowres else ())
         ops.copy_planes(hx[:, :c], h_buf)
         if ret_lowres:
             return flow_predictions, h_buf, inp, ops.copy_planes(flow, torch.empty_like(flow)) if fused else coords1 - coords0
