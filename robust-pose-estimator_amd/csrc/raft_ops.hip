@@ -110,6 +110,9 @@ __global__ __launch_bounds__(256) void k_copy_planes(const float* __restrict__ s
 //   y = norm(x + bias[c]);  if (relu) y = max(y, 0);  if (residual) y = max(residual + y, 0)
 // Instance norm (fnet): one workgroup per (b, c) plane, mean and biased variance by two passes over the plane (the
 // re-reads hit L2: a plane is <= 328 KB), eps inside the square root as torch.nn.InstanceNorm2d does.
+// Both passes work on v - K, K = the plane's first value (x[0] + bias): the difference of two plane values is exact or nearly so, where a
+// plain float32 sum of 16384 values near 1e4 is off by ~1e-3 of a standard deviation and a constant plane (variance 0, invstd =
+// 1/sqrt(eps) = 316) came out as +-1e-3 instead of 0.  The mean is never formed: y = ((v - K) - mean(v - K)) * invstd.
 __global__ __launch_bounds__(512) void k_instnorm_act(const float* __restrict__ x, const float* __restrict__ bias, int c, int hw,
                                                       float eps, int relu, const float* __restrict__ residual, float* __restrict__ out) {
     const int plane = blockIdx.x;                      // b * c + ch
@@ -131,19 +134,23 @@ __global__ __launch_bounds__(512) void k_instnorm_act(const float* __restrict__ 
         __syncthreads();
         return bc;
     };
+    __shared__ float kc;                               // the pivot, read once and handed round through LDS: out may be x (in place), and
+    if (threadIdx.x == 0) kc = xp[0] + bv;             // no thread may read x[0] again after thread 0 has overwritten it
+    __syncthreads();
+    const float K = kc;
     float acc = 0.0f;
-    if (v4) for (int i = threadIdx.x; i < n4; i += blockDim.x) { float4 v = ((const float4*)xp)[i]; acc += (v.x + bv) + (v.y + bv) + (v.z + bv) + (v.w + bv); }
-    else for (int i = threadIdx.x; i < hw; i += blockDim.x) acc += xp[i] + bv;
-    const float mean = block_sum(acc) / (float)hw;
+    if (v4) for (int i = threadIdx.x; i < n4; i += blockDim.x) { float4 v = ((const float4*)xp)[i]; acc += ((v.x + bv) - K) + ((v.y + bv) - K) + ((v.z + bv) - K) + ((v.w + bv) - K); }
+    else for (int i = threadIdx.x; i < hw; i += blockDim.x) acc += (xp[i] + bv) - K;
+    const float mean = block_sum(acc) / (float)hw;     // of v - K
     acc = 0.0f;
     if (v4) for (int i = threadIdx.x; i < n4; i += blockDim.x) {
         float4 v = ((const float4*)xp)[i];
-        float a = v.x + bv - mean, b = v.y + bv - mean, cc = v.z + bv - mean, d = v.w + bv - mean;
+        float a = ((v.x + bv) - K) - mean, b = ((v.y + bv) - K) - mean, cc = ((v.z + bv) - K) - mean, d = ((v.w + bv) - K) - mean;
         acc += a * a + b * b + cc * cc + d * d;
-    } else for (int i = threadIdx.x; i < hw; i += blockDim.x) { float a = xp[i] + bv - mean; acc += a * a; }
+    } else for (int i = threadIdx.x; i < hw; i += blockDim.x) { float a = ((xp[i] + bv) - K) - mean; acc += a * a; }
     const float invstd = 1.0f / sqrtf(block_sum(acc) / (float)hw + eps);
     auto fin = [&](float v, float r) -> float {
-        float y = (v + bv - mean) * invstd;
+        float y = (((v + bv) - K) - mean) * invstd;
         if (relu) y = y < 0.0f ? 0.0f : y;
         if (rp) { y = r + y; y = y < 0.0f ? 0.0f : y; }
         return y;
@@ -424,14 +431,17 @@ __global__ __launch_bounds__(256) void k_upsample_convex(const float* __restrict
             float m[9], mx = -INFINITY;
 #pragma unroll
             for (int k = 0; k < 9; ++k) { m[k] = mb[(size_t)(k * 64 + i * 8 + j) * mp]; mx = fmaxf(mx, m[k]); }
-            float sum = 0.0f;
+            // The softmax and the nine products are evaluated in double and rounded once.  8 * flow reaches 100 and more: there one float32 ulp
+            // of expf in two weights of opposite flow is 2.4e-5 and a float32 sum of nine terms adds as much (torch's float32 operator is
+            // off by 2.8e-5 against float64) -- more than the 2e-5 this kernel is held to.  (-Inf, +Inf and NaN logits behave as in float32.)
+            double e[9], sum = 0.0;
 #pragma unroll
-            for (int k = 0; k < 9; ++k) { m[k] = expf(m[k] - mx); sum += m[k]; }
-            float ax = 0.0f, ay = 0.0f;
+            for (int k = 0; k < 9; ++k) { e[k] = exp((double)m[k] - (double)mx); sum += e[k]; }
+            double ax = 0.0, ay = 0.0;
 #pragma unroll
-            for (int k = 0; k < 9; ++k) { float p = m[k] / sum; ax += p * fx[k]; ay += p * fy[k]; }
+            for (int k = 0; k < 9; ++k) { ax += e[k] * (double)fx[k]; ay += e[k] * (double)fy[k]; }
             const size_t o = (size_t)(8 * y + i) * W + 8 * x + j;
-            ox[o] = ax; oy[o] = ay;
+            ox[o] = (float)(ax / sum); oy[o] = (float)(ay / sum);
         }
     }
 }

@@ -248,7 +248,8 @@ def test_full_size_lookup_properties(rpe):
 def test_flow_head_last_layer(rpe):
     from rpe_amd import ops
     torch.manual_seed(5)
-    # widths that are a multiple of 4 take the four-pixels-per-thread kernel, the others the one-pixel kernel
+    # all of these run the one-pixel kernel: the four-pixels-per-thread kernel needs a width that is a multiple of 4 AND a launch of at
+    # least 256 workgroups (test_flow_head_kernels_agree_bitwise, tests/test_gpu_raft_ops_edges.py)
     for (b, c, h, w) in ((2, 256, 64, 80), (1, 20, 13, 37), (3, 37, 9, 12), (1, 256, 44, 48), (2, 5, 3, 4)):
         x = torch.randn(b, c, h, w)
         wt = torch.randn(2, c, 3, 3) * 0.05
