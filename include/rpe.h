@@ -61,8 +61,9 @@ const char *rpe_version(void);
  *   of the stride-2 3x3 layers), and rpe_corr_alt_bytes / rpe_corr_alt_prepare / rpe_corr_alt_lookup with RPE_OP_CORR_ALT_PREPARE /
  *   RPE_OP_CORR_ALT_LOOKUP (correlation without the all-pairs volume), and the entry points of the update loop on zero-padded maps:
  *   rpe_conv_wino_v, rpe_conv_wino24_v, rpe_conv_wino1d_v, rpe_conv1x1_v (struct rpe_conv_desc_v), rpe_stem_conv_v, rpe_conv3x3_to2_flow_v,
- *   rpe_corr_lookup_ex, rpe_corr_alt_lookup_ex, rpe_upsample_convex_ex, rpe_copy_rect with RPE_OP_* kinds 22-31; the next RPE_ABI_MINOR bump
- *   counts them and rpe_conv_wino24*. */
+ *   rpe_corr_lookup_ex, rpe_corr_alt_lookup_ex, rpe_upsample_convex_ex, rpe_copy_rect with RPE_OP_* kinds 22-31, and the entry points of the
+ *   encoders on zero-padded maps: rpe_enc_conv_wino_v, rpe_enc_conv_wino24_v, rpe_enc_conv_s2_v, rpe_enc_conv_s2_m96_v, rpe_instnorm_apply_v
+ *   with RPE_OP_* kinds 34-38 (32 and 33 are the event ops); the next RPE_ABI_MINOR bump counts them and rpe_conv_wino24*. */
 #define RPE_ABI_VERSION 5
 #define RPE_ABI_MINOR 4
 int rpe_abi_minor(void);
@@ -464,12 +465,29 @@ typedef struct rpe_conv_desc {
  * that of the plain entry point on the same map, bit for bit; h_valid == d.h and w_valid == d.w IS the plain entry point's launch.
  * h_valid > d.h or w_valid > d.w (or < 1), or a NULL pointer -> RPE_E_BADARG.  Supported: what the update loop uses -- rpe_conv_wino_v /
  * rpe_conv_wino24_v with the plain epilogue (bias, ReLU, out2; w % 4 == 0), rpe_conv_wino1d_v with every mode, rpe_conv1x1_v; anything
- * else the plain entry point takes -> RPE_E_UNSUPPORTED.  (core/RAFT/core/update.py's layers at any img_size, infer_f2f.yaml:13.) */
+ * else the plain entry point takes -> RPE_E_UNSUPPORTED.  (core/RAFT/core/update.py's layers at any img_size, infer_f2f.yaml:13.)
+ * The encoders' layers use the same struct through entry points of their own, rpe_enc_conv_wino_v, rpe_enc_conv_wino24_v, rpe_enc_conv_s2_v
+ * and rpe_enc_conv_s2_m96_v (below), which also take scale, residual, stats and pre_norm. */
 typedef struct rpe_conv_desc_v { rpe_conv_desc d; int h_valid, w_valid; } rpe_conv_desc_v;
 int rpe_conv_wino_v(const rpe_conv_desc_v *desc, void *stream);
 int rpe_conv_wino24_v(const rpe_conv_desc_v *desc, void *stream);
 int rpe_conv_wino1d_v(const rpe_conv_desc_v *desc, void *stream);
 int rpe_conv1x1_v(const rpe_conv_desc_v *desc, void *stream);
+/* The ENCODERS' valid-extent forms (core/RAFT/core/extractor.py's layer2, layer3 at any img_size), the same struct rpe_conv_desc_v:
+ *   rpe_enc_conv_wino_v / rpe_enc_conv_wino24_v: rpe_conv_wino / rpe_conv_wino24 with every descriptor field the encoders use -- bias,
+ *     scale, residual, stats, pre_norm, LINEAR / RELU -- on a map with w % 4 == 0 and 16-byte aligned slices.  Beside the zero stored
+ *     outside the extent: the `stats` records cover the outputs inside it only (a tile wholly outside leaves the record (0, 0, 0), which
+ *     rpe_instnorm_finalize skips), and with `pre_norm` the input counts as zero outside the extent AFTER normalising
+ *     (relu((0 - mean) / std) is not zero), so the result inside is that of the convolution on the cropped, normalised input.
+ *   rpe_enc_conv_s2_v / rpe_enc_conv_s2_m96_v: what rpe_conv_fused / rpe_conv_fused_m96 do at stride 2 (3x3 pad 1, the 1x1 shortcut; bias /
+ *     scale, stats, LINEAR / RELU); h_valid x w_valid is the extent of the OUTPUT map (d.h / 2 x d.w / 2).  The records (one per 32
+ *     output pixels) count and sum the pixels inside it; the two tile classes stay bit-identical.
+ * Extent == map is literally the plain entry point's launch (same kernel, same bits, records included).  Extent beyond the map or < 1,
+ * or a NULL pointer -> RPE_E_BADARG (checked before anything is dereferenced); a field the form does not take -> RPE_E_UNSUPPORTED. */
+int rpe_enc_conv_wino_v(const rpe_conv_desc_v *desc, void *stream);
+int rpe_enc_conv_wino24_v(const rpe_conv_desc_v *desc, void *stream);
+int rpe_enc_conv_s2_v(const rpe_conv_desc_v *desc, void *stream);
+int rpe_enc_conv_s2_m96_v(const rpe_conv_desc_v *desc, void *stream);
 /* number of floats of the packed form of a (cout, cin, kh, kw) weight tensor (0 on bad arguments) */
 size_t rpe_conv_packed_floats(int cout, int cin, int kh, int kw);
 /* weight (cout, cin, kh, kw) contiguous -> packed (tap-major 16-channel steps, output channels padded to 128) */
@@ -586,6 +604,12 @@ int rpe_instnorm_apply_ex(const float *x, const float *partials, int tiles, int 
 /* mean_inv (b,c,2) = (mean, 1/sqrt(var + eps)) of each plane from the same partial sums: the `pre_norm` input of the
  * next rpe_conv_fused, which then normalises its input on the fly (no separate pass for norm1 + ReLU of a ResidualBlock). */
 int rpe_instnorm_finalize(const float *partials, int tiles, int b, int c, int hw, float eps, float *mean_inv, void *stream);
+/* rpe_instnorm_apply_ex's pass (tiles == 0 form: mean_inv (b,c,2) from rpe_instnorm_finalize, whose merge weighs every record by its
+ * own count and so takes the valid-extent records as they are) on a zero-padded (h, w) map with h_valid x w_valid of content: the same
+ * bits inside the extent, ZERO outside it (relu((0 - mean) * inv) is not zero).  relu bits, residual and residual_mean_inv as there; out
+ * may alias x.  w % 4 == 0, 16-byte aligned tensors, else RPE_E_UNSUPPORTED; an extent beyond the map or < 1, NULL -> RPE_E_BADARG. */
+int rpe_instnorm_apply_v(const float *x, const float *mean_inv, int b, int c, int h, int w, int h_valid, int w_valid, int relu,
+                         const float *residual, const float *residual_mean_inv, float *out, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Prepared launch lists -- replace the HOST loop around the kernels above: RAFT.forward's `for itr in range(iters)` over lookup ->
@@ -635,6 +659,11 @@ int rpe_instnorm_finalize(const float *partials, int tiles, int b, int c, int hw
 #define RPE_OP_COPY_RECT 31        /*       const rpe_copy_rect_args *                     */
 #define RPE_OP_EVENT_RECORD 32     /*       void *const * (address of a hipEvent_t handle; NULL handle = no-op) */
 #define RPE_OP_STREAM_WAIT 33      /*       void *const * (the same)                       */
+#define RPE_OP_ENC_CONV_WINO_V 34  /*       const rpe_conv_desc_v * -> rpe_enc_conv_wino_v */
+#define RPE_OP_ENC_CONV_WINO24_V 35 /*      const rpe_conv_desc_v * -> rpe_enc_conv_wino24_v */
+#define RPE_OP_ENC_CONV_S2_V 36    /*       const rpe_conv_desc_v * -> rpe_enc_conv_s2_v   */
+#define RPE_OP_ENC_CONV_S2_M96_V 37 /*      const rpe_conv_desc_v * -> rpe_enc_conv_s2_m96_v */
+#define RPE_OP_INSTNORM_APPLY_V 38 /*       const rpe_instnorm_apply_v_args *              */
 typedef struct rpe_op {
     int kind;                      /* RPE_OP_*                                             */
     int stream;                    /* index into rpe_run_ops' streams[]                    */
@@ -682,6 +711,9 @@ typedef struct rpe_copy_rect_args {
     const float *src; long long src_batch_stride, src_plane_stride; int src_pitch; float *dst; long long dst_batch_stride, dst_plane_stride;
     int dst_pitch, b, c, h, w;
 } rpe_copy_rect_args;
+typedef struct rpe_instnorm_apply_v_args {
+    const float *x, *mean_inv; int b, c, h, w, h_valid, w_valid, relu; const float *residual, *residual_mean_inv; float *out;
+} rpe_instnorm_apply_v_args;
 /* streams: n_streams hipStream_t handles (NULL = the default stream).  failed_op may be NULL. */
 int rpe_run_ops(const rpe_op *ops, int n_ops, void *const *streams, int n_streams, int *failed_op);
 

@@ -129,6 +129,11 @@ class CopyRectArgs(_c.Structure):
                 ('dst_plane_stride', _ll), ('dst_pitch', _i), ('b', _i), ('c', _i), ('h', _i), ('w', _i)]
 
 
+class InstnormApplyVArgs(_c.Structure):
+    _fields_ = [('x', _vp), ('mean_inv', _vp), ('b', _i), ('c', _i), ('h', _i), ('w', _i), ('h_valid', _i), ('w_valid', _i), ('relu', _i),
+                ('residual', _vp), ('residual_mean_inv', _vp), ('out', _vp)]
+
+
 # RPE_OP_* of include/rpe.h
 OP_CONV_FUSED, OP_CONV_WINO, OP_CONV_WINO1D, OP_CONV1X1, OP_CONV_WINO_X3, OP_CONV_WINO1D_X3, OP_CONV1X1_X3 = 1, 2, 3, 4, 5, 6, 7
 OP_CORR_LOOKUP, OP_STEM_CONV, OP_FLOW_UPDATE, OP_COPY_PLANES, OP_INSTNORM_FINALIZE, OP_INSTNORM_APPLY, OP_UPSAMPLE_CONVEX, OP_CORR_BUILD = 8, 9, 10, 11, 12, 13, 14, 15
@@ -137,6 +142,7 @@ OP_CORR_ALT_PREPARE, OP_CORR_ALT_LOOKUP = 20, 21
 OP_CONV_WINO_V, OP_CONV_WINO24_V, OP_CONV_WINO1D_V, OP_CONV1X1_V, OP_STEM_CONV_V, OP_FLOW_UPDATE_V = 22, 23, 24, 25, 26, 27
 OP_CORR_LOOKUP_EX, OP_CORR_ALT_LOOKUP_EX, OP_UPSAMPLE_CONVEX_EX, OP_COPY_RECT = 28, 29, 30, 31
 OP_EVENT_RECORD, OP_STREAM_WAIT = 32, 33
+OP_ENC_CONV_WINO_V, OP_ENC_CONV_WINO24_V, OP_ENC_CONV_S2_V, OP_ENC_CONV_S2_M96_V, OP_INSTNORM_APPLY_V = 34, 35, 36, 37, 38
 # kind -> (entry point, argument struct) of every op a launch list carries (csrc/oplist.hip's run_one).  An entry point with an argument
 # struct takes its fields in order, then the stream; the rpe_conv_desc kinds take the descriptor by pointer, then the stream.
 LIST_OPS = {OP_CONV_FUSED: ('rpe_conv_fused', ConvDesc), OP_CONV_WINO: ('rpe_conv_wino', ConvDesc), OP_CONV_WINO1D: ('rpe_conv_wino1d', ConvDesc),
@@ -156,7 +162,16 @@ LIST_OPS = {OP_CONV_FUSED: ('rpe_conv_fused', ConvDesc), OP_CONV_WINO: ('rpe_con
             OP_STEM_CONV_V: ('rpe_stem_conv_v', StemConvVArgs), OP_FLOW_UPDATE_V: ('rpe_conv3x3_to2_flow_v', FlowUpdateVArgs),
             OP_CORR_LOOKUP_EX: ('rpe_corr_lookup_ex', CorrLookupExArgs), OP_CORR_ALT_LOOKUP_EX: ('rpe_corr_alt_lookup_ex', CorrAltLookupExArgs),
             OP_UPSAMPLE_CONVEX_EX: ('rpe_upsample_convex_ex', UpsampleConvexExArgs), OP_COPY_RECT: ('rpe_copy_rect', CopyRectArgs)}
-KIND_OF_ENTRY = {entry: kind for kind, (entry, _) in LIST_OPS.items()}
+# the kinds behind the two event ops: the encoders on zero-padded maps (RAFT's pad_encoders) -- the encoder epilogues, the stride-2 layers
+# and the normalising pass
+LIST_OPS_ENC = {OP_ENC_CONV_WINO_V: ('rpe_enc_conv_wino_v', ConvDesc), OP_ENC_CONV_WINO24_V: ('rpe_enc_conv_wino24_v', ConvDesc),
+            OP_ENC_CONV_S2_V: ('rpe_enc_conv_s2_v', ConvDesc), OP_ENC_CONV_S2_M96_V: ('rpe_enc_conv_s2_m96_v', ConvDesc),
+            OP_INSTNORM_APPLY_V: ('rpe_instnorm_apply_v', InstnormApplyVArgs)}
+# plain entry point -> its encoder valid-extent form (ops.conv_wino / conv_fused with ``enc_valid=``)
+ENC_FORM = {'rpe_conv_wino': 'rpe_enc_conv_wino_v', 'rpe_conv_wino24': 'rpe_enc_conv_wino24_v', 'rpe_conv_fused': 'rpe_enc_conv_s2_v',
+            'rpe_conv_fused_m96': 'rpe_enc_conv_s2_m96_v'}
+ALL_LIST_OPS = {**LIST_OPS, **LIST_OPS_ENC}           # every kind csrc/oplist.hip's run_one carries with an argument block
+KIND_OF_ENTRY = {entry: kind for kind, (entry, _) in ALL_LIST_OPS.items()}
 
 ABI_MINOR = 3              # RPE_ABI_MINOR of the single-map surfel entry points (rpe_surfel_*)
 ABI_MINOR_MANY = 4         # RPE_ABI_MINOR of rpe_surfel_*_many and rpe_pose_gate_chain_rows: the newest additions this binding calls
@@ -274,7 +289,7 @@ SIGNATURES = {
     'rpe_surfel_fuse_many': (_i, [_i, _SMP, _P64, _SMP, _P32, _P32, _i, _vp, _vp, _vp, _i, _i, _PVP, _PVP, _vp, _fl, _i, _i, _fl, _i, _vp,
                                   _vp]),
 }
-SIGNATURES.update({entry: (_i, ([_c.POINTER(ConvDesc)] if st is ConvDesc else [t for _, t in st._fields_]) + [_vp]) for entry, st in LIST_OPS.values()})
+SIGNATURES.update({entry: (_i, ([_c.POINTER(ConvDesc)] if st is ConvDesc else [t for _, t in st._fields_]) + [_vp]) for entry, st in ALL_LIST_OPS.values()})
 
 _lib = None
 

@@ -40,8 +40,11 @@
 // BN+1+n; row BN = O[-1] of the tile's first pixel), yi = 2y + dy - pad: the loader's aligned float4 (E,O,E,O of two
 // neighbouring outputs) is de-interleaved by the 4-byte LDS stores it needs anyway.  Taps: in[2x-1] = O[n-1], in[2x] =
 // E[n], in[2x+1] = O[n] -- plain row offsets again.
-template <int KW, int WM, bool ENC, int T, bool VERT, bool S2>
+// VALID (stride 2 with the encoder epilogue: rpe_enc_conv_s2_v): the output map is zero-padded with P.Hv x P.Wv of content; the epilogue
+// stores zero outside it (a select: NaN leaves as zero) and the statistics records count and sum the pixels inside it only.
+template <int KW, int WM, bool ENC, int T, bool VERT, bool S2, bool VALID = false>
 __global__ __launch_bounds__(256, 3) void k_conv_igemm(ConvP P) {
+    static_assert(!VALID || (S2 && ENC), "the valid-extent form exists for the stride-2 encoder layers");
     constexpr int WN = 4 / WM, WT = 32 * T, BM = WT * WM, BN = WT * WN, PW = VERT ? 0 : KW / 2;
     constexpr int VTX = 16, VTY = 8, VROWS = VTY + KW - 1;       // VERT patch: 16 x 8 pixels, VROWS staged rows of 16
     constexpr int KS = 20;
@@ -388,6 +391,13 @@ __global__ __launch_bounds__(256, 3) void k_conv_igemm(ConvP P) {
         float* outb = P.out + (size_t)bz * P.obs;
         float* out2b = EXTRA && P.out2 ? P.out2 + (size_t)bz * P.o2bs : nullptr;
         const bool relu = mode == RPE_CONV_RELU;
+        bool inx[T]; unsigned long long inmask[T];                // VALID: this lane's pixel of column block j lies inside the extent | the wave's ballot
+#pragma unroll
+        for (int j = 0; j < T; ++j) {
+            const int px = n0 + wn * WT + j * 32 + l31, py = px / W;
+            inx[j] = !VALID || (px < hw && py < P.Hv && px - py * W < P.Wv);
+            inmask[j] = VALID ? __ballot(inx[j]) : 0ull;
+        }
 #pragma unroll
         for (int i = 0; i < T; ++i) {
             const int row0 = wm * WT + i * 32 + 4 * lh;
@@ -436,15 +446,17 @@ __global__ __launch_bounds__(256, 3) void k_conv_igemm(ConvP P) {
                         for (int s2 = 0; s2 < NS; ++s2) {
                             const int vb = __builtin_bit_cast(int, vv[S2 ? s2 : 0]);
                             piv[s2] = __builtin_bit_cast(float, lh ? __builtin_amdgcn_readlane(vb, 32) : __builtin_amdgcn_readlane(vb, 0));
+                            if (VALID) piv[s2] = valid_pivot(vv[S2 ? s2 : 0], inmask[S2 ? s2 : 0], lh);
                             ssum[s2] = 0.0f; ssq[s2] = 0.0f;
                         }
                     }
 #pragma unroll
                     for (int j = 0; j < T; ++j) {
                         float v = vv[j];
-                        if (STATS) { const float dv = ok[j][r] ? v - piv[S2 ? j : 0] : 0.0f; ssum[S2 ? j : 0] += dv; ssq[S2 ? j : 0] = fmaf(dv, dv, ssq[S2 ? j : 0]); }
+                        if (STATS) { const float dv = (ok[j][r] && inx[j]) ? v - piv[S2 ? j : 0] : 0.0f; ssum[S2 ? j : 0] += dv; ssq[S2 ? j : 0] = fmaf(dv, dv, ssq[S2 ? j : 0]); }
                         if (relu) v = v < 0.0f ? 0.0f : v;
                         if (EXTRA && resb) { v = rv[j][r] + v; v = v < 0.0f ? 0.0f : v; }
+                        if (VALID) v = inx[j] ? v : 0.0f;
                         if (ok[j][r]) { outb[e[j][r]] = v; if (EXTRA && out2b) out2b[e[j][r]] = v; }
                     }
                     if (STATS) {                                 // sum over the 32 lanes that share this channel row
@@ -478,6 +490,7 @@ __global__ __launch_bounds__(256, 3) void k_conv_igemm(ConvP P) {
                         const int blk = (n0 + w2 * WT + s2 * 32) >> 5;
                         if (blk >= nrec) continue;
                         int nw = hw - blk * 32; nw = nw > 32 ? 32 : nw;                    // valid columns of the block (>= 1)
+                        if (VALID) nw = valid_before(blk * 32 + nw, W, P.Hv, P.Wv) - valid_before(blk * 32, W, P.Hv, P.Wv);   // (0: the record (0, 0, 0))
                         const float* rd = red + ((w2 * NS + s2) * BM + tid) * 3;
                         StatAcc A;
                         A.add_pivoted(nw, rd[0], rd[1], rd[2]);
@@ -711,7 +724,8 @@ static_assert(sizeof(rpe_conv_desc) == 200, "rpe_conv_desc layout is part of the
 
 // m96: stride-2 3x3 launches of 96 output channels run the 96-row tile class (conv_s2.hip; bit-identical, statistics records included)
 // when their epilogue is one it has; every other descriptor takes the route below either way.
-static int conv_fused(const rpe_conv_desc* d, void* stream, bool m96) {
+// hv, wv: the valid extent of the OUTPUT map (rpe_enc_conv_s2_v / _m96_v: stride 2 only); equal to it = the plain launch
+static int conv_fused(const rpe_conv_desc* d, void* stream, bool m96, int hv = 0, int wv = 0) {
     if (!conv_desc_present(d)) return RPE_E_BADARG;
     if (d->kh < 1 || !(d->kh & 1) || (d->kw != 1 && d->kw != 3 && d->kw != 5)) return RPE_E_UNSUPPORTED;
     if ((d->w & 3) || !aligned16(d->x, d->x_batch_stride)) return RPE_E_UNSUPPORTED;     // 16-B input loads
@@ -738,7 +752,20 @@ static int conv_fused(const rpe_conv_desc* d, void* stream, bool m96) {
         const bool small = conv_s2_small(d->cout, P.hw, d->b);
         if (d->stats && d->stats_tiles != 0 && d->stats_tiles != ceil_div(P.hw, 32)) return RPE_E_BADARG;
         // (whatever the launch size: the caller asks for this class where the launch fills the chip, raft.S2_M96_MIN_WGS)
-        if (m96 && d->kw == 3 && d->cout == 96 && !d->residual && !d->add && !d->out2) return conv_s2_m96_launch(P, d->b, s);
+        const bool valid = hv > 0 && (hv != P.H || wv != P.W);
+        P.Hv = hv; P.Wv = wv;
+        if (m96 && d->kw == 3 && d->cout == 96 && !d->residual && !d->add && !d->out2) return conv_s2_m96_launch(P, d->b, s, valid);
+        if (valid) {                                 // the same two tile classes, VALID
+            const dim3 g2(small ? t64 : t128, ceil_div(d->cout, small ? 64 : 128), d->b);
+            if (small) {
+                if (d->kw == 3) hipLaunchKernelGGL((k_conv_igemm<3, 2, true, 1, false, true, true>), g2, dim3(256), 0, s, P);
+                else hipLaunchKernelGGL((k_conv_igemm<1, 2, true, 1, false, true, true>), g2, dim3(256), 0, s, P);
+            } else {
+                if (d->kw == 3) hipLaunchKernelGGL((k_conv_igemm<3, 2, true, 2, false, true, true>), g2, dim3(256), 0, s, P);
+                else hipLaunchKernelGGL((k_conv_igemm<1, 2, true, 2, false, true, true>), g2, dim3(256), 0, s, P);
+            }
+            return rpe_check_launch();
+        }
         if (small) {
             dim3 g2(t64, ceil_div(d->cout, 64), d->b);
             if (d->kw == 3) hipLaunchKernelGGL((k_conv_igemm<3, 2, true, 1, false, true>), g2, dim3(256), 0, s, P);
@@ -777,6 +804,18 @@ static int conv_fused(const rpe_conv_desc* d, void* stream, bool m96) {
 extern "C" int rpe_conv_fused(const rpe_conv_desc* d, void* stream) { return conv_fused(d, stream, false); }
 extern "C" int rpe_conv_fused_m96(const rpe_conv_desc* d, void* stream) { return conv_fused(d, stream, true); }
 
+// The encoders' stride-2 layers (3x3 pad 1, the 1x1 shortcut) on zero-padded maps: what rpe_conv_fused / rpe_conv_fused_m96 do at stride 2
+// with bias / scale, stats and LINEAR / RELU, the valid extent given on the OUTPUT map (d.h / 2 x d.w / 2).  Extent == map: the plain launch.
+static int enc_conv_s2_v(const rpe_conv_desc_v* dv, void* stream, bool m96) {
+    if (!dv || !conv_desc_present(&dv->d)) return RPE_E_BADARG;
+    const rpe_conv_desc* d = &dv->d;
+    if (dv->h_valid < 1 || dv->w_valid < 1 || dv->h_valid > d->h / 2 || dv->w_valid > d->w / 2) return RPE_E_BADARG;
+    if (d->stride != 2 || !conv_linear_or_relu(d) || !conv_plain_only(d) || d->residual || d->pre_norm || d->out2) return RPE_E_UNSUPPORTED;
+    return conv_fused(d, stream, m96, dv->h_valid, dv->w_valid);
+}
+extern "C" int rpe_enc_conv_s2_v(const rpe_conv_desc_v* dv, void* stream) { return enc_conv_s2_v(dv, stream, false); }
+extern "C" int rpe_enc_conv_s2_m96_v(const rpe_conv_desc_v* dv, void* stream) { return enc_conv_s2_v(dv, stream, true); }
+
 extern "C" int rpe_conv_stats_tiles(int cout, int h, int w, int stride) {
     if (cout <= 0 || h <= 0 || w <= 0 || (stride != 1 && stride != 2)) return 0;
     if (stride == 2) return ceil_div((int64_t)(h / 2) * (w / 2), 32);  // one record per 32 output pixels, in either tile class
@@ -802,6 +841,54 @@ extern "C" int rpe_instnorm_apply_ex(const float* x, const float* partials, int 
 #endif
     if (tiles == 0) while (split < INA_MAXSPLIT && (long long)hw * 4 / (split * 2) >= INA_MINBYTES) split *= 2;
     hipLaunchKernelGGL(k_instnorm_apply, dim3(b * c * split), dim3(256), 0, (hipStream_t)stream, x, partials, tiles, c, hw, eps, relu, residual,
+                       residual_mean_inv, out, split);
+    return rpe_check_launch();
+}
+
+// The normalising pass on a zero-padded (h, w) map with (hv, wv) of content: k_instnorm_apply's arithmetic from given (mean, 1/std)
+// pairs inside the extent, zero outside it (relu((0 - mean) * inv) is not zero).  Each thread reads its quads before it writes them, so
+// ``out`` may be ``x``.
+__global__ __launch_bounds__(256) void k_instnorm_apply_v(const float* __restrict__ x, const float* __restrict__ mi, int h, int w, int hv, int wv, int relu,
+                                                          const float* residual, const float* __restrict__ res_mi, float* out, int split) {
+    const int plane = blockIdx.x / split, part = blockIdx.x % split;
+    const float mean = mi[(size_t)plane * 2], inv = mi[(size_t)plane * 2 + 1];
+    const size_t hw = (size_t)h * w;
+    const float4* xp = (const float4*)(x + plane * hw);
+    const float4* rp = residual ? (const float4*)(residual + plane * hw) : nullptr;
+    float4* op = (float4*)(out + plane * hw);
+    const bool rnorm = res_mi != nullptr;
+    const float rmean = rnorm ? res_mi[(size_t)plane * 2] : 0.0f, rinv = rnorm ? res_mi[(size_t)plane * 2 + 1] : 1.0f;
+    const bool yrelu = relu & 1, rrelu = !(relu & 2);
+    auto fin = [&](float v, float r, bool in) -> float {
+        float y = (v - mean) * inv;
+        if (yrelu) y = y < 0.0f ? 0.0f : y;
+        if (rp) {
+            if (rnorm) { r = (r - rmean) * rinv; if (rrelu) r = r < 0.0f ? 0.0f : r; }
+            y = r + y; y = y < 0.0f ? 0.0f : y;
+        }
+        return in ? y : 0.0f;                                     // a select: NaN outside the extent leaves as zero
+    };
+    const int w4 = w >> 2, n4all = h * w4;
+    const int per = (n4all + split - 1) / split;
+    const int n4 = (part + 1) * per < n4all ? (part + 1) * per : n4all;
+    for (int i = part * per + threadIdx.x; i < n4; i += blockDim.x) {
+        const int yy = i / w4, x0 = (i - yy * w4) * 4;
+        const bool rowin = yy < hv;
+        const float4 v = xp[i];
+        const float4 r = rp ? rp[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+        op[i] = make_float4(fin(v.x, r.x, rowin && x0 < wv), fin(v.y, r.y, rowin && x0 + 1 < wv), fin(v.z, r.z, rowin && x0 + 2 < wv),
+                            fin(v.w, r.w, rowin && x0 + 3 < wv));
+    }
+}
+
+extern "C" int rpe_instnorm_apply_v(const float* x, const float* mean_inv, int b, int c, int h, int w, int h_valid, int w_valid, int relu,
+                                    const float* residual, const float* residual_mean_inv, float* out, void* stream) {
+    if (!x || !mean_inv || !out || b <= 0 || c <= 0 || h <= 0 || w <= 0 || (residual_mean_inv && !residual)) return RPE_E_BADARG;
+    if (h_valid < 1 || w_valid < 1 || h_valid > h || w_valid > w) return RPE_E_BADARG;
+    if ((w & 3) || (relu & ~3) || !aligned16(x, 0) || !aligned16(out, 0) || !aligned16(residual, 0)) return RPE_E_UNSUPPORTED;
+    int split = 1;
+    while (split < 16 && (long long)h * w * 4 / (split * 2) >= 16384) split *= 2;
+    hipLaunchKernelGGL(k_instnorm_apply_v, dim3(b * c * split), dim3(256), 0, (hipStream_t)stream, x, mean_inv, h, w, h_valid, w_valid, relu, residual,
                        residual_mean_inv, out, split);
     return rpe_check_launch();
 }

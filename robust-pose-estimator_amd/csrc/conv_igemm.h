@@ -24,7 +24,22 @@ struct ConvP {
     const float* res; long long rbs;          // residual added after the activation, then ReLU again (encoder blocks)
     float* stats;                             // [b][cout][tiles_n][2] partial (sum, sum of squares) of v, or null
     const float* pre;                         // [b][cin][2] (mean, 1/std) or null: the input is normalised + ReLU'd as it is staged
+    int Hv, Wv;                               // valid extent of the OUTPUT map (the VALID stride-2 instantiations: rpe_enc_conv_s2_v)
 };
+
+// VALID: the pixels among the flattened pixels [0, p) of a map of row length W that lie inside its valid extent Hv x Wv
+__device__ __forceinline__ int valid_before(int p, int W, int Hv, int Wv) {
+    const int y = p / W, x = p - y * W;
+    return y < Hv ? y * Wv + (x < Wv ? x : Wv) : Hv * Wv;
+}
+// VALID: the statistics pivot of a 32-lane half = the value of its first lane inside the extent (``inside`` = the wave's ballot; a half
+// wholly outside takes its first lane, and its record's count is zero)
+__device__ __forceinline__ float valid_pivot(float v, unsigned long long inside, int lh) {
+    const unsigned lo = (unsigned)inside, hi = (unsigned)(inside >> 32);
+    const int ilo = lo ? __builtin_ctz(lo) : 0, ihi = 32 + (hi ? __builtin_ctz(hi) : 0);
+    const int vb = __builtin_bit_cast(int, v);
+    return __builtin_bit_cast(float, lh ? __builtin_amdgcn_readlane(vb, ihi) : __builtin_amdgcn_readlane(vb, ilo));
+}
 
 
 // Sum over each 32-lane half of the wave with DPP moves (VALU rate, no LDS traffic): quad butterflies, row half-mirror,
@@ -39,4 +54,4 @@ __device__ __forceinline__ float half_wave_sum(float v) {
 }
 
 // conv_s2.hip: the 96-row class of the stride-2 3x3 layers (cout == 96, no residual / addend / second output); P as rpe_conv_fused fills it
-int conv_s2_m96_launch(const ConvP& P, int batch, hipStream_t stream);
+int conv_s2_m96_launch(const ConvP& P, int batch, hipStream_t stream, bool valid = false);

@@ -16,6 +16,8 @@
 #include "conv_igemm.h"
 #include <type_traits>
 
+// VALID: as k_conv_igemm's -- zero stored outside the valid extent P.Hv x P.Wv of the output map, statistics over the pixels inside it
+template <bool VALID>
 __global__ __launch_bounds__(256, 2) void k_conv_s2_m96(ConvP P) {
     constexpr int BM = 96, BN = 128, KS = 20, NLB = BN / 32, KW = 3;
     __shared__ __attribute__((aligned(16))) float As[2][BM][KS];
@@ -163,6 +165,9 @@ __global__ __launch_bounds__(256, 2) void k_conv_s2_m96(ConvP P) {
     static_assert(4 * 3 <= 2 * KS, "statistics scratch must fit the weights tiles");
     const int px = n0 + wv * 32 + l31;
     const bool pok = px < hw;
+    const int py = px / W;
+    const bool inx = !VALID || (pok && py < P.Hv && px - py * W < P.Wv);
+    const unsigned long long inmask = VALID ? __ballot(inx) : 0ull;
     float* outb = P.out + (size_t)bz * P.obs;
     const bool relu = P.mode == RPE_CONV_RELU;
     auto epilogue = [&](auto statsc) {
@@ -179,8 +184,9 @@ __global__ __launch_bounds__(256, 2) void k_conv_s2_m96(ConvP P) {
                     float v = fmaf(acc[i][rb + r], s2.x, s2.y);
                     if (STATS) {                                 // k_conv_igemm's pivoted record of this 32-pixel block (see there)
                         const int vb = __builtin_bit_cast(int, v);
-                        const float piv = __builtin_bit_cast(float, lh ? __builtin_amdgcn_readlane(vb, 32) : __builtin_amdgcn_readlane(vb, 0));
-                        const float dv = pok ? v - piv : 0.0f;
+                        float piv = __builtin_bit_cast(float, lh ? __builtin_amdgcn_readlane(vb, 32) : __builtin_amdgcn_readlane(vb, 0));
+                        if (VALID) piv = valid_pivot(v, inmask, lh);
+                        const float dv = (pok && inx) ? v - piv : 0.0f;
                         float ssum = 0.0f, ssq = 0.0f;
                         ssum += dv; ssq = fmaf(dv, dv, ssq);
                         const float a = half_wave_sum(ssum), q = half_wave_sum(ssq);
@@ -188,6 +194,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_s2_m96(ConvP P) {
                         if (l31 == 31) { rd[0] = a; rd[1] = q; rd[2] = piv; }
                     }
                     if (relu) v = v < 0.0f ? 0.0f : v;
+                    if (VALID) v = inx ? v : 0.0f;
                     if (pok) outb[(size_t)row * hw + px] = v;
                 }
             }
@@ -203,6 +210,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_s2_m96(ConvP P) {
                 const int blk = (n0 + w2 * 32) >> 5;
                 if (blk >= nrec) continue;
                 int nw = hw - blk * 32; nw = nw > 32 ? 32 : nw;                            // valid columns of the block (>= 1)
+                if (VALID) nw = valid_before(blk * 32 + nw, W, P.Hv, P.Wv) - valid_before(blk * 32, W, P.Hv, P.Wv);
                 const float* rd = red + (w2 * BM + tid) * 3;
                 StatAcc A;
                 A.add_pivoted(nw, rd[0], rd[1], rd[2]);
@@ -213,7 +221,8 @@ __global__ __launch_bounds__(256, 2) void k_conv_s2_m96(ConvP P) {
     }
 }
 
-int conv_s2_m96_launch(const ConvP& P, int batch, hipStream_t stream) {
-    hipLaunchKernelGGL(k_conv_s2_m96, dim3(ceil_div(P.hw, 128), 1, batch), dim3(256), 0, stream, P);
+int conv_s2_m96_launch(const ConvP& P, int batch, hipStream_t stream, bool valid) {
+    if (valid) hipLaunchKernelGGL(k_conv_s2_m96<true>, dim3(ceil_div(P.hw, 128), 1, batch), dim3(256), 0, stream, P);
+    else hipLaunchKernelGGL(k_conv_s2_m96<false>, dim3(ceil_div(P.hw, 128), 1, batch), dim3(256), 0, stream, P);
     return rpe_check_launch();
 }

@@ -91,6 +91,11 @@ extern "C" int rpe_debug_wino_timing(unsigned long long* out8) { return hipMemcp
 template <int EPI, bool PRE, int CB, bool RQ, bool VALID = false>
 __global__ __launch_bounds__(256, 2) void k_conv_wino(WinoP P) {
     constexpr bool HAS_AFFINE = EPI == 1 || EPI == 3, HAS_STATS = EPI == 2 || EPI == 3;
+    // VALID with the loader-side normalisation (quad patches only): relu((0 - mean) / std) of the padding is not zero, so the elements of
+    // the raw patch outside the valid extent get the padding value (-inf) where the out-of-map ones get it -- patch_raw, border workgroups
+    // only; the transform and the K loop are untouched
+    constexpr bool VPRE = VALID && PRE && RQ;
+    static_assert(!(VALID && PRE) || RQ, "the valid-extent form of the normalising loader exists for quad patches");
     constexpr int TCO = 32 * CB, UT_STEP = WK * TCO * 16;
     constexpr int RROW = RQ ? 24 : RAW_W, RCH = RROW * RAW_H, RBUF = RQ ? 1024 : RAW_BUF, RCOL0 = RQ ? 3 : 0;   // (patch column 0 = map column x0 - 1)
     constexpr int NRAW = RQ ? 1 : 3;                                         // raw-patch DMA instructions per wave and step
@@ -142,7 +147,11 @@ __global__ __launch_bounds__(256, 2) void k_conv_wino(WinoP P) {
         const int q0 = wv * 64 + lane, q = q0 < 240 ? q0 : 239;
         const int ci = q / 60, rem = q - ci * 60, r = rem / 6, qc = rem - r * 6;
         int yy = y0 - 1 + r, xx = x0 - 4 + 4 * qc;
-        if (q0 < 240 && (yy < 0 || yy >= H || xx < 0 || xx >= W)) oob = 1u;
+        if (q0 < 240 && (yy < 0 || yy >= H || xx < 0 || xx >= W)) oob = VPRE ? 0xFu : 1u;
+        else if (VPRE && q0 < 240) {                          // an in-map quad: bit e = its element e lies outside the valid extent
+#pragma unroll
+            for (int e = 0; e < 4; ++e) oob |= (yy >= P.Hv || xx + e >= P.Wv) ? 1u << e : 0u;
+        }
         yy = yy < 0 ? 0 : (yy >= H ? H - 1 : yy); xx = xx < 0 ? 0 : (xx >= W ? W - 4 : xx);
         roff[0] = (unsigned)(ci * hw + yy * W + xx) * 4u; roff[1] = roff[2] = 0u;
     } else {
@@ -158,7 +167,9 @@ __global__ __launch_bounds__(256, 2) void k_conv_wino(WinoP P) {
         }
     }
     // (RQ: the patch's right halo column x0 + 16 sits in a quad of its own, so a patch ending exactly at the map's edge is a border one)
-    const bool border = (y0 < 1) | (y0 + 2 * WB_TY >= H) | (x0 < 1) | (x0 + 2 * WB_TX >= W);       // workgroup-uniform
+    // (VPRE: a patch that reaches past the valid extent is a border one too -- the extent's edge is the map's edge for the normalised input)
+    const bool border = (y0 < 1) | (y0 + 2 * WB_TY >= H) | (x0 < 1) | (x0 + 2 * WB_TX >= W) |       // workgroup-uniform
+                        (VPRE && ((y0 + 2 * WB_TY >= P.Hv) | (x0 + 2 * WB_TX >= P.Wv)));
     // padding: zero; with the loader-side normalisation -inf, which relu((x - mean) / std) turns into the zero torch pads with (1/std > 0)
     const float padv = PRE ? -__builtin_inff() : 0.0f;
     auto patch_raw = [&](int buf) {
@@ -166,7 +177,10 @@ __global__ __launch_bounds__(256, 2) void k_conv_wino(WinoP P) {
             if (RQ) {
                 if (oob) {
                     float* q4 = &Rs[buf][4 * (wv * 64 + lane) + 1];
-                    q4[0] = padv; q4[1] = padv; q4[2] = padv; q4[3] = padv;
+                    if (VPRE) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) if ((oob >> e) & 1) q4[e] = padv;
+                    } else { q4[0] = padv; q4[1] = padv; q4[2] = padv; q4[3] = padv; }
                 }
             } else {
 #pragma unroll
@@ -470,7 +484,16 @@ __global__ __launch_bounds__(256, 2) void k_conv_wino(WinoP P) {
     float* ob = P.out + (size_t)bz * P.obs;
     float* ob2 = P.out2 ? P.out2 + (size_t)bz * P.o2bs : nullptr;
     const float* rsb = (HAS_AFFINE && P.res) ? P.res + (size_t)bz * P.rbs : nullptr;
-    const float nvalid = 4.0f * (float)__popcll(__ballot(pix_ok) & 0xFFFFull);   // pixels of this wave's 16 tiles inside the map
+    // VALID: which of the tile's pixels (e = 2 row + column) lie inside the valid extent -- the moments cover those only
+    bool ev[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) ev[e] = pix_ok && (!VALID || (oy + (e >> 1) < P.Hv && ox + (e & 1) < P.Wv));
+    float nvalid = 4.0f * (float)__popcll(__ballot(pix_ok) & 0xFFFFull);         // pixels of this wave's 16 tiles inside the map
+    if (VALID && HAS_STATS) {
+        nvalid = 0.0f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) nvalid += (float)__popcll(__ballot(ev[e]) & 0xFFFFull);
+    }
     const float inv_nvalid = nvalid > 0.0f ? 1.0f / nvalid : 0.0f;               // (4, 8, ..., 64: the reciprocal is exact or 1 ulp)
     const bool odd = li & 1;                                        // lane pairs = two x-neighbouring tiles
     // the residual quads of all eight (block, row) iterations are requested up front (the per-channel constants at kernel start):
@@ -516,15 +539,16 @@ __global__ __launch_bounds__(256, 2) void k_conv_wino(WinoP P) {
                 float s1 = 0.0f, s2 = 0.0f;
                 if (pix_ok) {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) { const float dv = y[e] - piv; s1 += dv; s2 += dv * dv; }
+                    for (int e = 0; e < 4; ++e) if (!VALID || ev[e]) { const float dv = y[e] - piv; s1 += dv; s2 += dv * dv; }
                 }
                 s1 = row16_sum(s1); s2 = row16_sum(s2);
                 // one (count, mean, M2) record per channel, patch and tile half: rpe_instnorm_apply / _finalize merge records in f64
                 // anyway (the pivot is a sample, so s2 - s1^2/n loses at most a factor ~2 in f32).  Every lane of the row has the
                 // totals; lane r keeps them, and the four records of a block leave together below (a store per record and value --
                 // 24 nearly empty store instructions per wave -- cost the epilogue more than the arithmetic)
-                const float m = s1 * inv_nvalid;
-                if (li == r) { rec[0] = nvalid; rec[1] = piv + m; rec[2] = s2 - s1 * m; }
+                const float m = VALID ? (nvalid > 0.0f ? s1 / nvalid : 0.0f) : s1 * inv_nvalid;    // (VALID: counts that are no power-of-two multiples)
+                // (VALID: a wave wholly outside the extent leaves the zero-count record (0, 0, 0), which the merge skips: its pivot is no sample)
+                if (li == r) { rec[0] = nvalid; rec[1] = (VALID && nvalid == 0.0f) ? 0.0f : piv + m; rec[2] = s2 - s1 * m; }
             }
             if (P.mode == RPE_CONV_RELU) {                                   // NaN stays NaN, like torch.relu
 #pragma unroll
@@ -610,7 +634,8 @@ extern "C" int rpe_conv_wino_stats_tiles(int h, int w) {
     return (h > 0 && w > 0) ? 2 * ceil_div(w, 2 * WB_TX) * ceil_div(h, 2 * WB_TY) : 0;      // two records (tile halves) per 16x8 patch
 }
 
-static int conv_wino_launch(const rpe_conv_desc* d, int hv, int wv, void* stream) {
+// enc: rpe_enc_conv_wino_v -- every epilogue class and the normalising loader under a valid extent (quad patches, 16-byte stores)
+static int conv_wino_launch(const rpe_conv_desc* d, int hv, int wv, void* stream, bool enc = false) {
     if (!conv_desc_present(d)) return RPE_E_BADARG;
     // tiles of 2 x 2 outputs: even maps (the only 3x3 Winograd kernel that takes w % 4 == 2)
     if (d->kh != 3 || d->kw != 3 || !stride_is_1(d) || (d->cin % WK) || (d->h & 1) || (d->w & 1)) return RPE_E_UNSUPPORTED;
@@ -631,9 +656,16 @@ static int conv_wino_launch(const rpe_conv_desc* d, int hv, int wv, void* stream
     const int epi = wino_epilogue_class(d);
     const unsigned gx = ceil_div(d->w, 2 * WB_TX) * ceil_div(d->h, 2 * WB_TY);
     const bool valid = hv != d->h || wv != d->w;               // a valid extent smaller than the map: the plain epilogue's 16-byte stores only
-    if (valid && (epi != 0 || !P.v4)) return RPE_E_UNSUPPORTED;
+    if (valid && (enc ? (!P.v4 || !quads) : (epi != 0 || !P.v4))) return RPE_E_UNSUPPORTED;
     P.Hv = hv; P.Wv = wv;
     auto launch = [&](auto cb, int tiles) {
+        if (valid && enc) {
+            dispatch_epi_pre(epi, d->pre_norm != nullptr, [&](auto e, auto pre) {
+                hipLaunchKernelGGL((k_conv_wino<decltype(e)::value, decltype(pre)::value, decltype(cb)::value, true, true>), dim3(gx, tiles, d->b), dim3(256), 0,
+                                   (hipStream_t)stream, P);
+            });
+            return;
+        }
         if (valid) {
             constexpr int CB = decltype(cb)::value;
             const dim3 grid(gx, tiles, d->b);
@@ -662,4 +694,11 @@ extern "C" int rpe_conv_wino(const rpe_conv_desc* d, void* stream) { return conv
 extern "C" int rpe_conv_wino_v(const rpe_conv_desc_v* dv, void* stream) {
     if (!dv || !conv_valid_extent_ok(dv)) return RPE_E_BADARG;
     return conv_wino_launch(&dv->d, dv->h_valid, dv->w_valid, stream);
+}
+
+// The encoders' form: bias / scale / residual / stats / pre_norm under a valid extent (the stored map, the moments and the normalised input
+// are all zero / absent outside it).  Extent == map: literally rpe_conv_wino's launch.
+extern "C" int rpe_enc_conv_wino_v(const rpe_conv_desc_v* dv, void* stream) {
+    if (!dv || !conv_valid_extent_ok(dv)) return RPE_E_BADARG;
+    return conv_wino_launch(&dv->d, dv->h_valid, dv->w_valid, stream, true);
 }

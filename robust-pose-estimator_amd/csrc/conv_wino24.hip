@@ -73,6 +73,7 @@ __host__ __device__ constexpr int w4_phys(int slot, int row) { return (slot + ((
 template <int EPI, bool PRE, int CB, bool VALID = false>
 __global__ __launch_bounds__(256, 2) void k_conv_wino24(Wino24P P) {
     constexpr bool HAS_AFFINE = EPI == 1 || EPI == 3, HAS_STATS = EPI == 2 || EPI == 3;
+    constexpr bool VPRE = VALID && PRE;                                      // (conv_wino.hip: the raw patch outside the valid extent gets the padding value)
     constexpr int NW = 4, TCO = 32 * CB, UT_STEP = W4K * TCO * W4_NP;
     constexpr int NRAW = 1;                                                  // raw-patch DMA instructions per wave and step
     constexpr int NG = 3 * CB;                                               // groups of 4 positions per wave (CB = 1: half of them)
@@ -104,19 +105,28 @@ __global__ __launch_bounds__(256, 2) void k_conv_wino24(Wino24P P) {
         const int q0 = 64 * (NW * j + wv) + lane, q = q0 < 240 ? q0 : 239;
         const int ci = q / 60, rem = q - ci * 60, r = rem / 6, qc = rem - r * 6;
         int yy = y0 - 1 + r, xx = x0 - 4 + 4 * qc;
-        if (q0 < 240 && (yy < 0 || yy >= H || xx < 0 || xx >= W)) oob |= 1u << j;
+        if (q0 < 240 && (yy < 0 || yy >= H || xx < 0 || xx >= W)) oob |= VPRE ? 0xFu : 1u << j;
+        else if (VPRE && q0 < 240) {                          // an in-map quad: bit e = its element e lies outside the valid extent
+#pragma unroll
+            for (int e = 0; e < 4; ++e) oob |= (yy >= P.Hv || xx + e >= P.Wv) ? 1u << e : 0u;
+        }
         yy = yy < 0 ? 0 : (yy >= H ? H - 1 : yy); xx = xx < 0 ? 0 : (xx >= W ? W - 4 : xx);
         roff[j] = (unsigned)(ci * hw + yy * W + xx) * 4u;
     }
-    const bool border = (y0 < 1) | (y0 + 8 >= H) | (x0 < 1) | (x0 + 16 >= W);       // workgroup-uniform
+    const bool border = (y0 < 1) | (y0 + 8 >= H) | (x0 < 1) | (x0 + 16 >= W) |       // workgroup-uniform
+                        (VPRE && ((y0 + 8 >= P.Hv) | (x0 + 16 >= P.Wv)));
+    static_assert(NRAW == 1, "VPRE keeps the quad's four element bits in oob");
     const float padv = PRE ? -__builtin_inff() : 0.0f;                              // relu((-inf - mean) / std) = 0
     auto patch_raw = [&](int buf) {
         if (border) {
 #pragma unroll
             for (int j = 0; j < NRAW; ++j)
-                if ((oob >> j) & 1) {
+                if (VPRE ? oob != 0 : (oob >> j) & 1) {
                     float* q4 = &Rs[buf][4 * (64 * (NW * j + wv) + lane) + 1];
-                    q4[0] = padv; q4[1] = padv; q4[2] = padv; q4[3] = padv;
+                    if (VPRE) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) if ((oob >> e) & 1) q4[e] = padv;
+                    } else { q4[0] = padv; q4[1] = padv; q4[2] = padv; q4[3] = padv; }
                 }
         }
     };
@@ -323,7 +333,20 @@ __global__ __launch_bounds__(256, 2) void k_conv_wino24(Wino24P P) {
     const float* rsb = (HAS_AFFINE && P.res) ? P.res + (size_t)bz * P.rbs : nullptr;
     const unsigned long long vmask = __ballot(pix_ok);
     const int hf = li >> 3;                                   // moment record: top (tiles 0-7) or bottom (8-15) 16 x 4 pixels
-    const float nvalid = 8.0f * (float)__popcll((vmask >> (8 * hf)) & 0xFFull);
+    float nvalid = 8.0f * (float)__popcll((vmask >> (8 * hf)) & 0xFFull);
+    // VALID: which of the tile's 2 x 4 pixels lie inside the valid extent -- the moments cover those only
+    bool ev[2][4];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) ev[i][e] = pix_ok && (!VALID || (oy + i < P.Hv && ox + e < P.Wv));
+    if (VALID && HAS_STATS) {
+        nvalid = 0.0f;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) nvalid += (float)__popcll((__ballot(ev[i][e]) >> (8 * hf)) & 0xFFull);
+    }
     const float inv_nvalid = nvalid > 0.0f ? 1.0f / nvalid : 0.0f;
     // CB = 1: the wave pair exchanges halves through LDS (U's buffers, free now): wave ph finishes channel rows 2 ph, 2 ph + 1 and hands
     // its partner (wave ^ 2) the other two rows of its 12 positions.  xr[2 p + rr] = the partner's position p of row 2 ph + rr.
@@ -399,11 +422,11 @@ __global__ __launch_bounds__(256, 2) void k_conv_wino24(Wino24P P) {
 #pragma unroll
                     for (int i = 0; i < 2; ++i)
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) { const float dv = y[i][e] - piv; s1 += dv; s2 += dv * dv; }
+                        for (int e = 0; e < 4; ++e) if (!VALID || ev[i][e]) { const float dv = y[i][e] - piv; s1 += dv; s2 += dv * dv; }
                 }
                 s1 = row8_sum(s1); s2 = row8_sum(s2);
-                const float m = s1 * inv_nvalid;
-                if ((li & 7) == r) { rec[0] = nvalid; rec[1] = piv + m; rec[2] = s2 - s1 * m; }
+                const float m = VALID ? (nvalid > 0.0f ? s1 / nvalid : 0.0f) : s1 * inv_nvalid;
+                if ((li & 7) == r) { rec[0] = nvalid; rec[1] = (VALID && nvalid == 0.0f) ? 0.0f : piv + m; rec[2] = s2 - s1 * m; }   // (zero-count record: (0, 0, 0))
             }
             if (P.mode == RPE_CONV_RELU) {
 #pragma unroll
@@ -480,7 +503,7 @@ extern "C" int rpe_conv_wino24_pack(const float* weight, int cout, int cin, floa
     return launch_pack(k_wino24_pack, weight, packed, cout, cin, W4K, (long long)rpe_conv_wino24_packed_floats(cout, cin), stream, round_up(cout, W4_CO));
 }
 
-static int conv_wino24_launch(const rpe_conv_desc* d, int hv, int wv, void* stream) {
+static int conv_wino24_launch(const rpe_conv_desc* d, int hv, int wv, void* stream, bool enc = false) {
     if (!conv_desc_present(d)) return RPE_E_BADARG;
     // tiles of 2 x 4 outputs, and every map row moved as 16-byte quads
     if (d->kh != 3 || d->kw != 3 || !stride_is_1(d) || (d->cin % W4K) || (d->h & 1) || (d->w & 3)) return RPE_E_UNSUPPORTED;
@@ -494,9 +517,16 @@ static int conv_wino24_launch(const rpe_conv_desc* d, int hv, int wv, void* stre
     const int epi = wino_epilogue_class(d);
     const unsigned gx = ceil_div(d->w, 16) * ceil_div(d->h, 8);
     const bool valid = hv != d->h || wv != d->w;               // a valid extent smaller than the map: the plain epilogue only
-    if (valid && epi != 0) return RPE_E_UNSUPPORTED;
+    if (valid && !enc && epi != 0) return RPE_E_UNSUPPORTED;
     P.Hv = hv; P.Wv = wv;
     auto launch = [&](auto cb, int tiles) {
+        if (valid && enc) {                                   // rpe_enc_conv_wino24_v: every epilogue class and the normalising loader
+            dispatch_epi_pre(epi, d->pre_norm != nullptr, [&](auto e, auto pre) {
+                hipLaunchKernelGGL((k_conv_wino24<decltype(e)::value, decltype(pre)::value, decltype(cb)::value, true>), dim3(gx, tiles, d->b), dim3(256), 0,
+                                   (hipStream_t)stream, P);
+            });
+            return;
+        }
         if (valid) {
             hipLaunchKernelGGL((k_conv_wino24<0, false, decltype(cb)::value, true>), dim3(gx, tiles, d->b), dim3(256), 0, (hipStream_t)stream, P);
             return;
@@ -517,4 +547,10 @@ extern "C" int rpe_conv_wino24(const rpe_conv_desc* d, void* stream) { return co
 extern "C" int rpe_conv_wino24_v(const rpe_conv_desc_v* dv, void* stream) {
     if (!dv || !conv_valid_extent_ok(dv)) return RPE_E_BADARG;
     return conv_wino24_launch(&dv->d, dv->h_valid, dv->w_valid, stream);
+}
+
+// The encoders' form (see rpe_enc_conv_wino_v).  Extent == map: literally rpe_conv_wino24's launch.
+extern "C" int rpe_enc_conv_wino24_v(const rpe_conv_desc_v* dv, void* stream) {
+    if (!dv || !conv_valid_extent_ok(dv)) return RPE_E_BADARG;
+    return conv_wino24_launch(&dv->d, dv->h_valid, dv->w_valid, stream, true);
 }

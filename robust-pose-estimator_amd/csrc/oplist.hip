@@ -26,6 +26,7 @@ static_assert(sizeof(rpe_stem_conv_v_args) == 104, "rpe_stem_conv_v_args: layout
 static_assert(sizeof(rpe_flow_update_v_args) == 104, "rpe_flow_update_v_args: layout changed -- update _lib.py and RPE_ABI_VERSION");
 static_assert(sizeof(rpe_upsample_convex_ex_args) == 48, "rpe_upsample_convex_ex_args: layout changed -- update _lib.py and RPE_ABI_VERSION");
 static_assert(sizeof(rpe_copy_rect_args) == 80, "rpe_copy_rect_args: layout changed -- update _lib.py and RPE_ABI_VERSION");
+static_assert(sizeof(rpe_instnorm_apply_v_args) == 72, "rpe_instnorm_apply_v_args: layout changed -- update _lib.py and RPE_ABI_VERSION");
 static_assert(sizeof(rpe_solve_opts) == 32, "rpe_solve_opts: layout changed -- update _lib.py and RPE_ABI_VERSION");
 
 template <typename A>
@@ -126,6 +127,14 @@ static int run_one(const rpe_op& op, void* const* streams, int n_streams) {
         const auto* a = as<rpe_copy_rect_args>(op);
         return rpe_copy_rect(a->src, a->src_batch_stride, a->src_plane_stride, a->src_pitch, a->dst, a->dst_batch_stride, a->dst_plane_stride,
                              a->dst_pitch, a->b, a->c, a->h, a->w, st);
+    }
+    case RPE_OP_ENC_CONV_WINO_V: return rpe_enc_conv_wino_v(as<rpe_conv_desc_v>(op), st);
+    case RPE_OP_ENC_CONV_WINO24_V: return rpe_enc_conv_wino24_v(as<rpe_conv_desc_v>(op), st);
+    case RPE_OP_ENC_CONV_S2_V: return rpe_enc_conv_s2_v(as<rpe_conv_desc_v>(op), st);
+    case RPE_OP_ENC_CONV_S2_M96_V: return rpe_enc_conv_s2_m96_v(as<rpe_conv_desc_v>(op), st);
+    case RPE_OP_INSTNORM_APPLY_V: {
+        const auto* a = as<rpe_instnorm_apply_v_args>(op);
+        return rpe_instnorm_apply_v(a->x, a->mean_inv, a->b, a->c, a->h, a->w, a->h_valid, a->w_valid, a->relu, a->residual, a->residual_mean_inv, a->out, st);
     }
     case RPE_OP_EVENT_RECORD: {
         hipEvent_t ev = (hipEvent_t) * static_cast<void* const*>(op.args);

@@ -149,7 +149,7 @@ class _Launcher:
     = what the struct points into.  ``L`` is the library whose entry point it calls."""
 
     def __init__(self, kind, a, keep, result, L):
-        entry, struct = _lib.LIST_OPS[kind]
+        entry, struct = _lib.ALL_LIST_OPS[kind]
         self.op, self.keep, self._result, self._entry, self._fn = (kind, a), keep, result, entry, getattr(L, entry)
         self._args = (lambda d, ref=ctypes.byref(a): (ref,)) if struct is _lib.ConvDesc else operator.attrgetter(*(f for f, _ in struct._fields_))
 
@@ -168,7 +168,7 @@ def _launch(kind, args, keep, result, prepare=False):
     of its argument struct (the descriptor itself for the rpe_conv_desc kinds); ``keep``: the objects they point into.  Launches on the
     current stream and returns ``result``, or (``prepare``) returns a _Launcher on the real library -- never on a CountingLib that stands
     in while it is built.  While a Recorder is active, every launch is logged with its struct."""
-    entry, struct = _lib.LIST_OPS[kind]
+    entry, struct = _lib.ALL_LIST_OPS[kind]
     desc = struct is _lib.ConvDesc
     if not prepare and _REC is None:                  # call by call: no struct beyond the descriptor the wrapper built anyway
         st = getattr(lib(), entry)(*((ctypes.byref(args),) if desc else args), stream_ptr())
@@ -915,23 +915,32 @@ _FUSED_MODES = (CONV_LINEAR, CONV_RELU, CONV_GATE_ZR, CONV_GATE_H, CONV_TANH)
 
 
 def conv_fused(x, pc, mode, out, out2=None, add=None, hidden=None, zgate=None, gate_channels=0, scale=None, bias='packed',
-               residual=None, stats=None, stride=1, pre_norm=None, prepare=False, entry='rpe_conv_fused', valid=None):
+               residual=None, stats=None, stride=1, pre_norm=None, prepare=False, entry='rpe_conv_fused', valid=None, enc_valid=None):
     """rpe_conv_fused: out = epilogue(conv(x; pc) * scale + add + bias).  All tensors are channel slices of NCHW buffers.
     ``bias`` defaults to the one packed with the weights; ``stats`` (from conv_stats_buffer) collects the per-tile moments
     instnorm_apply needs.  ``prepare=True`` returns a zero-argument launcher instead of launching: the GRU loop runs the same
     nine convolutions on the same buffers twelve times, and at batch 1 the Python argument checking costs more than the kernels.
     ``valid`` = (hv, wv): the entry point's ``_v`` form (rpe_conv_wino1d_v, rpe_conv1x1_v): the map is zero-padded, the epilogue stores zero
-    outside its hv x wv of content."""
+    outside its hv x wv of content.  ``enc_valid`` = (hv, wv) of the OUTPUT map: the encoders' stride-2 form (rpe_enc_conv_s2_v / _m96_v), whose
+    ``stats`` records also cover the content only."""
+    if enc_valid is not None:
+        if valid is not None or stride != 2:
+            raise _lib.RpeError('conv_fused: enc_valid is the stride-2 encoder form (not with valid=)')
+        valid = enc_valid
     d, bias, stats = _conv_desc('conv_fused', x, pc, mode, dict(add=add, out=out, out2=out2, hidden=hidden, zgate=zgate, residual=residual),
                                 _FUSED_RULES.get(mode, _PLAIN_RULES), scale, bias, stats, pre_norm, modes=_FUSED_MODES, tile_major=False,
                                 kernel=(pc.kh, pc.kw), stride=stride, gate_channels=gate_channels, valid=valid)
-    return _launch(_kind(entry, valid), d, (x, pc, out, out2, add, hidden, zgate, scale, bias, residual, stats, pre_norm), out, prepare)
+    return _launch(_kind(entry, valid, enc_valid is not None), d, (x, pc, out, out2, add, hidden, zgate, scale, bias, residual, stats, pre_norm), out, prepare)
 
 
-def _kind(entry, valid):
+def _kind(entry, valid, enc=False):
     """The launch-list kind of ``entry``, or of its valid-extent form ``entry + '_v'`` (an entry point without one raises)."""
     if valid is None:
         return _lib.KIND_OF_ENTRY[entry]
+    if enc:                                                   # the encoders' forms: their own entry points, every encoder epilogue
+        if entry not in _lib.ENC_FORM:
+            raise _lib.RpeError(f'{entry} has no encoder valid-extent form')
+        return _lib.KIND_OF_ENTRY[_lib.ENC_FORM[entry]]
     if entry + '_v' not in _lib.KIND_OF_ENTRY:
         raise _lib.RpeError(f'{entry} has no valid-extent form')
     return _lib.KIND_OF_ENTRY[entry + '_v']
@@ -1070,13 +1079,20 @@ class PackedWinoX3(_Packed):
         return tuple(weight.shape[2:]) == (3, 3) and weight.shape[1] % 16 == 0 and hh % 2 == 0 and ww % 4 == 0
 
 
-def conv_wino(x, pw, mode, out, out2=None, scale=None, bias='packed', residual=None, stats=None, pre_norm=None, prepare=False, valid=None):
+def conv_wino(x, pw, mode, out, out2=None, scale=None, bias='packed', residual=None, stats=None, pre_norm=None, prepare=False, valid=None,
+              enc_valid=None):
     """rpe_conv_wino: out = epilogue(conv3x3(x; pw) * scale + bias) by Winograd F(2x2,3x3) -- F(2x4,3x3) with a PackedWino24, the
     labelled bf16x3 variant with a PackedWinoX3; tensors are channel slices of NCHW buffers.  ``stats`` (conv_wino_stats_buffer) /
-    ``pre_norm`` / ``residual`` / ``scale``: the encoders' epilogues, as conv_fused."""
+    ``pre_norm`` / ``residual`` / ``scale``: the encoders' epilogues, as conv_fused.  ``enc_valid`` = (hv, wv): the encoders' valid-extent
+    form (rpe_enc_conv_wino_v / _wino24_v) -- ``valid``'s zero outside the content with every epilogue above, the records of ``stats`` over
+    the content only, and ``pre_norm``'s normalised input zero outside it."""
+    if enc_valid is not None:
+        if valid is not None:
+            raise _lib.RpeError('conv_wino: valid= and enc_valid= are two entry points')
+        valid = enc_valid
     d, bias, stats = _conv_desc('conv_wino', x, pw, mode, dict(out=out, out2=out2, residual=residual), _WINO_RULES, scale, bias, stats, pre_norm,
                                 modes=(CONV_LINEAR, CONV_RELU), tile_major=True, kernel=(3, 3), valid=valid)
-    return _launch(_kind(pw.entry, valid), d, (x, pw, out, out2, scale, bias, residual, stats, pre_norm), out, prepare)
+    return _launch(_kind(pw.entry, valid, enc_valid is not None), d, (x, pw, out, out2, scale, bias, residual, stats, pre_norm), out, prepare)
 
 
 class TileMajorStats:
@@ -1130,12 +1146,14 @@ def instnorm_finalize(stats, hw, eps=1e-5, channels=None):
     return _launch(_lib.OP_INSTNORM_FINALIZE, (ptr(t), tiles, b, c, hw, float(eps), ptr(mi)), (t, mi), mi)
 
 
-def instnorm_apply(x, stats, eps=1e-5, relu=True, residual=None, out=None, residual_norm=None, residual_relu=True):
+def instnorm_apply(x, stats, eps=1e-5, relu=True, residual=None, out=None, residual_norm=None, residual_relu=True, valid=None):
     """Instance norm of x (b,c,h,w) from the partial sums of conv_fused(..., stats=stats): one read + one write pass.
     ``stats`` may also be the (b,c,2) result of instnorm_finalize on those sums (``eps`` is then already in it): the pass is then a
     pure stream with several workgroups per plane, the faster form behind large maps (the records are merged once, not per workgroup).
     ``residual_norm`` (b,c,2) from instnorm_finalize: the residual is a RAW convolution output, normalised (+ ReLU'd unless
-    ``residual_relu=False``: a stride-2 block's shortcut has none) on the fly."""
+    ``residual_relu=False``: a stride-2 block's shortcut has none) on the fly.
+    ``valid`` = (hv, wv): x is a zero-padded map with hv x wv of content (rpe_instnorm_apply_v): the same bits inside, zero outside;
+    ``stats`` are then the pairs of instnorm_finalize, or records, which are finalized first (over hv * wv pixels)."""
     _nchw(x, 'instnorm_apply: x')
     b, c, hh, ww = x.shape
     if isinstance(stats, torch.Tensor) and stats.dim() == 3:              # (mean, 1/std) pairs of instnorm_finalize: a pure streaming pass
@@ -1150,6 +1168,12 @@ def instnorm_apply(x, stats, eps=1e-5, relu=True, residual=None, out=None, resid
         _f32(residual_norm, 'instnorm_apply: residual_norm', (b, c, 2))
     out = x if out is None else _nchw(out, 'instnorm_apply: out')
     flags = int(bool(relu)) | (0 if residual_relu or residual_norm is None else 2)
+    if valid is not None:
+        hv, wv = _valid_extent('instnorm_apply', valid, hh, ww)
+        if tiles != 0:
+            t = instnorm_finalize(stats, hv * wv, eps=eps, channels=c)
+        return _launch(_lib.OP_INSTNORM_APPLY_V, (ptr(x), ptr(t), b, c, hh, ww, hv, wv, flags, ptr(residual), ptr(residual_norm), ptr(out)),
+                       (x, t, residual, residual_norm, out), out)
     return _launch(_lib.OP_INSTNORM_APPLY, (ptr(x), ptr(t), tiles, b, c, hh * ww, float(eps), flags, ptr(residual), ptr(residual_norm), ptr(out)),
                    (x, t, residual, residual_norm, out), out)
 

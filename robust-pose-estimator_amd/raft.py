@@ -14,7 +14,11 @@ What runs where (MI355X-first split), all hand-written HIP 
   * flow-head output layer with the coords / flow bookkeeping of the loop, convex up-sampling, norm / bias passes, slice copies
     (csrc/raft_ops.hip)
   * opt-in (config ``pad_maps``): at such map sizes the UPDATE LOOP on the tuned kernels over zero-padded maps (padded_size; the kernels' valid-extent
-    entry points rpe_conv_*_v keep the padding zero); the encoders stay on the generic route below
+    entry points rpe_conv_*_v keep the padding zero); the encoders stay on the generic route below unless
+  * opt-in (config ``pad_encoders``): at such sizes layer2, layer3 and the output layer of both ENCODERS on the tuned kernels over maps zero-padded
+    to 4x / 2x / 1x padded_size (the encoder forms rpe_enc_conv_wino_v / _wino24_v / _s2_v / _s2_m96_v, rpe_instnorm_apply_v, rpe_conv1x1_v: zero
+    stored outside the content, instance-norm moments and the loader-side normalisation over the content only); the stem and layer1 keep the
+    true 1/2 map, the result leaves cropped
   * map sizes the tuned kernels refuse (odd maps, rows that are not whole 16-byte quads: image widths that are not a multiple of 32,
     heights not a multiple of 16): the same layers on the generic implicit GEMM (csrc/conv_direct.hip) with the stand-alone epilogue
     kernels -- robust, slower; no launch of a pass goes to a library at any size
@@ -62,6 +66,9 @@ SIDE_STREAM = True
 # RAFT's ``pad_maps`` for models built without the config key (tools/bench_pad_maps.py, A/B runs): at 1/8 maps the tuned kernels refuse, the
 # update loop runs on maps zero-padded to the next size they take (padded_size).  Opt-in; no effect on maps they take as they are.
 PAD_MAPS = False
+# RAFT's ``pad_encoders`` for models built without the config key: at image sizes whose 1/8 map the tuned kernels refuse, both encoders run
+# layer2, layer3 and the output layer on zero-padded maps instead of on the generic convolution.  Opt-in; no effect at any other size.
+PAD_ENCODERS = False
 # The update loop as ONE call into the library (ops.OpList -> rpe_run_ops): the 12 iterations' ~130-180 launches and stream fork / joins are
 # enqueued by a C loop over prepared argument blocks instead of one Python-dispatched ctypes call each (bit-identical: the same entry
 # points with the same arguments).  False = launch by launch from Python (bench.py's per-convolution diagnostic pass, A/B runs).
@@ -92,7 +99,7 @@ SIDE_STREAM_MAX = 8 * 5120                                     # queries per pas
 # recorded under them, so a switch flipped on a live model (tests, bench.py's A/B runs) is honoured by all of it at the next pass.
 # (LOOP_OPLIST, LOOKUP_EVENT_SINK, FRAME_OPLISTS and FRAME_OPLISTS_MAX_IMAGES choose how launches are dispatched, not what is cached.)
 ROUTE_SWITCHES = ('WINOGRAD', 'WINO_2X4', 'S2_M96', 'S2_M96_MIN_WGS', 'CORR_BF16X3', 'CONV_BF16X3', 'X3_MIN_CIN', 'X3_GRU', 'SIDE_STREAM', 'SIDE_STREAM_MAX',
-                  'LOOKUP_FUSED', 'LOOKUP_FUSED_MAX_WGS', 'ENC_STREAMS', 'ENC_STREAMS_MIN', 'PAD_MAPS')
+                  'LOOKUP_FUSED', 'LOOKUP_FUSED_MAX_WGS', 'ENC_STREAMS', 'ENC_STREAMS_MIN', 'PAD_MAPS', 'PAD_ENCODERS')
 _switch_values = operator.itemgetter(*ROUTE_SWITCHES)
 
 
@@ -139,18 +146,23 @@ class ResidualBlock(nn.Module):
         return (isinstance(self.norm1, nn.InstanceNorm2d) and self.downsample is None and _fusable(self.conv1, x) and x.shape[-1] % 4 == 0
                 and _wino(self.conv1, x) is not None)
 
-    def forward(self, x, x_norm=None):
+    def forward(self, x, x_norm=None, valid=None):
         """relu(x' + relu(norm2(conv2(relu(norm1(conv1 x)))))), x' = x or norm3(conv1x1 x); every convolution with its
         (bias, norm, ReLU, residual) epilogue fused (conv_norm_act).  With instance norm (fnet) norm1 + ReLU never exist
         as a tensor: conv1 leaves its raw output and partial sums, and conv2 normalises that input while staging it.
-        ``x_norm`` (b,c,2): x is a raw convolution output whose relu((x - mean) * inv) is this block's real input (takes_raw_input)."""
+        ``x_norm`` (b,c,2): x is a raw convolution output whose relu((x - mean) * inv) is this block's real input (takes_raw_input).
+        ``valid`` = (hv, wv) (pad_encoders): x and every map of the block are zero-padded, the block's OUTPUT map holds hv x wv of content;
+        every launch takes its encoder valid-extent form, which keeps the padding zero and the moments on the content."""
+        vk = {} if valid is None else dict(valid=valid)           # (flag off: every call below is the call it always was)
         fused_in = isinstance(self.norm1, nn.InstanceNorm2d) and _fusable(self.conv1, x) and x.shape[-1] // self.conv1.stride[0] % 4 == 0
         if x_norm is not None and not (fused_in and self.takes_raw_input(x)):
             raise RuntimeError('ResidualBlock: x_norm needs the fused stride-1 Winograd route')
+        if valid is not None and not (_fusable(self.conv1, x) and (fused_in or isinstance(self.norm1, nn.BatchNorm2d))):
+            raise ops._lib.RpeError('ResidualBlock: pad_encoders needs a padded map the tuned kernels take')
         if fused_in:
             st = self.conv1.stride[0]
-            hw = (x.shape[-2] // st) * (x.shape[-1] // st)
-            raw1, stats1 = _encoder_conv(self.conv1, x, pre_norm=x_norm, moments=True)   # (stride 1: Winograd, moments per 16x8-pixel patch)
+            hw = (x.shape[-2] // st) * (x.shape[-1] // st) if valid is None else valid[0] * valid[1]       # (the pixel count of the moments)
+            raw1, stats1 = _encoder_conv(self.conv1, x, pre_norm=x_norm, moments=True, **vk)   # (stride 1: Winograd, moments per 16x8-pixel patch)
             mi = ops.instnorm_finalize(stats1, hw, eps=self.norm1.eps, channels=self.conv1.out_channels)
             res_relu = True
             if self.downsample is not None:
@@ -158,19 +170,19 @@ class ResidualBlock(nn.Module):
                 if _fusable(sc, x):
                     # the shortcut norm3(conv1x1 x) never exists as a tensor either: its raw convolution output and (mean, 1/std) go to
                     # the block's last pass, which normalises it on the fly (bit-identical to a pass of its own, tested)
-                    x, stats_sc = _encoder_conv(sc, x, moments=True)
+                    x, stats_sc = _encoder_conv(sc, x, moments=True, **vk)
                     x_norm = ops.instnorm_finalize(stats_sc, hw, eps=self.norm3.eps, channels=sc.out_channels)
                     res_relu = False
                 else:
                     x = conv_norm_act(sc, self.norm3, x, relu=False)
-            raw2, stats2 = _encoder_conv(self.conv2, raw1, pre_norm=mi, moments=True)
+            raw2, stats2 = _encoder_conv(self.conv2, raw1, pre_norm=mi, moments=True, **vk)
             if isinstance(stats2, ops.TileMajorStats):            # merge the Winograd kernel's records once (a small launch), then stream
                 stats2 = ops.instnorm_finalize(stats2, hw, eps=self.norm2.eps, channels=self.conv2.out_channels)
-            return ops.instnorm_apply(raw2, stats2, eps=self.norm2.eps, relu=True, residual=x, residual_norm=x_norm, residual_relu=res_relu)
-        y = conv_norm_act(self.conv1, self.norm1, x, relu=True)
+            return ops.instnorm_apply(raw2, stats2, eps=self.norm2.eps, relu=True, residual=x, residual_norm=x_norm, residual_relu=res_relu, **vk)
+        y = conv_norm_act(self.conv1, self.norm1, x, relu=True, **vk)
         if self.downsample is not None:
-            x = conv_norm_act(self.downsample[0], self.norm3, x, relu=False)
-        return conv_norm_act(self.conv2, self.norm2, y, relu=True, residual=x)
+            x = conv_norm_act(self.downsample[0], self.norm3, x, relu=False, **vk)
+        return conv_norm_act(self.conv2, self.norm2, y, relu=True, residual=x, **vk)
 
 
 def _bounded_put(cache, key, value, keep=2):
@@ -232,33 +244,38 @@ def _fusable(conv, x):
     return (s1 or s2) and ww % 4 == 0 and ((hh // stride) * (ww // stride)) % 4 == 0 and x.is_contiguous()
 
 
-def conv_norm_act(conv, norm, x, relu, residual=None):
+def conv_norm_act(conv, norm, x, relu, residual=None, valid=None):
     """norm(conv(x) + bias) [ReLU] [+ residual, ReLU].  The residual blocks' convolutions -- 3x3 stride 1, 3x3 stride 2 and
     the 1x1 stride-2 shortcut -- run on the fused HIP implicit GEMM when the map width is a multiple of 4 (folded batch
     norm / ReLU / residual inside its epilogue; for instance norm the epilogue leaves per-tile partial sums and one more
-    read+write pass normalises); shapes those kernels refuse run on the generic kernel (ops.conv_direct) + a stand-alone epilogue pass."""
+    read+write pass normalises); shapes those kernels refuse run on the generic kernel (ops.conv_direct) + a stand-alone epilogue pass.
+    ``valid`` (pad_encoders): the extent of the content of the zero-padded output map, as ResidualBlock.forward."""
     fused = _fusable(conv, x)
+    if valid is not None and not fused:
+        raise ops._lib.RpeError('conv_norm_act: pad_encoders needs a padded map the tuned kernels take')
     if isinstance(norm, nn.BatchNorm2d):
         if norm.training:
             raise RuntimeError('the RAFT encoders run with frozen batch norm (RAFT.freeze_bn, pose_net.py:22)')
         scale, shift = _bn_affine(conv, norm)
         if fused:                                              # (cnet's stride-1 3x3 layers: Winograd with the folded batch norm in the epilogue)
-            return _encoder_conv(conv, x, ops.CONV_RELU if relu else ops.CONV_LINEAR, affine=(scale, shift), residual=residual)[0]
+            return _encoder_conv(conv, x, ops.CONV_RELU if relu else ops.CONV_LINEAR, affine=(scale, shift), residual=residual, valid=valid)[0]
         return ops.affine_act(ops.conv_direct(x, conv.weight, None, conv.stride, conv.padding), scale, shift, relu=relu, residual=residual)
     if isinstance(norm, nn.InstanceNorm2d):
         if fused:
-            pre, stats = _encoder_conv(conv, x, moments=True)
-            return ops.instnorm_apply(pre, stats, eps=norm.eps, relu=relu, residual=residual)
+            pre, stats = _encoder_conv(conv, x, moments=True, valid=valid)
+            return ops.instnorm_apply(pre, stats, eps=norm.eps, relu=relu, residual=residual, **({} if valid is None else dict(valid=valid)))
         return ops.instnorm_act(ops.conv_direct(x, conv.weight, None, conv.stride, conv.padding), conv.bias, eps=norm.eps, relu=relu, residual=residual)
     raise NotImplementedError(type(norm))
 
 
-def _encoder_conv(conv, x, mode=ops.CONV_LINEAR, affine=None, residual=None, pre_norm=None, moments=False):
+def _encoder_conv(conv, x, mode=ops.CONV_LINEAR, affine=None, residual=None, pre_norm=None, moments=False, valid=None):
     """An encoder convolution that _fusable accepts, on the route its input allows: Winograd (rpe_conv_wino*) when _wino has a packing for
     it, else the fused implicit GEMM (rpe_conv_fused, which also takes stride 2 and the 1x1 shortcut).  The epilogue adds the conv bias, or
     with ``affine`` = (scale, shift) applies the folded batch norm; ``mode`` (LINEAR / RELU), ``residual`` and ``pre_norm`` as ops.conv_fused.
     Returns (the output, the per-tile moments for instnorm_finalize / instnorm_apply in the layout of the kernel that ran -- TileMajorStats
-    from Winograd, channel-major records from the implicit GEMM -- when ``moments``, else None)."""
+    from Winograd, channel-major records from the implicit GEMM -- when ``moments``, else None).  ``valid`` (pad_encoders) = the content of
+    the zero-padded OUTPUT map: the kernels' encoder valid-extent forms (ops.conv_wino / conv_fused with enc_valid=)."""
+    vk = {} if valid is None else dict(enc_valid=valid)
     b, _, hh, ww = x.shape
     st, cout = conv.stride[0], conv.out_channels
     scale, bias = affine if affine is not None else (None, conv.bias.detach())
@@ -266,12 +283,14 @@ def _encoder_conv(conv, x, mode=ops.CONV_LINEAR, affine=None, residual=None, pre
     out = torch.empty(b, cout, hh // st, ww // st, device=x.device)
     if pw is not None:
         stats = ops.conv_wino_stats_buffer(b, cout, hh, ww, x.device) if moments else None
-        ops.conv_wino(x, pw, mode, out, scale=scale, bias=bias, residual=residual, stats=stats, pre_norm=pre_norm)
+        ops.conv_wino(x, pw, mode, out, scale=scale, bias=bias, residual=residual, stats=stats, pre_norm=pre_norm, **vk)
     else:
+        if valid is not None and (st != 2 or not WINOGRAD):
+            raise ops._lib.RpeError('pad_encoders runs the stride-1 3x3 layers on the Winograd kernels (WINOGRAD)')
         stats = ops.conv_stats_buffer(b, cout, hh, ww, x.device, stride=st) if moments else None
         m96 = S2_M96 and st == 2 and conv.kernel_size == (3, 3) and cout == 96 and b * -(-(hh // 2) * (ww // 2) // 128) >= S2_M96_MIN_WGS
         ops.conv_fused(x, _packed(conv), mode, out, scale=scale, bias=bias, residual=residual, stats=stats, stride=st, pre_norm=pre_norm,
-                       entry='rpe_conv_fused_m96' if m96 else 'rpe_conv_fused')
+                       entry='rpe_conv_fused_m96' if m96 else 'rpe_conv_fused', **vk)
     return out, stats
 
 
@@ -318,10 +337,18 @@ class _Recorded:
         self._failed.clear()
 
 
+def _check_pad_encoders(flag):
+    """The encoders' valid-extent entry points exist for the f32 Winograd / GEMM kernels only: pad_encoders is refused together with the bf16x3
+    variant of the convolutions and without WINOGRAD (at construction, and at every pass for the module-level switches), as pad_maps is."""
+    if (flag or PAD_ENCODERS) and (CONV_BF16X3 or not WINOGRAD):
+        raise ops._lib.RpeError('RAFT: pad_encoders runs on the f32 Winograd kernels -- not with CONV_BF16X3, not without WINOGRAD')
+
+
 class BasicEncoder(nn.Module):
     def __init__(self, output_dim=128, norm_fn='batch', dropout=0.0):
         super().__init__()
         self.norm_fn = norm_fn
+        self.pad_encoders = False                              # RAFT's config key ``pad_encoders`` (set by RAFT; PAD_ENCODERS for tools)
         self.norm1 = _norm(norm_fn, 64)
         self.conv1 = nn.Conv2d(3, 64, kernel_size=7, stride=2, padding=3)
         self.relu1 = nn.ReLU(inplace=True)
@@ -377,11 +404,13 @@ class BasicEncoder(nn.Module):
             return out, ops.instnorm_finalize(stats, (hh // 2) * (ww // 2), eps=self.norm1.eps, channels=64)
         return ops.instnorm_apply(out, stats, eps=self.norm1.eps, relu=True), None
 
-    def _final(self, x, split_act):
+    def _final(self, x, split_act, valid=None):
         """conv2, the 1x1 output layer (128 -> output_dim), on the implicit GEMM.  ``split_act`` (the context encoder as RAFT uses
         it, core/RAFT/core/raft.py: net, inp = split(cnet); net = tanh(net); inp = relu(inp)): channels [0, 128) leave through
-        tanh, the rest through ReLU, in the convolution's epilogue."""
+        tanh, the rest through ReLU, in the convolution's epilogue.  ``valid`` (pad_encoders): x is a zero-padded map with that much content;
+        the layer runs on it (rpe_conv1x1_v) and the result leaves cropped and contiguous (rpe_copy_rect)."""
         m = self.conv2
+        vk = {} if valid is None else dict(valid=valid)
         b, _, hh, ww = x.shape
         half = m.out_channels // 2
         if ww % 4 == 0 and x.is_contiguous():
@@ -391,10 +420,16 @@ class BasicEncoder(nn.Module):
             whole, lo, hi = _cached(self, '_final_packed', _wkey(m.weight, m.bias), pack)
             out = torch.empty(b, m.out_channels, hh, ww, device=x.device)
             if not split_act:
-                return whole(x, ops.CONV_LINEAR, out, x3=CONV_BF16X3)
-            lo(x, ops.CONV_TANH, out[:, :half])
-            hi(x, ops.CONV_RELU, out[:, half:], x3=CONV_BF16X3)
+                whole(x, ops.CONV_LINEAR, out, x3=CONV_BF16X3, **vk)
+            else:
+                lo(x, ops.CONV_TANH, out[:, :half], **vk)
+                hi(x, ops.CONV_RELU, out[:, half:], x3=CONV_BF16X3, **vk)
+            if valid is not None:
+                self._ws['out'] = out
+                return ops.copy_rect(out, torch.empty(b, m.out_channels, *valid, device=x.device), *valid)
             return out
+        if valid is not None:
+            raise ops._lib.RpeError('BasicEncoder: pad_encoders needs a padded map the tuned kernels take')
         y = ops.conv_direct(x, m.weight, m.bias, 1, 0)           # (maps whose rows are not whole 16-byte quads)
         if split_act:
             y[:, :half] = torch.tanh(y[:, :half])
@@ -419,6 +454,8 @@ class BasicEncoder(nn.Module):
                 and all(im.is_contiguous() and im.dtype == torch.float32 and im.device == first.device for im in images) and not _overlap(images):
             recorded, wkey = _recording(self, self)
             key = (tuple(tuple(im.shape) for im in images), first.device.index, ops.raw_stream(), split_act, _switches(), self.training, wkey)
+            if self.pad_encoders:                                 # (a pass without the key keeps the key it always had)
+                key += ('pad_encoders',)
             rec = recorded.get(key)
             if rec is not None:
                 out = torch.empty(rec.out_shape, device=first.device)
@@ -449,8 +486,37 @@ class BasicEncoder(nn.Module):
             x = (torch.cat(list(x), dim=0) if many else x).contiguous()
             x = conv_norm_act(self.conv1, self.norm1, 2 * (x / 255.0) - 1.0 if raw255 else x, relu=True)
         x = self.layer1[1](self.layer1[0](x, x_norm))
-        x = self.layer3(self.layer2(x))
-        return self._final(x, split_act)
+        padded = self._padded(hh, ww)
+        if padded is None:
+            x = self.layer3(self.layer2(x))
+            return self._final(x, split_act)
+        # pad_encoders: layer1's output enters the zero-padded pitch by one strided copy; from here every map is P2 / P4 / P8 with the true
+        # 1/2, 1/4, 1/8 map as content, every stride-2 layer keeps input = 2 x output, and every launch stores zero outside the content
+        (hp, wp), h8, w8 = padded, hh // 8, ww // 8
+        ws = self._ws = dict(valid=(h8, w8), p2=self._p2(x.shape[0], 4 * hp, 4 * wp, (4 * h8, 4 * w8), x.device))
+        x = ops.copy_rect(x, ws['p2'], 4 * h8, 4 * w8)
+        for name, layer, v in (('l2', self.layer2, (2 * h8, 2 * w8)), ('l3', self.layer3, (h8, w8))):
+            ws[name] = x = layer[1](layer[0](x, valid=v), valid=v)
+        return self._final(x, split_act, valid=(h8, w8))
+
+    def _padded(self, hh, ww):
+        """padded_size of the 1/8 map when this pass runs layer2, layer3 and the output layer on zero-padded maps (pad_encoders), else None:
+        switch off, a 1/8 map the tuned kernels take as it is (the predicate of RAFT._padded), or an image that is no whole number of 8x8 cells."""
+        if not (self.pad_encoders or PAD_ENCODERS) or hh % 8 or ww % 8:
+            return None
+        _check_pad_encoders(True)
+        hp, wp = padded_size(hh // 8, ww // 8)
+        return None if (hp, wp) == (hh // 8, ww // 8) else (hp, wp)
+
+    def _p2(self, n, h2, w2, content, device):
+        """The zero-filled 64-channel map layer1's output is copied into: allocated and cleared once per (batch, size, content, device: two image sizes may share a padded size) -- the copy
+        writes the content only and nothing else writes it, so its padding stays zero pass after pass (single-stream use, as RAFT._workspace).
+        A recorded pass keeps the one it was recorded with."""
+        cache = self.__dict__.setdefault('_p2_cache', {})
+        key = (n, h2, w2, content, str(device))
+        if key not in cache:
+            _bounded_put(cache, key, torch.zeros(n, 64, h2, w2, device=device), keep=2)
+        return cache[key]
 
 
 class FlowHead(nn.Module):
@@ -735,12 +801,16 @@ class RAFT(nn.Module):
         # on maps zero-padded to padded_size(h8, w8) instead of on the generic convolution; the encoders keep the generic route there.
         self.pad_maps = bool(config.get('pad_maps', False))
         self._check_pad_maps()
+        # ``pad_encoders`` (opt-in): at the same sizes both encoders run layer2, layer3 and the output layer on zero-padded maps (BasicEncoder._padded)
+        self.pad_encoders = bool(config.get('pad_encoders', False))
+        _check_pad_encoders(self.pad_encoders)
         self.iters = int(config.get('iters', 12))
         self.hidden_dim = self.context_dim = 128
         self.corr_levels, self.corr_radius = 4, 4
         drop = config.get('dropout', 0.0)
         self.fnet = BasicEncoder(output_dim=256, norm_fn='instance', dropout=drop)
         self.cnet = BasicEncoder(output_dim=256, norm_fn='batch', dropout=drop)
+        self.fnet.pad_encoders = self.cnet.pad_encoders = self.pad_encoders
         self.update_block = BasicUpdateBlock(self.corr_levels, self.corr_radius, hidden_dim=128)
         self._pyr = None
         self._ws = None
@@ -860,12 +930,14 @@ class RAFT(nn.Module):
     @torch.no_grad()
     def encode_features(self, images):
         """fnet on raw 0..255 images (normalised like forward does); one batch or a list of batches encoded as one."""
+        _check_pad_encoders(self.pad_encoders)
         return self.fnet(images, raw255=True).float()
 
     @torch.no_grad()
     def encode_context(self, images):
         """cnet on raw 0..255 images (one batch or a list of batches): (N,256,H/8,W/8) = (tanh(net) | relu(inp)), the initial
         hidden state and the context features of core/RAFT/core/raft.py, activated in the output layer's epilogue."""
+        _check_pad_encoders(self.pad_encoders)
         return self.cnet(images, raw255=True, split_act=True)
 
     @torch.no_grad()
