@@ -27,7 +27,7 @@ extern "C" {
 
 #define RPE_F32 0
 #define RPE_F64 1
-#define RPE_F16 2      /* rpe_corr_build_ex only: feature maps rounded to fp16 */
+#define RPE_F16 2      /* rpe_corr_build_ex and the rpe_corr_alt_*_ex / _dt entry points only: feature maps rounded to fp16 */
 #define RPE_F32X3 3    /* rpe_corr_build_ex only: f32 feature maps, every f32 product evaluated as six bf16 products (3-way exact split) */
 
 /* solver modes of rpe_pose_solve */
@@ -63,7 +63,9 @@ const char *rpe_version(void);
  *   rpe_conv_wino_v, rpe_conv_wino24_v, rpe_conv_wino1d_v, rpe_conv1x1_v (struct rpe_conv_desc_v), rpe_stem_conv_v, rpe_conv3x3_to2_flow_v,
  *   rpe_corr_lookup_ex, rpe_corr_alt_lookup_ex, rpe_upsample_convex_ex, rpe_copy_rect with RPE_OP_* kinds 22-31, and the entry points of the
  *   encoders on zero-padded maps: rpe_enc_conv_wino_v, rpe_enc_conv_wino24_v, rpe_enc_conv_s2_v, rpe_enc_conv_s2_m96_v, rpe_instnorm_apply_v
- *   with RPE_OP_* kinds 34-38 (32 and 33 are the event ops); the next RPE_ABI_MINOR bump counts them and rpe_conv_wino24*. */
+ *   with RPE_OP_* kinds 34-38 (32 and 33 are the event ops), and the fp16 feature maps of the correlation without the volume:
+ *   rpe_corr_alt_bytes_ex, rpe_corr_alt_prepare_ex, rpe_corr_alt_lookup_dt with RPE_OP_CORR_ALT_PREPARE_EX / RPE_OP_CORR_ALT_LOOKUP_DT (39, 40);
+ *   the next RPE_ABI_MINOR bump counts them and rpe_conv_wino24*. */
 #define RPE_ABI_VERSION 5
 #define RPE_ABI_MINOR 4
 int rpe_abi_minor(void);
@@ -318,7 +320,7 @@ int rpe_corr_export_level(const void *pyramid, int b, int h8, int w8, int levels
 /* ---- Correlation WITHOUT the all-pairs volume (upstream RAFT's alternate_corr; csrc/corr_alt.hip).  The window of every query is
  * recomputed from the two feature maps at every lookup; what is kept between lookups is a scratch of pixel-major feature maps:
  * fmap1 / sqrt(c) and fmap2 with its levels - 1 pooled copies (2x2 mean, stride 2, sizes floored) -- pooling fmap2 and pooling the
- * correlation over its target axes are the same linear map.  f32 only; c as rpe_corr_build takes it (a multiple of 16, <= 256).
+ * correlation over its target axes are the same linear map.  f32 (fp16: the _ex / _dt forms below); c as rpe_corr_build takes it (a multiple of 16, <= 256).
  * rpe_corr_alt_bytes: bytes of the scratch; 0 for exactly the (b, h8, w8, levels) for which rpe_corr_pyramid_bytes_ex(.., RPE_F32) is 0
  * (and for a c the route does not take).  At most b c h8 w8 4 (1 + 4/3) bytes plus RPE_CORR_ALT_PAD bytes per level. */
 #define RPE_CORR_ALT_PAD 512
@@ -334,6 +336,25 @@ int rpe_corr_alt_lookup(const void *scratch, const float *coords, int b, int c, 
 /* rpe_corr_alt_lookup with coords and out in (map_h, map_w) maps, as rpe_corr_lookup_ex. */
 int rpe_corr_alt_lookup_ex(const void *scratch, const float *coords, int b, int c, int h8, int w8, int levels, int radius, int map_h, int map_w,
                            float *out, void *stream);
+/* The same route with the precision of the scratch selectable (BASELINE config 5 on this route; upstream's AlternateCorrBlock under
+ * autocast): feature_dtype = RPE_F32 forwards to the three functions above, bit for bit; RPE_F16 keeps the scratch in fp16 and runs the
+ * window products on the 16-bit matrix cores (v_mfma_f32_32x32x16_f16, f32 accumulation); anything else -> RPE_E_BADARG (0 bytes).
+ *   Layout (RPE_F16): as above -- pixel-major, a pixel's c channels contiguous and now 2 c bytes apart, the blocks F1, F2_0 .. F2_{levels-1}
+ *     each rounded up to 256 bytes.
+ *   Rounding: F1 = half(fmap1) and F2_0 = half(fmap2), round to nearest even, UNSCALED; F2_l (l >= 1) is pooled from the STORED fp16 F2_{l-1}:
+ *     the four values converted to f32, summed in row-major order, times 0.25, rounded once to fp16 (upstream pools its fp16 maps level
+ *     after level; sizes floored).  The lookup accumulates the c products of a window value in f32 in a fixed order and multiplies the sum by
+ *     1 / sqrt(c) in f32, so a c that is no power of 4 loses nothing in the features.  Blend, taps, zeros outside the map, channel order
+ *     and the bit-for-bit independence of a query from its neighbours and its batch are those of rpe_corr_alt_lookup.
+ *   Bytes (RPE_F16): 0 exactly where rpe_corr_alt_bytes is 0; otherwise at least 2 (b c h8 w8 2) and at most b c h8 w8 2 (1 + 4/3) plus
+ *     RPE_CORR_ALT_PAD bytes per level -- half of the f32 scratch up to that padding.
+ * The argument checks are those of the f32 forms (null pointers, 16-byte alignment of the scratch, radius 4, the geometry rule,
+ * map_h >= h8, map_w >= w8; b > 65535 -> RPE_E_UNSUPPORTED).  rpe_corr_alt_lookup_dt with map_h = h8, map_w = w8 is the dense lookup. */
+size_t rpe_corr_alt_bytes_ex(int b, int c, int h8, int w8, int levels, int feature_dtype);
+int rpe_corr_alt_prepare_ex(const float *fmap1, const float *fmap2, int b, int c, int h8, int w8, int levels, int feature_dtype, void *scratch,
+                            void *stream);
+int rpe_corr_alt_lookup_dt(const void *scratch, const float *coords, int b, int c, int h8, int w8, int levels, int radius, int map_h, int map_w,
+                           int feature_dtype, float *out, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * RAFT update block, element-wise halves of SepConvGRU (core/RAFT/core/update.py) fused around the
@@ -664,6 +685,8 @@ int rpe_instnorm_apply_v(const float *x, const float *mean_inv, int b, int c, in
 #define RPE_OP_ENC_CONV_S2_V 36    /*       const rpe_conv_desc_v * -> rpe_enc_conv_s2_v   */
 #define RPE_OP_ENC_CONV_S2_M96_V 37 /*      const rpe_conv_desc_v * -> rpe_enc_conv_s2_m96_v */
 #define RPE_OP_INSTNORM_APPLY_V 38 /*       const rpe_instnorm_apply_v_args *              */
+#define RPE_OP_CORR_ALT_PREPARE_EX 39 /*    const rpe_corr_alt_prepare_ex_args *           */
+#define RPE_OP_CORR_ALT_LOOKUP_DT 40 /*     const rpe_corr_alt_lookup_dt_args *            */
 typedef struct rpe_op {
     int kind;                      /* RPE_OP_*                                             */
     int stream;                    /* index into rpe_run_ops' streams[]                    */
@@ -714,6 +737,12 @@ typedef struct rpe_copy_rect_args {
 typedef struct rpe_instnorm_apply_v_args {
     const float *x, *mean_inv; int b, c, h, w, h_valid, w_valid, relu; const float *residual, *residual_mean_inv; float *out;
 } rpe_instnorm_apply_v_args;
+typedef struct rpe_corr_alt_prepare_ex_args {
+    const float *fmap1, *fmap2; int b, c, h8, w8, levels, feature_dtype; void *scratch;
+} rpe_corr_alt_prepare_ex_args;
+typedef struct rpe_corr_alt_lookup_dt_args {
+    const void *scratch; const float *coords; int b, c, h8, w8, levels, radius, map_h, map_w, feature_dtype; float *out;
+} rpe_corr_alt_lookup_dt_args;
 /* streams: n_streams hipStream_t handles (NULL = the default stream).  failed_op may be NULL. */
 int rpe_run_ops(const rpe_op *ops, int n_ops, void *const *streams, int n_streams, int *failed_op);
 

@@ -20,6 +20,14 @@
 // 8t .. 8t+3, lanes 32-63 channels 8t+4 .. 8t+7, step by step), which depends on the query's row of F1 and the pixel's row of F2_l only --
 // not on the box, the round or the neighbours' flow --, so a query's 81 outputs are bit-identical however its neighbours move and
 // whichever batch it sits in.  No atomics: every output has one writer.
+//
+// RPE_F16 features (rpe_corr_alt_prepare_ex / rpe_corr_alt_lookup_dt; upstream's AlternateCorrBlock under autocast): the same scratch in
+// fp16, a pixel's c channels 2 c bytes apart, blocks still rounded to 256 bytes and in the same order.  F1 = half(fmap1) and F2_0 =
+// half(fmap2), round to nearest even and UNSCALED; F2_l = half(0.25 * (sum of the four STORED fp16 values of F2_{l-1}, in f32, k_alt_pool's
+// order)): one rounding per level, upstream's fp16 avg_pool2d level after level.  The lookup is the same kernel (a template on the operand
+// type) with the products on v_mfma_f32_32x32x16_f16 -- lane (l31, lh) holds channels 16t + 8 lh .. + 7 of its row, one 16-byte load per
+// operand and 16 channels -- f32 accumulation in the fixed order t = 0, 1, .., and 1 / sqrt(c) applied in f32 where the accumulators go
+// to the LDS product (so a c that is no power of 4 costs the features nothing).  Rounds, boxes, blend and addressing are shared code.
 #include "rpe_common.h"
 #include "corr_taps.h"
 
@@ -34,19 +42,25 @@
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+// the 16-byte piece of a pixel's channels a lane loads per operand: V channels of type T
+template <typename T> struct AltVec;
+template <> struct AltVec<float> { typedef f32x4 type; static constexpr int V = 4; };
+template <> struct AltVec<_Float16> { typedef f16x8 type; static constexpr int V = 8; };
 
 struct AltGeom {
     int b, c, h8, w8, levels;
     int h[ALT_LEVELS], w[ALT_LEVELS];
-    long long f2[ALT_LEVELS];           // float offset of F2_l (F1 is at 0)
-    long long total;                    // floats
+    long long f2[ALT_LEVELS];           // element offset of F2_l (F1 is at 0)
+    long long total;                    // elements (floats, or halves with esize = 2)
 };
 
-static bool alt_geom(int b, int c, int h8, int w8, int levels, AltGeom& G) {
+static bool alt_geom(int b, int c, int h8, int w8, int levels, AltGeom& G, int esize = 4) {
     if (c <= 0 || c > 256 || c % 16 != 0) return false;                                  // rpe_corr_build's channel rule
     if (rpe_corr_pyramid_bytes_ex(b, h8, w8, levels, RPE_F32) == 0) return false;       // the pyramid route's geometry rule
     G.b = b; G.c = c; G.h8 = h8; G.w8 = w8; G.levels = levels;
-    const long long al = ALT_ALIGN / 4;
+    const long long al = ALT_ALIGN / esize;
     long long off = ((long long)b * h8 * w8 * c + al - 1) / al * al;
     int h = h8, w = w8;
     for (int l = 0; l < ALT_LEVELS; ++l) {
@@ -63,14 +77,22 @@ extern "C" size_t rpe_corr_alt_bytes(int b, int c, int h8, int w8, int levels) {
     return alt_geom(b, c, h8, w8, levels, G) ? (size_t)G.total * 4 : 0;
 }
 
+extern "C" size_t rpe_corr_alt_bytes_ex(int b, int c, int h8, int w8, int levels, int feature_dtype) {
+    if (feature_dtype == RPE_F32) return rpe_corr_alt_bytes(b, c, h8, w8, levels);
+    AltGeom G;
+    return feature_dtype == RPE_F16 && alt_geom(b, c, h8, w8, levels, G, 2) ? (size_t)G.total * 2 : 0;
+}
+
 // ------------------------------------------------------------------------------------------------ prepare
 // (b, C, n) -> (b, n, C) * scale through a 32 x 32 LDS tile: reads and writes both run along their fastest axis
-__global__ __launch_bounds__(256) void k_alt_pack(const float* __restrict__ f, float* __restrict__ out, int C, int n, float scale) {
+// (T = _Float16: the product rounded to nearest even, like tensor.half(); the caller passes scale 1)
+template <typename T>
+__global__ __launch_bounds__(256) void k_alt_pack(const float* __restrict__ f, T* __restrict__ out, int C, int n, float scale) {
     __shared__ float tile[32][33];
     const int bz = blockIdx.z, p0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     const float* src = f + (size_t)bz * C * n;
-    float* dst = out + (size_t)bz * n * C;
+    T* dst = out + (size_t)bz * n * C;
     for (int r = ty; r < 32; r += 8) {
         const int ch = c0 + r, p = p0 + tx;
         tile[r][tx] = (ch < C && p < n) ? src[(size_t)ch * n + p] : 0.0f;
@@ -78,42 +100,57 @@ __global__ __launch_bounds__(256) void k_alt_pack(const float* __restrict__ f, f
     __syncthreads();
     for (int r = ty; r < 32; r += 8) {
         const int p = p0 + r, ch = c0 + tx;
-        if (p < n && ch < C) dst[(size_t)p * C + ch] = tile[tx][r] * scale;
+        if (p < n && ch < C) dst[(size_t)p * C + ch] = (T)(tile[tx][r] * scale);
     }
 }
 
 // 2x2 mean, stride 2, floored sizes, in F.avg_pool2d's order of operations (row-major sum of the window, then the division)
-__global__ __launch_bounds__(256) void k_alt_pool(const float* __restrict__ src, float* __restrict__ dst, int C4, int hs, int ws, int hd, int wd, long long total) {
+// (T = _Float16: the four stored values summed in f32 in that order, times 0.25, rounded once to fp16; C4 = c / 8, a thread's 16 bytes)
+template <typename T>
+__global__ __launch_bounds__(256) void k_alt_pool(const T* __restrict__ src, T* __restrict__ dst, int C4, int hs, int ws, int hd, int wd, long long total) {
+    typedef typename AltVec<T>::type vec;
     const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;           // (b, y, x, c / 4)
     if (e >= total) return;
     const int c4 = (int)(e % C4);
     const long long p = e / C4;
     const int x = (int)(p % wd), y = (int)((p / wd) % hd);
     const long long bz = p / ((long long)wd * hd);
-    const f32x4* s = (const f32x4*)src + ((bz * hs + 2 * y) * ws + 2 * x) * C4 + c4;
-    const f32x4 v00 = s[0], v01 = s[C4], v10 = s[(long long)ws * C4], v11 = s[(long long)ws * C4 + C4];
-    f32x4 o;
+    const vec* s = (const vec*)src + ((bz * hs + 2 * y) * ws + 2 * x) * C4 + c4;
+    const vec v00 = s[0], v01 = s[C4], v10 = s[(long long)ws * C4], v11 = s[(long long)ws * C4 + C4];
+    vec o;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) o[k] = rn_mul(rn_add(rn_add(rn_add(v00[k], v01[k]), v10[k]), v11[k]), 0.25f);
-    ((f32x4*)dst)[e] = o;
+    for (int k = 0; k < AltVec<T>::V; ++k) o[k] = (T)rn_mul(rn_add(rn_add(rn_add((float)v00[k], (float)v01[k]), (float)v10[k]), (float)v11[k]), 0.25f);
+    ((vec*)dst)[e] = o;
+}
+
+template <typename T>
+static int alt_prepare(const float* fmap1, const float* fmap2, const AltGeom& G, float scale1, T* base, hipStream_t s) {
+    const int b = G.b, c = G.c, nq = G.h8 * G.w8, V = AltVec<T>::V;
+    const dim3 grid(ceil_div(nq, 32), ceil_div(c, 32), b);
+    hipLaunchKernelGGL(k_alt_pack<T>, grid, dim3(256), 0, s, fmap1, base, c, nq, scale1);
+    hipLaunchKernelGGL(k_alt_pack<T>, grid, dim3(256), 0, s, fmap2, base + G.f2[0], c, nq, 1.0f);
+    for (int l = 1; l < G.levels; ++l) {
+        const long long total = (long long)b * G.h[l] * G.w[l] * (c / V);
+        hipLaunchKernelGGL(k_alt_pool<T>, dim3(ceil_div(total, 256)), dim3(256), 0, s, (const T*)(base + G.f2[l - 1]), base + G.f2[l], c / V, G.h[l - 1],
+                           G.w[l - 1], G.h[l], G.w[l], total);
+    }
+    return rpe_check_launch();
 }
 
 extern "C" int rpe_corr_alt_prepare(const float* fmap1, const float* fmap2, int b, int c, int h8, int w8, int levels, void* scratch, void* stream) {
     AltGeom G;
     if (!fmap1 || !fmap2 || !scratch || (((uintptr_t)scratch) & 15) || !alt_geom(b, c, h8, w8, levels, G)) return RPE_E_BADARG;
     if (b > 65535) return RPE_E_UNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    float* base = (float*)scratch;
-    const int nq = h8 * w8;
-    const dim3 grid(ceil_div(nq, 32), ceil_div(c, 32), b);
-    hipLaunchKernelGGL(k_alt_pack, grid, dim3(256), 0, s, fmap1, base, c, nq, 1.0f / sqrtf((float)c));
-    hipLaunchKernelGGL(k_alt_pack, grid, dim3(256), 0, s, fmap2, base + G.f2[0], c, nq, 1.0f);
-    for (int l = 1; l < levels; ++l) {
-        const long long total = (long long)b * G.h[l] * G.w[l] * (c / 4);
-        hipLaunchKernelGGL(k_alt_pool, dim3(ceil_div(total, 256)), dim3(256), 0, s, (const float*)(base + G.f2[l - 1]), base + G.f2[l], c / 4, G.h[l - 1],
-                           G.w[l - 1], G.h[l], G.w[l], total);
-    }
-    return rpe_check_launch();
+    return alt_prepare<float>(fmap1, fmap2, G, 1.0f / sqrtf((float)c), (float*)scratch, (hipStream_t)stream);
+}
+
+extern "C" int rpe_corr_alt_prepare_ex(const float* fmap1, const float* fmap2, int b, int c, int h8, int w8, int levels, int feature_dtype, void* scratch,
+                                       void* stream) {
+    if (feature_dtype == RPE_F32) return rpe_corr_alt_prepare(fmap1, fmap2, b, c, h8, w8, levels, scratch, stream);
+    AltGeom G;
+    if (feature_dtype != RPE_F16 || !fmap1 || !fmap2 || !scratch || (((uintptr_t)scratch) & 15) || !alt_geom(b, c, h8, w8, levels, G, 2)) return RPE_E_BADARG;
+    if (b > 65535) return RPE_E_UNSUPPORTED;
+    return alt_prepare<_Float16>(fmap1, fmap2, G, 1.0f, (_Float16*)scratch, (hipStream_t)stream);      // unscaled: the lookup applies 1 / sqrt(c)
 }
 
 // ------------------------------------------------------------------------------------------------ lookup
@@ -131,8 +168,13 @@ __device__ __forceinline__ int wave_max_i(int v) {
 // Q (64 x c) . Box (c x 32 NB) for this wave's NB column blocks; a[m] / bp[n]: this lane's row of F1 / F2_l, already offset by its half's
 // four channels.  THE summation order of the route: per 8 channels four matrix steps, step j adding channel 8t + j (lanes 0-31's operand)
 // and then channel 8t + 4 + j (lanes 32-63's) to the accumulator.
-template <int NB>
-__device__ __forceinline__ void alt_products(const float* const (&a)[2], const float* const (&bp)[3], int c, float* prod, const int (&col)[3], int l31, int lh) {
+// T = _Float16: the pointers are offset by the half's EIGHT channels and one v_mfma_f32_32x32x16_f16 adds the 16 channels of step t (operand
+// element j of lane half h = channel 16t + 8h + j, the same for both operands) -- the order over t is the route's order; ``scale`` =
+// 1 / sqrt(c) multiplies the finished accumulators (f32: F1 carries it, the accumulators are stored as they are).
+template <typename T, int NB>
+__device__ __forceinline__ void alt_products(const T* const (&a)[2], const T* const (&bp)[3], int c, float* prod, const int (&col)[3], int l31, int lh, float scale) {
+    typedef typename AltVec<T>::type vec;
+    constexpr bool F16 = sizeof(T) == 2;
     f32x16 acc[2][NB];
 #pragma unroll
     for (int m = 0; m < 2; ++m)
@@ -140,19 +182,34 @@ __device__ __forceinline__ void alt_products(const float* const (&a)[2], const f
         for (int n = 0; n < NB; ++n)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.0f;
-#pragma unroll 2
-    for (int t = 0; t < c; t += 8) {
-        f32x4 av[2], bv[NB];
+    if constexpr (F16) {
+#pragma unroll 4
+        for (int t = 0; t < c; t += 16) {
+            f16x8 av[2], bv[NB];
 #pragma unroll
-        for (int m = 0; m < 2; ++m) av[m] = *(const f32x4*)(a[m] + t);
+            for (int m = 0; m < 2; ++m) av[m] = *(const f16x8*)(a[m] + t);
 #pragma unroll
-        for (int n = 0; n < NB; ++n) bv[n] = *(const f32x4*)(bp[n] + t);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
+            for (int n = 0; n < NB; ++n) bv[n] = *(const f16x8*)(bp[n] + t);
 #pragma unroll
             for (int m = 0; m < 2; ++m)
 #pragma unroll
-                for (int n = 0; n < NB; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[m][j], bv[n][j], acc[m][n], 0, 0, 0);
+                for (int n = 0; n < NB; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[m], bv[n], acc[m][n], 0, 0, 0);
+        }
+    } else {
+#pragma unroll 2
+        for (int t = 0; t < c; t += 8) {
+            f32x4 av[2], bv[NB];
+#pragma unroll
+            for (int m = 0; m < 2; ++m) av[m] = *(const f32x4*)(a[m] + t);
+#pragma unroll
+            for (int n = 0; n < NB; ++n) bv[n] = *(const f32x4*)(bp[n] + t);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int m = 0; m < 2; ++m)
+#pragma unroll
+                    for (int n = 0; n < NB; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[m][j], bv[n][j], acc[m][n], 0, 0, 0);
+        }
     }
     // C/D layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
 #pragma unroll
@@ -160,21 +217,25 @@ __device__ __forceinline__ void alt_products(const float* const (&a)[2], const f
 #pragma unroll
         for (int n = 0; n < NB; ++n)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) prod[(m * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * ALT_PP + col[n] + l31] = acc[m][n][r];
+            for (int r = 0; r < 16; ++r)
+                prod[(m * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * ALT_PP + col[n] + l31] = F16 ? rn_mul(acc[m][n][r], scale) : acc[m][n][r];
 }
 
 // map_h x map_w: the maps coords and out live in, of which the top-left h8 x w8 is read / written (rpe_corr_alt_lookup_ex: the update loop's
 // padded workspace; = h8 x w8 for dense tensors).  The feature maps and every tap keep the true (h8, w8).
-__global__ __launch_bounds__(256, 1) void k_alt_lookup(const float* __restrict__ scratch, const float* __restrict__ coords, float* __restrict__ out, AltGeom G,
-                                                       int tiles_x, int map_h, int map_w) {
+// T: the scratch's element type (float, or _Float16 with ``scale`` = 1 / sqrt(c); see alt_products).
+template <typename T>
+__global__ __launch_bounds__(256, 1) void k_alt_lookup(const T* __restrict__ scratch, const float* __restrict__ coords, float* __restrict__ out, AltGeom G,
+                                                       int tiles_x, int map_h, int map_w, float scale) {
+    constexpr int V = AltVec<T>::V;
     __shared__ float prod[64 * ALT_PP];
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int l31 = lane & 31, lh = lane >> 5;
     const int l = blockIdx.y, bz = blockIdx.z;
     const int ty0 = (blockIdx.x / tiles_x) * ALT_TQ, tx0 = (blockIdx.x % tiles_x) * ALT_TQ;
     const int nq = G.h8 * G.w8, c = G.c, hl = G.h[l], wl = G.w[l];
-    const float* f1 = scratch + (size_t)bz * nq * c;
-    const float* f2 = scratch + G.f2[l] + (size_t)bz * hl * wl * c;
+    const T* f1 = scratch + (size_t)bz * nq * c;
+    const T* f2 = scratch + G.f2[l] + (size_t)bz * hl * wl * c;
 
     // every wave holds the 64 queries of the tile, lane = query, and plans the rounds for itself: same inputs, same instructions, same plan
     const int qy = ty0 + (lane >> 3), qx = tx0 + (lane & 7);
@@ -195,12 +256,12 @@ __global__ __launch_bounds__(256, 1) void k_alt_lookup(const float* __restrict__
         for (int i = 0; i < WIN; ++i) { X.a0[i] = X.a1[i] = X.a2[i] = 0.0f; Y.a0[i] = Y.a1[i] = Y.a2[i] = 0.0f; }
     }
     // A operands: rows m * 32 + l31 of the tile
-    const float* a[2];
+    const T* a[2];
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
         const int r = m * 32 + l31, ay = ty0 + (r >> 3), ax = tx0 + (r & 7);
         const bool ok = ay < G.h8 && ax < G.w8;
-        a[m] = f1 + (size_t)(ok ? ay * G.w8 + ax : ty0 * G.w8 + tx0) * c + 4 * lh;
+        a[m] = f1 + (size_t)(ok ? ay * G.w8 + ax : ty0 * G.w8 + tx0) * c + V * lh;
     }
     float* obase = out + ((size_t)bz * G.levels + l) * (WIN * WIN) * mp + q;
 
@@ -226,7 +287,7 @@ __global__ __launch_bounds__(256, 1) void k_alt_lookup(const float* __restrict__
         // ---- products: wave wv takes column blocks wv, wv + 4, wv + 8
         const int nmine = nblk > wv ? (nblk - wv + 3) >> 2 : 0;
         if (nmine > 0) {
-            const float* bp[3];
+            const T* bp[3];
             int col[3];
 #pragma unroll
             for (int n = 0; n < 3; ++n) {
@@ -234,11 +295,11 @@ __global__ __launch_bounds__(256, 1) void k_alt_lookup(const float* __restrict__
                 int p = col[n] + l31;
                 p = p < P ? p : 0;                                        // (padding columns: computed, never read)
                 const int py = p / bw, px = p - py * bw;
-                bp[n] = f2 + ((size_t)(by_lo + py) * wl + (bx_lo + px)) * c + 4 * lh;
+                bp[n] = f2 + ((size_t)(by_lo + py) * wl + (bx_lo + px)) * c + V * lh;
             }
-            if (nmine == 1) alt_products<1>(a, bp, c, prod, col, l31, lh);
-            else if (nmine == 2) alt_products<2>(a, bp, c, prod, col, l31, lh);
-            else alt_products<3>(a, bp, c, prod, col, l31, lh);
+            if (nmine == 1) alt_products<T, 1>(a, bp, c, prod, col, l31, lh, scale);
+            else if (nmine == 2) alt_products<T, 2>(a, bp, c, prod, col, l31, lh, scale);
+            else alt_products<T, 3>(a, bp, c, prod, col, l31, lh, scale);
         }
         __syncthreads();
         // ---- blend: lane = query, wave wv takes the window rows j = wv, wv + 4, wv + 8.  Window pixel (cc, rr) of the query is box pixel
@@ -276,13 +337,19 @@ __global__ __launch_bounds__(256, 1) void k_alt_lookup(const float* __restrict__
     }
 }
 
+template <typename T>
+static int alt_lookup(const void* scratch, const float* coords, const AltGeom& G, int map_h, int map_w, float scale, float* out, void* stream) {
+    const int tiles_x = ceil_div(G.w8, ALT_TQ), tiles_y = ceil_div(G.h8, ALT_TQ);
+    hipLaunchKernelGGL(k_alt_lookup<T>, dim3(tiles_x * tiles_y, G.levels, G.b), dim3(256), 0, (hipStream_t)stream, (const T*)scratch, coords, out, G, tiles_x,
+                       map_h, map_w, scale);
+    return rpe_check_launch();
+}
+
 extern "C" int rpe_corr_alt_lookup(const void* scratch, const float* coords, int b, int c, int h8, int w8, int levels, int radius, float* out, void* stream) {
     AltGeom G;
     if (!scratch || !coords || !out || radius != RADIUS || (((uintptr_t)scratch) & 15) || !alt_geom(b, c, h8, w8, levels, G)) return RPE_E_BADARG;
     if (b > 65535) return RPE_E_UNSUPPORTED;
-    const int tiles_x = ceil_div(w8, ALT_TQ), tiles_y = ceil_div(h8, ALT_TQ);
-    hipLaunchKernelGGL(k_alt_lookup, dim3(tiles_x * tiles_y, levels, b), dim3(256), 0, (hipStream_t)stream, (const float*)scratch, coords, out, G, tiles_x, h8, w8);
-    return rpe_check_launch();
+    return alt_lookup<float>(scratch, coords, G, h8, w8, 1.0f, out, stream);
 }
 
 extern "C" int rpe_corr_alt_lookup_ex(const void* scratch, const float* coords, int b, int c, int h8, int w8, int levels, int radius, int map_h, int map_w,
@@ -291,8 +358,16 @@ extern "C" int rpe_corr_alt_lookup_ex(const void* scratch, const float* coords, 
     if (!scratch || !coords || !out || radius != RADIUS || map_h < h8 || map_w < w8 || (((uintptr_t)scratch) & 15) || !alt_geom(b, c, h8, w8, levels, G))
         return RPE_E_BADARG;
     if (b > 65535) return RPE_E_UNSUPPORTED;
-    const int tiles_x = ceil_div(w8, ALT_TQ), tiles_y = ceil_div(h8, ALT_TQ);
-    hipLaunchKernelGGL(k_alt_lookup, dim3(tiles_x * tiles_y, levels, b), dim3(256), 0, (hipStream_t)stream, (const float*)scratch, coords, out, G, tiles_x,
-                       map_h, map_w);
-    return rpe_check_launch();
+    return alt_lookup<float>(scratch, coords, G, map_h, map_w, 1.0f, out, stream);
+}
+
+extern "C" int rpe_corr_alt_lookup_dt(const void* scratch, const float* coords, int b, int c, int h8, int w8, int levels, int radius, int map_h, int map_w,
+                                      int feature_dtype, float* out, void* stream) {
+    if (feature_dtype == RPE_F32) return rpe_corr_alt_lookup_ex(scratch, coords, b, c, h8, w8, levels, radius, map_h, map_w, out, stream);
+    AltGeom G;
+    if (feature_dtype != RPE_F16 || !scratch || !coords || !out || radius != RADIUS || map_h < h8 || map_w < w8 || (((uintptr_t)scratch) & 15) ||
+        !alt_geom(b, c, h8, w8, levels, G, 2))
+        return RPE_E_BADARG;
+    if (b > 65535) return RPE_E_UNSUPPORTED;
+    return alt_lookup<_Float16>(scratch, coords, G, map_h, map_w, 1.0f / sqrtf((float)c), out, stream);
 }

@@ -27,6 +27,8 @@ static_assert(sizeof(rpe_flow_update_v_args) == 104, "rpe_flow_update_v_args: la
 static_assert(sizeof(rpe_upsample_convex_ex_args) == 48, "rpe_upsample_convex_ex_args: layout changed -- update _lib.py and RPE_ABI_VERSION");
 static_assert(sizeof(rpe_copy_rect_args) == 80, "rpe_copy_rect_args: layout changed -- update _lib.py and RPE_ABI_VERSION");
 static_assert(sizeof(rpe_instnorm_apply_v_args) == 72, "rpe_instnorm_apply_v_args: layout changed -- update _lib.py and RPE_ABI_VERSION");
+static_assert(sizeof(rpe_corr_alt_prepare_ex_args) == 48, "rpe_corr_alt_prepare_ex_args: layout changed -- update _lib.py and RPE_ABI_VERSION");
+static_assert(sizeof(rpe_corr_alt_lookup_dt_args) == 64, "rpe_corr_alt_lookup_dt_args: layout changed -- update _lib.py and RPE_ABI_VERSION");
 static_assert(sizeof(rpe_solve_opts) == 32, "rpe_solve_opts: layout changed -- update _lib.py and RPE_ABI_VERSION");
 
 template <typename A>
@@ -135,6 +137,15 @@ static int run_one(const rpe_op& op, void* const* streams, int n_streams) {
     case RPE_OP_INSTNORM_APPLY_V: {
         const auto* a = as<rpe_instnorm_apply_v_args>(op);
         return rpe_instnorm_apply_v(a->x, a->mean_inv, a->b, a->c, a->h, a->w, a->h_valid, a->w_valid, a->relu, a->residual, a->residual_mean_inv, a->out, st);
+    }
+    case RPE_OP_CORR_ALT_PREPARE_EX: {
+        const auto* a = as<rpe_corr_alt_prepare_ex_args>(op);
+        return rpe_corr_alt_prepare_ex(a->fmap1, a->fmap2, a->b, a->c, a->h8, a->w8, a->levels, a->feature_dtype, a->scratch, st);
+    }
+    case RPE_OP_CORR_ALT_LOOKUP_DT: {
+        const auto* a = as<rpe_corr_alt_lookup_dt_args>(op);
+        return rpe_corr_alt_lookup_dt(a->scratch, a->coords, a->b, a->c, a->h8, a->w8, a->levels, a->radius, a->map_h, a->map_w, a->feature_dtype,
+                                      a->out, st);
     }
     case RPE_OP_EVENT_RECORD: {
         hipEvent_t ev = (hipEvent_t) * static_cast<void* const*>(op.args);

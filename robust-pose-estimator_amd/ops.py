@@ -529,11 +529,14 @@ class CorrPyramid:
 class AltCorr:
     """The correlation of a batch of pairs WITHOUT the all-pairs volume (upstream RAFT's ``alternate_corr``; csrc/corr_alt.hip): the
     device buffer holds fmap1 / sqrt(c) and fmap2 with its pooled copies, pixel-major, and every lookup recomputes its windows from
-    them.  f32 only.  Same build / lookup interface as CorrPyramid (what RAFT's loop calls); ``nbytes`` = the size of the buffer."""
+    them.  Same build / lookup interface as CorrPyramid (what RAFT's loop calls); ``nbytes`` = the size of the buffer.
+    ``fp16=True`` (rpe_corr_alt_prepare_ex / rpe_corr_alt_lookup_dt with RPE_F16): the buffer holds half(fmap1) and half(fmap2), unscaled,
+    with the pooled copies rounded to fp16 level after level -- half the bytes --, the window products run on the 16-bit matrix cores with
+    f32 accumulation and 1 / sqrt(c) is applied in f32.  ``fp16=False`` makes exactly the f32 calls."""
 
-    def __init__(self, b, c, h8, w8, levels=4, radius=4, device='cuda'):
-        self.b, self.c, self.h8, self.w8, self.levels, self.radius = b, c, h8, w8, levels, radius
-        self.nbytes = lib().rpe_corr_alt_bytes(b, c, h8, w8, levels)
+    def __init__(self, b, c, h8, w8, levels=4, radius=4, device='cuda', fp16=False):
+        self.b, self.c, self.h8, self.w8, self.levels, self.radius, self.fp16 = b, c, h8, w8, levels, radius, bool(fp16)
+        self.nbytes = lib().rpe_corr_alt_bytes_ex(b, c, h8, w8, levels, _lib.F16 if self.fp16 else _lib.F32)
         if self.nbytes == 0 or radius != 4:
             raise _lib.RpeError('rpe_corr_alt_bytes: unsupported geometry')
         self.buf = torch.empty(self.nbytes, dtype=torch.uint8, device=device)
@@ -542,16 +545,20 @@ class AltCorr:
         f1, f2 = _dev(fmap1, torch.float32, 'fmap1'), _dev(fmap2, torch.float32, 'fmap2')
         if tuple(f1.shape) != (self.b, self.c, self.h8, self.w8) or f2.shape != f1.shape:
             raise _lib.RpeError('corr alt build: shape mismatch')
+        if self.fp16:
+            return _launch(_lib.OP_CORR_ALT_PREPARE_EX, (ptr(f1), ptr(f2), self.b, self.c, self.h8, self.w8, self.levels, _lib.F16, ptr(self.buf)), (f1, f2, self),
+                           self)
         return _launch(_lib.OP_CORR_ALT_PREPARE, (ptr(f1), ptr(f2), self.b, self.c, self.h8, self.w8, self.levels, ptr(self.buf)), (f1, f2, self), self)
 
     def lookup(self, coords, out=None, prepare=False, map_size=None):
         """``prepare=True`` (needs ``out``): a zero-argument launcher on these buffers, with ``.op`` for an OpList.  ``map_size``: as
-        CorrPyramid.lookup (rpe_corr_alt_lookup_ex)."""
+        CorrPyramid.lookup (rpe_corr_alt_lookup_ex).  With ``fp16`` every form is rpe_corr_alt_lookup_dt (dense: map_size = (h8, w8))."""
         co = _dev(coords, torch.float32, 'coords')
         ch = self.levels * (2 * self.radius + 1) ** 2
         if map_size is not None:
-            return _lookup_ex(self, _lib.OP_CORR_ALT_LOOKUP_EX, (ptr(self.buf), ptr(co), self.b, self.c, self.h8, self.w8, self.levels, self.radius), coords, co,
-                              out, ch, map_size, prepare)
+            return _lookup_ex(self, _lib.OP_CORR_ALT_LOOKUP_DT if self.fp16 else _lib.OP_CORR_ALT_LOOKUP_EX,
+                              (ptr(self.buf), ptr(co), self.b, self.c, self.h8, self.w8, self.levels, self.radius), coords, co, out, ch, map_size, prepare,
+                              tail=(_lib.F16,) if self.fp16 else ())
         if tuple(co.shape) != (self.b, 2, self.h8, self.w8):
             raise _lib.RpeError('corr alt lookup: coords shape mismatch')
         if out is None:
@@ -560,18 +567,22 @@ class AltCorr:
             raise _lib.RpeError('corr alt lookup: a prepared launch needs contiguous coords and a (b, levels*(2r+1)^2, h8, w8) out buffer')
         if tuple(_nchw(out, 'out').shape) != (self.b, ch, self.h8, self.w8):
             raise _lib.RpeError('corr alt lookup: out must be a contiguous (b, levels*(2r+1)^2, h8, w8) buffer')
+        if self.fp16:
+            return _launch(_lib.OP_CORR_ALT_LOOKUP_DT, (ptr(self.buf), ptr(co), self.b, self.c, self.h8, self.w8, self.levels, self.radius, self.h8, self.w8,
+                                                        _lib.F16, ptr(out)), (self, co, out), out, prepare)
         return _launch(_lib.OP_CORR_ALT_LOOKUP, (ptr(self.buf), ptr(co), self.b, self.c, self.h8, self.w8, self.levels, self.radius, ptr(out)),
                        (self, co, out), out, prepare)
 
 
-def _lookup_ex(corr, kind, head, coords, co, out, ch, map_size, prepare):
-    """The pitched lookup of CorrPyramid / AltCorr: ``head`` = the entry point's arguments up to the radius."""
+def _lookup_ex(corr, kind, head, coords, co, out, ch, map_size, prepare, tail=()):
+    """The pitched lookup of CorrPyramid / AltCorr: ``head`` = the entry point's arguments up to the radius, ``tail`` = those between the map
+    size and ``out``."""
     mh, mw = map_size
     if mh < corr.h8 or mw < corr.w8 or co is not coords or tuple(co.shape) != (corr.b, 2, mh, mw):
         raise _lib.RpeError(f'corr lookup: with map_size coords must be a contiguous ({corr.b},2,{mh},{mw}) tensor, the map at least ({corr.h8},{corr.w8})')
     if out is None or tuple(_nchw(out, 'out').shape) != (corr.b, ch, mh, mw):
         raise _lib.RpeError(f'corr lookup: with map_size out must be a contiguous ({corr.b},{ch},{mh},{mw}) buffer')
-    return _launch(kind, (*head, mh, mw, ptr(out)), (corr, co, out), out, prepare)
+    return _launch(kind, (*head, mh, mw, *tail, ptr(out)), (corr, co, out), out, prepare)
 
 
 class _Packed:

@@ -672,7 +672,7 @@ class BasicUpdateBlock(nn.Module):
         launch where that pays (LOOKUP_FUSED), else None."""
         packed_key, P = self.packed_convs(ws['hx'].shape[-1], with_key=True)
         alt = isinstance(pyr, ops.AltCorr)                  # (alternate_corr: lookup into the cor buffer, then convc1 -- LOOKUP_FUSED does not apply)
-        key = (packed_key, None if pyr is None else (pyr.buf.data_ptr(), alt), ws.get('valid'))
+        key = (packed_key, None if pyr is None else (pyr.buf.data_ptr(), 'fp16' if alt and pyr.fp16 else alt), ws.get('valid'))
         return _cached(ws, '_launchers', key, lambda: self._make_launchers(ws, P, pyr, alt), with_key)
 
     def _make_launchers(self, ws, P, pyr, alt):
@@ -794,8 +794,11 @@ class RAFT(nn.Module):
         # fp16 where the correlation consumes them (16-bit matrix cores, f32 accumulation, f32 pyramid).
         self.mixed_precision = bool(config.get('mixed_precision', False))
         # upstream RAFT's ``alternate_corr``: no all-pairs volume; every iteration recomputes its correlation windows from the feature maps
-        # (ops.AltCorr, csrc/corr_alt.hip).  Opt-in, f32 only.
+        # (ops.AltCorr, csrc/corr_alt.hip).  Opt-in, f32 only -- or, with ``alt_corr_fp16`` (needs alternate_corr), BASELINE config 5 on this
+        # route: the feature maps rounded to fp16 in the scratch (half its bytes), the window products on the 16-bit matrix cores, f32
+        # accumulation and blend.  ``mixed_precision`` keeps meaning the pyramid route's fp16 build and stays refused with alternate_corr.
         self.alternate_corr = bool(config.get('alternate_corr', False))
+        self.alt_corr_fp16 = bool(config.get('alt_corr_fp16', False))
         self._check_alternate_corr()
         # ``pad_maps`` (opt-in): at 1/8 maps the tuned kernels refuse -- odd heights, rows that are not whole 16-byte quads -- the update loop runs
         # on maps zero-padded to padded_size(h8, w8) instead of on the generic convolution; the encoders keep the generic route there.
@@ -830,8 +833,10 @@ class RAFT(nn.Module):
     def _check_alternate_corr(self):
         """The on-the-fly correlation is f32 only: refused together with fp16 features or a bf16x3 variant (at construction, and at every
         pass for the module-level switches)."""
+        if self.alt_corr_fp16 and not self.alternate_corr:
+            raise ops._lib.RpeError('RAFT: alt_corr_fp16 selects the feature precision of alternate_corr and needs alternate_corr: True')
         if self.alternate_corr and (self.mixed_precision or CORR_BF16X3 or CONV_BF16X3):
-            raise ops._lib.RpeError('RAFT: alternate_corr is f32 only -- not with mixed_precision, CORR_BF16X3 or CONV_BF16X3')
+            raise ops._lib.RpeError('RAFT: alternate_corr is f32 only (fp16 features: alt_corr_fp16) -- not with mixed_precision, CORR_BF16X3 or CONV_BF16X3')
 
     def _check_pad_maps(self):
         """The valid-extent entry points exist for the f32 Winograd / GEMM kernels only: pad_maps is refused together with the bf16x3 variant of
@@ -852,8 +857,8 @@ class RAFT(nn.Module):
         if self.alternate_corr:
             self._check_alternate_corr()
             c = self.fnet.conv2.out_channels
-            if not isinstance(p, ops.AltCorr) or (p.b, p.c, p.h8, p.w8) != (b, c, h8, w8) or p.buf.device != device:
-                self._pyr = p = ops.AltCorr(b, c, h8, w8, self.corr_levels, self.corr_radius, device=device)
+            if not isinstance(p, ops.AltCorr) or (p.b, p.c, p.h8, p.w8, p.fp16) != (b, c, h8, w8, self.alt_corr_fp16) or p.buf.device != device:
+                self._pyr = p = ops.AltCorr(b, c, h8, w8, self.corr_levels, self.corr_radius, device=device, fp16=self.alt_corr_fp16)
             return p
         x3 = CORR_BF16X3 or CONV_BF16X3
         if p is None or (p.b, p.h8, p.w8) != (b, h8, w8) or p.buf.device != device or getattr(p, 'x3', False) != x3:
@@ -1050,6 +1055,8 @@ class RAFT(nn.Module):
         ws = self._workspace(N, h8, w8, dev, self._padded(h8, w8))
         key = (N, h8, w8, dev.index, ops.raw_stream(), iters, upsample, self.mixed_precision, self.alternate_corr, self.pad_maps, _switches(),
                pyr.buf.data_ptr(), ws['hx'].data_ptr(), wkey)
+        if self.alt_corr_fp16:
+            key += ('alt_corr_fp16',)
         if flow_init is not None or ret_lowres:                       # (a cold pass keeps the key it always had)
             key += ('warm' if flow_init is not None else 'cold', ret_lowres)
         ins = {'f1': fmap1, 'f2': fmap2, 'cnet': cnet}
