@@ -64,7 +64,8 @@ const char *rpe_version(void);
  *   rpe_corr_lookup_ex, rpe_corr_alt_lookup_ex, rpe_upsample_convex_ex, rpe_copy_rect with RPE_OP_* kinds 22-31, and the entry points of the
  *   encoders on zero-padded maps: rpe_enc_conv_wino_v, rpe_enc_conv_wino24_v, rpe_enc_conv_s2_v, rpe_enc_conv_s2_m96_v, rpe_instnorm_apply_v
  *   with RPE_OP_* kinds 34-38 (32 and 33 are the event ops), and the fp16 feature maps of the correlation without the volume:
- *   rpe_corr_alt_bytes_ex, rpe_corr_alt_prepare_ex, rpe_corr_alt_lookup_dt with RPE_OP_CORR_ALT_PREPARE_EX / RPE_OP_CORR_ALT_LOOKUP_DT (39, 40);
+ *   rpe_corr_alt_bytes_ex, rpe_corr_alt_prepare_ex, rpe_corr_alt_lookup_dt with RPE_OP_CORR_ALT_PREPARE_EX / RPE_OP_CORR_ALT_LOOKUP_DT (39, 40),
+ *   and the update block's convolutions with fp16 operands: rpe_conv_f16_packed_bytes, rpe_conv_f16_pack, rpe_conv_f16 with RPE_OP_CONV_F16 (41);
  *   the next RPE_ABI_MINOR bump counts them and rpe_conv_wino24*. */
 #define RPE_ABI_VERSION 5
 #define RPE_ABI_MINOR 4
@@ -590,6 +591,29 @@ int rpe_conv1x1(const rpe_conv_desc *desc, void *stream);
 size_t rpe_conv1x1_x3_packed_bytes(int cout, int cin);
 int rpe_conv1x1_x3_pack(const float *weight, int cout, int cin, void *packed, void *stream);
 int rpe_conv1x1_x3(const rpe_conv_desc *desc, void *stream);
+/* OPT-IN PRECISION CONTRACT (RAFT's ``update_fp16``; never in a headline number): rpe_conv_fused's operation for stride-1 "same" convolutions
+ * with (kh, kw) in {1x1, 3x3, 1x5, 5x1} and fp16 OPERANDS on the 16-bit matrix cores (v_mfma_f32_32x32x16_f16; csrc/conv_f16.hip) -- what
+ * upstream RAFT's mixed_precision (autocast) does to the update block, core/RAFT/core/update.py; call sites core/pose/pose_net.py:47,65,129.
+ *   - every input activation and every weight is rounded to IEEE fp16, round to nearest even, unscaled; the products are exact in f32;
+ *   - the sum is f32 in one fixed order (no atomics, no split K over workgroups), the same for every batch size and launch size: a batch
+ *     row's result does not depend on the batch it is launched in, bit for bit;
+ *   - everything after the sum is f32 exactly as rpe_conv_fused defines it above: bias, add, ReLU / tanh, the GRU gates with hidden / zgate,
+ *     out2 (the kernels share the epilogue's code); activations stay f32 in memory -- only the operands are rounded, while they are staged.
+ * Supported: any cin >= 1 (the pack pads the K tail with zero weights and the kernel stages channels >= cin as zero WITHOUT reading them: what
+ * lies behind the slice cannot enter, not even a NaN through 0 * NaN), any cout, w % 4 == 0, 16-byte aligned slices with batch strides
+ * % 4 == 0, b <= 65535, every mode of rpe_conv_fused (LINEAR, RELU, TANH, GATE_ZR, GATE_H) with bias, add, hidden, zgate, out2, gate_channels;
+ * out may alias hidden.  scale / residual / stats / pre_norm, stride 2, another kernel shape or a misaligned slice -> RPE_E_UNSUPPORTED; a NULL
+ * pointer or a non-positive extent -> RPE_E_BADARG, checked before anything is dereferenced.  desc->packed must come from rpe_conv_f16_pack
+ * (rpe_conv_f16_packed_bytes bytes, 0 = unsupported shape; 16-byte aligned): fp16 in matrix-fragment order, packed on the device.
+ * SPECIAL VALUES (this entry point; the f32 kernels do not share it): an activation or weight with |x| > 65504 becomes +-Inf where round to
+ * nearest even says so (from 65520 on), and +-Inf then follows IEEE through the sum (Inf - Inf, 0 * Inf -> NaN); NaN operands give NaN in
+ * every output they reach, and only there.  Values below the smallest fp16 normal (2^-14) round to fp16 subnormals or zero.
+ * FP16 SUBNORMAL OPERANDS (observed once on an MI355X with a 1x1 identity layer; no test asserts it): they are NOT flushed.  Activations of
+ * 2^-15, 2^-24, 3 * 2^-24 came back exactly, 2^-25 as 0 and 1.5 * 2^-24 as 2^-23 (the ties-to-even roundings into the subnormal range), and
+ * a subnormal weight 2^-20 against 1024 gave 2^-10 exactly: v_cvt_f16_f32 produces subnormals and v_mfma_f32_32x32x16_f16 multiplies them. */
+size_t rpe_conv_f16_packed_bytes(int cout, int cin, int kh, int kw);
+int rpe_conv_f16_pack(const float *weight, int cout, int cin, int kh, int kw, void *packed, void *stream);
+int rpe_conv_f16(const rpe_conv_desc *desc, void *stream);
 /* Generic convolution for every shape the tuned kernels above refuse (odd maps, rows that are not whole 16-byte quads): replaces
  * torch.nn.functional.conv2d(x, weight, bias, stride, padding) as the host code's fallback route, so that every convolution of the
  * reference's RAFT (core/RAFT/core/extractor.py, update.py) runs in this library for any img_size (configuration/infer_f2f.yaml:13).
@@ -687,6 +711,7 @@ int rpe_instnorm_apply_v(const float *x, const float *mean_inv, int b, int c, in
 #define RPE_OP_INSTNORM_APPLY_V 38 /*       const rpe_instnorm_apply_v_args *              */
 #define RPE_OP_CORR_ALT_PREPARE_EX 39 /*    const rpe_corr_alt_prepare_ex_args *           */
 #define RPE_OP_CORR_ALT_LOOKUP_DT 40 /*     const rpe_corr_alt_lookup_dt_args *            */
+#define RPE_OP_CONV_F16 (RPE_OP_CORR_ALT_LOOKUP_DT + 1) /* = 41: const rpe_conv_desc * -> rpe_conv_f16 (the kind after the last one) */
 typedef struct rpe_op {
     int kind;                      /* RPE_OP_*                                             */
     int stream;                    /* index into rpe_run_ops' streams[]                    */

@@ -153,6 +153,7 @@ OP_CORR_LOOKUP_EX, OP_CORR_ALT_LOOKUP_EX, OP_UPSAMPLE_CONVEX_EX, OP_COPY_RECT = 
 OP_EVENT_RECORD, OP_STREAM_WAIT = 32, 33
 OP_ENC_CONV_WINO_V, OP_ENC_CONV_WINO24_V, OP_ENC_CONV_S2_V, OP_ENC_CONV_S2_M96_V, OP_INSTNORM_APPLY_V = 34, 35, 36, 37, 38
 OP_CORR_ALT_PREPARE_EX, OP_CORR_ALT_LOOKUP_DT = 39, 40
+OP_CONV_F16 = 41
 F32, F16 = 0, 2            # RPE_F32 / RPE_F16: the feature_dtype of rpe_corr_alt_*_ex / _dt
 # kind -> (entry point, argument struct) of every op a launch list carries (csrc/oplist.hip's run_one).  An entry point with an argument
 # struct takes its fields in order, then the stream; the rpe_conv_desc kinds take the descriptor by pointer, then the stream.
@@ -183,12 +184,14 @@ ENC_FORM = {'rpe_conv_wino': 'rpe_enc_conv_wino_v', 'rpe_conv_wino24': 'rpe_enc_
             'rpe_conv_fused_m96': 'rpe_enc_conv_s2_m96_v'}
 # likewise behind the event ops: the on-the-fly correlation with a selectable feature precision (RAFT's alt_corr_fp16)
 LIST_OPS_ALT_DT = {OP_CORR_ALT_PREPARE_EX: ('rpe_corr_alt_prepare_ex', CorrAltPrepareExArgs), OP_CORR_ALT_LOOKUP_DT: ('rpe_corr_alt_lookup_dt', CorrAltLookupDtArgs)}
-ALL_LIST_OPS = {**LIST_OPS, **LIST_OPS_ENC, **LIST_OPS_ALT_DT}           # every kind csrc/oplist.hip's run_one carries with an argument block
+# and the update block's convolutions with fp16 operands (RAFT's update_fp16)
+LIST_OPS_F16 = {OP_CONV_F16: ('rpe_conv_f16', ConvDesc)}
+ALL_LIST_OPS = {**LIST_OPS, **LIST_OPS_ENC, **LIST_OPS_ALT_DT, **LIST_OPS_F16}           # every kind csrc/oplist.hip's run_one carries with an argument block
 KIND_OF_ENTRY = {entry: kind for kind, (entry, _) in ALL_LIST_OPS.items()}
 
 ABI_MINOR = 3              # RPE_ABI_MINOR of the single-map surfel entry points (rpe_surfel_*)
 ABI_MINOR_MANY = 4         # RPE_ABI_MINOR of rpe_surfel_*_many and rpe_pose_gate_chain_rows: the newest additions this binding calls
-                           # (rpe_conv_wino24*, rpe_flow_forward_interpolate, rpe_flow_seed, rpe_ingest_stereo, rpe_conv_fused_m96, rpe_corr_alt_* (with the fp16 forms rpe_corr_alt_*_ex / _dt) and the padded loop's rpe_conv_*_v / rpe_*_ex / rpe_copy_rect came later under the same minor:
+                           # (rpe_conv_wino24*, rpe_flow_forward_interpolate, rpe_flow_seed, rpe_ingest_stereo, rpe_conv_fused_m96, rpe_corr_alt_* (with the fp16 forms rpe_corr_alt_*_ex / _dt), rpe_conv_f16* and the padded loop's rpe_conv_*_v / rpe_*_ex / rpe_copy_rect came later under the same minor:
                            # loading binds every SIGNATURES entry, so a library without them fails there)
 SURFEL_MAX_MAPS = 64       # RPE_SURFEL_MAX_MAPS: maps per rpe_surfel_*_many call
 ABI_VERSION = 5            # RPE_ABI_VERSION of include/rpe.h these struct mirrors were written against
@@ -268,6 +271,8 @@ SIGNATURES = {
     'rpe_conv_wino1d_pack': (_i, [_vp, _i, _i, _vp, _vp]),
     'rpe_conv_wino1d_x3_packed_bytes': (_sz, [_i, _i]),
     'rpe_conv_wino1d_x3_pack': (_i, [_vp, _i, _i, _vp, _vp]),
+    'rpe_conv_f16_packed_bytes': (_sz, [_i, _i, _i, _i]),
+    'rpe_conv_f16_pack': (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     'rpe_conv_stats_tiles': (_i, [_i, _i, _i, _i]),
     'rpe_conv_stats_tiles_batch': (_i, [_i, _i, _i, _i, _i]),
     'rpe_instnorm_apply': (_i, [_vp, _vp, _i, _i, _i, _i, _c.c_float, _i, _vp, _vp, _vp]),

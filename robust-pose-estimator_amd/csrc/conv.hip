@@ -20,6 +20,7 @@
 // (x+dx outside the row) are masked per lane when the B operand is read.
 #include "conv_host.h"
 #include "conv_igemm.h"
+#include "conv_epilogue.h"
 #include <type_traits>
 
 // LDS layouts are K-contiguous: As[m][KS], Bs[4 + n][KS] with KS = 20 floats (16 used): a lane fetches the 8 k-values
@@ -330,6 +331,7 @@ __global__ __launch_bounds__(256, 3) void k_conv_igemm(ConvP P) {
         const float* zb = P.z ? P.z + (size_t)bz * P.zbs : nullptr;
         float* outb0 = P.out + (size_t)bz * P.obs;
         float* out2b0 = P.out2 ? P.out2 + (size_t)bz * P.o2bs : nullptr;
+        const ConvEpi E = {P.bias, addb0, hb, zb, outb0, out2b0, mode, cg, P.cout, hw};
 #pragma unroll
         for (int i = 0; i < T; ++i)
 #pragma unroll
@@ -339,39 +341,8 @@ __global__ __launch_bounds__(256, 3) void k_conv_igemm(ConvP P) {
                 const bool pok = VERT ? (vy0 + nl / VTX < P.H && vx0 + nl % VTX < W) : px < hw;
                 const int co0 = m0 + wm * WT + i * 32 + 4 * lh;
 #pragma unroll
-                for (int rb = 0; rb < 16; rb += 4) {                 // four rows per batch: loads together, then arithmetic, then masked stores
-                    size_t e[4]; bool ok[4]; float av[4], bv[4], xv[4], yv[4];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int co = co0 + r + 8 * (rb >> 2);
-                        ok[r] = pok && co < P.cout;
-                        e[r] = ok[r] ? (size_t)co * hw + px : 0;
-                        bv[r] = P.bias ? P.bias[ok[r] ? co : 0] : 0.0f;
-                        av[r] = addb0 ? addb0[e[r]] : 0.0f;
-                    }
-                    const bool rrows = co0 + 8 * (rb >> 2) >= cg;    // (GATE_ZR; uniform per batch when cg % 4 == 0)
-                    if (mode == RPE_CONV_GATE_ZR) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) xv[r] = hb[(rrows && ok[r]) ? e[r] - (size_t)cg * hw : 0];
-                    } else if (mode == RPE_CONV_GATE_H) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) { xv[r] = zb[e[r]]; yv[r] = hb[e[r]]; }
-                    }
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        float v = acc[i][j][rb + r] + av[r] + bv[r];
-                        if (mode == RPE_CONV_GATE_ZR) {
-                            const float sg = sigmoid_f(v);
-                            if (ok[r]) { if (rrows) out2b0[e[r] - (size_t)cg * hw] = sg * xv[r]; else outb0[e[r]] = sg; }
-                        } else if (mode == RPE_CONV_GATE_H) {
-                            if (ok[r]) outb0[e[r]] = (1.0f - xv[r]) * yv[r] + xv[r] * tanh_f(v);
-                        } else {
-                            if (mode == RPE_CONV_RELU) v = v < 0.0f ? 0.0f : v;    // NaN stays NaN, like torch.relu
-                            else if (mode == RPE_CONV_TANH) v = tanh_f(v);
-                            if (ok[r]) { outb0[e[r]] = v; if (out2b0) out2b0[e[r]] = v; }
-                        }
-                    }
-                }
+                for (int rb = 0; rb < 16; rb += 4)                   // four rows per batch: loads together, then arithmetic, then masked stores (conv_epilogue.h)
+                    conv_epilogue_rows4(E, acc[i][j][rb], acc[i][j][rb + 1], acc[i][j][rb + 2], acc[i][j][rb + 3], co0 + 8 * (rb >> 2), px, pok);
             }
         return;
     }

@@ -47,6 +47,7 @@ static int run_one(const rpe_op& op, void* const* streams, int n_streams) {
     case RPE_OP_CONV_WINO_X3: return rpe_conv_wino_x3(as<rpe_conv_desc>(op), st);
     case RPE_OP_CONV_WINO1D_X3: return rpe_conv_wino1d_x3(as<rpe_conv_desc>(op), st);
     case RPE_OP_CONV1X1_X3: return rpe_conv1x1_x3(as<rpe_conv_desc>(op), st);
+    case RPE_OP_CONV_F16: return rpe_conv_f16(as<rpe_conv_desc>(op), st);
     case RPE_OP_CORR_LOOKUP: {
         const auto* a = as<rpe_corr_lookup_args>(op);
         return rpe_corr_lookup(a->pyramid, a->coords, a->b, a->h8, a->w8, a->levels, a->radius, a->out, st);

@@ -872,6 +872,23 @@ class PackedConv1x1X3(_Packed):
     size, pack, entry = 'rpe_conv1x1_x3_packed_bytes', 'rpe_conv1x1_x3_pack', 'rpe_conv1x1_x3'
 
 
+class PackedConvF16(_Packed):
+    """Weights of a stride-1 'same' convolution (1x1, 3x3, 1x5, 5x1; any cin, any cout) rounded to fp16 and laid out in matrix-fragment
+    order for rpe_conv_f16: rpe_conv_fused's operation with fp16 OPERANDS (round to nearest even), f32 products, f32 sum in a fixed order,
+    f32 epilogue -- the precision contract of RAFT's ``update_fp16`` (include/rpe.h).  conv_fused, conv_wino, conv_wino1d, conv1x1 and
+    Conv1x1(..., f16=True) run rpe_conv_f16 when handed this packing; every epilogue mode of conv_fused, no scale / residual / stats /
+    pre_norm / stride 2 / valid extent."""
+    kernels, error, in_bytes = ((1, 1), (3, 3), (1, 5), (5, 1)), 'needs a (cout, cin, kh, kw) weight with (kh, kw) in 1x1, 3x3, 1x5, 5x1', True
+    size, pack, entry = 'rpe_conv_f16_packed_bytes', 'rpe_conv_f16_pack', 'rpe_conv_f16'
+
+    def _dims(self):
+        return self.cout, self.cin, self.kh, self.kw
+
+    @staticmethod
+    def supported(weight, h, w):
+        return tuple(weight.shape[2:]) in PackedConvF16.kernels and h > 0 and w > 0 and w % 4 == 0
+
+
 def conv1x1(x, pc, mode, out, out2=None, prepare=False, valid=None):
     """rpe_conv1x1: out = act(W x + bias) for a PackedConv1x1 (LINEAR / RELU / TANH), channel-slice destinations like conv_fused
     (a PackedConv1x1X3 runs rpe_conv1x1_x3)."""
@@ -898,9 +915,14 @@ class Conv1x1:
     fused = property(lambda self: self._packing(PackedConv))
     gemm = property(lambda self: self._packing(PackedConv1x1))
     gemm_x3 = property(lambda self: self._packing(PackedConv1x1X3))
+    f16 = property(lambda self: self._packing(PackedConvF16))
 
-    def __call__(self, x, mode, out, out2=None, prepare=False, x3=False, valid=None):
+    def __call__(self, x, mode, out, out2=None, prepare=False, x3=False, valid=None, f16=False):
         b, _, hh, ww = x.shape
+        if f16:                                               # the fp16-operand contract (raft.UPDATE_FP16): rpe_conv_f16 at EVERY launch size, or an error
+            if x3 or valid is not None:
+                raise _lib.RpeError('Conv1x1: f16 runs on rpe_conv_f16 alone -- not with x3, and there is no valid-extent form of it')
+            return conv_fused(x, self.f16, mode, out, out2=out2, prepare=prepare)
         # rpe_conv1x1's own preconditions (16-byte DMA pieces): plane size, base and batch stride of the input slice
         aligned = PackedConv1x1.supported(hh, ww) and x.data_ptr() % 16 == 0 and x.stride(0) % 4 == 0
         big = b * -(-(hh * ww) // 128) * -(-self.cout // 128) >= 512 and aligned
@@ -938,6 +960,8 @@ def conv_fused(x, pc, mode, out, out2=None, add=None, hidden=None, zgate=None, g
         if valid is not None or stride != 2:
             raise _lib.RpeError('conv_fused: enc_valid is the stride-2 encoder form (not with valid=)')
         valid = enc_valid
+    if isinstance(pc, PackedConvF16):                         # the kernel that belongs to the packing (what it refuses is an error, never another route)
+        entry = pc.entry
     d, bias, stats = _conv_desc('conv_fused', x, pc, mode, dict(add=add, out=out, out2=out2, hidden=hidden, zgate=zgate, residual=residual),
                                 _FUSED_RULES.get(mode, _PLAIN_RULES), scale, bias, stats, pre_norm, modes=_FUSED_MODES, tile_major=False,
                                 kernel=(pc.kh, pc.kw), stride=stride, gate_channels=gate_channels, valid=valid)
@@ -1101,6 +1125,8 @@ def conv_wino(x, pw, mode, out, out2=None, scale=None, bias='packed', residual=N
         if valid is not None:
             raise _lib.RpeError('conv_wino: valid= and enc_valid= are two entry points')
         valid = enc_valid
+    if (pw.kh, pw.kw) != (3, 3):                              # (a PackedConvF16 exists for other shapes too: those go through conv_fused)
+        raise _lib.RpeError(f'conv_wino: needs the packing of a 3x3 weight, got {pw.kh}x{pw.kw}')
     d, bias, stats = _conv_desc('conv_wino', x, pw, mode, dict(out=out, out2=out2, residual=residual), _WINO_RULES, scale, bias, stats, pre_norm,
                                 modes=(CONV_LINEAR, CONV_RELU), tile_major=True, kernel=(3, 3), valid=valid)
     return _launch(_kind(pw.entry, valid, enc_valid is not None), d, (x, pw, out, out2, scale, bias, residual, stats, pre_norm), out, prepare)

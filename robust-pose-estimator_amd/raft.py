@@ -59,6 +59,13 @@ X3_MIN_CIN = 128         # rpe_conv_wino_x3 pays from 8 K steps of 16 channels o
 X3_GRU = False           # under CONV_BF16X3, also the SepConvGRU's 1x5 / 5x1 layers on rpe_conv_wino1d_x3.  Off: in the bench step its launches
 #                          take 449 / 410 us (z|r, 1x5 / 5x1) and 251 / 237 us (q) against rpe_conv_wino1d's 407 / 395 and 240 / 224 -- one
 #                          workgroup per CU has nothing to run beside its memory-bound gate pass (csrc/conv_wino1d_x3.hip); kept, tested, opt-in.
+# RAFT's ``update_fp16`` for models built without the config key (tools/bench_update_fp16.py): the update block's convolutions with fp16
+# OPERANDS on the 16-bit matrix cores (rpe_conv_f16: operands rounded to nearest even, f32 products, sum and epilogue) -- what upstream
+# RAFT's mixed_precision (autocast) does to the update block.  Covered: convc1, convc2, convf2, conv, the GRU convolutions' loop-varying 256
+# input channels with their gates, FlowHead.conv1, the mask head.  Not covered (f32): the GRU's context terms, convf1, FlowHead.conv2, the
+# encoders, the correlation.  A precision contract, uniform over the covered layers; opt-in, never the headline.  Refused with CONV_BF16X3,
+# without WINOGRAD, with pad_maps / pad_encoders and on 1/8 maps with w % 4 != 0 (RAFT._check_update_fp16).
+UPDATE_FP16 = False
 # The motion encoder's flow branch (convf1 -> convf2) on a side stream beside lookup -> convc1 -> convc2.  Measured (MI355X, 640x512):
 # batch 1-2 (sequential tracking) 9.22 -> 9.08 ms per frame pair, 110.2 -> 111.9 frames/s; batch 32: 72.49 vs 72.41 ms per step (every
 # launch fills the chip on its own), so it is used for small passes only.
@@ -99,7 +106,7 @@ SIDE_STREAM_MAX = 8 * 5120                                     # queries per pas
 # recorded under them, so a switch flipped on a live model (tests, bench.py's A/B runs) is honoured by all of it at the next pass.
 # (LOOP_OPLIST, LOOKUP_EVENT_SINK, FRAME_OPLISTS and FRAME_OPLISTS_MAX_IMAGES choose how launches are dispatched, not what is cached.)
 ROUTE_SWITCHES = ('WINOGRAD', 'WINO_2X4', 'S2_M96', 'S2_M96_MIN_WGS', 'CORR_BF16X3', 'CONV_BF16X3', 'X3_MIN_CIN', 'X3_GRU', 'SIDE_STREAM', 'SIDE_STREAM_MAX',
-                  'LOOKUP_FUSED', 'LOOKUP_FUSED_MAX_WGS', 'ENC_STREAMS', 'ENC_STREAMS_MIN', 'PAD_MAPS', 'PAD_ENCODERS')
+                  'LOOKUP_FUSED', 'LOOKUP_FUSED_MAX_WGS', 'ENC_STREAMS', 'ENC_STREAMS_MIN', 'PAD_MAPS', 'PAD_ENCODERS', 'UPDATE_FP16')
 _switch_values = operator.itemgetter(*ROUTE_SWITCHES)
 
 
@@ -577,6 +584,7 @@ class BasicUpdateBlock(nn.Module):
     def __init__(self, corr_levels=4, corr_radius=4, hidden_dim=128):
         super().__init__()
         self.hidden_dim = hidden_dim
+        self.update_fp16 = False                               # RAFT's config key ``update_fp16`` (set by RAFT; UPDATE_FP16 for tools)
         self.encoder = BasicMotionEncoder(corr_levels, corr_radius)
         self.gru = SepConvGRU(hidden_dim=hidden_dim, input_dim=128 + hidden_dim)
         self.flow_head = FlowHead(hidden_dim, hidden_dim=256)
@@ -617,16 +625,24 @@ class BasicUpdateBlock(nn.Module):
         pads = {'zr1': (0, 2), 'q1': (0, 2), 'zr2': (2, 0), 'q2': (2, 0)}
         return {k: ops.conv_direct(inp, W[k][1], W[k][2], 1, pads[k]) for k in W}
 
+    def fp16(self):
+        """This pass runs the covered layers on rpe_conv_f16 (the config key, or the module switch)."""
+        return bool(self.update_fp16 or UPDATE_FP16)
+
     def packed_convs(self, width, with_key=False):
         """Weights of the update block's convolutions in rpe_conv_fused's layout (cached until a parameter, the stacked gate weights or a
         route switch changes), or None when the fused kernels do not apply (map width not a multiple of 4)."""
         if width % 4 != 0:
+            if self.fp16():
+                raise ops._lib.RpeError(f'RAFT: update_fp16 needs a 1/8 map with w % 4 == 0 (rpe_conv_f16), got w8 = {width}; it does not run in f32 instead')
             return (None, None) if with_key else None
         e, fh = self.encoder, self.flow_head
         mods = (e.convc1, e.convc2, e.convf2, e.conv, fh.conv1)
         gate_key, W = self.gate_weights(with_key=True)
         # (the convolutions' own weight / bias attributes: walking module.parameters() costs ~100 us a call, and this runs 26 times a frame)
         key = (_wkey(*[t for m in mods + (e.convf1,) for t in (m.weight, m.bias)]), gate_key, _switches())
+        if self.update_fp16:                                   # (a model without the key keeps the key it always had)
+            key += ('update_fp16',)
         return _cached(self, '_packed', key, lambda: self._pack_convs(mods, W), with_key)
 
     def _pack_convs(self, mods, W):
@@ -651,6 +667,18 @@ class BasicUpdateBlock(nn.Module):
             P[n] = (ops.PackedWino1dX3 if CONV_BF16X3 and X3_GRU and ops.PackedWino1dX3.supported(W[n][0], 4) else ops.PackedWino1d)(W[n][0]) if WINOGRAD \
                 else ops.PackedConv(W[n][0])
             P['ctx_' + n] = (ops.PackedWino1d if WINOGRAD else ops.PackedConv)(W[n][1], W[n][2])
+        if self.fp16():
+            # update_fp16: the covered layers' weights as fp16 matrix fragments (rpe_conv_f16); the gate convolutions' loop-varying 256
+            # input channels only -- the context terms above stay f32 and enter as ``add``
+            # (made when launchers are first built from this dict, like convc1's lookup-fused packing: kept as long as the dict)
+            made = {}
+
+            def f16():
+                if not made:
+                    made.update({n: ops.PackedConvF16(m.weight, m.bias) for n, m in zip(('convc1', 'convc2', 'convf2', 'conv', 'fh1'), mods)})
+                    made.update({n: ops.PackedConvF16(W[n][0]) for n in ('zr1', 'q1', 'zr2', 'q2')})
+                return made
+            P['f16'] = f16
         scratch = {}
 
         def buf(name, like, c):                            # scratch for intermediate activations, one set per workspace (``like`` is one of
@@ -688,8 +716,13 @@ class BasicUpdateBlock(nn.Module):
         if wino and hx.shape[-1] % 4 == 0:
             wino.update(P['wino24'])
             wino.update(P['wino_x3'])                      # (CONV_BF16X3: conv_wino runs the kernel that belongs to the packing)
+        f16 = P['f16']() if 'f16' in P else None            # update_fp16: every covered layer on rpe_conv_f16 (None: every call below is the call it always was)
+        if f16 is not None and valid is not None:
+            raise ops._lib.RpeError('RAFT: update_fp16 has no valid-extent form yet -- not with pad_maps')
 
         def c3(name, x, out, out2=None):                    # a 3x3 layer: Winograd when available, else the direct implicit GEMM
+            if f16 is not None:
+                return ops.conv_fused(x, f16[name], ops.CONV_RELU, out, out2=out2, prepare=True)
             if name in wino:
                 return ops.conv_wino(x, wino[name], ops.CONV_RELU, out, out2=out2, prepare=True, **vk)
             if valid is not None:
@@ -698,6 +731,8 @@ class BasicUpdateBlock(nn.Module):
         # each GRU half = two implicit-GEMM convolutions whose epilogues are the gates:
         #   z = s(convz hx + ctx), r*h -> rhx ;  h <- (1-z) h + z tanh(convq rhx + ctx)   (in place on hx[:, :c])
         gconv = ops.conv_wino1d if isinstance(P['zr1'], (ops.PackedWino1d, ops.PackedWino1dX3)) else ops.conv_fused
+        if f16 is not None:
+            P, gconv = dict(P, **{n: f16[n] for n in ('zr1', 'q1', 'zr2', 'q2')}), ops.conv_fused
         gru = []
         for zr, q in (('zr1', 'q1'), ('zr2', 'q2')):
             gru.append(gconv(hx, P[zr], ops.CONV_GATE_ZR, z_buf, out2=rhx[:, :c], add=ctx[zr], hidden=hx[:, :c], gate_channels=c, prepare=True, **vk))
@@ -705,14 +740,15 @@ class BasicUpdateBlock(nn.Module):
         gru.append(c3('fh1', hx[:, :c], fh_buf))
         gru.append(ops.flow_update(fh_buf, fh.conv2.weight, fh.conv2.bias.detach(), coords1, coords1, flow_out=flow, dst1=hx[:, 2 * c - 2:],
                                    dst2=rhx[:, 2 * c - 2:], prepare=True, **vk))
-        L = SimpleNamespace(flo=flo, vk=vk, c1=P['convc1_1x1'](corr, ops.CONV_RELU, cor, prepare=True, x3=CONV_BF16X3, **vk), c2=c3('convc2', cor, cat_buf[:, :192]),
+        L = SimpleNamespace(flo=flo, vk=vk, c1=P['convc1_1x1'](corr, ops.CONV_RELU, cor, prepare=True, x3=CONV_BF16X3, **vk) if f16 is None else
+                            ops.conv_fused(corr, f16['convc1'], ops.CONV_RELU, cor, prepare=True), c2=c3('convc2', cor, cat_buf[:, :192]),
                             f1=ops.stem_conv(flow, P['convf1'], bias=e.convf1.bias.detach(), relu=True, div=1.0, mul=1.0, sub=0.0, out=flo, prepare=True, **vk),
                             f2=c3('convf2', flo, cat_buf[:, 192:]), cv=c3('conv', cat_buf, hx[:, 128:254], rhx[:, 128:254]), gru=gru)
         if pyr is not None:
             # (pad_maps: the pyramid and the taps keep the true (h8, w8); coords and the 324 channels live in the padded maps)
             L.lookup, L.lookup_c1 = pyr.lookup(coords1, out=corr, prepare=True, **({} if valid is None else dict(map_size=tuple(hx.shape[-2:])))), None
             n_wgs = hx.shape[0] * -(-(hx.shape[2] * -(-hx.shape[3] // 8)) // 8)
-            if valid is None and not alt and LOOKUP_FUSED and not CONV_BF16X3 and n_wgs <= LOOKUP_FUSED_MAX_WGS and ops.PackedLookupConv.supported(pyr.levels, pyr.radius, pyr.w8):
+            if valid is None and not alt and LOOKUP_FUSED and not CONV_BF16X3 and f16 is None and n_wgs <= LOOKUP_FUSED_MAX_WGS and ops.PackedLookupConv.supported(pyr.levels, pyr.radius, pyr.w8):
                 # (convc1 in the fused kernel's layout: made when a pass first takes this route, kept while convc1 stays as it is)
                 pl = _cached(self, '_lookup_packed', _wkey(e.convc1.weight, e.convc1.bias), lambda: ops.PackedLookupConv(e.convc1.weight, e.convc1.bias))
                 L.lookup_c1 = pyr.lookup_conv1x1(coords1, pl, cor, relu=True, prepare=True)
@@ -763,6 +799,14 @@ class BasicUpdateBlock(nn.Module):
         hh, ww = net.shape[-2:]
         x3 = CONV_BF16X3 and c1.in_channels >= X3_MIN_CIN and ops.PackedWinoX3.supported(c1.weight, hh, ww)
         w24 = WINO_2X4 and not CONV_BF16X3 and ops.PackedWino24.supported(c1.weight, hh, ww)
+        if self.fp16() and c1.weight.is_cuda:
+            # update_fp16: both layers on rpe_conv_f16, the x0.25 fold kept (a power of two: it commutes with the fp16 rounding of normal weights)
+            if not ops.PackedConvF16.supported(c1.weight, hh, ww) or torch.is_grad_enabled():
+                raise ops._lib.RpeError(f'RAFT: update_fp16 needs a 1/8 map with w % 4 == 0 and no autograd (got w8 = {ww}); it does not run in f32 instead')
+            p1, p2 = _cached(self, '_mask_packed', (_wkey(*mp), 'f16', _switches()), lambda: (
+                ops.PackedConvF16(c1.weight, c1.bias), ops.PackedConvF16((0.25 * c2.weight).detach(), (0.25 * c2.bias).detach())))
+            t = ops.conv_fused(net, p1, ops.CONV_RELU, torch.empty(net.shape[0], c1.out_channels, hh, ww, device=net.device))
+            return ops.conv_fused(t, p2, ops.CONV_LINEAR, torch.empty(net.shape[0], c2.out_channels, hh, ww, device=net.device))
 
         def pack():
             pw = (ops.PackedWinoX3 if x3 else ops.PackedWino24 if w24 else ops.PackedWino)(c1.weight, c1.bias) if WINOGRAD and c1.weight.is_cuda else None
@@ -807,6 +851,11 @@ class RAFT(nn.Module):
         # ``pad_encoders`` (opt-in): at the same sizes both encoders run layer2, layer3 and the output layer on zero-padded maps (BasicEncoder._padded)
         self.pad_encoders = bool(config.get('pad_encoders', False))
         _check_pad_encoders(self.pad_encoders)
+        # ``update_fp16`` (opt-in): the update block's convolutions with fp16 operands on the 16-bit matrix cores (UPDATE_FP16 above names the
+        # covered layers and the contract) -- what a user of upstream RAFT's mixed_precision expects of the update block.  Allowed together
+        # with mixed_precision and with alternate_corr [+ alt_corr_fp16], which keep their own meaning (the correlation's feature maps).
+        self.update_fp16 = bool(config.get('update_fp16', False))
+        self._check_update_fp16()
         self.iters = int(config.get('iters', 12))
         self.hidden_dim = self.context_dim = 128
         self.corr_levels, self.corr_radius = 4, 4
@@ -815,6 +864,7 @@ class RAFT(nn.Module):
         self.cnet = BasicEncoder(output_dim=256, norm_fn='batch', dropout=drop)
         self.fnet.pad_encoders = self.cnet.pad_encoders = self.pad_encoders
         self.update_block = BasicUpdateBlock(self.corr_levels, self.corr_radius, hidden_dim=128)
+        self.update_block.update_fp16 = self.update_fp16
         self._pyr = None
         self._ws = None
 
@@ -843,6 +893,22 @@ class RAFT(nn.Module):
         the convolutions and without WINOGRAD (at construction, and at every pass for the module-level switches)."""
         if (self.pad_maps or PAD_MAPS) and (CONV_BF16X3 or not WINOGRAD):
             raise ops._lib.RpeError('RAFT: pad_maps runs on the f32 Winograd kernels -- not with CONV_BF16X3 (X3_GRU), not without WINOGRAD')
+
+    def _check_update_fp16(self, w8=None):
+        """update_fp16 runs its covered layers on rpe_conv_f16 or not at all: refused together with the bf16x3 variant of the convolutions,
+        without WINOGRAD (the f32 layers beside it -- the context terms -- are the headline's), with pad_maps / pad_encoders (rpe_conv_f16 has
+        no valid-extent form yet) and on a 1/8 map its kernel does not take (at construction, and at every pass for the module-level
+        switches and the map)."""
+        if not (self.update_fp16 or UPDATE_FP16):
+            return
+        if CONV_BF16X3:
+            raise ops._lib.RpeError('RAFT: update_fp16 and CONV_BF16X3 are two precisions for the same layers -- choose one')
+        if not WINOGRAD:
+            raise ops._lib.RpeError('RAFT: update_fp16 keeps its f32 layers on the Winograd kernels -- not with WINOGRAD = False')
+        if self.pad_maps or PAD_MAPS or self.pad_encoders or PAD_ENCODERS:
+            raise ops._lib.RpeError('RAFT: update_fp16 has no valid-extent form yet -- not with pad_maps / pad_encoders')
+        if w8 is not None and w8 % 4 != 0:
+            raise ops._lib.RpeError(f'RAFT: update_fp16 needs a 1/8 map with w % 4 == 0 (rpe_conv_f16), got w8 = {w8}; it does not run in f32 instead')
 
     def _padded(self, h8, w8):
         """padded_size(h8, w8) when this pass runs its update loop on padded maps, else None (flag off, or a map the kernels take as it is)."""
@@ -1057,6 +1123,8 @@ class RAFT(nn.Module):
                pyr.buf.data_ptr(), ws['hx'].data_ptr(), wkey)
         if self.alt_corr_fp16:
             key += ('alt_corr_fp16',)
+        if self.update_fp16:
+            key += ('update_fp16',)
         if flow_init is not None or ret_lowres:                       # (a cold pass keeps the key it always had)
             key += ('warm' if flow_init is not None else 'cold', ret_lowres)
         ins = {'f1': fmap1, 'f2': fmap2, 'cnet': cnet}
@@ -1110,6 +1178,8 @@ class RAFT(nn.Module):
             N, _, H, W = image1.shape
             h8, w8 = H // 8, W // 8
             dev = image1.device
+        self.update_block.update_fp16 = self.update_fp16
+        self._check_update_fp16(w8)                            # (before the encoders run: a refused pass launches nothing)
         if fmaps is None:
             f = self.encode_features((image1, image2))
             fmap1, fmap2 = f[:N], f[N:]

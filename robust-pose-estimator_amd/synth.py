@@ -97,14 +97,15 @@ def infer_args(s):
 
 
 def model_config(h, w, iters=12, lbgfs_iters=8, solver='lbfgs', use_weights=True, mixed_precision=False, alternate_corr=False, pad_maps=False, pad_encoders=False,
-                 alt_corr_fp16=False):
+                 alt_corr_fp16=False, update_fp16=False):
     """The ``model`` section of configuration/train.yaml:1-9 of the reference + image shape / solver settings.
     ``mixed_precision`` (upstream RAFT's flag): fp16 feature maps into the correlation (BASELINE config 5).
     ``alternate_corr`` (upstream RAFT's flag): the correlation windows recomputed from the feature maps at every iteration, no all-pairs volume.
-    ``alt_corr_fp16`` (needs ``alternate_corr``): that route on fp16 feature maps (BASELINE config 5 without the volume)."""
+    ``alt_corr_fp16`` (needs ``alternate_corr``): that route on fp16 feature maps (BASELINE config 5 without the volume).
+    ``update_fp16``: the update block's convolutions with fp16 operands on the 16-bit matrix cores (raft.UPDATE_FP16 states the contract)."""
     return dict(small=False, dropout=0.0, iters=iters, pose_scale=1.0, lbgfs_iters=lbgfs_iters, use_weights=use_weights,
                 image_shape=(h, w), solver=solver, mixed_precision=mixed_precision, alternate_corr=alternate_corr, pad_maps=pad_maps, pad_encoders=pad_encoders,
-                alt_corr_fp16=alt_corr_fp16)
+                update_fp16=update_fp16, alt_corr_fp16=alt_corr_fp16)
 
 
 def init_synthetic_weights(model, seed=1234, flow_bias=-0.35):
