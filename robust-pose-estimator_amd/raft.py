@@ -35,11 +35,13 @@ see oracle/raft.py for the CPU restatement these kernels are tested against.
 """
 import operator
 from types import SimpleNamespace
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
 
 from . import ops
+from ._lib import RpeError
 
 # Module-level route constants (no environment switches in the product: tools/ and bench.py's labelled experiments set these attributes)
 WINOGRAD = True          # 3x3 layers as F(2x2,3x3), the GRU's 1x5 / 5x1 as F(4,5); False = the direct implicit GEMM (A/B measurements)
@@ -64,7 +66,7 @@ X3_GRU = False           # under CONV_BF16X3, also the SepConvGRU's 1x5 / 5x1 la
 # RAFT's mixed_precision (autocast) does to the update block.  Covered: convc1, convc2, convf2, conv, the GRU convolutions' loop-varying 256
 # input channels with their gates, FlowHead.conv1, the mask head.  Not covered (f32): the GRU's context terms, convf1, FlowHead.conv2, the
 # encoders, the correlation.  A precision contract, uniform over the covered layers; opt-in, never the headline.  Refused with CONV_BF16X3,
-# without WINOGRAD, with pad_maps / pad_encoders and on 1/8 maps with w % 4 != 0 (RAFT._check_update_fp16).
+# without WINOGRAD, with pad_maps / pad_encoders and on 1/8 maps with w % 4 != 0 (resolve_route).
 UPDATE_FP16 = False
 # The motion encoder's flow branch (convf1 -> convf2) on a side stream beside lookup -> convc1 -> convc2.  Measured (MI355X, 640x512):
 # batch 1-2 (sequential tracking) 9.22 -> 9.08 ms per frame pair, 110.2 -> 111.9 frames/s; batch 32: 72.49 vs 72.41 ms per step (every
@@ -123,6 +125,69 @@ def padded_size(h8, w8):
     return h8 + (h8 & 1), (w8 + 3) // 4 * 4
 
 
+class Route(NamedTuple):
+    """What a pass runs on, resolved once (resolve_route) and handed down: the six options as they take effect -- the config key, or for
+    the last three the module switch -- and, for a pass of known size, what follows from them.  Hashable: ``options`` is part of every key
+    of what is packed or recorded under it (beside _switches() and the sizes), so no option can be left out of a key."""
+    mixed_precision: bool = False
+    alternate_corr: bool = False
+    alt_corr_fp16: bool = False
+    pad_maps: bool = False
+    pad_encoders: bool = False
+    update_fp16: bool = False
+    loop_pad: Optional[Tuple[int, int]] = None                 # the zero-padded map the update loop runs on; None = the 1/8 map itself
+    enc_pad: Optional[Tuple[int, int]] = None                  # likewise of the encoders' layer2 / layer3 / output layer (in 1/8 cells)
+    fused: Optional[bool] = None                               # the loop's map has rows of whole quads: the tuned kernels, not the generic route
+
+    @property
+    def options(self):
+        return Route(*self[:6])
+
+
+def _fused(w8, update_fp16):
+    """Do the update block's tuned kernels take a map of this width (Route.fused)?  update_fp16 has no other route: refused."""
+    if w8 % 4 != 0 and update_fp16:
+        raise RpeError(f'RAFT: update_fp16 needs a 1/8 map with w % 4 == 0 (rpe_conv_f16), got w8 = {w8}; it does not run in f32 instead')
+    return w8 % 4 == 0
+
+
+def resolve_route(mixed_precision=False, alternate_corr=False, alt_corr_fp16=False, pad_maps=False, pad_encoders=False, update_fp16=False,
+                  map_size=None, image_size=None):
+    """The Route of a pass with these instance flags under the current module switches, on a 1/8 map ``map_size`` or an image
+    ``image_size`` where known.  Every refusal of a combination is raised here and nowhere else, in this order, before anything is built
+    or launched: at construction, at the start of every pass and of every encoder call -- so a switch flipped or a flag assigned on a
+    live model is refused, or honoured, at the next pass."""
+    pad_maps, pad_encoders, update_fp16 = bool(pad_maps or PAD_MAPS), bool(pad_encoders or PAD_ENCODERS), bool(update_fp16 or UPDATE_FP16)
+    # the on-the-fly correlation is f32, or fp16 by its own flag
+    if alt_corr_fp16 and not alternate_corr:
+        raise RpeError('RAFT: alt_corr_fp16 selects the feature precision of alternate_corr and needs alternate_corr: True')
+    if alternate_corr and (mixed_precision or CORR_BF16X3 or CONV_BF16X3):
+        raise RpeError('RAFT: alternate_corr is f32 only (fp16 features: alt_corr_fp16) -- not with mixed_precision, CORR_BF16X3 or CONV_BF16X3')
+    # the valid-extent entry points exist for the f32 Winograd / GEMM kernels only
+    if pad_maps and (CONV_BF16X3 or not WINOGRAD):
+        raise RpeError('RAFT: pad_maps runs on the f32 Winograd kernels -- not with CONV_BF16X3 (X3_GRU), not without WINOGRAD')
+    if pad_encoders and (CONV_BF16X3 or not WINOGRAD):
+        raise RpeError('RAFT: pad_encoders runs on the f32 Winograd kernels -- not with CONV_BF16X3, not without WINOGRAD')
+    # update_fp16 runs its covered layers on rpe_conv_f16 or not at all; the f32 layers beside it (the context terms) are the headline's
+    if update_fp16 and CONV_BF16X3:
+        raise RpeError('RAFT: update_fp16 and CONV_BF16X3 are two precisions for the same layers -- choose one')
+    if update_fp16 and not WINOGRAD:
+        raise RpeError('RAFT: update_fp16 keeps its f32 layers on the Winograd kernels -- not with WINOGRAD = False')
+    if update_fp16 and (pad_maps or pad_encoders):
+        raise RpeError('RAFT: update_fp16 has no valid-extent form yet -- not with pad_maps / pad_encoders')
+    options = (bool(mixed_precision), bool(alternate_corr), bool(alt_corr_fp16), pad_maps, pad_encoders, update_fp16)
+    if image_size is not None:
+        map_size = image_size[0] // 8, image_size[1] // 8
+    if map_size is None:
+        return Route(*options)
+    padded = padded_size(*map_size)
+    padded = None if padded == tuple(map_size) else padded
+    loop_pad = padded if pad_maps else None
+    # (the encoders pad whole 8x8 cells only: any other image keeps their generic route)
+    enc_pad = padded if pad_encoders and image_size is not None and image_size[0] % 8 == 0 and image_size[1] % 8 == 0 else None
+    return Route(*options, loop_pad, enc_pad, _fused((loop_pad or map_size)[1], update_fp16))
+
+
 def _norm(kind, ch):
     if kind == 'batch':
         return nn.BatchNorm2d(ch)
@@ -160,16 +225,13 @@ class ResidualBlock(nn.Module):
         ``x_norm`` (b,c,2): x is a raw convolution output whose relu((x - mean) * inv) is this block's real input (takes_raw_input).
         ``valid`` = (hv, wv) (pad_encoders): x and every map of the block are zero-padded, the block's OUTPUT map holds hv x wv of content;
         every launch takes its encoder valid-extent form, which keeps the padding zero and the moments on the content."""
-        vk = {} if valid is None else dict(valid=valid)           # (flag off: every call below is the call it always was)
         fused_in = isinstance(self.norm1, nn.InstanceNorm2d) and _fusable(self.conv1, x) and x.shape[-1] // self.conv1.stride[0] % 4 == 0
         if x_norm is not None and not (fused_in and self.takes_raw_input(x)):
             raise RuntimeError('ResidualBlock: x_norm needs the fused stride-1 Winograd route')
-        if valid is not None and not (_fusable(self.conv1, x) and (fused_in or isinstance(self.norm1, nn.BatchNorm2d))):
-            raise ops._lib.RpeError('ResidualBlock: pad_encoders needs a padded map the tuned kernels take')
         if fused_in:
             st = self.conv1.stride[0]
             hw = (x.shape[-2] // st) * (x.shape[-1] // st) if valid is None else valid[0] * valid[1]       # (the pixel count of the moments)
-            raw1, stats1 = _encoder_conv(self.conv1, x, pre_norm=x_norm, moments=True, **vk)   # (stride 1: Winograd, moments per 16x8-pixel patch)
+            raw1, stats1 = _encoder_conv(self.conv1, x, pre_norm=x_norm, moments=True, valid=valid)   # (stride 1: Winograd, moments per 16x8-pixel patch)
             mi = ops.instnorm_finalize(stats1, hw, eps=self.norm1.eps, channels=self.conv1.out_channels)
             res_relu = True
             if self.downsample is not None:
@@ -177,19 +239,19 @@ class ResidualBlock(nn.Module):
                 if _fusable(sc, x):
                     # the shortcut norm3(conv1x1 x) never exists as a tensor either: its raw convolution output and (mean, 1/std) go to
                     # the block's last pass, which normalises it on the fly (bit-identical to a pass of its own, tested)
-                    x, stats_sc = _encoder_conv(sc, x, moments=True, **vk)
+                    x, stats_sc = _encoder_conv(sc, x, moments=True, valid=valid)
                     x_norm = ops.instnorm_finalize(stats_sc, hw, eps=self.norm3.eps, channels=sc.out_channels)
                     res_relu = False
                 else:
                     x = conv_norm_act(sc, self.norm3, x, relu=False)
-            raw2, stats2 = _encoder_conv(self.conv2, raw1, pre_norm=mi, moments=True, **vk)
+            raw2, stats2 = _encoder_conv(self.conv2, raw1, pre_norm=mi, moments=True, valid=valid)
             if isinstance(stats2, ops.TileMajorStats):            # merge the Winograd kernel's records once (a small launch), then stream
                 stats2 = ops.instnorm_finalize(stats2, hw, eps=self.norm2.eps, channels=self.conv2.out_channels)
-            return ops.instnorm_apply(raw2, stats2, eps=self.norm2.eps, relu=True, residual=x, residual_norm=x_norm, residual_relu=res_relu, **vk)
-        y = conv_norm_act(self.conv1, self.norm1, x, relu=True, **vk)
+            return ops.instnorm_apply(raw2, stats2, eps=self.norm2.eps, relu=True, residual=x, residual_norm=x_norm, residual_relu=res_relu, valid=valid)
+        y = conv_norm_act(self.conv1, self.norm1, x, relu=True, valid=valid)
         if self.downsample is not None:
-            x = conv_norm_act(self.downsample[0], self.norm3, x, relu=False, **vk)
-        return conv_norm_act(self.conv2, self.norm2, y, relu=True, residual=x, **vk)
+            x = conv_norm_act(self.downsample[0], self.norm3, x, relu=False, valid=valid)
+        return conv_norm_act(self.conv2, self.norm2, y, relu=True, residual=x, valid=valid)
 
 
 def _bounded_put(cache, key, value, keep=2):
@@ -258,8 +320,6 @@ def conv_norm_act(conv, norm, x, relu, residual=None, valid=None):
     read+write pass normalises); shapes those kernels refuse run on the generic kernel (ops.conv_direct) + a stand-alone epilogue pass.
     ``valid`` (pad_encoders): the extent of the content of the zero-padded output map, as ResidualBlock.forward."""
     fused = _fusable(conv, x)
-    if valid is not None and not fused:
-        raise ops._lib.RpeError('conv_norm_act: pad_encoders needs a padded map the tuned kernels take')
     if isinstance(norm, nn.BatchNorm2d):
         if norm.training:
             raise RuntimeError('the RAFT encoders run with frozen batch norm (RAFT.freeze_bn, pose_net.py:22)')
@@ -270,7 +330,7 @@ def conv_norm_act(conv, norm, x, relu, residual=None, valid=None):
     if isinstance(norm, nn.InstanceNorm2d):
         if fused:
             pre, stats = _encoder_conv(conv, x, moments=True, valid=valid)
-            return ops.instnorm_apply(pre, stats, eps=norm.eps, relu=relu, residual=residual, **({} if valid is None else dict(valid=valid)))
+            return ops.instnorm_apply(pre, stats, eps=norm.eps, relu=relu, residual=residual, valid=valid)
         return ops.instnorm_act(ops.conv_direct(x, conv.weight, None, conv.stride, conv.padding), conv.bias, eps=norm.eps, relu=relu, residual=residual)
     raise NotImplementedError(type(norm))
 
@@ -282,7 +342,6 @@ def _encoder_conv(conv, x, mode=ops.CONV_LINEAR, affine=None, residual=None, pre
     Returns (the output, the per-tile moments for instnorm_finalize / instnorm_apply in the layout of the kernel that ran -- TileMajorStats
     from Winograd, channel-major records from the implicit GEMM -- when ``moments``, else None).  ``valid`` (pad_encoders) = the content of
     the zero-padded OUTPUT map: the kernels' encoder valid-extent forms (ops.conv_wino / conv_fused with enc_valid=)."""
-    vk = {} if valid is None else dict(enc_valid=valid)
     b, _, hh, ww = x.shape
     st, cout = conv.stride[0], conv.out_channels
     scale, bias = affine if affine is not None else (None, conv.bias.detach())
@@ -290,14 +349,12 @@ def _encoder_conv(conv, x, mode=ops.CONV_LINEAR, affine=None, residual=None, pre
     out = torch.empty(b, cout, hh // st, ww // st, device=x.device)
     if pw is not None:
         stats = ops.conv_wino_stats_buffer(b, cout, hh, ww, x.device) if moments else None
-        ops.conv_wino(x, pw, mode, out, scale=scale, bias=bias, residual=residual, stats=stats, pre_norm=pre_norm, **vk)
+        ops.conv_wino(x, pw, mode, out, scale=scale, bias=bias, residual=residual, stats=stats, pre_norm=pre_norm, enc_valid=valid)
     else:
-        if valid is not None and (st != 2 or not WINOGRAD):
-            raise ops._lib.RpeError('pad_encoders runs the stride-1 3x3 layers on the Winograd kernels (WINOGRAD)')
         stats = ops.conv_stats_buffer(b, cout, hh, ww, x.device, stride=st) if moments else None
         m96 = S2_M96 and st == 2 and conv.kernel_size == (3, 3) and cout == 96 and b * -(-(hh // 2) * (ww // 2) // 128) >= S2_M96_MIN_WGS
         ops.conv_fused(x, _packed(conv), mode, out, scale=scale, bias=bias, residual=residual, stats=stats, stride=st, pre_norm=pre_norm,
-                       entry='rpe_conv_fused_m96' if m96 else 'rpe_conv_fused', **vk)
+                       entry='rpe_conv_fused_m96' if m96 else 'rpe_conv_fused', enc_valid=valid)
     return out, stats
 
 
@@ -344,18 +401,11 @@ class _Recorded:
         self._failed.clear()
 
 
-def _check_pad_encoders(flag):
-    """The encoders' valid-extent entry points exist for the f32 Winograd / GEMM kernels only: pad_encoders is refused together with the bf16x3
-    variant of the convolutions and without WINOGRAD (at construction, and at every pass for the module-level switches), as pad_maps is."""
-    if (flag or PAD_ENCODERS) and (CONV_BF16X3 or not WINOGRAD):
-        raise ops._lib.RpeError('RAFT: pad_encoders runs on the f32 Winograd kernels -- not with CONV_BF16X3, not without WINOGRAD')
-
-
 class BasicEncoder(nn.Module):
-    def __init__(self, output_dim=128, norm_fn='batch', dropout=0.0):
+    def __init__(self, output_dim=128, norm_fn='batch', dropout=0.0, pad_encoders=False):
         super().__init__()
         self.norm_fn = norm_fn
-        self.pad_encoders = False                              # RAFT's config key ``pad_encoders`` (set by RAFT; PAD_ENCODERS for tools)
+        self.pad_encoders = pad_encoders                       # RAFT's config key ``pad_encoders``, for an encoder called on its own (_route)
         self.norm1 = _norm(norm_fn, 64)
         self.conv1 = nn.Conv2d(3, 64, kernel_size=7, stride=2, padding=3)
         self.relu1 = nn.ReLU(inplace=True)
@@ -417,7 +467,6 @@ class BasicEncoder(nn.Module):
         tanh, the rest through ReLU, in the convolution's epilogue.  ``valid`` (pad_encoders): x is a zero-padded map with that much content;
         the layer runs on it (rpe_conv1x1_v) and the result leaves cropped and contiguous (rpe_copy_rect)."""
         m = self.conv2
-        vk = {} if valid is None else dict(valid=valid)
         b, _, hh, ww = x.shape
         half = m.out_channels // 2
         if ww % 4 == 0 and x.is_contiguous():
@@ -427,16 +476,14 @@ class BasicEncoder(nn.Module):
             whole, lo, hi = _cached(self, '_final_packed', _wkey(m.weight, m.bias), pack)
             out = torch.empty(b, m.out_channels, hh, ww, device=x.device)
             if not split_act:
-                whole(x, ops.CONV_LINEAR, out, x3=CONV_BF16X3, **vk)
+                whole(x, ops.CONV_LINEAR, out, x3=CONV_BF16X3, valid=valid)
             else:
-                lo(x, ops.CONV_TANH, out[:, :half], **vk)
-                hi(x, ops.CONV_RELU, out[:, half:], x3=CONV_BF16X3, **vk)
+                lo(x, ops.CONV_TANH, out[:, :half], valid=valid)
+                hi(x, ops.CONV_RELU, out[:, half:], x3=CONV_BF16X3, valid=valid)
             if valid is not None:
                 self._ws['out'] = out
                 return ops.copy_rect(out, torch.empty(b, m.out_channels, *valid, device=x.device), *valid)
             return out
-        if valid is not None:
-            raise ops._lib.RpeError('BasicEncoder: pad_encoders needs a padded map the tuned kernels take')
         y = ops.conv_direct(x, m.weight, m.bias, 1, 0)           # (maps whose rows are not whole 16-byte quads)
         if split_act:
             y[:, :half] = torch.tanh(y[:, :half])
@@ -450,19 +497,20 @@ class BasicEncoder(nn.Module):
             self._recorded.clear()
         return r
 
-    def forward(self, x, raw255=False, split_act=False):
+    def forward(self, x, raw255=False, split_act=False, route=None):
         """``raw255``: x is the raw 0..255 image (RAFT.forward's normalisation is then done inside the first kernel), or a list of
-        such image batches, encoded as one batch.  ``split_act``: see _final.
-        Small inference passes (FRAME_OPLISTS) are recorded once per (shapes, stream, weights) and replayed as one launch list."""
+        such image batches, encoded as one batch.  ``split_act``: see _final.  ``route``: the pass's Route (RAFT hands it down; an encoder
+        called on its own resolves its own flag).
+        Small inference passes (FRAME_OPLISTS) are recorded once per (shapes, stream, weights, route) and replayed as one launch list."""
         images = list(x) if isinstance(x, (list, tuple)) else [x]
         first = images[0]
+        if route is None:
+            route = resolve_route(pad_encoders=self.pad_encoders, image_size=first.shape[-2:])
         if FRAME_OPLISTS and raw255 and first.is_cuda and first.device.index == torch.cuda.current_device() and not torch.is_grad_enabled() \
                 and sum(im.shape[0] for im in images) <= FRAME_OPLISTS_MAX_IMAGES \
                 and all(im.is_contiguous() and im.dtype == torch.float32 and im.device == first.device for im in images) and not _overlap(images):
             recorded, wkey = _recording(self, self)
-            key = (tuple(tuple(im.shape) for im in images), first.device.index, ops.raw_stream(), split_act, _switches(), self.training, wkey)
-            if self.pad_encoders:                                 # (a pass without the key keeps the key it always had)
-                key += ('pad_encoders',)
+            key = (tuple(tuple(im.shape) for im in images), first.device.index, ops.raw_stream(), split_act, _switches(), self.training, wkey, route.options)
             rec = recorded.get(key)
             if rec is not None:
                 out = torch.empty(rec.out_shape, device=first.device)
@@ -471,7 +519,7 @@ class BasicEncoder(nn.Module):
             if recorded.wanted(key):
                 rec = ops.Recorder()
                 with rec:
-                    out = self._forward(x, raw255, split_act)
+                    out = self._forward(x, raw255, split_act, route.enc_pad)
                 if rec.complete and out.is_contiguous():
                     for i, im in enumerate(images):
                         rec.complete = rec.complete and rec.bind(i, im) > 0
@@ -479,9 +527,10 @@ class BasicEncoder(nn.Module):
                     rec.out_shape = tuple(out.shape)
                 recorded.put(key, rec)
                 return out
-        return self._forward(x, raw255, split_act)
+        return self._forward(x, raw255, split_act, route.enc_pad)
 
-    def _forward(self, x, raw255=False, split_act=False):
+    def _forward(self, x, raw255, split_act, padded):
+        """``padded`` = Route.enc_pad: layer2, layer3 and the output layer on maps zero-padded to that many 1/8 cells (pad_encoders)."""
         many = isinstance(x, (list, tuple))
         first = x[0] if many else x
         hh, ww = first.shape[-2:]
@@ -493,7 +542,6 @@ class BasicEncoder(nn.Module):
             x = (torch.cat(list(x), dim=0) if many else x).contiguous()
             x = conv_norm_act(self.conv1, self.norm1, 2 * (x / 255.0) - 1.0 if raw255 else x, relu=True)
         x = self.layer1[1](self.layer1[0](x, x_norm))
-        padded = self._padded(hh, ww)
         if padded is None:
             x = self.layer3(self.layer2(x))
             return self._final(x, split_act)
@@ -507,13 +555,8 @@ class BasicEncoder(nn.Module):
         return self._final(x, split_act, valid=(h8, w8))
 
     def _padded(self, hh, ww):
-        """padded_size of the 1/8 map when this pass runs layer2, layer3 and the output layer on zero-padded maps (pad_encoders), else None:
-        switch off, a 1/8 map the tuned kernels take as it is (the predicate of RAFT._padded), or an image that is no whole number of 8x8 cells."""
-        if not (self.pad_encoders or PAD_ENCODERS) or hh % 8 or ww % 8:
-            return None
-        _check_pad_encoders(True)
-        hp, wp = padded_size(hh // 8, ww // 8)
-        return None if (hp, wp) == (hh // 8, ww // 8) else (hp, wp)
+        """Route.enc_pad of this encoder called on its own on an (hh, ww) image: its flag (or PAD_ENCODERS), nothing else set."""
+        return resolve_route(pad_encoders=self.pad_encoders, image_size=(hh, ww)).enc_pad
 
     def _p2(self, n, h2, w2, content, device):
         """The zero-filled 64-channel map layer1's output is copied into: allocated and cleared once per (batch, size, content, device: two image sizes may share a padded size) -- the copy
@@ -584,7 +627,7 @@ class BasicUpdateBlock(nn.Module):
     def __init__(self, corr_levels=4, corr_radius=4, hidden_dim=128):
         super().__init__()
         self.hidden_dim = hidden_dim
-        self.update_fp16 = False                               # RAFT's config key ``update_fp16`` (set by RAFT; UPDATE_FP16 for tools)
+        self.route = resolve_route()                           # the options of the pass's Route (RAFT._route sets them: at construction, at every pass)
         self.encoder = BasicMotionEncoder(corr_levels, corr_radius)
         self.gru = SepConvGRU(hidden_dim=hidden_dim, input_dim=128 + hidden_dim)
         self.flow_head = FlowHead(hidden_dim, hidden_dim=256)
@@ -627,22 +670,20 @@ class BasicUpdateBlock(nn.Module):
 
     def fp16(self):
         """This pass runs the covered layers on rpe_conv_f16 (the config key, or the module switch)."""
-        return bool(self.update_fp16 or UPDATE_FP16)
+        return self.route.update_fp16
+
+    update_fp16 = property(fp16)
 
     def packed_convs(self, width, with_key=False):
         """Weights of the update block's convolutions in rpe_conv_fused's layout (cached until a parameter, the stacked gate weights or a
         route switch changes), or None when the fused kernels do not apply (map width not a multiple of 4)."""
-        if width % 4 != 0:
-            if self.fp16():
-                raise ops._lib.RpeError(f'RAFT: update_fp16 needs a 1/8 map with w % 4 == 0 (rpe_conv_f16), got w8 = {width}; it does not run in f32 instead')
+        if not _fused(width, self.fp16()):                      # (a pass has this from its Route; a caller of its own asks here)
             return (None, None) if with_key else None
         e, fh = self.encoder, self.flow_head
         mods = (e.convc1, e.convc2, e.convf2, e.conv, fh.conv1)
         gate_key, W = self.gate_weights(with_key=True)
         # (the convolutions' own weight / bias attributes: walking module.parameters() costs ~100 us a call, and this runs 26 times a frame)
-        key = (_wkey(*[t for m in mods + (e.convf1,) for t in (m.weight, m.bias)]), gate_key, _switches())
-        if self.update_fp16:                                   # (a model without the key keeps the key it always had)
-            key += ('update_fp16',)
+        key = (_wkey(*[t for m in mods + (e.convf1,) for t in (m.weight, m.bias)]), gate_key, _switches(), self.route)
         return _cached(self, '_packed', key, lambda: self._pack_convs(mods, W), with_key)
 
     def _pack_convs(self, mods, W):
@@ -711,22 +752,19 @@ class BasicUpdateBlock(nn.Module):
         # pad_maps: the buffers are zero-padded maps with ``valid`` = (h8, w8) of content; every launch below then takes its entry point's
         # valid-extent form, whose epilogue stores zero in the padding (None = the maps are the content: the plain entry points)
         valid = ws.get('valid')
-        vk = {} if valid is None else dict(valid=valid)   # (flag off: every call below is the call it always was)
+        # (stem_conv, flow_update and the lookup get the keyword only when set: bench.py --full and tests wrap them with the signatures of before this route)
+        vk = {} if valid is None else dict(valid=valid)
         wino = dict(P['wino']) if hx.shape[-1] % 2 == 0 and hx.shape[-2] % 2 == 0 else {}
         if wino and hx.shape[-1] % 4 == 0:
             wino.update(P['wino24'])
             wino.update(P['wino_x3'])                      # (CONV_BF16X3: conv_wino runs the kernel that belongs to the packing)
-        f16 = P['f16']() if 'f16' in P else None            # update_fp16: every covered layer on rpe_conv_f16 (None: every call below is the call it always was)
-        if f16 is not None and valid is not None:
-            raise ops._lib.RpeError('RAFT: update_fp16 has no valid-extent form yet -- not with pad_maps')
+        f16 = P['f16']() if 'f16' in P else None            # update_fp16: every covered layer on rpe_conv_f16 (never on padded maps: resolve_route)
 
         def c3(name, x, out, out2=None):                    # a 3x3 layer: Winograd when available, else the direct implicit GEMM
             if f16 is not None:
                 return ops.conv_fused(x, f16[name], ops.CONV_RELU, out, out2=out2, prepare=True)
             if name in wino:
-                return ops.conv_wino(x, wino[name], ops.CONV_RELU, out, out2=out2, prepare=True, **vk)
-            if valid is not None:
-                raise ops._lib.RpeError('RAFT: pad_maps runs the 3x3 layers on the Winograd kernels (WINOGRAD)')
+                return ops.conv_wino(x, wino[name], ops.CONV_RELU, out, out2=out2, prepare=True, valid=valid)
             return ops.conv_fused(x, P[name], ops.CONV_RELU, out, out2=out2, prepare=True)
         # each GRU half = two implicit-GEMM convolutions whose epilogues are the gates:
         #   z = s(convz hx + ctx), r*h -> rhx ;  h <- (1-z) h + z tanh(convq rhx + ctx)   (in place on hx[:, :c])
@@ -735,12 +773,12 @@ class BasicUpdateBlock(nn.Module):
             P, gconv = dict(P, **{n: f16[n] for n in ('zr1', 'q1', 'zr2', 'q2')}), ops.conv_fused
         gru = []
         for zr, q in (('zr1', 'q1'), ('zr2', 'q2')):
-            gru.append(gconv(hx, P[zr], ops.CONV_GATE_ZR, z_buf, out2=rhx[:, :c], add=ctx[zr], hidden=hx[:, :c], gate_channels=c, prepare=True, **vk))
-            gru.append(gconv(rhx, P[q], ops.CONV_GATE_H, hx[:, :c], add=ctx[q], hidden=hx[:, :c], zgate=z_buf, prepare=True, **vk))
+            gru.append(gconv(hx, P[zr], ops.CONV_GATE_ZR, z_buf, out2=rhx[:, :c], add=ctx[zr], hidden=hx[:, :c], gate_channels=c, prepare=True, valid=valid))
+            gru.append(gconv(rhx, P[q], ops.CONV_GATE_H, hx[:, :c], add=ctx[q], hidden=hx[:, :c], zgate=z_buf, prepare=True, valid=valid))
         gru.append(c3('fh1', hx[:, :c], fh_buf))
         gru.append(ops.flow_update(fh_buf, fh.conv2.weight, fh.conv2.bias.detach(), coords1, coords1, flow_out=flow, dst1=hx[:, 2 * c - 2:],
                                    dst2=rhx[:, 2 * c - 2:], prepare=True, **vk))
-        L = SimpleNamespace(flo=flo, vk=vk, c1=P['convc1_1x1'](corr, ops.CONV_RELU, cor, prepare=True, x3=CONV_BF16X3, **vk) if f16 is None else
+        L = SimpleNamespace(flo=flo, vk=vk, c1=P['convc1_1x1'](corr, ops.CONV_RELU, cor, prepare=True, x3=CONV_BF16X3, valid=valid) if f16 is None else
                             ops.conv_fused(corr, f16['convc1'], ops.CONV_RELU, cor, prepare=True), c2=c3('convc2', cor, cat_buf[:, :192]),
                             f1=ops.stem_conv(flow, P['convf1'], bias=e.convf1.bias.detach(), relu=True, div=1.0, mul=1.0, sub=0.0, out=flo, prepare=True, **vk),
                             f2=c3('convf2', flo, cat_buf[:, 192:]), cv=c3('conv', cat_buf, hx[:, 128:254], rhx[:, 128:254]), gru=gru)
@@ -801,8 +839,6 @@ class BasicUpdateBlock(nn.Module):
         w24 = WINO_2X4 and not CONV_BF16X3 and ops.PackedWino24.supported(c1.weight, hh, ww)
         if self.fp16() and c1.weight.is_cuda:
             # update_fp16: both layers on rpe_conv_f16, the x0.25 fold kept (a power of two: it commutes with the fp16 rounding of normal weights)
-            if not ops.PackedConvF16.supported(c1.weight, hh, ww) or torch.is_grad_enabled():
-                raise ops._lib.RpeError(f'RAFT: update_fp16 needs a 1/8 map with w % 4 == 0 and no autograd (got w8 = {ww}); it does not run in f32 instead')
             p1, p2 = _cached(self, '_mask_packed', (_wkey(*mp), 'f16', _switches()), lambda: (
                 ops.PackedConvF16(c1.weight, c1.bias), ops.PackedConvF16((0.25 * c2.weight).detach(), (0.25 * c2.bias).detach())))
             t = ops.conv_fused(net, p1, ops.CONV_RELU, torch.empty(net.shape[0], c1.out_channels, hh, ww, device=net.device))
@@ -843,28 +879,23 @@ class RAFT(nn.Module):
         # accumulation and blend.  ``mixed_precision`` keeps meaning the pyramid route's fp16 build and stays refused with alternate_corr.
         self.alternate_corr = bool(config.get('alternate_corr', False))
         self.alt_corr_fp16 = bool(config.get('alt_corr_fp16', False))
-        self._check_alternate_corr()
         # ``pad_maps`` (opt-in): at 1/8 maps the tuned kernels refuse -- odd heights, rows that are not whole 16-byte quads -- the update loop runs
         # on maps zero-padded to padded_size(h8, w8) instead of on the generic convolution; the encoders keep the generic route there.
         self.pad_maps = bool(config.get('pad_maps', False))
-        self._check_pad_maps()
-        # ``pad_encoders`` (opt-in): at the same sizes both encoders run layer2, layer3 and the output layer on zero-padded maps (BasicEncoder._padded)
+        # ``pad_encoders`` (opt-in): at the same sizes both encoders run layer2, layer3 and the output layer on zero-padded maps (Route.enc_pad)
         self.pad_encoders = bool(config.get('pad_encoders', False))
-        _check_pad_encoders(self.pad_encoders)
         # ``update_fp16`` (opt-in): the update block's convolutions with fp16 operands on the 16-bit matrix cores (UPDATE_FP16 above names the
         # covered layers and the contract) -- what a user of upstream RAFT's mixed_precision expects of the update block.  Allowed together
         # with mixed_precision and with alternate_corr [+ alt_corr_fp16], which keep their own meaning (the correlation's feature maps).
         self.update_fp16 = bool(config.get('update_fp16', False))
-        self._check_update_fp16()
         self.iters = int(config.get('iters', 12))
         self.hidden_dim = self.context_dim = 128
         self.corr_levels, self.corr_radius = 4, 4
         drop = config.get('dropout', 0.0)
-        self.fnet = BasicEncoder(output_dim=256, norm_fn='instance', dropout=drop)
-        self.cnet = BasicEncoder(output_dim=256, norm_fn='batch', dropout=drop)
-        self.fnet.pad_encoders = self.cnet.pad_encoders = self.pad_encoders
+        self.fnet = BasicEncoder(output_dim=256, norm_fn='instance', dropout=drop, pad_encoders=self.pad_encoders)
+        self.cnet = BasicEncoder(output_dim=256, norm_fn='batch', dropout=drop, pad_encoders=self.pad_encoders)
         self.update_block = BasicUpdateBlock(self.corr_levels, self.corr_radius, hidden_dim=128)
-        self.update_block.update_fp16 = self.update_fp16
+        self._route()                                          # (refuses what does not go together)
         self._pyr = None
         self._ws = None
 
@@ -880,51 +911,28 @@ class RAFT(nn.Module):
                 self._side = s = (torch.cuda.Stream(device=device), torch.cuda.Event(), torch.cuda.Event())
         return s
 
-    def _check_alternate_corr(self):
-        """The on-the-fly correlation is f32 only: refused together with fp16 features or a bf16x3 variant (at construction, and at every
-        pass for the module-level switches)."""
-        if self.alt_corr_fp16 and not self.alternate_corr:
-            raise ops._lib.RpeError('RAFT: alt_corr_fp16 selects the feature precision of alternate_corr and needs alternate_corr: True')
-        if self.alternate_corr and (self.mixed_precision or CORR_BF16X3 or CONV_BF16X3):
-            raise ops._lib.RpeError('RAFT: alternate_corr is f32 only (fp16 features: alt_corr_fp16) -- not with mixed_precision, CORR_BF16X3 or CONV_BF16X3')
-
-    def _check_pad_maps(self):
-        """The valid-extent entry points exist for the f32 Winograd / GEMM kernels only: pad_maps is refused together with the bf16x3 variant of
-        the convolutions and without WINOGRAD (at construction, and at every pass for the module-level switches)."""
-        if (self.pad_maps or PAD_MAPS) and (CONV_BF16X3 or not WINOGRAD):
-            raise ops._lib.RpeError('RAFT: pad_maps runs on the f32 Winograd kernels -- not with CONV_BF16X3 (X3_GRU), not without WINOGRAD')
-
-    def _check_update_fp16(self, w8=None):
-        """update_fp16 runs its covered layers on rpe_conv_f16 or not at all: refused together with the bf16x3 variant of the convolutions,
-        without WINOGRAD (the f32 layers beside it -- the context terms -- are the headline's), with pad_maps / pad_encoders (rpe_conv_f16 has
-        no valid-extent form yet) and on a 1/8 map its kernel does not take (at construction, and at every pass for the module-level
-        switches and the map)."""
-        if not (self.update_fp16 or UPDATE_FP16):
-            return
-        if CONV_BF16X3:
-            raise ops._lib.RpeError('RAFT: update_fp16 and CONV_BF16X3 are two precisions for the same layers -- choose one')
-        if not WINOGRAD:
-            raise ops._lib.RpeError('RAFT: update_fp16 keeps its f32 layers on the Winograd kernels -- not with WINOGRAD = False')
-        if self.pad_maps or PAD_MAPS or self.pad_encoders or PAD_ENCODERS:
-            raise ops._lib.RpeError('RAFT: update_fp16 has no valid-extent form yet -- not with pad_maps / pad_encoders')
-        if w8 is not None and w8 % 4 != 0:
-            raise ops._lib.RpeError(f'RAFT: update_fp16 needs a 1/8 map with w % 4 == 0 (rpe_conv_f16), got w8 = {w8}; it does not run in f32 instead')
+    def _route(self, map_size=None, image_size=None):
+        """The Route of a pass of this model, as it is configured now, on that 1/8 map or image (resolve_route: refuses what does not go
+        together); the update block runs on it from here on."""
+        route = resolve_route(self.mixed_precision, self.alternate_corr, self.alt_corr_fp16, self.pad_maps, self.pad_encoders, self.update_fp16,
+                              map_size, image_size)
+        ub = self.update_block
+        if ub.route[:6] != route[:6]:                          # (rarely: assigning a module attribute costs as much as resolving)
+            ub.route = route.options
+        return route
 
     def _padded(self, h8, w8):
-        """padded_size(h8, w8) when this pass runs its update loop on padded maps, else None (flag off, or a map the kernels take as it is)."""
-        if not (self.pad_maps or PAD_MAPS):
-            return None
-        self._check_pad_maps()
-        hp, wp = padded_size(h8, w8)
-        return None if (hp, wp) == (h8, w8) else (hp, wp)
+        return self._route(map_size=(h8, w8)).loop_pad
 
-    def _pyramid(self, b, h8, w8, device):
+    def _check_update_fp16(self, w8):
+        self._route(map_size=(w8, w8))                         # (the refusals read the width only)
+
+    def _pyramid(self, route, b, h8, w8, device):
         p = self._pyr
-        if self.alternate_corr:
-            self._check_alternate_corr()
+        if route.alternate_corr:
             c = self.fnet.conv2.out_channels
-            if not isinstance(p, ops.AltCorr) or (p.b, p.c, p.h8, p.w8, p.fp16) != (b, c, h8, w8, self.alt_corr_fp16) or p.buf.device != device:
-                self._pyr = p = ops.AltCorr(b, c, h8, w8, self.corr_levels, self.corr_radius, device=device, fp16=self.alt_corr_fp16)
+            if not isinstance(p, ops.AltCorr) or (p.b, p.c, p.h8, p.w8, p.fp16) != (b, c, h8, w8, route.alt_corr_fp16) or p.buf.device != device:
+                self._pyr = p = ops.AltCorr(b, c, h8, w8, self.corr_levels, self.corr_radius, device=device, fp16=route.alt_corr_fp16)
             return p
         x3 = CORR_BF16X3 or CONV_BF16X3
         if p is None or (p.b, p.h8, p.w8) != (b, h8, w8) or p.buf.device != device or getattr(p, 'x3', False) != x3:
@@ -998,18 +1006,23 @@ class RAFT(nn.Module):
         prog.armed = False
         return prog, marks
 
+    def _encode(self, net, images, route=None, **kw):
+        """``net`` on raw 0..255 images under the pass's ``route``; a call from outside a pass resolves its own first, and is refused like a pass."""
+        if route is None:
+            first = images[0] if isinstance(images, (list, tuple)) else images
+            route = self._route(image_size=None if first is None else first.shape[-2:])
+        return net(images, raw255=True, route=route, **kw)
+
     @torch.no_grad()
     def encode_features(self, images):
         """fnet on raw 0..255 images (normalised like forward does); one batch or a list of batches encoded as one."""
-        _check_pad_encoders(self.pad_encoders)
-        return self.fnet(images, raw255=True).float()
+        return self._encode(self.fnet, images).float()
 
     @torch.no_grad()
     def encode_context(self, images):
         """cnet on raw 0..255 images (one batch or a list of batches): (N,256,H/8,W/8) = (tanh(net) | relu(inp)), the initial
         hidden state and the context features of core/RAFT/core/raft.py, activated in the output layer's epilogue."""
-        _check_pad_encoders(self.pad_encoders)
-        return self.cnet(images, raw255=True, split_act=True)
+        return self._encode(self.cnet, images, split_act=True)
 
     @torch.no_grad()
     def encode_both(self, feature_images, context_images):
@@ -1035,16 +1048,16 @@ class RAFT(nn.Module):
         cn.record_stream(cur)                                 # allocated on the side stream, consumed (and freed) on the caller's
         return f, cn
 
-    def _begin(self, pyr, ws, fmap1, fmap2, cnet, fused, flow_init=None):
+    def _begin(self, route, pyr, ws, fmap1, fmap2, cnet, fused, flow_init=None):
         """Everything of a pass in front of the update loop: the correlation pyramid, h <- tanh half of the context encoder's output, the
         GRU's four loop-invariant context terms, and (fused route) coords1 <- grid, flow <- 0 in the workspace's persistent buffers,
         which the flow head's output layer then updates in place.  ``flow_init`` (warm start): coords1 <- grid + flow_init and flow_init
         as the flow the first iteration's motion encoder sees, in ONE launch (rpe_flow_seed) instead of the four plane copies."""
         c = self.hidden_dim
-        if self.alternate_corr:
+        if route.alternate_corr:
             pyr.build(fmap1.float(), fmap2.float())
         else:
-            pyr.build(fmap1.float(), fmap2.float(), fp16_features=self.mixed_precision, bf16x3=(CORR_BF16X3 or CONV_BF16X3) and not self.mixed_precision)
+            pyr.build(fmap1.float(), fmap2.float(), fp16_features=route.mixed_precision, bf16x3=(CORR_BF16X3 or CONV_BF16X3) and not route.mixed_precision)
         hx, rhx = ws['hx'], ws['rhx']
         if ws['valid'] is not None:
             # pad_maps: net, inp and flow_init go into the zero-padded maps by one strided copy each; the context terms are computed on the
@@ -1067,26 +1080,24 @@ class RAFT(nn.Module):
             ops.copy_planes(ws['zero2'], rhx[:, 2 * c - 2:])
         return ctx
 
-    def _prediction(self, flow, hx, upsample):
-        """What forward() returns for the 1/8 ``flow``: mask head on the hidden state + convex x8 up-sampling, or a copy of the flow."""
-        valid = None if self._ws is None else next((w['valid'] for w in self._ws.values() if w['hx'] is hx), None)
-        if valid is not None:                                     # pad_maps: the heads read the padded maps and write the true-size flow
-            if upsample:
-                return ops.upsample_convex(flow, self.update_block.up_mask(hx[:, :self.hidden_dim]), size=valid)
-            return ops.copy_rect(flow, torch.empty(flow.shape[0], 2, *valid, device=flow.device), *valid)
+    def _prediction(self, flow, hx, upsample, valid=None):
+        """What forward() returns for the 1/8 ``flow``: mask head on the hidden state + convex x8 up-sampling, or a copy of the flow.
+        ``valid`` (pad_maps: the workspace's): the heads read the padded maps and write the true-size flow."""
         if upsample:
-            return ops.upsample_convex(flow, self.update_block.up_mask(hx[:, :self.hidden_dim]))
+            return ops.upsample_convex(flow, self.update_block.up_mask(hx[:, :self.hidden_dim]), size=valid)
+        if valid is not None:
+            return ops.copy_rect(flow, torch.empty(flow.shape[0], 2, *valid, device=flow.device), *valid)
         return ops.copy_planes(flow, torch.empty_like(flow))
 
     def _finish(self, ws, upsample, ret_lowres=False):
         """Behind the loop of the fused route: the returned prediction (mask head + convex x8 up-sampling, or a copy of the 1/8 flow), the
         returned hidden state and (``ret_lowres``) a copy of the last 1/8 flow, all fresh tensors (the last one None when not asked for)."""
         c = self.hidden_dim
-        hx, flow = ws['hx'], ws['flow']
-        pred = self._prediction(flow, hx, upsample)
-        if ws['valid'] is not None:                               # pad_maps: hidden state and 1/8 flow come out cropped and contiguous
-            fresh = lambda ch: torch.empty(hx.shape[0], ch, *ws['valid'], device=hx.device)
-            return pred, ops.copy_rect(hx[:, :c], fresh(c), *ws['valid']), ops.copy_rect(flow, fresh(2), *ws['valid']) if ret_lowres else None
+        hx, flow, valid = ws['hx'], ws['flow'], ws['valid']
+        pred = self._prediction(flow, hx, upsample, valid)
+        if valid is not None:                                     # pad_maps: hidden state and 1/8 flow come out cropped and contiguous
+            fresh = lambda ch: torch.empty(hx.shape[0], ch, *valid, device=hx.device)
+            return pred, ops.copy_rect(hx[:, :c], fresh(c), *valid), ops.copy_rect(flow, fresh(2), *valid) if ret_lowres else None
         h_buf = ops.copy_planes(hx[:, :c], torch.empty(hx.shape[0], c, hx.shape[2], hx.shape[3], device=hx.device))
         low = ops.copy_planes(flow, torch.empty_like(flow)) if ret_lowres else None
         return pred, h_buf, low
@@ -1104,10 +1115,10 @@ class RAFT(nn.Module):
         streams = (ops.raw_stream(),) if side is None else (ops.raw_stream(), side[0].cuda_stream)
         return prog, marks, streams
 
-    def _forward_recorded(self, fmap1, fmap2, cnet, iters, upsample, flow_init=None, ret_lowres=False):
+    def _forward_recorded(self, route, fmap1, fmap2, cnet, iters, upsample, flow_init=None, ret_lowres=False):
         """forward() for a small pass on given encoder outputs (sequential tracking: one or two flow pairs per frame) as THREE calls into
         the library: the recorded front (_begin; a warm pass's seeding launch included, flow_init bound like the encoder outputs), the
-        loop's launch list, the recorded tail (_finish).  None = this pass cannot be recorded (the caller goes on call by call)."""
+        loop's launch list, the recorded tail (_finish), whose result it returns.  None = this pass cannot be recorded (the caller goes on call by call)."""
         N, _, h8, w8 = fmap1.shape
         dev = fmap1.device
         c = self.hidden_dim
@@ -1117,16 +1128,10 @@ class RAFT(nn.Module):
                 or (flow_init is not None and tuple(flow_init.shape) != (N, 2, h8, w8)):
             return None                                               # (the call-by-call route raises what needs raising)
         recorded, wkey = _recording(self, self.update_block)
-        pyr = self._pyramid(N, h8, w8, dev)
-        ws = self._workspace(N, h8, w8, dev, self._padded(h8, w8))
-        key = (N, h8, w8, dev.index, ops.raw_stream(), iters, upsample, self.mixed_precision, self.alternate_corr, self.pad_maps, _switches(),
+        pyr = self._pyramid(route, N, h8, w8, dev)
+        ws = self._workspace(N, h8, w8, dev, route.loop_pad)
+        key = (N, h8, w8, dev.index, ops.raw_stream(), iters, upsample, flow_init is not None, ret_lowres, route.options, _switches(),
                pyr.buf.data_ptr(), ws['hx'].data_ptr(), wkey)
-        if self.alt_corr_fp16:
-            key += ('alt_corr_fp16',)
-        if self.update_fp16:
-            key += ('update_fp16',)
-        if flow_init is not None or ret_lowres:                       # (a cold pass keeps the key it always had)
-            key += ('warm' if flow_init is not None else 'cold', ret_lowres)
         ins = {'f1': fmap1, 'f2': fmap2, 'cnet': cnet}
         if flow_init is not None:
             ins['finit'] = flow_init
@@ -1138,17 +1143,15 @@ class RAFT(nn.Module):
             prog, _, streams = self._run_loop(pyr, ws, iters, side)
             prog.run(streams)
             pred, h_buf = torch.empty(post.pred_shape, device=dev), torch.empty(N, c, h8, w8, device=dev)
-            outs = {'pred': pred, 'h': h_buf}
-            if ret_lowres:
-                outs['low'] = low = torch.empty(N, 2, h8, w8, device=dev)
-            post.replay(outs)
-            return ([pred], h_buf, cnet[:, c:], low) if ret_lowres else ([pred], h_buf, cnet[:, c:])
+            low = torch.empty(N, 2, h8, w8, device=dev) if ret_lowres else None
+            post.replay({'pred': pred, 'h': h_buf, **({'low': low} if ret_lowres else {})})
+            return pred, h_buf, low
         if not recorded.wanted(key):
             return None
         prog, _, streams = self._run_loop(pyr, ws, iters, side)      # (built outside the recordings: its launchers must hold the real entry points)
         pre = ops.Recorder()
         with pre:
-            self._begin(pyr, ws, fmap1, fmap2, cnet, True, flow_init)
+            self._begin(route, pyr, ws, fmap1, fmap2, cnet, True, flow_init)
         prog.run(streams)
         post = ops.Recorder()
         with post:
@@ -1160,7 +1163,7 @@ class RAFT(nn.Module):
         post.complete = post.complete and pre.complete
         post.pre, post.pred_shape = pre, tuple(pred.shape)
         recorded.put(key, post)
-        return ([pred], h_buf, cnet[:, c:], low) if ret_lowres else ([pred], h_buf, cnet[:, c:])
+        return pred, h_buf, low
 
     @torch.no_grad()
     def forward(self, image1, image2, upsample=True, iters=None, all_flows=False, fmaps=None, cnet=None, flow_init=None, ret_lowres=False):
@@ -1174,80 +1177,76 @@ class RAFT(nn.Module):
         iters = self.iters if iters is None else iters
         if image1 is None:                                    # encoder outputs given: the images are not needed again
             (N, _, h8, w8), dev = fmaps[0].shape, fmaps[0].device
+            route = self._route(map_size=(h8, w8))
         else:
-            N, _, H, W = image1.shape
+            (N, _, H, W), dev = image1.shape, image1.device
             h8, w8 = H // 8, W // 8
-            dev = image1.device
-        self.update_block.update_fp16 = self.update_fp16
-        self._check_update_fp16(w8)                            # (before the encoders run: a refused pass launches nothing)
+            route = self._route(image_size=(H, W))            # (before the encoders run: a refused pass launches nothing)
         if fmaps is None:
-            f = self.encode_features((image1, image2))
+            f = self._encode(self.fnet, (image1, image2), route).float()
             fmap1, fmap2 = f[:N], f[N:]
         else:
             fmap1, fmap2 = fmaps                              # precomputed by encode_features (caller de-duplicates)
         if cnet is None:
-            cnet = self.encode_context(image1)                # (tanh(net) | relu(inp))
+            cnet = self._encode(self.cnet, image1, route, split_act=True)       # (tanh(net) | relu(inp))
         c = self.hidden_dim
         if flow_init is not None:
             if tuple(flow_init.shape) != (N, 2, h8, w8) or flow_init.dtype != torch.float32 or flow_init.device != dev:
                 raise ValueError(f'RAFT.forward: flow_init must be a float32 ({N},2,{h8},{w8}) tensor on {dev}, got '
                                  f'{flow_init.dtype} {tuple(flow_init.shape)} on {flow_init.device}')
             flow_init = flow_init.contiguous()
+        tail = lambda flows, hidden, low: (flows, hidden, cnet[:, c:]) + ((low,) if ret_lowres else ())      # (what forward returns)
         ub = self.update_block
-        padded = self._padded(h8, w8)                          # pad_maps: the loop's maps, when the tuned kernels refuse (h8, w8)
-        P = ub.packed_convs(w8 if padded is None else padded[1])
+        padded = route.loop_pad                                # pad_maps: the loop's maps, when the tuned kernels refuse (h8, w8)
+        P = ub.packed_convs((padded or (h8, w8))[1])
         fused = P is not None
         if fused and FRAME_OPLISTS and LOOP_OPLIST and not all_flows and N <= FRAME_OPLISTS_MAX_IMAGES and LOOKUP_EVENT_SINK is None:
-            r = self._forward_recorded(fmap1, fmap2, cnet, iters, upsample, flow_init, ret_lowres)
+            r = self._forward_recorded(route, fmap1, fmap2, cnet, iters, upsample, flow_init, ret_lowres)
             if r is not None:
-                return r
-        pyr = self._pyramid(N, h8, w8, dev)
+                return tail([r[0]], r[1], r[2])
+        pyr = self._pyramid(route, N, h8, w8, dev)
         ws = self._workspace(N, h8, w8, dev, padded)
-        ctx = self._begin(pyr, ws, fmap1, fmap2, cnet, fused, flow_init)
+        ctx = self._begin(route, pyr, ws, fmap1, fmap2, cnet, fused, flow_init)
         hx, corr = ws['hx'], ws['corr']                     # hx = (h | motion | flow)
-        h_buf = torch.empty(N, c, h8, w8, device=dev)         # returned to the caller: fresh
-        inp = cnet[:, c:]
-        coords0 = ws['coords0']
         flow_predictions = []
-        if fused:
-            coords1, flow = ws['coords1'], ws['flow']
-        elif flow_init is not None:
-            coords1 = ops.flow_seed(flow_init, coords_out=torch.empty_like(coords0))          # coords0 + flow_init
-        else:
-            coords1 = coords0.clone()
         side = self._side_stream(dev) if fused and SIDE_STREAM and N * h8 * w8 <= SIDE_STREAM_MAX else None
-        if fused and LOOP_OPLIST:
+        if fused and LOOP_OPLIST:                             # the loop as a launch list: whole, or iteration by iteration for their flows
             prog, marks, streams = self._run_loop(pyr, ws, iters, side)
             if not all_flows:
                 prog.run(streams)
             for itr in range(iters if all_flows else 0):
                 prog.run(streams, marks[itr], marks[itr + 1])
                 if itr < iters - 1:
-                    flow_predictions.append(self._prediction(flow, hx, upsample))
-            flow_predictions.append(self._prediction(flow, hx, upsample))
-            iters = 0                                             # (the launch-by-launch loop below is the other route)
+                    flow_predictions.append(self._prediction(ws['flow'], hx, upsample, ws['valid']))
+        elif fused:                                           # the same launches, one by one from Python
+            for itr in range(iters):
+                done = None
+                if side is not None:
+                    # the motion encoder's flow branch (convf1 -> convf2) needs only the flow: it runs on a side stream beside
+                    # lookup -> convc1 -> convc2 and fills the partly idle last rounds of those launches
+                    stream, ev_flow, done = side
+                    ev_flow.record()
+                    with torch.cuda.stream(stream):
+                        stream.wait_event(ev_flow)
+                        ub.encoder.flow_branch(ws['flow'], P, ub.launchers(ws))
+                        done.record()
+                pyr.lookup(ws['coords1'], out=corr, **({} if padded is None else dict(map_size=padded)))
+                ub.step(ws, ctx, ws['flow'], ws['coords1'], None, flow_branch_done=done)
+                if all_flows and itr < iters - 1:
+                    flow_predictions.append(self._prediction(ws['flow'], hx, upsample, ws['valid']))
+        if fused:
+            pred, h_buf, low = self._finish(ws, upsample, ret_lowres)
+            return tail(flow_predictions + [pred], h_buf, low)
+        # the generic route: coords and flow are tensors of the pass, the heads run on a contiguous copy of h
+        coords0 = ws['coords0']
+        coords1 = coords0.clone() if flow_init is None else ops.flow_seed(flow_init, coords_out=torch.empty_like(coords0))     # coords0 + flow_init
+        h_buf = torch.empty(N, c, h8, w8, device=dev)         # returned to the caller: fresh
         for itr in range(iters):
-            done = None
-            if side is not None:
-                # the motion encoder's flow branch (convf1 -> convf2) needs only the flow: it runs on a side stream beside
-                # lookup -> convc1 -> convc2 and fills the partly idle last rounds of those launches
-                stream, ev_flow, done = side
-                ev_flow.record()
-                with torch.cuda.stream(stream):
-                    stream.wait_event(ev_flow)
-                    ub.encoder.flow_branch(flow, P, ub.launchers(ws))
-                    done.record()
-            pyr.lookup(coords1, out=corr, **({} if padded is None else dict(map_size=padded)))
-            if not fused:
-                flow = flow_init if itr == 0 and flow_init is not None else coords1 - coords0
-            coords1 = ub.step(ws, ctx, flow, coords1, h_buf, flow_branch_done=done)
+            pyr.lookup(coords1, out=corr)
+            flow = flow_init if itr == 0 and flow_init is not None else coords1 - coords0
+            coords1 = ub.step(ws, ctx, flow, coords1, h_buf)
             if all_flows or itr == iters - 1:
-                lowres = flow if fused else coords1 - coords0
-                flow_predictions.append(self._prediction(lowres, hx, upsample) if upsample or fused else lowres)
-        if padded is not None:
-            ops.copy_rect(hx[:, :c], h_buf, h8, w8)
-            return (flow_predictions, h_buf, inp) + ((ops.copy_rect(flow, torch.empty(N, 2, h8, w8, device=dev), h8, w8),) if ret_lowres else ())
+                lowres = coords1 - coords0
+                flow_predictions.append(self._prediction(lowres, hx, upsample) if upsample else lowres)
         ops.copy_planes(hx[:, :c], h_buf)
-        if ret_lowres:
-            return flow_predictions, h_buf, inp, ops.copy_planes(flow, torch.empty_like(flow)) if fused else coords1 - coords0
-        return flow_predictions, h_buf, inp
+        return tail(flow_predictions, h_buf, coords1 - coords0 if ret_lowres else None)

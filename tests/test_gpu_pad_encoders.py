@@ -294,7 +294,7 @@ def test_encoder_dispatch_routes_and_module_switch(encs, norm):
                     outs[name] = enc(x, raw255=True, split_act=norm == 'batch')
             finally:
                 _switch(raft, **old)
-        key = [k for k in enc._recorded._progs if k[-1] == 'pad_encoders']
+        key = [k for k in enc._recorded._progs if k[-1].pad_encoders]
         assert key and enc._recorded._progs[key[-1]].complete
         with torch.no_grad():
             outs['row 1 alone'] = torch.cat((outs['call by call'][:1], enc(x[1:2], raw255=True, split_act=norm == 'batch')))
