@@ -5,7 +5,8 @@ Follows core/pose/pose_estimator.py:26-48 (checkpoint + config overrides, 1/dept
 :50-96 (forward: failure gate ``isnan | |log| > 0.1`` -> identity, de-normalise, chain
 ``last_pose <- last_pose * rel^-1``) and :98-125 (get_pose_f2f), and core/utils/frame_class.py:5-50 (Frame).
 Frame-to-model tracking (``frame2frame: False``, :56-96,127-150 with core/fusion/surfel_map.py) is ``SurfelPoseEstimator`` below;
-``from_config`` picks the class from the config as scripts/infer_trajectory.py:50-51 would.
+``from_config`` picks the class from the config as scripts/infer_trajectory.py:50-51 would.  ``MultiPoseEstimator`` / ``MultiSurfelPoseEstimator``
+advance K independent sequences in lockstep, one batched pass per step (``from_config_many``).
 """
 import time
 import warnings
@@ -368,6 +369,36 @@ class SurfelPoseEstimator(PoseEstimator):
         return SE3(p.rel.data.reshape(1, 7)), model_frame, p.flow, p.weights
 
 
+def _many_args(who, intrinsics, baselines, init_poses, max_seq, max_name):
+    """The per-sequence constructor arguments of the lockstep trackers, checked: (intrinsics (K,3,3), baselines (K,), init_poses (K,7)
+    tensor or None, K)."""
+    intrinsics = torch.as_tensor(intrinsics)
+    baselines = torch.as_tensor(baselines)
+    if intrinsics.ndim != 3 or tuple(intrinsics.shape[1:]) != (3, 3):
+        raise ValueError(f'{who}: intrinsics must be (K,3,3), got {tuple(intrinsics.shape)}')
+    n = intrinsics.shape[0]
+    if baselines.shape != (n,):
+        raise ValueError(f'{who}: {n} intrinsics need baselines of shape ({n},), got {tuple(baselines.shape)}')
+    if init_poses is not None:
+        init_poses = (init_poses.data if hasattr(init_poses, 'data') and not isinstance(init_poses, torch.Tensor) else init_poses)
+        if tuple(init_poses.shape) != (n, 7):
+            raise ValueError(f'{who}: {n} sequences need init_poses of shape ({n}, 7), got {tuple(init_poses.shape)}')
+    if not 1 <= n <= max_seq:
+        raise ValueError(f'{who}: 1 to {max_seq} sequences ({max_name}), got {n}')
+    return intrinsics, baselines, init_poses, n
+
+
+def _many_rows(who, rows, n_seq, limgs, rimgs, masks):
+    """``rows`` of a lockstep ``forward`` as a checked list (default: every sequence in order), one input row each."""
+    rows = list(range(n_seq)) if rows is None else [int(k) for k in rows]
+    R = len(rows)
+    if R == 0 or len(set(rows)) != R or any(k < 0 or k >= n_seq for k in rows):
+        raise ValueError(f'{who}.forward: rows must be distinct sequence indices in [0, {n_seq}), got {rows}')
+    if limgs.shape[0] != R or rimgs.shape[0] != R or masks.shape[0] != R:
+        raise ValueError(f'{who}.forward: {R} rows need {R} images and masks, got {limgs.shape[0]}, {rimgs.shape[0]}, {masks.shape[0]}')
+    return rows
+
+
 class MultiSurfelPoseEstimator(PoseEstimator):
     """K independent frame-to-model sequences advanced in lockstep (e.g. the (start, end) scenarios of the reference's
     scripts/benchmark_test.py): ``forward(limgs, rimgs, masks, rows)`` moves every listed sequence on by one frame with one batched
@@ -384,19 +415,8 @@ class MultiSurfelPoseEstimator(PoseEstimator):
         if config.get('frame2frame', True):
             raise ValueError('MultiSurfelPoseEstimator is frame-to-model tracking (frame2frame: False); frame-to-frame tracking already '
                              'batches the frames of one sequence: PoseEstimator.forward_chunk')
-        intrinsics = torch.as_tensor(intrinsics)
-        baselines = torch.as_tensor(baselines)
-        if intrinsics.ndim != 3 or tuple(intrinsics.shape[1:]) != (3, 3):
-            raise ValueError(f'MultiSurfelPoseEstimator: intrinsics must be (K,3,3), got {tuple(intrinsics.shape)}')
-        n = intrinsics.shape[0]
-        if baselines.shape != (n,):
-            raise ValueError(f'MultiSurfelPoseEstimator: {n} intrinsics need baselines of shape ({n},), got {tuple(baselines.shape)}')
-        if init_poses is not None:
-            init_poses = (init_poses.data if hasattr(init_poses, 'data') and not isinstance(init_poses, torch.Tensor) else init_poses)
-            if tuple(init_poses.shape) != (n, 7):
-                raise ValueError(f'MultiSurfelPoseEstimator: {n} sequences need init_poses of shape ({n}, 7), got {tuple(init_poses.shape)}')
-        if not 1 <= n <= SURFEL_MAX_MAPS:
-            raise ValueError(f'MultiSurfelPoseEstimator: 1 to {SURFEL_MAX_MAPS} sequences (RPE_SURFEL_MAX_MAPS), got {n}')
+        intrinsics, baselines, init_poses, n = _many_args('MultiSurfelPoseEstimator', intrinsics, baselines, init_poses, SURFEL_MAX_MAPS,
+                                                          'RPE_SURFEL_MAX_MAPS')
         super().__init__(config, intrinsics[0], 0.0, checkpoint, img_shape)
         self.intrinsics = intrinsics.float()                              # (K,3,3): the buffer PoseEstimator registered, per sequence
         self.baseline = baselines.float()                                 # (K,): torch.tensor(b).float() of each single tracker
@@ -435,13 +455,8 @@ class MultiSurfelPoseEstimator(PoseEstimator):
         row j of the inputs belonging to sequence rows[j].  Returns (absolute poses SE3 (R,7), success (R,) bool on the host, the R
         maps, flow (R,2,h,w), weights)."""
         from . import surfel_map
-        rows = list(range(self.n_seq)) if rows is None else [int(k) for k in rows]
+        rows = _many_rows('MultiSurfelPoseEstimator', rows, self.n_seq, limgs, rimgs, masks)
         R = len(rows)
-        if R == 0 or len(set(rows)) != R or any(k < 0 or k >= self.n_seq for k in rows):
-            raise ValueError(f'MultiSurfelPoseEstimator.forward: rows must be distinct sequence indices in [0, {self.n_seq}), got {rows}')
-        if limgs.shape[0] != R or rimgs.shape[0] != R or masks.shape[0] != R:
-            raise ValueError(f'MultiSurfelPoseEstimator.forward: {R} rows need {R} images and masks, got {limgs.shape[0]}, '
-                             f'{rimgs.shape[0]}, {masks.shape[0]}')
         dev = limgs.device
         limgs, rimgs = limgs.contiguous(), rimgs.contiguous()
         masks = masks.bool()                                               # (a bool mask is the caller's tensor, as Frame keeps it)
@@ -498,6 +513,160 @@ class MultiSurfelPoseEstimator(PoseEstimator):
             surfel_map.fuse_many([self.scenes[rows[j]] for j in passed], Frame(limgs, rimgs, depth=p.depth2 / self.scale, mask=masks),
                                  pose, rows=passed)
         return SE3(pose), okh, [self.scenes[k] for k in rows], p.flow, p.weights
+
+
+MULTI_MAX_SEQUENCES = 64            # (MultiSurfelPoseEstimator's bound, RPE_SURFEL_MAX_MAPS: from_config_many takes the same K in either mode)
+
+
+def _stack_rows(parts):
+    """Rows ``(tensor, j)`` as one batch: the tensor itself when they are exactly its rows in order (the lockstep steady state: no copy),
+    else device slices concatenated (no index tensor, so no blocking host copy)."""
+    t0 = parts[0][0]
+    if t0.shape[0] == len(parts) and all(t is t0 and j == i for i, (t, j) in enumerate(parts)):
+        return t0
+    return torch.cat([t[j:j + 1] for t, j in parts])
+
+
+class MultiPoseEstimator(PoseEstimator):
+    """K independent frame-to-frame sequences advanced in lockstep, frames arriving one at a time per sequence (K live feeds, or the
+    (start, end) scenarios of the reference's scripts/benchmark_test.py): ``forward(limgs, rimgs, masks, rows)`` moves every listed
+    sequence on by one frame with ONE RAFT pass over the 2 R' pairs of the R' rows that have a previous frame, one ``flow2depth`` for the
+    rows that do not (both kinds may share a call), one solve (``rows_alone=True``), one ``ops.pose_gate_chain_rows`` and ONE host
+    synchronisation for all success flags.  Sequence k gets bit for bit what a ``PoseEstimator`` fed its frames alone gets -- poses,
+    success flags, flow, ``last_quality`` rows -- whichever rows share the call: every kernel computes a row independently of its batch
+    and the solve runs with ``partition_rows = 1``.  Honours ``warm_start`` (per row; a row without a kept flow starts from zeros, which
+    is the cold pass bit for bit), ``report_quality`` (row j of ``last_quality`` belongs to sequence rows[j]) and ``reuse_features``.
+    intrinsics (K,3,3), baselines (K,), init_poses (K,7) (SE3 or tensor; default identity).  State per sequence: ``last_pose[k]``,
+    ``success[k]``, and its last frame (image, depth, mask, stereo flow, encoder outputs) and kept 1/8 flow as a row of the batch
+    that produced them, so a lockstep step over the same rows as the last one builds its inputs without a copy."""
+
+    def __init__(self, config, intrinsics, baselines, checkpoint, img_shape, init_poses=None):
+        if not config.get('frame2frame', True):
+            raise ValueError('MultiPoseEstimator is frame-to-frame tracking (frame2frame: True); several frame-to-model sequences are '
+                             'MultiSurfelPoseEstimator (or from_config_many)')
+        intrinsics, baselines, init_poses, n = _many_args('MultiPoseEstimator', intrinsics, baselines, init_poses, MULTI_MAX_SEQUENCES,
+                                                          'MULTI_MAX_SEQUENCES')
+        super().__init__(config, intrinsics[0], 0.0, checkpoint, img_shape)
+        self.intrinsics = intrinsics.float()                              # (K,3,3): the buffer PoseEstimator registered, per sequence
+        self.baseline = baselines.float()                                 # (K,): torch.tensor(b).float() of each single tracker
+        self.n_seq = n
+        self._init_poses = None if init_poses is None else init_poses.float()
+        self.reset()
+
+    def _init_pose_of(self, k):
+        return SE3.Identity(1) if self._init_poses is None else SE3(self._init_poses[k:k + 1])
+
+    def reset(self, rows=None):
+        """Forget sequences ``rows`` (default: all): each restarts at its initial pose, its next frame is a first frame again."""
+        if rows is None:
+            self.last_pose = [None] * self.n_seq
+            self.success = [True] * self.n_seq
+            self._prev = [None] * self.n_seq                              # (the batch dict that holds the sequence's last frame, its row)
+            self._flow_lows = [None] * self.n_seq                         # warm start: (a pass's temporal 1/8 flows, the sequence's row)
+            self.last_quality = None
+            rows = range(self.n_seq)
+        for k in rows:
+            self.last_pose[k] = self._init_pose_of(k)
+            self.success[k] = True
+            self._prev[k] = None
+            self._flow_lows[k] = None
+        return self
+
+    def submit(self, *a, **k):
+        raise RuntimeError('MultiPoseEstimator: submit / result hide ONE sequence\'s encoders behind its previous frame; here the frames '
+                           'of K sequences share each pass, so they cannot be pipelined as well (forward with rows=)')
+
+    def forward_chunk(self, *a, **k):
+        raise RuntimeError('MultiPoseEstimator: forward_chunk batches frames of ONE sequence that are already known, so frames cannot be '
+                           'chunked here; it batches sequences instead (forward with rows=)')
+
+    def _warm_rows(self, seqs):
+        """``_flow_init`` for the tracked sequences ``seqs`` of a call: one forward_interpolate launch over their kept 1/8 flows, zeros for
+        a sequence without one; no flow_init at all (the cold pass) when none has one."""
+        if not self.warm_start:
+            return {}
+        lows = [self._flow_lows[k] for k in seqs]
+        have = [x for x in lows if x is not None]
+        if not have:
+            return dict(ret_lowres=True)
+        zero = (torch.zeros_like(have[0][0][:1]), 0)
+        return dict(ret_lowres=True, flow_init=ops.forward_interpolate(_stack_rows([zero if x is None else x for x in lows])))
+
+    @torch.no_grad()
+    def forward(self, limgs, rimgs, masks, rows=None):
+        """One frame of each sequence in ``rows`` (default: all, in order): limgs, rimgs (R,3,h,w) 0..255, masks (R,1,h,w) True = valid,
+        row j of the inputs belonging to sequence rows[j].  Returns (absolute poses SE3 (R,7), success (R,) bool on the host, flow
+        (R,2,h,w), weights (w2d, w3d) each (R,1,h,w)).  A row on its sequence's first frame has nothing to be tracked against: it returns
+        the sequence's initial pose and success True, its rows of flow and weights are ZEROS (PoseEstimator returns None there) and its
+        ``last_quality`` row is the report of a frame without a solve.  A row the gate rejects keeps its pose, and its frame becomes the
+        sequence's next reference, as in PoseEstimator."""
+        rows = _many_rows('MultiPoseEstimator', rows, self.n_seq, limgs, rimgs, masks)
+        R = len(rows)
+        dev = limgs.device
+        limgs, rimgs = limgs.contiguous(), rimgs.contiguous()
+        masks = masks.bool()                                               # (a bool mask is the caller's tensor, as Frame keeps it)
+        for k in rows:
+            self.last_pose[k] = self.last_pose[k].to(dev)
+        every = rows == list(range(self.n_seq))                            # (device slices, not an index tensor: no blocking host copy)
+        K = self.intrinsics if every else torch.cat([self.intrinsics[k:k + 1] for k in rows])
+        baseline = (self.baseline if every else torch.cat([self.baseline[k:k + 1] for k in rows])) * self.scale
+        tracked = [j for j in range(R) if self._prev[rows[j]] is not None]
+        new = [j for j in range(R) if self._prev[rows[j]] is None]
+        at = {j: i for i, j in enumerate(tracked)}                         # input row -> row of the pass
+
+        def pick(t, idx):
+            return t if len(idx) == R else torch.cat([t[j:j + 1] for j in idx])
+
+        def merge(t, fill):
+            """(R, ...) in input-row order from the pass's rows ``t`` and ``fill`` (1, ...) for every first-frame row."""
+            if not new:
+                return t
+            return torch.cat([t[at[j]:at[j] + 1] if j in at else fill for j in range(R)])
+        if new:                                                            # first frames: stereo depth only (get_pose_f2f)
+            l, r = pick(limgs, new), pick(rimgs, new)
+            depth, stereo_flow, _, cache = self.model.flow2depth(l, r, pick(baseline, new), ret_cache=True)
+            first = dict(img=l, depth=depth / self.scale, mask=pick(masks, new), flow=stereo_flow, fmap=cache['fmap'], cnet=cache['cnet'])
+        p = None
+        if tracked:                                                        # every other row: previous frame -> frame, one pass
+            prev = [self._prev[rows[j]] for j in tracked]
+            f1 = SimpleNamespace(**{name: _stack_rows([(b[name], i) for b, i in prev]) for name in ('img', 'depth', 'mask', 'flow')})
+            cache1 = {name: _stack_rows([(b[name], i) for b, i in prev]) for name in ('fmap', 'cnet')} if self.reuse_features else None
+            l, r, m = pick(limgs, tracked), pick(rimgs, tracked), pick(masks, tracked)
+            p = self._pass(f1, l, r, m, pick(K, tracked), pick(baseline, tracked), cache1=cache1, ret_cache=True, rows_alone=True,
+                           **self._warm_rows([rows[j] for j in tracked]))
+            if new:
+                for j, i in at.items():
+                    masks[j:j + 1] = m[i:i + 1]                            # (`mask2 &= valid` reaches the caller's tensor, as in PoseEstimator)
+            cur = dict(img=l, depth=p.depth2 / self.scale, mask=m, flow=p.stereo_flow, fmap=p.cache['fmap'], cnet=p.cache['cnet'])
+        # :81-91, row by row; a first-frame row chains the identity onto its initial pose, as PoseEstimator.forward does
+        last = torch.cat([self.last_pose[k].data.reshape(1, 7) for k in rows])
+        rel = merge(p.rel.data.reshape(-1, 7) if tracked else None, SE3.Identity(1, device=dev).data if new else None)
+        rel_g, pose, ok = ops.pose_gate_chain_rows(rel, last, self._inv_scale, 1.0e-1)
+        if self.report_quality:                                            # row j belongs to sequence rows[j]; also filled for a rejected row
+            q = denormalise_quality(p.quality, self._inv_scale) if tracked else None
+            blank = blank_quality(1, dev) if new else None
+            self.last_quality = {key: merge(q[key] if tracked else None, blank[key] if new else None) for key in (q or blank)}
+        zeros = (lambda c: torch.zeros((1, c, *limgs.shape[-2:]), device=dev)) if new else (lambda c: None)
+        flow = merge(p.flow if tracked else None, zeros(2))
+        weights = tuple(merge(p.weights[i] if tracked else None, zeros(1)) for i in range(2))
+        self.t_enqueued = time.perf_counter()
+        okh = ok.cpu().bool()                                              # the lockstep frame's one host synchronisation
+        _warn_skipped(R - int(okh.sum()))
+        for j, k in enumerate(rows):
+            self.success[k] = bool(okh[j])
+            self.last_pose[k] = SE3(pose[j:j + 1])
+            self._prev[k] = (cur, at[j]) if j in at else (first, new.index(j))
+            if self.warm_start:                                            # (a rejected frame: the next pair spans two frames, start it cold)
+                self._flow_lows[k] = (p.flow_low, at[j]) if j in at and self.success[k] else None
+        self.last_rel_poses = rel_g
+        return SE3(pose), okh, flow, weights
+
+
+def from_config_many(config, intrinsics, baselines, checkpoint, img_shape, init_poses=None):
+    """``from_config`` for K sequences in lockstep (intrinsics (K,3,3), baselines (K,), init_poses (K,7) or None): MultiPoseEstimator for
+    frame2frame True, MultiSurfelPoseEstimator for False."""
+    cls = MultiPoseEstimator if config.get('frame2frame', True) else MultiSurfelPoseEstimator
+    return cls(config, intrinsics, baselines, checkpoint, img_shape, init_poses)
 
 
 def from_config(config, intrinsics, baseline, checkpoint, img_shape, init_pose=None):

@@ -127,11 +127,12 @@ def track_host_frames(estimator, source, ingest, start_stamp=0, pipelined=True, 
 
 
 def track_sequences(estimator, sequences, start_stamps=None, quality=False):
-    """``track_sequence`` for K sequences at once on a MultiSurfelPoseEstimator: ``sequences[k]`` yields (limg, rimg, mask, stamp) of
-    sequence k (row k of the estimator).  Every lockstep step takes the next frame of each sequence that has one and advances those
-    rows in one ``estimator.forward`` call; a sequence that ends leaves the batch.  With the estimator's init_poses the K runs can be
-    the (start, end) scenarios of one recording (scripts/benchmark_test.py).  Returns the K trajectories in track_sequence's format,
-    each bit for bit the one a SurfelPoseEstimator run of that sequence alone gives.  ``quality``: as ``track_sequence``."""
+    """``track_sequence`` for K sequences at once on a MultiSurfelPoseEstimator (frame to model) or a MultiPoseEstimator (frame to frame):
+    ``sequences[k]`` yields (limg, rimg, mask, stamp) of sequence k (row k of the estimator).  Every lockstep step takes the next frame of
+    each sequence that has one and advances those rows in one ``estimator.forward`` call; a sequence that ends leaves the batch.  With the
+    estimator's init_poses the K runs can be the (start, end) scenarios of one recording (scripts/benchmark_test.py).  Returns the K
+    trajectories in track_sequence's format, each bit for bit the one a SurfelPoseEstimator / PoseEstimator run of that sequence alone
+    gives.  ``quality``: as ``track_sequence``."""
     import torch
     qlog = _QualityLog(estimator, quality)
     n = len(sequences)
