@@ -66,6 +66,8 @@ const char *rpe_version(void);
  *   with RPE_OP_* kinds 34-38 (32 and 33 are the event ops), and the fp16 feature maps of the correlation without the volume:
  *   rpe_corr_alt_bytes_ex, rpe_corr_alt_prepare_ex, rpe_corr_alt_lookup_dt with RPE_OP_CORR_ALT_PREPARE_EX / RPE_OP_CORR_ALT_LOOKUP_DT (39, 40),
  *   and the update block's convolutions with fp16 operands: rpe_conv_f16_packed_bytes, rpe_conv_f16_pack, rpe_conv_f16 with RPE_OP_CONV_F16 (41);
+ *   and the backward of the geometry stage: rpe_depth_backproject_warp_backward, rpe_depth_backproject_warp_backward_workspace_bytes,
+ *   rpe_flow2depth_backward;
  *   the next RPE_ABI_MINOR bump counts them and rpe_conv_wino24*. */
 #define RPE_ABI_VERSION 5
 #define RPE_ABI_MINOR 4
@@ -249,6 +251,45 @@ int rpe_flow2depth(const float *stereo_flow, const float *baseline, int n, int h
  * round-half-even (nearest) of the un-normalised grid_sample position.  Each (n,h,w) int32.            */
 int rpe_warp_taps(const float *flow, int n, int h, int w, int32_t *x0, int32_t *y0, int32_t *xn, int32_t *yn,
                   void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Backward of rpe_depth_backproject_warp (training): the adjoint of core/pose/pose_net.py:73-79,104-113 and
+ * core/interpol/flow_utils.py:4-14, from the gradients of pcl1, pcl2w, inp1 and inp2 to the three flows and depth1.
+ *
+ *   in : the forward's stereo_flow2, time_flow, baseline, K, depth1, image2l, stereo_flow1, mask2 and n, h, w (h, w multiples of 8).
+ *        depth1, stereo_flow1 and mask2 are not read (the stage is linear in the first two, and masks carry no gradient); they are
+ *        required all the same, so that the call names the forward it differentiates.
+ *        grad_pcl1, grad_pcl2w (n,3,h,w), grad_inp1, grad_inp2 (n,8,h/8,w/8): the incoming gradients; any may be NULL = zero.
+ *   out: grad_time_flow, grad_stereo_flow2, grad_stereo_flow1 (n,2,h,w), grad_depth1 (n,1,h,w); any may be NULL = not wanted (the
+ *        others are the same bits).  Every wanted output is written in full.
+ *   - down8: grad_inp* / 4 lands on the 2x2 pixels at offsets 3, 4 of each 8x8 cell.  inp1 channels 0-1 -> grad_stereo_flow1, 2-4 (the
+ *     image) nowhere, 5-7 join grad_pcl1; grad_depth1 = <that, K^-1 [x+.5, y+.5, 1]>.
+ *   - the bilinear warp by time_flow (grid_sample, align_corners=True, zero padding) of stereo_flow2 (2), image2l (3), pcl2 (3):
+ *     grad_time_flow = sum over the 8 channels of g * d(sample)/d(ix, iy), torch's convention (tap differences, a tap outside the image
+ *     reads as zero, d ix / d flow.x = 1); a position that does not read (NaN, or beyond +-1e6: rpe_warp_taps) gives 0.
+ *     The value gradient g * tap weight is summed per SOURCE pixel into grad_stereo_flow2 (both channels) and the pcl2 gradient.
+ *   - pcl2 = depth2 * ray, depth2 = baseline / -sf2.x, replaced by 1 where !(0 < depth2 <= 1) (the forward's float32 test):
+ *     grad_stereo_flow2.x += <grad pcl2, ray> * baseline / sf2.x^2 where valid, 0 where clamped.  mask2 does not gate this.
+ *   Sampling positions and taps are the forward's (float32, rpe_warp_taps); the sums behind them are float64, rounded once.
+ *   The scatter uses no float atomics: taps are counted per source pixel (integer atomics), the counts scanned, the per-source lists
+ *   filled and each list sorted and summed in destination-index order -- bit-identical from run to run, and a row's result does not
+ *   depend on its batch.  One source pixel's list is sorted and summed by one thread: a flow that sends a large share of an image to
+ *   one pixel serialises on it (n log n in the list length).
+ *   workspace: rpe_depth_backproject_warp_backward_workspace_bytes(n, h, w) bytes (0 for non-positive sizes), 16-byte aligned like every
+ *   (n,2|3,h,w) pointer of the call (RPE_E_BADARG otherwise).  NULL required pointers, h % 8, w % 8, non-positive h / w, n < 0 and n > 65535 (a row is
+ *   one grid line of the launches; rpe_flow2depth_backward has the same limit) return RPE_E_BADARG before any launch; h*w >= 2^29 returns RPE_E_UNSUPPORTED; n == 0 is RPE_OK.
+ * rpe_flow2depth_backward: the same disparity adjoint for rpe_flow2depth (the first frame's depth1): grad_stereo_flow (n,2,h,w) with
+ *   .x = grad_depth * baseline / sf.x^2 where the depth is valid, 0 where it was clamped, .y = 0.  Any h, w.
+ * --------------------------------------------------------------------------------------------------------- */
+size_t rpe_depth_backproject_warp_backward_workspace_bytes(int n, int h, int w);
+int rpe_depth_backproject_warp_backward(const float *stereo_flow2, const float *time_flow, const float *baseline,
+                                        const float *K, const float *depth1, const float *image2l,
+                                        const float *stereo_flow1, const uint8_t *mask2, int n, int h, int w,
+                                        const float *grad_pcl1, const float *grad_pcl2w, const float *grad_inp1,
+                                        const float *grad_inp2, float *grad_time_flow, float *grad_stereo_flow2,
+                                        float *grad_stereo_flow1, float *grad_depth1, void *workspace, void *stream);
+int rpe_flow2depth_backward(const float *stereo_flow, const float *baseline, const float *grad_depth, int n, int h, int w,
+                            float *grad_stereo_flow, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * RAFT correlation -- replaces CorrBlock (core/RAFT/core/corr.py of the aimi-lab/RAFT submodule: all-pairs

@@ -236,6 +236,9 @@ SIGNATURES = {
     'rpe_depth_backproject_warp': (_i, [_vp] * 9 + [_i, _i, _i] + [_vp] * 9),
     'rpe_flow2depth': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     'rpe_warp_taps': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    'rpe_depth_backproject_warp_backward_workspace_bytes': (_sz, [_i, _i, _i]),
+    'rpe_depth_backproject_warp_backward': (_i, [_vp] * 8 + [_i, _i, _i] + [_vp] * 10),
+    'rpe_flow2depth_backward': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     'rpe_flow_forward_interpolate': (_i, [_vp, _i, _i, _i, _vp, _vp]),
     'rpe_corr_pyramid_bytes': (_sz, [_i, _i, _i, _i]),
     'rpe_corr_pyramid_bytes_ex': (_sz, [_i, _i, _i, _i, _i]),

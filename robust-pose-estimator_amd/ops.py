@@ -444,6 +444,95 @@ def warp_taps(flow):
     return dict(x0=outs[0], y0=outs[1], xn=outs[2], yn=outs[3])
 
 
+GEOMETRY_GRADS = ('time_flow', 'stereo_flow2', 'stereo_flow1', 'depth1')
+
+
+def depth_backproject_warp_backward(stereo_flow2, time_flow, baseline, K, depth1, image2l, stereo_flow1, mask2, grad_pcl1=None,
+                                    grad_pcl2w=None, grad_inp1=None, grad_inp2=None, want=GEOMETRY_GRADS):
+    """rpe_depth_backproject_warp_backward: the gradients named in ``want`` (subset of GEOMETRY_GRADS) of the stage whose forward is
+    ``depth_backproject_warp``, from the incoming gradients of pcl1, pcl2w (n,3,h,w) and inp1, inp2 (n,8,h/8,w/8); None = zero.
+    -> dict of float32 tensors.  Bit-identical from run to run, a row independent of its batch (no float atomics: include/rpe.h)."""
+    f32 = torch.float32
+    sf2 = _dev(stereo_flow2, f32, 'stereo_flow2')
+    n, _, h, w = sf2.shape
+    tf, b, K = _dev(time_flow, f32, 'time_flow'), _dev(baseline, f32, 'baseline'), _dev(K, f32, 'K')
+    d1, i2 = _dev(depth1, f32, 'depth1'), _dev(image2l, f32, 'image2l')
+    sf1, m2 = _dev(stereo_flow1, f32, 'stereo_flow1'), _mask(mask2, 'mask2')
+    gin = [None if g is None else _dev(g, f32, nm) for g, nm in ((grad_pcl1, 'grad_pcl1'), (grad_pcl2w, 'grad_pcl2w'), (grad_inp1, 'grad_inp1'),
+                                                                 (grad_inp2, 'grad_inp2'))]
+    for g, shape in zip(gin, ((n, 3, h, w), (n, 3, h, w), (n, 8, h // 8, w // 8), (n, 8, h // 8, w // 8))):
+        if g is not None and tuple(g.shape) != shape:
+            raise _lib.RpeError(f'depth_backproject_warp_backward: an incoming gradient has shape {tuple(g.shape)}, expected {shape}')
+    unknown = [k for k in want if k not in GEOMETRY_GRADS]
+    if unknown:
+        raise _lib.RpeError(f'depth_backproject_warp_backward: unknown gradients {unknown}')
+    ch = dict(time_flow=2, stereo_flow2=2, stereo_flow1=2, depth1=1)
+    outs = {k: (torch.empty(n, ch[k], h, w, dtype=f32, device=sf2.device) if k in want else None) for k in GEOMETRY_GRADS}
+    ws = torch.empty(lib().rpe_depth_backproject_warp_backward_workspace_bytes(n, h, w), dtype=torch.uint8, device=sf2.device)
+    check(lib().rpe_depth_backproject_warp_backward(ptr(sf2), ptr(tf), ptr(b), ptr(K), ptr(d1), ptr(i2), ptr(sf1), ptr(m2), n, h, w,
+                                                    *[ptr(g) for g in gin], *[ptr(outs[k]) for k in GEOMETRY_GRADS], ptr(ws),
+                                                    stream_ptr()), 'rpe_depth_backproject_warp_backward')
+    return {k: v for k, v in outs.items() if v is not None}
+
+
+def flow2depth_backward(stereo_flow, baseline, grad_depth):
+    """rpe_flow2depth_backward: grad of ``flow2depth``'s depth with respect to the stereo flow (n,2,h,w); the y channel is zero."""
+    sf = _dev(stereo_flow, torch.float32, 'stereo_flow')
+    n, _, h, w = sf.shape
+    b, gd = _dev(baseline, torch.float32, 'baseline'), _dev(grad_depth, torch.float32, 'grad_depth')
+    out = torch.empty_like(sf)
+    check(lib().rpe_flow2depth_backward(ptr(sf), ptr(b), ptr(gd), n, h, w, ptr(out), stream_ptr()), 'rpe_flow2depth_backward')
+    return out
+
+
+class _GeometryStageFn(torch.autograd.Function):
+    """``depth_backproject_warp`` as one autograd node: forward = that call, backward = depth_backproject_warp_backward.  Differentiable
+    inputs: stereo_flow2, time_flow, depth1, stereo_flow1; differentiable outputs: pcl1, pcl2w, inp1, inp2."""
+
+    @staticmethod
+    def forward(ctx, stereo_flow2, time_flow, baseline, K, depth1, image1l, image2l, stereo_flow1, mask2):
+        g = depth_backproject_warp(stereo_flow2, time_flow, baseline, K, depth1, image1l, image2l, stereo_flow1, mask2)
+        ctx.save_for_backward(stereo_flow2, time_flow, baseline, K, depth1, image2l, stereo_flow1, mask2)
+        ctx.mark_non_differentiable(g['depth2'], g['mask2'], g['mask2w'])
+        ctx.set_materialize_grads(False)                    # an output nothing differentiates arrives as None = the kernel's NULL
+        return g['pcl1'], g['pcl2w'], g['inp1'], g['inp2'], g['depth2'], g['mask2'], g['mask2w']
+
+    @staticmethod
+    def backward(ctx, g_pcl1, g_pcl2w, g_inp1, g_inp2, *_):
+        need = ctx.needs_input_grad
+        names = {'stereo_flow2': need[0], 'time_flow': need[1], 'depth1': need[4], 'stereo_flow1': need[7]}
+        want = [k for k in GEOMETRY_GRADS if names[k]]
+        g = depth_backproject_warp_backward(*ctx.saved_tensors, g_pcl1, g_pcl2w, g_inp1, g_inp2, want=want) if want else {}
+        return (g.get('stereo_flow2'), g.get('time_flow'), None, None, g.get('depth1'), None, None, g.get('stereo_flow1'), None)
+
+
+def geometry_stage(stereo_flow2, time_flow, baseline, K, depth1, image1l, image2l, stereo_flow1, mask2):
+    """``depth_backproject_warp`` (the same dict, bit for bit; 'pcl2' is None) with gradients: pcl1, pcl2w, inp1 and inp2 are
+    differentiable with respect to stereo_flow2, time_flow, depth1 and stereo_flow1; depth2 and the masks carry none."""
+    pcl1, pcl2w, inp1, inp2, depth2, m2v, m2w = _GeometryStageFn.apply(stereo_flow2, time_flow, baseline, K, depth1, image1l, image2l,
+                                                                        stereo_flow1, mask2)
+    return dict(depth2=depth2, mask2=m2v, pcl1=pcl1, pcl2w=pcl2w, mask2w=m2w, inp1=inp1, inp2=inp2, pcl2=None)
+
+
+class _Flow2DepthFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, stereo_flow, baseline):
+        depth, valid = flow2depth(stereo_flow, baseline)
+        ctx.save_for_backward(stereo_flow, baseline)
+        ctx.mark_non_differentiable(valid)
+        ctx.set_materialize_grads(False)
+        return depth, valid
+
+    @staticmethod
+    def backward(ctx, g_depth, _):
+        return (None if g_depth is None else flow2depth_backward(*ctx.saved_tensors, g_depth)), None
+
+
+def flow2depth_grad(stereo_flow, baseline):
+    """``flow2depth`` (the same depth and validity, bit for bit) with the depth differentiable with respect to the stereo flow."""
+    return _Flow2DepthFn.apply(stereo_flow, baseline)
+
+
 # ------------------------------------------------------------------------------------------------- correlation
 class CorrPyramid:
     """Opaque device buffer holding the 4-level correlation pyramid of a batch of pairs."""

@@ -68,12 +68,18 @@ class PoseNet(nn.Module):
             return depth, flow, valid, dict(fmap=f[:n], cnet=cn)
         return depth, flow, valid
 
-    def forward(self, image1l, image2l, intrinsics, baseline, image1r, image2r, mask1=None, mask2=None, ret_confmap=False):
+    def forward(self, image1l, image2l, intrinsics, baseline, image1r, image2r, mask1=None, mask2=None, ret_confmap=False, ret_flows=False):
         """The reference's TRAINING forward (core/pose/pose_net.py:28-58): both stereo depths, the temporal flow, the weight
         maps and the declarative pose layer -> (log-pose (n,6), depth1, depth2[, (w2d, w3d)]).  Gradients reach what the
         reference trains while the flow network is frozen (train.yaml: freeze_flow_steps; RAFT.eval() always): the two
         weight heads and ``loss_weight``, through the layer's closed-form backward (csrc/pose_backward.hip).  Flow, depth
-        and the warps are computed by the (non-differentiable) HIP kernels, i.e. this mirrors the frozen-flow phase."""
+        and the warps are computed by the (non-differentiable) HIP kernels, i.e. this mirrors the frozen-flow phase.
+        ``ret_flows``: the gradients go one stage further, to the three flows.  The flows of the (still gradient-free) RAFT passes become
+        leaves that require grad, depth1 comes from ``ops.flow2depth_grad`` and the geometry stage runs as ``ops.geometry_stage``
+        (csrc/geometry_backward.hip), so the heads' inputs and the pose layer's time_flow / pcl1 / pcl2w carry gradients.  The result gains
+        a last element {'time_flow', 'stereo_flow1', 'stereo_flow2'}: after ``loss.backward()`` each tensor's ``.grad`` is d loss / d that
+        flow -- what a differentiable flow model has to be handed.  Values, and the gradients of the heads and ``loss_weight``, are those
+        of the default call; without the flag nothing here changes, launches included."""
         n = image1l.shape[0]
         intrinsics = intrinsics.expand(n, 3, 3).contiguous()
         baseline = baseline.expand(n).contiguous()
@@ -81,7 +87,8 @@ class PoseNet(nn.Module):
             depth1, stereo_flow1, valid1 = self.flow2depth(image1l, image1r, baseline)
             mask1 = (mask1.bool() & valid1) if mask1 is not None else valid1
             mask2 = mask2.bool().clone() if mask2 is not None else torch.ones_like(valid1)
-            s = self.stages(image1l, image2l, intrinsics, baseline, depth1, image2r, mask1, mask2, stereo_flow1, heads=False)
+            s = self.stages(image1l, image2l, intrinsics, baseline, depth1, image2r, mask1, mask2, stereo_flow1, heads=False,
+                            grad_flows=ret_flows)
         if self.use_weights and self.train_heads_hip:
             # the heads' training route on hand-written kernels (csrc/unet_train.hip): the parts are read where they are (no torch.cat),
             # the Sigmoid modules' work is fused into the resize
@@ -95,15 +102,18 @@ class PoseNet(nn.Module):
         _, log6 = self.pose_head(s['time_flow'], s['pcl1'], s['pcl2w'], w2d, w3d, mask1, s['mask2w'], s['intrinsics'],
                                  self.loss_weight.repeat(n, 1))
         pose_tan = log6.squeeze(1)
-        if ret_confmap:
-            return pose_tan, depth1, s['depth2'], (w2d, w3d)
-        return pose_tan, depth1, s['depth2']
+        out = (pose_tan, depth1, s['depth2'], (w2d, w3d)) if ret_confmap else (pose_tan, depth1, s['depth2'])
+        if ret_flows:
+            out = (*out, {k: s[k] for k in ('time_flow', 'stereo_flow1', 'stereo_flow2')})
+        return out
 
     def freeze_flow(self, freeze=True):
-        """pose_net.py:148-153.  Un-freezing the flow network needs its backward, which is not built (SURVEY.md 8f-4 covers the
-        declarative layer): refuse instead of training the heads against silently missing flow gradients."""
+        """pose_net.py:148-153.  Un-freezing the flow network needs its backward, which is not built: the gradients of the pose loss now
+        reach the three flows (``forward(..., ret_flows=True)``: the pose layer's and the geometry stage's backward) and stop there.
+        Refuse instead of training the heads against silently missing flow-network gradients."""
         if not freeze:
-            raise NotImplementedError('training the flow network (freeze_flow(False)) is out of scope: RAFT has no backward here')
+            raise NotImplementedError('training the flow network (freeze_flow(False)) is out of scope: the gradients stop at the flows '
+                                      '(forward(..., ret_flows=True) returns them); RAFT has no backward here')
         for p in self.parameters():
             p.requires_grad = True
         for p in self.flow.parameters():
@@ -144,13 +154,16 @@ class PoseNet(nn.Module):
 
     @torch.no_grad()
     def stages(self, image1l, image2l, intrinsics, baseline, depth1, image2r, mask1, mask2, stereo_flow1, cache1=None, heads=True, enc2=None,
-               flow_init=None, ret_lowres=False):
+               flow_init=None, ret_lowres=False, grad_flows=False):
         """Every stage of infer() before the solve.  ``cache1`` = {'fmap','cnet'} of image1l from the previous call
         (streaming: frame t's image2l is frame t+1's image1l), so only the two new images are encoded -- or not even those when
         ``enc2`` = encode_frame(image2l, image2r) was computed ahead of the call (needs cache1).
         ``flow_init`` (n,2,h/8,w/8): warm start of the n TEMPORAL pairs (RAFT.forward's flow_init); the n stereo pairs of the same RAFT
         batch start from zero, so depth and stereo flow are bit-identical to a cold pass.  ``ret_lowres``: the temporal pairs' last 1/8 flow
-        (n,2,h/8,w/8) is added as 'time_flow_low' to the result and to its 'cache2'."""
+        (n,2,h/8,w/8) is added as 'time_flow_low' to the result and to its 'cache2'.
+        ``grad_flows`` (the training forward's ``ret_flows``): time_flow, stereo_flow2 and stereo_flow1 become leaves that require grad
+        ('stereo_flow1' is added to the result) and the geometry stage runs, with gradients enabled, through ``ops.flow2depth_grad`` and
+        ``ops.geometry_stage``: the same values, now differentiable with respect to the three flows."""
         n = image1l.shape[0]
         intrinsics = intrinsics.expand(n, 3, 3).contiguous()
         baseline = baseline.expand(n).contiguous()
@@ -177,8 +190,15 @@ class PoseNet(nn.Module):
         time_flow = flow_predictions[-1][:n].contiguous()
         stereo_flow2 = flow_predictions[-1][n:].contiguous()
         hidden, context = hidden[:n], context[:n]
-        g = ops.depth_backproject_warp(stereo_flow2, time_flow, baseline, intrinsics, depth1, image1l, image2l,
-                                       stereo_flow1, mask2)
+        if grad_flows:
+            with torch.enable_grad():
+                time_flow, stereo_flow2, stereo_flow1 = (t.detach().requires_grad_(True) for t in (time_flow, stereo_flow2, stereo_flow1))
+                g = ops.geometry_stage(stereo_flow2, time_flow, baseline, intrinsics, ops.flow2depth_grad(stereo_flow1, baseline)[0],
+                                       image1l, image2l, stereo_flow1, mask2)
+            g['stereo_flow1'] = stereo_flow1
+        else:
+            g = ops.depth_backproject_warp(stereo_flow2, time_flow, baseline, intrinsics, depth1, image1l, image2l,
+                                           stereo_flow1, mask2)
         w2d, w3d = self._heads(g, hidden, context) if heads else (None, None)
         g.update(time_flow=time_flow, stereo_flow2=stereo_flow2, hidden=hidden, context=context, w2d=w2d, w3d=w3d,
                  intrinsics=intrinsics, cache2=dict(fmap=f2l, cnet=c2l))
