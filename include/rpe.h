@@ -939,8 +939,10 @@ int rpe_ingest_stereo(const uint8_t *frames, const uint8_t *right, int n, int h,
  * Layout: SoA f32 with capacity cap -- opts (3,cap) world points in mm, rgb (3,cap), conf (cap), t_created (cap) -- so that
  * [:, :n] views are the reference's (3,N) tensors.  The count n lives in a device int32 (*count); *overflow is a device int32 that a
  * kernel ORs with 1 when it would have written past cap (it then writes nothing past cap, stores n = cap and returns normally) and
- * with 2 when n exceeded the caller's n_bound (items past the bound were not visited).  No entry point synchronises the host: every
- * kernel reads n from *count and is launched over n_bound, a host-side upper bound of n (the caller tracks n + h*w per fuse).
+ * with 2 when n exceeded the caller's n_bound (surfels past the bound are not updated, and source or pixel items past the last
+ * launched tile of 1024 are dropped: beyond n <= cap and writes staying inside the destination, the result is then unspecified).
+ * No entry point synchronises the host: every kernel reads n from *count and is launched over n_bound, a host-side upper bound
+ * of n (the caller tracks n + h*w per fuse).
  * Compactions (init, fuse, prune) preserve order and are deterministic (block counts -> scan -> scatter): the map's order is the
  * reference's (boolean-mask gathers, torch.cat appends).  They read a source map and write a DIFFERENT destination map (the caller
  * ping-pongs two buffers); fuse also updates the source's matched surfels in place before compacting.

@@ -142,6 +142,87 @@ def test_restatement_reproduces_reference_renders(rpe, gold, case):
     assert fills > 0 or case == 'a'              # (case a: most surfels saturate at conf 1, so nearly every pixel is a tie)
 
 
+def test_restatement_dtype_float32_is_todays_and_float64_agrees(rpe, gold):
+    """The restatement's dtype argument: float32 given explicitly reproduces the golden hashes bit for bit (as the default does
+    above); float64 runs the same operations and lands within float32 rounding of it where no decision is involved (the init)."""
+    K, frames, poses = _scene(gold)
+    img, depth, mask, conf = frames[0]
+    m = sr.RefMap(K, img, depth, mask, conf, poses[0], dtype=torch.float32, **CASES['b'])
+    d = sr.RefMap(K, img, depth, mask, conf, poses[0], dtype=torch.float64, **CASES['b'])
+    assert d.opts.dtype == torch.float64 and torch.allclose(d.opts, m.opts.double(), rtol=1e-5, atol=1e-4)
+    for s in range(1, 21):
+        img, depth, mask, _ = frames[s]
+        m.fuse(img, depth, mask, poses[s])
+        assert m.opts.dtype == torch.float32 and _sha(m.conf) + _sha(m.t_created) == gold[f'b_sha'][s], s
+    g = {k[2:]: v for k, v in gold.items() if k.startswith('b_')}
+    opts, rgb, conf = (torch.from_numpy(g[k]) for k in ('r_opts', 'r_rgb', 'r_conf'))
+    T = torch.from_numpy(g['T1'])
+    a = sr.render(opts, rgb, conf, K, T, (32, 48), True)
+    b = sr.render(opts, rgb, conf, K, T, (32, 48), True, dtype=torch.float32)
+    for x, y in zip(a, b):
+        assert x.dtype == y.dtype and torch.equal(torch.nan_to_num(x.double()), torch.nan_to_num(y.double()))
+    c = sr.render(opts, rgb, conf, K, T, (32, 48), True, dtype=torch.float64)
+    assert c[0].dtype == torch.float64 and torch.equal(c[2].float(), a[2])       # the winners' conf: copied, so equal
+
+
+@pytest.mark.parametrize('pose', ['identity', 'shift', 'turn'])
+def test_exact_scenes_decide_alike_in_float32_and_float64(rpe, pose):
+    """The precondition of tests/test_gpu_surfel_edges.py, also where there is no GPU: on the exact scenes the float32 and float64
+    restatements take the same decisions, and those are the ones each scene was built to provoke."""
+    import surfel_edges as se
+    s = se.fuse_scene(pose)
+    for case in se.FUSE_CASES:
+        _, t = se.check_exact_fuse(s, *case)
+        assert torch.equal(t['flags'], s['expect']), [n for n, f, e in zip(s['names'], t['flags'], s['expect']) if f != e]
+        assert int(t['new'].sum()) == 77                          # 96 pixels - 1 masked - 18 matched
+        if case[1] < 2 and case[2] == 7:
+            assert t['n'] == 2                                    # t_max 0 / 1: the appended surfels go again; 'stable' and 'clamp' stay
+    if pose == 'identity':
+        _, t = se.check_exact_fuse(se.negzero_scene(), True, 2, 7)
+        assert bool(t['flags'].all()) and not bool(t['new'].reshape(8, 12)[2, 0]) and not bool(t['new'].reshape(8, 12)[6, 0])
+        for h, w, n, mask in ((8, 12, 0, True), (8, 12, 3, False), (1, 1, 2, True), (8, 1, 2, True)):
+            _, t = se.check_exact_fuse(se.small_scene(h, w, n, mask), True, 2, 7)
+            assert not bool(t['flags'].any()) and t['n'] == n + (h * w if mask else 0)
+    for h, w in se.RENDER_SHAPES:
+        for nan_plane in (False, True):
+            for dt in (False, True):
+                a, b = se.check_exact_render(se.render_scene(h, w, pose, nan_plane), dt)
+                assert not bool(torch.isnan(b['img']).any())
+    if pose == 'identity':
+        for axis, pix in (('u', (2, 0)), ('v', (0, 4))):          # a -0.0 coordinate is inside, and its surfel wins column / row 0
+            for dt in (False, True):
+                _, t = se.check_exact_render(se.render_negzero_scene(axis), dt)
+                assert int(t['winner'][pix[0] * 12 + pix[1]]) == 1 and float(t['confidence'][pix]) == .5
+    _, t = se.check_exact_render(se.zero_conf_scene(), False)
+    assert int(t['mask'].sum()) == 1 and float(t['confidence'][1, 5]) == -float('inf')       # zero-conf winners: mask 0; -inf: mask 1
+
+
+def test_prune_rows_are_what_the_patterns_say(rpe):
+    import surfel_edges as se
+    for n in se.PRUNE_SIZES[:10]:
+        for pat in se.PRUNE_PATTERNS:
+            rows, keep = se.prune_rows(n, pat)
+            assert rows.shape == (8, n) and keep.shape == (n,)
+            if pat == 'tiles' and n > 1024:
+                assert not bool(keep[:1024].any()) and bool(keep[1024:min(n, 2048)].all())
+    rows, keep = se.prune_edge_rows()
+    assert torch.equal(se.prune_keep(rows[6].view(torch.float32), rows[7].view(torch.float32), 20, 6), keep)
+
+
+def test_render_refuses_two_pixel_axes_without_a_gpu(rpe):
+    from rpe_amd import _lib
+    L = rpe.lib()
+    fake = ctypes.c_void_p(0x1000)
+    good = _lib.SurfelMapDesc(fake, fake, fake, fake, 16, fake, fake)
+    for h, w in ((2, 4), (4, 2), (2, 2)):
+        assert L.rpe_surfel_render(good, 0, fake, fake, 1, h, w, fake, fake, fake, fake, fake, None) == -1
+    assert L.rpe_surfel_render(good, 17, fake, fake, 1, 4, 4, fake, fake, fake, fake, fake, None) == -1      # bound past the capacity
+    descs = (_lib.SurfelMapDesc * 65)(*[good] * 65)
+    nb = (ctypes.c_int64 * 65)(*[0] * 65)
+    assert L.rpe_surfel_render_many(65, descs, nb, fake, fake, 1, 4, 4, fake, fake, fake, fake, fake, None) == -1   # K = 65
+    assert L.rpe_surfel_workspace_bytes_many(65, nb, 4, 4) == 0 and L.rpe_surfel_workspace_bytes_many(64, nb, 4, 4) > 0
+
+
 def test_ply_writer_reproduces_reference_bytes(rpe, gold, tmp_path):
     from rpe_amd.surfel_map import SurfelMap
     m = SurfelMap(opts=torch.from_numpy(gold['a_opts20']), rgb=torch.from_numpy(gold['a_rgb20']), conf=torch.from_numpy(gold['a_conf20']),
