@@ -68,6 +68,8 @@ const char *rpe_version(void);
  *   and the update block's convolutions with fp16 operands: rpe_conv_f16_packed_bytes, rpe_conv_f16_pack, rpe_conv_f16 with RPE_OP_CONV_F16 (41);
  *   and the backward of the geometry stage: rpe_depth_backproject_warp_backward, rpe_depth_backproject_warp_backward_workspace_bytes,
  *   rpe_flow2depth_backward;
+ *   and the backward of RAFT's output heads: rpe_upsample_convex_backward, rpe_conv_bwd_weight, rpe_conv_bwd_weight_workspace_bytes,
+ *   rpe_conv3x3_to2_bwd_data, rpe_relu_backward, rpe_sum_groups;
  *   the next RPE_ABI_MINOR bump counts them and rpe_conv_wino24*. */
 #define RPE_ABI_VERSION 5
 #define RPE_ABI_MINOR 4
@@ -290,6 +292,42 @@ int rpe_depth_backproject_warp_backward(const float *stereo_flow2, const float *
                                         float *grad_stereo_flow1, float *grad_depth1, void *workspace, void *stream);
 int rpe_flow2depth_backward(const float *stereo_flow, const float *baseline, const float *grad_depth, int n, int h, int w,
                             float *grad_stereo_flow, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Backward of RAFT's output heads (csrc/raft_backward.hip): the tail of the last update iteration,
+ *     t_f = relu(conv3x3(net; fh.conv1)), delta = conv3x3(t_f; fh.conv2), t_m = relu(conv3x3(net; mask.0)),
+ *     m = 0.25 conv1x1(t_m; mask.2), flow_up = upsample_convex(flow_prev + delta, m)
+ * (core/RAFT/core/update.py FlowHead, BasicUpdateBlock.mask; core/RAFT/core/raft.py upsample_flow).  f32, NCHW.  No float atomics; every
+ * sum runs in an order fixed by the shapes alone: two runs give the same bits, on any device.
+ * rpe_upsample_convex_backward: from grad_up (b,2,8 h8,8 w8; 16-byte aligned), flow (b,2,h8,w8) and mask (b,576,h8,w8) -- the logits exactly
+ *   as rpe_upsample_convex reads them -- d_flow (b,2,h8,w8) and d_mask (b,576,h8,w8), both written in full.  Gather form: d_flow at a cell
+ *   collects from the nine cells whose 3x3 window (zero padded, as the forward's unfold) holds it; d_mask_k = p_k (g_k - sum_k' p_k' g_k') per
+ *   sub-pixel with the forward's softmax code (double).  Dense tensors; any h8, w8; b == 0 is RPE_OK, b > 65535 RPE_E_BADARG.
+ * rpe_conv_bwd_weight: d_weight (cout,cin,kh,kw) and d_bias (cout) (either may be NULL) of y = conv(x; W) + bias, stride 1, 'same' zero
+ *   padding, (kh,kw) = (3,3) or (1,1), from x (b,cin,h,w) and dy (b,cout,h,w) at ANY h, w; x and dy may be channel slices (batch strides in
+ *   floats, at least the slice).  A GEMM on the f32 matrix cores (v_mfma_f32_32x32x2_f32) with M = cout, N = cin kh kw, K = b h w; layers of one
+ *   or two output channels run a plain kernel.  K is split into chunks of c(K) = max(1024, round_up(ceil(K / 64), 32)) pixels -- at most 64, a
+ *   function of b h w alone --, each chunk writes a partial and the partials are added in index order in f64; d_bias is dy's channel sum under
+ *   the same rule; both leave multiplied by ``scale`` (the mask head's 0.25; 1 otherwise), applied to the f64 sum.  workspace: rpe_conv_bwd_weight_workspace_bytes(...) bytes (0 for a shape it refuses), 16-byte aligned.  Non-positive
+ *   sizes, other kernels, NULL x / dy / workspace: RPE_E_BADARG; b h w, cin h w, cout h w or the weight's size >= 2^31: RPE_E_UNSUPPORTED.
+ * rpe_conv3x3_to2_bwd_data: the data gradient of rpe_conv3x3_to2 (weight (2,c,3,3)): dx (b,c,h,w) = conv(dy (b,2,h,w); W transposed and
+ *   flipped), multiplied by [act > 0] when act (b,c,h,w: the ReLU output that was the layer's input) is given.  Channel slices throughout.
+ * rpe_relu_backward: out = act > 0 ? grad : 0 on (b,c,hw) channel slices; out may be grad.
+ * rpe_sum_groups: out (b,c,hw; a channel slice) = act(sum_g parts[g] + bias[c]) for parts (groups,b,c,hw) dense, added in group order in f64,
+ *   bias may be NULL, relu 0 / 1.  The forward convolution kernels add in one k-ordered f32 chain; the tail runs them on groups of input
+ *   channels and adds the groups here, which keeps its results at the error of a blocked float32 sum.
+ * --------------------------------------------------------------------------------------------------------- */
+int rpe_upsample_convex_backward(const float *grad_up, const float *flow, const float *mask, int b, int h8, int w8, float *d_flow,
+                                 float *d_mask, void *stream);
+size_t rpe_conv_bwd_weight_workspace_bytes(int b, int cin, int cout, int h, int w, int kh, int kw);
+int rpe_conv_bwd_weight(const float *x, long long x_batch_stride, const float *dy, long long dy_batch_stride, int b, int cin, int cout,
+                        int h, int w, int kh, int kw, float scale, float *d_weight, float *d_bias, void *workspace, void *stream);
+int rpe_conv3x3_to2_bwd_data(const float *dy, long long dy_batch_stride, const float *weight, const float *act,
+                             long long act_batch_stride, int b, int c, int h, int w, float *dx, long long dx_batch_stride, void *stream);
+int rpe_relu_backward(const float *grad, long long grad_batch_stride, const float *act, long long act_batch_stride, int b, int c, int hw,
+                      float *out, long long out_batch_stride, void *stream);
+int rpe_sum_groups(const float *parts, int groups, int b, int c, int hw, const float *bias, int relu, float *out, long long out_batch_stride,
+                   void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * RAFT correlation -- replaces CorrBlock (core/RAFT/core/corr.py of the aimi-lab/RAFT submodule: all-pairs

@@ -239,6 +239,12 @@ SIGNATURES = {
     'rpe_depth_backproject_warp_backward_workspace_bytes': (_sz, [_i, _i, _i]),
     'rpe_depth_backproject_warp_backward': (_i, [_vp] * 8 + [_i, _i, _i] + [_vp] * 10),
     'rpe_flow2depth_backward': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    'rpe_upsample_convex_backward': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    'rpe_conv_bwd_weight_workspace_bytes': (_sz, [_i] * 7),
+    'rpe_conv_bwd_weight': (_i, [_vp, _ll, _vp, _ll] + [_i] * 7 + [_fl, _vp, _vp, _vp, _vp]),
+    'rpe_conv3x3_to2_bwd_data': (_i, [_vp, _ll, _vp, _vp, _ll, _i, _i, _i, _i, _vp, _ll, _vp]),
+    'rpe_relu_backward': (_i, [_vp, _ll, _vp, _ll, _i, _i, _i, _vp, _ll, _vp]),
+    'rpe_sum_groups': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _ll, _vp]),
     'rpe_flow_forward_interpolate': (_i, [_vp, _i, _i, _i, _vp, _vp]),
     'rpe_corr_pyramid_bytes': (_sz, [_i, _i, _i, _i]),
     'rpe_corr_pyramid_bytes_ex': (_sz, [_i, _i, _i, _i, _i]),

@@ -7,6 +7,7 @@
 // generic route (conv_direct.hip: map sizes the tuned kernels refuse) and remove the sigmoid / mul / cat / tanh / blend round trips
 // through HBM between the convolutions.
 #include "rpe_common.h"
+#include "upsample_device.h"
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
@@ -435,8 +436,7 @@ __global__ __launch_bounds__(256) void k_upsample_convex(const float* __restrict
             // of expf in two weights of opposite flow is 2.4e-5 and a float32 sum of nine terms adds as much (torch's float32 operator is
             // off by 2.8e-5 against float64) -- more than the 2e-5 this kernel is held to.  (-Inf, +Inf and NaN logits behave as in float32.)
             double e[9], sum = 0.0;
-#pragma unroll
-            for (int k = 0; k < 9; ++k) { e[k] = exp((double)m[k] - (double)mx); sum += e[k]; }
+            CONVEX_SOFTMAX9(m, mx, e, sum)                                // (upsample_device.h: the backward recomputes the same weights)
             double ax = 0.0, ay = 0.0;
 #pragma unroll
             for (int k = 0; k < 9; ++k) { ax += e[k] * (double)fx[k]; ay += e[k] * (double)fy[k]; }

@@ -1444,3 +1444,226 @@ def unet_train_grad_offsets(cin):
     """First float of each of the 36 parameter gradients in unet_train_backward's blob, and the blob's size as the 37th entry."""
     L = lib()
     return [L.rpe_unet_train_grad_offset(cin, k) for k in range(UNET_TRAIN_NPARAM + 1)]
+
+
+# ------------------------------------------------------------------------------------------------- backward of RAFT's output heads
+def upsample_convex_backward(grad_up, flow, mask):
+    """rpe_upsample_convex_backward: (d_flow (b,2,h8,w8), d_mask (b,576,h8,w8)) of ``upsample_convex(flow, mask)`` from grad_up
+    (b,2,8 h8,8 w8); ``mask`` = the logits as the forward read them.  Bit-identical from run to run."""
+    fl, mk, gu = _nchw(flow, 'flow'), _nchw(mask, 'mask'), _nchw(grad_up, 'grad_up')
+    b, _, h8, w8 = fl.shape
+    if tuple(fl.shape) != (b, 2, h8, w8) or tuple(mk.shape) != (b, 576, h8, w8) or tuple(gu.shape) != (b, 2, 8 * h8, 8 * w8):
+        raise _lib.RpeError('upsample_convex_backward: flow (b,2,h8,w8), mask (b,576,h8,w8) and grad_up (b,2,8 h8,8 w8) expected')
+    d_flow, d_mask = torch.empty_like(fl), torch.empty_like(mk)
+    check(lib().rpe_upsample_convex_backward(ptr(gu), ptr(fl), ptr(mk), b, h8, w8, ptr(d_flow), ptr(d_mask), stream_ptr()),
+          'rpe_upsample_convex_backward')
+    return d_flow, d_mask
+
+
+def conv_bwd_weight(x, dy, kernel, scale=1.0, bias=True):
+    """rpe_conv_bwd_weight: (dW (cout,cin,kh,kw), db (cout) or None) of a stride-1 'same' convolution with ``kernel`` = (3,3) or (1,1) from
+    its input x (b,cin,h,w) and the gradient dy (b,cout,h,w) of its output, at any map size; both may be channel slices.  On the f32 matrix
+    cores, K = b h w split by a rule of the shapes alone: bit-identical from run to run.  ``scale`` multiplies both results."""
+    xp, xbs = _chan_slice(x, 'conv_bwd_weight: x')
+    dp, dbs = _chan_slice(dy, 'conv_bwd_weight: dy')
+    b, cin, hh, ww = x.shape
+    cout = dy.shape[1]
+    kh, kw = kernel
+    if tuple(dy.shape) != (b, cout, hh, ww):
+        raise _lib.RpeError(f'conv_bwd_weight: dy {tuple(dy.shape)} does not match x {tuple(x.shape)}')
+    nws = lib().rpe_conv_bwd_weight_workspace_bytes(b, cin, cout, hh, ww, kh, kw)
+    if nws == 0:
+        raise _lib.RpeError(f'conv_bwd_weight: unsupported shape (kernel {kh}x{kw}; 3x3 and 1x1, non-empty tensors)')
+    ws = torch.empty(nws, dtype=torch.uint8, device=x.device)
+    dw = torch.empty(cout, cin, kh, kw, dtype=torch.float32, device=x.device)
+    db = torch.empty(cout, dtype=torch.float32, device=x.device) if bias else None
+    check(lib().rpe_conv_bwd_weight(xp, xbs, dp, dbs, b, cin, cout, hh, ww, kh, kw, float(scale), ptr(dw), ptr(db), ptr(ws), stream_ptr()),
+          'rpe_conv_bwd_weight')
+    return dw, db
+
+
+def conv3x3_to2_bwd_data(dy, weight, act=None, out=None):
+    """rpe_conv3x3_to2_bwd_data: the data gradient of ``conv3x3_to2`` (weight (2,c,3,3)) from dy (b,2,h,w), times [act > 0] when ``act``
+    (b,c,h,w) -- the ReLU output that was the layer's input -- is given; ``out`` may be a channel slice."""
+    dp, dbs = _chan_slice(dy, 'conv3x3_to2_bwd_data: dy')
+    b, two, hh, ww = dy.shape
+    w = _nchw(weight.detach() if weight.requires_grad else weight, 'conv3x3_to2_bwd_data: weight')
+    c = w.shape[1]
+    if two != 2 or tuple(w.shape) != (2, c, 3, 3):
+        raise _lib.RpeError('conv3x3_to2_bwd_data: dy must be (b,2,h,w) and weight (2,c,3,3)')
+    if out is None:
+        out = torch.empty(b, c, hh, ww, dtype=torch.float32, device=dy.device)
+    ap, abs_ = (None, 0) if act is None else _chan_slice(act, 'conv3x3_to2_bwd_data: act')
+    for name, t in (('act', act), ('out', out)):
+        if t is not None and tuple(t.shape) != (b, c, hh, ww):
+            raise _lib.RpeError(f'conv3x3_to2_bwd_data: {name} must be ({b},{c},{hh},{ww})')
+    op, obs = _chan_slice(out, 'conv3x3_to2_bwd_data: out')
+    check(lib().rpe_conv3x3_to2_bwd_data(dp, dbs, ptr(w), ap, abs_, b, c, hh, ww, op, obs, stream_ptr()), 'rpe_conv3x3_to2_bwd_data')
+    return out
+
+
+def relu_backward(grad, act, out=None):
+    """rpe_relu_backward: out = act > 0 ? grad : 0 on channel slices (default: in place on ``grad``)."""
+    out = grad if out is None else out
+    gp, gbs = _chan_slice(grad, 'relu_backward: grad')
+    ap, abs_ = _chan_slice(act, 'relu_backward: act')
+    op, obs = _chan_slice(out, 'relu_backward: out')
+    b, c, hh, ww = grad.shape
+    if tuple(act.shape) != (b, c, hh, ww) or tuple(out.shape) != (b, c, hh, ww):
+        raise _lib.RpeError('relu_backward: grad, act and out must have one shape')
+    check(lib().rpe_relu_backward(gp, gbs, ap, abs_, b, c, hh * ww, op, obs, stream_ptr()), 'rpe_relu_backward')
+    return out
+
+
+def _wkey(*tensors):
+    """Cache key of what is packed from ``tensors``: an in-place update bumps the version, a move or a replaced Parameter changes the pointer."""
+    return tuple((t._version, t.data_ptr()) for t in tensors)
+
+
+_TAIL_PACKED = {}          # _wkey of the eight head parameters -> the packings raft_tail_backward made from them (the two newest weight sets)
+
+
+def sum_groups(parts, bias=None, relu=False, out=None):
+    """rpe_sum_groups: act(sum_g parts[g] + bias[c]) for parts (groups,b,c,h,w), added in group order in f64 -> (b,c,h,w) (``out`` may be a
+    channel slice)."""
+    if not (_is_f32(parts) and parts.dim() == 5):
+        raise _lib.RpeError('sum_groups: parts must be a contiguous float32 (groups,b,c,h,w) GPU tensor')
+    _on_current_device(parts, 'sum_groups: parts')
+    groups, b, c, hh, ww = parts.shape
+    if bias is not None:
+        _f32(bias, 'sum_groups: bias', numel=c)
+    if out is None:
+        out = torch.empty(b, c, hh, ww, dtype=torch.float32, device=parts.device)
+    elif tuple(out.shape) != (b, c, hh, ww):
+        raise _lib.RpeError(f'sum_groups: out must be ({b},{c},{hh},{ww})')
+    op, obs = _chan_slice(out, 'sum_groups: out')
+    check(lib().rpe_sum_groups(ptr(parts), groups, b, c, hh * ww, ptr(bias), int(bool(relu)), op, obs, stream_ptr()), 'rpe_sum_groups')
+    return out
+
+
+TAIL_GROUP_3X3_FWD, TAIL_GROUP_3X3_BWD, TAIL_GROUP_1X1 = 16, 32, 64      # input channels per launch of the tail's forward-kernel convolutions
+
+
+class _TailPacked:
+    """What raft_tail_backward packs from the eight head parameters, each made on first use.  Forward: the two 3x3 layers that read ``net``
+    stacked along their OUTPUT channels (one launch computes t_f and t_m) and the mask head's 1x1 (x 0.25, as RAFT's forward folds it).  Data
+    gradients: the TRANSPOSED, FLIPPED weights -- dX = conv(dY; W^T flipped) is a forward convolution --, the two 256 -> 128 3x3 layers
+    stacked along their INPUT channels (the launches compute the sum of both data gradients) and the 576 -> 256 1x1 layer (x 0.25).
+    Every one of them runs through conv_split: the forward kernels on groups of input channels, the groups added in f64."""
+
+    def __init__(self, fh, mk):
+        self.fh, self.mk, self._made = [t.detach() for t in fh], [t.detach() for t in mk], {}
+        self.w3, self.b3 = torch.cat((self.fh[0], self.mk[0]), dim=0).contiguous(), torch.cat((self.fh[1], self.mk[1]), dim=0).contiguous()
+        self.w3t = torch.cat((self.fh[0].transpose(0, 1).flip(2, 3), self.mk[0].transpose(0, 1).flip(2, 3)), dim=1).contiguous()
+        self.w1, self.b1 = (0.25 * self.mk[2]).contiguous(), (0.25 * self.mk[3]).contiguous()
+        self.w1t = (0.25 * self.mk[2]).transpose(0, 1).contiguous()
+
+    def get(self, name, make):
+        if name not in self._made:
+            self._made[name] = make()
+        return self._made[name]
+
+    def conv_split(self, name, x, weight, bias, relu, group, out=None):
+        """act(conv(x; weight) + bias), stride 1, 'same', 3x3 or 1x1, on the forward's kernels -- rpe_conv_fused where the map is one it takes
+        (rows of whole 16-byte quads), ops.conv_direct at every other size -- run on ``group`` input channels at a time and the groups' results
+        added in f64 (sum_groups).  Those kernels add their products in one k-ordered f32 chain: over all 1152 / 4608 terms of the tail's
+        layers its error is 3-5 times that of a blocked float32 sum, over a group's 144-288 terms it is not."""
+        b, cin, hh, ww = x.shape
+        cout, k = weight.shape[0], weight.shape[2]
+        bounds = [(lo, min(cin, lo + group)) for lo in range(0, cin, group)]
+        parts = torch.empty(len(bounds), b, cout, hh, ww, dtype=torch.float32, device=x.device)
+        fused = ww % 4 == 0 and x.data_ptr() % 16 == 0 and x.stride(0) % 4 == 0
+        for gi, (lo, hi) in enumerate(bounds):
+            wg = self.get((name, gi, 'w'), lambda: weight[:, lo:hi].contiguous())
+            if fused:
+                conv_fused(x[:, lo:hi], self.get((name, gi, 'packed'), lambda: PackedConv(wg, None)), CONV_LINEAR, parts[gi])
+            else:
+                conv_direct(x[:, lo:hi], wg, None, 1, k // 2, out=parts[gi])
+        return sum_groups(parts, bias, relu, out)
+
+
+def _tail_packed(fh_params, mask_params):
+    key = _wkey(*fh_params, *mask_params)
+    if key not in _TAIL_PACKED:
+        while len(_TAIL_PACKED) >= 2:
+            _TAIL_PACKED.pop(next(iter(_TAIL_PACKED)))
+        _TAIL_PACKED[key] = _TailPacked(fh_params, mask_params)
+    return _TAIL_PACKED[key]
+
+
+def raft_tail_backward(net, flow_low, grad_up, fh_params, mask_params):
+    """Backward of the tail of RAFT's last update iteration (csrc/raft_backward.hip):
+        t_f = relu(conv3x3(net; fh.conv1)); delta = conv3x3(t_f; fh.conv2); t_m = relu(conv3x3(net; mask.0)); m = .25 conv1x1(t_m; mask.2)
+        flow_up = upsample_convex(flow_prev + delta, m)
+    net (b,128,h8,w8): the returned hidden state; flow_low (b,2,h8,w8) = flow_prev + delta, the pass's last 1/8 flow (``ret_lowres``; d / d delta
+    = d / d flow_low, so flow_prev is not needed); grad_up (b,2,8 h8,8 w8); fh_params = (conv1.weight, conv1.bias, conv2.weight, conv2.bias)
+    of the flow head, mask_params = (mask.0.weight, mask.0.bias, mask.2.weight, mask.2.bias).
+    -> (d_net, (the eight parameter gradients in that order)).  t_f, t_m and m are recomputed from ``net`` with the forward's kernels
+    (nothing is kept by the forward pass), which also compute the data gradients; each runs on groups of input channels whose results
+    are added in f64 (_TailPacked.conv_split).  f32 throughout, bit-identical from run to run."""
+    net, fl, gu = _nchw(net, 'raft_tail_backward: net'), _nchw(flow_low, 'raft_tail_backward: flow_low'), _nchw(grad_up, 'raft_tail_backward: grad_up')
+    fh, mk = tuple(fh_params), tuple(mask_params)
+    b, c, hh, ww = net.shape
+    for t in fh + mk:
+        _nchw(t.detach(), 'raft_tail_backward: a head parameter')
+    hid = fh[0].shape[0]
+    if len(fh) != 4 or len(mk) != 4 or tuple(fh[0].shape) != (hid, c, 3, 3) or tuple(fh[2].shape) != (2, hid, 3, 3) \
+            or tuple(mk[0].shape) != (hid, c, 3, 3) or tuple(mk[2].shape) != (576, hid, 1, 1):
+        raise _lib.RpeError('raft_tail_backward: expected the flow head\'s (h,c,3,3), (2,h,3,3) and the mask head\'s (h,c,3,3), (576,h,1,1) weights')
+    if tuple(fl.shape) != (b, 2, hh, ww) or tuple(gu.shape) != (b, 2, 8 * hh, 8 * ww):
+        raise _lib.RpeError('raft_tail_backward: flow_low must be (b,2,h8,w8) and grad_up (b,2,8 h8,8 w8) for net (b,c,h8,w8)')
+    P = _tail_packed(fh, mk)
+    with torch.no_grad():
+        # the forward, again
+        t = P.conv_split('w3', net, P.w3, P.b3, True, TAIL_GROUP_3X3_FWD)              # (t_f | t_m): both layers read net
+        t_f, t_m = t[:, :hid], t[:, hid:]
+        m = P.conv_split('w1', t_m, P.w1, P.b1, False, TAIL_GROUP_1X1)
+        # the adjoints, last layer first
+        d_flow, d_m = upsample_convex_backward(gu, fl, m)
+        g = torch.empty(b, 2 * hid, hh, ww, dtype=torch.float32, device=net.device)       # (d t_f | d t_m) in front of their ReLUs
+        dw_fh2, db_fh2 = conv_bwd_weight(t_f, d_flow, (3, 3))
+        conv3x3_to2_bwd_data(d_flow, P.fh[2], act=t_f, out=g[:, :hid])
+        dw_m2, db_m2 = conv_bwd_weight(t_m, d_m, (1, 1), scale=0.25)
+        P.conv_split('w1t', d_m, P.w1t, None, False, TAIL_GROUP_1X1, out=g[:, hid:])
+        relu_backward(g[:, hid:], t_m)
+        dw1, db1 = conv_bwd_weight(net, g, (3, 3))                      # both 3x3 layers read net: one GEMM of 2 * hid output channels
+        d_net = P.conv_split('w3t', g, P.w3t, None, False, TAIL_GROUP_3X3_BWD)
+    return d_net, (dw1[:hid], db1[:hid], dw_fh2, db_fh2, dw1[hid:], db1[hid:], dw_m2, db_m2)
+
+
+class _RaftTailFn(torch.autograd.Function):
+    """The tails of k gradient-free RAFT passes as ONE autograd node: inputs k x (flow_up, hidden, flow_low) and the eight head parameters,
+    outputs the k up-sampled flows unchanged.  Backward = raft_tail_backward per pass, in the order the passes were given; the parameter
+    gradients are summed in that order (a pass whose flow nothing differentiates is skipped), so the sum's bits do not depend on the
+    autograd engine's scheduling."""
+
+    @staticmethod
+    def forward(ctx, k, *tensors):
+        ctx.k = k
+        ctx.save_for_backward(*tensors)
+        ctx.set_materialize_grads(False)
+        outs = tuple(tensors[3 * i].view_as(tensors[3 * i]) for i in range(k))
+        return outs[0] if k == 1 else outs
+
+    @staticmethod
+    def backward(ctx, *grads):
+        t, k = ctx.saved_tensors, ctx.k
+        params = t[3 * k:]
+        total, d_nets = None, [None] * k
+        for i, g in enumerate(grads):
+            if g is None:
+                continue
+            d_nets[i], pg = raft_tail_backward(t[3 * i + 1].detach(), t[3 * i + 2], g.contiguous(), params[:4], params[4:])
+            total = list(pg) if total is None else [a + b for a, b in zip(total, pg)]
+        per_pass = [x for i in range(k) for x in (None, d_nets[i], None)]
+        return (None, *per_pass, *(total if total is not None else [None] * 8))
+
+
+def raft_tail_attach(passes, fh_params, mask_params):
+    """Attach the tail's backward to the results of gradient-free RAFT passes: ``passes`` = [(flow_up, hidden, flow_low), ...] with hidden a
+    leaf that requires grad -> the list of up-sampled flows (the same values), outputs of one autograd node whose backward is
+    ``raft_tail_backward`` per pass and whose inputs are the hidden states and the eight parameters."""
+    flat = [x for p in passes for x in p]
+    with torch.enable_grad():
+        out = _RaftTailFn.apply(len(passes), *flat, *fh_params, *mask_params)
+    return [out] if len(passes) == 1 else list(out)

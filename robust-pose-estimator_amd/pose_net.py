@@ -55,15 +55,19 @@ class PoseNet(nn.Module):
         return dict(f=f, c=c)
 
     @torch.no_grad()
-    def flow2depth(self, imagel, imager, baseline, upsample=True, ret_cache=False, enc=None):
+    def flow2depth(self, imagel, imager, baseline, upsample=True, ret_cache=False, enc=None, ret_tail=False):
         """pose_net.py:127-135 -> (depth (n,1,h,w), stereo flow (n,2,h,w), valid (n,1,h,w) bool).
         ``upsample=False``: everything at 1/8 resolution, the flow in 1/8-pixel units and the depth divided by 8 (:131-132;
         a division by a power of two commutes with the rounding of b / -flow.x, so the kernel is handed b / 8).
-        ``ret_cache`` additionally returns the encoder outputs of ``imagel`` for reuse by the next ``infer``."""
+        ``ret_cache`` additionally returns the encoder outputs of ``imagel`` for reuse by the next ``infer``.
+        ``ret_tail`` additionally returns (hidden state, last 1/8 flow) of the pass: what the backward of RAFT's output heads reads."""
         n = imagel.shape[0]
         f, cn = (enc['f'], enc['c']) if enc is not None else self._encode_both((imagel, imager), imagel)
-        flow = self.flow(None, None, upsample=upsample, fmaps=(f[:n], f[n:]), cnet=cn)[0][-1]
+        r = self.flow(None, None, upsample=upsample, fmaps=(f[:n], f[n:]), cnet=cn, **(dict(ret_lowres=True) if ret_tail else {}))
+        flow = r[0][-1]
         depth, valid = ops.flow2depth(flow, baseline if upsample else baseline / 8.0)
+        if ret_tail:
+            return depth, flow, valid, (r[1], r[3])
         if ret_cache:
             return depth, flow, valid, dict(fmap=f[:n], cnet=cn)
         return depth, flow, valid
@@ -79,16 +83,29 @@ class PoseNet(nn.Module):
         (csrc/geometry_backward.hip), so the heads' inputs and the pose layer's time_flow / pcl1 / pcl2w carry gradients.  The result gains
         a last element {'time_flow', 'stereo_flow1', 'stereo_flow2'}: after ``loss.backward()`` each tensor's ``.grad`` is d loss / d that
         flow -- what a differentiable flow model has to be handed.  Values, and the gradients of the heads and ``loss_weight``, are those
-        of the default call; without the flag nothing here changes, launches included."""
+        of the default call; without the flag nothing here changes, launches included.
+        With RAFT's output heads trainable (``freeze_flow(False, parts='heads')``) the call takes the ``ret_flows`` route whether asked or
+        not, and the three flows are the outputs of ONE autograd node (ops.raft_tail_attach; passes in the order time, stereo1, stereo2)
+        over the three RAFT results -- the ``flow2depth`` pass of frame 1 and both halves of the batched pass --, whose backward
+        (ops.raft_tail_backward) hands the pose loss's gradient to the flow head's and the mask head's eight parameters, summed over the
+        three.  The flows keep their ``.grad`` (retain_grad), and with ``ret_flows`` the returned dict gains 'hidden': {'time', 'stereo1',
+        'stereo2'}, leaves whose ``.grad`` is the tail's d loss / d net_N, plus the weight heads' input gradient for 'time'."""
         n = image1l.shape[0]
         intrinsics = intrinsics.expand(n, 3, 3).contiguous()
         baseline = baseline.expand(n).contiguous()
+        grad_heads = self.flow_heads_trainable()
+        if grad_heads:
+            self.flow.check_grad_heads()                       # (before anything is launched)
         with torch.no_grad():
-            depth1, stereo_flow1, valid1 = self.flow2depth(image1l, image1r, baseline)
+            tail1 = None
+            if grad_heads:
+                depth1, stereo_flow1, valid1, tail1 = self.flow2depth(image1l, image1r, baseline, ret_tail=True)
+            else:
+                depth1, stereo_flow1, valid1 = self.flow2depth(image1l, image1r, baseline)
             mask1 = (mask1.bool() & valid1) if mask1 is not None else valid1
             mask2 = mask2.bool().clone() if mask2 is not None else torch.ones_like(valid1)
             s = self.stages(image1l, image2l, intrinsics, baseline, depth1, image2r, mask1, mask2, stereo_flow1, heads=False,
-                            grad_flows=ret_flows)
+                            grad_flows=ret_flows or grad_heads, tail1=tail1)
         if self.use_weights and self.train_heads_hip:
             # the heads' training route on hand-written kernels (csrc/unet_train.hip): the parts are read where they are (no torch.cat),
             # the Sigmoid modules' work is fused into the resize
@@ -104,13 +121,32 @@ class PoseNet(nn.Module):
         pose_tan = log6.squeeze(1)
         out = (pose_tan, depth1, s['depth2'], (w2d, w3d)) if ret_confmap else (pose_tan, depth1, s['depth2'])
         if ret_flows:
-            out = (*out, {k: s[k] for k in ('time_flow', 'stereo_flow1', 'stereo_flow2')})
+            flows = {k: s[k] for k in ('time_flow', 'stereo_flow1', 'stereo_flow2')}
+            if grad_heads:
+                flows['hidden'] = s['hidden_leaves']
+            out = (*out, flows)
         return out
 
-    def freeze_flow(self, freeze=True):
-        """pose_net.py:148-153.  Un-freezing the flow network needs its backward, which is not built: the gradients of the pose loss now
-        reach the three flows (``forward(..., ret_flows=True)``: the pose layer's and the geometry stage's backward) and stop there.
-        Refuse instead of training the heads against silently missing flow-network gradients."""
+    def flow_head_params(self):
+        """RAFT's flow-head and mask-head parameters (ops.raft_tail_backward's order): what ``freeze_flow(False, parts='heads')`` trains."""
+        fh, mk = self.flow.head_params()
+        return fh + mk
+
+    def flow_heads_trainable(self):
+        return any(p.requires_grad for p in self.flow_head_params())
+
+    def freeze_flow(self, freeze=True, parts=None):
+        """pose_net.py:148-153.  Un-freezing the whole flow network needs its backward, which is not built: the gradients of the pose loss
+        reach the three flows (``forward(..., ret_flows=True)``: the pose layer's and the geometry stage's backward) and, through the backward
+        of RAFT's last flow-head / mask-head application (csrc/raft_backward.hip), those heads' parameters -- ``freeze_flow(False,
+        parts='heads')`` sets requires_grad on ``flow.update_block.flow_head`` and ``flow.update_block.mask`` only.  Everything else of RAFT has no
+        backward here: ``freeze_flow(False)`` without ``parts`` is refused instead of training against silently missing gradients."""
+        if parts not in (None, 'heads'):
+            raise ValueError(f"freeze_flow: parts must be None or 'heads', got {parts!r}")
+        if not freeze and parts == 'heads':
+            for p in self.flow_head_params():
+                p.requires_grad = True
+            return self
         if not freeze:
             raise NotImplementedError('training the flow network (freeze_flow(False)) is out of scope: the gradients stop at the flows '
                                       '(forward(..., ret_flows=True) returns them); RAFT has no backward here')
@@ -154,7 +190,7 @@ class PoseNet(nn.Module):
 
     @torch.no_grad()
     def stages(self, image1l, image2l, intrinsics, baseline, depth1, image2r, mask1, mask2, stereo_flow1, cache1=None, heads=True, enc2=None,
-               flow_init=None, ret_lowres=False, grad_flows=False):
+               flow_init=None, ret_lowres=False, grad_flows=False, tail1=None):
         """Every stage of infer() before the solve.  ``cache1`` = {'fmap','cnet'} of image1l from the previous call
         (streaming: frame t's image2l is frame t+1's image1l), so only the two new images are encoded -- or not even those when
         ``enc2`` = encode_frame(image2l, image2r) was computed ahead of the call (needs cache1).
@@ -163,7 +199,10 @@ class PoseNet(nn.Module):
         (n,2,h/8,w/8) is added as 'time_flow_low' to the result and to its 'cache2'.
         ``grad_flows`` (the training forward's ``ret_flows``): time_flow, stereo_flow2 and stereo_flow1 become leaves that require grad
         ('stereo_flow1' is added to the result) and the geometry stage runs, with gradients enabled, through ``ops.flow2depth_grad`` and
-        ``ops.geometry_stage``: the same values, now differentiable with respect to the three flows."""
+        ``ops.geometry_stage``: the same values, now differentiable with respect to the three flows.
+        ``tail1`` = (hidden, 1/8 flow) of the pass that made stereo_flow1 (flow2depth's ``ret_tail``; needs grad_flows): RAFT's output heads
+        train -- the three flows leave one ops.raft_tail_attach node (time, stereo1, stereo2), 'hidden' is the temporal pairs' hidden state as a
+        leaf that requires grad, and 'hidden_leaves' = {'time', 'stereo1', 'stereo2'}."""
         n = image1l.shape[0]
         intrinsics = intrinsics.expand(n, 3, 3).contiguous()
         baseline = baseline.expand(n).contiguous()
@@ -183,16 +222,29 @@ class PoseNet(nn.Module):
         kw = {}
         if flow_init is not None:
             kw['flow_init'] = torch.cat((flow_init, torch.zeros_like(flow_init)), dim=0)      # (temporal | stereo) rows of the RAFT batch
-        if ret_lowres:
+        if ret_lowres or tail1 is not None:
             kw['ret_lowres'] = True
         r = self.flow(None, None, upsample=True, fmaps=fmaps, cnet=cn, **kw)
         flow_predictions, hidden, context = r[:3]
         time_flow = flow_predictions[-1][:n].contiguous()
         stereo_flow2 = flow_predictions[-1][n:].contiguous()
         hidden, context = hidden[:n], context[:n]
+        leaves = None
         if grad_flows:
             with torch.enable_grad():
-                time_flow, stereo_flow2, stereo_flow1 = (t.detach().requires_grad_(True) for t in (time_flow, stereo_flow2, stereo_flow1))
+                if tail1 is not None:
+                    low = r[3]
+                    leaves = dict(time=hidden, stereo1=tail1[0], stereo2=r[1][n:])
+                    leaves = {k: t.detach().requires_grad_(True) for k, t in leaves.items()}
+                    hidden = leaves['time']                    # (the weight heads read it: their input gradient lands in its .grad)
+                    fh, mk = self.flow.head_params()
+                    time_flow, stereo_flow1, stereo_flow2 = ops.raft_tail_attach(
+                        [(time_flow, leaves['time'], low[:n]), (stereo_flow1.contiguous(), leaves['stereo1'], tail1[1]),
+                         (stereo_flow2, leaves['stereo2'], low[n:])], fh, mk)
+                    for t in (time_flow, stereo_flow1, stereo_flow2):
+                        t.retain_grad()
+                else:
+                    time_flow, stereo_flow2, stereo_flow1 = (t.detach().requires_grad_(True) for t in (time_flow, stereo_flow2, stereo_flow1))
                 g = ops.geometry_stage(stereo_flow2, time_flow, baseline, intrinsics, ops.flow2depth_grad(stereo_flow1, baseline)[0],
                                        image1l, image2l, stereo_flow1, mask2)
             g['stereo_flow1'] = stereo_flow1
@@ -202,6 +254,8 @@ class PoseNet(nn.Module):
         w2d, w3d = self._heads(g, hidden, context) if heads else (None, None)
         g.update(time_flow=time_flow, stereo_flow2=stereo_flow2, hidden=hidden, context=context, w2d=w2d, w3d=w3d,
                  intrinsics=intrinsics, cache2=dict(fmap=f2l, cnet=c2l))
+        if leaves is not None:
+            g['hidden_leaves'] = leaves
         if ret_lowres:
             g['time_flow_low'] = g['cache2']['time_flow_low'] = r[3][:n]
         return g

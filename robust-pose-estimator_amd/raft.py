@@ -1165,15 +1165,46 @@ class RAFT(nn.Module):
         recorded.put(key, post)
         return pred, h_buf, low
 
+    def head_params(self):
+        """The eight parameters of the output heads in ops.raft_tail_backward's order: (flow head, mask head)."""
+        fh, mk = self.update_block.flow_head, self.update_block.mask
+        return (fh.conv1.weight, fh.conv1.bias, fh.conv2.weight, fh.conv2.bias), (mk[0].weight, mk[0].bias, mk[2].weight, mk[2].bias)
+
+    def check_grad_heads(self, upsample=True):
+        """The refusals of ``grad_heads`` (raised before anything is launched): the tail's backward differentiates the f32 layers; a route
+        that rounds their operands has no honest gradient here."""
+        route = self._route()
+        if route.update_fp16:
+            raise RpeError('RAFT: grad_heads differentiates the f32 output heads -- not with update_fp16 (fp16 operands in the flow and mask heads)')
+        if CONV_BF16X3:
+            raise RpeError('RAFT: grad_heads differentiates the f32 output heads -- not with CONV_BF16X3 (bf16x3 products in the flow and mask heads)')
+        if route.mixed_precision:
+            raise RpeError('RAFT: grad_heads is f32 only -- not with mixed_precision')
+        if not upsample:
+            raise RpeError('RAFT: grad_heads attaches to the up-sampled prediction: it needs upsample=True')
+
     @torch.no_grad()
-    def forward(self, image1, image2, upsample=True, iters=None, all_flows=False, fmaps=None, cnet=None, flow_init=None, ret_lowres=False):
+    def forward(self, image1, image2, upsample=True, iters=None, all_flows=False, fmaps=None, cnet=None, flow_init=None, ret_lowres=False,
+                grad_heads=False):
         """image1, image2: (N,3,H,W) in 0..255.  Inference only (the reference freezes RAFT, train.yaml:51).
         ``fmaps`` / ``cnet`` accept encoder outputs computed elsewhere (both encoders normalise per sample -- instance
         norm / frozen batch norm -- so a caller may encode every distinct image once and reuse it); with both given the
         images may be None.  ``cnet`` is encode_context's output: (tanh(net) | relu(inp)).
         ``flow_init`` (N,2,H/8,W/8) f32: warm start as upstream RAFT's (coords1 = coords0 + flow_init; the first iteration's motion encoder
         sees flow = flow_init), e.g. ops.forward_interpolate of the previous frame's 1/8 flow; all zeros gives the cold pass bit for bit.
-        ``ret_lowres``: a 4th return element, the last iteration's 1/8 flow as a fresh tensor."""
+        ``ret_lowres``: a 4th return element, the last iteration's 1/8 flow as a fresh tensor.
+        ``grad_heads``: the pass runs as ever (gradient-free, the launches of a ``ret_lowres`` pass, the same bits); the returned LAST
+        prediction is then the output of one autograd node (ops.raft_tail_attach) whose inputs are the flow head's and the mask head's
+        eight parameters and the returned hidden state, which comes back as a leaf that requires grad.  Upstream detaches coords1 at the
+        top of every iteration, so that prediction depends on those parameters through their last application only: the node's backward
+        (ops.raft_tail_backward, csrc/raft_backward.hip) is their exact gradient, and hidden.grad is d loss / d net_N.  Refused with
+        update_fp16, CONV_BF16X3 and mixed_precision (check_grad_heads)."""
+        if grad_heads:
+            self.check_grad_heads(upsample)
+            flows, hidden, context, low = self.forward(image1, image2, upsample, iters, all_flows, fmaps, cnet, flow_init, ret_lowres=True)
+            hidden.requires_grad_(True)
+            flows[-1] = ops.raft_tail_attach([(flows[-1], hidden, low)], *self.head_params())[0]
+            return (flows, hidden, context) + ((low,) if ret_lowres else ())
         iters = self.iters if iters is None else iters
         if image1 is None:                                    # encoder outputs given: the images are not needed again
             (N, _, h8, w8), dev = fmaps[0].shape, fmaps[0].device
