@@ -91,24 +91,28 @@ def objective_derivatives(P, T):
     return fY, fYY, g2u, g3u, t, g
 
 
-def layer_backward(flow, pcl1, pcl2, w1, w2, mask1, mask2, K, loss_weight, vec7, v, eps=1e-3):
+def layer_backward(flow, pcl1, pcl2, w1, w2, mask1, mask2, K, loss_weight, vec7, v, eps=1e-3, u=None):
     """Gradients the layer's backward returns for (flow, pcl1, pcl2, w1, w2, loss_weight), float64, given the layer's
     float32 output pose ``vec7`` (n,[1,]7) and the incoming tangent gradient ``v`` (n,[1,]6)
-    (DeclarativeFunctionLie.backward :249-267 -> gradient :13-82).  All zeros when the optimality check fails."""
+    (DeclarativeFunctionLie.backward :249-267 -> gradient :13-82).  All zeros when the optimality check fails.
+    With ``u`` (n,6) given, ``v``, the optimality check and the 6x6 solve are skipped: the closed forms of fXY^T u alone, at any pose."""
     P = _prep(flow, pcl1, pcl2, w1, w2, mask1, mask2, K, loss_weight)
     n, h, w = P['n'], P['h'], P['w']
     T = vec7.reshape(n, 7).to(F64)
     fY, fYY, g2u, g3u, t, g = objective_derivatives(P, T)
     shapes = dict(flow=(n, 2, h, w), pcl1=(n, 3, h, w), pcl2=(n, 3, h, w), w1=(n, 1, h, w), w2=(n, 1, h, w), loss_weight=(n, 2))
-    if not torch.allclose(fY, torch.zeros_like(fY), rtol=0.0, atol=eps):            # :43-47
+    if u is not None:
+        u = torch.as_tensor(u).to(F64).reshape(n, 6)
+    elif not torch.allclose(fY, torch.zeros_like(fY), rtol=0.0, atol=eps):          # :43-47
         warnings.warn('Non-zero objective function gradient at y')
         return {k: torch.zeros(s, dtype=F64) for k, s in shapes.items()}, fY, fYY
-    H = 0.5 * (fYY + fYY.transpose(1, 2))                                           # :51
-    try:
-        u = torch.cholesky_solve(-v.reshape(n, 6, 1).to(F64), torch.linalg.cholesky(H))[..., 0]
-    except Exception:
-        warnings.warn('linear system is not positive definite')
-        return {k: torch.zeros(s, dtype=F64) for k, s in shapes.items()}, fY, fYY
+    else:
+        H = 0.5 * (fYY + fYY.transpose(1, 2))                                       # :51
+        try:
+            u = torch.cholesky_solve(-v.reshape(n, 6, 1).to(F64), torch.linalg.cholesky(H))[..., 0]
+        except Exception:
+            warnings.warn('linear system is not positive definite')
+            return {k: torch.zeros(s, dtype=F64) for k, s in shapes.items()}, fY, fYY
     u = torch.nan_to_num(u, nan=0.0, posinf=float('inf'), neginf=float('-inf'))     # u[isnan] = 0
     X = t['X']
     Ju = u[:, None, :3] + _cross(u[:, None, 3:].expand_as(X), X)                    # J u = u_tau + u_phi x X
