@@ -70,6 +70,9 @@ const char *rpe_version(void);
  *   rpe_flow2depth_backward;
  *   and the backward of RAFT's output heads: rpe_upsample_convex_backward, rpe_conv_bwd_weight, rpe_conv_bwd_weight_workspace_bytes,
  *   rpe_conv3x3_to2_bwd_data, rpe_relu_backward, rpe_sum_groups;
+ *   and the backward of one update-block application: rpe_gru_gates_zr_recompute, rpe_gru_gates_h_recompute,
+ *   rpe_gru_gates_zq_backward, rpe_gru_gates_r_backward (rpe_conv_bwd_weight also takes
+ *   (1,5), (5,1) and (7,7) since then: rpe_conv_bwd_weight_workspace_bytes returns 0 for them in a library that does not);
  *   the next RPE_ABI_MINOR bump counts them and rpe_conv_wino24*. */
 #define RPE_ABI_VERSION 5
 #define RPE_ABI_MINOR 4
@@ -304,9 +307,9 @@ int rpe_flow2depth_backward(const float *stereo_flow, const float *baseline, con
  *   collects from the nine cells whose 3x3 window (zero padded, as the forward's unfold) holds it; d_mask_k = p_k (g_k - sum_k' p_k' g_k') per
  *   sub-pixel with the forward's softmax code (double).  Dense tensors; any h8, w8; b == 0 is RPE_OK, b > 65535 RPE_E_BADARG.
  * rpe_conv_bwd_weight: d_weight (cout,cin,kh,kw) and d_bias (cout) (either may be NULL) of y = conv(x; W) + bias, stride 1, 'same' zero
- *   padding, (kh,kw) = (3,3) or (1,1), from x (b,cin,h,w) and dy (b,cout,h,w) at ANY h, w; x and dy may be channel slices (batch strides in
+ *   padding, (kh,kw) = (3,3), (1,1), (1,5), (5,1) or (7,7), from x (b,cin,h,w) and dy (b,cout,h,w) at ANY h, w; x and dy may be channel slices (batch strides in
  *   floats, at least the slice).  A GEMM on the f32 matrix cores (v_mfma_f32_32x32x2_f32) with M = cout, N = cin kh kw, K = b h w; layers of one
- *   or two output channels run a plain kernel.  K is split into chunks of c(K) = max(1024, round_up(ceil(K / 64), 32)) pixels -- at most 64, a
+ *   or two output channels run a plain kernel (3x3 and 1x1; the other sizes run the GEMM at any cout).  K is split into chunks of c(K) = max(1024, round_up(ceil(K / 64), 32)) pixels -- at most 64, a
  *   function of b h w alone --, each chunk writes a partial and the partials are added in index order in f64; d_bias is dy's channel sum under
  *   the same rule; both leave multiplied by ``scale`` (the mask head's 0.25; 1 otherwise), applied to the f64 sum.  workspace: rpe_conv_bwd_weight_workspace_bytes(...) bytes (0 for a shape it refuses), 16-byte aligned.  Non-positive
  *   sizes, other kernels, NULL x / dy / workspace: RPE_E_BADARG; b h w, cin h w, cout h w or the weight's size >= 2^31: RPE_E_UNSUPPORTED.
@@ -328,6 +331,33 @@ int rpe_relu_backward(const float *grad, long long grad_batch_stride, const floa
                       float *out, long long out_batch_stride, void *stream);
 int rpe_sum_groups(const float *parts, int groups, int b, int c, int hw, const float *bias, int relu, float *out, long long out_batch_stride,
                    void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Backward of one update-block application (csrc/update_backward.hip; core/RAFT/core/update.py SepConvGRU): the adjoints of the gate
+ * epilogues rpe_gru_gates_zr / rpe_gru_gates_h for ONE half,  h' = (1 - z) h + z q,  z = s(z_pre), r = s(r_pre), q = tanh(q_pre), rh = r h.
+ * All operands are (b,c,hw) f32 channel slices (batch strides in floats, at least c hw); z, r, q are the POST-activation values.
+ * rpe_gru_gates_zq_backward: from d_h_new = d loss / d h':  d_z_pre = d (q - h) z (1 - z),  d_q_pre = d z (1 - q^2),  d_h = d (1 - z).
+ * rpe_gru_gates_r_backward: from d_rh = d loss / d (r h) (convq's data gradient):  d_r_pre = d_rh h r (1 - r),  d_h_out = d_h_in + d_rh r;
+ *   d_h_out may be d_h_in or d_rh (in place).  Products in double, one rounding per result; a saturated gate gives exact zeros.
+ * rpe_gru_gates_zr_recompute / _h_recompute: the gates again with everything the adjoints read kept (the forward's epilogues keep z and r h
+ *   only): from zr_pre (b,2c,hw: z | r, bias added) and h:  z, r, rh = r h;  from q_pre, z and h:  q = tanh(q_pre), h_new = (1 - z) h + z q.
+ *   Activations in double, rounded once.
+ * The weight and data gradients of the step's convolutions are rpe_conv_bwd_weight and forward convolutions on transposed weights.
+ * b == 0 is RPE_OK; NULL, b > 65535, c or hw <= 0, a batch stride shorter than the slice: RPE_E_BADARG.
+ * --------------------------------------------------------------------------------------------------------- */
+int rpe_gru_gates_zr_recompute(const float *zr_pre, long long zr_batch_stride, const float *h, long long h_batch_stride, int b, int c, int hw,
+                               float *z, long long z_batch_stride, float *r, long long r_batch_stride, float *rh, long long rh_batch_stride,
+                               void *stream);
+int rpe_gru_gates_h_recompute(const float *q_pre, long long qp_batch_stride, const float *z, long long z_batch_stride, const float *h,
+                              long long h_batch_stride, int b, int c, int hw, float *q, long long q_batch_stride, float *h_new,
+                              long long hn_batch_stride, void *stream);
+int rpe_gru_gates_zq_backward(const float *d_h_new, long long d_batch_stride, const float *h, long long h_batch_stride, const float *z,
+                              long long z_batch_stride, const float *q, long long q_batch_stride, int b, int c, int hw, float *d_z_pre,
+                              long long dz_batch_stride, float *d_q_pre, long long dq_batch_stride, float *d_h, long long dh_batch_stride,
+                              void *stream);
+int rpe_gru_gates_r_backward(const float *d_rh, long long drh_batch_stride, const float *h, long long h_batch_stride, const float *r,
+                             long long r_batch_stride, const float *d_h_in, long long dhi_batch_stride, int b, int c, int hw, float *d_r_pre,
+                             long long dr_batch_stride, float *d_h_out, long long dho_batch_stride, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * RAFT correlation -- replaces CorrBlock (core/RAFT/core/corr.py of the aimi-lab/RAFT submodule: all-pairs

@@ -245,6 +245,10 @@ SIGNATURES = {
     'rpe_conv3x3_to2_bwd_data': (_i, [_vp, _ll, _vp, _vp, _ll, _i, _i, _i, _i, _vp, _ll, _vp]),
     'rpe_relu_backward': (_i, [_vp, _ll, _vp, _ll, _i, _i, _i, _vp, _ll, _vp]),
     'rpe_sum_groups': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _ll, _vp]),
+    'rpe_gru_gates_zr_recompute': (_i, [_vp, _ll] * 2 + [_i, _i, _i] + [_vp, _ll] * 3 + [_vp]),
+    'rpe_gru_gates_h_recompute': (_i, [_vp, _ll] * 3 + [_i, _i, _i] + [_vp, _ll] * 2 + [_vp]),
+    'rpe_gru_gates_zq_backward': (_i, [_vp, _ll] * 4 + [_i, _i, _i] + [_vp, _ll] * 3 + [_vp]),
+    'rpe_gru_gates_r_backward': (_i, [_vp, _ll] * 4 + [_i, _i, _i] + [_vp, _ll] * 2 + [_vp]),
     'rpe_flow_forward_interpolate': (_i, [_vp, _i, _i, _i, _vp, _vp]),
     'rpe_corr_pyramid_bytes': (_sz, [_i, _i, _i, _i]),
     'rpe_corr_pyramid_bytes_ex': (_sz, [_i, _i, _i, _i, _i]),

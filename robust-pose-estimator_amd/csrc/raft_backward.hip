@@ -10,6 +10,7 @@
 // No float atomics anywhere; every sum runs in an order fixed by the shapes, so two runs give the same bits on any device.
 #include "rpe_common.h"
 #include "upsample_device.h"
+#include "bw_gemm.h"
 
 static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
@@ -98,119 +99,13 @@ __global__ __launch_bounds__(UB_T * UB_T) void k_upsample_convex_bwd(const float
 // The split of K: chunks of bw_chunk(K) pixels -- a function of b * h * w alone, never of the device --, chunk c -> partial c, and the
 // partials are added in index order in f64 (k_bw_sum).  Inside a chunk the f32 matrix cores sum in steps of 32 pixels, each step's pixels
 // in the fixed order of the instruction: one bit pattern per shape.
-static inline long long bw_chunk(long long K) {
-    long long c = ((K + 63) / 64 + 31) / 32 * 32;                 // at most 64 chunks, whole 32-pixel steps
-    return c < 1024 ? 1024 : c;                                   // ... of at least 1024 pixels
-}
-static inline int bw_chunks(long long K) { return (int)((K + bw_chunk(K) - 1) / bw_chunk(K)); }
-
-#define BW_BM 128                 // output channels per workgroup
-#define BW_BN 128                 // (input channel, tap) pairs per workgroup
-#define BW_BK 32                  // pixels per step
-#define BW_LD (BW_BK + 4)         // LDS row pitch in floats: 16-byte aligned rows, 4-float reads of a lane's k-run
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// Workgroup = 4 waves, each 2 x 2 tiles of v_mfma_f32_32x32x2_f32 (64 accumulators per lane).  Staging: thread t loads pixel column
-// t & 31 of rows (t >> 5) + 8 r, r = 0..15, of both operand tiles, so the pixel's (batch, y, x) split and its nine border tests are done
-// once per step and a load is coalesced along the pixels; a tap outside the map (or a row / pixel outside the problem) is read from a
-// clamped address and SELECTED to zero.  K is permuted inside a step (lane half h takes pixels 16 h .. 16 h + 15 of the step, for BOTH
-// operands): a sum does not care, and a lane's operands of four consecutive instructions are one 16-byte LDS read.
+// (bw_chunk, the tile constants and the GEMM's body: bw_gemm.h, shared with update_backward.hip)
 template <int TAPS>
 __global__ __launch_bounds__(256) void k_bw_gemm(const float* __restrict__ x, long long xbs, const float* __restrict__ dy, long long dybs,
                                                  int cin, int cout, int h, int w, long long K, long long kc, float* __restrict__ part) {
     __shared__ __attribute__((aligned(16))) float sA[BW_BM * BW_LD];
     __shared__ __attribute__((aligned(16))) float sB[BW_BN * BW_LD];
-    const int N = cin * TAPS, M = cout;
-    const int n0 = blockIdx.x * BW_BN, m0 = blockIdx.y * BW_BM;
-    const long long kbeg = (long long)blockIdx.z * kc, kend = kbeg + kc < K ? kbeg + kc : K;
-    const int hw = h * w;
-    const int tid = threadIdx.x, kl = tid & 31, r0 = tid >> 5;
-    // per staged row: the operand's offset inside a batch item, and (B) the tap whose border test decides it; 31 = a row outside the problem
-    int aoff[16], boff[16], btap[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int m = m0 + r0 + 8 * r, n = n0 + r0 + 8 * r;
-        aoff[r] = m < M ? m * hw : -1;
-        const int ci = n / TAPS, tap = n - ci * TAPS;
-        const int dyo = TAPS == 9 ? tap / 3 - 1 : 0, dxo = TAPS == 9 ? tap % 3 - 1 : 0;
-        boff[r] = ci * hw + dyo * w + dxo;
-        btap[r] = n < N ? tap : 31;
-    }
-    float ra[16], rb[16];
-    auto load = [&](long long kstep) {
-        const long long k = kstep + kl;
-        const bool kv = k < kend;
-        const long long kk = kv ? k : kbeg;                           // (kbeg < K: the grid has no empty chunk)
-        const int bb = (int)(kk / hw), p = (int)(kk - (long long)bb * hw);
-        const int py = p / w, px = p - py * w;
-        unsigned vm = 0;
-        if (TAPS == 9) {
-#pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                const int yy = py + t / 3 - 1, xx = px + t % 3 - 1;
-                vm |= (unsigned)(kv && yy >= 0 && yy < h && xx >= 0 && xx < w) << t;
-            }
-        } else vm = kv ? 1u : 0u;
-        const float* ab = dy + (size_t)bb * dybs + p;
-        const float* xb = x + (size_t)bb * xbs + p;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const bool av = kv && aoff[r] >= 0;
-            const float a = ab[av ? aoff[r] : 0];                     // (offset 0 + p: inside channel 0 of this batch item)
-            ra[r] = av ? a : 0.0f;
-            const bool bv = (vm >> btap[r]) & 1u;
-            const float v = xb[bv ? boff[r] : 0];
-            rb[r] = bv ? v : 0.0f;
-        }
-    };
-    const int lane = tid & 63, wv = tid >> 6, wm = wv >> 1, wn = wv & 1;
-    const int li = lane & 31, lh = lane >> 5;
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[a][c][e] = 0.0f;
-    load(kbeg);
-    for (long long ks = kbeg; ks < kend; ks += BW_BK) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { sA[(r0 + 8 * r) * BW_LD + kl] = ra[r]; sB[(r0 + 8 * r) * BW_LD + kl] = rb[r]; }
-        __syncthreads();
-        if (ks + BW_BK < kend) load(ks + BW_BK);                      // the next step's operands travel while this one multiplies
-#pragma unroll
-        for (int t4 = 0; t4 < 4; ++t4) {
-            float fa[2][4], fb[2][4];
-#pragma unroll
-            for (int a = 0; a < 2; ++a) {
-                const float4 va = *(const float4*)&sA[(wm * 64 + a * 32 + li) * BW_LD + lh * 16 + t4 * 4];
-                const float4 vb = *(const float4*)&sB[(wn * 64 + a * 32 + li) * BW_LD + lh * 16 + t4 * 4];
-                fa[a][0] = va.x; fa[a][1] = va.y; fa[a][2] = va.z; fa[a][3] = va.w;
-                fb[a][0] = vb.x; fb[a][1] = vb.y; fb[a][2] = vb.z; fb[a][3] = vb.w;
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-#pragma unroll
-                    for (int c = 0; c < 2; ++c)
-                        acc[a][c] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[a][e], fb[c][e], acc[a][c], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-    // C / D layout of the 32 x 32 forms: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
-    float* out = part + (size_t)blockIdx.z * M * N;
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const int n = n0 + wn * 64 + c * 32 + li;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int m = m0 + wm * 64 + a * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
-                if (m < M && n < N) out[(size_t)m * N + n] = acc[a][c][e];
-            }
-        }
+    bw_gemm_body<TAPS == 9 ? 3 : 1, TAPS == 9 ? 3 : 1>(x, xbs, dy, dybs, cin, cout, h, w, K, kc, part, sA, sB);
 }
 
 // The layers with one or two output channels (FlowHead.conv2, 256 -> 2) do not fill a matrix tile: a plain kernel, one workgroup per
@@ -359,7 +254,7 @@ extern "C" int rpe_upsample_convex_backward(const float* grad_up, const float* f
 }
 
 static inline bool bw_shape_ok(int b, int cin, int cout, int h, int w, int kh, int kw) {
-    return b > 0 && cin > 0 && cout > 0 && h > 0 && w > 0 && ((kh == 3 && kw == 3) || (kh == 1 && kw == 1));
+    return b > 0 && cin > 0 && cout > 0 && h > 0 && w > 0 && ((kh == 3 && kw == 3) || (kh == 1 && kw == 1) || bw_ext_kernel(kh, kw));
 }
 
 // floats: partials (chunks, cout, cin, kh, kw), rounded up to 256 bytes | doubles: bias partials (chunks, cout)
@@ -386,7 +281,9 @@ extern "C" int rpe_conv_bwd_weight(const float* x, long long x_batch_stride, con
     float* part = (float*)workspace;
     double* bpart = (double*)((char*)workspace + ((size_t)chunks * per * sizeof(float) + 255) / 256 * 256);
     if (d_weight) {
-        if (cout <= 2) {
+        if (bw_ext_kernel(kh, kw)) {                                 // the update block's 1x5, 5x1, 7x7: update_backward.hip, any cout
+            if (!bw_gemm_launch_ext(x, x_batch_stride, dy, dy_batch_stride, cin, cout, h, w, kh, kw, K, kc, chunks, part, s)) return RPE_E_UNSUPPORTED;
+        } else if (cout <= 2) {
             const dim3 g(cin, chunks);
             if (taps == 9) hipLaunchKernelGGL(k_bw_small<9>, g, dim3(256), 0, s, x, x_batch_stride, dy, dy_batch_stride, cin, cout, h, w, K, kc, part);
             else hipLaunchKernelGGL(k_bw_small<1>, g, dim3(256), 0, s, x, x_batch_stride, dy, dy_batch_stride, cin, cout, h, w, K, kc, part);

@@ -1461,8 +1461,8 @@ def upsample_convex_backward(grad_up, flow, mask):
 
 
 def conv_bwd_weight(x, dy, kernel, scale=1.0, bias=True):
-    """rpe_conv_bwd_weight: (dW (cout,cin,kh,kw), db (cout) or None) of a stride-1 'same' convolution with ``kernel`` = (3,3) or (1,1) from
-    its input x (b,cin,h,w) and the gradient dy (b,cout,h,w) of its output, at any map size; both may be channel slices.  On the f32 matrix
+    """rpe_conv_bwd_weight: (dW (cout,cin,kh,kw), db (cout) or None) of a stride-1 'same' convolution with ``kernel`` = (3,3), (1,1), (1,5), (5,1) or (7,7)
+    from its input x (b,cin,h,w) and the gradient dy (b,cout,h,w) of its output, at any map size; both may be channel slices.  On the f32 matrix
     cores, K = b h w split by a rule of the shapes alone: bit-identical from run to run.  ``scale`` multiplies both results."""
     xp, xbs = _chan_slice(x, 'conv_bwd_weight: x')
     dp, dbs = _chan_slice(dy, 'conv_bwd_weight: dy')
@@ -1473,7 +1473,7 @@ def conv_bwd_weight(x, dy, kernel, scale=1.0, bias=True):
         raise _lib.RpeError(f'conv_bwd_weight: dy {tuple(dy.shape)} does not match x {tuple(x.shape)}')
     nws = lib().rpe_conv_bwd_weight_workspace_bytes(b, cin, cout, hh, ww, kh, kw)
     if nws == 0:
-        raise _lib.RpeError(f'conv_bwd_weight: unsupported shape (kernel {kh}x{kw}; 3x3 and 1x1, non-empty tensors)')
+        raise _lib.RpeError(f'conv_bwd_weight: unsupported shape (kernel {kh}x{kw}; 3x3, 1x1, 1x5, 5x1 and 7x7, non-empty tensors)')
     ws = torch.empty(nws, dtype=torch.uint8, device=x.device)
     dw = torch.empty(cout, cin, kh, kw, dtype=torch.float32, device=x.device)
     db = torch.empty(cout, dtype=torch.float32, device=x.device) if bias else None
@@ -1563,23 +1563,28 @@ class _TailPacked:
             self._made[name] = make()
         return self._made[name]
 
-    def conv_split(self, name, x, weight, bias, relu, group, out=None):
-        """act(conv(x; weight) + bias), stride 1, 'same', 3x3 or 1x1, on the forward's kernels -- rpe_conv_fused where the map is one it takes
+    def conv_split(self, name, x, weight, bias, relu, group, out=None, extra=0, fill=None):
+        """act(conv(x; weight) + bias), stride 1, 'same', 3x3, 1x1, 1x5 or 5x1, on the forward's kernels -- rpe_conv_fused where the map is one it takes
         (rows of whole 16-byte quads), ops.conv_direct at every other size -- run on ``group`` input channels at a time and the groups' results
         added in f64 (sum_groups).  Those kernels add their products in one k-ordered f32 chain: over all 1152 / 4608 terms of the tail's
         layers its error is 3-5 times that of a blocked float32 sum, over a group's 144-288 terms it is not."""
         b, cin, hh, ww = x.shape
-        cout, k = weight.shape[0], weight.shape[2]
+        cout, kh, kw = weight.shape[0], weight.shape[2], weight.shape[3]
         bounds = [(lo, min(cin, lo + group)) for lo in range(0, cin, group)]
-        parts = torch.empty(len(bounds), b, cout, hh, ww, dtype=torch.float32, device=x.device)
+        # ``extra``: that many more (b,cout,h,w) terms of the f64 sum behind the groups' results; ``fill(terms)`` writes them (the update
+        # block's backward adds the gradients that reach the same tensor by other paths there, instead of in f32 afterwards)
+        allp = torch.empty(len(bounds) + extra, b, cout, hh, ww, dtype=torch.float32, device=x.device)
+        parts = allp[:len(bounds)]
+        if extra:
+            fill(allp[len(bounds):])
         fused = ww % 4 == 0 and x.data_ptr() % 16 == 0 and x.stride(0) % 4 == 0
         for gi, (lo, hi) in enumerate(bounds):
             wg = self.get((name, gi, 'w'), lambda: weight[:, lo:hi].contiguous())
             if fused:
                 conv_fused(x[:, lo:hi], self.get((name, gi, 'packed'), lambda: PackedConv(wg, None)), CONV_LINEAR, parts[gi])
             else:
-                conv_direct(x[:, lo:hi], wg, None, 1, k // 2, out=parts[gi])
-        return sum_groups(parts, bias, relu, out)
+                conv_direct(x[:, lo:hi], wg, None, 1, (kh // 2, kw // 2), out=parts[gi])
+        return sum_groups(parts if extra == 0 else allp, bias, relu, out)
 
 
 def _tail_packed(fh_params, mask_params):
@@ -1666,4 +1671,232 @@ def raft_tail_attach(passes, fh_params, mask_params):
     flat = [x for p in passes for x in p]
     with torch.enable_grad():
         out = _RaftTailFn.apply(len(passes), *flat, *fh_params, *mask_params)
+    return [out] if len(passes) == 1 else list(out)
+
+
+# ------------------------------------------------------------------------------------------------- backward of RAFT's update block
+def _gate_slices(who, **named):
+    """[pointer, batch stride, ...] of equally shaped channel slices -> (flat list, (b, c, h, w))."""
+    shape, sl = None, []
+    for name, t in named.items():
+        sl += _chan_slice(t, f'{who}: {name}')
+        if shape is None:
+            shape = tuple(t.shape)
+        elif tuple(t.shape) != shape:
+            raise _lib.RpeError(f'{who}: {name} has shape {tuple(t.shape)}, expected {shape}')
+    return sl, shape
+
+
+def gru_gates_zr_recompute(zr_pre, h, z, r, rh):
+    """rpe_gru_gates_zr_recompute: z = s(zr_pre[:, :c]), r = s(zr_pre[:, c:]), rh = r h from the pre-activations (b,2c,h,w; bias added) -- the
+    gates with everything their adjoints read kept.  Channel slices."""
+    zp, zbs = _chan_slice(zr_pre, 'gru_gates_zr_recompute: zr_pre')
+    sl, (b, c, hh, ww) = _gate_slices('gru_gates_zr_recompute', h=h, z=z, r=r, rh=rh)
+    if tuple(zr_pre.shape) != (b, 2 * c, hh, ww):
+        raise _lib.RpeError(f'gru_gates_zr_recompute: zr_pre must be ({b},{2 * c},{hh},{ww})')
+    check(lib().rpe_gru_gates_zr_recompute(zp, zbs, *sl[:2], b, c, hh * ww, *sl[2:], stream_ptr()), 'rpe_gru_gates_zr_recompute')
+    return z, r, rh
+
+
+def gru_gates_h_recompute(q_pre, z, h, q, h_new):
+    """rpe_gru_gates_h_recompute: q = tanh(q_pre), h_new = (1 - z) h + z q.  Channel slices."""
+    sl, (b, c, hh, ww) = _gate_slices('gru_gates_h_recompute', q_pre=q_pre, z=z, h=h, q=q, h_new=h_new)
+    check(lib().rpe_gru_gates_h_recompute(*sl[:6], b, c, hh * ww, *sl[6:], stream_ptr()), 'rpe_gru_gates_h_recompute')
+    return q, h_new
+
+
+def gru_gates_zq_backward(d_h_new, h, z, q, d_z_pre, d_q_pre, d_h):
+    """rpe_gru_gates_zq_backward, the adjoint of one GRU half's blend h' = (1 - z) h + z q from d_h_new and the post-activation z, q:
+    d_z_pre = d (q - h) z (1 - z), d_q_pre = d z (1 - q^2), d_h = d (1 - z) (the direct term).  Channel slices (d_z_pre: e.g. the first half of
+    the stacked z | r buffer); the outputs must not overlap the inputs."""
+    sl, (b, c, hh, ww) = _gate_slices('gru_gates_zq_backward', d_h_new=d_h_new, h=h, z=z, q=q, d_z_pre=d_z_pre, d_q_pre=d_q_pre, d_h=d_h)
+    check(lib().rpe_gru_gates_zq_backward(*sl[:8], b, c, hh * ww, *sl[8:], stream_ptr()), 'rpe_gru_gates_zq_backward')
+    return d_z_pre, d_q_pre, d_h
+
+
+def gru_gates_r_backward(d_rh, h, r, d_h_in, d_r_pre, d_h_out):
+    """rpe_gru_gates_r_backward, once convq's data gradient d_rh = d loss / d (r h) is known: d_r_pre = d_rh h r (1 - r), d_h_out = d_h_in +
+    d_rh r.  d_h_out may be d_h_in or d_rh."""
+    sl, (b, c, hh, ww) = _gate_slices('gru_gates_r_backward', d_rh=d_rh, h=h, r=r, d_h_in=d_h_in, d_r_pre=d_r_pre, d_h_out=d_h_out)
+    check(lib().rpe_gru_gates_r_backward(*sl[:8], b, c, hh * ww, *sl[8:], stream_ptr()), 'rpe_gru_gates_r_backward')
+    return d_r_pre, d_h_out
+
+
+# ops.update_step_backward's parameter (and gradient) order: weight, bias of each -- 12 tensors of ``gru``, 10 of ``encoder``
+UPDATE_PARAMS = tuple(f'{m}.{t}' for m in ('gru.convz1', 'gru.convr1', 'gru.convq1', 'gru.convz2', 'gru.convr2', 'gru.convq2', 'encoder.convc1',
+                                           'encoder.convc2', 'encoder.convf1', 'encoder.convf2', 'encoder.conv') for t in ('weight', 'bias'))
+# input channels per launch of the step's forward-kernel convolutions (forward recomputation and data gradients alike): 144 terms of a 3x3
+# layer, 160 of a 5-tap layer, 64 of the 1x1 -- the k-ordered f32 chain of a launch stays below the tail's 288, the groups are added in f64
+UPDATE_GROUP_3X3, UPDATE_GROUP_5TAP, UPDATE_GROUP_1X1 = 16, 32, 64
+_UPDATE_PACKED = {}        # _wkey of the 22 parameters -> _UpdatePacked (the two newest weight sets)
+
+
+class _UpdatePacked(_TailPacked):
+    """What update_step_backward packs from the 22 parameters, each group's packing made on first use (_TailPacked.get / conv_split).
+    Forward: convz | convr of a half stacked along their OUTPUT channels, as the forward stacks them (gate_weights), in upstream's input
+    order [h | inp | motion | flow].  Data gradients: the TRANSPOSED, FLIPPED weights, zr stacked along its INPUT channels."""
+
+    def __init__(self, params):
+        p = [t.detach() for t in params]
+        self._made = {}
+        self.w = {name: (p[2 * i], p[2 * i + 1]) for i, name in enumerate(('z1', 'r1', 'q1', 'z2', 'r2', 'q2', 'c1', 'c2', 'f1', 'f2', 'cv'))}
+        tr = lambda w: w.transpose(0, 1).flip(2, 3)
+        for hf in ('1', '2'):
+            wz, bz = self.w['z' + hf]
+            wr, br = self.w['r' + hf]
+            self.w['zr' + hf] = (torch.cat((wz, wr), 0).contiguous(), torch.cat((bz, br), 0).contiguous())
+            self.w['zr' + hf + 't'] = torch.cat((tr(wz), tr(wr)), 1).contiguous()
+            self.w['q' + hf + 't'] = tr(self.w['q' + hf][0]).contiguous()
+        for name in ('c2', 'f2', 'cv'):
+            self.w[name + 't'] = tr(self.w[name][0]).contiguous()
+
+
+def _update_packed(params):
+    key = _wkey(*params)
+    if key not in _UPDATE_PACKED:
+        while len(_UPDATE_PACKED) >= 2:
+            _UPDATE_PACKED.pop(next(iter(_UPDATE_PACKED)))
+        _UPDATE_PACKED[key] = _UpdatePacked(params)
+    return _UPDATE_PACKED[key]
+
+
+def update_step_backward(hx, inp, corr, d_net, params):
+    """Backward of ONE application of RAFT's update block without its heads (csrc/update_backward.hip):
+        cor = relu(convc2(relu(convc1(corr)))); flo = relu(convf2(relu(convf1(flow)))); m = relu(conv([cor | flo])); x = [inp | m | flow]
+        per half (1x5, then 5x1): z = s(convz([h | x])), r = s(convr([h | x])), q = tanh(convq([r h | x])), h <- (1 - z) h + z q
+    hx (b,256,h8,w8): the step's entry state (h_{k-1} | motion slot | flow_k) in the workspace's layout -- the motion slot is not read;
+    inp (b,128,h8,w8); corr (b,324,h8,w8): the looked-up window; d_net (b,128,h8,w8) = d loss / d net_k; params: the 22 tensors of
+    UPDATE_PARAMS.  corr and flow are constants (upstream detaches coords1 at the top of the iteration): no gradient is formed into them.
+    -> (d_net_prev, d_inp, grads) with grads in UPDATE_PARAMS' order.  Every intermediate is recomputed here with the forward's kernels on
+    groups of input channels added in f64 (conv_split), which also compute the data gradients; the gradients that reach a tensor by several
+    paths are added in that same f64 sum.  f32 throughout, bit-identical from run to run, a row's result independent of its batch."""
+    who = 'update_step_backward'
+    hx, inp, corr, d_net = _nchw(hx, f'{who}: hx'), _nchw(inp, f'{who}: inp'), _nchw(corr, f'{who}: corr'), _nchw(d_net, f'{who}: d_net')
+    params = tuple(params)
+    b, c2, hh, ww = hx.shape
+    c = c2 // 2
+    for t in params:
+        _nchw(t.detach(), f'{who}: a parameter')
+    want = [(c, 3 * c, 1, 5)] * 3 + [(c, 3 * c, 5, 1)] * 3 + [(256, corr.shape[1], 1, 1), (192, 256, 3, 3), (128, 2, 7, 7), (64, 128, 3, 3), (c - 2, 256, 3, 3)]
+    if len(params) != 22 or c != 128 or any(tuple(params[2 * i].shape) != s or tuple(params[2 * i + 1].shape) != s[:1] for i, s in enumerate(want)):
+        raise _lib.RpeError(f'{who}: expected the 22 tensors of UPDATE_PARAMS (SepConvGRU and BasicMotionEncoder of hidden size 128) and hx with 256 channels')
+    if tuple(inp.shape) != (b, c, hh, ww) or tuple(d_net.shape) != (b, c, hh, ww) or tuple(corr.shape[::2]) != (b, hh) or corr.shape[3] != ww:
+        raise _lib.RpeError(f'{who}: inp and d_net must be ({b},{c},{hh},{ww}) and corr (b,324,h8,w8) for hx {tuple(hx.shape)}')
+    P = _update_packed(params)
+    G3, G5, G1 = UPDATE_GROUP_3X3, UPDATE_GROUP_5TAP, UPDATE_GROUP_1X1
+    new = lambda ch: torch.empty(b, ch, hh, ww, dtype=torch.float32, device=hx.device)
+    with torch.no_grad():
+        flow = hx[:, 2 * c - 2:]
+        # the motion encoder, again
+        c1 = P.conv_split('c1', corr, *P.w['c1'], True, G1)
+        cat = new(256)                                                  # (cor | flo)
+        P.conv_split('c2', c1, *P.w['c2'], True, G3, out=cat[:, :192])
+        f1 = conv_direct(flow, *P.w['f1'], 1, 3, relu=True)              # 2 -> 128, 7x7: 98 terms
+        P.conv_split('f2', f1, *P.w['f2'], True, G3, out=cat[:, 192:])
+        # the GRU's two halves, again: A = [h | inp | m | flow] (upstream's order), R = [r h | inp | m | flow]
+        A1, R1, A2, R2 = new(3 * c), new(3 * c), new(3 * c), new(3 * c)
+        copy_planes(hx[:, :c], A1[:, :c])
+        copy_planes(inp, A1[:, c:2 * c])
+        P.conv_split('cv', cat, *P.w['cv'], True, G3, out=A1[:, 2 * c:3 * c - 2])
+        copy_planes(flow, A1[:, 3 * c - 2:])
+        z, r, q = (new(c), new(c)), (new(c), new(c)), (new(c), new(c))
+        for i, (A, R, nxt) in enumerate(((A1, R1, A2), (A2, R2, None))):
+            hf = '12'[i]
+            copy_planes(A[:, c:], R[:, c:])
+            if nxt is not None:
+                copy_planes(A[:, c:], nxt[:, c:])
+            zr_pre = P.conv_split('zr' + hf, A, *P.w['zr' + hf], False, G5)
+            gru_gates_zr_recompute(zr_pre, A[:, :c], z[i], r[i], R[:, :c])
+            q_pre = P.conv_split('q' + hf, R, *P.w['q' + hf], False, G5)
+            gru_gates_h_recompute(q_pre, z[i], A[:, :c], q[i], nxt[:, :c] if nxt is not None else new(c))      # (net_k itself is not needed again)
+        # the adjoints, second half first.  T = [d h_old | d x] of a half: first convq's data gradient ([d (r h) | d x]), then, with the
+        # gates' terms written over its first c channels, one more term of the f64 sum behind convz | convr's data gradient
+        grads, d, carry = {}, d_net, None
+        for i, (A, R) in ((1, (A2, R2)), (0, (A1, R1))):
+            hf = '12'[i]
+            kernel = (1, 5) if i == 0 else (5, 1)
+            dzr, dq, dh = new(2 * c), new(c), new(c)
+            gru_gates_zq_backward(d, A[:, :c], z[i], q[i], dzr[:, :c], dq, dh)
+            grads['q' + hf] = conv_bwd_weight(R, dq, kernel)
+            T = P.conv_split('q' + hf + 't', dq, P.w['q' + hf + 't'], None, False, G5)
+            gru_gates_r_backward(T[:, :c], A[:, :c], r[i], dh, dzr[:, c:], T[:, :c])
+            dw, db = conv_bwd_weight(A, dzr, kernel)                     # convz | convr read the same input: one GEMM of 2 c output channels
+            grads['z' + hf], grads['r' + hf] = (dw[:c], db[:c]), (dw[c:], db[c:])
+
+            def fill(terms, T=T, carry=carry):
+                copy_planes(T, terms[0])
+                if carry is not None:                                   # the other half's d x (its d h_old went into this half as ``d``)
+                    terms[1][:, :c].zero_()
+                    copy_planes(carry[:, c:], terms[1][:, c:])
+            carry = P.conv_split('zr' + hf + 't', dzr, P.w['zr' + hf + 't'], None, False, G5, extra=1 if carry is None else 2, fill=fill)
+            d = carry[:, :c]
+        d_net_prev, d_inp = new(c), new(c)
+        copy_planes(carry[:, :c], d_net_prev)
+        copy_planes(carry[:, c:2 * c], d_inp)
+        # the motion encoder's adjoint (nothing into flow or corr)
+        m = A1[:, 2 * c:3 * c - 2]
+        dm = relu_backward(carry[:, 2 * c:3 * c - 2], m)
+        grads['cv'] = conv_bwd_weight(cat, dm, (3, 3))
+        dcat = P.conv_split('cvt', dm, P.w['cvt'], None, False, G3)
+        relu_backward(dcat, cat)
+        grads['c2'] = conv_bwd_weight(c1, dcat[:, :192], (3, 3))
+        grads['f2'] = conv_bwd_weight(f1, dcat[:, 192:], (3, 3))
+        dc1 = P.conv_split('c2t', dcat[:, :192], P.w['c2t'], None, False, G3)
+        relu_backward(dc1, c1)
+        grads['c1'] = conv_bwd_weight(corr, dc1, (1, 1))
+        df1 = P.conv_split('f2t', dcat[:, 192:], P.w['f2t'], None, False, G3)
+        relu_backward(df1, f1)
+        grads['f1'] = conv_bwd_weight(flow, df1, (7, 7))
+    order = ('z1', 'r1', 'q1', 'z2', 'r2', 'q2', 'c1', 'c2', 'f1', 'f2', 'cv')
+    return d_net_prev, d_inp, tuple(t for name in order for t in grads[name])
+
+
+class _RaftBpttFn(torch.autograd.Function):
+    """k gradient-free RAFT passes run with ``grad_update`` as ONE autograd node: inputs k x (flow_up, hidden, flow_low, net_0, inp), the
+    eight head parameters and the 22 of UPDATE_PARAMS; outputs the k up-sampled flows unchanged.  ``saved[i]`` = (states, corr_of): the
+    dense entry states (hx_k, coords1_k), k = 1 .. N, of pass i and a function k -> the window the pass looked up for states[k]
+    (RAFT.corr_of; it holds the pyramid).  Backward, per pass in the order given: raft_tail_backward (d net_N), then update_step_backward for k = N .. 1; the parameter
+    gradients are summed over the steps in descending k, then over the passes in the given order (a pass whose flow nothing
+    differentiates is skipped): the sum's bits do not depend on the autograd engine's scheduling."""
+
+    @staticmethod
+    def forward(ctx, k, saved, *tensors):
+        ctx.k, ctx.saved = k, saved
+        ctx.save_for_backward(*tensors)
+        ctx.set_materialize_grads(False)
+        outs = tuple(tensors[5 * i].view_as(tensors[5 * i]) for i in range(k))
+        return outs[0] if k == 1 else outs
+
+    @staticmethod
+    def backward(ctx, *grads):
+        t, k = ctx.saved_tensors, ctx.k
+        heads, upd = t[5 * k:5 * k + 8], t[5 * k + 8:]
+        totals, per_pass = None, []
+        for i, g in enumerate(grads):
+            if g is None:
+                per_pass += [None] * 5
+                continue
+            hidden, low, inp = t[5 * i + 1].detach(), t[5 * i + 2], t[5 * i + 4].detach()
+            d_net_n, pg = raft_tail_backward(hidden, low, g.contiguous(), heads[:4], heads[4:])
+            states, corr_of = ctx.saved[i]
+            d, d_inp, ug = d_net_n, None, None
+            for step in reversed(range(len(states))):
+                d, di, sg = update_step_backward(states[step][0], inp, corr_of(step), d, upd)
+                d_inp = di if d_inp is None else d_inp + di
+                ug = list(sg) if ug is None else [a + b for a, b in zip(ug, sg)]
+            both = list(pg) + (ug if ug is not None else [torch.zeros_like(p) for p in upd])
+            totals = both if totals is None else [a + b for a, b in zip(totals, both)]
+            per_pass += [None, d_net_n, None, d, d_inp]
+        return (None, None, *per_pass, *(totals if totals is not None else [None] * 30))
+
+
+def update_bptt_attach(passes, saved, fh_params, mask_params, update_params):
+    """Attach the update block's backward through time to the results of gradient-free RAFT passes (RAFT.forward(grad_update=True)):
+    ``passes`` = [(flow_up, hidden, flow_low, net_0, inp), ...] with hidden, net_0 and inp leaves that require grad; ``saved`` = per pass
+    (states, corr_of) as _RaftBpttFn describes -> the list of up-sampled flows (the same values), outputs of one autograd node.  After a
+    backward: hidden.grad = d loss / d net_N, net_0.grad = d loss / d net_0, inp.grad = d loss / d inp (summed over the iterations, last
+    first), and the 30 parameters' .grad."""
+    flat = [x for p in passes for x in p]
+    with torch.enable_grad():
+        out = _RaftBpttFn.apply(len(passes), list(saved), *flat, *fh_params, *mask_params, *update_params)
     return [out] if len(passes) == 1 else list(out)

@@ -55,19 +55,26 @@ class PoseNet(nn.Module):
         return dict(f=f, c=c)
 
     @torch.no_grad()
-    def flow2depth(self, imagel, imager, baseline, upsample=True, ret_cache=False, enc=None, ret_tail=False):
+    def flow2depth(self, imagel, imager, baseline, upsample=True, ret_cache=False, enc=None, ret_tail=False, save_states=False):
         """pose_net.py:127-135 -> (depth (n,1,h,w), stereo flow (n,2,h,w), valid (n,1,h,w) bool).
         ``upsample=False``: everything at 1/8 resolution, the flow in 1/8-pixel units and the depth divided by 8 (:131-132;
         a division by a power of two commutes with the rounding of b / -flow.x, so the kernel is handed b / 8).
         ``ret_cache`` additionally returns the encoder outputs of ``imagel`` for reuse by the next ``infer``.
-        ``ret_tail`` additionally returns (hidden state, last 1/8 flow) of the pass: what the backward of RAFT's output heads reads."""
+        ``ret_tail`` additionally returns (hidden state, last 1/8 flow) of the pass: what the backward of RAFT's output heads reads; with
+        ``save_states`` (needs ret_tail) the tuple goes on with what the update block's backward reads: the context encoder's output, the
+        pass's saved entry states and its pyramid (RAFT.pass_with_states)."""
         n = imagel.shape[0]
         f, cn = (enc['f'], enc['c']) if enc is not None else self._encode_both((imagel, imager), imagel)
-        r = self.flow(None, None, upsample=upsample, fmaps=(f[:n], f[n:]), cnet=cn, **(dict(ret_lowres=True) if ret_tail else {}))
+        more = ()
+        if save_states:
+            r, states, pyr = self.flow.pass_with_states((f[:n], f[n:]), cn, upsample=upsample)
+            more = (cn, states, pyr)
+        else:
+            r = self.flow(None, None, upsample=upsample, fmaps=(f[:n], f[n:]), cnet=cn, **(dict(ret_lowres=True) if ret_tail else {}))
         flow = r[0][-1]
         depth, valid = ops.flow2depth(flow, baseline if upsample else baseline / 8.0)
         if ret_tail:
-            return depth, flow, valid, (r[1], r[3])
+            return depth, flow, valid, (r[1], r[3]) + more
         if ret_cache:
             return depth, flow, valid, dict(fmap=f[:n], cnet=cn)
         return depth, flow, valid
@@ -88,18 +95,23 @@ class PoseNet(nn.Module):
         not, and the three flows are the outputs of ONE autograd node (ops.raft_tail_attach; passes in the order time, stereo1, stereo2)
         over the three RAFT results -- the ``flow2depth`` pass of frame 1 and both halves of the batched pass --, whose backward
         (ops.raft_tail_backward) hands the pose loss's gradient to the flow head's and the mask head's eight parameters, summed over the
-        three.  The flows keep their ``.grad`` (retain_grad), and with ``ret_flows`` the returned dict gains 'hidden': {'time', 'stereo1',
+        three.  With the whole update block trainable (``freeze_flow(False, parts='update')``) that node is ops.update_bptt_attach instead:
+        the three passes also save the entry state of every iteration, and the node's backward goes on from the tail through the N
+        applications of the SepConvGRU and the motion encoder (ops.update_step_backward) -- all 30 update-block parameters get the pose
+        loss's exact gradient under upstream's detach of coords1; the dict then gains 'net0' and 'inp', leaves per pass whose ``.grad`` is
+        d loss / d net_0 and d loss / d inp.  The flows keep their ``.grad`` (retain_grad), and with ``ret_flows`` the returned dict gains 'hidden': {'time', 'stereo1',
         'stereo2'}, leaves whose ``.grad`` is the tail's d loss / d net_N, plus the weight heads' input gradient for 'time'."""
         n = image1l.shape[0]
         intrinsics = intrinsics.expand(n, 3, 3).contiguous()
         baseline = baseline.expand(n).contiguous()
-        grad_heads = self.flow_heads_trainable()
+        grad_update = self.flow_update_trainable()
+        grad_heads = self.flow_heads_trainable() or grad_update
         if grad_heads:
             self.flow.check_grad_heads()                       # (before anything is launched)
         with torch.no_grad():
             tail1 = None
             if grad_heads:
-                depth1, stereo_flow1, valid1, tail1 = self.flow2depth(image1l, image1r, baseline, ret_tail=True)
+                depth1, stereo_flow1, valid1, tail1 = self.flow2depth(image1l, image1r, baseline, ret_tail=True, save_states=grad_update)
             else:
                 depth1, stereo_flow1, valid1 = self.flow2depth(image1l, image1r, baseline)
             mask1 = (mask1.bool() & valid1) if mask1 is not None else valid1
@@ -124,6 +136,8 @@ class PoseNet(nn.Module):
             flows = {k: s[k] for k in ('time_flow', 'stereo_flow1', 'stereo_flow2')}
             if grad_heads:
                 flows['hidden'] = s['hidden_leaves']
+            if grad_update:
+                flows['net0'], flows['inp'] = s['net0_leaves'], s['inp_leaves']
             out = (*out, flows)
         return out
 
@@ -135,21 +149,34 @@ class PoseNet(nn.Module):
     def flow_heads_trainable(self):
         return any(p.requires_grad for p in self.flow_head_params())
 
+    def flow_update_trainable(self):
+        """Does a parameter of RAFT's SepConvGRU or motion encoder require grad (``freeze_flow(False, parts='update')``)?"""
+        params = getattr(self.flow, 'update_params', None)
+        return params is not None and any(p.requires_grad for p in params())
+
     def freeze_flow(self, freeze=True, parts=None):
-        """pose_net.py:148-153.  Un-freezing the whole flow network needs its backward, which is not built: the gradients of the pose loss
-        reach the three flows (``forward(..., ret_flows=True)``: the pose layer's and the geometry stage's backward) and, through the backward
-        of RAFT's last flow-head / mask-head application (csrc/raft_backward.hip), those heads' parameters -- ``freeze_flow(False,
-        parts='heads')`` sets requires_grad on ``flow.update_block.flow_head`` and ``flow.update_block.mask`` only.  Everything else of RAFT has no
-        backward here: ``freeze_flow(False)`` without ``parts`` is refused instead of training against silently missing gradients."""
-        if parts not in (None, 'heads'):
-            raise ValueError(f"freeze_flow: parts must be None or 'heads', got {parts!r}")
+        """pose_net.py:148-153.  Un-freezing the whole flow network needs its backward, which is built from the loss inwards as far as the
+        update block: the gradients of the pose loss reach the three flows (``forward(..., ret_flows=True)``: the pose layer's and the geometry
+        stage's backward), through the backward of RAFT's last flow-head / mask-head application (csrc/raft_backward.hip) those heads'
+        parameters -- ``freeze_flow(False, parts='heads')`` sets requires_grad on ``flow.update_block.flow_head`` and ``flow.update_block.mask``
+        only --, and through the backward of the N update steps (csrc/update_backward.hip, ops.update_step_backward) the SepConvGRU and the
+        motion encoder -- ``freeze_flow(False, parts='update')`` sets it on all of ``flow.update_block``.  The two encoders and the correlation
+        (build and lookup) have no backward here: ``freeze_flow(False)`` without ``parts`` is refused instead of training against silently
+        missing gradients."""
+        if parts not in (None, 'heads', 'update'):
+            raise ValueError(f"freeze_flow: parts must be None, 'heads' or 'update', got {parts!r}")
         if not freeze and parts == 'heads':
             for p in self.flow_head_params():
                 p.requires_grad = True
             return self
+        if not freeze and parts == 'update':
+            for p in self.flow.update_block.parameters():
+                p.requires_grad = True
+            return self
         if not freeze:
-            raise NotImplementedError('training the flow network (freeze_flow(False)) is out of scope: the gradients stop at the flows '
-                                      '(forward(..., ret_flows=True) returns them); RAFT has no backward here')
+            raise NotImplementedError('training the whole flow network (freeze_flow(False)) is out of scope: the gradients stop at the flows '
+                                      '(forward(..., ret_flows=True) returns them), at RAFT\'s output heads (parts=\'heads\') or at its update '
+                                      'block (parts=\'update\'); the encoders and the correlation have no backward here')
         for p in self.parameters():
             p.requires_grad = True
         for p in self.flow.parameters():
@@ -224,7 +251,12 @@ class PoseNet(nn.Module):
             kw['flow_init'] = torch.cat((flow_init, torch.zeros_like(flow_init)), dim=0)      # (temporal | stereo) rows of the RAFT batch
         if ret_lowres or tail1 is not None:
             kw['ret_lowres'] = True
-        r = self.flow(None, None, upsample=True, fmaps=fmaps, cnet=cn, **kw)
+        bptt = tail1 is not None and len(tail1) > 2              # (flow2depth's save_states: the update block trains)
+        if bptt:
+            kw.pop('ret_lowres')
+            r, states2, pyr2 = self.flow.pass_with_states(fmaps, cn, upsample=True, **kw)
+        else:
+            r = self.flow(None, None, upsample=True, fmaps=fmaps, cnet=cn, **kw)
         flow_predictions, hidden, context = r[:3]
         time_flow = flow_predictions[-1][:n].contiguous()
         stereo_flow2 = flow_predictions[-1][n:].contiguous()
@@ -238,9 +270,21 @@ class PoseNet(nn.Module):
                     leaves = {k: t.detach().requires_grad_(True) for k, t in leaves.items()}
                     hidden = leaves['time']                    # (the weight heads read it: their input gradient lands in its .grad)
                     fh, mk = self.flow.head_params()
-                    time_flow, stereo_flow1, stereo_flow2 = ops.raft_tail_attach(
-                        [(time_flow, leaves['time'], low[:n]), (stereo_flow1.contiguous(), leaves['stereo1'], tail1[1]),
-                         (stereo_flow2, leaves['stereo2'], low[n:])], fh, mk)
+                    passes = [(time_flow, leaves['time'], low[:n]), (stereo_flow1.contiguous(), leaves['stereo1'], tail1[1]),
+                              (stereo_flow2, leaves['stereo2'], low[n:])]
+                    if bptt:
+                        c = hidden.shape[1]
+                        cn1, states1, pyr1 = tail1[2:]
+                        rows = dict(time=(cn, 0, n), stereo1=(cn1, 0, n), stereo2=(cn, n, 2 * n))
+                        net0 = {k: t[lo:hi, :c].clone().requires_grad_(True) for k, (t, lo, hi) in rows.items()}
+                        inp = {k: t[lo:hi, c:].clone().requires_grad_(True) for k, (t, lo, hi) in rows.items()}
+                        corr_of = self.flow.corr_of
+                        saved = [([(st[:n], co[:n]) for st, co in states2], corr_of(pyr2, states2, (0, n))), (states1, corr_of(pyr1, states1)),
+                                 ([(st[n:], co[n:]) for st, co in states2], corr_of(pyr2, states2, (n, 2 * n)))]
+                        passes = [p + (net0[k], inp[k]) for p, k in zip(passes, ('time', 'stereo1', 'stereo2'))]
+                        time_flow, stereo_flow1, stereo_flow2 = ops.update_bptt_attach(passes, saved, fh, mk, self.flow.update_params())
+                    else:
+                        time_flow, stereo_flow1, stereo_flow2 = ops.raft_tail_attach(passes, fh, mk)
                     for t in (time_flow, stereo_flow1, stereo_flow2):
                         t.retain_grad()
                 else:
@@ -256,6 +300,8 @@ class PoseNet(nn.Module):
                  intrinsics=intrinsics, cache2=dict(fmap=f2l, cnet=c2l))
         if leaves is not None:
             g['hidden_leaves'] = leaves
+            if bptt:
+                g['net0_leaves'], g['inp_leaves'] = net0, inp
         if ret_lowres:
             g['time_flow_low'] = g['cache2']['time_flow_low'] = r[3][:n]
         return g

@@ -1170,6 +1170,49 @@ class RAFT(nn.Module):
         fh, mk = self.update_block.flow_head, self.update_block.mask
         return (fh.conv1.weight, fh.conv1.bias, fh.conv2.weight, fh.conv2.bias), (mk[0].weight, mk[0].bias, mk[2].weight, mk[2].bias)
 
+    def update_params(self):
+        """The 22 parameters of the SepConvGRU and the motion encoder in ops.UPDATE_PARAMS' order (ops.update_step_backward)."""
+        return tuple(operator.attrgetter(name)(self.update_block) for name in ops.UPDATE_PARAMS)
+
+    def _save_state(self, ws, states, flow=None, coords1=None):
+        """``grad_update``: the entry state of the iteration about to run as dense tensors of their own -- (hx's 256 channels: h_{k-1} |
+        motion slot | flow_k, and coords1_k, which the lookup is about to read), the content only when the workspace is padded: one copy
+        of hx and one of the two coordinate planes.  ``flow`` / ``coords1``: the generic route's, which keeps them outside the workspace
+        (and writes flow_k into hx inside the step)."""
+        hx, valid = ws['hx'], ws['valid']
+        co = ws['coords1'] if coords1 is None else coords1.contiguous()
+        if valid is not None:
+            new = lambda ch: torch.empty(hx.shape[0], ch, *valid, device=hx.device)
+            states.append((ops.copy_rect(hx, new(hx.shape[1]), *valid), ops.copy_rect(co, new(2), *valid)))
+            return
+        st = ops.copy_planes(hx, torch.empty_like(hx))
+        if flow is not None:
+            ops.copy_planes(flow.contiguous(), st[:, hx.shape[1] - 2:])
+        states.append((st, ops.copy_planes(co, torch.empty_like(co))))
+
+    @staticmethod
+    def corr_of(pyr, states, rows=None):
+        """k -> the window iteration k + 1 looked up (``states[k]`` = its (hx, coords1)): the pass's lookup on the saved coordinates against
+        its pyramid, which the returned function keeps alive (the model builds itself a new one for its next pass) -- the forward's bits;
+        ``rows`` = (lo, hi): those rows of the batch only.  (coords0 + flow_k would not do: coords1 - coords0 rounds where a target lies
+        much closer to column or row 0 than its source.)"""
+        last = {}
+
+        def corr(k):
+            if last.get('k') != k:
+                last.update(k=k, corr=pyr.lookup(states[k][1]))
+            return last['corr'] if rows is None else last['corr'][rows[0]:rows[1]]
+        return corr
+
+    def pass_with_states(self, fmaps, cnet, **kw):
+        """A gradient-free ``ret_lowres`` pass on given encoder outputs that also saves what ``grad_update`` saves -> (the pass's result,
+        the dense entry states hx_1 .. hx_N, the pass's pyramid -- no longer the model's)."""
+        self.check_grad_heads(kw.get('upsample', True))
+        states = []
+        r = self.forward(None, None, fmaps=fmaps, cnet=cnet, ret_lowres=True, _states=states, **kw)
+        pyr, self._pyr = self._pyr, None
+        return r, states, pyr
+
     def check_grad_heads(self, upsample=True):
         """The refusals of ``grad_heads`` (raised before anything is launched): the tail's backward differentiates the f32 layers; a route
         that rounds their operands has no honest gradient here."""
@@ -1185,7 +1228,7 @@ class RAFT(nn.Module):
 
     @torch.no_grad()
     def forward(self, image1, image2, upsample=True, iters=None, all_flows=False, fmaps=None, cnet=None, flow_init=None, ret_lowres=False,
-                grad_heads=False):
+                grad_heads=False, grad_update=False, _states=None):
         """image1, image2: (N,3,H,W) in 0..255.  Inference only (the reference freezes RAFT, train.yaml:51).
         ``fmaps`` / ``cnet`` accept encoder outputs computed elsewhere (both encoders normalise per sample -- instance
         norm / frozen batch norm -- so a caller may encode every distinct image once and reuse it); with both given the
@@ -1198,7 +1241,30 @@ class RAFT(nn.Module):
         eight parameters and the returned hidden state, which comes back as a leaf that requires grad.  Upstream detaches coords1 at the
         top of every iteration, so that prediction depends on those parameters through their last application only: the node's backward
         (ops.raft_tail_backward, csrc/raft_backward.hip) is their exact gradient, and hidden.grad is d loss / d net_N.  Refused with
-        update_fp16, CONV_BF16X3 and mixed_precision (check_grad_heads)."""
+        update_fp16, CONV_BF16X3 and mixed_precision (check_grad_heads).
+        ``grad_update``: ``grad_heads`` extended to the whole update block.  The pass runs as ever (gradient-free, the kernels and the bits of
+        a ``ret_lowres`` pass, launched iteration by iteration) and additionally copies the entry state of every iteration -- hx's 256
+        channels: h_{k-1}, the stale motion slot and flow_k, and the two planes of coords1_k -- into dense tensors of their own: 258 h8 w8 4
+        bytes per pair and iteration, 5.3 MB at 640 x 512, 63 MB per pair for 12 iterations.  The correlation window is not saved: the
+        node looks it up again at the saved coordinates in the pass's pyramid, which it keeps alive (the forward's bits).  The last prediction is the output of one node (ops.update_bptt_attach)
+        whose backward is the tail's, then ops.update_step_backward for k = N .. 1: the exact gradient of all 30 update-block parameters
+        under upstream's detach of coords1 (the only path through time is the hidden state).  ``hidden`` is a leaf as under grad_heads; two
+        more elements are appended to the result, the leaves ``net_0`` (N,128,h8,w8) and ``inp`` (a leaf copy of the context), whose .grad are
+        d loss / d net_0 and d loss / d inp summed over the iterations.  The same refusals as grad_heads, before any launch."""
+        if grad_update:
+            self.check_grad_heads(upsample)
+            states = []
+            flows, hidden, context, low = self.forward(image1, image2, upsample, iters, all_flows, fmaps, cnet, flow_init, ret_lowres=True,
+                                                       _states=states)
+            pyr, self._pyr = self._pyr, None                   # the node's from here on
+            c = self.hidden_dim
+            net0 = ops.copy_planes(states[0][0][:, :c], torch.empty_like(hidden)) if states else hidden.clone()
+            inp = context.clone()
+            for t in (hidden, net0, inp):
+                t.requires_grad_(True)
+            flows[-1] = ops.update_bptt_attach([(flows[-1], hidden, low, net0, inp)], [(states, self.corr_of(pyr, states))], *self.head_params(),
+                                               self.update_params())[0]
+            return (flows, hidden, context) + ((low,) if ret_lowres else ()) + (net0, inp)
         if grad_heads:
             self.check_grad_heads(upsample)
             flows, hidden, context, low = self.forward(image1, image2, upsample, iters, all_flows, fmaps, cnet, flow_init, ret_lowres=True)
@@ -1231,7 +1297,8 @@ class RAFT(nn.Module):
         padded = route.loop_pad                                # pad_maps: the loop's maps, when the tuned kernels refuse (h8, w8)
         P = ub.packed_convs((padded or (h8, w8))[1])
         fused = P is not None
-        if fused and FRAME_OPLISTS and LOOP_OPLIST and not all_flows and N <= FRAME_OPLISTS_MAX_IMAGES and LOOKUP_EVENT_SINK is None:
+        if fused and FRAME_OPLISTS and LOOP_OPLIST and not all_flows and N <= FRAME_OPLISTS_MAX_IMAGES and LOOKUP_EVENT_SINK is None \
+                and _states is None:                           # (grad_update: the state copies sit between the iterations)
             r = self._forward_recorded(route, fmap1, fmap2, cnet, iters, upsample, flow_init, ret_lowres)
             if r is not None:
                 return tail([r[0]], r[1], r[2])
@@ -1243,15 +1310,19 @@ class RAFT(nn.Module):
         side = self._side_stream(dev) if fused and SIDE_STREAM and N * h8 * w8 <= SIDE_STREAM_MAX else None
         if fused and LOOP_OPLIST:                             # the loop as a launch list: whole, or iteration by iteration for their flows
             prog, marks, streams = self._run_loop(pyr, ws, iters, side)
-            if not all_flows:
+            if not all_flows and _states is None:
                 prog.run(streams)
-            for itr in range(iters if all_flows else 0):
+            for itr in range(iters if all_flows or _states is not None else 0):
+                if _states is not None:
+                    self._save_state(ws, _states)
                 prog.run(streams, marks[itr], marks[itr + 1])
-                if itr < iters - 1:
+                if all_flows and itr < iters - 1:
                     flow_predictions.append(self._prediction(ws['flow'], hx, upsample, ws['valid']))
         elif fused:                                           # the same launches, one by one from Python
             for itr in range(iters):
                 done = None
+                if _states is not None:
+                    self._save_state(ws, _states)
                 if side is not None:
                     # the motion encoder's flow branch (convf1 -> convf2) needs only the flow: it runs on a side stream beside
                     # lookup -> convc1 -> convc2 and fills the partly idle last rounds of those launches
@@ -1275,6 +1346,8 @@ class RAFT(nn.Module):
         for itr in range(iters):
             pyr.lookup(coords1, out=corr)
             flow = flow_init if itr == 0 and flow_init is not None else coords1 - coords0
+            if _states is not None:
+                self._save_state(ws, _states, flow, coords1)
             coords1 = ub.step(ws, ctx, flow, coords1, h_buf)
             if all_flows or itr == iters - 1:
                 lowres = coords1 - coords0
