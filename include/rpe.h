@@ -73,6 +73,8 @@ const char *rpe_version(void);
  *   and the backward of one update-block application: rpe_gru_gates_zr_recompute, rpe_gru_gates_h_recompute,
  *   rpe_gru_gates_zq_backward, rpe_gru_gates_r_backward (rpe_conv_bwd_weight also takes
  *   (1,5), (5,1) and (7,7) since then: rpe_conv_bwd_weight_workspace_bytes returns 0 for them in a library that does not);
+ *   and the backward of the correlation: rpe_corr_grad_volume_floats, rpe_corr_lookup_backward, rpe_corr_build_backward_workspace_bytes,
+ *   rpe_corr_build_backward;
  *   the next RPE_ABI_MINOR bump counts them and rpe_conv_wino24*. */
 #define RPE_ABI_VERSION 5
 #define RPE_ABI_MINOR 4
@@ -358,6 +360,35 @@ int rpe_gru_gates_zq_backward(const float *d_h_new, long long d_batch_stride, co
 int rpe_gru_gates_r_backward(const float *d_rh, long long drh_batch_stride, const float *h, long long h_batch_stride, const float *r,
                              long long r_batch_stride, const float *d_h_in, long long dhi_batch_stride, int b, int c, int hw, float *d_r_pre,
                              long long dr_batch_stride, float *d_h_out, long long dho_batch_stride, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Backward of the correlation (csrc/corr_backward.hip; core/RAFT/core/corr.py CorrBlock), f32 pyramid route.  Upstream detaches coords1, so
+ * the lookup coordinates are constants: the window is linear in the pyramid, the pyramid bilinear in (fmap1, fmap2); the gradient is exact.
+ * The gradient volume G = d loss / d pyramid is a dense f32 (b, h8 w8, S) tensor, S = sum_l h_l w_l with h_l = h8 >> l, w_l = w8 >> l (the
+ *   pyramid's level sizes, every level at least 2 x 2): row p holds the levels' maps of query p one after the other, each row-major.
+ *   S h8 w8 4 bytes per pair: 139 MB at 640 x 512 (h8 w8 = 5120, S = 6800), 2.2 GB at 1280 x 1024.  rpe_corr_grad_volume_floats: its size,
+ *   0 for a geometry the pyramid refuses.
+ * rpe_corr_lookup_backward: G += the adjoint of ONE rpe_corr_lookup at coords (b,2,h8,w8) from d_corr (b, levels 81, h8, w8), the gradient
+ *   of the looked-up window (channel l 81 + i 9 + j samples level l at (x + i - r, y + j - r): upstream's transposed window order).  The
+ *   integer taps and fractions are the forward's (the function behind rpe_corr_lookup_taps); a cell is the sum of its (at most four non-zero)
+ *   weight x gradient terms in one fixed order; cells outside a level are dropped (zero padding).  One wave owns a query's row: no atomics;
+ *   calls accumulate in stream order; bit-identical from run to run and independent of the batch.  The caller zero-fills G.  radius == 4.
+ * rpe_corr_build_backward: d_fmap1, d_fmap2 (b,c,h8,w8) from G and the feature maps.  With F2cat (c x S) = fmap2 followed by its
+ *   successively 2x2-pooled copies (floor: a last odd row / column is dropped, as avg_pool2d does):
+ *       d_fmap1 = F2cat G^T / sqrt(c),   dF2cat = fmap1 G / sqrt(c),   d_fmap2 = dF2cat's level 0 + the pool adjoints of the levels above,
+ *   applied from the last level down to 0 (a quarter to each covered cell, nothing to a dropped row or column).  The GEMMs run on the f32
+ *   matrix cores (v_mfma_f32_32x32x2_f32); the contraction axis K (S, then h8 w8) is split into chunks of max(512, round_up(ceil(K / 8), 32))
+ *   -- a function of the shape alone --, the partials are added in chunk order in f64 and scaled there.  No float atomics.  c: a multiple of
+ *   4 up to 256.  d_f2cat (b,c,S) may be NULL (it then lives in the workspace).  workspace: rpe_corr_build_backward_workspace_bytes(...) bytes
+ *   (0 for a shape it refuses), 16-byte aligned.
+ * NULL, a refused geometry or c, radius != 4, b > 65535: RPE_E_BADARG.
+ * --------------------------------------------------------------------------------------------------------- */
+size_t rpe_corr_grad_volume_floats(int b, int h8, int w8, int levels);
+int rpe_corr_lookup_backward(const float *coords, const float *d_corr, int b, int h8, int w8, int levels, int radius, float *grad_volume,
+                             void *stream);
+size_t rpe_corr_build_backward_workspace_bytes(int b, int c, int h8, int w8, int levels);
+int rpe_corr_build_backward(const float *grad_volume, const float *fmap1, const float *fmap2, int b, int c, int h8, int w8, int levels,
+                            float *d_fmap1, float *d_fmap2, float *d_f2cat, void *workspace, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * RAFT correlation -- replaces CorrBlock (core/RAFT/core/corr.py of the aimi-lab/RAFT submodule: all-pairs

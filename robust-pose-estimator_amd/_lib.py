@@ -249,6 +249,10 @@ SIGNATURES = {
     'rpe_gru_gates_h_recompute': (_i, [_vp, _ll] * 3 + [_i, _i, _i] + [_vp, _ll] * 2 + [_vp]),
     'rpe_gru_gates_zq_backward': (_i, [_vp, _ll] * 4 + [_i, _i, _i] + [_vp, _ll] * 3 + [_vp]),
     'rpe_gru_gates_r_backward': (_i, [_vp, _ll] * 4 + [_i, _i, _i] + [_vp, _ll] * 2 + [_vp]),
+    'rpe_corr_grad_volume_floats': (_sz, [_i, _i, _i, _i]),
+    'rpe_corr_lookup_backward': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    'rpe_corr_build_backward_workspace_bytes': (_sz, [_i] * 5),
+    'rpe_corr_build_backward': (_i, [_vp, _vp, _vp] + [_i] * 5 + [_vp] * 5),
     'rpe_flow_forward_interpolate': (_i, [_vp, _i, _i, _i, _vp, _vp]),
     'rpe_corr_pyramid_bytes': (_sz, [_i, _i, _i, _i]),
     'rpe_corr_pyramid_bytes_ex': (_sz, [_i, _i, _i, _i, _i]),

@@ -1747,7 +1747,7 @@ class _UpdatePacked(_TailPacked):
             self.w['zr' + hf] = (torch.cat((wz, wr), 0).contiguous(), torch.cat((bz, br), 0).contiguous())
             self.w['zr' + hf + 't'] = torch.cat((tr(wz), tr(wr)), 1).contiguous()
             self.w['q' + hf + 't'] = tr(self.w['q' + hf][0]).contiguous()
-        for name in ('c2', 'f2', 'cv'):
+        for name in ('c1', 'c2', 'f2', 'cv'):
             self.w[name + 't'] = tr(self.w[name][0]).contiguous()
 
 
@@ -1760,14 +1760,17 @@ def _update_packed(params):
     return _UPDATE_PACKED[key]
 
 
-def update_step_backward(hx, inp, corr, d_net, params):
+def update_step_backward(hx, inp, corr, d_net, params, ret_d_corr=False):
     """Backward of ONE application of RAFT's update block without its heads (csrc/update_backward.hip):
         cor = relu(convc2(relu(convc1(corr)))); flo = relu(convf2(relu(convf1(flow)))); m = relu(conv([cor | flo])); x = [inp | m | flow]
         per half (1x5, then 5x1): z = s(convz([h | x])), r = s(convr([h | x])), q = tanh(convq([r h | x])), h <- (1 - z) h + z q
     hx (b,256,h8,w8): the step's entry state (h_{k-1} | motion slot | flow_k) in the workspace's layout -- the motion slot is not read;
     inp (b,128,h8,w8); corr (b,324,h8,w8): the looked-up window; d_net (b,128,h8,w8) = d loss / d net_k; params: the 22 tensors of
-    UPDATE_PARAMS.  corr and flow are constants (upstream detaches coords1 at the top of the iteration): no gradient is formed into them.
-    -> (d_net_prev, d_inp, grads) with grads in UPDATE_PARAMS' order.  Every intermediate is recomputed here with the forward's kernels on
+    UPDATE_PARAMS.  corr and flow are constants (upstream detaches coords1 at the top of the iteration): no gradient is formed into the flow,
+    and none into corr unless asked for.
+    -> (d_net_prev, d_inp, grads) with grads in UPDATE_PARAMS' order; with ``ret_d_corr`` additionally d_corr (b,324,h8,w8) = d loss / d corr,
+    convc1's transposed 1x1 weight applied to the gradient in front of convc1's ReLU (conv_split, groups of UPDATE_GROUP_1X1 channels added
+    in f64): what ops.corr_lookup_backward accumulates.  Without the flag the launches and the results are those of a call without it.  Every intermediate is recomputed here with the forward's kernels on
     groups of input channels added in f64 (conv_split), which also compute the data gradients; the gradients that reach a tensor by several
     paths are added in that same f64 sum.  f32 throughout, bit-identical from run to run, a row's result independent of its batch."""
     who = 'update_step_backward'
@@ -1847,47 +1850,128 @@ def update_step_backward(hx, inp, corr, d_net, params):
         df1 = P.conv_split('f2t', dcat[:, 192:], P.w['f2t'], None, False, G3)
         relu_backward(df1, f1)
         grads['f1'] = conv_bwd_weight(flow, df1, (7, 7))
+        d_corr = P.conv_split('c1t', dc1, P.w['c1t'], None, False, G1) if ret_d_corr else None
     order = ('z1', 'r1', 'q1', 'z2', 'r2', 'q2', 'c1', 'c2', 'f1', 'f2', 'cv')
-    return d_net_prev, d_inp, tuple(t for name in order for t in grads[name])
+    out = (d_net_prev, d_inp, tuple(t for name in order for t in grads[name]))
+    return out + (d_corr,) if ret_d_corr else out
+
+
+# ------------------------------------------------------------------------------------------------- backward of the correlation
+def corr_grad_levels(h8, w8, levels=4):
+    """[(h_l, w_l)] of the pyramid's levels (h8 >> l, w8 >> l): a row of the gradient volume G holds them one after the other."""
+    return [(h8 >> l, w8 >> l) for l in range(levels)]
+
+
+def corr_grad_volume(b, h8, w8, levels=4, device='cuda'):
+    """The zero-filled gradient volume G (b, h8 w8, S), S = sum_l h_l w_l, of ops.corr_lookup_backward / corr_build_backward: d loss / d pyramid,
+    row p = the levels' maps of query p one after the other, each row-major.  S h8 w8 4 bytes per pair: 139 MB at 640 x 512, 2.2 GB at
+    1280 x 1024."""
+    n = lib().rpe_corr_grad_volume_floats(b, h8, w8, levels)
+    if n == 0:
+        raise _lib.RpeError(f'corr_grad_volume: unsupported geometry ({b} x {h8} x {w8}, {levels} levels: every level must be at least 2 x 2)')
+    return torch.zeros(b, h8 * w8, n // (b * h8 * w8), dtype=torch.float32, device=device)
+
+
+def _grad_volume(who, G, b, h8, w8, levels):
+    n = lib().rpe_corr_grad_volume_floats(b, h8, w8, levels)
+    if n == 0:
+        raise _lib.RpeError(f'{who}: unsupported geometry ({b} x {h8} x {w8}, {levels} levels: every level must be at least 2 x 2)')
+    if not (_is_f32(G) and tuple(G.shape) == (b, h8 * w8, n // (b * h8 * w8))):
+        raise _lib.RpeError(f'{who}: G must be a contiguous float32 ({b},{h8 * w8},{n // (b * h8 * w8)}) GPU tensor (ops.corr_grad_volume)')
+    _on_current_device(G, f'{who}: G')
+
+
+def corr_lookup_backward(coords, d_corr, G, radius=4):
+    """rpe_corr_lookup_backward: G += the adjoint of one window lookup at ``coords`` (b,2,h8,w8) from ``d_corr`` (b, levels 81, h8, w8), the
+    gradient of the looked-up window (ops.update_step_backward's ``ret_d_corr``).  G: ops.corr_grad_volume's layout, zero-filled by the caller
+    before the first call; calls accumulate in stream order.  The forward's own taps and fractions, cells outside a level dropped; one wave
+    owns a query's row, no atomics: bit-identical from run to run, a row's bits independent of the batch.  Nothing goes into the coordinates
+    (upstream detaches them).  -> G."""
+    who = 'corr_lookup_backward'
+    co, dc = _nchw(coords, f'{who}: coords'), _nchw(d_corr, f'{who}: d_corr')
+    b, two, h8, w8 = co.shape
+    win2 = (2 * radius + 1) ** 2
+    levels = dc.shape[1] // win2
+    if two != 2 or radius != 4 or levels < 1 or tuple(dc.shape) != (b, levels * win2, h8, w8):
+        raise _lib.RpeError(f'{who}: coords must be (b,2,h8,w8) and d_corr (b, levels 81, h8, w8) of the same maps (radius 4)')
+    _grad_volume(who, G, b, h8, w8, levels)
+    check(lib().rpe_corr_lookup_backward(ptr(co), ptr(dc), b, h8, w8, levels, radius, ptr(G), stream_ptr()), 'rpe_corr_lookup_backward')
+    return G
+
+
+def corr_build_backward(G, fmap1, fmap2, levels=4, ret_df2cat=False):
+    """rpe_corr_build_backward: (d_fmap1, d_fmap2), each (b,c,h8,w8), of the pyramid build from the gradient volume G (ops.corr_grad_volume's
+    layout) and the f32 feature maps the pass correlated.  Pooling is linear, so with F2cat (c x S) = fmap2 followed by its 2x2-pooled copies
+    (floor): d_fmap1 = F2cat G^T / sqrt(c), dF2cat = fmap1 G / sqrt(c), and d_fmap2 = the pool adjoints of dF2cat's level blocks applied from
+    level 3 down to 0.  GEMMs on the f32 matrix cores, the contraction split by the shape alone and added in f64 in a second pass; no float
+    atomics, bit-identical from run to run, a row's bits independent of the batch.  c: a multiple of 4 up to 256.  ``ret_df2cat``: dF2cat
+    (b,c,S) as a third result.  Memory: G itself is S h8 w8 4 bytes per pair (139 MB at 640 x 512, 2.2 GB at 1280 x 1024)."""
+    who = 'corr_build_backward'
+    f1, f2 = _nchw(fmap1, f'{who}: fmap1'), _nchw(fmap2, f'{who}: fmap2')
+    b, c, h8, w8 = f1.shape
+    if f2.shape != f1.shape:
+        raise _lib.RpeError(f'{who}: fmap1 {tuple(f1.shape)} and fmap2 {tuple(f2.shape)} must have one shape')
+    _grad_volume(who, G, b, h8, w8, levels)
+    nws = lib().rpe_corr_build_backward_workspace_bytes(b, c, h8, w8, levels)
+    if nws == 0:
+        raise _lib.RpeError(f'{who}: unsupported shape (c = {c}: a multiple of 4 up to 256)')
+    ws = torch.empty(nws, dtype=torch.uint8, device=f1.device)
+    d1, d2 = torch.empty_like(f1), torch.empty_like(f2)
+    dcat = torch.empty(b, c, G.shape[2], dtype=torch.float32, device=f1.device) if ret_df2cat else None
+    check(lib().rpe_corr_build_backward(ptr(G), ptr(f1), ptr(f2), b, c, h8, w8, levels, ptr(d1), ptr(d2), ptr(dcat), ptr(ws), stream_ptr()),
+          'rpe_corr_build_backward')
+    return (d1, d2, dcat) if ret_df2cat else (d1, d2)
 
 
 class _RaftBpttFn(torch.autograd.Function):
     """k gradient-free RAFT passes run with ``grad_update`` as ONE autograd node: inputs k x (flow_up, hidden, flow_low, net_0, inp), the
-    eight head parameters and the 22 of UPDATE_PARAMS; outputs the k up-sampled flows unchanged.  ``saved[i]`` = (states, corr_of): the
+    eight head parameters and the 22 of UPDATE_PARAMS; outputs the k up-sampled flows unchanged.  With ``per`` = 7 (``grad_corr``) a pass
+    carries two more leaves, (..., fmap1, fmap2): every step also forms d_corr and accumulates it into the pass's gradient volume at the
+    saved coordinates (corr_lookup_backward, k = N .. 1), and after step 1 the build's adjoint runs once (corr_build_backward); everything
+    else is computed by the same launches as with ``per`` = 5.  ``saved[i]`` = (states, corr_of): the
     dense entry states (hx_k, coords1_k), k = 1 .. N, of pass i and a function k -> the window the pass looked up for states[k]
     (RAFT.corr_of; it holds the pyramid).  Backward, per pass in the order given: raft_tail_backward (d net_N), then update_step_backward for k = N .. 1; the parameter
     gradients are summed over the steps in descending k, then over the passes in the given order (a pass whose flow nothing
     differentiates is skipped): the sum's bits do not depend on the autograd engine's scheduling."""
 
     @staticmethod
-    def forward(ctx, k, saved, *tensors):
-        ctx.k, ctx.saved = k, saved
+    def forward(ctx, k, saved, per, *tensors):
+        ctx.k, ctx.saved, ctx.per = k, saved, per
         ctx.save_for_backward(*tensors)
         ctx.set_materialize_grads(False)
-        outs = tuple(tensors[5 * i].view_as(tensors[5 * i]) for i in range(k))
+        outs = tuple(tensors[per * i].view_as(tensors[per * i]) for i in range(k))
         return outs[0] if k == 1 else outs
 
     @staticmethod
     def backward(ctx, *grads):
-        t, k = ctx.saved_tensors, ctx.k
-        heads, upd = t[5 * k:5 * k + 8], t[5 * k + 8:]
+        t, k, per = ctx.saved_tensors, ctx.k, ctx.per
+        heads, upd = t[per * k:per * k + 8], t[per * k + 8:]
         totals, per_pass = None, []
         for i, g in enumerate(grads):
             if g is None:
-                per_pass += [None] * 5
+                per_pass += [None] * per
                 continue
-            hidden, low, inp = t[5 * i + 1].detach(), t[5 * i + 2], t[5 * i + 4].detach()
+            hidden, low, inp = t[per * i + 1].detach(), t[per * i + 2], t[per * i + 4].detach()
             d_net_n, pg = raft_tail_backward(hidden, low, g.contiguous(), heads[:4], heads[4:])
             states, corr_of = ctx.saved[i]
-            d, d_inp, ug = d_net_n, None, None
+            d, d_inp, ug, vol = d_net_n, None, None, None
             for step in reversed(range(len(states))):
-                d, di, sg = update_step_backward(states[step][0], inp, corr_of(step), d, upd)
+                r = update_step_backward(states[step][0], inp, corr_of(step), d, upd, ret_d_corr=per == 7)
+                d, di, sg = r[:3]
+                if per == 7:
+                    if vol is None:
+                        vol = corr_grad_volume(r[3].shape[0], *r[3].shape[2:], r[3].shape[1] // 81, device=r[3].device)
+                    corr_lookup_backward(states[step][1], r[3], vol)
                 d_inp = di if d_inp is None else d_inp + di
                 ug = list(sg) if ug is None else [a + b for a, b in zip(ug, sg)]
             both = list(pg) + (ug if ug is not None else [torch.zeros_like(p) for p in upd])
             totals = both if totals is None else [a + b for a, b in zip(totals, both)]
             per_pass += [None, d_net_n, None, d, d_inp]
-        return (None, None, *per_pass, *(totals if totals is not None else [None] * 30))
+            if per == 7:
+                f1, f2 = t[per * i + 5].detach(), t[per * i + 6].detach()
+                per_pass += list(corr_build_backward(vol, f1, f2, r[3].shape[1] // 81)) if vol is not None else [None, None]
+                vol = None                                              # (S h8 w8 4 bytes per pair: freed before the next pass)
+        return (None, None, None, *per_pass, *(totals if totals is not None else [None] * 30))
 
 
 def update_bptt_attach(passes, saved, fh_params, mask_params, update_params):
@@ -1895,8 +1979,14 @@ def update_bptt_attach(passes, saved, fh_params, mask_params, update_params):
     ``passes`` = [(flow_up, hidden, flow_low, net_0, inp), ...] with hidden, net_0 and inp leaves that require grad; ``saved`` = per pass
     (states, corr_of) as _RaftBpttFn describes -> the list of up-sampled flows (the same values), outputs of one autograd node.  After a
     backward: hidden.grad = d loss / d net_N, net_0.grad = d loss / d net_0, inp.grad = d loss / d inp (summed over the iterations, last
-    first), and the 30 parameters' .grad."""
+    first), and the 30 parameters' .grad.  Passes of SEVEN tensors, (..., fmap1, fmap2) with the two feature maps the pass correlated as leaf
+    copies that require grad (``grad_corr``): the backward goes on through the correlation -- fmap1.grad = d loss / d fmap1 and fmap2.grad
+    likewise, exact under upstream's detach of coords1 (the window is linear in the pyramid, the pyramid bilinear in the maps).  The pass's
+    gradient volume lives during its backward only: S h8 w8 4 bytes per pair, 139 MB at 640 x 512."""
+    per = {len(p) for p in passes}
+    if per not in ({5}, {7}):
+        raise _lib.RpeError('update_bptt_attach: every pass is (flow_up, hidden, flow_low, net_0, inp) or every pass has fmap1, fmap2 as well')
     flat = [x for p in passes for x in p]
     with torch.enable_grad():
-        out = _RaftBpttFn.apply(len(passes), list(saved), *flat, *fh_params, *mask_params, *update_params)
+        out = _RaftBpttFn.apply(len(passes), list(saved), per.pop(), *flat, *fh_params, *mask_params, *update_params)
     return [out] if len(passes) == 1 else list(out)

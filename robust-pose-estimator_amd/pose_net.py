@@ -62,13 +62,13 @@ class PoseNet(nn.Module):
         ``ret_cache`` additionally returns the encoder outputs of ``imagel`` for reuse by the next ``infer``.
         ``ret_tail`` additionally returns (hidden state, last 1/8 flow) of the pass: what the backward of RAFT's output heads reads; with
         ``save_states`` (needs ret_tail) the tuple goes on with what the update block's backward reads: the context encoder's output, the
-        pass's saved entry states and its pyramid (RAFT.pass_with_states)."""
+        pass's saved entry states, its pyramid (RAFT.pass_with_states) and the two feature maps it correlated."""
         n = imagel.shape[0]
         f, cn = (enc['f'], enc['c']) if enc is not None else self._encode_both((imagel, imager), imagel)
         more = ()
         if save_states:
             r, states, pyr = self.flow.pass_with_states((f[:n], f[n:]), cn, upsample=upsample)
-            more = (cn, states, pyr)
+            more = (cn, states, pyr, (f[:n], f[n:]))
         else:
             r = self.flow(None, None, upsample=upsample, fmaps=(f[:n], f[n:]), cnet=cn, **(dict(ret_lowres=True) if ret_tail else {}))
         flow = r[0][-1]
@@ -79,7 +79,8 @@ class PoseNet(nn.Module):
             return depth, flow, valid, dict(fmap=f[:n], cnet=cn)
         return depth, flow, valid
 
-    def forward(self, image1l, image2l, intrinsics, baseline, image1r, image2r, mask1=None, mask2=None, ret_confmap=False, ret_flows=False):
+    def forward(self, image1l, image2l, intrinsics, baseline, image1r, image2r, mask1=None, mask2=None, ret_confmap=False, ret_flows=False,
+                grad_corr=False):
         """The reference's TRAINING forward (core/pose/pose_net.py:28-58): both stereo depths, the temporal flow, the weight
         maps and the declarative pose layer -> (log-pose (n,6), depth1, depth2[, (w2d, w3d)]).  Gradients reach what the
         reference trains while the flow network is frozen (train.yaml: freeze_flow_steps; RAFT.eval() always): the two
@@ -100,14 +101,23 @@ class PoseNet(nn.Module):
         applications of the SepConvGRU and the motion encoder (ops.update_step_backward) -- all 30 update-block parameters get the pose
         loss's exact gradient under upstream's detach of coords1; the dict then gains 'net0' and 'inp', leaves per pass whose ``.grad`` is
         d loss / d net_0 and d loss / d inp.  The flows keep their ``.grad`` (retain_grad), and with ``ret_flows`` the returned dict gains 'hidden': {'time', 'stereo1',
-        'stereo2'}, leaves whose ``.grad`` is the tail's d loss / d net_N, plus the weight heads' input gradient for 'time'."""
+        'stereo2'}, leaves whose ``.grad`` is the tail's d loss / d net_N, plus the weight heads' input gradient for 'time'.
+        ``grad_corr`` (with ``ret_flows``): the call takes the update-block route whether or not the update block's parameters require grad,
+        and the node's backward goes on through the correlation (RAFT.forward's ``grad_corr``: csrc/corr_backward.hip): the dict gains
+        'fmap1' and 'fmap2', leaves per pass ('time', 'stereo1', 'stereo2') beside 'net0' and 'inp' -- copies of the rows of the feature maps
+        each pass correlated -- whose ``.grad`` is d loss / d fmap: what a backward of the feature encoder has to be handed.  Pose, depths
+        and every other gradient keep their bits.  Refused before any launch with alternate_corr."""
         n = image1l.shape[0]
         intrinsics = intrinsics.expand(n, 3, 3).contiguous()
         baseline = baseline.expand(n).contiguous()
-        grad_update = self.flow_update_trainable()
+        if grad_corr and not ret_flows:
+            raise ValueError('PoseNet.forward: grad_corr returns its leaves in the dict of ret_flows: it needs ret_flows=True')
+        grad_update = self.flow_update_trainable() or grad_corr
         grad_heads = self.flow_heads_trainable() or grad_update
         if grad_heads:
             self.flow.check_grad_heads()                       # (before anything is launched)
+        if grad_corr:
+            self.flow.check_grad_corr()
         with torch.no_grad():
             tail1 = None
             if grad_heads:
@@ -117,7 +127,7 @@ class PoseNet(nn.Module):
             mask1 = (mask1.bool() & valid1) if mask1 is not None else valid1
             mask2 = mask2.bool().clone() if mask2 is not None else torch.ones_like(valid1)
             s = self.stages(image1l, image2l, intrinsics, baseline, depth1, image2r, mask1, mask2, stereo_flow1, heads=False,
-                            grad_flows=ret_flows or grad_heads, tail1=tail1)
+                            grad_flows=ret_flows or grad_heads, tail1=tail1, grad_corr=grad_corr)
         if self.use_weights and self.train_heads_hip:
             # the heads' training route on hand-written kernels (csrc/unet_train.hip): the parts are read where they are (no torch.cat),
             # the Sigmoid modules' work is fused into the resize
@@ -138,6 +148,8 @@ class PoseNet(nn.Module):
                 flows['hidden'] = s['hidden_leaves']
             if grad_update:
                 flows['net0'], flows['inp'] = s['net0_leaves'], s['inp_leaves']
+            if grad_corr:
+                flows['fmap1'], flows['fmap2'] = s['fmap1_leaves'], s['fmap2_leaves']
             out = (*out, flows)
         return out
 
@@ -160,9 +172,10 @@ class PoseNet(nn.Module):
         stage's backward), through the backward of RAFT's last flow-head / mask-head application (csrc/raft_backward.hip) those heads'
         parameters -- ``freeze_flow(False, parts='heads')`` sets requires_grad on ``flow.update_block.flow_head`` and ``flow.update_block.mask``
         only --, and through the backward of the N update steps (csrc/update_backward.hip, ops.update_step_backward) the SepConvGRU and the
-        motion encoder -- ``freeze_flow(False, parts='update')`` sets it on all of ``flow.update_block``.  The two encoders and the correlation
-        (build and lookup) have no backward here: ``freeze_flow(False)`` without ``parts`` is refused instead of training against silently
-        missing gradients."""
+        motion encoder -- ``freeze_flow(False, parts='update')`` sets it on all of ``flow.update_block``.  The correlation has a backward as
+        well (csrc/corr_backward.hip; it has no parameters): ``forward(..., ret_flows=True, grad_corr=True)`` hands the gradient to the two
+        feature maps of every pass.  Only the two encoders have no backward here: ``freeze_flow(False)`` without ``parts`` is refused
+        instead of training against silently missing gradients."""
         if parts not in (None, 'heads', 'update'):
             raise ValueError(f"freeze_flow: parts must be None, 'heads' or 'update', got {parts!r}")
         if not freeze and parts == 'heads':
@@ -176,7 +189,8 @@ class PoseNet(nn.Module):
         if not freeze:
             raise NotImplementedError('training the whole flow network (freeze_flow(False)) is out of scope: the gradients stop at the flows '
                                       '(forward(..., ret_flows=True) returns them), at RAFT\'s output heads (parts=\'heads\') or at its update '
-                                      'block (parts=\'update\'); the encoders and the correlation have no backward here')
+                                      'block (parts=\'update\'), and through the correlation at the feature maps (grad_corr=True); the two '
+                                      'encoders have no backward here')
         for p in self.parameters():
             p.requires_grad = True
         for p in self.flow.parameters():
@@ -217,7 +231,7 @@ class PoseNet(nn.Module):
 
     @torch.no_grad()
     def stages(self, image1l, image2l, intrinsics, baseline, depth1, image2r, mask1, mask2, stereo_flow1, cache1=None, heads=True, enc2=None,
-               flow_init=None, ret_lowres=False, grad_flows=False, tail1=None):
+               flow_init=None, ret_lowres=False, grad_flows=False, tail1=None, grad_corr=False):
         """Every stage of infer() before the solve.  ``cache1`` = {'fmap','cnet'} of image1l from the previous call
         (streaming: frame t's image2l is frame t+1's image1l), so only the two new images are encoded -- or not even those when
         ``enc2`` = encode_frame(image2l, image2r) was computed ahead of the call (needs cache1).
@@ -229,7 +243,9 @@ class PoseNet(nn.Module):
         ``ops.geometry_stage``: the same values, now differentiable with respect to the three flows.
         ``tail1`` = (hidden, 1/8 flow) of the pass that made stereo_flow1 (flow2depth's ``ret_tail``; needs grad_flows): RAFT's output heads
         train -- the three flows leave one ops.raft_tail_attach node (time, stereo1, stereo2), 'hidden' is the temporal pairs' hidden state as a
-        leaf that requires grad, and 'hidden_leaves' = {'time', 'stereo1', 'stereo2'}."""
+        leaf that requires grad, and 'hidden_leaves' = {'time', 'stereo1', 'stereo2'}.
+        ``grad_corr`` (needs flow2depth's save_states in ``tail1``): the passes of the update block's node carry leaf copies of their rows of
+        the feature maps as well ('fmap1_leaves', 'fmap2_leaves'), and its backward goes on through the correlation."""
         n = image1l.shape[0]
         intrinsics = intrinsics.expand(n, 3, 3).contiguous()
         baseline = baseline.expand(n).contiguous()
@@ -274,7 +290,7 @@ class PoseNet(nn.Module):
                               (stereo_flow2, leaves['stereo2'], low[n:])]
                     if bptt:
                         c = hidden.shape[1]
-                        cn1, states1, pyr1 = tail1[2:]
+                        cn1, states1, pyr1, fm1 = tail1[2:]
                         rows = dict(time=(cn, 0, n), stereo1=(cn1, 0, n), stereo2=(cn, n, 2 * n))
                         net0 = {k: t[lo:hi, :c].clone().requires_grad_(True) for k, (t, lo, hi) in rows.items()}
                         inp = {k: t[lo:hi, c:].clone().requires_grad_(True) for k, (t, lo, hi) in rows.items()}
@@ -282,6 +298,11 @@ class PoseNet(nn.Module):
                         saved = [([(st[:n], co[:n]) for st, co in states2], corr_of(pyr2, states2, (0, n))), (states1, corr_of(pyr1, states1)),
                                  ([(st[n:], co[n:]) for st, co in states2], corr_of(pyr2, states2, (n, 2 * n)))]
                         passes = [p + (net0[k], inp[k]) for p, k in zip(passes, ('time', 'stereo1', 'stereo2'))]
+                        if grad_corr:                          # rows of the batched pass's maps are slices, as corr_of(rows=) slices the window
+                            frows = dict(time=(fmaps, 0, n), stereo1=(fm1, 0, n), stereo2=(fmaps, n, 2 * n))
+                            fleaf = [{k: t[j][lo:hi].float().clone(memory_format=torch.contiguous_format).requires_grad_(True)
+                                      for k, (t, lo, hi) in frows.items()} for j in (0, 1)]
+                            passes = [p + (fleaf[0][k], fleaf[1][k]) for p, k in zip(passes, ('time', 'stereo1', 'stereo2'))]
                         time_flow, stereo_flow1, stereo_flow2 = ops.update_bptt_attach(passes, saved, fh, mk, self.flow.update_params())
                     else:
                         time_flow, stereo_flow1, stereo_flow2 = ops.raft_tail_attach(passes, fh, mk)
@@ -302,6 +323,8 @@ class PoseNet(nn.Module):
             g['hidden_leaves'] = leaves
             if bptt:
                 g['net0_leaves'], g['inp_leaves'] = net0, inp
+                if grad_corr:
+                    g['fmap1_leaves'], g['fmap2_leaves'] = fleaf
         if ret_lowres:
             g['time_flow_low'] = g['cache2']['time_flow_low'] = r[3][:n]
         return g

@@ -1226,9 +1226,18 @@ class RAFT(nn.Module):
         if not upsample:
             raise RpeError('RAFT: grad_heads attaches to the up-sampled prediction: it needs upsample=True')
 
+    def check_grad_corr(self):
+        """The refusals of ``grad_corr`` beyond check_grad_heads' (raised before anything is launched): the correlation's backward
+        differentiates the f32 pyramid; ``alternate_corr`` has no pyramid, and CORR_BF16X3 does not form f32 products."""
+        route = self._route()
+        if route.alternate_corr:
+            raise RpeError('RAFT: grad_corr differentiates the correlation pyramid -- not with alternate_corr (no pyramid is built)')
+        if CORR_BF16X3:
+            raise RpeError('RAFT: grad_corr is f32 only -- not with CORR_BF16X3')
+
     @torch.no_grad()
     def forward(self, image1, image2, upsample=True, iters=None, all_flows=False, fmaps=None, cnet=None, flow_init=None, ret_lowres=False,
-                grad_heads=False, grad_update=False, _states=None):
+                grad_heads=False, grad_update=False, grad_corr=False, _states=None, _fmaps=None):
         """image1, image2: (N,3,H,W) in 0..255.  Inference only (the reference freezes RAFT, train.yaml:51).
         ``fmaps`` / ``cnet`` accept encoder outputs computed elsewhere (both encoders normalise per sample -- instance
         norm / frozen batch norm -- so a caller may encode every distinct image once and reuse it); with both given the
@@ -1250,21 +1259,32 @@ class RAFT(nn.Module):
         whose backward is the tail's, then ops.update_step_backward for k = N .. 1: the exact gradient of all 30 update-block parameters
         under upstream's detach of coords1 (the only path through time is the hidden state).  ``hidden`` is a leaf as under grad_heads; two
         more elements are appended to the result, the leaves ``net_0`` (N,128,h8,w8) and ``inp`` (a leaf copy of the context), whose .grad are
-        d loss / d net_0 and d loss / d inp summed over the iterations.  The same refusals as grad_heads, before any launch."""
-        if grad_update:
+        d loss / d net_0 and d loss / d inp summed over the iterations.  The same refusals as grad_heads, before any launch.
+        ``grad_corr`` (implies grad_update): the node's backward goes on through the correlation -- every step also forms d corr_k
+        (convc1's adjoint), accumulates it at the saved coords1_k into the pass's gradient volume G = d loss / d pyramid (the lookup's
+        adjoint; S h8 w8 4 bytes per pair, S = the cells of the four levels: 139 MB at 640 x 512, 2.2 GB at 1280 x 1024, alive during the
+        backward only), and after step 1 the build's adjoint runs once (csrc/corr_backward.hip).  Two more leaves are appended behind
+        ``inp``: ``fmap1`` and ``fmap2``, copies of the maps the pass correlated, whose .grad is d loss / d fmap -- exact under upstream's
+        detach of coords1 (the window is linear in the pyramid, the pyramid bilinear in the maps; nothing goes into the coordinates).
+        Everything grad_update returns, and every gradient it forms, keeps its bits.  Refused, before any launch, with what grad_heads
+        refuses and with alternate_corr and CORR_BF16X3 (check_grad_corr)."""
+        if grad_update or grad_corr:
             self.check_grad_heads(upsample)
-            states = []
+            if grad_corr:
+                self.check_grad_corr()
+            states, fm = [], ([] if grad_corr else None)
             flows, hidden, context, low = self.forward(image1, image2, upsample, iters, all_flows, fmaps, cnet, flow_init, ret_lowres=True,
-                                                       _states=states)
+                                                       _states=states, _fmaps=fm)
             pyr, self._pyr = self._pyr, None                   # the node's from here on
             c = self.hidden_dim
             net0 = ops.copy_planes(states[0][0][:, :c], torch.empty_like(hidden)) if states else hidden.clone()
             inp = context.clone()
-            for t in (hidden, net0, inp):
+            leaves = (net0, inp) + (tuple(f.float().clone(memory_format=torch.contiguous_format) for f in fm) if grad_corr else ())
+            for t in (hidden,) + leaves:
                 t.requires_grad_(True)
-            flows[-1] = ops.update_bptt_attach([(flows[-1], hidden, low, net0, inp)], [(states, self.corr_of(pyr, states))], *self.head_params(),
+            flows[-1] = ops.update_bptt_attach([(flows[-1], hidden, low) + leaves], [(states, self.corr_of(pyr, states))], *self.head_params(),
                                                self.update_params())[0]
-            return (flows, hidden, context) + ((low,) if ret_lowres else ()) + (net0, inp)
+            return (flows, hidden, context) + ((low,) if ret_lowres else ()) + leaves
         if grad_heads:
             self.check_grad_heads(upsample)
             flows, hidden, context, low = self.forward(image1, image2, upsample, iters, all_flows, fmaps, cnet, flow_init, ret_lowres=True)
@@ -1284,6 +1304,8 @@ class RAFT(nn.Module):
             fmap1, fmap2 = f[:N], f[N:]
         else:
             fmap1, fmap2 = fmaps                              # precomputed by encode_features (caller de-duplicates)
+        if _fmaps is not None:                                # (grad_corr: what the pass correlates)
+            _fmaps.extend((fmap1, fmap2))
         if cnet is None:
             cnet = self._encode(self.cnet, image1, route, split_act=True)       # (tanh(net) | relu(inp))
         c = self.hidden_dim
