@@ -9,6 +9,7 @@ Layout:
   se3.py              lietorch-style SE3 value type on the rpe_se3_* kernels
   raft.py, unet.py    RAFT / TinyUNet host mirrors (convolutions on PyTorch-ROCm, correlation / gates /
                       up-sampling in HIP)
+  raft_grad.py        RAFT's training backward: the stage functions, a pass's record (GradPass) and the one autograd node over them
   pose_head.py        DPoseSE3Head / DeclarativeLayerLie mirrors on rpe_pose_solve
   pose_net.py         PoseNet.infer / flow2depth mirror
   pose_estimator.py   frame-to-frame tracker mirror (+ Frame), SurfelPoseEstimator (frame to model), MultiSurfelPoseEstimator (K sequences), from_config

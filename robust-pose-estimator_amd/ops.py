@@ -212,6 +212,19 @@ def _f32(t, name, shape=None, numel=None):
     return t
 
 
+def bounded_put(cache, key, value, keep=2):
+    """Insert into a small insertion-ordered cache, evicting the oldest entries (and the buffers / launch descriptors they pin)."""
+    while len(cache) >= keep:
+        cache.pop(next(iter(cache)))
+    cache[key] = value
+
+
+def wkey(*tensors):
+    """Cache key of what is made from ``tensors`` (None = absent, and stays None in its place): an in-place update bumps the version,
+    .to() / .float() move the data, and a replaced Parameter is another tensor."""
+    return tuple(None if t is None else (t._version, t.data_ptr()) for t in tensors)
+
+
 def _mask(t, name):
     t = _dev(t, None, name)
     if t.dtype == torch.bool:
@@ -1447,6 +1460,7 @@ def unet_train_grad_offsets(cin):
 
 
 # ------------------------------------------------------------------------------------------------- backward of RAFT's output heads
+# (this and the next two sections: one kernel per wrapper; raft_grad.py composes them into the tail's, the update step's and the pass's backward)
 def upsample_convex_backward(grad_up, flow, mask):
     """rpe_upsample_convex_backward: (d_flow (b,2,h8,w8), d_mask (b,576,h8,w8)) of ``upsample_convex(flow, mask)`` from grad_up
     (b,2,8 h8,8 w8); ``mask`` = the logits as the forward read them.  Bit-identical from run to run."""
@@ -1515,14 +1529,6 @@ def relu_backward(grad, act, out=None):
     return out
 
 
-def _wkey(*tensors):
-    """Cache key of what is packed from ``tensors``: an in-place update bumps the version, a move or a replaced Parameter changes the pointer."""
-    return tuple((t._version, t.data_ptr()) for t in tensors)
-
-
-_TAIL_PACKED = {}          # _wkey of the eight head parameters -> the packings raft_tail_backward made from them (the two newest weight sets)
-
-
 def sum_groups(parts, bias=None, relu=False, out=None):
     """rpe_sum_groups: act(sum_g parts[g] + bias[c]) for parts (groups,b,c,h,w), added in group order in f64 -> (b,c,h,w) (``out`` may be a
     channel slice)."""
@@ -1539,139 +1545,6 @@ def sum_groups(parts, bias=None, relu=False, out=None):
     op, obs = _chan_slice(out, 'sum_groups: out')
     check(lib().rpe_sum_groups(ptr(parts), groups, b, c, hh * ww, ptr(bias), int(bool(relu)), op, obs, stream_ptr()), 'rpe_sum_groups')
     return out
-
-
-TAIL_GROUP_3X3_FWD, TAIL_GROUP_3X3_BWD, TAIL_GROUP_1X1 = 16, 32, 64      # input channels per launch of the tail's forward-kernel convolutions
-
-
-class _TailPacked:
-    """What raft_tail_backward packs from the eight head parameters, each made on first use.  Forward: the two 3x3 layers that read ``net``
-    stacked along their OUTPUT channels (one launch computes t_f and t_m) and the mask head's 1x1 (x 0.25, as RAFT's forward folds it).  Data
-    gradients: the TRANSPOSED, FLIPPED weights -- dX = conv(dY; W^T flipped) is a forward convolution --, the two 256 -> 128 3x3 layers
-    stacked along their INPUT channels (the launches compute the sum of both data gradients) and the 576 -> 256 1x1 layer (x 0.25).
-    Every one of them runs through conv_split: the forward kernels on groups of input channels, the groups added in f64."""
-
-    def __init__(self, fh, mk):
-        self.fh, self.mk, self._made = [t.detach() for t in fh], [t.detach() for t in mk], {}
-        self.w3, self.b3 = torch.cat((self.fh[0], self.mk[0]), dim=0).contiguous(), torch.cat((self.fh[1], self.mk[1]), dim=0).contiguous()
-        self.w3t = torch.cat((self.fh[0].transpose(0, 1).flip(2, 3), self.mk[0].transpose(0, 1).flip(2, 3)), dim=1).contiguous()
-        self.w1, self.b1 = (0.25 * self.mk[2]).contiguous(), (0.25 * self.mk[3]).contiguous()
-        self.w1t = (0.25 * self.mk[2]).transpose(0, 1).contiguous()
-
-    def get(self, name, make):
-        if name not in self._made:
-            self._made[name] = make()
-        return self._made[name]
-
-    def conv_split(self, name, x, weight, bias, relu, group, out=None, extra=0, fill=None):
-        """act(conv(x; weight) + bias), stride 1, 'same', 3x3, 1x1, 1x5 or 5x1, on the forward's kernels -- rpe_conv_fused where the map is one it takes
-        (rows of whole 16-byte quads), ops.conv_direct at every other size -- run on ``group`` input channels at a time and the groups' results
-        added in f64 (sum_groups).  Those kernels add their products in one k-ordered f32 chain: over all 1152 / 4608 terms of the tail's
-        layers its error is 3-5 times that of a blocked float32 sum, over a group's 144-288 terms it is not."""
-        b, cin, hh, ww = x.shape
-        cout, kh, kw = weight.shape[0], weight.shape[2], weight.shape[3]
-        bounds = [(lo, min(cin, lo + group)) for lo in range(0, cin, group)]
-        # ``extra``: that many more (b,cout,h,w) terms of the f64 sum behind the groups' results; ``fill(terms)`` writes them (the update
-        # block's backward adds the gradients that reach the same tensor by other paths there, instead of in f32 afterwards)
-        allp = torch.empty(len(bounds) + extra, b, cout, hh, ww, dtype=torch.float32, device=x.device)
-        parts = allp[:len(bounds)]
-        if extra:
-            fill(allp[len(bounds):])
-        fused = ww % 4 == 0 and x.data_ptr() % 16 == 0 and x.stride(0) % 4 == 0
-        for gi, (lo, hi) in enumerate(bounds):
-            wg = self.get((name, gi, 'w'), lambda: weight[:, lo:hi].contiguous())
-            if fused:
-                conv_fused(x[:, lo:hi], self.get((name, gi, 'packed'), lambda: PackedConv(wg, None)), CONV_LINEAR, parts[gi])
-            else:
-                conv_direct(x[:, lo:hi], wg, None, 1, (kh // 2, kw // 2), out=parts[gi])
-        return sum_groups(parts if extra == 0 else allp, bias, relu, out)
-
-
-def _tail_packed(fh_params, mask_params):
-    key = _wkey(*fh_params, *mask_params)
-    if key not in _TAIL_PACKED:
-        while len(_TAIL_PACKED) >= 2:
-            _TAIL_PACKED.pop(next(iter(_TAIL_PACKED)))
-        _TAIL_PACKED[key] = _TailPacked(fh_params, mask_params)
-    return _TAIL_PACKED[key]
-
-
-def raft_tail_backward(net, flow_low, grad_up, fh_params, mask_params):
-    """Backward of the tail of RAFT's last update iteration (csrc/raft_backward.hip):
-        t_f = relu(conv3x3(net; fh.conv1)); delta = conv3x3(t_f; fh.conv2); t_m = relu(conv3x3(net; mask.0)); m = .25 conv1x1(t_m; mask.2)
-        flow_up = upsample_convex(flow_prev + delta, m)
-    net (b,128,h8,w8): the returned hidden state; flow_low (b,2,h8,w8) = flow_prev + delta, the pass's last 1/8 flow (``ret_lowres``; d / d delta
-    = d / d flow_low, so flow_prev is not needed); grad_up (b,2,8 h8,8 w8); fh_params = (conv1.weight, conv1.bias, conv2.weight, conv2.bias)
-    of the flow head, mask_params = (mask.0.weight, mask.0.bias, mask.2.weight, mask.2.bias).
-    -> (d_net, (the eight parameter gradients in that order)).  t_f, t_m and m are recomputed from ``net`` with the forward's kernels
-    (nothing is kept by the forward pass), which also compute the data gradients; each runs on groups of input channels whose results
-    are added in f64 (_TailPacked.conv_split).  f32 throughout, bit-identical from run to run."""
-    net, fl, gu = _nchw(net, 'raft_tail_backward: net'), _nchw(flow_low, 'raft_tail_backward: flow_low'), _nchw(grad_up, 'raft_tail_backward: grad_up')
-    fh, mk = tuple(fh_params), tuple(mask_params)
-    b, c, hh, ww = net.shape
-    for t in fh + mk:
-        _nchw(t.detach(), 'raft_tail_backward: a head parameter')
-    hid = fh[0].shape[0]
-    if len(fh) != 4 or len(mk) != 4 or tuple(fh[0].shape) != (hid, c, 3, 3) or tuple(fh[2].shape) != (2, hid, 3, 3) \
-            or tuple(mk[0].shape) != (hid, c, 3, 3) or tuple(mk[2].shape) != (576, hid, 1, 1):
-        raise _lib.RpeError('raft_tail_backward: expected the flow head\'s (h,c,3,3), (2,h,3,3) and the mask head\'s (h,c,3,3), (576,h,1,1) weights')
-    if tuple(fl.shape) != (b, 2, hh, ww) or tuple(gu.shape) != (b, 2, 8 * hh, 8 * ww):
-        raise _lib.RpeError('raft_tail_backward: flow_low must be (b,2,h8,w8) and grad_up (b,2,8 h8,8 w8) for net (b,c,h8,w8)')
-    P = _tail_packed(fh, mk)
-    with torch.no_grad():
-        # the forward, again
-        t = P.conv_split('w3', net, P.w3, P.b3, True, TAIL_GROUP_3X3_FWD)              # (t_f | t_m): both layers read net
-        t_f, t_m = t[:, :hid], t[:, hid:]
-        m = P.conv_split('w1', t_m, P.w1, P.b1, False, TAIL_GROUP_1X1)
-        # the adjoints, last layer first
-        d_flow, d_m = upsample_convex_backward(gu, fl, m)
-        g = torch.empty(b, 2 * hid, hh, ww, dtype=torch.float32, device=net.device)       # (d t_f | d t_m) in front of their ReLUs
-        dw_fh2, db_fh2 = conv_bwd_weight(t_f, d_flow, (3, 3))
-        conv3x3_to2_bwd_data(d_flow, P.fh[2], act=t_f, out=g[:, :hid])
-        dw_m2, db_m2 = conv_bwd_weight(t_m, d_m, (1, 1), scale=0.25)
-        P.conv_split('w1t', d_m, P.w1t, None, False, TAIL_GROUP_1X1, out=g[:, hid:])
-        relu_backward(g[:, hid:], t_m)
-        dw1, db1 = conv_bwd_weight(net, g, (3, 3))                      # both 3x3 layers read net: one GEMM of 2 * hid output channels
-        d_net = P.conv_split('w3t', g, P.w3t, None, False, TAIL_GROUP_3X3_BWD)
-    return d_net, (dw1[:hid], db1[:hid], dw_fh2, db_fh2, dw1[hid:], db1[hid:], dw_m2, db_m2)
-
-
-class _RaftTailFn(torch.autograd.Function):
-    """The tails of k gradient-free RAFT passes as ONE autograd node: inputs k x (flow_up, hidden, flow_low) and the eight head parameters,
-    outputs the k up-sampled flows unchanged.  Backward = raft_tail_backward per pass, in the order the passes were given; the parameter
-    gradients are summed in that order (a pass whose flow nothing differentiates is skipped), so the sum's bits do not depend on the
-    autograd engine's scheduling."""
-
-    @staticmethod
-    def forward(ctx, k, *tensors):
-        ctx.k = k
-        ctx.save_for_backward(*tensors)
-        ctx.set_materialize_grads(False)
-        outs = tuple(tensors[3 * i].view_as(tensors[3 * i]) for i in range(k))
-        return outs[0] if k == 1 else outs
-
-    @staticmethod
-    def backward(ctx, *grads):
-        t, k = ctx.saved_tensors, ctx.k
-        params = t[3 * k:]
-        total, d_nets = None, [None] * k
-        for i, g in enumerate(grads):
-            if g is None:
-                continue
-            d_nets[i], pg = raft_tail_backward(t[3 * i + 1].detach(), t[3 * i + 2], g.contiguous(), params[:4], params[4:])
-            total = list(pg) if total is None else [a + b for a, b in zip(total, pg)]
-        per_pass = [x for i in range(k) for x in (None, d_nets[i], None)]
-        return (None, *per_pass, *(total if total is not None else [None] * 8))
-
-
-def raft_tail_attach(passes, fh_params, mask_params):
-    """Attach the tail's backward to the results of gradient-free RAFT passes: ``passes`` = [(flow_up, hidden, flow_low), ...] with hidden a
-    leaf that requires grad -> the list of up-sampled flows (the same values), outputs of one autograd node whose backward is
-    ``raft_tail_backward`` per pass and whose inputs are the hidden states and the eight parameters."""
-    flat = [x for p in passes for x in p]
-    with torch.enable_grad():
-        out = _RaftTailFn.apply(len(passes), *flat, *fh_params, *mask_params)
-    return [out] if len(passes) == 1 else list(out)
 
 
 # ------------------------------------------------------------------------------------------------- backward of RAFT's update block
@@ -1722,140 +1595,6 @@ def gru_gates_r_backward(d_rh, h, r, d_h_in, d_r_pre, d_h_out):
     return d_r_pre, d_h_out
 
 
-# ops.update_step_backward's parameter (and gradient) order: weight, bias of each -- 12 tensors of ``gru``, 10 of ``encoder``
-UPDATE_PARAMS = tuple(f'{m}.{t}' for m in ('gru.convz1', 'gru.convr1', 'gru.convq1', 'gru.convz2', 'gru.convr2', 'gru.convq2', 'encoder.convc1',
-                                           'encoder.convc2', 'encoder.convf1', 'encoder.convf2', 'encoder.conv') for t in ('weight', 'bias'))
-# input channels per launch of the step's forward-kernel convolutions (forward recomputation and data gradients alike): 144 terms of a 3x3
-# layer, 160 of a 5-tap layer, 64 of the 1x1 -- the k-ordered f32 chain of a launch stays below the tail's 288, the groups are added in f64
-UPDATE_GROUP_3X3, UPDATE_GROUP_5TAP, UPDATE_GROUP_1X1 = 16, 32, 64
-_UPDATE_PACKED = {}        # _wkey of the 22 parameters -> _UpdatePacked (the two newest weight sets)
-
-
-class _UpdatePacked(_TailPacked):
-    """What update_step_backward packs from the 22 parameters, each group's packing made on first use (_TailPacked.get / conv_split).
-    Forward: convz | convr of a half stacked along their OUTPUT channels, as the forward stacks them (gate_weights), in upstream's input
-    order [h | inp | motion | flow].  Data gradients: the TRANSPOSED, FLIPPED weights, zr stacked along its INPUT channels."""
-
-    def __init__(self, params):
-        p = [t.detach() for t in params]
-        self._made = {}
-        self.w = {name: (p[2 * i], p[2 * i + 1]) for i, name in enumerate(('z1', 'r1', 'q1', 'z2', 'r2', 'q2', 'c1', 'c2', 'f1', 'f2', 'cv'))}
-        tr = lambda w: w.transpose(0, 1).flip(2, 3)
-        for hf in ('1', '2'):
-            wz, bz = self.w['z' + hf]
-            wr, br = self.w['r' + hf]
-            self.w['zr' + hf] = (torch.cat((wz, wr), 0).contiguous(), torch.cat((bz, br), 0).contiguous())
-            self.w['zr' + hf + 't'] = torch.cat((tr(wz), tr(wr)), 1).contiguous()
-            self.w['q' + hf + 't'] = tr(self.w['q' + hf][0]).contiguous()
-        for name in ('c1', 'c2', 'f2', 'cv'):
-            self.w[name + 't'] = tr(self.w[name][0]).contiguous()
-
-
-def _update_packed(params):
-    key = _wkey(*params)
-    if key not in _UPDATE_PACKED:
-        while len(_UPDATE_PACKED) >= 2:
-            _UPDATE_PACKED.pop(next(iter(_UPDATE_PACKED)))
-        _UPDATE_PACKED[key] = _UpdatePacked(params)
-    return _UPDATE_PACKED[key]
-
-
-def update_step_backward(hx, inp, corr, d_net, params, ret_d_corr=False):
-    """Backward of ONE application of RAFT's update block without its heads (csrc/update_backward.hip):
-        cor = relu(convc2(relu(convc1(corr)))); flo = relu(convf2(relu(convf1(flow)))); m = relu(conv([cor | flo])); x = [inp | m | flow]
-        per half (1x5, then 5x1): z = s(convz([h | x])), r = s(convr([h | x])), q = tanh(convq([r h | x])), h <- (1 - z) h + z q
-    hx (b,256,h8,w8): the step's entry state (h_{k-1} | motion slot | flow_k) in the workspace's layout -- the motion slot is not read;
-    inp (b,128,h8,w8); corr (b,324,h8,w8): the looked-up window; d_net (b,128,h8,w8) = d loss / d net_k; params: the 22 tensors of
-    UPDATE_PARAMS.  corr and flow are constants (upstream detaches coords1 at the top of the iteration): no gradient is formed into the flow,
-    and none into corr unless asked for.
-    -> (d_net_prev, d_inp, grads) with grads in UPDATE_PARAMS' order; with ``ret_d_corr`` additionally d_corr (b,324,h8,w8) = d loss / d corr,
-    convc1's transposed 1x1 weight applied to the gradient in front of convc1's ReLU (conv_split, groups of UPDATE_GROUP_1X1 channels added
-    in f64): what ops.corr_lookup_backward accumulates.  Without the flag the launches and the results are those of a call without it.  Every intermediate is recomputed here with the forward's kernels on
-    groups of input channels added in f64 (conv_split), which also compute the data gradients; the gradients that reach a tensor by several
-    paths are added in that same f64 sum.  f32 throughout, bit-identical from run to run, a row's result independent of its batch."""
-    who = 'update_step_backward'
-    hx, inp, corr, d_net = _nchw(hx, f'{who}: hx'), _nchw(inp, f'{who}: inp'), _nchw(corr, f'{who}: corr'), _nchw(d_net, f'{who}: d_net')
-    params = tuple(params)
-    b, c2, hh, ww = hx.shape
-    c = c2 // 2
-    for t in params:
-        _nchw(t.detach(), f'{who}: a parameter')
-    want = [(c, 3 * c, 1, 5)] * 3 + [(c, 3 * c, 5, 1)] * 3 + [(256, corr.shape[1], 1, 1), (192, 256, 3, 3), (128, 2, 7, 7), (64, 128, 3, 3), (c - 2, 256, 3, 3)]
-    if len(params) != 22 or c != 128 or any(tuple(params[2 * i].shape) != s or tuple(params[2 * i + 1].shape) != s[:1] for i, s in enumerate(want)):
-        raise _lib.RpeError(f'{who}: expected the 22 tensors of UPDATE_PARAMS (SepConvGRU and BasicMotionEncoder of hidden size 128) and hx with 256 channels')
-    if tuple(inp.shape) != (b, c, hh, ww) or tuple(d_net.shape) != (b, c, hh, ww) or tuple(corr.shape[::2]) != (b, hh) or corr.shape[3] != ww:
-        raise _lib.RpeError(f'{who}: inp and d_net must be ({b},{c},{hh},{ww}) and corr (b,324,h8,w8) for hx {tuple(hx.shape)}')
-    P = _update_packed(params)
-    G3, G5, G1 = UPDATE_GROUP_3X3, UPDATE_GROUP_5TAP, UPDATE_GROUP_1X1
-    new = lambda ch: torch.empty(b, ch, hh, ww, dtype=torch.float32, device=hx.device)
-    with torch.no_grad():
-        flow = hx[:, 2 * c - 2:]
-        # the motion encoder, again
-        c1 = P.conv_split('c1', corr, *P.w['c1'], True, G1)
-        cat = new(256)                                                  # (cor | flo)
-        P.conv_split('c2', c1, *P.w['c2'], True, G3, out=cat[:, :192])
-        f1 = conv_direct(flow, *P.w['f1'], 1, 3, relu=True)              # 2 -> 128, 7x7: 98 terms
-        P.conv_split('f2', f1, *P.w['f2'], True, G3, out=cat[:, 192:])
-        # the GRU's two halves, again: A = [h | inp | m | flow] (upstream's order), R = [r h | inp | m | flow]
-        A1, R1, A2, R2 = new(3 * c), new(3 * c), new(3 * c), new(3 * c)
-        copy_planes(hx[:, :c], A1[:, :c])
-        copy_planes(inp, A1[:, c:2 * c])
-        P.conv_split('cv', cat, *P.w['cv'], True, G3, out=A1[:, 2 * c:3 * c - 2])
-        copy_planes(flow, A1[:, 3 * c - 2:])
-        z, r, q = (new(c), new(c)), (new(c), new(c)), (new(c), new(c))
-        for i, (A, R, nxt) in enumerate(((A1, R1, A2), (A2, R2, None))):
-            hf = '12'[i]
-            copy_planes(A[:, c:], R[:, c:])
-            if nxt is not None:
-                copy_planes(A[:, c:], nxt[:, c:])
-            zr_pre = P.conv_split('zr' + hf, A, *P.w['zr' + hf], False, G5)
-            gru_gates_zr_recompute(zr_pre, A[:, :c], z[i], r[i], R[:, :c])
-            q_pre = P.conv_split('q' + hf, R, *P.w['q' + hf], False, G5)
-            gru_gates_h_recompute(q_pre, z[i], A[:, :c], q[i], nxt[:, :c] if nxt is not None else new(c))      # (net_k itself is not needed again)
-        # the adjoints, second half first.  T = [d h_old | d x] of a half: first convq's data gradient ([d (r h) | d x]), then, with the
-        # gates' terms written over its first c channels, one more term of the f64 sum behind convz | convr's data gradient
-        grads, d, carry = {}, d_net, None
-        for i, (A, R) in ((1, (A2, R2)), (0, (A1, R1))):
-            hf = '12'[i]
-            kernel = (1, 5) if i == 0 else (5, 1)
-            dzr, dq, dh = new(2 * c), new(c), new(c)
-            gru_gates_zq_backward(d, A[:, :c], z[i], q[i], dzr[:, :c], dq, dh)
-            grads['q' + hf] = conv_bwd_weight(R, dq, kernel)
-            T = P.conv_split('q' + hf + 't', dq, P.w['q' + hf + 't'], None, False, G5)
-            gru_gates_r_backward(T[:, :c], A[:, :c], r[i], dh, dzr[:, c:], T[:, :c])
-            dw, db = conv_bwd_weight(A, dzr, kernel)                     # convz | convr read the same input: one GEMM of 2 c output channels
-            grads['z' + hf], grads['r' + hf] = (dw[:c], db[:c]), (dw[c:], db[c:])
-
-            def fill(terms, T=T, carry=carry):
-                copy_planes(T, terms[0])
-                if carry is not None:                                   # the other half's d x (its d h_old went into this half as ``d``)
-                    terms[1][:, :c].zero_()
-                    copy_planes(carry[:, c:], terms[1][:, c:])
-            carry = P.conv_split('zr' + hf + 't', dzr, P.w['zr' + hf + 't'], None, False, G5, extra=1 if carry is None else 2, fill=fill)
-            d = carry[:, :c]
-        d_net_prev, d_inp = new(c), new(c)
-        copy_planes(carry[:, :c], d_net_prev)
-        copy_planes(carry[:, c:2 * c], d_inp)
-        # the motion encoder's adjoint (nothing into flow or corr)
-        m = A1[:, 2 * c:3 * c - 2]
-        dm = relu_backward(carry[:, 2 * c:3 * c - 2], m)
-        grads['cv'] = conv_bwd_weight(cat, dm, (3, 3))
-        dcat = P.conv_split('cvt', dm, P.w['cvt'], None, False, G3)
-        relu_backward(dcat, cat)
-        grads['c2'] = conv_bwd_weight(c1, dcat[:, :192], (3, 3))
-        grads['f2'] = conv_bwd_weight(f1, dcat[:, 192:], (3, 3))
-        dc1 = P.conv_split('c2t', dcat[:, :192], P.w['c2t'], None, False, G3)
-        relu_backward(dc1, c1)
-        grads['c1'] = conv_bwd_weight(corr, dc1, (1, 1))
-        df1 = P.conv_split('f2t', dcat[:, 192:], P.w['f2t'], None, False, G3)
-        relu_backward(df1, f1)
-        grads['f1'] = conv_bwd_weight(flow, df1, (7, 7))
-        d_corr = P.conv_split('c1t', dc1, P.w['c1t'], None, False, G1) if ret_d_corr else None
-    order = ('z1', 'r1', 'q1', 'z2', 'r2', 'q2', 'c1', 'c2', 'f1', 'f2', 'cv')
-    out = (d_net_prev, d_inp, tuple(t for name in order for t in grads[name]))
-    return out + (d_corr,) if ret_d_corr else out
-
-
 # ------------------------------------------------------------------------------------------------- backward of the correlation
 def corr_grad_levels(h8, w8, levels=4):
     """[(h_l, w_l)] of the pyramid's levels (h8 >> l, w8 >> l): a row of the gradient volume G holds them one after the other."""
@@ -1883,7 +1622,7 @@ def _grad_volume(who, G, b, h8, w8, levels):
 
 def corr_lookup_backward(coords, d_corr, G, radius=4):
     """rpe_corr_lookup_backward: G += the adjoint of one window lookup at ``coords`` (b,2,h8,w8) from ``d_corr`` (b, levels 81, h8, w8), the
-    gradient of the looked-up window (ops.update_step_backward's ``ret_d_corr``).  G: ops.corr_grad_volume's layout, zero-filled by the caller
+    gradient of the looked-up window (raft_grad.update_step_backward's ``ret_d_corr``).  G: ops.corr_grad_volume's layout, zero-filled by the caller
     before the first call; calls accumulate in stream order.  The forward's own taps and fractions, cells outside a level dropped; one wave
     owns a query's row, no atomics: bit-identical from run to run, a row's bits independent of the batch.  Nothing goes into the coordinates
     (upstream detaches them).  -> G."""
@@ -1921,72 +1660,3 @@ def corr_build_backward(G, fmap1, fmap2, levels=4, ret_df2cat=False):
     check(lib().rpe_corr_build_backward(ptr(G), ptr(f1), ptr(f2), b, c, h8, w8, levels, ptr(d1), ptr(d2), ptr(dcat), ptr(ws), stream_ptr()),
           'rpe_corr_build_backward')
     return (d1, d2, dcat) if ret_df2cat else (d1, d2)
-
-
-class _RaftBpttFn(torch.autograd.Function):
-    """k gradient-free RAFT passes run with ``grad_update`` as ONE autograd node: inputs k x (flow_up, hidden, flow_low, net_0, inp), the
-    eight head parameters and the 22 of UPDATE_PARAMS; outputs the k up-sampled flows unchanged.  With ``per`` = 7 (``grad_corr``) a pass
-    carries two more leaves, (..., fmap1, fmap2): every step also forms d_corr and accumulates it into the pass's gradient volume at the
-    saved coordinates (corr_lookup_backward, k = N .. 1), and after step 1 the build's adjoint runs once (corr_build_backward); everything
-    else is computed by the same launches as with ``per`` = 5.  ``saved[i]`` = (states, corr_of): the
-    dense entry states (hx_k, coords1_k), k = 1 .. N, of pass i and a function k -> the window the pass looked up for states[k]
-    (RAFT.corr_of; it holds the pyramid).  Backward, per pass in the order given: raft_tail_backward (d net_N), then update_step_backward for k = N .. 1; the parameter
-    gradients are summed over the steps in descending k, then over the passes in the given order (a pass whose flow nothing
-    differentiates is skipped): the sum's bits do not depend on the autograd engine's scheduling."""
-
-    @staticmethod
-    def forward(ctx, k, saved, per, *tensors):
-        ctx.k, ctx.saved, ctx.per = k, saved, per
-        ctx.save_for_backward(*tensors)
-        ctx.set_materialize_grads(False)
-        outs = tuple(tensors[per * i].view_as(tensors[per * i]) for i in range(k))
-        return outs[0] if k == 1 else outs
-
-    @staticmethod
-    def backward(ctx, *grads):
-        t, k, per = ctx.saved_tensors, ctx.k, ctx.per
-        heads, upd = t[per * k:per * k + 8], t[per * k + 8:]
-        totals, per_pass = None, []
-        for i, g in enumerate(grads):
-            if g is None:
-                per_pass += [None] * per
-                continue
-            hidden, low, inp = t[per * i + 1].detach(), t[per * i + 2], t[per * i + 4].detach()
-            d_net_n, pg = raft_tail_backward(hidden, low, g.contiguous(), heads[:4], heads[4:])
-            states, corr_of = ctx.saved[i]
-            d, d_inp, ug, vol = d_net_n, None, None, None
-            for step in reversed(range(len(states))):
-                r = update_step_backward(states[step][0], inp, corr_of(step), d, upd, ret_d_corr=per == 7)
-                d, di, sg = r[:3]
-                if per == 7:
-                    if vol is None:
-                        vol = corr_grad_volume(r[3].shape[0], *r[3].shape[2:], r[3].shape[1] // 81, device=r[3].device)
-                    corr_lookup_backward(states[step][1], r[3], vol)
-                d_inp = di if d_inp is None else d_inp + di
-                ug = list(sg) if ug is None else [a + b for a, b in zip(ug, sg)]
-            both = list(pg) + (ug if ug is not None else [torch.zeros_like(p) for p in upd])
-            totals = both if totals is None else [a + b for a, b in zip(totals, both)]
-            per_pass += [None, d_net_n, None, d, d_inp]
-            if per == 7:
-                f1, f2 = t[per * i + 5].detach(), t[per * i + 6].detach()
-                per_pass += list(corr_build_backward(vol, f1, f2, r[3].shape[1] // 81)) if vol is not None else [None, None]
-                vol = None                                              # (S h8 w8 4 bytes per pair: freed before the next pass)
-        return (None, None, None, *per_pass, *(totals if totals is not None else [None] * 30))
-
-
-def update_bptt_attach(passes, saved, fh_params, mask_params, update_params):
-    """Attach the update block's backward through time to the results of gradient-free RAFT passes (RAFT.forward(grad_update=True)):
-    ``passes`` = [(flow_up, hidden, flow_low, net_0, inp), ...] with hidden, net_0 and inp leaves that require grad; ``saved`` = per pass
-    (states, corr_of) as _RaftBpttFn describes -> the list of up-sampled flows (the same values), outputs of one autograd node.  After a
-    backward: hidden.grad = d loss / d net_N, net_0.grad = d loss / d net_0, inp.grad = d loss / d inp (summed over the iterations, last
-    first), and the 30 parameters' .grad.  Passes of SEVEN tensors, (..., fmap1, fmap2) with the two feature maps the pass correlated as leaf
-    copies that require grad (``grad_corr``): the backward goes on through the correlation -- fmap1.grad = d loss / d fmap1 and fmap2.grad
-    likewise, exact under upstream's detach of coords1 (the window is linear in the pyramid, the pyramid bilinear in the maps).  The pass's
-    gradient volume lives during its backward only: S h8 w8 4 bytes per pair, 139 MB at 640 x 512."""
-    per = {len(p) for p in passes}
-    if per not in ({5}, {7}):
-        raise _lib.RpeError('update_bptt_attach: every pass is (flow_up, hidden, flow_low, net_0, inp) or every pass has fmap1, fmap2 as well')
-    flat = [x for p in passes for x in p]
-    with torch.enable_grad():
-        out = _RaftBpttFn.apply(len(passes), list(saved), per.pop(), *flat, *fh_params, *mask_params, *update_params)
-    return [out] if len(passes) == 1 else list(out)

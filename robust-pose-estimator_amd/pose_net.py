@@ -11,7 +11,7 @@ the kernels of csrc/unet_train.hip with config['train_heads_hip']), and the devi
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import ops, raft_grad
 from .pose_head import DeclarativeLayerLie, DPoseSE3Head, create_img_coords_t
 from .raft import RAFT
 from .se3 import SE3
@@ -55,26 +55,23 @@ class PoseNet(nn.Module):
         return dict(f=f, c=c)
 
     @torch.no_grad()
-    def flow2depth(self, imagel, imager, baseline, upsample=True, ret_cache=False, enc=None, ret_tail=False, save_states=False):
+    def flow2depth(self, imagel, imager, baseline, upsample=True, ret_cache=False, enc=None, grad=None):
         """pose_net.py:127-135 -> (depth (n,1,h,w), stereo flow (n,2,h,w), valid (n,1,h,w) bool).
         ``upsample=False``: everything at 1/8 resolution, the flow in 1/8-pixel units and the depth divided by 8 (:131-132;
         a division by a power of two commutes with the rounding of b / -flow.x, so the kernel is handed b / 8).
         ``ret_cache`` additionally returns the encoder outputs of ``imagel`` for reuse by the next ``infer``.
-        ``ret_tail`` additionally returns (hidden state, last 1/8 flow) of the pass: what the backward of RAFT's output heads reads; with
-        ``save_states`` (needs ret_tail) the tuple goes on with what the update block's backward reads: the context encoder's output, the
-        pass's saved entry states, its pyramid (RAFT.pass_with_states) and the two feature maps it correlated."""
+        ``grad`` = 'heads', 'update' or 'corr': the pass runs as RAFT.grad_pass runs it, and its raft_grad.GradPass, leaves made, is
+        returned as a fourth element: what ``stages`` takes as ``pass1``."""
         n = imagel.shape[0]
         f, cn = (enc['f'], enc['c']) if enc is not None else self._encode_both((imagel, imager), imagel)
-        more = ()
-        if save_states:
-            r, states, pyr = self.flow.pass_with_states((f[:n], f[n:]), cn, upsample=upsample)
-            more = (cn, states, pyr, (f[:n], f[n:]))
+        if grad is not None:
+            r, rec = self.flow.grad_pass((f[:n], f[n:]), cn, stages=grad, upsample=upsample)
         else:
-            r = self.flow(None, None, upsample=upsample, fmaps=(f[:n], f[n:]), cnet=cn, **(dict(ret_lowres=True) if ret_tail else {}))
+            r = self.flow(None, None, upsample=upsample, fmaps=(f[:n], f[n:]), cnet=cn)
         flow = r[0][-1]
         depth, valid = ops.flow2depth(flow, baseline if upsample else baseline / 8.0)
-        if ret_tail:
-            return depth, flow, valid, (r[1], r[3]) + more
+        if grad is not None:
+            return depth, flow, valid, rec.rows(0, n)
         if ret_cache:
             return depth, flow, valid, dict(fmap=f[:n], cnet=cn)
         return depth, flow, valid
@@ -93,41 +90,36 @@ class PoseNet(nn.Module):
         flow -- what a differentiable flow model has to be handed.  Values, and the gradients of the heads and ``loss_weight``, are those
         of the default call; without the flag nothing here changes, launches included.
         With RAFT's output heads trainable (``freeze_flow(False, parts='heads')``) the call takes the ``ret_flows`` route whether asked or
-        not, and the three flows are the outputs of ONE autograd node (ops.raft_tail_attach; passes in the order time, stereo1, stereo2)
-        over the three RAFT results -- the ``flow2depth`` pass of frame 1 and both halves of the batched pass --, whose backward
-        (ops.raft_tail_backward) hands the pose loss's gradient to the flow head's and the mask head's eight parameters, summed over the
-        three.  With the whole update block trainable (``freeze_flow(False, parts='update')``) that node is ops.update_bptt_attach instead:
-        the three passes also save the entry state of every iteration, and the node's backward goes on from the tail through the N
-        applications of the SepConvGRU and the motion encoder (ops.update_step_backward) -- all 30 update-block parameters get the pose
-        loss's exact gradient under upstream's detach of coords1; the dict then gains 'net0' and 'inp', leaves per pass whose ``.grad`` is
-        d loss / d net_0 and d loss / d inp.  The flows keep their ``.grad`` (retain_grad), and with ``ret_flows`` the returned dict gains 'hidden': {'time', 'stereo1',
-        'stereo2'}, leaves whose ``.grad`` is the tail's d loss / d net_N, plus the weight heads' input gradient for 'time'.
-        ``grad_corr`` (with ``ret_flows``): the call takes the update-block route whether or not the update block's parameters require grad,
-        and the node's backward goes on through the correlation (RAFT.forward's ``grad_corr``: csrc/corr_backward.hip): the dict gains
-        'fmap1' and 'fmap2', leaves per pass ('time', 'stereo1', 'stereo2') beside 'net0' and 'inp' -- copies of the rows of the feature maps
-        each pass correlated -- whose ``.grad`` is d loss / d fmap: what a backward of the feature encoder has to be handed.  Pose, depths
-        and every other gradient keep their bits.  Refused before any launch with alternate_corr."""
+        not, and the three flows are the outputs of ONE autograd node (raft_grad.attach; passes in the order time, stereo1, stereo2)
+        over the three RAFT results -- the ``flow2depth`` pass of frame 1 and both halves of the batched pass --, whose backward hands the
+        pose loss's gradient to the flow head's and the mask head's eight parameters, summed over the three.  With the whole update
+        block trainable (``freeze_flow(False, parts='update')``) the passes and the node go as deep as 'update': all 30 update-block
+        parameters get the pose loss's exact gradient under upstream's detach of coords1 (raft_grad's module docstring says what each
+        depth saves, costs and differentiates), and the dict gains 'net0' and 'inp', leaves per pass whose ``.grad`` is d loss / d net_0 and
+        d loss / d inp.  The flows keep their ``.grad`` (retain_grad), and with ``ret_flows`` the returned dict gains 'hidden': {'time',
+        'stereo1', 'stereo2'}, leaves whose ``.grad`` is the tail's d loss / d net_N, plus the weight heads' input gradient for 'time'.
+        ``grad_corr`` (with ``ret_flows``): the call goes as deep as 'corr' whether or not the update block's parameters require grad: the
+        dict gains 'fmap1' and 'fmap2', leaves per pass ('time', 'stereo1', 'stereo2') beside 'net0' and 'inp' -- copies of the rows of the
+        feature maps each pass correlated -- whose ``.grad`` is d loss / d fmap: what a backward of the feature encoder has to be handed.
+        Pose, depths and every other gradient keep their bits.  Refused before any launch with alternate_corr."""
         n = image1l.shape[0]
         intrinsics = intrinsics.expand(n, 3, 3).contiguous()
         baseline = baseline.expand(n).contiguous()
         if grad_corr and not ret_flows:
             raise ValueError('PoseNet.forward: grad_corr returns its leaves in the dict of ret_flows: it needs ret_flows=True')
-        grad_update = self.flow_update_trainable() or grad_corr
-        grad_heads = self.flow_heads_trainable() or grad_update
-        if grad_heads:
-            self.flow.check_grad_heads()                       # (before anything is launched)
-        if grad_corr:
-            self.flow.check_grad_corr()
+        grad = 'corr' if grad_corr else 'update' if self.flow_update_trainable() else 'heads' if self.flow_heads_trainable() else None
+        if grad is not None:
+            self.flow.check_grad(grad)                         # (before anything is launched)
         with torch.no_grad():
-            tail1 = None
-            if grad_heads:
-                depth1, stereo_flow1, valid1, tail1 = self.flow2depth(image1l, image1r, baseline, ret_tail=True, save_states=grad_update)
+            pass1 = None
+            if grad is not None:
+                depth1, stereo_flow1, valid1, pass1 = self.flow2depth(image1l, image1r, baseline, grad=grad)
             else:
                 depth1, stereo_flow1, valid1 = self.flow2depth(image1l, image1r, baseline)
             mask1 = (mask1.bool() & valid1) if mask1 is not None else valid1
             mask2 = mask2.bool().clone() if mask2 is not None else torch.ones_like(valid1)
             s = self.stages(image1l, image2l, intrinsics, baseline, depth1, image2r, mask1, mask2, stereo_flow1, heads=False,
-                            grad_flows=ret_flows or grad_heads, tail1=tail1, grad_corr=grad_corr)
+                            grad_flows=ret_flows or grad is not None, pass1=pass1)
         if self.use_weights and self.train_heads_hip:
             # the heads' training route on hand-written kernels (csrc/unet_train.hip): the parts are read where they are (no torch.cat),
             # the Sigmoid modules' work is fused into the resize
@@ -144,17 +136,12 @@ class PoseNet(nn.Module):
         out = (pose_tan, depth1, s['depth2'], (w2d, w3d)) if ret_confmap else (pose_tan, depth1, s['depth2'])
         if ret_flows:
             flows = {k: s[k] for k in ('time_flow', 'stereo_flow1', 'stereo_flow2')}
-            if grad_heads:
-                flows['hidden'] = s['hidden_leaves']
-            if grad_update:
-                flows['net0'], flows['inp'] = s['net0_leaves'], s['inp_leaves']
-            if grad_corr:
-                flows['fmap1'], flows['fmap2'] = s['fmap1_leaves'], s['fmap2_leaves']
+            flows.update({k: s[k + '_leaves'] for k in raft_grad.GradPass.LEAVES if k + '_leaves' in s})      # (the leaves of the passes' depth)
             out = (*out, flows)
         return out
 
     def flow_head_params(self):
-        """RAFT's flow-head and mask-head parameters (ops.raft_tail_backward's order): what ``freeze_flow(False, parts='heads')`` trains."""
+        """RAFT's flow-head and mask-head parameters (raft_grad.raft_tail_backward's order): what ``freeze_flow(False, parts='heads')`` trains."""
         fh, mk = self.flow.head_params()
         return fh + mk
 
@@ -171,7 +158,7 @@ class PoseNet(nn.Module):
         update block: the gradients of the pose loss reach the three flows (``forward(..., ret_flows=True)``: the pose layer's and the geometry
         stage's backward), through the backward of RAFT's last flow-head / mask-head application (csrc/raft_backward.hip) those heads'
         parameters -- ``freeze_flow(False, parts='heads')`` sets requires_grad on ``flow.update_block.flow_head`` and ``flow.update_block.mask``
-        only --, and through the backward of the N update steps (csrc/update_backward.hip, ops.update_step_backward) the SepConvGRU and the
+        only --, and through the backward of the N update steps (csrc/update_backward.hip, raft_grad.update_step_backward) the SepConvGRU and the
         motion encoder -- ``freeze_flow(False, parts='update')`` sets it on all of ``flow.update_block``.  The correlation has a backward as
         well (csrc/corr_backward.hip; it has no parameters): ``forward(..., ret_flows=True, grad_corr=True)`` hands the gradient to the two
         feature maps of every pass.  Only the two encoders have no backward here: ``freeze_flow(False)`` without ``parts`` is refused
@@ -231,7 +218,7 @@ class PoseNet(nn.Module):
 
     @torch.no_grad()
     def stages(self, image1l, image2l, intrinsics, baseline, depth1, image2r, mask1, mask2, stereo_flow1, cache1=None, heads=True, enc2=None,
-               flow_init=None, ret_lowres=False, grad_flows=False, tail1=None, grad_corr=False):
+               flow_init=None, ret_lowres=False, grad_flows=False, pass1=None):
         """Every stage of infer() before the solve.  ``cache1`` = {'fmap','cnet'} of image1l from the previous call
         (streaming: frame t's image2l is frame t+1's image1l), so only the two new images are encoded -- or not even those when
         ``enc2`` = encode_frame(image2l, image2r) was computed ahead of the call (needs cache1).
@@ -241,11 +228,11 @@ class PoseNet(nn.Module):
         ``grad_flows`` (the training forward's ``ret_flows``): time_flow, stereo_flow2 and stereo_flow1 become leaves that require grad
         ('stereo_flow1' is added to the result) and the geometry stage runs, with gradients enabled, through ``ops.flow2depth_grad`` and
         ``ops.geometry_stage``: the same values, now differentiable with respect to the three flows.
-        ``tail1`` = (hidden, 1/8 flow) of the pass that made stereo_flow1 (flow2depth's ``ret_tail``; needs grad_flows): RAFT's output heads
-        train -- the three flows leave one ops.raft_tail_attach node (time, stereo1, stereo2), 'hidden' is the temporal pairs' hidden state as a
-        leaf that requires grad, and 'hidden_leaves' = {'time', 'stereo1', 'stereo2'}.
-        ``grad_corr`` (needs flow2depth's save_states in ``tail1``): the passes of the update block's node carry leaf copies of their rows of
-        the feature maps as well ('fmap1_leaves', 'fmap2_leaves'), and its backward goes on through the correlation."""
+        ``pass1`` = the raft_grad.GradPass of the pass that made stereo_flow1 (flow2depth's ``grad``; needs grad_flows): RAFT trains as deep
+        as that record goes.  The batched pass runs as deep (RAFT.grad_pass), its two halves are rows of its record, and the three flows
+        leave ONE raft_grad.attach node over (time, stereo1, stereo2).  'hidden' is the temporal pairs' hidden state as a leaf that requires
+        grad, and for every leaf field the records carry -- 'hidden'; 'net0', 'inp'; 'fmap1', 'fmap2' -- the result gains
+        '<field>_leaves' = {'time', 'stereo1', 'stereo2'}."""
         n = image1l.shape[0]
         intrinsics = intrinsics.expand(n, 3, 3).contiguous()
         baseline = baseline.expand(n).contiguous()
@@ -265,47 +252,22 @@ class PoseNet(nn.Module):
         kw = {}
         if flow_init is not None:
             kw['flow_init'] = torch.cat((flow_init, torch.zeros_like(flow_init)), dim=0)      # (temporal | stereo) rows of the RAFT batch
-        if ret_lowres or tail1 is not None:
-            kw['ret_lowres'] = True
-        bptt = tail1 is not None and len(tail1) > 2              # (flow2depth's save_states: the update block trains)
-        if bptt:
-            kw.pop('ret_lowres')
-            r, states2, pyr2 = self.flow.pass_with_states(fmaps, cn, upsample=True, **kw)
+        if pass1 is not None:
+            r, rec2 = self.flow.grad_pass(fmaps, cn, stages=pass1.depth, upsample=True, **kw)
         else:
-            r = self.flow(None, None, upsample=True, fmaps=fmaps, cnet=cn, **kw)
+            r = self.flow(None, None, upsample=True, fmaps=fmaps, cnet=cn, ret_lowres=ret_lowres, **kw)
         flow_predictions, hidden, context = r[:3]
         time_flow = flow_predictions[-1][:n].contiguous()
         stereo_flow2 = flow_predictions[-1][n:].contiguous()
         hidden, context = hidden[:n], context[:n]
-        leaves = None
+        passes = None
         if grad_flows:
             with torch.enable_grad():
-                if tail1 is not None:
-                    low = r[3]
-                    leaves = dict(time=hidden, stereo1=tail1[0], stereo2=r[1][n:])
-                    leaves = {k: t.detach().requires_grad_(True) for k, t in leaves.items()}
-                    hidden = leaves['time']                    # (the weight heads read it: their input gradient lands in its .grad)
-                    fh, mk = self.flow.head_params()
-                    passes = [(time_flow, leaves['time'], low[:n]), (stereo_flow1.contiguous(), leaves['stereo1'], tail1[1]),
-                              (stereo_flow2, leaves['stereo2'], low[n:])]
-                    if bptt:
-                        c = hidden.shape[1]
-                        cn1, states1, pyr1, fm1 = tail1[2:]
-                        rows = dict(time=(cn, 0, n), stereo1=(cn1, 0, n), stereo2=(cn, n, 2 * n))
-                        net0 = {k: t[lo:hi, :c].clone().requires_grad_(True) for k, (t, lo, hi) in rows.items()}
-                        inp = {k: t[lo:hi, c:].clone().requires_grad_(True) for k, (t, lo, hi) in rows.items()}
-                        corr_of = self.flow.corr_of
-                        saved = [([(st[:n], co[:n]) for st, co in states2], corr_of(pyr2, states2, (0, n))), (states1, corr_of(pyr1, states1)),
-                                 ([(st[n:], co[n:]) for st, co in states2], corr_of(pyr2, states2, (n, 2 * n)))]
-                        passes = [p + (net0[k], inp[k]) for p, k in zip(passes, ('time', 'stereo1', 'stereo2'))]
-                        if grad_corr:                          # rows of the batched pass's maps are slices, as corr_of(rows=) slices the window
-                            frows = dict(time=(fmaps, 0, n), stereo1=(fm1, 0, n), stereo2=(fmaps, n, 2 * n))
-                            fleaf = [{k: t[j][lo:hi].float().clone(memory_format=torch.contiguous_format).requires_grad_(True)
-                                      for k, (t, lo, hi) in frows.items()} for j in (0, 1)]
-                            passes = [p + (fleaf[0][k], fleaf[1][k]) for p, k in zip(passes, ('time', 'stereo1', 'stereo2'))]
-                        time_flow, stereo_flow1, stereo_flow2 = ops.update_bptt_attach(passes, saved, fh, mk, self.flow.update_params())
-                    else:
-                        time_flow, stereo_flow1, stereo_flow2 = ops.raft_tail_attach(passes, fh, mk)
+                if pass1 is not None:
+                    passes = dict(time=rec2.rows(0, n), stereo1=pass1, stereo2=rec2.rows(n, 2 * n))
+                    hidden = passes['time'].hidden             # (the weight heads read it: their input gradient lands in its .grad)
+                    time_flow, stereo_flow1, stereo_flow2 = raft_grad.attach(
+                        list(passes.values()), self.flow.head_params(), None if pass1.depth == 'heads' else self.flow.update_params())
                     for t in (time_flow, stereo_flow1, stereo_flow2):
                         t.retain_grad()
                 else:
@@ -319,12 +281,8 @@ class PoseNet(nn.Module):
         w2d, w3d = self._heads(g, hidden, context) if heads else (None, None)
         g.update(time_flow=time_flow, stereo_flow2=stereo_flow2, hidden=hidden, context=context, w2d=w2d, w3d=w3d,
                  intrinsics=intrinsics, cache2=dict(fmap=f2l, cnet=c2l))
-        if leaves is not None:
-            g['hidden_leaves'] = leaves
-            if bptt:
-                g['net0_leaves'], g['inp_leaves'] = net0, inp
-                if grad_corr:
-                    g['fmap1_leaves'], g['fmap2_leaves'] = fleaf
+        if passes is not None:
+            g.update({k + '_leaves': {p: getattr(rec, k) for p, rec in passes.items()} for k in raft_grad.GradPass.LEAVES if getattr(pass1, k) is not None})
         if ret_lowres:
             g['time_flow_low'] = g['cache2']['time_flow_low'] = r[3][:n]
         return g

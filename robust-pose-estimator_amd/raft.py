@@ -40,8 +40,9 @@ from typing import NamedTuple, Optional, Tuple
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import ops, raft_grad
 from ._lib import RpeError
+from .ops import bounded_put, wkey
 
 # Module-level route constants (no environment switches in the product: tools/ and bench.py's labelled experiments set these attributes)
 WINOGRAD = True          # 3x3 layers as F(2x2,3x3), the GRU's 1x5 / 5x1 as F(4,5); False = the direct implicit GEMM (A/B measurements)
@@ -254,19 +255,6 @@ class ResidualBlock(nn.Module):
         return conv_norm_act(self.conv2, self.norm2, y, relu=True, residual=x, valid=valid)
 
 
-def _bounded_put(cache, key, value, keep=2):
-    """Insert into a small insertion-ordered cache, evicting the oldest entries (and the buffers / launch descriptors they pin)."""
-    while len(cache) >= keep:
-        cache.pop(next(iter(cache)))
-    cache[key] = value
-
-
-def _wkey(*tensors):
-    """Cache key of what is made from ``tensors`` (None = absent, and stays None in its place): an in-place update bumps the version,
-    .to() / .float() move the data, and a replaced Parameter is another tensor."""
-    return tuple(None if t is None else (t._version, t.data_ptr()) for t in tensors)
-
-
 def _cached(owner, attr, key, make, with_key=False):
     """``make()`` kept on ``owner`` -- a module (as attribute ``attr``) or a workspace dict (as entry ``attr``) -- until ``key`` changes.
     ``with_key``: returns (key, value), for a caller whose own cache depends on this one and therefore keys on its key."""
@@ -282,12 +270,12 @@ def _bn_affine(conv, norm):
     def fold():
         scale = (norm.weight / torch.sqrt(norm.running_var + norm.eps)).detach().float().contiguous()
         return scale, ((conv.bias - norm.running_mean) * scale + norm.bias).detach().float().contiguous()
-    return _cached(norm, '_rpe_affine', _wkey(conv.bias, norm.weight, norm.bias, norm.running_mean, norm.running_var), fold)
+    return _cached(norm, '_rpe_affine', wkey(conv.bias, norm.weight, norm.bias, norm.running_mean, norm.running_var), fold)
 
 
 def _packed(conv):
     """PackedConv of a module's weight (no bias), cached on the module until the weight changes."""
-    return _cached(conv, '_rpe_packed', _wkey(conv.weight), lambda: ops.PackedConv(conv.weight, None))
+    return _cached(conv, '_rpe_packed', wkey(conv.weight), lambda: ops.PackedConv(conv.weight, None))
 
 
 def _wino(conv, x):
@@ -298,7 +286,7 @@ def _wino(conv, x):
     if not ops.PackedWino.supported(conv.weight, x.shape[-2], x.shape[-1]) or conv.in_channels > 128 or not x.is_contiguous():
         return None
     kind = ops.PackedWino24 if WINO_2X4 and ops.PackedWino24.supported(conv.weight, x.shape[-2], x.shape[-1]) else ops.PackedWino
-    return _cached(conv, '_rpe_wino', (_wkey(conv.weight), kind), lambda: kind(conv.weight, None))
+    return _cached(conv, '_rpe_wino', (wkey(conv.weight), kind), lambda: kind(conv.weight, None))
 
 
 def _fusable(conv, x):
@@ -359,7 +347,7 @@ def _encoder_conv(conv, x, mode=ops.CONV_LINEAR, affine=None, residual=None, pre
 
 
 def _recording(owner, root):
-    """The set-up of a module that records its small passes: (``owner``'s cache of recorded passes, the _wkey of every parameter and
+    """The set-up of a module that records its small passes: (``owner``'s cache of recorded passes, the wkey of every parameter and
     buffer below ``root``).  The (dict, name) slots are collected once and read afresh for every key, so a Parameter object that is
     REPLACED shows up, not only one that is updated in place."""
     d = owner.__dict__
@@ -367,7 +355,7 @@ def _recording(owner, root):
         d['_recorded'] = _Recorded()
     if '_key_tensors' not in d:
         d['_key_tensors'] = [(slots, n) for m in root.modules() for slots in (m._parameters, m._buffers) for n in slots]
-    return d['_recorded'], _wkey(*[slots[n] for slots, n in d['_key_tensors']])
+    return d['_recorded'], wkey(*[slots[n] for slots, n in d['_key_tensors']])
 
 
 def _overlap(tensors):
@@ -390,7 +378,7 @@ class _Recorded:
 
     def put(self, key, rec):
         if rec.complete:
-            _bounded_put(self._progs, key, rec, keep=self._keep)
+            bounded_put(self._progs, key, rec, keep=self._keep)
         else:
             if len(self._failed) > 64:
                 self._failed.clear()
@@ -433,7 +421,7 @@ class BasicEncoder(nn.Module):
         """conv1 + norm1 + ReLU run on the RAW 0..255 image: the normalisation 2*(x/255)-1 happens while the kernel stages its
         input patch (rpe_stem_conv)."""
         w = self.conv1.weight
-        return _cached(self, '_stem_packed', _wkey(w), lambda: ops.PackedStem(w))
+        return _cached(self, '_stem_packed', wkey(w), lambda: ops.PackedStem(w))
 
     def _stem_many(self, images):
         """The stem over several image batches, written into batch slices of ONE output (no torch.cat of the inputs)."""
@@ -473,7 +461,7 @@ class BasicEncoder(nn.Module):
             def pack():
                 w, bv = m.weight.detach(), m.bias.detach()
                 return ops.Conv1x1(w, bv), ops.Conv1x1(w[:half].contiguous(), bv[:half].contiguous()), ops.Conv1x1(w[half:].contiguous(), bv[half:].contiguous())
-            whole, lo, hi = _cached(self, '_final_packed', _wkey(m.weight, m.bias), pack)
+            whole, lo, hi = _cached(self, '_final_packed', wkey(m.weight, m.bias), pack)
             out = torch.empty(b, m.out_channels, hh, ww, device=x.device)
             if not split_act:
                 whole(x, ops.CONV_LINEAR, out, x3=CONV_BF16X3, valid=valid)
@@ -565,7 +553,7 @@ class BasicEncoder(nn.Module):
         cache = self.__dict__.setdefault('_p2_cache', {})
         key = (n, h2, w2, content, str(device))
         if key not in cache:
-            _bounded_put(cache, key, torch.zeros(n, 64, h2, w2, device=device), keep=2)
+            bounded_put(cache, key, torch.zeros(n, 64, h2, w2, device=device), keep=2)
         return cache[key]
 
 
@@ -652,7 +640,7 @@ class BasicUpdateBlock(nn.Module):
                 bvec = torch.cat([m.bias for m in convs], 0).detach().contiguous()
                 W[name] = (*split(w), bvec)
             return W
-        key = _wkey(*[t for m in (g.convz1, g.convr1, g.convq1, g.convz2, g.convr2, g.convq2) for t in (m.weight, m.bias)])
+        key = wkey(*[t for m in (g.convz1, g.convr1, g.convq1, g.convz2, g.convr2, g.convq2) for t in (m.weight, m.bias)])
         return _cached(self, '_stacked', key, stack, with_key)
 
     def context_terms(self, inp, out=None):
@@ -683,7 +671,7 @@ class BasicUpdateBlock(nn.Module):
         mods = (e.convc1, e.convc2, e.convf2, e.conv, fh.conv1)
         gate_key, W = self.gate_weights(with_key=True)
         # (the convolutions' own weight / bias attributes: walking module.parameters() costs ~100 us a call, and this runs 26 times a frame)
-        key = (_wkey(*[t for m in mods + (e.convf1,) for t in (m.weight, m.bias)]), gate_key, _switches(), self.route)
+        key = (wkey(*[t for m in mods + (e.convf1,) for t in (m.weight, m.bias)]), gate_key, _switches(), self.route)
         return _cached(self, '_packed', key, lambda: self._pack_convs(mods, W), with_key)
 
     def _pack_convs(self, mods, W):
@@ -725,7 +713,7 @@ class BasicUpdateBlock(nn.Module):
         def buf(name, like, c):                            # scratch for intermediate activations, one set per workspace (``like`` is one of
             k = (name, like.data_ptr(), like.shape[0], c, like.shape[2], like.shape[3], like.device)   # RAFT._workspace's buffers)
             if k not in scratch:
-                _bounded_put(scratch, k, torch.empty(like.shape[0], c, like.shape[2], like.shape[3], device=like.device), keep=12)
+                bounded_put(scratch, k, torch.empty(like.shape[0], c, like.shape[2], like.shape[3], device=like.device), keep=12)
             return scratch[k]
         P['cor_buf'] = lambda like: buf('cor', like, 256)
         P['fh_buf'] = lambda like: buf('fh', like, 256)
@@ -788,7 +776,7 @@ class BasicUpdateBlock(nn.Module):
             n_wgs = hx.shape[0] * -(-(hx.shape[2] * -(-hx.shape[3] // 8)) // 8)
             if valid is None and not alt and LOOKUP_FUSED and not CONV_BF16X3 and f16 is None and n_wgs <= LOOKUP_FUSED_MAX_WGS and ops.PackedLookupConv.supported(pyr.levels, pyr.radius, pyr.w8):
                 # (convc1 in the fused kernel's layout: made when a pass first takes this route, kept while convc1 stays as it is)
-                pl = _cached(self, '_lookup_packed', _wkey(e.convc1.weight, e.convc1.bias), lambda: ops.PackedLookupConv(e.convc1.weight, e.convc1.bias))
+                pl = _cached(self, '_lookup_packed', wkey(e.convc1.weight, e.convc1.bias), lambda: ops.PackedLookupConv(e.convc1.weight, e.convc1.bias))
                 L.lookup_c1 = pyr.lookup_conv1x1(coords1, pl, cor, relu=True, prepare=True)
         return L
 
@@ -839,7 +827,7 @@ class BasicUpdateBlock(nn.Module):
         w24 = WINO_2X4 and not CONV_BF16X3 and ops.PackedWino24.supported(c1.weight, hh, ww)
         if self.fp16() and c1.weight.is_cuda:
             # update_fp16: both layers on rpe_conv_f16, the x0.25 fold kept (a power of two: it commutes with the fp16 rounding of normal weights)
-            p1, p2 = _cached(self, '_mask_packed', (_wkey(*mp), 'f16', _switches()), lambda: (
+            p1, p2 = _cached(self, '_mask_packed', (wkey(*mp), 'f16', _switches()), lambda: (
                 ops.PackedConvF16(c1.weight, c1.bias), ops.PackedConvF16((0.25 * c2.weight).detach(), (0.25 * c2.bias).detach())))
             t = ops.conv_fused(net, p1, ops.CONV_RELU, torch.empty(net.shape[0], c1.out_channels, hh, ww, device=net.device))
             return ops.conv_fused(t, p2, ops.CONV_LINEAR, torch.empty(net.shape[0], c2.out_channels, hh, ww, device=net.device))
@@ -848,7 +836,7 @@ class BasicUpdateBlock(nn.Module):
             pw = (ops.PackedWinoX3 if x3 else ops.PackedWino24 if w24 else ops.PackedWino)(c1.weight, c1.bias) if WINOGRAD and c1.weight.is_cuda else None
             w2, b2 = (0.25 * c2.weight).detach(), (0.25 * c2.bias).detach()
             return pw, w2, b2, ops.Conv1x1(w2, b2) if c2.weight.is_cuda else None
-        pw, w2, b2, p2 = _cached(self, '_mask_packed', (_wkey(*mp), x3, w24, _switches()), pack)
+        pw, w2, b2, p2 = _cached(self, '_mask_packed', (wkey(*mp), x3, w24, _switches()), pack)
         if pw is not None and not torch.is_grad_enabled() and hh % 2 == 0 and ww % 2 == 0:      # (net may be a channel slice: hx[:, :128]; pad_maps: of a padded map)
             t = ops.conv_wino(net, pw, ops.CONV_RELU, torch.empty(net.shape[0], c1.out_channels, hh, ww, device=net.device))
         else:
@@ -1166,13 +1154,13 @@ class RAFT(nn.Module):
         return pred, h_buf, low
 
     def head_params(self):
-        """The eight parameters of the output heads in ops.raft_tail_backward's order: (flow head, mask head)."""
+        """The eight parameters of the output heads in raft_grad.raft_tail_backward's order: (flow head, mask head)."""
         fh, mk = self.update_block.flow_head, self.update_block.mask
         return (fh.conv1.weight, fh.conv1.bias, fh.conv2.weight, fh.conv2.bias), (mk[0].weight, mk[0].bias, mk[2].weight, mk[2].bias)
 
     def update_params(self):
-        """The 22 parameters of the SepConvGRU and the motion encoder in ops.UPDATE_PARAMS' order (ops.update_step_backward)."""
-        return tuple(operator.attrgetter(name)(self.update_block) for name in ops.UPDATE_PARAMS)
+        """The 22 parameters of the SepConvGRU and the motion encoder in raft_grad.UPDATE_PARAMS' order (raft_grad.update_step_backward)."""
+        return tuple(operator.attrgetter(name)(self.update_block) for name in raft_grad.UPDATE_PARAMS)
 
     def _save_state(self, ws, states, flow=None, coords1=None):
         """``grad_update``: the entry state of the iteration about to run as dense tensors of their own -- (hx's 256 channels: h_{k-1} |
@@ -1190,28 +1178,32 @@ class RAFT(nn.Module):
             ops.copy_planes(flow.contiguous(), st[:, hx.shape[1] - 2:])
         states.append((st, ops.copy_planes(co, torch.empty_like(co))))
 
-    @staticmethod
-    def corr_of(pyr, states, rows=None):
-        """k -> the window iteration k + 1 looked up (``states[k]`` = its (hx, coords1)): the pass's lookup on the saved coordinates against
-        its pyramid, which the returned function keeps alive (the model builds itself a new one for its next pass) -- the forward's bits;
-        ``rows`` = (lo, hi): those rows of the batch only.  (coords0 + flow_k would not do: coords1 - coords0 rounds where a target lies
-        much closer to column or row 0 than its source.)"""
-        last = {}
+    @torch.no_grad()
+    def grad_pass(self, fmaps, cnet, *, stages, **kw):
+        """One gradient-free ``ret_lowres`` pass on given encoder outputs (``kw``: upsample, iters, all_flows, flow_init), run so that
+        raft_grad can differentiate it as far as ``stages`` -- 'heads', 'update' or 'corr' (raft_grad's module docstring) -> (forward's
+        result with the 1/8 flow as its 4th element, the raft_grad.GradPass of the whole batch; GradPass.rows makes its leaves).  The
+        refusals are raised before any launch.  Below 'heads' the pass runs iteration by iteration and saves every iteration's entry
+        state, and its pyramid is the record's from here on, no longer the model's."""
+        self.check_grad(stages, kw.get('upsample', True))
+        states = None if stages == 'heads' else []
+        r = self._forward_impl(self._route(map_size=tuple(fmaps[0].shape[-2:])), fmaps, cnet, ret_lowres=True, states=states, **kw)
+        rec = raft_grad.GradPass(r[0][-1], r[1], r[3])
+        if states is not None:
+            c = self.hidden_dim
+            rec.net0, rec.inp, rec.states = cnet[:, :c], cnet[:, c:], states
+            rec.pyr, self._pyr = self._pyr, None
+        if stages == 'corr':
+            rec.fmap1, rec.fmap2 = fmaps                      # (what the pass correlated)
+        return r, rec
 
-        def corr(k):
-            if last.get('k') != k:
-                last.update(k=k, corr=pyr.lookup(states[k][1]))
-            return last['corr'] if rows is None else last['corr'][rows[0]:rows[1]]
-        return corr
-
-    def pass_with_states(self, fmaps, cnet, **kw):
-        """A gradient-free ``ret_lowres`` pass on given encoder outputs that also saves what ``grad_update`` saves -> (the pass's result,
-        the dense entry states hx_1 .. hx_N, the pass's pyramid -- no longer the model's)."""
-        self.check_grad_heads(kw.get('upsample', True))
-        states = []
-        r = self.forward(None, None, fmaps=fmaps, cnet=cnet, ret_lowres=True, _states=states, **kw)
-        pyr, self._pyr = self._pyr, None
-        return r, states, pyr
+    def check_grad(self, stages, upsample=True):
+        """Every refusal of a gradient pass as deep as ``stages``, before anything is launched."""
+        if stages not in raft_grad.STAGES:
+            raise ValueError(f'RAFT: stages must be one of {raft_grad.STAGES}, got {stages!r}')
+        self.check_grad_heads(upsample)
+        if stages == 'corr':
+            self.check_grad_corr()
 
     def check_grad_heads(self, upsample=True):
         """The refusals of ``grad_heads`` (raised before anything is launched): the tail's backward differentiates the f32 layers; a route
@@ -1237,7 +1229,7 @@ class RAFT(nn.Module):
 
     @torch.no_grad()
     def forward(self, image1, image2, upsample=True, iters=None, all_flows=False, fmaps=None, cnet=None, flow_init=None, ret_lowres=False,
-                grad_heads=False, grad_update=False, grad_corr=False, _states=None, _fmaps=None):
+                grad_heads=False, grad_update=False, grad_corr=False):
         """image1, image2: (N,3,H,W) in 0..255.  Inference only (the reference freezes RAFT, train.yaml:51).
         ``fmaps`` / ``cnet`` accept encoder outputs computed elsewhere (both encoders normalise per sample -- instance
         norm / frozen batch norm -- so a caller may encode every distinct image once and reuse it); with both given the
@@ -1245,69 +1237,44 @@ class RAFT(nn.Module):
         ``flow_init`` (N,2,H/8,W/8) f32: warm start as upstream RAFT's (coords1 = coords0 + flow_init; the first iteration's motion encoder
         sees flow = flow_init), e.g. ops.forward_interpolate of the previous frame's 1/8 flow; all zeros gives the cold pass bit for bit.
         ``ret_lowres``: a 4th return element, the last iteration's 1/8 flow as a fresh tensor.
-        ``grad_heads``: the pass runs as ever (gradient-free, the launches of a ``ret_lowres`` pass, the same bits); the returned LAST
-        prediction is then the output of one autograd node (ops.raft_tail_attach) whose inputs are the flow head's and the mask head's
-        eight parameters and the returned hidden state, which comes back as a leaf that requires grad.  Upstream detaches coords1 at the
-        top of every iteration, so that prediction depends on those parameters through their last application only: the node's backward
-        (ops.raft_tail_backward, csrc/raft_backward.hip) is their exact gradient, and hidden.grad is d loss / d net_N.  Refused with
-        update_fp16, CONV_BF16X3 and mixed_precision (check_grad_heads).
-        ``grad_update``: ``grad_heads`` extended to the whole update block.  The pass runs as ever (gradient-free, the kernels and the bits of
-        a ``ret_lowres`` pass, launched iteration by iteration) and additionally copies the entry state of every iteration -- hx's 256
-        channels: h_{k-1}, the stale motion slot and flow_k, and the two planes of coords1_k -- into dense tensors of their own: 258 h8 w8 4
-        bytes per pair and iteration, 5.3 MB at 640 x 512, 63 MB per pair for 12 iterations.  The correlation window is not saved: the
-        node looks it up again at the saved coordinates in the pass's pyramid, which it keeps alive (the forward's bits).  The last prediction is the output of one node (ops.update_bptt_attach)
-        whose backward is the tail's, then ops.update_step_backward for k = N .. 1: the exact gradient of all 30 update-block parameters
-        under upstream's detach of coords1 (the only path through time is the hidden state).  ``hidden`` is a leaf as under grad_heads; two
-        more elements are appended to the result, the leaves ``net_0`` (N,128,h8,w8) and ``inp`` (a leaf copy of the context), whose .grad are
-        d loss / d net_0 and d loss / d inp summed over the iterations.  The same refusals as grad_heads, before any launch.
-        ``grad_corr`` (implies grad_update): the node's backward goes on through the correlation -- every step also forms d corr_k
-        (convc1's adjoint), accumulates it at the saved coords1_k into the pass's gradient volume G = d loss / d pyramid (the lookup's
-        adjoint; S h8 w8 4 bytes per pair, S = the cells of the four levels: 139 MB at 640 x 512, 2.2 GB at 1280 x 1024, alive during the
-        backward only), and after step 1 the build's adjoint runs once (csrc/corr_backward.hip).  Two more leaves are appended behind
-        ``inp``: ``fmap1`` and ``fmap2``, copies of the maps the pass correlated, whose .grad is d loss / d fmap -- exact under upstream's
-        detach of coords1 (the window is linear in the pyramid, the pyramid bilinear in the maps; nothing goes into the coordinates).
-        Everything grad_update returns, and every gradient it forms, keeps its bits.  Refused, before any launch, with what grad_heads
-        refuses and with alternate_corr and CORR_BF16X3 (check_grad_corr)."""
-        if grad_update or grad_corr:
-            self.check_grad_heads(upsample)
-            if grad_corr:
-                self.check_grad_corr()
-            states, fm = [], ([] if grad_corr else None)
-            flows, hidden, context, low = self.forward(image1, image2, upsample, iters, all_flows, fmaps, cnet, flow_init, ret_lowres=True,
-                                                       _states=states, _fmaps=fm)
-            pyr, self._pyr = self._pyr, None                   # the node's from here on
-            c = self.hidden_dim
-            net0 = ops.copy_planes(states[0][0][:, :c], torch.empty_like(hidden)) if states else hidden.clone()
-            inp = context.clone()
-            leaves = (net0, inp) + (tuple(f.float().clone(memory_format=torch.contiguous_format) for f in fm) if grad_corr else ())
-            for t in (hidden,) + leaves:
-                t.requires_grad_(True)
-            flows[-1] = ops.update_bptt_attach([(flows[-1], hidden, low) + leaves], [(states, self.corr_of(pyr, states))], *self.head_params(),
-                                               self.update_params())[0]
-            return (flows, hidden, context) + ((low,) if ret_lowres else ()) + leaves
-        if grad_heads:
-            self.check_grad_heads(upsample)
-            flows, hidden, context, low = self.forward(image1, image2, upsample, iters, all_flows, fmaps, cnet, flow_init, ret_lowres=True)
-            hidden.requires_grad_(True)
-            flows[-1] = ops.raft_tail_attach([(flows[-1], hidden, low)], *self.head_params())[0]
-            return (flows, hidden, context) + ((low,) if ret_lowres else ())
-        iters = self.iters if iters is None else iters
+        ``grad_heads`` / ``grad_update`` / ``grad_corr`` (each implies the one before): the pass runs as ever, gradient-free, as grad_pass
+        runs it, and the returned LAST prediction is the output of one autograd node (raft_grad.attach) whose backward goes as far as
+        the output heads / the whole update block through time / the correlation.  raft_grad's module docstring says what each stage
+        saves, costs, differentiates and refuses.  ``hidden`` comes back as a leaf that requires grad (.grad = d loss / d net_N); behind
+        the result grad_update appends the leaves ``net_0`` (N,128,h8,w8) and ``inp`` (a leaf copy of the context), grad_corr also
+        ``fmap1`` and ``fmap2`` (leaf copies of the maps the pass correlated)."""
+        stages = 'corr' if grad_corr else 'update' if grad_update else 'heads' if grad_heads else None
+        if stages is not None:
+            self.check_grad(stages, upsample)                  # (before the encoders run: a refused pass launches nothing)
+        fmaps, cnet, route = self._encoded(image1, image2, fmaps, cnet)
+        if stages is None:
+            return self._forward_impl(route, fmaps, cnet, upsample, iters, all_flows, flow_init, ret_lowres)
+        (flows, _, context, low), rec = self.grad_pass(fmaps, cnet, stages=stages, upsample=upsample, iters=iters, all_flows=all_flows, flow_init=flow_init)
+        rec = rec.rows(0, rec.hidden.shape[0])
+        flows[-1] = raft_grad.attach([rec], self.head_params(), None if stages == 'heads' else self.update_params())[0]
+        leaves = tuple(t for t in (rec.net0, rec.inp, rec.fmap1, rec.fmap2) if t is not None)
+        return (flows, rec.hidden, context) + ((low,) if ret_lowres else ()) + leaves
+
+    def _encoded(self, image1, image2, fmaps, cnet):
+        """What forward's caller did not bring of the encoder outputs -> ((fmap1, fmap2), cnet, the pass's Route)."""
         if image1 is None:                                    # encoder outputs given: the images are not needed again
-            (N, _, h8, w8), dev = fmaps[0].shape, fmaps[0].device
-            route = self._route(map_size=(h8, w8))
+            route = self._route(map_size=tuple(fmaps[0].shape[-2:]))
         else:
-            (N, _, H, W), dev = image1.shape, image1.device
-            h8, w8 = H // 8, W // 8
-            route = self._route(image_size=(H, W))            # (before the encoders run: a refused pass launches nothing)
+            route = self._route(image_size=tuple(image1.shape[-2:]))       # (before the encoders run: a refused pass launches nothing)
         if fmaps is None:
+            N = image1.shape[0]
             f = self._encode(self.fnet, (image1, image2), route).float()
-            fmap1, fmap2 = f[:N], f[N:]
-        else:
-            fmap1, fmap2 = fmaps                              # precomputed by encode_features (caller de-duplicates)
-        if _fmaps is not None:                                # (grad_corr: what the pass correlates)
-            _fmaps.extend((fmap1, fmap2))
+            fmaps = f[:N], f[N:]                              # (else precomputed by encode_features: the caller de-duplicates)
         if cnet is None:
             cnet = self._encode(self.cnet, image1, route, split_act=True)       # (tanh(net) | relu(inp))
+        return fmaps, cnet, route
+
+    def _forward_impl(self, route, fmaps, cnet, upsample=True, iters=None, all_flows=False, flow_init=None, ret_lowres=False, states=None):
+        """forward on the encoder outputs under ``route``.  ``states`` (grad_pass): a list that receives every iteration's entry state
+        (_save_state); the copies sit between the iterations, so such a pass is neither recorded nor run as one launch list."""
+        iters = self.iters if iters is None else iters
+        fmap1, fmap2 = fmaps
+        (N, _, h8, w8), dev = fmap1.shape, fmap1.device
         c = self.hidden_dim
         if flow_init is not None:
             if tuple(flow_init.shape) != (N, 2, h8, w8) or flow_init.dtype != torch.float32 or flow_init.device != dev:
@@ -1320,7 +1287,7 @@ class RAFT(nn.Module):
         P = ub.packed_convs((padded or (h8, w8))[1])
         fused = P is not None
         if fused and FRAME_OPLISTS and LOOP_OPLIST and not all_flows and N <= FRAME_OPLISTS_MAX_IMAGES and LOOKUP_EVENT_SINK is None \
-                and _states is None:                           # (grad_update: the state copies sit between the iterations)
+                and states is None:                           # (grad_update: the state copies sit between the iterations)
             r = self._forward_recorded(route, fmap1, fmap2, cnet, iters, upsample, flow_init, ret_lowres)
             if r is not None:
                 return tail([r[0]], r[1], r[2])
@@ -1332,19 +1299,19 @@ class RAFT(nn.Module):
         side = self._side_stream(dev) if fused and SIDE_STREAM and N * h8 * w8 <= SIDE_STREAM_MAX else None
         if fused and LOOP_OPLIST:                             # the loop as a launch list: whole, or iteration by iteration for their flows
             prog, marks, streams = self._run_loop(pyr, ws, iters, side)
-            if not all_flows and _states is None:
+            if not all_flows and states is None:
                 prog.run(streams)
-            for itr in range(iters if all_flows or _states is not None else 0):
-                if _states is not None:
-                    self._save_state(ws, _states)
+            for itr in range(iters if all_flows or states is not None else 0):
+                if states is not None:
+                    self._save_state(ws, states)
                 prog.run(streams, marks[itr], marks[itr + 1])
                 if all_flows and itr < iters - 1:
                     flow_predictions.append(self._prediction(ws['flow'], hx, upsample, ws['valid']))
         elif fused:                                           # the same launches, one by one from Python
             for itr in range(iters):
                 done = None
-                if _states is not None:
-                    self._save_state(ws, _states)
+                if states is not None:
+                    self._save_state(ws, states)
                 if side is not None:
                     # the motion encoder's flow branch (convf1 -> convf2) needs only the flow: it runs on a side stream beside
                     # lookup -> convc1 -> convc2 and fills the partly idle last rounds of those launches
@@ -1368,8 +1335,8 @@ class RAFT(nn.Module):
         for itr in range(iters):
             pyr.lookup(coords1, out=corr)
             flow = flow_init if itr == 0 and flow_init is not None else coords1 - coords0
-            if _states is not None:
-                self._save_state(ws, _states, flow, coords1)
+            if states is not None:
+                self._save_state(ws, states, flow, coords1)
             coords1 = ub.step(ws, ctx, flow, coords1, h_buf)
             if all_flows or itr == iters - 1:
                 lowres = coords1 - coords0

@@ -9,7 +9,7 @@ by the up-sampling's definition).  Its forward is pinned to tests/raft_ops_ref.u
 import torch
 import torch.nn.functional as F
 
-PARAMS = ('fh1_w', 'fh1_b', 'fh2_w', 'fh2_b', 'm0_w', 'm0_b', 'm2_w', 'm2_b')          # ops.raft_tail_backward's order
+PARAMS = ('fh1_w', 'fh1_b', 'fh2_w', 'fh2_b', 'm0_w', 'm0_b', 'm2_w', 'm2_b')          # raft_grad.raft_tail_backward's order
 
 
 def upsample_convex(flow, mask):

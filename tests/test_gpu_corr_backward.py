@@ -1,4 +1,4 @@
-"""GPU: the backward of the correlation (csrc/corr_backward.hip; ops.corr_lookup_backward, ops.corr_build_backward, ops.update_step_backward's
+"""GPU: the backward of the correlation (csrc/corr_backward.hip; ops.corr_lookup_backward, ops.corr_build_backward, raft_grad.update_step_backward's
 ``ret_d_corr``, RAFT.forward(grad_corr=True), PoseNet.forward(grad_corr=True)).  Truth is the float64 restatement tests/corr_grad_ref.py (pinned
 to autograd through oracle.raft.CorrBlock by tests/test_corr_grad_ref_cpu.py) or float64 autograd, on the CPU.
 
@@ -152,7 +152,7 @@ def _hx(net, flow):
 
 
 def test_ret_d_corr_against_float64_and_flag_off_bits(rpe):
-    from rpe_amd import ops
+    from rpe_amd.raft_grad import update_step_backward as step
     shape, seed = (1, 8, 12), 41
     P, c = ubref.make_params(seed), ubref.make_case(*shape, seed)
     assert ubref.relu_margin(c, P) > 1e-5
@@ -164,7 +164,7 @@ def test_ret_d_corr_against_float64_and_flag_off_bits(rpe):
     w64, w32 = d_corr(torch.float64), d_corr(torch.float32)
     params = tuple(P[k].to(DEV) for k in ubref.PARAMS)
     args = (_hx(c['net'], c['flow'][0]), c['inp'].to(DEV), c['corr'][0].to(DEV), c['d_net'].to(DEV), params)
-    on, off, plain = ops.update_step_backward(*args, ret_d_corr=True), ops.update_step_backward(*args, ret_d_corr=False), ops.update_step_backward(*args)
+    on, off, plain = step(*args, ret_d_corr=True), step(*args, ret_d_corr=False), step(*args)
     assert len(on) == 4 and len(off) == len(plain) == 3 and tuple(on[3].shape) == (1, 324, 8, 12)
     for r in (on, off):
         assert torch.equal(r[0], plain[0]) and torch.equal(r[1], plain[1]) and len(r[2]) == 22 and all(torch.equal(a, b) for a, b in zip(r[2], plain[2]))
@@ -228,7 +228,7 @@ def test_grad_corr_through_time_against_float64(rpe, raft_model):
         assert len(pa) == 30 and all(torch.equal(a, b) for a, b in zip(pa, pb))
         f1, f2 = ra[6], ra[7]
         assert bool(torch.isfinite(f1.grad).all()) and bool(torch.isfinite(f2.grad).all()) and float(f1.grad.abs().max()) > 0 and float(f2.grad.abs().max()) > 0
-        states = node.saved[0][0]
+        states = node.passes[0].states
         coords, flows = [co.cpu() for _, co in states], [st[:, 254:].cpu() for st, _ in states]
         Pu = {k: p.detach().cpu() for k, p in zip(ubref.PARAMS, upd)}
         Pt = {k: p.detach().cpu() for k, p in zip(tref.PARAMS, fh + mk)}

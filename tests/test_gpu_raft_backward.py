@@ -1,4 +1,4 @@
-"""GPU: the backward of RAFT's output heads (csrc/raft_backward.hip, ops.raft_tail_backward, RAFT.forward(grad_heads=True),
+"""GPU: the backward of RAFT's output heads (csrc/raft_backward.hip, raft_grad.raft_tail_backward, RAFT.forward(grad_heads=True),
 PoseNet.freeze_flow(False, parts='heads')).  Truth is float64 autograd on the CPU over the restatement tests/raft_tail_ref.py.
 Bounds: where a result is a plain sum of products, the derived per-element bound n * 2^-24 * sum |a| |b| (n = terms + partials: any f32
 summation order satisfies it, an indexing error does not); elsewhere the project's usual rule, twice the error of the same restatement run
@@ -114,15 +114,15 @@ def test_weight_gradient_on_channel_slices(rpe):
 def test_backward_data_through_the_transposed_packings(rpe, hh, ww):
     """dX = conv(dY; W^T flipped) on the forward's kernels: the tuned route (8x12: rpe_conv_fused) and the generic one (5x7:
     rpe_conv_direct), each on groups of input channels added in f64; the group sum itself; and the small kernels."""
-    from rpe_amd import ops
+    from rpe_amd import ops, raft_grad
     P = {k: v.to(DEV) for k, v in ref.make_params(128, 256, seed=23).items()}
     fh, mk = tuple(P[k] for k in ref.PARAMS[:4]), tuple(P[k] for k in ref.PARAMS[4:])
-    T = ops._tail_packed(fh, mk)
+    T = raft_grad._packed(raft_grad._TailPacked, fh + mk)
     g = _gen(29)
     b = 2
     # the two 256 -> 128 3x3 layers, stacked: d_net = conv_T(g_f; fh1) + conv_T(g_m; m0)
     gg = torch.randn(b, 512, hh, ww, generator=g)
-    d_net = T.conv_split('w3t', gg.to(DEV), T.w3t, None, False, ops.TAIL_GROUP_3X3_BWD).cpu().double()
+    d_net = T.conv_split('w3t', gg.to(DEV), T.w3t, None, False, raft_grad.TAIL_GROUP_3X3_BWD).cpu().double()
     wf, wm = P['fh1_w'].cpu().double(), P['m0_w'].cpu().double()
     want = F.conv_transpose2d(gg[:, :256].double(), wf, padding=1) + F.conv_transpose2d(gg[:, 256:].double(), wm, padding=1)
     bound = F.conv_transpose2d(gg[:, :256].double().abs(), wf.abs(), padding=1) + F.conv_transpose2d(gg[:, 256:].double().abs(), wm.abs(), padding=1)
@@ -131,7 +131,7 @@ def test_backward_data_through_the_transposed_packings(rpe, hh, ww):
     assert bool((err <= 512 * 9 * U * bound).all())
     # the 576 -> 256 1x1 layer (x 0.25)
     gm = torch.randn(b, 576, hh, ww, generator=g)
-    out = T.conv_split('w1t', gm.to(DEV), T.w1t, None, False, ops.TAIL_GROUP_1X1)
+    out = T.conv_split('w1t', gm.to(DEV), T.w1t, None, False, raft_grad.TAIL_GROUP_1X1)
     w2 = 0.25 * P['m2_w'].cpu().double()
     want, bound = F.conv_transpose2d(gm.double(), w2), F.conv_transpose2d(gm.double().abs(), w2.abs())
     assert bool(((out.cpu().double() - want).abs() <= 576 * U * bound).all())
@@ -164,19 +164,19 @@ TAIL_CASES = [((2, 8, 12), 319), ((1, 5, 7), 5)]
 
 @pytest.mark.parametrize('shape,seed', TAIL_CASES)
 def test_whole_tail_against_float64(rpe, shape, seed):
-    """ops.raft_tail_backward against the float64 restatement under the twice-float32 rule, all nine results.  (With the forward kernels run
+    """raft_grad.raft_tail_backward against the float64 restatement under the twice-float32 rule, all nine results.  (With the forward kernels run
     over all input channels at once, d_net, fh2_w and m2_w came out at 2.3 - 4.4 times the float32 figure -- their k-ordered f32 sums of
     1152 and 4608 terms --; on groups of input channels added in f64 every result is at 0.1 - 1.6 times it.)"""
-    from rpe_amd import ops
+    from rpe_amd import raft_grad
     P = ref.make_params(128, 256, seed)
     c = ref.make_case(*shape, 128, seed)
     assert ref.relu_margin(c['net'], P) > 1e-5
     dn64, g64, low64, _ = ref.tail_grads(c, P, torch.float64)
     dn32, g32, _, _ = ref.tail_grads(c, P, torch.float32)
     Pd = {k: v.to(DEV) for k, v in P.items()}
-    d_net, grads = ops.raft_tail_backward(c['net'].to(DEV), low64.float().to(DEV), c['grad_up'].to(DEV), tuple(Pd[k] for k in ref.PARAMS[:4]),
+    d_net, grads = raft_grad.raft_tail_backward(c['net'].to(DEV), low64.float().to(DEV), c['grad_up'].to(DEV), tuple(Pd[k] for k in ref.PARAMS[:4]),
                                           tuple(Pd[k] for k in ref.PARAMS[4:]))
-    again = ops.raft_tail_backward(c['net'].to(DEV), low64.float().to(DEV), c['grad_up'].to(DEV), tuple(Pd[k] for k in ref.PARAMS[:4]),
+    again = raft_grad.raft_tail_backward(c['net'].to(DEV), low64.float().to(DEV), c['grad_up'].to(DEV), tuple(Pd[k] for k in ref.PARAMS[:4]),
                                    tuple(Pd[k] for k in ref.PARAMS[4:]))
     assert torch.equal(d_net, again[0]) and all(torch.equal(a, b) for a, b in zip(grads, again[1]))
     missed = []
@@ -199,8 +199,8 @@ def raft_model(rpe):
 def test_grad_heads_is_the_plain_pass_plus_one_node(rpe, raft_model, h, w):
     """(128,160): 16 x 20 maps, the tuned route; (136,168): 17 x 21 maps, the generic route -- the smallest maps of either kind a RAFT pass takes
     (the correlation's four levels need a 1/8 map of at least 16 x 16: 64 x 96 and 72 x 104 images are refused by both correlation routes).  Predictions and hidden state are the plain pass's bits; after a backward the eight .grads and
-    hidden.grad are the bits of a direct ops.raft_tail_backward call on the pass's own outputs."""
-    from rpe_amd import ops
+    hidden.grad are the bits of a direct raft_grad.raft_tail_backward call on the pass's own outputs."""
+    from rpe_amd import raft_grad
     g = _gen(31)
     im1, im2 = (255.0 * torch.rand(2, 3, h, w, generator=g)).to(DEV), (255.0 * torch.rand(2, 3, h, w, generator=g)).to(DEV)
     G = torch.randn(2, 2, h, w, generator=g).to(DEV)
@@ -214,7 +214,7 @@ def test_grad_heads_is_the_plain_pass_plus_one_node(rpe, raft_model, h, w):
     assert torch.equal(flows[-1], plain[0][-1]) and torch.equal(hidden, plain[1]) and torch.equal(context, plain[2]) and torch.equal(low, plain[3])
     assert hidden.is_leaf and hidden.requires_grad and flows[-1].requires_grad
     (flows[-1] * G).sum().backward()
-    d_net, grads = ops.raft_tail_backward(plain[1], plain[3], G, fh, mk)
+    d_net, grads = raft_grad.raft_tail_backward(plain[1], plain[3], G, fh, mk)
     assert torch.equal(hidden.grad, d_net)
     for p, want in zip(fh + mk, grads):
         assert p.grad is not None and bool(torch.isfinite(p.grad).all()) and float(p.grad.abs().max()) > 0.0 and torch.equal(p.grad, want)
@@ -261,7 +261,7 @@ def _step(model, a, target, **kw):
 
 
 def test_posenet_trains_the_output_heads(rpe):
-    from rpe_amd import ops
+    from rpe_amd import raft_grad
     model, a = _posenet_case()
     target = torch.tensor([[0.004, -0.003, 0.002, 0.01, -0.008, 0.006]], device=DEV)
     with torch.backends.cudnn.flags(enabled=True, benchmark=False, deterministic=True):      # (the module route of the weight heads)
@@ -279,15 +279,15 @@ def test_posenet_trains_the_output_heads(rpe):
         hid = flows['hidden']
         n = 1
         with torch.no_grad():
-            d1, sf1, v1, tail1 = model.flow2depth(a['image1l'], a['image2r'], a['baseline'].expand(1).contiguous(), ret_tail=True)
+            d1, sf1, v1, pass1 = model.flow2depth(a['image1l'], a['image2r'], a['baseline'].expand(1).contiguous(), grad='heads')
             f, cn = model._encode_both((a['image1l'], a['image2l'], a['image2r']), (a['image1l'], a['image2l']))
             r = model.flow(None, None, upsample=True, fmaps=(f[:2 * n], f[n:]), cnet=cn, ret_lowres=True)
         assert torch.equal(sf1, flows['stereo_flow1']) and torch.equal(r[0][-1][:n], flows['time_flow']) and torch.equal(r[0][-1][n:], flows['stereo_flow2'])
         fh, mk = model.flow.head_params()
-        passes = [(flows['time_flow'].grad, r[1][:n], r[3][:n]), (flows['stereo_flow1'].grad, tail1[0], tail1[1]), (flows['stereo_flow2'].grad, r[1][n:], r[3][n:])]
+        passes = [(flows['time_flow'].grad, r[1][:n], r[3][:n]), (flows['stereo_flow1'].grad, pass1.hidden.detach(), pass1.flow_low), (flows['stereo_flow2'].grad, r[1][n:], r[3][n:])]
         total, d_nets = None, []
         for gup, net, low in passes:
-            d_net, pg = ops.raft_tail_backward(net.contiguous(), low.contiguous(), gup.contiguous(), fh, mk)
+            d_net, pg = raft_grad.raft_tail_backward(net.contiguous(), low.contiguous(), gup.contiguous(), fh, mk)
             d_nets.append(d_net)
             total = list(pg) if total is None else [x + y for x, y in zip(total, pg)]
         for p, want in zip(fh + mk, total):

@@ -1,4 +1,4 @@
-"""GPU: the backward of RAFT's update block through time (csrc/update_backward.hip, ops.update_step_backward, ops.update_bptt_attach,
+"""GPU: the backward of RAFT's update block through time (csrc/update_backward.hip, raft_grad.update_step_backward, raft_grad.attach,
 RAFT.forward(grad_update=True), PoseNet.freeze_flow(False, parts='update')).  Truth is float64 autograd on the CPU over the restatement
 tests/update_block_ref.py.  Bounds as in test_gpu_raft_backward.py: where a result is a plain sum of products, the derived per-element
 bound n * 2^-24 * sum |a| |b| (n = terms + partials); elsewhere twice the error of the same restatement run in float32 on the CPU, relative
@@ -175,14 +175,14 @@ def _named(d_net, d_inp, grads):
 @pytest.mark.parametrize('shape,seed', STEP_CASES)
 def test_one_step_against_float64(rpe, shape, seed):
     """(1,8,12): the tuned route (rpe_conv_fused on groups), (1,5,7): the generic one (rpe_conv_direct) -- all 24 results."""
-    from rpe_amd import ops
+    from rpe_amd import raft_grad
     P, c = ref.make_params(seed), ref.make_case(*shape, seed)
     assert ref.relu_margin(c, P) > 1e-5
     w64, w32 = _named(*ref.step_grads(c, P, torch.float64)), _named(*ref.step_grads(c, P, torch.float32))
     params = tuple(P[k].to(DEV) for k in ref.PARAMS)
     args = (_hx(c['net'], c['flow'][0]), c['inp'].to(DEV), c['corr'][0].to(DEV), c['d_net'].to(DEV), params)
-    d_net, d_inp, grads = ops.update_step_backward(*args)
-    again = ops.update_step_backward(*args)
+    d_net, d_inp, grads = raft_grad.update_step_backward(*args)
+    again = raft_grad.update_step_backward(*args)
     assert len(grads) == 22 and torch.equal(d_net, again[0]) and torch.equal(d_inp, again[1]) and all(torch.equal(a, b) for a, b in zip(grads, again[2]))
     _check(f'one step {shape}', [('d_net_prev', d_net), ('d_inp', d_inp)] + list(zip(ref.PARAMS, grads)), w64, w32)
 
@@ -192,7 +192,7 @@ def test_bptt_against_float64_and_single_step_bits(rpe):
     """The chain the node runs behind the tail -- steps N .. 1 on the entry states, the gradients summed in descending k -- against float64
     autograd through all three steps; the node itself is held to this chain bit for bit by the plumbing tests below.  The entry states
     are the restatement's float64 ones, rounded.  One step of the chain IS the one-step op."""
-    from rpe_amd import ops
+    from rpe_amd import raft_grad
     shape, seed, steps = BPTT_CASE
     P, c = ref.make_params(seed), ref.make_case(*shape, seed, steps=steps)
     assert ref.relu_margin(c, P) > 1e-5
@@ -201,10 +201,10 @@ def test_bptt_against_float64_and_single_step_bits(rpe):
     nets = ref.states(c, P)
     states, corr = [_hx(nets[k].float(), c['flow'][k]) for k in range(steps)], [t.to(DEV) for t in c['corr']]
     inp, d = c['inp'].to(DEV), c['d_net'].to(DEV)
-    one = ops.update_step_backward(states[-1], inp, corr[-1], d, params)
+    one = raft_grad.update_step_backward(states[-1], inp, corr[-1], d, params)
     total, d_inp = None, None
     for k in reversed(range(steps)):
-        d, di, g = ops.update_step_backward(states[k], inp, corr[k], d, params)
+        d, di, g = raft_grad.update_step_backward(states[k], inp, corr[k], d, params)
         d_inp = di if d_inp is None else d_inp + di
         if k == steps - 1:
             assert torch.equal(d, one[0]) and torch.equal(di, one[1]) and all(torch.equal(a, b) for a, b in zip(g, one[2]))
@@ -232,7 +232,7 @@ def _grad_pass(model, im1, im2, G):
 def test_grad_update_is_the_plain_pass_plus_one_node(rpe, raft_model, h, w):
     """(128,160): 16 x 20 maps, the tuned route; (136,168): 17 x 21 maps, the generic one.  The pass's outputs, the saved states, the
     recomputed window and every gradient bit for bit against the plain passes and the hand chain."""
-    from rpe_amd import ops
+    from rpe_amd import raft_grad
     g = _gen(31)
     im1, im2 = (255.0 * torch.rand(2, 3, h, w, generator=g)).to(DEV), (255.0 * torch.rand(2, 3, h, w, generator=g)).to(DEV)
     G = torch.randn(2, 2, h, w, generator=g).to(DEV)
@@ -248,7 +248,7 @@ def test_grad_update_is_the_plain_pass_plus_one_node(rpe, raft_model, h, w):
         plain = model(im1, im2, ret_lowres=True)
         assert torch.equal(flows[-1], plain[0][-1]) and torch.equal(hidden, plain[1]) and torch.equal(context, plain[2]) and torch.equal(low, plain[3])
         assert all(t.is_leaf and t.requires_grad for t in (hidden, net0, inp)) and torch.equal(inp, plain[2])
-        states, corr_of = node.saved[0]
+        states, corr_of = node.passes[0].states, node.passes[0].corr
         assert len(states) == 3 and all(tuple(s.shape) == (2, 256, h // 8, w // 8) and tuple(co.shape) == (2, 2, h // 8, w // 8) for s, co in states)
         assert torch.equal(net0, states[0][0][:, :128]) and not bool(states[0][0][:, 254:].any())
         for k in (2, 3):                                                # h_{k-1}, flow_k = the results of a (k - 1)-iteration plain pass
@@ -256,11 +256,11 @@ def test_grad_update_is_the_plain_pass_plus_one_node(rpe, raft_model, h, w):
             assert torch.equal(states[k - 1][0][:, :128], short[1]) and torch.equal(states[k - 1][0][:, 254:], short[3]), k
         assert torch.equal(corr_of(2), last_corr)
         # the hand chain
-        d, pg = ops.raft_tail_backward(plain[1], plain[3], G, fh, mk)
+        d, pg = raft_grad.raft_tail_backward(plain[1], plain[3], G, fh, mk)
         assert torch.equal(hidden.grad, d)
         total, d_inp = None, None
         for k in (2, 1, 0):
-            d, di, sg = ops.update_step_backward(states[k][0], plain[2].contiguous(), corr_of(k), d, upd)
+            d, di, sg = raft_grad.update_step_backward(states[k][0], plain[2].contiguous(), corr_of(k), d, upd)
             d_inp = di if d_inp is None else d_inp + di
             total = list(sg) if total is None else [a + b for a, b in zip(total, sg)]
         assert torch.equal(net0.grad, d) and torch.equal(inp.grad, d_inp)
@@ -316,7 +316,7 @@ def _step(model, a, target, **kw):
 
 def test_posenet_trains_the_update_block(rpe):
     """Three iterations per pass (the chain's length does not change what is checked; twelve cost four times the launches)."""
-    from rpe_amd import ops
+    from rpe_amd import raft_grad
     model, a = _posenet_case()
     target = torch.tensor([[0.004, -0.003, 0.002, 0.01, -0.008, 0.006]], device=DEV)
     with torch.backends.cudnn.flags(enabled=True, benchmark=False, deterministic=True):      # (the module route of the weight heads)
@@ -328,7 +328,7 @@ def test_posenet_trains_the_update_block(rpe):
         out = model(a['image1l'], a['image2l'], a['K'], a['baseline'], a['image2r'], a['image2r'], mask1=a['mask1'], mask2=a['mask2'],
                     ret_confmap=True, ret_flows=True)
         node = out[-1]['time_flow'].grad_fn
-        lows = [node.saved_tensors[5 * i + 2] for i in range(3)]
+        lows = [rec.flow_low for rec in node.passes]
         (out[0] - target).abs().sum().backward()
         g_on = {k: p.grad.clone() for k, p in model.named_parameters() if p.grad is not None}
     ub = [(k, p) for k, p in model.named_parameters() if k.startswith('flow.update_block.')]
@@ -348,12 +348,12 @@ def test_posenet_trains_the_update_block(rpe):
     for i, key in enumerate(('time', 'stereo1', 'stereo2')):
         hidden, low, inp = flows['hidden'][key], lows[i], flows['inp'][key]
         gup = flows[('time_flow', 'stereo_flow1', 'stereo_flow2')[i]].grad
-        d, pg = ops.raft_tail_backward(hidden.detach(), low, gup.contiguous(), fh, mk)
-        states, corr_of = node.saved[i]
+        d, pg = raft_grad.raft_tail_backward(hidden.detach(), low, gup.contiguous(), fh, mk)
+        states, corr_of = node.passes[i].states, node.passes[i].corr
         assert len(states) == 3
         ug, d_inp = None, None
         for k in (2, 1, 0):
-            d, di, sg = ops.update_step_backward(states[k][0], inp.detach(), corr_of(k), d, upd)
+            d, di, sg = raft_grad.update_step_backward(states[k][0], inp.detach(), corr_of(k), d, upd)
             d_inp = di if d_inp is None else d_inp + di
             ug = list(sg) if ug is None else [x + y for x, y in zip(ug, sg)]
         assert torch.equal(flows['net0'][key].grad, d) and torch.equal(inp.grad, d_inp), key

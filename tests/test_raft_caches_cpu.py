@@ -1,4 +1,4 @@
-"""CPU: the weight-derived caches of raft.py (_cached / _wkey / _switches) with a stand-in for raft.ops whose packing classes count their
+"""CPU: the weight-derived caches of raft.py (_cached / wkey / _switches) with a stand-in for raft.ops whose packing classes count their
 constructions and need no library: nothing is rebuilt while nothing changes, a changed weight rebuilds exactly what was made from it, and
 every route switch invalidates the update block's packings."""
 import collections

@@ -26,7 +26,7 @@ def test_declared_bound_exported_minor_unchanged(rpe):
 
 def test_weight_gradient_kernel_sizes(rpe):
     """(1,5), (5,1), (7,7) join (3,3) and (1,1) under the same workspace rule; everything else is still refused, in the library and in ops."""
-    from rpe_amd import ops
+    from rpe_amd import ops, raft_grad
     from rpe_amd._lib import RpeError
     L = rpe.lib()
     f = L.rpe_conv_bwd_weight_workspace_bytes
@@ -46,7 +46,7 @@ def test_weight_gradient_kernel_sizes(rpe):
         for kernel in ((5, 5), (1, 3)):
             with pytest.raises(RpeError, match='unsupported shape'):
                 ops.conv_bwd_weight(x, dy, kernel)
-    assert len(ops.UPDATE_PARAMS) == 22 and ops.UPDATE_PARAMS[0] == 'gru.convz1.weight' and ops.UPDATE_PARAMS[-1] == 'encoder.conv.bias'
+    assert len(raft_grad.UPDATE_PARAMS) == 22 and raft_grad.UPDATE_PARAMS[0] == 'gru.convz1.weight' and raft_grad.UPDATE_PARAMS[-1] == 'encoder.conv.bias'
 
 
 def test_gate_entry_points_refuse_bad_arguments_without_a_gpu(rpe):

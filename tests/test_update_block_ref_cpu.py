@@ -60,7 +60,7 @@ def test_a_gradient_against_central_differences():
 
 
 def test_order_and_margin():
-    """PARAMS is ops.UPDATE_PARAMS' order; the margin is that of the five encoder ReLUs and does not depend on the hidden state."""
+    """PARAMS is raft_grad.UPDATE_PARAMS' order; the margin is that of the five encoder ReLUs and does not depend on the hidden state."""
     assert len(ref.PARAMS) == 22 and ref.PARAMS[:2] == ('z1_w', 'z1_b') and ref.PARAMS[12:14] == ('c1_w', 'c1_b') and ref.PARAMS[-1] == 'cv_b'
     P, c = ref.make_params(1), ref.make_case(1, 3, 4, 1)
     m = ref.relu_margin(c, P)

@@ -1,10 +1,10 @@
 """Test infrastructure: float64 / float32 CPU restatement of ONE application of RAFT's update block without its heads, and of N of them
 through time, with ``flow`` and ``corr`` as constants (upstream detaches coords1 at the top of every iteration) -- the truth
-ops.update_step_backward and the BPTT node are held to.  Pinned to oracle.raft.BasicUpdateBlock by tests/test_update_block_ref_cpu.py."""
+raft_grad.update_step_backward and the node through time are held to.  Pinned to oracle.raft.BasicUpdateBlock by tests/test_update_block_ref_cpu.py."""
 import torch
 import torch.nn.functional as F
 
-# (name, cout, cin, kh, kw) in ops.UPDATE_PARAMS' order: 12 tensors of the SepConvGRU, 10 of the motion encoder
+# (name, cout, cin, kh, kw) in raft_grad.UPDATE_PARAMS' order: 12 tensors of the SepConvGRU, 10 of the motion encoder
 LAYERS = (('z1', 128, 384, 1, 5), ('r1', 128, 384, 1, 5), ('q1', 128, 384, 1, 5), ('z2', 128, 384, 5, 1), ('r2', 128, 384, 5, 1),
           ('q2', 128, 384, 5, 1), ('c1', 256, 324, 1, 1), ('c2', 192, 256, 3, 3), ('f1', 128, 2, 7, 7), ('f2', 64, 128, 3, 3), ('cv', 126, 256, 3, 3))
 PARAMS = tuple(f'{n}_{t}' for n, *_ in LAYERS for t in ('w', 'b'))

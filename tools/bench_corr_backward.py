@@ -2,7 +2,7 @@
 NOTES.md quotes).  Median of --reps after --warmup, HIP events around each call, everything in one process:
   * one ops.corr_lookup_backward (the lookup's adjoint of one iteration into the gradient volume G),
   * one ops.corr_build_backward (the pool, the two GEMMs with their second passes, the pool adjoints),
-  * one ops.update_step_backward with and without ``ret_d_corr``,
+  * one raft_grad.update_step_backward with and without ``ret_d_corr``,
   * a whole pass and its backward through time with ``grad_update`` (the parent's "backward (tail + 12 steps)") and with ``grad_corr``.
 G is S h8 w8 4 bytes per pair (139 MB at 640x512).  Prints one JSON line."""
 import argparse
@@ -28,7 +28,7 @@ def main():
     ap.add_argument('--warmup', type=int, default=1)
     a = ap.parse_args()
     import rpe_amd  # noqa: F401
-    from rpe_amd import ops, raft, synth
+    from rpe_amd import ops, raft, raft_grad, synth
     dev = 'cuda'
     b, hh, ww = a.pairs, a.height // 8, a.width // 8
     g = torch.Generator().manual_seed(0)
@@ -45,8 +45,8 @@ def main():
     model = synth.init_synthetic_weights(raft.RAFT(synth.model_config(a.height, a.width, iters=a.iters))).eval().to(dev)
     upd = model.update_params()
     hx, inp, corr, d_net = r(b, 256, hh, ww), torch.relu(r(b, 128, hh, ww)), r(b, 324, hh, ww), r(b, 128, hh, ww)
-    out['update_step_backward_ms'] = T(lambda: ops.update_step_backward(hx, inp, corr, d_net, upd))
-    out['update_step_backward_d_corr_ms'] = T(lambda: ops.update_step_backward(hx, inp, corr, d_net, upd, ret_d_corr=True))
+    out['update_step_backward_ms'] = T(lambda: raft_grad.update_step_backward(hx, inp, corr, d_net, upd))
+    out['update_step_backward_d_corr_ms'] = T(lambda: raft_grad.update_step_backward(hx, inp, corr, d_net, upd, ret_d_corr=True))
     im1, im2 = (255.0 * torch.rand(b, 3, a.height, a.width, generator=g)).to(dev), (255.0 * torch.rand(b, 3, a.height, a.width, generator=g)).to(dev)
     G = r(b, 2, a.height, a.width)
     for p in model.head_params()[0] + model.head_params()[1] + upd:

@@ -1,6 +1,6 @@
 """Backward of RAFT's output heads at the bench geometry: 640x512 (64x80 maps), 48 rows (n = 16 x three passes).
 Median of 30 after 5 warm-ups, HIP events around each call, everything in one process:
-  * every kernel of the tail backward (csrc/raft_backward.hip) and the whole of ops.raft_tail_backward,
+  * every kernel of the tail backward (csrc/raft_backward.hip) and the whole of raft_grad.raft_tail_backward,
   * the weight-gradient GEMM's share of the f32 matrix peak (256 CUs x 4 SIMDs x 64 FLOP / clock at the clock given with --mhz),
   * the same tail's backward through PyTorch-ROCm autograd (conv2d, unfold, softmax).
 Prints one JSON line."""
@@ -40,7 +40,7 @@ def main():
     ap.add_argument('--mhz', type=float, default=2400.0, help='matrix clock assumed for the peak')
     a = ap.parse_args()
     import rpe_amd  # noqa: F401
-    from rpe_amd import ops
+    from rpe_amd import ops, raft_grad
     dev = 'cuda'
     b, hh, ww = a.rows, a.h8, a.w8
     g = torch.Generator().manual_seed(0)
@@ -57,7 +57,7 @@ def main():
     out['wgrad_3x3_256_2_ms'] = T(lambda: ops.conv_bwd_weight(t_f, low, (3, 3)))
     out['to2_bwd_data_ms'] = T(lambda: ops.conv3x3_to2_bwd_data(low, fh[2], act=t_f, out=g512[:, :256]))
     out['relu_backward_ms'] = T(lambda: ops.relu_backward(g512[:, 256:], t_m))
-    out['tail_backward_ms'] = T(lambda: ops.raft_tail_backward(net, low, gup, fh, mk))
+    out['tail_backward_ms'] = T(lambda: raft_grad.raft_tail_backward(net, low, gup, fh, mk))
     peak = 256 * 4 * 64 * a.mhz * 1e6
     flops = 2.0 * b * hh * ww * 512 * 128 * 9
     out['wgrad_3x3_tflops'] = flops / (out['wgrad_3x3_128_512_ms'] * 1e-3) / 1e12

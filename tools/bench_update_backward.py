@@ -1,7 +1,7 @@
 """Backward of RAFT's update block at the bench geometry: 640x512 (64x80 maps), with --pairs flow pairs in one pass (2 and 16 are the
 figures NOTES.md quotes).  Median of --reps after --warmup, HIP events around each call, everything in one process:
   * every new kernel (csrc/update_backward.hip): the weight-gradient GEMM at 1x5 / 5x1 / 7x7 and the four gate kernels,
-  * one ops.update_step_backward,
+  * one raft_grad.update_step_backward,
   * a whole pass with ``grad_update`` (12 iterations) and its backward through time, beside the plain forward of the same pass.
 Prints one JSON line."""
 import argparse
@@ -39,7 +39,7 @@ def main():
     ap.add_argument('--warmup', type=int, default=2)
     a = ap.parse_args()
     import rpe_amd  # noqa: F401
-    from rpe_amd import ops, raft, synth
+    from rpe_amd import ops, raft, raft_grad, synth
     dev = 'cuda'
     b, hh, ww = a.pairs, a.height // 8, a.width // 8
     g = torch.Generator().manual_seed(0)
@@ -58,7 +58,7 @@ def main():
     model = synth.init_synthetic_weights(raft.RAFT(synth.model_config(a.height, a.width, iters=a.iters))).eval().to(dev)
     upd = model.update_params()
     hx, inp, corr, d_net = r(b, 256, hh, ww), torch.relu(r(b, 128, hh, ww)), r(b, 324, hh, ww), r(b, 128, hh, ww)
-    out['update_step_backward_ms'] = T(lambda: ops.update_step_backward(hx, inp, corr, d_net, upd))
+    out['update_step_backward_ms'] = T(lambda: raft_grad.update_step_backward(hx, inp, corr, d_net, upd))
     im1, im2 = (255.0 * torch.rand(b, 3, a.height, a.width, generator=g)).to(dev), (255.0 * torch.rand(b, 3, a.height, a.width, generator=g)).to(dev)
     G = r(b, 2, a.height, a.width)
     for p in model.head_params()[0] + model.head_params()[1] + upd:
