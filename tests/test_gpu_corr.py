@@ -75,17 +75,14 @@ def test_lookup_taps_bit_exact(rpe):
     coords = coords_for(11, b, h8, w8, 3.0)
     x0, y0 = pyr.taps(coords.cuda())
     x0, y0 = x0.cpu().numpy(), y0.cpu().numpy()
+    from corr_ref import tap_floor_f32                                       # the numpy f32 restatement (moved to tests/corr_ref.py)
     c = coords.numpy().reshape(b, 2, -1)
-    one, two = np.float32(1), np.float32(2)
     for l in range(4):
         wl, hl = w8 >> l, h8 >> l
-        for i in range(9):
-            d = np.float32(i - 4)
-            for axis, size, got in ((0, wl, x0), (1, hl, y0)):
-                v = c[:, axis] / np.float32(2 ** l) + d
-                g = two * v / np.float32(size - 1) - one
-                pos = ((g + one) / two) * np.float32(size - 1)
-                assert np.array_equal(got[:, l, i], np.floor(pos).astype(np.int32)), (l, i, axis)
+        for axis, size, got in ((0, wl, x0), (1, hl, y0)):
+            floor_pos = tap_floor_f32(c[:, axis], size, l)[0]
+            for i in range(9):
+                assert np.array_equal(got[:, l, i], floor_pos[i]), (l, i, axis)
 
 
 def test_lookup_handles_nonfinite_and_far_coords(rpe):
