@@ -1,18 +1,29 @@
-// The convolution weight gradient's GEMM on the f32 matrix cores, shared by raft_backward.hip (3x3, 1x1) and update_backward.hip (1x5, 5x1,
-// 7x7): the split of K, the tile constants and the kernel body.
+// What the split-K GEMMs of the training backward share, whatever their operands: part = A B^T per chunk of the contraction axis on the f32
+// matrix cores, then a second pass that adds the chunks' partials.  The users are the convolution weight gradient (raft_backward.hip, all five
+// kernel sizes) and the two GEMMs of the correlation build's adjoint (corr_backward.hip).
+//   split_chunk / split_chunks   the chunk of the contraction axis, a function of its length alone (part of the result's bits)
+//   BW_*, f32x16                 the tile: 128 x 128 x 32 per workgroup, LDS pitch, the accumulator type
+//   bw_gemm_body<KH, KW>         the weight gradient's tile over one chunk: stage, multiply, store the partial
+//   k_splitk_reduce              out = scale * the partials added in chunk order in f64, rounded once
+// k_cb_gemm (corr_backward.hip) keeps a main loop of its own with the same tile: one loop over a loader object was tried and moved the
+// register allocation of every instantiation (NOTES.md), so the two loops stay apart until that can be done at equal registers.
 #pragma once
 #include <type_traits>
 #include "rpe_common.h"
 
-static inline long long bw_chunk(long long K) {
-    long long c = ((K + 63) / 64 + 31) / 32 * 32;                 // at most 64 chunks, whole 32-pixel steps
-    return c < 1024 ? 1024 : c;                                   // ... of at least 1024 pixels
+// at most max_chunks chunks of whole 32-steps, each at least min_len long
+static inline long long split_chunk(long long K, int max_chunks, int min_len) {
+    const long long c = ((K + max_chunks - 1) / max_chunks + 31) / 32 * 32;
+    return c < min_len ? min_len : c;
 }
-static inline int bw_chunks(long long K) { return (int)((K + bw_chunk(K) - 1) / bw_chunk(K)); }
+static inline int split_chunks(long long K, int max_chunks, int min_len) {
+    const long long c = split_chunk(K, max_chunks, min_len);
+    return (int)((K + c - 1) / c);
+}
 
-#define BW_BM 128                 // output channels per workgroup
-#define BW_BN 128                 // (input channel, tap) pairs per workgroup
-#define BW_BK 32                  // pixels per step
+#define BW_BM 128                 // rows of A (M) per workgroup: output channels
+#define BW_BN 128                 // rows of B (N) per workgroup: (input channel, tap) pairs
+#define BW_BK 32                  // k per step: pixels
 #define BW_LD (BW_BK + 4)         // LDS row pitch in floats: 16-byte aligned rows, 4-float reads of a lane's k-run
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -21,8 +32,8 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // once per step and a load is coalesced along the pixels; a tap outside the map (or a row / pixel outside the problem) is read from a
 // clamped address and SELECTED to zero.  K is permuted inside a step (lane half h takes pixels 16 h .. 16 h + 15 of the step, for BOTH
 // operands): a sum does not care, and a lane's operands of four consecutive instructions are one 16-byte LDS read.
-// The body is a device function over (KH, KW) -- tap t = (t / KW - KH / 2, t % KW - KW / 2) -- so that the kernels of raft_backward.hip (3x3, 1x1)
-// and of update_backward.hip (1x5, 5x1, 7x7) are one piece of code; sA / sB: BW_BM * BW_LD and BW_BN * BW_LD floats of LDS, 16-byte aligned.
+// The body is a device function over (KH, KW) -- tap t = (t / KW - KH / 2, t % KW - KW / 2) --, one piece of code for the five kernel sizes of
+// raft_backward.hip's k_bw_gemm; sA / sB: BW_BM * BW_LD and BW_BN * BW_LD floats of LDS, 16-byte aligned.
 template <int KH, int KW>
 __device__ __forceinline__ void bw_gemm_body(const float* __restrict__ x, long long xbs, const float* __restrict__ dy, long long dybs, int cin,
                                              int cout, int h, int w, long long K, long long kc, float* __restrict__ part, float* sA, float* sB) {
@@ -122,7 +133,16 @@ __device__ __forceinline__ void bw_gemm_body(const float* __restrict__ x, long l
         }
 }
 
-// The kernel sizes beyond 3x3 and 1x1 ('same' padding (0,2), (2,0), (3,3)) and the launch of their first pass (update_backward.hip)
-static inline bool bw_ext_kernel(int kh, int kw) { return (kh == 1 && kw == 5) || (kh == 5 && kw == 1) || (kh == 7 && kw == 7); }
-bool bw_gemm_launch_ext(const float* x, long long xbs, const float* dy, long long dybs, int cin, int cout, int h, int w, int kh, int kw,
-                        long long K, long long kc, int chunks, float* part, hipStream_t s);
+// out[bz][e] = (float)(scale * sum_c part[bz][c][e]), e < per: c in index order, in f64, one rounding.  grid (blocks, batch), any block count.
+static __global__ __launch_bounds__(256) void k_splitk_reduce(const float* __restrict__ part, int chunks, size_t per, double scale,
+                                                              float* __restrict__ out) {
+    const int bz = blockIdx.y;
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < per; e += (size_t)gridDim.x * 256) {
+        double s = 0.0;
+        for (int c = 0; c < chunks; ++c) s += (double)part[((size_t)bz * chunks + c) * per + e];
+        out[(size_t)bz * per + e] = (float)(scale * s);
+    }
+}
+static inline void splitk_reduce_launch(const float* part, int batch, int chunks, long long per, double scale, float* out, hipStream_t s) {
+    hipLaunchKernelGGL(k_splitk_reduce, dim3(min(ceil_div(per, 256), 2048), batch), dim3(256), 0, s, part, chunks, (size_t)per, scale, out);
+}

@@ -12,16 +12,17 @@
 //                      dropped (grid_sample's zero padding).  One wave owns a query's row of G: no atomics, the stream orders the calls.
 //   k_cb_pool          F2cat (b, c, S): fmap2 followed by its successively 2x2-pooled copies (floor: a last odd row / column is dropped).
 //                      Pooling is linear: avg_pool2d of the correlation over the second image = correlating against the pooled fmap2.
-//   k_cb_gemm          the two GEMMs on the f32 matrix cores (v_mfma_f32_32x32x2_f32), tiles as bw_gemm.h's:
+//   k_cb_gemm          the two GEMMs on the f32 matrix cores (v_mfma_f32_32x32x2_f32), bw_gemm.h's tile constants under a main loop of this file's:
 //                          d_fmap1 = F2cat G^T / sqrt(c)   (c x S by S x h8 w8: contraction over S)
 //                          dF2cat  = fmap1 G / sqrt(c)     (c x h8 w8 by h8 w8 x S: contraction over the queries)
-//                      the contraction axis is split by cb_chunk(K), a function of the shape alone; every chunk writes a partial
-//   k_cb_reduce        the partials added in chunk order in f64, times 1 / sqrt(c), rounded once
+//                      the contraction axis is split by split_chunk(K, 8, 512), a function of the shape alone; every chunk writes a partial
+//   k_splitk_reduce    (bw_gemm.h) the partials added in chunk order in f64, times 1 / sqrt(c), rounded once
 //   k_cb_unpool        d_fmap2 = dF2cat's level 0 + the pool adjoints of the levels above, applied from the last level down to 0: a quarter
 //                      of a value to each of the four cells its pool covered, nothing to a dropped row or column
 // No float atomics; every sum's order is fixed by the shapes: two runs give the same bits and a batch row's bits do not depend on the batch.
 #include "rpe_common.h"
 #include "corr_taps.h"
+#include "bw_gemm.h"
 
 #define CB_MAX_LEVELS 4
 #define CB_FOOT (WIN + 2)          // cells per axis a window can touch: lo .. lo + 10
@@ -134,31 +135,24 @@ __global__ __launch_bounds__(256) void k_cb_pool(const float* __restrict__ fmap2
     }
 }
 
-#define CB_BM 128
-#define CB_BN 128
-#define CB_BK 32
-#define CB_LD (CB_BK + 4)
-typedef float cb_f32x16 __attribute__((ext_vector_type(16)));
-
 // chunk of the contraction axis: at most 8 chunks of whole 32-steps, at least 512 long -- a function of K alone
-static inline int cb_chunk(int K) {
-    const int c = ((K + 7) / 8 + 31) / 32 * 32;
-    return c < 512 ? 512 : c;
-}
-static inline int cb_chunks(int K) { return (K + cb_chunk(K) - 1) / cb_chunk(K); }
+static inline int cb_chunk(int K) { return (int)split_chunk(K, 8, 512); }
+static inline int cb_chunks(int K) { return split_chunks(K, 8, 512); }
 
 // part[bz][chunk][m][n] = sum_{k in chunk} A[bz][m][k] B[bz][n][k]:  A[m][k] at A[m lda + k];  B[n][k] at B[n ldb + k] (BT = false: d_fmap1,
-// B = G, k = the cell) or at B[k ldb + n] (BT = true: dF2cat, B = G, k = the query).  Workgroup = 4 waves of 2 x 2 32x32x2 tiles, staging and
-// the permuted K of a step as in bw_gemm.h; a row / column / k outside the problem is read from a clamped address and selected to zero.
+// B = G, k = the cell) or at B[k ldb + n] (BT = true: dF2cat, B = G, k = the query).  Staging: A, and B along k, as thread
+// t's k column t & 31 of rows (t >> 5) + 8 r; B across k as its column t & 127 at k = (t >> 7) + 2 r, coalesced along n.  A row / column / k
+// outside the problem is read from a clamped address and selected to zero.  The tile and the
+// multiply are bw_gemm_body's (bw_gemm.h), restated here: see that header for why.
 template <bool BT>
 __global__ __launch_bounds__(256) void k_cb_gemm(const float* __restrict__ A, long long abs_, int lda, const float* __restrict__ B, long long bbs,
                                                  int ldb, int M, int N, int K, int kc, int chunks, float* __restrict__ part) {
-    __shared__ __attribute__((aligned(16))) float sA[CB_BM * CB_LD];
-    __shared__ __attribute__((aligned(16))) float sB[CB_BN * CB_LD];
+    __shared__ __attribute__((aligned(16))) float sA[BW_BM * BW_LD];
+    __shared__ __attribute__((aligned(16))) float sB[BW_BN * BW_LD];
     const int bz = blockIdx.z / chunks, ch = blockIdx.z - bz * chunks;
     A += (size_t)bz * abs_;
     B += (size_t)bz * bbs;
-    const int n0 = blockIdx.x * CB_BN, m0 = blockIdx.y * CB_BM;
+    const int n0 = blockIdx.x * BW_BN, m0 = blockIdx.y * BW_BM;
     const int kbeg = ch * kc, kend = kbeg + kc < K ? kbeg + kc : K;
     const int tid = threadIdx.x, kl = tid & 31, r0 = tid >> 5, nl = tid & 127, kh = tid >> 7;
     float ra[16], rb[16];
@@ -186,7 +180,7 @@ __global__ __launch_bounds__(256) void k_cb_gemm(const float* __restrict__ A, lo
     };
     const int lane = tid & 63, wv = tid >> 6, wm = wv >> 1, wn = wv & 1;
     const int li = lane & 31, lh = lane >> 5;
-    cb_f32x16 acc[2][2];
+    f32x16 acc[2][2];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -194,22 +188,22 @@ __global__ __launch_bounds__(256) void k_cb_gemm(const float* __restrict__ A, lo
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[a][c][e] = 0.0f;
     load(kbeg);
-    for (int ks = kbeg; ks < kend; ks += CB_BK) {
+    for (int ks = kbeg; ks < kend; ks += BW_BK) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            sA[(r0 + 8 * r) * CB_LD + kl] = ra[r];
-            if (!BT) sB[(r0 + 8 * r) * CB_LD + kl] = rb[r];
-            else sB[nl * CB_LD + kh + 2 * r] = rb[r];
+            sA[(r0 + 8 * r) * BW_LD + kl] = ra[r];
+            if (!BT) sB[(r0 + 8 * r) * BW_LD + kl] = rb[r];
+            else sB[nl * BW_LD + kh + 2 * r] = rb[r];
         }
         __syncthreads();
-        if (ks + CB_BK < kend) load(ks + CB_BK);
+        if (ks + BW_BK < kend) load(ks + BW_BK);
 #pragma unroll
         for (int t4 = 0; t4 < 4; ++t4) {
             float fa[2][4], fb[2][4];
 #pragma unroll
             for (int a = 0; a < 2; ++a) {
-                const float4 va = *(const float4*)&sA[(wm * 64 + a * 32 + li) * CB_LD + lh * 16 + t4 * 4];
-                const float4 vb = *(const float4*)&sB[(wn * 64 + a * 32 + li) * CB_LD + lh * 16 + t4 * 4];
+                const float4 va = *(const float4*)&sA[(wm * 64 + a * 32 + li) * BW_LD + lh * 16 + t4 * 4];
+                const float4 vb = *(const float4*)&sB[(wn * 64 + a * 32 + li) * BW_LD + lh * 16 + t4 * 4];
                 fa[a][0] = va.x; fa[a][1] = va.y; fa[a][2] = va.z; fa[a][3] = va.w;
                 fb[a][0] = vb.x; fb[a][1] = vb.y; fb[a][2] = vb.z; fb[a][3] = vb.w;
             }
@@ -236,16 +230,6 @@ __global__ __launch_bounds__(256) void k_cb_gemm(const float* __restrict__ A, lo
                 if (m < M && n < N) out[(size_t)m * N + n] = acc[a][c][e];
             }
         }
-}
-
-// out[bz][e] = (float)(scale * sum_chunk part[bz][chunk][e]), e < per = M N: chunk order, f64, one rounding
-__global__ __launch_bounds__(256) void k_cb_reduce(const float* __restrict__ part, int chunks, size_t per, double scale, float* __restrict__ out) {
-    const int bz = blockIdx.y;
-    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < per; e += (size_t)gridDim.x * 256) {
-        double s = 0.0;
-        for (int c = 0; c < chunks; ++c) s += (double)part[((size_t)bz * chunks + c) * per + e];
-        out[(size_t)bz * per + e] = (float)(scale * s);
-    }
 }
 
 // d_fmap2 (b c planes of h8 x w8) from dF2cat (planes of S).  Gather form of "levels applied from the last down to 0": cell (y, x) of level 0
@@ -312,13 +296,13 @@ extern "C" int rpe_corr_build_backward(const float* grad_volume, const float* fm
     const double scale = 1.0 / sqrt((double)c);
     const long long gbs = (long long)g.nq * g.S;
     // d_fmap1 = F2cat G^T: M = c, N = queries, K = S
-    hipLaunchKernelGGL((k_cb_gemm<false>), dim3(ceil_div(g.nq, CB_BN), ceil_div(c, CB_BM), b * ch1), dim3(256), 0, s, F, (long long)c * g.S, g.S,
+    hipLaunchKernelGGL((k_cb_gemm<false>), dim3(ceil_div(g.nq, BW_BN), ceil_div(c, BW_BM), b * ch1), dim3(256), 0, s, F, (long long)c * g.S, g.S,
                        grad_volume, gbs, g.S, c, g.nq, g.S, cb_chunk(g.S), ch1, part);
-    hipLaunchKernelGGL(k_cb_reduce, dim3(min(ceil_div((long long)c * g.nq, 256), 2048), b), dim3(256), 0, s, part, ch1, (size_t)c * g.nq, scale, d_fmap1);
+    splitk_reduce_launch(part, b, ch1, (long long)c * g.nq, scale, d_fmap1, s);
     // dF2cat = fmap1 G: M = c, N = S, K = queries
-    hipLaunchKernelGGL((k_cb_gemm<true>), dim3(ceil_div(g.S, CB_BN), ceil_div(c, CB_BM), b * ch2), dim3(256), 0, s, fmap1, (long long)c * g.nq, g.nq,
+    hipLaunchKernelGGL((k_cb_gemm<true>), dim3(ceil_div(g.S, BW_BN), ceil_div(c, BW_BM), b * ch2), dim3(256), 0, s, fmap1, (long long)c * g.nq, g.nq,
                        grad_volume, gbs, g.S, c, g.S, g.nq, cb_chunk(g.nq), ch2, part);
-    hipLaunchKernelGGL(k_cb_reduce, dim3(min(ceil_div((long long)c * g.S, 256), 2048), b), dim3(256), 0, s, part, ch2, (size_t)c * g.S, scale, D);
+    splitk_reduce_launch(part, b, ch2, (long long)c * g.S, scale, D, s);
     hipLaunchKernelGGL(k_cb_unpool, dim3(min(ceil_div((long long)planes * g.nq, 256), 4096)), dim3(256), 0, s, D, d_fmap2, g, planes);
     return rpe_check_launch();
 }

@@ -5,8 +5,9 @@
 //     flow_up = upsample_convex(flow_prev + delta, m)
 // Upstream detaches coords1 at the top of every iteration, so this tail carries the EXACT pose-loss gradient of the eight head parameters.
 // Here: the up-sampling's adjoint, the weight (and bias) gradient of a stride-1 'same' convolution as a GEMM on the f32 matrix cores with a
-// fixed split of the pixel axis, the data gradient of the 2-channel output layer with t_f's ReLU mask, and the ReLU mask as a pass of its
-// own.  The other data gradients are FORWARD convolutions on transposed, flipped weights and reuse the forward's kernels (ops.py).
+// fixed split of the pixel axis -- for the heads' 3x3 and 1x1 and for the update block's 1x5, 5x1 and 7x7 layers alike --, the data gradient
+// of the 2-channel output layer with t_f's ReLU mask, and the ReLU mask as a pass of its own.  The other data gradients are FORWARD
+// convolutions on transposed, flipped weights and reuse the forward's kernels (ops.py).
 // No float atomics anywhere; every sum runs in an order fixed by the shapes, so two runs give the same bits on any device.
 #include "rpe_common.h"
 #include "upsample_device.h"
@@ -96,16 +97,21 @@ __global__ __launch_bounds__(UB_T * UB_T) void k_upsample_convex_bwd(const float
 // dW[co][ci][ky][kx] = sum_{b,y,x} dy[b][co][y][x] * x[b][ci][y + ky - kh/2][x + kx - kw/2]  (zero outside the map):  a GEMM with
 // M = cout, N = cin * taps (n = ci * taps + tap: dW's own layout), K = b * h * w.  Both operands are contiguous along K in memory.
 //
-// The split of K: chunks of bw_chunk(K) pixels -- a function of b * h * w alone, never of the device --, chunk c -> partial c, and the
-// partials are added in index order in f64 (k_bw_sum).  Inside a chunk the f32 matrix cores sum in steps of 32 pixels, each step's pixels
-// in the fixed order of the instruction: one bit pattern per shape.
-// (bw_chunk, the tile constants and the GEMM's body: bw_gemm.h, shared with update_backward.hip)
-template <int TAPS>
+// The split of K: chunks of split_chunk(K, 64, 1024) pixels -- a function of b * h * w alone, never of the device --, chunk c -> partial c,
+// and the partials are added in index order in f64 (k_splitk_reduce).  Inside a chunk the f32 matrix cores sum in steps of 32 pixels, each
+// step's pixels in the fixed order of the instruction: one bit pattern per shape.
+// (the tile's body and the second pass: bw_gemm.h, which corr_backward.hip shares; here: the kernel sizes and their one launch path)
+static inline long long bw_chunk(long long K) { return split_chunk(K, 64, 1024); }
+static inline int bw_chunks(long long K) { return split_chunks(K, 64, 1024); }
+
+// grid (N tiles, M tiles, chunks): M = cout, N = cin * taps, at any cout (a ragged M or N tile is selected to zero: convf1's 2 x 49 = 98
+// columns fill one tile in part)
+template <int KH, int KW>
 __global__ __launch_bounds__(256) void k_bw_gemm(const float* __restrict__ x, long long xbs, const float* __restrict__ dy, long long dybs,
                                                  int cin, int cout, int h, int w, long long K, long long kc, float* __restrict__ part) {
     __shared__ __attribute__((aligned(16))) float sA[BW_BM * BW_LD];
     __shared__ __attribute__((aligned(16))) float sB[BW_BN * BW_LD];
-    bw_gemm_body<TAPS == 9 ? 3 : 1, TAPS == 9 ? 3 : 1>(x, xbs, dy, dybs, cin, cout, h, w, K, kc, part, sA, sB);
+    bw_gemm_body<KH, KW>(x, xbs, dy, dybs, cin, cout, h, w, K, kc, part, sA, sB);
 }
 
 // The layers with one or two output channels (FlowHead.conv2, 256 -> 2) do not fill a matrix tile: a plain kernel, one workgroup per
@@ -151,15 +157,6 @@ __global__ __launch_bounds__(256) void k_bw_small(const float* __restrict__ x, l
         const double v = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
         if (o < cout) part[(size_t)blockIdx.y * cout * cin * TAPS + ((size_t)o * cin + ci) * TAPS + t] = (float)v;
     }
-}
-
-// out[e] = scale * sum_c part[c][e], c in index order, in f64
-__global__ __launch_bounds__(256) void k_bw_sum(const float* __restrict__ part, int chunks, size_t per, double scale, float* __restrict__ out) {
-    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= per) return;
-    double s = 0.0;
-    for (int c = 0; c < chunks; ++c) s += (double)part[(size_t)c * per + e];
-    out[e] = (float)(s * scale);
 }
 
 // db[co] = sum of dy's channel co: one workgroup per (channel, chunk) -> an f64 partial, then the same index-order sum
@@ -253,8 +250,27 @@ extern "C" int rpe_upsample_convex_backward(const float* grad_up, const float* f
     return rpe_check_launch();
 }
 
+// the kernel sizes, each with 'same' padding: the heads' 3x3 and 1x1, the update block's 1x5, 5x1 and 7x7
+typedef void (*bw_kernel_t)(const float*, long long, const float*, long long, int, int, int, int, long long, long long, float*);
+static inline bw_kernel_t bw_gemm_kernel(int kh, int kw) {
+    if (kh == 3 && kw == 3) return k_bw_gemm<3, 3>;
+    if (kh == 1 && kw == 1) return k_bw_gemm<1, 1>;
+    if (kh == 1 && kw == 5) return k_bw_gemm<1, 5>;
+    if (kh == 5 && kw == 1) return k_bw_gemm<5, 1>;
+    if (kh == 7 && kw == 7) return k_bw_gemm<7, 7>;
+    return nullptr;
+}
+
+// one or two output channels at 3x3 and 1x1: no matrix tile to fill (nullptr: the GEMM)
+static inline bw_kernel_t bw_small_kernel(int kh, int kw, int cout) {
+    if (cout > 2) return nullptr;
+    if (kh == 3 && kw == 3) return k_bw_small<9>;
+    if (kh == 1 && kw == 1) return k_bw_small<1>;
+    return nullptr;
+}
+
 static inline bool bw_shape_ok(int b, int cin, int cout, int h, int w, int kh, int kw) {
-    return b > 0 && cin > 0 && cout > 0 && h > 0 && w > 0 && ((kh == 3 && kw == 3) || (kh == 1 && kw == 1) || bw_ext_kernel(kh, kw));
+    return b > 0 && cin > 0 && cout > 0 && h > 0 && w > 0 && bw_gemm_kernel(kh, kw);
 }
 
 // floats: partials (chunks, cout, cin, kh, kw), rounded up to 256 bytes | doubles: bias partials (chunks, cout)
@@ -281,19 +297,14 @@ extern "C" int rpe_conv_bwd_weight(const float* x, long long x_batch_stride, con
     float* part = (float*)workspace;
     double* bpart = (double*)((char*)workspace + ((size_t)chunks * per * sizeof(float) + 255) / 256 * 256);
     if (d_weight) {
-        if (bw_ext_kernel(kh, kw)) {                                 // the update block's 1x5, 5x1, 7x7: update_backward.hip, any cout
-            if (!bw_gemm_launch_ext(x, x_batch_stride, dy, dy_batch_stride, cin, cout, h, w, kh, kw, K, kc, chunks, part, s)) return RPE_E_UNSUPPORTED;
-        } else if (cout <= 2) {
-            const dim3 g(cin, chunks);
-            if (taps == 9) hipLaunchKernelGGL(k_bw_small<9>, g, dim3(256), 0, s, x, x_batch_stride, dy, dy_batch_stride, cin, cout, h, w, K, kc, part);
-            else hipLaunchKernelGGL(k_bw_small<1>, g, dim3(256), 0, s, x, x_batch_stride, dy, dy_batch_stride, cin, cout, h, w, K, kc, part);
+        if (const bw_kernel_t small = bw_small_kernel(kh, kw, cout)) {
+            hipLaunchKernelGGL(small, dim3(cin, chunks), dim3(256), 0, s, x, x_batch_stride, dy, dy_batch_stride, cin, cout, h, w, K, kc, part);
         } else {
             const dim3 g(ceil_div((long long)cin * taps, BW_BN), ceil_div(cout, BW_BM), chunks);
             if (g.y > 65535) return RPE_E_UNSUPPORTED;
-            if (taps == 9) hipLaunchKernelGGL(k_bw_gemm<9>, g, dim3(256), 0, s, x, x_batch_stride, dy, dy_batch_stride, cin, cout, h, w, K, kc, part);
-            else hipLaunchKernelGGL(k_bw_gemm<1>, g, dim3(256), 0, s, x, x_batch_stride, dy, dy_batch_stride, cin, cout, h, w, K, kc, part);
+            hipLaunchKernelGGL(bw_gemm_kernel(kh, kw), g, dim3(256), 0, s, x, x_batch_stride, dy, dy_batch_stride, cin, cout, h, w, K, kc, part);
         }
-        hipLaunchKernelGGL(k_bw_sum, dim3(ceil_div(per, 256)), dim3(256), 0, s, (const float*)part, chunks, (size_t)per, (double)scale, d_weight);
+        splitk_reduce_launch(part, 1, chunks, per, (double)scale, d_weight, s);
     }
     if (d_bias) {
         hipLaunchKernelGGL(k_bw_bias_part, dim3(cout, chunks), dim3(256), 0, s, dy, dy_batch_stride, cout, h * w, K, kc, bpart);

@@ -2,35 +2,11 @@
 //     cor = relu(convc2(relu(convc1(corr))))   flo = relu(convf2(relu(convf1(flow))))   m = relu(conv([cor | flo]))   x = [inp | m | flow]
 //     per half (1x5, then 5x1):  z = s(convz([h | x]))  r = s(convr([h | x]))  q = tanh(convq([r h | x]))  h <- (1 - z) h + z q
 // Upstream detaches coords1 at the top of every iteration, so corr and flow are constants of the step and the only path through time is h.
-// Here: what the step's backward needs beyond raft_backward.hip -- the weight-gradient GEMM (bw_gemm.h) for the 1x5, 5x1 and 7x7 layers,
-// reached through rpe_conv_bwd_weight, and the adjoints of the GRU's gate epilogues (rpe_gru_gates_zr / _h).  The data gradients are FORWARD
-// convolutions on transposed, flipped weights over groups of input channels (ops.py), as in the tail.
+// Here: what the step's backward needs beyond raft_backward.hip -- the adjoints of the GRU's gate epilogues and the gates' recomputation
+// (rpe_gru_gates_*).  The weight gradients of the 1x5, 5x1 and 7x7 layers are rpe_conv_bwd_weight's (raft_backward.hip); the data gradients
+// are FORWARD convolutions on transposed, flipped weights over groups of input channels (ops.py), as in the tail.
 // No float atomics; every sum runs in an order fixed by the shapes, so two runs give the same bits; a row's result does not depend on its batch.
 #include "rpe_common.h"
-#include "bw_gemm.h"
-
-// ------------------------------------------------------------------------------------------------ weight gradient: 1x5, 5x1, 7x7
-template <int KH, int KW>
-__global__ __launch_bounds__(256) void k_bwx_gemm(const float* __restrict__ x, long long xbs, const float* __restrict__ dy, long long dybs,
-                                                  int cin, int cout, int h, int w, long long K, long long kc, float* __restrict__ part) {
-    __shared__ __attribute__((aligned(16))) float sA[BW_BM * BW_LD];
-    __shared__ __attribute__((aligned(16))) float sB[BW_BN * BW_LD];
-    bw_gemm_body<KH, KW>(x, xbs, dy, dybs, cin, cout, h, w, K, kc, part, sA, sB);
-}
-
-// rpe_conv_bwd_weight's first pass for (kh, kw) in (1,5), (5,1), (7,7): the partials of every chunk, at any cout (a ragged M or N tile is
-// selected to zero: convf1's 2 x 49 = 98 columns fill one tile in part).  The caller (raft_backward.hip) has checked the arguments, and runs
-// the same second pass as for 3x3 and 1x1.  false = not one of these kernel sizes (or a grid the launch cannot take).
-bool bw_gemm_launch_ext(const float* x, long long xbs, const float* dy, long long dybs, int cin, int cout, int h, int w, int kh, int kw,
-                        long long K, long long kc, int chunks, float* part, hipStream_t s) {
-    const dim3 g(ceil_div((long long)cin * kh * kw, BW_BN), ceil_div(cout, BW_BM), chunks);
-    if (g.y > 65535) return false;
-    if (kh == 1 && kw == 5) hipLaunchKernelGGL((k_bwx_gemm<1, 5>), g, dim3(256), 0, s, x, xbs, dy, dybs, cin, cout, h, w, K, kc, part);
-    else if (kh == 5 && kw == 1) hipLaunchKernelGGL((k_bwx_gemm<5, 1>), g, dim3(256), 0, s, x, xbs, dy, dybs, cin, cout, h, w, K, kc, part);
-    else if (kh == 7 && kw == 7) hipLaunchKernelGGL((k_bwx_gemm<7, 7>), g, dim3(256), 0, s, x, xbs, dy, dybs, cin, cout, h, w, K, kc, part);
-    else return false;
-    return true;
-}
 
 // ------------------------------------------------------------------------------------------------------------------- GRU gates, adjoint
 // One half:  h' = (1 - z) h + z q,  z = s(z_pre), q = tanh(q_pre), and rh = r h feeds convq, r = s(r_pre).  From d = d loss / d h' and the

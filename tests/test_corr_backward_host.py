@@ -92,7 +92,7 @@ def test_kernels_build_for_gfx950_without_scratch(tmp_path):
     names = re.findall(r'Function Name: (\S+)', r.stderr)
     scratch = [int(v) for v in re.findall(r'ScratchSize \[bytes/lane\]: (\d+)', r.stderr)]
     assert len(names) == len(scratch) == 6, names
-    for kernel in ('k_corr_lookup_bwd', 'k_cb_pool', 'k_cb_gemmILb0E', 'k_cb_gemmILb1E', 'k_cb_reduce', 'k_cb_unpool'):
+    for kernel in ('k_corr_lookup_bwd', 'k_cb_pool', 'k_cb_gemmILb0E', 'k_cb_gemmILb1E', 'k_splitk_reduce', 'k_cb_unpool'):
         assert any(kernel in nm for nm in names), kernel
     assert scratch == [0] * 6, dict(zip(names, scratch))
     makefile = open(os.path.join(ROOT, 'robust-pose-estimator_amd', 'csrc', 'Makefile')).read()

@@ -129,10 +129,11 @@ def test_kernels_build_for_gfx950_without_scratch(tmp_path):
     assert r.returncode == 0, r.stderr[-2000:]
     names = re.findall(r'Function Name: (\S+)', r.stderr)
     scratch = [int(v) for v in re.findall(r'ScratchSize \[bytes/lane\]: (\d+)', r.stderr)]
-    assert len(names) == len(scratch) == 11, names
-    for kernel in ('k_upsample_convex_bwd', 'k_bw_gemmILi9E', 'k_bw_gemmILi1E', 'k_bw_smallILi9E', 'k_bw_sum', 'k_bw_bias_part', 'k_bw_bias_sum',
-                   'k_conv3x3_to2_bwd_data', 'k_relu_bwd', 'k_sum_groups'):
+    assert len(names) == len(scratch) == 14, names
+    for kernel in ('k_upsample_convex_bwd', 'k_bw_gemmILi3ELi3E', 'k_bw_gemmILi1ELi1E', 'k_bw_gemmILi1ELi5E', 'k_bw_gemmILi5ELi1E', 'k_bw_gemmILi7ELi7E',
+                   'k_bw_smallILi9E', 'k_bw_smallILi1E', 'k_splitk_reduce', 'k_bw_bias_part', 'k_bw_bias_sum', 'k_conv3x3_to2_bwd_data', 'k_relu_bwd',
+                   'k_sum_groups'):
         assert any(kernel in nm for nm in names), kernel
-    assert scratch == [0] * 11, dict(zip(names, scratch))
+    assert scratch == [0] * 14, dict(zip(names, scratch))
     makefile = open(os.path.join(ROOT, 'robust-pose-estimator_amd', 'csrc', 'Makefile')).read()
     assert 'raft_backward.hip' in makefile and re.search(r'build/raft_backward\.o: CXXFLAGS \+= -Rpass-analysis=kernel-resource-usage', makefile)
