@@ -943,8 +943,17 @@ int rpe_unet_heads(const float *inp1, const float *inp2, const float *hidden, co
  *     src / params / train_mask / sizes.  It writes the parameter gradients back to back in the params order into grad_params
  *     (rpe_unet_train_grad_floats(cin) floats; tensor k starts at rpe_unet_train_grad_offset(cin, k), k = 36 gives the total) and the
  *     gradient of the concatenated input (n,cin,h8,w8) into grad_input unless that is NULL.  `out` (the forward's output) is read
- *     only with `sigmoid`.  The 1/8 grid must be at least 44x44, otherwise RPE_E_UNSUPPORTED. */
+ *     only with `sigmoid`.  The 1/8 grid must be at least 44x44, otherwise RPE_E_UNSUPPORTED.
+ *   Where the buffers of the workspace lie (for tests and tools that read a saved activation or an activation gradient):
+ *     rpe_unet_train_workspace_offset gives the first float of buffer `index` counted from the workspace pointer rounded up to 256
+ *     bytes, (size_t)-1 for an unsupported shape or an index outside [0, 46); rpe_unet_train_workspace_extent writes
+ *     (rows, channels, h, w) of that buffer into extent[4] (RPE_E_BADARG for such an index, RPE_E_UNSUPPORTED for such a shape).
+ *     Index order = order in memory (documented with the plan in csrc/unet_train_host.h): per encoder stage a1, r1, g_r1, skip,
+ *     g_skip, [pool, g_pool,] mean, invstd; per decoder stage up, g_up, r, nrm, g_nrm, dout, g_dout, mean, invstd; hm, g_hm, wpart
+ *     (doubles: 2 rows channels floats). */
 size_t rpe_unet_train_workspace_bytes(int n, int cin, int h8, int w8, int out_h, int out_w);
+size_t rpe_unet_train_workspace_offset(int n, int cin, int h8, int w8, int index);
+int rpe_unet_train_workspace_extent(int n, int cin, int h8, int w8, int index, int *extent);
 size_t rpe_unet_train_grad_floats(int cin);
 size_t rpe_unet_train_grad_offset(int cin, int index);
 int rpe_unet_train_forward(const float *const *src, const int *src_channels, const long long *src_batch_strides, int nsrc,

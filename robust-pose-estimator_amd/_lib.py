@@ -297,6 +297,8 @@ SIGNATURES = {
     'rpe_unet_workspace_bytes': (_sz, [_i, _i, _i]),
     'rpe_unet_heads': (_i, [_vp, _vp, _vp, _vp, _ll, _ll, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'rpe_unet_train_workspace_bytes': (_sz, [_i, _i, _i, _i, _i, _i]),
+    'rpe_unet_train_workspace_offset': (_sz, [_i, _i, _i, _i, _i]),
+    'rpe_unet_train_workspace_extent': (_i, [_i, _i, _i, _i, _i, _c.POINTER(_i)]),
     'rpe_unet_train_grad_floats': (_sz, [_i]),
     'rpe_unet_train_grad_offset': (_sz, [_i, _i]),
     'rpe_unet_train_forward': (_i, [_PVP, _c.POINTER(_i), _c.POINTER(_ll), _i, _PVP, _PVP, _PVP, _PVP, _c.POINTER(_fl), _c.POINTER(_fl), _i,

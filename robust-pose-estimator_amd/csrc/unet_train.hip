@@ -504,6 +504,19 @@ extern "C" size_t rpe_unet_train_grad_offset(int cin, int index) {
     return cin > 0 && cin % 8 == 0 && index >= 0 && index <= UT_NPARAM ? ut_grad_offset(cin, index) : 0;
 }
 
+extern "C" size_t rpe_unet_train_workspace_offset(int n, int cin, int h8, int w8, int index) {
+    UtBuf b;
+    return ut_workspace_buffer(n, cin, h8, w8, index, b) ? b.off : (size_t)-1;
+}
+
+extern "C" int rpe_unet_train_workspace_extent(int n, int cin, int h8, int w8, int index, int* extent) {
+    UtBuf b;
+    if (!extent) return RPE_E_BADARG;
+    if (!ut_workspace_buffer(n, cin, h8, w8, index, b)) return index < 0 || index >= UT_NBUF ? RPE_E_BADARG : RPE_E_UNSUPPORTED;
+    extent[0] = b.rows; extent[1] = b.c; extent[2] = b.h; extent[3] = b.w;
+    return RPE_OK;
+}
+
 namespace {
 struct TCall {                      // what forward and backward share: checked arguments, the geometry and the workspace plan
     UtGeo g; UtPlan pl; float* ws; TSrc in[4]; int nsrc, cin, n, h8, w8; const float* const* prm; hipStream_t s;

@@ -104,6 +104,46 @@ static inline void ut_plan(const UtGeo& g, int n, int cin, UtPlan& p) {
     p.total = at;
 }
 
+// The plan's buffers by index, in the order ut_plan lays them out (so the offsets grow with the index), UT_NBUF in all:
+//   encoder stage i = 0..2, from index 0 / 9 / 18:  a1 | r1 | g_r1 | skip | g_skip | pool | g_pool (stages 0 and 1 only) | mean | invstd
+//   decoder stage j = 0..1, from index 25 + 9 j:    up | g_up | r | nrm | g_nrm | dout | g_dout | mean (norm 3 + j) | invstd
+//   43 hm | 44 g_hm | 45 wpart
+// c, h, w: the extent of one batch row of the buffer (n rows each); mean / invstd are (c) vectors (rows = 1, h = w = 1), and wpart is
+// UT_WCHUNK_MAX_N rows of DOUBLES, one per entry of the largest weight tensor (c), so it spans 2 rows c floats.
+#define UT_NBUF 46
+
+struct UtBuf { size_t off; int rows, c, h, w; };
+
+static inline bool ut_plan_buffer(const UtGeo& g, const UtPlan& p, int n, int cin, int index, UtBuf& b) {
+    int k = 0;
+    auto hit = [&](size_t off, int rows, int c, int h, int w) { if (k++ != index) return false; b = UtBuf{off, rows, c, h, w}; return true; };
+    for (int i = 0; i < 3; ++i) {
+        const int c = UT_WIDTHS[i];
+        if (hit(p.a1[i], n, c, g.h[i], g.w[i]) || hit(p.r1[i], n, c, g.h[i], g.w[i]) || hit(p.g_r1[i], n, c, g.h[i], g.w[i]) ||
+            hit(p.skip[i], n, c, g.hs[i], g.ws[i]) || hit(p.g_skip[i], n, c, g.hs[i], g.ws[i])) return true;
+        if (i < 2 && (hit(p.pool[i], n, c, g.hs[i] / 2, g.ws[i] / 2) || hit(p.g_pool[i], n, c, g.hs[i] / 2, g.ws[i] / 2))) return true;
+        if (hit(p.mean[i], 1, c, 1, 1) || hit(p.invstd[i], 1, c, 1, 1)) return true;
+    }
+    for (int j = 0; j < 2; ++j) {
+        const int c2 = UT_WIDTHS[2 - j] / 2, mh = g.dh[j] + 2, mw = g.dw[j] + 2;
+        if (hit(p.up[j], n, c2, g.uh[j], g.uw[j]) || hit(p.g_up[j], n, c2, g.uh[j], g.uw[j]) || hit(p.r[j], n, c2, mh, mw) ||
+            hit(p.nrm[j], n, c2, mh, mw) || hit(p.g_nrm[j], n, c2, mh, mw) || hit(p.dout[j], n, c2, g.dh[j], g.dw[j]) ||
+            hit(p.g_dout[j], n, c2, g.dh[j], g.dw[j]) || hit(p.mean[3 + j], 1, c2, 1, 1) || hit(p.invstd[3 + j], 1, c2, 1, 1)) return true;
+    }
+    size_t wmax = 0;
+    for (int q = 0; q < UT_NPARAM; ++q) { const size_t f = ut_param_floats(cin, q); wmax = f > wmax ? f : wmax; }
+    return hit(p.hm, n, 1, g.dh[1], g.dw[1]) || hit(p.g_hm, n, 1, g.dh[1], g.dw[1]) || hit(p.wpart, UT_WCHUNK_MAX_N, (int)wmax, 1, 1);
+}
+
+// buffer `index` of the plan of a supported shape; false for an unsupported shape or an index outside [0, UT_NBUF)
+static inline bool ut_workspace_buffer(int n, int cin, int h8, int w8, int index, UtBuf& b) {
+    UtGeo g;
+    if (n <= 0 || cin <= 0 || cin % 8 != 0 || index < 0 || index >= UT_NBUF || !ut_geo(h8, w8, g)) return false;
+    UtPlan p;
+    ut_plan(g, n, cin, p);
+    return ut_plan_buffer(g, p, n, cin, index, b);
+}
+
 static inline size_t ut_workspace_bytes(int n, int cin, int h8, int w8) {
     UtGeo g;
     if (n <= 0 || cin <= 0 || cin % 8 != 0 || !ut_geo(h8, w8, g)) return 0;

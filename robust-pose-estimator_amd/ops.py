@@ -1453,6 +1453,37 @@ def unet_train_backward(grad_out, out, ctx, input_grad=False):
     return blob, gin
 
 
+def _unet_train_ws_names():
+    names = []
+    for i in range(3):
+        names += [f'{k}.{i}' for k in ('a1', 'r1', 'g_r1', 'skip', 'g_skip') + (('pool', 'g_pool') if i < 2 else ())] + [f'mean.{i}', f'invstd.{i}']
+    for j in range(2):
+        names += [f'{k}.{j}' for k in ('up', 'g_up', 'r', 'nrm', 'g_nrm', 'dout', 'g_dout')] + [f'mean.{3 + j}', f'invstd.{3 + j}']
+    return tuple(names + ['hm', 'g_hm', 'wpart'])
+
+
+UNET_TRAIN_WS_NAMES = _unet_train_ws_names()         # the buffers of the workspace in index order (UT_NBUF of csrc/unet_train_host.h)
+
+
+def unet_train_workspace_views(ctx):
+    """The buffers of ``ctx.ws`` by name (UNET_TRAIN_WS_NAMES; '<field>.<stage>' of UtPlan, norms 0..4) as tensor views, located by
+    rpe_unet_train_workspace_offset / _extent: maps (n,c,h,w) float32, mean / invstd (c,), 'wpart' (32, largest weight) float64.  The
+    forward fills the saved activations, the backward the g_* buffers (some in place: see csrc/unet_train.hip)."""
+    L = lib()
+    base = (-ctx.ws.data_ptr()) % 256                 # the library rounds the pointer up to 256 bytes
+    views, ext = {}, (ctypes.c_int * 4)()
+    for k, name in enumerate(UNET_TRAIN_WS_NAMES):
+        off = L.rpe_unet_train_workspace_offset(ctx.n, ctx.cin, ctx.h8, ctx.w8, k)
+        check(L.rpe_unet_train_workspace_extent(ctx.n, ctx.cin, ctx.h8, ctx.w8, k, ext), 'rpe_unet_train_workspace_extent')
+        rows, c, h, w = ext
+        if name == 'wpart':
+            views[name] = ctx.ws[base + 4 * off:base + 4 * off + 8 * rows * c].view(torch.float64).view(rows, c)
+        else:
+            v = ctx.ws[base + 4 * off:base + 4 * off + 4 * rows * c * h * w].view(torch.float32)
+            views[name] = v.view(c) if name.startswith(('mean', 'invstd')) else v.view(rows, c, h, w)
+    return views
+
+
 def unet_train_grad_offsets(cin):
     """First float of each of the 36 parameter gradients in unet_train_backward's blob, and the blob's size as the 37th entry."""
     L = lib()

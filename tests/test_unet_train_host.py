@@ -109,3 +109,43 @@ def test_the_route_is_off_by_default_and_then_never_touches_the_training_kernels
         net.train_hip = True
         with pytest.raises(rpe.RpeError):
             net(x)
+
+
+@pytest.mark.parametrize('n,cin,h8,w8', [(1, 264, 44, 44), (3, 272, 45, 47), (3, 264, 52, 60), (2, 8, 64, 80)])
+def test_workspace_offsets_follow_the_plan(rpe, n, cin, h8, w8):
+    """rpe_unet_train_workspace_offset / _extent: 46 buffers in the order they lie in memory, each on a multiple of 64 floats, each ending
+    where the next begins (rounded up to 64 floats: no overlap and no gap the plan does not make), the last inside the workspace."""
+    from rpe_amd import ops
+    L = rpe.lib()
+    assert len(ops.UNET_TRAIN_WS_NAMES) == len(set(ops.UNET_TRAIN_WS_NAMES)) == 46
+    ext = (ctypes.c_int * 4)()
+    offs, floats = [], []
+    for k, name in enumerate(ops.UNET_TRAIN_WS_NAMES):
+        offs.append(L.rpe_unet_train_workspace_offset(n, cin, h8, w8, k))
+        assert L.rpe_unet_train_workspace_extent(n, cin, h8, w8, k, ext) == 0
+        rows, c, h, w = ext
+        assert rows == (1 if name.startswith(('mean', 'invstd')) else 32 if name == 'wpart' else n) and min(c, h, w) >= 1, name
+        floats.append(rows * c * h * w * (2 if name == 'wpart' else 1))
+    assert offs[0] == 0 and all(o % 64 == 0 for o in offs)
+    assert all(b > a for a, b in zip(offs, offs[1:]))
+    assert all(a + (f + 63) // 64 * 64 == b for a, f, b in zip(offs, floats, offs[1:]))
+    assert 4 * (offs[-1] + floats[-1]) + 256 <= L.rpe_unet_train_workspace_bytes(n, cin, h8, w8, 8 * h8, 8 * w8)
+    # a few extents, from the architecture: valid 3x3 convolutions, 2x2 pooling, the head map
+    shape = lambda name: (L.rpe_unet_train_workspace_extent(n, cin, h8, w8, ops.UNET_TRAIN_WS_NAMES.index(name), ext), tuple(ext))[1]
+    assert shape('a1.0') == (n, 16, h8 - 2, w8 - 2) and shape('skip.0') == (n, 16, h8 - 4, w8 - 4)
+    assert shape('pool.0') == (n, 16, (h8 - 4) // 2, (w8 - 4) // 2) and shape('mean.4') == (1, 16, 1, 1)
+    assert shape('hm') == shape('g_hm') and shape('hm')[1] == 1 and shape('wpart') == (32, max(16 * cin, 64 * 64) * 9, 1, 1)
+
+
+def test_workspace_offset_refuses_what_the_plan_does_not_hold(rpe):
+    L = rpe.lib()
+    none = ctypes.c_size_t(-1).value
+    q = L.rpe_unet_train_workspace_offset
+    ext = (ctypes.c_int * 4)()
+    assert q(1, 264, 44, 44, 45) not in (0, none)
+    for args in ((1, 264, 44, 44, 46), (1, 264, 44, 44, -1), (1, 264, 43, 44, 0), (1, 264, 44, 43, 0), (1, 264, 8, 8, 3), (0, 264, 44, 44, 0),
+                 (1, 260, 44, 44, 0), (1, 0, 44, 44, 0)):
+        assert q(*args) == none, args
+        assert L.rpe_unet_train_workspace_extent(*args, ext) in (-1, -3), args
+    assert L.rpe_unet_train_workspace_extent(1, 264, 44, 44, 46, ext) == -1 and L.rpe_unet_train_workspace_extent(1, 264, 43, 44, 0, ext) == -3
+    assert L.rpe_unet_train_workspace_extent(1, 264, 44, 44, 0, None) == -1
