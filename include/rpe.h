@@ -75,6 +75,8 @@ const char *rpe_version(void);
  *   (1,5), (5,1) and (7,7) since then: rpe_conv_bwd_weight_workspace_bytes returns 0 for them in a library that does not);
  *   and the backward of the correlation: rpe_corr_grad_volume_floats, rpe_corr_lookup_backward, rpe_corr_build_backward_workspace_bytes,
  *   rpe_corr_build_backward;
+ *   and the backward of the encoders: rpe_conv_s2_bwd_weight, rpe_conv_s2_bwd_weight_workspace_bytes, rpe_conv_s2_bwd_data,
+ *   rpe_bn_frozen_backward, rpe_bn_frozen_backward_workspace_bytes, rpe_instnorm_backward, rpe_split_act_backward;
  *   the next RPE_ABI_MINOR bump counts them and rpe_conv_wino24*. */
 #define RPE_ABI_VERSION 5
 #define RPE_ABI_MINOR 4
@@ -389,6 +391,49 @@ int rpe_corr_lookup_backward(const float *coords, const float *d_corr, int b, in
 size_t rpe_corr_build_backward_workspace_bytes(int b, int c, int h8, int w8, int levels);
 int rpe_corr_build_backward(const float *grad_volume, const float *fmap1, const float *fmap2, int b, int c, int h8, int w8, int levels,
                             float *d_fmap1, float *d_fmap2, float *d_f2cat, void *workspace, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Backward of RAFT's encoders (csrc/encoder_backward.hip; core/RAFT/core/extractor.py BasicEncoder, ResidualBlock): what the stride-1
+ * entry points above do not cover.  f32, NCHW, channel slices (batch strides in floats, at least the slice).  No float atomics; every sum
+ * runs in an order fixed by the shapes alone: two runs give the same bits, on any device.  Any map size.
+ * The three STRIDE-2 forms: kernel k = 3 (padding 1), 1 (padding 0) and 7 (padding 3, the stem), ho = (hi + 2 (k / 2) - k) / 2 + 1 and
+ *   wo likewise; any other k, or ho / wo that do not follow from hi / wi: RPE_E_BADARG (workspace query: 0).
+ * rpe_conv_s2_bwd_weight: d_weight (cout,cin,k,k) and d_bias (cout) (either may be NULL) of y = conv(x; W, stride 2) + bias from
+ *   x (b,cin,hi,wi) and dy (b,cout,ho,wo): rpe_conv_bwd_weight's GEMM (v_mfma_f32_32x32x2_f32, the same tile) with M = cout, N = cin k k,
+ *   K = b ho wo, the same chunks c(K) = max(1024, round_up(ceil(K / 64), 32)) added in index order in f64, ``scale`` applied to the f64
+ *   sum; a staged pixel reads x at (2 py + ty - k/2, 2 px + tx - k/2), border taps from a clamped address, selected to zero.  d_bias is
+ *   rpe_conv_bwd_weight's bias sum on dy.  workspace: rpe_conv_s2_bwd_weight_workspace_bytes(...) bytes, 16-byte aligned.  NULL x / dy /
+ *   workspace, non-positive sizes: RPE_E_BADARG; b ho wo, cin hi wi, cout ho wo or the weight's size >= 2^31: RPE_E_UNSUPPORTED.
+ * rpe_conv_s2_bwd_data: dx (b,cin,hi,wi) of the k = 3 and k = 1 forms from dy and weight (cout,cin,k,k), in gather form: an input pixel
+ *   adds only the taps whose parity reaches it (1, 2, 2 or 4 at 3x3; one pixel in four at 1x1) and is an exact zero where none does; no
+ *   zero-inserted copy of dy exists.  The sum over (cout, taps) runs in f64 in one fixed order and is rounded once.  k = 7: RPE_E_BADARG
+ *   (images are not trained).  b == 0 is RPE_OK.
+ * rpe_bn_frozen_backward: the adjoint of y = s (z + conv_bias - mean) + beta, s = gamma / sqrt(var + eps), with (mean, var) the running
+ *   statistics (constants), from dy (b,c,hw; behind the ReLU mask) and the raw convolution output z:  d_beta = S0 = sum dy,
+ *   d_gamma = (sum dy z + (conv_bias - mean) S0) / sqrt(var + eps),  d_conv_bias = s S0,  dz (b,c,hw) = s dy (may be dy).  The two sums run
+ *   over K = b hw in chunks of c(K), threads and waves in a fixed tree, chunks in index order, all f64.  conv_bias and every output may be
+ *   NULL.  workspace: rpe_bn_frozen_backward_workspace_bytes(b, c, hw) bytes, 16-byte aligned.  b <= 0 or > 65535, c > 65535: RPE_E_BADARG.
+ * rpe_instnorm_backward: the adjoint of y = (z - mean) / sigma per (b,c) plane, sigma = sqrt(biased var + eps), no affine parameters:
+ *   dz = (dy - mean(dy) - xh mean(dy xh)) / sigma, xh = (z - mean) / sigma.  The four plane moments in f64 (one workgroup per plane, fixed
+ *   tree), then a pass that applies them; a NaN stays inside its plane.  dz may be dy.  (A bias added in front of the norm cancels: its
+ *   gradient is zero.)  b == 0 is RPE_OK.
+ * rpe_split_act_backward: out = grad (1 - act^2) on channels [0, half) (tanh) and act > 0 ? grad : 0 on [half, c) (ReLU), act = the
+ *   activated output (the context encoder's net | inp); products in f64, rounded once; out may be grad.
+ * --------------------------------------------------------------------------------------------------------- */
+size_t rpe_conv_s2_bwd_weight_workspace_bytes(int b, int cin, int cout, int hi, int wi, int ho, int wo, int k);
+int rpe_conv_s2_bwd_weight(const float *x, long long x_batch_stride, const float *dy, long long dy_batch_stride, int b, int cin, int cout,
+                           int hi, int wi, int ho, int wo, int k, float scale, float *d_weight, float *d_bias, void *workspace,
+                           void *stream);
+int rpe_conv_s2_bwd_data(const float *dy, long long dy_batch_stride, const float *weight, int b, int cin, int cout, int hi, int wi, int ho,
+                         int wo, int k, float *dx, long long dx_batch_stride, void *stream);
+size_t rpe_bn_frozen_backward_workspace_bytes(int b, int c, int hw);
+int rpe_bn_frozen_backward(const float *dy, long long dy_batch_stride, const float *z, long long z_batch_stride, const float *gamma,
+                           const float *conv_bias, const float *mean, const float *var, double eps, int b, int c, int hw, float *d_gamma,
+                           float *d_beta, float *d_conv_bias, float *dz, long long dz_batch_stride, void *workspace, void *stream);
+int rpe_instnorm_backward(const float *dy, long long dy_batch_stride, const float *z, long long z_batch_stride, int b, int c, int hw,
+                          double eps, float *dz, long long dz_batch_stride, void *stream);
+int rpe_split_act_backward(const float *grad, long long grad_batch_stride, const float *act, long long act_batch_stride, int b, int c,
+                           int half, int hw, float *out, long long out_batch_stride, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * RAFT correlation -- replaces CorrBlock (core/RAFT/core/corr.py of the aimi-lab/RAFT submodule: all-pairs

@@ -253,6 +253,13 @@ SIGNATURES = {
     'rpe_corr_lookup_backward': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     'rpe_corr_build_backward_workspace_bytes': (_sz, [_i] * 5),
     'rpe_corr_build_backward': (_i, [_vp, _vp, _vp] + [_i] * 5 + [_vp] * 5),
+    'rpe_conv_s2_bwd_weight_workspace_bytes': (_sz, [_i] * 8),
+    'rpe_conv_s2_bwd_weight': (_i, [_vp, _ll, _vp, _ll] + [_i] * 8 + [_fl, _vp, _vp, _vp, _vp]),
+    'rpe_conv_s2_bwd_data': (_i, [_vp, _ll, _vp] + [_i] * 8 + [_vp, _ll, _vp]),
+    'rpe_bn_frozen_backward_workspace_bytes': (_sz, [_i, _i, _i]),
+    'rpe_bn_frozen_backward': (_i, [_vp, _ll, _vp, _ll, _vp, _vp, _vp, _vp, _d, _i, _i, _i, _vp, _vp, _vp, _vp, _ll, _vp, _vp]),
+    'rpe_instnorm_backward': (_i, [_vp, _ll, _vp, _ll, _i, _i, _i, _d, _vp, _ll, _vp]),
+    'rpe_split_act_backward': (_i, [_vp, _ll, _vp, _ll, _i, _i, _i, _i, _vp, _ll, _vp]),
     'rpe_flow_forward_interpolate': (_i, [_vp, _i, _i, _i, _vp, _vp]),
     'rpe_corr_pyramid_bytes': (_sz, [_i, _i, _i, _i]),
     'rpe_corr_pyramid_bytes_ex': (_sz, [_i, _i, _i, _i, _i]),

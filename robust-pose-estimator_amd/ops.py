@@ -1691,3 +1691,103 @@ def corr_build_backward(G, fmap1, fmap2, levels=4, ret_df2cat=False):
     check(lib().rpe_corr_build_backward(ptr(G), ptr(f1), ptr(f2), b, c, h8, w8, levels, ptr(d1), ptr(d2), ptr(dcat), ptr(ws), stream_ptr()),
           'rpe_corr_build_backward')
     return (d1, d2, dcat) if ret_df2cat else (d1, d2)
+
+
+# ------------------------------------------------------------------------------------------------- backward of the encoders
+# (one kernel per wrapper, csrc/encoder_backward.hip; raft_grad.py composes them into residual_block_backward and encoder_backward)
+def _s2_out(hi, wi, k):
+    return (hi + 2 * (k // 2) - k) // 2 + 1, (wi + 2 * (k // 2) - k) // 2 + 1
+
+
+def conv_s2_bwd_weight(x, dy, k, scale=1.0, bias=True):
+    """rpe_conv_s2_bwd_weight: (dW (cout,cin,k,k), db (cout) or None) of a STRIDE-2 convolution with kernel k = 3 (padding 1), 1 (padding 0)
+    or 7 (padding 3) from its input x (b,cin,hi,wi) and the gradient dy (b,cout,ho,wo) of its output, at any map size; both may be channel
+    slices.  conv_bwd_weight's GEMM and split of K = b ho wo: bit-identical from run to run.  ``scale`` multiplies both results."""
+    xp, xbs = _chan_slice(x, 'conv_s2_bwd_weight: x')
+    dp, dbs = _chan_slice(dy, 'conv_s2_bwd_weight: dy')
+    b, cin, hi, wi = x.shape
+    cout, ho, wo = dy.shape[1:]
+    if k not in (1, 3, 7) or tuple(dy.shape) != (b, cout, *_s2_out(hi, wi, k)):
+        raise _lib.RpeError(f'conv_s2_bwd_weight: kernel {k} (3, 1 or 7) and dy {tuple(dy.shape)} do not match x {tuple(x.shape)} at stride 2')
+    nws = lib().rpe_conv_s2_bwd_weight_workspace_bytes(b, cin, cout, hi, wi, ho, wo, k)
+    if nws == 0:
+        raise _lib.RpeError('conv_s2_bwd_weight: unsupported shape (non-empty tensors)')
+    ws = torch.empty(nws, dtype=torch.uint8, device=x.device)
+    dw = torch.empty(cout, cin, k, k, dtype=torch.float32, device=x.device)
+    db = torch.empty(cout, dtype=torch.float32, device=x.device) if bias else None
+    check(lib().rpe_conv_s2_bwd_weight(xp, xbs, dp, dbs, b, cin, cout, hi, wi, ho, wo, k, float(scale), ptr(dw), ptr(db), ptr(ws), stream_ptr()),
+          'rpe_conv_s2_bwd_weight')
+    return dw, db
+
+
+def conv_s2_bwd_data(dy, weight, size, out=None):
+    """rpe_conv_s2_bwd_data: dx (b,cin,hi,wi), ``size`` = (hi, wi), of a stride-2 convolution with weight (cout,cin,k,k), k = 3 (padding 1) or
+    1 (padding 0), from dy (b,cout,ho,wo).  Gather form, summed in f64; exact zeros where no tap reaches; ``out`` may be a channel slice."""
+    dp, dbs = _chan_slice(dy, 'conv_s2_bwd_data: dy')
+    w = _nchw(weight.detach(), 'conv_s2_bwd_data: weight')
+    b, cout, ho, wo = dy.shape
+    cin, k = w.shape[1], w.shape[2]
+    hi, wi = size
+    if tuple(w.shape) != (cout, cin, k, k) or k not in (1, 3) or (ho, wo) != _s2_out(hi, wi, k):
+        raise _lib.RpeError(f'conv_s2_bwd_data: weight {tuple(w.shape)} (3x3 or 1x1) and dy {tuple(dy.shape)} do not give a {hi} x {wi} input at stride 2')
+    if out is None:
+        out = torch.empty(b, cin, hi, wi, dtype=torch.float32, device=dy.device)
+    elif tuple(out.shape) != (b, cin, hi, wi):
+        raise _lib.RpeError(f'conv_s2_bwd_data: out must be ({b},{cin},{hi},{wi})')
+    op, obs = _chan_slice(out, 'conv_s2_bwd_data: out')
+    check(lib().rpe_conv_s2_bwd_data(dp, dbs, ptr(w), b, cin, cout, hi, wi, ho, wo, k, op, obs, stream_ptr()), 'rpe_conv_s2_bwd_data')
+    return out
+
+
+def bn_frozen_backward(dy, z, gamma, conv_bias, mean, var, eps, dz=None):
+    """rpe_bn_frozen_backward: the adjoint of y = s (z + conv_bias - mean) + beta, s = gamma / sqrt(var + eps), on running statistics, from dy
+    (behind the ReLU mask) and the raw convolution output z -> (dz = s dy, d_gamma, d_beta, d_conv_bias); ``dz`` may be given (dy itself: in
+    place).  The per-channel sums run in f64 under a fixed tree."""
+    who = 'bn_frozen_backward'
+    dp, dbs = _chan_slice(dy, f'{who}: dy')
+    zp, zbs = _chan_slice(z, f'{who}: z')
+    b, c, hh, ww = dy.shape
+    if tuple(z.shape) != (b, c, hh, ww):
+        raise _lib.RpeError(f'{who}: dy and z must have one shape')
+    for name, t in (('gamma', gamma), ('mean', mean), ('var', var)) + ((('conv_bias', conv_bias),) if conv_bias is not None else ()):
+        _f32(t, f'{who}: {name}', numel=c)
+    dz = torch.empty(b, c, hh, ww, dtype=torch.float32, device=dy.device) if dz is None else dz
+    if tuple(dz.shape) != (b, c, hh, ww):
+        raise _lib.RpeError(f'{who}: dz must be ({b},{c},{hh},{ww})')
+    op, obs = _chan_slice(dz, f'{who}: dz')
+    nws = lib().rpe_bn_frozen_backward_workspace_bytes(b, c, hh * ww)
+    if nws == 0:
+        raise _lib.RpeError(f'{who}: empty tensors')
+    ws = torch.empty(nws, dtype=torch.uint8, device=dy.device)
+    dg, dbeta, dcb = (torch.empty(c, dtype=torch.float32, device=dy.device) for _ in range(3))
+    check(lib().rpe_bn_frozen_backward(dp, dbs, zp, zbs, ptr(gamma), ptr(conv_bias), ptr(mean), ptr(var), float(eps), b, c, hh * ww, ptr(dg),
+                                       ptr(dbeta), ptr(dcb), op, obs, ptr(ws), stream_ptr()), 'rpe_bn_frozen_backward')
+    return dz, dg, dbeta, dcb
+
+
+def instnorm_backward(dy, z, eps=1e-5, dz=None):
+    """rpe_instnorm_backward: dz = (dy - mean(dy) - xh mean(dy xh)) / sigma per plane of an instance norm without affine parameters, from dy
+    (behind the ReLU mask) and the norm's input z; plane moments in f64.  ``dz`` defaults to a new tensor (dy itself: in place)."""
+    dp, dbs = _chan_slice(dy, 'instnorm_backward: dy')
+    zp, zbs = _chan_slice(z, 'instnorm_backward: z')
+    b, c, hh, ww = dy.shape
+    dz = torch.empty(b, c, hh, ww, dtype=torch.float32, device=dy.device) if dz is None else dz
+    if tuple(z.shape) != (b, c, hh, ww) or tuple(dz.shape) != (b, c, hh, ww):
+        raise _lib.RpeError('instnorm_backward: dy, z and dz must have one shape')
+    op, obs = _chan_slice(dz, 'instnorm_backward: dz')
+    check(lib().rpe_instnorm_backward(dp, dbs, zp, zbs, b, c, hh * ww, float(eps), op, obs, stream_ptr()), 'rpe_instnorm_backward')
+    return dz
+
+
+def split_act_backward(grad, act, half, out=None):
+    """rpe_split_act_backward: grad (1 - act^2) on channels [0, half) and act > 0 ? grad : 0 on the rest, ``act`` = the activated output
+    (tanh | ReLU: the context encoder's net | inp); default in place on ``grad``."""
+    out = grad if out is None else out
+    gp, gbs = _chan_slice(grad, 'split_act_backward: grad')
+    ap, abs_ = _chan_slice(act, 'split_act_backward: act')
+    op, obs = _chan_slice(out, 'split_act_backward: out')
+    b, c, hh, ww = grad.shape
+    if tuple(act.shape) != (b, c, hh, ww) or tuple(out.shape) != (b, c, hh, ww) or not 0 <= half <= c:
+        raise _lib.RpeError('split_act_backward: grad, act and out must have one shape, and 0 <= half <= channels')
+    check(lib().rpe_split_act_backward(gp, gbs, ap, abs_, b, c, half, hh * ww, op, obs, stream_ptr()), 'rpe_split_act_backward')
+    return out

@@ -1162,6 +1162,23 @@ class RAFT(nn.Module):
         """The 22 parameters of the SepConvGRU and the motion encoder in raft_grad.UPDATE_PARAMS' order (raft_grad.update_step_backward)."""
         return tuple(operator.attrgetter(name)(self.update_block) for name in raft_grad.UPDATE_PARAMS)
 
+    def backward_encoders(self, image1, image2, fmap1, fmap2, net0, inp):
+        """The encoders' backward behind a ``forward(image1, image2, ..., grad_corr=True)`` pass whose loss has been differentiated: the
+        four leaves that pass returned carry d loss / d (fmap1, fmap2, net_0, inp) in their .grad; raft_grad.encoder_backward takes it
+        through fnet (both images, one batch) and through cnet (image1, behind the tanh | ReLU of its output) and the results are ADDED
+        into the .grad of the encoders' parameters, fnet's first, each in raft_grad.encoder_params' order.  With the node's own
+        gradients (heads, update block) that is RAFT's whole gradient, in two calls.  Nothing else of the model is touched."""
+        leaves = (fmap1, fmap2, net0, inp)
+        if any(t.grad is None for t in leaves):
+            raise RpeError('RAFT.backward_encoders: fmap1, fmap2, net0 and inp must be the leaves of a grad_corr pass after loss.backward() (a .grad is None)')
+        route = self._route(image_size=tuple(image1.shape[-2:]))
+        jobs = ((self.fnet, [image1, image2], torch.cat((fmap1.grad, fmap2.grad), dim=0), False),
+                (self.cnet, image1, torch.cat((net0.grad, inp.grad), dim=1), True))
+        for enc, images, d_out, split in jobs:
+            grads = raft_grad.encoder_backward(enc, images, d_out, raw255=True, split_act=split, route=route)
+            for p, g in zip(raft_grad.encoder_params(enc), grads):
+                p.grad = g if p.grad is None else p.grad + g
+
     def _save_state(self, ws, states, flow=None, coords1=None):
         """``grad_update``: the entry state of the iteration about to run as dense tensors of their own -- (hx's 256 channels: h_{k-1} |
         motion slot | flow_k, and coords1_k, which the lookup is about to read), the content only when the workspace is padded: one copy

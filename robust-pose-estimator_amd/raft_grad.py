@@ -23,16 +23,22 @@ fields are present; each stage includes the ones above it:
             window being linear in the pyramid and the pyramid bilinear in the maps; nothing goes into the coordinates.  Every launch
             and every gradient of 'update' keeps its bits.
 Refused before any launch (RAFT.check_grad_heads): update_fp16, CONV_BF16X3, mixed_precision -- a route that rounds the heads' operands
-has no honest gradient here -- and upsample=False; for 'corr' also alternate_corr (no pyramid) and CORR_BF16X3 (RAFT.check_grad_corr)."""
+has no honest gradient here -- and upsample=False; for 'corr' also alternate_corr (no pyramid) and CORR_BF16X3 (RAFT.check_grad_corr).
+
+The two encoders have their backward as stage functions of their own (encoder_params, residual_block_backward, encoder_backward;
+csrc/encoder_backward.hip), not yet as a depth of the record: RAFT.backward_encoders hands them the .grad of a 'corr' pass's leaves
+(fmap1, fmap2, net0, inp) and adds the results into the encoders' parameters."""
 import dataclasses
 from typing import Any, List, Optional, Tuple
 
 import torch
+import torch.nn as nn
 
 from . import _lib, ops
-from .ops import (CONV_LINEAR, PackedConv, _nchw, bounded_put, conv3x3_to2_bwd_data, conv_bwd_weight, conv_direct, conv_fused, copy_planes,
-                  gru_gates_h_recompute, gru_gates_r_backward, gru_gates_zq_backward, gru_gates_zr_recompute, relu_backward, sum_groups,
-                  upsample_convex_backward, wkey)
+from .ops import (CONV_LINEAR, PackedConv, _nchw, affine_act, bn_frozen_backward, bounded_put, conv3x3_to2_bwd_data, conv_bwd_weight,
+                  conv_direct, conv_fused, conv_s2_bwd_data, conv_s2_bwd_weight, copy_planes, gru_gates_h_recompute, gru_gates_r_backward,
+                  gru_gates_zq_backward, gru_gates_zr_recompute, instnorm_act, instnorm_backward, relu_backward, split_act_backward,
+                  sum_groups, upsample_convex_backward, wkey)
 
 TAIL_GROUP_3X3_FWD, TAIL_GROUP_3X3_BWD, TAIL_GROUP_1X1 = 16, 32, 64      # input channels per launch of the tail's forward-kernel convolutions
 # update_step_backward's parameter (and gradient) order: weight, bias of each -- 12 tensors of ``gru``, 10 of ``encoder``
@@ -41,6 +47,9 @@ UPDATE_PARAMS = tuple(f'{m}.{t}' for m in ('gru.convz1', 'gru.convr1', 'gru.conv
 # input channels per launch of the step's forward-kernel convolutions (forward recomputation and data gradients alike): 144 terms of a 3x3
 # layer, 160 of a 5-tap layer, 64 of the 1x1 -- the k-ordered f32 chain of a launch stays below the tail's 288, the groups are added in f64
 UPDATE_GROUP_3X3, UPDATE_GROUP_5TAP, UPDATE_GROUP_1X1 = 16, 32, 64
+# the encoders' backward: input channels per launch of a 3x3 layer's forward recomputation (144 terms), of its data gradient (288) and of
+# the 1x1 output layer (64); a stride-2 layer's recomputation runs ops.conv_direct on groups of at most ENC_CHAIN terms
+ENC_GROUP_3X3_FWD, ENC_GROUP_3X3_BWD, ENC_GROUP_1X1, ENC_CHAIN = 16, 32, 64, 288
 
 
 # ------------------------------------------------------------------------------------------------- weight packings
@@ -263,8 +272,242 @@ def update_step_backward(hx, inp, corr, d_net, params, ret_d_corr=False):
     return out + (d_corr,) if ret_d_corr else out
 
 
+# ------------------------------------------------------------------------------------------------- the encoders
+class _EncoderPacked(_SplitConvs):
+    """What the encoders' backward packs from an encoder's (or one block's) parameters: nothing at construction; the transposed, flipped
+    weight of every stride-1 layer (``tr``) and each channel group's slice and PackedConv on first use, under the layer's name."""
+
+    def __init__(self, params):
+        super().__init__()
+
+    def tr(self, name, weight):
+        return self.get((name, 'tr'), lambda: weight.detach().transpose(0, 1).flip(2, 3).contiguous())
+
+
+def _encoder_units(enc):
+    """(name, conv, norm or None) of an encoder's convolutions in encoder_params' order."""
+    units = [('conv1', enc.conv1, enc.norm1)]
+    for ln in ('layer1', 'layer2', 'layer3'):
+        for bi, blk in enumerate(getattr(enc, ln)):
+            units += _block_units(blk, f'{ln}.{bi}')
+    return units + [('conv2', enc.conv2, None)]
+
+
+def _block_units(blk, name):
+    units = [(f'{name}.conv1', blk.conv1, blk.norm1), (f'{name}.conv2', blk.conv2, blk.norm2)]
+    if blk.downsample is not None:
+        units.append((f'{name}.downsample', blk.downsample[0], blk.norm3))
+    return units
+
+
+def _unit_params(conv, norm):
+    affine = norm is not None and getattr(norm, 'weight', None) is not None
+    return [conv.weight, conv.bias] + ([norm.weight, norm.bias] if affine else [])
+
+
+def encoder_params(enc):
+    """A BasicEncoder's parameters in encoder_backward's order: the stem (conv1, norm1), then layer1[0], layer1[1], layer2[0], layer2[1],
+    layer3[0], layer3[1] -- of each block conv1 / norm1, conv2 / norm2 and, where it has one, downsample[0] / norm3 --, then conv2.  Each
+    convolution contributes (weight, bias), followed by its norm's (weight, bias) where the norm has them: 62 tensors with batch norm
+    (cnet), 32 with instance norm (fnet, whose norms have no parameters)."""
+    return [p for _, conv, norm in _encoder_units(enc) for p in _unit_params(conv, norm)]
+
+
+def block_params(block):
+    """One ResidualBlock's parameters in residual_block_backward's order (its part of encoder_params)."""
+    return [p for _, conv, norm in _block_units(block, '') for p in _unit_params(conv, norm)]
+
+
+def _conv_raw(P, name, conv, x):
+    """conv(x) WITHOUT its bias, on the backward's unfused route: stride 1 through conv_split; stride 2 on ops.conv_direct, on groups of input
+    channels of at most ENC_CHAIN terms added in f64 (one launch where the whole layer has no more: the 1x1 shortcuts, the stem)."""
+    w = conv.weight.detach()
+    cout, cin, k = w.shape[0], w.shape[1], w.shape[2]
+    if conv.stride[0] == 1:
+        return P.conv_split(name, x, w, None, False, ENC_GROUP_3X3_FWD if k == 3 else ENC_GROUP_1X1)
+    group = max(1, ENC_CHAIN // (k * k))
+    if cin <= group:
+        return conv_direct(x, w, None, 2, k // 2)
+    bounds = [(lo, min(cin, lo + group)) for lo in range(0, cin, group)]
+    b, _, hi, wi = x.shape
+    parts = torch.empty(len(bounds), b, cout, *ops._s2_out(hi, wi, k), dtype=torch.float32, device=x.device)
+    for gi, (lo, hi_) in enumerate(bounds):
+        conv_direct(x[:, lo:hi_], P.get((name, gi, 'w'), lambda: w[:, lo:hi_].contiguous()), None, 2, k // 2, out=parts[gi])
+    return sum_groups(parts)
+
+
+def _norm_act(P, name, conv, norm, z, relu, out=None):
+    """relu?(norm(z + conv.bias)) into a new tensor (or ``out``); z, the raw convolution output, stays: the adjoint reads it."""
+    out = torch.empty_like(z) if out is None else out
+    if isinstance(norm, nn.BatchNorm2d):
+        def fold():
+            scale = (norm.weight / torch.sqrt(norm.running_var + norm.eps)).detach().float().contiguous()
+            return scale, ((conv.bias - norm.running_mean) * scale + norm.bias).detach().float().contiguous()
+        key = wkey(norm.running_mean, norm.running_var)
+        scale, shift = P.get((name, 'affine', key), fold)
+        return affine_act(z, scale, shift, relu=relu, out=out)
+    return instnorm_act(z, conv.bias.detach(), eps=norm.eps, relu=relu, out=out)
+
+
+def _norm_adjoint(conv, norm, dy, z):
+    """The norm's adjoint in place on ``dy`` (behind the ReLU mask) -> (dz, the gradients of conv.bias and of the norm's parameters in
+    encoder_params' order).  Instance norm: the bias cancels under the norm, its gradient is exact zeros."""
+    if isinstance(norm, nn.BatchNorm2d):
+        dz, dg, dbeta, dcb = bn_frozen_backward(dy, z, norm.weight.detach(), conv.bias.detach(), norm.running_mean, norm.running_var, norm.eps, dz=dy)
+        return dz, [dcb, dg, dbeta]
+    return instnorm_backward(dy, z, eps=norm.eps, dz=dy), [torch.zeros_like(conv.bias)]
+
+
+def _block_forward(block, x, P, name):
+    """One ResidualBlock again, every intermediate kept: out = relu(skip + relu(norm2(conv2(relu(norm1(conv1 x)))))), skip = x or
+    norm3(conv1x1(x)) -> the record _block_backward reads."""
+    r = {'x': x}
+    r['z1'] = _conv_raw(P, f'{name}.conv1', block.conv1, x)
+    r['a1'] = _norm_act(P, f'{name}.conv1', block.conv1, block.norm1, r['z1'], True)
+    r['z2'] = _conv_raw(P, f'{name}.conv2', block.conv2, r['a1'])
+    pair = torch.empty(2, *r['z2'].shape, dtype=torch.float32, device=x.device)          # (skip, y): the two terms of the residual add
+    r['y'] = _norm_act(P, f'{name}.conv2', block.conv2, block.norm2, r['z2'], True, out=pair[1])
+    if block.downsample is not None:
+        r['zs'] = _conv_raw(P, f'{name}.downsample', block.downsample[0], x)
+        _norm_act(P, f'{name}.downsample', block.downsample[0], block.norm3, r['zs'], False, out=pair[0])
+    else:
+        copy_planes(x, pair[0])
+    r['out'] = sum_groups(pair, None, True)
+    return r
+
+
+def _block_backward(block, r, d_out, P, name):
+    """-> (d_x, the block's gradients in block_params' order) from the record of _block_forward."""
+    x, s2 = r['x'], block.downsample is not None
+    g = relu_backward(d_out, r['out'], out=torch.empty_like(d_out))          # behind the block's last ReLU: ONE mask, the gradient of both paths
+    gy = relu_backward(g, r['y'], out=torch.empty_like(g))
+    dz2, gn2 = _norm_adjoint(block.conv2, block.norm2, gy, r['z2'])
+    dw2 = conv_bwd_weight(r['a1'], dz2, (3, 3), bias=False)[0]
+    da1 = P.conv_split(f'{name}.conv2.t', dz2, P.tr(f'{name}.conv2', block.conv2.weight), None, False, ENC_GROUP_3X3_BWD)
+    relu_backward(da1, r['a1'])
+    dz1, gn1 = _norm_adjoint(block.conv1, block.norm1, da1, r['z1'])
+    if not s2:
+        dw1 = conv_bwd_weight(x, dz1, (3, 3), bias=False)[0]
+        # d x = conv1's data gradient + the shortcut's g, one more term of the same f64 sum
+        d_x = P.conv_split(f'{name}.conv1.t', dz1, P.tr(f'{name}.conv1', block.conv1.weight), None, False, ENC_GROUP_3X3_BWD, extra=1,
+                           fill=lambda terms: copy_planes(g, terms[0]))
+        return d_x, [dw1] + gn1 + [dw2] + gn2
+    dw1 = conv_s2_bwd_weight(x, dz1, 3, bias=False)[0]
+    dzs, gns = _norm_adjoint(block.downsample[0], block.norm3, g, r['zs'])
+    dws = conv_s2_bwd_weight(x, dzs, 1, bias=False)[0]
+    both = torch.empty(2, *x.shape, dtype=torch.float32, device=x.device)
+    conv_s2_bwd_data(dz1, block.conv1.weight, x.shape[-2:], out=both[0])
+    conv_s2_bwd_data(dzs, block.downsample[0].weight, x.shape[-2:], out=both[1])
+    return sum_groups(both), [dw1] + gn1 + [dw2] + gn2 + [dws] + gns
+
+
+def _check_modes(who, module):
+    """The refusals that need no tensor: a batch norm that would update its statistics, an active dropout."""
+    for m in module.modules():
+        if isinstance(m, nn.BatchNorm2d) and m.training:
+            raise _lib.RpeError(f'{who}: the batch norms must be frozen (eval mode, RAFT.freeze_bn): a batch norm in training mode has no backward here')
+        if isinstance(m, (nn.Dropout, nn.Dropout2d)) and m.training and m.p > 0:
+            raise _lib.RpeError(f'{who}: dropout > 0 in training mode has no backward here')
+
+
+def _check_block(who, block):
+    if block.conv1.stride[0] not in (1, 2) or (block.conv1.stride[0] == 2) != (block.downsample is not None) \
+            or not isinstance(block.norm1, (nn.BatchNorm2d, nn.InstanceNorm2d)):
+        raise _lib.RpeError(f'{who}: expected a ResidualBlock of stride 1, or of stride 2 with the norm3(conv1x1) shortcut, with batch or instance norm')
+    if isinstance(block.norm1, nn.InstanceNorm2d) and block.norm1.affine:
+        raise _lib.RpeError(f'{who}: the instance norms have no affine parameters here (raft._norm)')
+
+
+def residual_block_backward(block, x, d_out, packed, name='block'):
+    """Backward of ONE ResidualBlock (csrc/encoder_backward.hip), both norm kinds, stride 1 and stride 2 with the norm3(conv1x1) shortcut:
+    x (b,cin,h,w): the block's input; d_out: the gradient of its output; ``packed``: the _SplitConvs the weight slices are kept in
+    (``_packed(_EncoderPacked, block_params(block))``, or the encoder's, with the block's ``name`` in it).
+    -> (d_x, the gradients in block_params' order).  The block is recomputed from x on the unfused route; f32, bit-identical from run to run."""
+    who = 'residual_block_backward'
+    _check_modes(who, block)
+    _check_block(who, block)
+    x, d_out = _nchw(x, f'{who}: x'), _nchw(d_out, f'{who}: d_out')
+    b, cin, hi, wi = x.shape
+    st = block.conv1.stride[0]
+    want = (b, block.conv2.out_channels) + ((hi, wi) if st == 1 else ops._s2_out(hi, wi, 3))
+    if cin != block.conv1.in_channels or tuple(d_out.shape) != want:
+        raise _lib.RpeError(f'{who}: x must have {block.conv1.in_channels} channels and d_out be {want}, got {tuple(x.shape)} and {tuple(d_out.shape)}')
+    with torch.no_grad():
+        return _block_backward(block, _block_forward(block, x, packed, name), d_out, packed, name)
+
+
+def _encoder_out_shape(enc, n, hh, ww):
+    for _ in range(3):
+        hh, ww = ops._s2_out(hh, ww, 3)
+    return (n, enc.conv2.out_channels, hh, ww)
+
+
+def encoder_backward(enc, images, d_out, raw255=True, split_act=False, route=None):
+    """Backward of a BasicEncoder (fnet: instance norm; cnet: frozen batch norm) for one batch: ``images`` as BasicEncoder.forward takes them
+    (one batch or a list of batches, raw 0..255 with ``raw255``), d_out = d loss / d (the encoder's output), behind the tanh | ReLU of
+    ``split_act`` when that is set -> the list of parameter gradients in encoder_params' order.  Nothing goes into the images.
+    Every intermediate is recomputed from the images on an unfused route of its own -- the forward keeps nothing --: stride-1 layers and
+    their data gradients through conv_split, stride-2 layers on ops.conv_direct, the norms as passes of their own; raw convolution outputs
+    and block inputs live during the call only.  ``route``: the pass's raft.Route (RAFT hands its own; else the encoder's own flags under
+    the module switches).  Refused before any launch: a batch norm in training mode, dropout > 0 in training mode, update_fp16,
+    CONV_BF16X3, mixed_precision, tensors that are not float32, a d_out that is not the encoder's output shape.  f32, bit-identical
+    from run to run."""
+    from . import raft
+    who = 'encoder_backward'
+    _check_modes(who, enc)
+    route = raft.resolve_route(pad_encoders=enc.pad_encoders) if route is None else route
+    for flag, on in (('update_fp16', route.update_fp16), ('CONV_BF16X3', raft.CONV_BF16X3), ('mixed_precision', route.mixed_precision)):
+        if on:
+            raise _lib.RpeError(f'{who}: the encoders\' backward differentiates the f32 layers -- not with {flag}')
+    many = list(images) if isinstance(images, (list, tuple)) else [images]
+    for t in many + [d_out]:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise _lib.RpeError(f'{who}: images and d_out must be float32 tensors')
+    if any(im.dim() != 4 or im.shape[1:] != many[0].shape[1:] or im.shape[1] != enc.conv1.in_channels for im in many):
+        raise _lib.RpeError(f'{who}: images must be (n,{enc.conv1.in_channels},H,W) batches of one size')
+    want = _encoder_out_shape(enc, sum(im.shape[0] for im in many), *many[0].shape[-2:])
+    if tuple(d_out.shape) != want:
+        raise _lib.RpeError(f'{who}: d_out must have the encoder\'s output shape {want}, got {tuple(d_out.shape)}')
+    blocks = [(f'{ln}.{bi}', blk) for ln in ('layer1', 'layer2', 'layer3') for bi, blk in enumerate(getattr(enc, ln))]
+    for name, blk in blocks:
+        _check_block(f'{who}: {name}', blk)
+    d_out = _nchw(d_out, f'{who}: d_out')
+    P = _packed(_EncoderPacked, encoder_params(enc))
+    half = enc.conv2.out_channels // 2
+    with torch.no_grad():
+        x0 = _nchw((torch.cat(many, dim=0) if len(many) > 1 else many[0]).contiguous(), f'{who}: images')
+        if raw255:
+            x0 = 2 * (x0 / 255.0) - 1.0
+        # the forward, again
+        z0 = _conv_raw(P, 'conv1', enc.conv1, x0)
+        a0 = _norm_act(P, 'conv1', enc.conv1, enc.norm1, z0, True)
+        recs, x = [], a0
+        for name, blk in blocks:
+            recs.append(_block_forward(blk, x, P, name))
+            x = recs[-1]['out']
+        w2, b2 = enc.conv2.weight.detach(), enc.conv2.bias.detach()
+        if split_act:
+            out = torch.empty(want, dtype=torch.float32, device=x.device)
+            P.conv_split('conv2.lo', x, w2[:half], b2[:half].contiguous(), False, ENC_GROUP_1X1, out=out[:, :half])
+            out[:, :half].tanh_()
+            P.conv_split('conv2.hi', x, w2[half:], b2[half:].contiguous(), True, ENC_GROUP_1X1, out=out[:, half:])
+            d = split_act_backward(d_out, out, half, out=torch.empty_like(d_out))
+        else:
+            d = d_out
+        # the adjoints, last layer first
+        grads = list(conv_bwd_weight(x, d, (1, 1)))
+        d = P.conv_split('conv2.t', d, P.tr('conv2', w2), None, False, ENC_GROUP_1X1)
+        for (name, blk), r in zip(reversed(blocks), reversed(recs)):
+            d, g = _block_backward(blk, r, d, P, name)
+            grads = g + grads
+            r.clear()
+        relu_backward(d, a0)
+        dz0, gn0 = _norm_adjoint(enc.conv1, enc.norm1, d, z0)
+        return [conv_s2_bwd_weight(x0, dz0, 7, bias=False)[0]] + gn0 + grads
+
+
 # ------------------------------------------------------------------------------------------------- a pass's record and the node
-STAGES = ('heads', 'update', 'corr')
+STAGES =('heads', 'update', 'corr')
 
 
 @dataclasses.dataclass(eq=False)
