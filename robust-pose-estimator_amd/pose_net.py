@@ -60,12 +60,16 @@ class PoseNet(nn.Module):
         ``upsample=False``: everything at 1/8 resolution, the flow in 1/8-pixel units and the depth divided by 8 (:131-132;
         a division by a power of two commutes with the rounding of b / -flow.x, so the kernel is handed b / 8).
         ``ret_cache`` additionally returns the encoder outputs of ``imagel`` for reuse by the next ``infer``.
-        ``grad`` = 'heads', 'update' or 'corr': the pass runs as RAFT.grad_pass runs it, and its raft_grad.GradPass, leaves made, is
-        returned as a fourth element: what ``stages`` takes as ``pass1``."""
+        ``grad`` = 'heads', 'update', 'corr' or 'encoders': the pass runs as RAFT.grad_pass runs it, and its raft_grad.GradPass, leaves
+        made, is returned as a fourth element: what ``stages`` takes as ``pass1``.  At 'encoders' the record names ``imagel`` and ``imager``
+        as the sources of its maps (not with ``enc``: maps encoded elsewhere cannot be differentiated here)."""
         n = imagel.shape[0]
+        if grad == 'encoders' and enc is not None:
+            raise ValueError("flow2depth: grad='encoders' encodes the images itself: not with enc=")
         f, cn = (enc['f'], enc['c']) if enc is not None else self._encode_both((imagel, imager), imagel)
         if grad is not None:
-            r, rec = self.flow.grad_pass((f[:n], f[n:]), cn, stages=grad, upsample=upsample)
+            kw = dict(sources=((imagel, 0, n), (imager, 0, n), (imagel, 0, n))) if grad == 'encoders' else {}
+            r, rec = self.flow.grad_pass((f[:n], f[n:]), cn, stages=grad, upsample=upsample, **kw)
         else:
             r = self.flow(None, None, upsample=upsample, fmaps=(f[:n], f[n:]), cnet=cn)
         flow = r[0][-1]
@@ -101,13 +105,20 @@ class PoseNet(nn.Module):
         ``grad_corr`` (with ``ret_flows``): the call goes as deep as 'corr' whether or not the update block's parameters require grad: the
         dict gains 'fmap1' and 'fmap2', leaves per pass ('time', 'stereo1', 'stereo2') beside 'net0' and 'inp' -- copies of the rows of the
         feature maps each pass correlated -- whose ``.grad`` is d loss / d fmap: what a backward of the feature encoder has to be handed.
-        Pose, depths and every other gradient keep their bits.  Refused before any launch with alternate_corr."""
+        Pose, depths and every other gradient keep their bits.  Refused before any launch with alternate_corr.
+        With a parameter of an encoder trainable (``freeze_flow(False, parts='fnet' | 'cnet' | 'encoders' | 'raft')``) the call goes as deep as
+        'encoders', whatever ``ret_flows`` and ``grad_corr`` say: the node runs each encoder's backward once, on the distinct images -- fnet
+        on (1l, 2l, 1r, 2r), cnet on (1l, 2l), the gradients of the passes that share an image summed first --, and the weight heads read the
+        time pass's ``hidden_out`` and ``context_out``, so the pose loss also reaches the GRU and the context encoder through the weight
+        heads, as in the reference's training forward.  The dict carries the same leaf groups as with ``grad_corr``; their .grad hold
+        the full gradients.  Pose, depths, weight maps and the gradients of the weight heads and ``loss_weight`` keep their bits."""
         n = image1l.shape[0]
         intrinsics = intrinsics.expand(n, 3, 3).contiguous()
         baseline = baseline.expand(n).contiguous()
         if grad_corr and not ret_flows:
             raise ValueError('PoseNet.forward: grad_corr returns its leaves in the dict of ret_flows: it needs ret_flows=True')
-        grad = 'corr' if grad_corr else 'update' if self.flow_update_trainable() else 'heads' if self.flow_heads_trainable() else None
+        grad = 'encoders' if self.flow_encoders_trainable() else 'corr' if grad_corr else 'update' if self.flow_update_trainable() \
+            else 'heads' if self.flow_heads_trainable() else None
         if grad is not None:
             self.flow.check_grad(grad)                         # (before anything is launched)
         with torch.no_grad():
@@ -153,6 +164,16 @@ class PoseNet(nn.Module):
         params = getattr(self.flow, 'update_params', None)
         return params is not None and any(p.requires_grad for p in params())
 
+    def flow_encoder_params(self, which='encoders'):
+        """The parameters of RAFT's feature encoder ('fnet'), context encoder ('cnet') or both, fnet's first, in raft_grad.encoder_params' order."""
+        return [p for name in (('fnet', 'cnet') if which == 'encoders' else (which,)) for p in raft_grad.encoder_params(getattr(self.flow, name))]
+
+    def flow_encoders_trainable(self):
+        """Does a parameter of RAFT's encoders require grad (``freeze_flow(False, parts='fnet' | 'cnet' | 'encoders' | 'raft')``)?"""
+        if not (hasattr(self.flow, 'fnet') and hasattr(self.flow, 'cnet')):
+            return False
+        return any(p.requires_grad for p in self.flow_encoder_params())
+
     def freeze_flow(self, freeze=True, parts=None):
         """pose_net.py:148-153.  Un-freezing the whole flow network needs its backward, which is built from the loss inwards as far as the
         update block: the gradients of the pose loss reach the three flows (``forward(..., ret_flows=True)``: the pose layer's and the geometry
@@ -161,10 +182,14 @@ class PoseNet(nn.Module):
         only --, and through the backward of the N update steps (csrc/update_backward.hip, raft_grad.update_step_backward) the SepConvGRU and the
         motion encoder -- ``freeze_flow(False, parts='update')`` sets it on all of ``flow.update_block``.  The correlation has a backward as
         well (csrc/corr_backward.hip; it has no parameters): ``forward(..., ret_flows=True, grad_corr=True)`` hands the gradient to the two
-        feature maps of every pass.  Only the two encoders have no backward here: ``freeze_flow(False)`` without ``parts`` is refused
-        instead of training against silently missing gradients."""
-        if parts not in (None, 'heads', 'update'):
-            raise ValueError(f"freeze_flow: parts must be None, 'heads' or 'update', got {parts!r}")
+        feature maps of every pass.  Behind it the two encoders have theirs (csrc/encoder_backward.hip, raft_grad.encoder_backward), run by
+        the same node: ``parts='fnet'`` and ``parts='cnet'`` set requires_grad on that encoder's parameters only, ``parts='encoders'`` on both,
+        and ``parts='raft'`` on every parameter of ``self.flow`` -- ``freeze_flow(False, parts='raft')`` is what the reference's
+        ``freeze_flow(False)`` means here: the whole flow network trains on the pose loss through ``forward`` and ``loss.backward()``.
+        The bare ``freeze_flow(False)`` without ``parts`` is still refused, with the message it had while the encoders had no backward:
+        callers (and this project's tests) that rely on the refusal keep it, and training RAFT whole is asked for by name."""
+        if parts not in (None, 'heads', 'update', 'fnet', 'cnet', 'encoders', 'raft'):
+            raise ValueError(f"freeze_flow: parts must be None, 'heads', 'update', 'fnet', 'cnet', 'encoders' or 'raft', got {parts!r}")
         if not freeze and parts == 'heads':
             for p in self.flow_head_params():
                 p.requires_grad = True
@@ -173,11 +198,20 @@ class PoseNet(nn.Module):
             for p in self.flow.update_block.parameters():
                 p.requires_grad = True
             return self
+        if not freeze and parts in ('fnet', 'cnet', 'encoders'):
+            for p in self.flow_encoder_params(parts):
+                p.requires_grad = True
+            return self
+        if not freeze and parts == 'raft':
+            for p in self.flow.parameters():
+                p.requires_grad = True
+            return self
         if not freeze:
             raise NotImplementedError('training the whole flow network (freeze_flow(False)) is out of scope: the gradients stop at the flows '
                                       '(forward(..., ret_flows=True) returns them), at RAFT\'s output heads (parts=\'heads\') or at its update '
                                       'block (parts=\'update\'), and through the correlation at the feature maps (grad_corr=True); the two '
-                                      'encoders have no backward here')
+                                      'encoders have no backward here under this spelling -- whole-network training, the reference\'s '
+                                      'freeze_flow(False), is freeze_flow(False, parts=\'raft\')')
         for p in self.parameters():
             p.requires_grad = True
         for p in self.flow.parameters():
@@ -231,7 +265,8 @@ class PoseNet(nn.Module):
         ``pass1`` = the raft_grad.GradPass of the pass that made stereo_flow1 (flow2depth's ``grad``; needs grad_flows): RAFT trains as deep
         as that record goes.  The batched pass runs as deep (RAFT.grad_pass), its two halves are rows of its record, and the three flows
         leave ONE raft_grad.attach node over (time, stereo1, stereo2).  'hidden' is the temporal pairs' hidden state as a leaf that requires
-        grad, and for every leaf field the records carry -- 'hidden'; 'net0', 'inp'; 'fmap1', 'fmap2' -- the result gains
+        grad -- at depth 'encoders' 'hidden' and 'context' are the time pass's hidden_out and context_out of the node, and the batched pass's
+        record names (image1l | image2l), (image2l | image2r) and (image1l | image2l) as the sources of its maps --, and for every leaf field the records carry -- 'hidden'; 'net0', 'inp'; 'fmap1', 'fmap2' -- the result gains
         '<field>_leaves' = {'time', 'stereo1', 'stereo2'}."""
         n = image1l.shape[0]
         intrinsics = intrinsics.expand(n, 3, 3).contiguous()
@@ -253,6 +288,11 @@ class PoseNet(nn.Module):
         if flow_init is not None:
             kw['flow_init'] = torch.cat((flow_init, torch.zeros_like(flow_init)), dim=0)      # (temporal | stereo) rows of the RAFT batch
         if pass1 is not None:
+            deep = pass1.depth == 'encoders'
+            if deep and cache1 is not None:
+                raise ValueError("stages: a pass1 of depth 'encoders' encodes every image here: not with cache1=")
+            if deep:                                          # (fmaps = f[:2n], f[n:] of f = fnet(1l | 2l | 2r); cn = cnet(1l | 2l))
+                kw['sources'] = (((image1l, image2l), 0, 2 * n), ((image2l, image2r), 0, 2 * n), ((image1l, image2l), 0, 2 * n))
             r, rec2 = self.flow.grad_pass(fmaps, cn, stages=pass1.depth, upsample=True, **kw)
         else:
             r = self.flow(None, None, upsample=True, fmaps=fmaps, cnet=cn, ret_lowres=ret_lowres, **kw)
@@ -266,8 +306,12 @@ class PoseNet(nn.Module):
                 if pass1 is not None:
                     passes = dict(time=rec2.rows(0, n), stereo1=pass1, stereo2=rec2.rows(n, 2 * n))
                     hidden = passes['time'].hidden             # (the weight heads read it: their input gradient lands in its .grad)
-                    time_flow, stereo_flow1, stereo_flow2 = raft_grad.attach(
-                        list(passes.values()), self.flow.head_params(), None if pass1.depth == 'heads' else self.flow.update_params())
+                    outs = raft_grad.attach(list(passes.values()), self.flow.head_params(), None if pass1.depth == 'heads' else self.flow.update_params(),
+                                            (self.flow.fnet, self.flow.cnet) if deep else None)
+                    if deep:                                   # (the weight heads read the node's outputs: their input gradients return into the chain)
+                        _, hidden, context = outs[0]
+                        outs = [o[0] for o in outs]
+                    time_flow, stereo_flow1, stereo_flow2 = outs
                     for t in (time_flow, stereo_flow1, stereo_flow2):
                         t.retain_grad()
                 else:

@@ -1196,13 +1196,21 @@ class RAFT(nn.Module):
         states.append((st, ops.copy_planes(co, torch.empty_like(co))))
 
     @torch.no_grad()
-    def grad_pass(self, fmaps, cnet, *, stages, **kw):
+    def grad_pass(self, fmaps, cnet, *, stages, sources=None, **kw):
         """One gradient-free ``ret_lowres`` pass on given encoder outputs (``kw``: upsample, iters, all_flows, flow_init), run so that
-        raft_grad can differentiate it as far as ``stages`` -- 'heads', 'update' or 'corr' (raft_grad's module docstring) -> (forward's
-        result with the 1/8 flow as its 4th element, the raft_grad.GradPass of the whole batch; GradPass.rows makes its leaves).  The
-        refusals are raised before any launch.  Below 'heads' the pass runs iteration by iteration and saves every iteration's entry
-        state, and its pyramid is the record's from here on, no longer the model's."""
+        raft_grad can differentiate it as far as ``stages`` -- 'heads', 'update', 'corr' or 'encoders' (raft_grad's module docstring) ->
+        (forward's result with the 1/8 flow as its 4th element, the raft_grad.GradPass of the whole batch; GradPass.rows makes its
+        leaves).  ``sources`` (with 'encoders', and only then): where fmaps[0], fmaps[1] and cnet came from, an (images, lo, hi) each --
+        one raw 0..255 image batch, or a tuple of batches that were encoded as one, and the rows of it.  The refusals are raised before
+        any launch.  Below 'heads' the pass runs iteration by iteration and saves every iteration's entry state, and its pyramid is the
+        record's from here on, no longer the model's."""
         self.check_grad(stages, kw.get('upsample', True))
+        if (sources is None) != (stages != 'encoders'):
+            raise RpeError("RAFT.grad_pass: sources goes with stages='encoders', and only with it")
+        if sources is not None:
+            for (_, lo, hi), t in zip(sources, (*fmaps, cnet)):
+                if hi - lo != t.shape[0]:
+                    raise RpeError(f'RAFT.grad_pass: a source names {hi - lo} images for {t.shape[0]} rows of encoder output')
         states = None if stages == 'heads' else []
         r = self._forward_impl(self._route(map_size=tuple(fmaps[0].shape[-2:])), fmaps, cnet, ret_lowres=True, states=states, **kw)
         rec = raft_grad.GradPass(r[0][-1], r[1], r[3])
@@ -1210,8 +1218,10 @@ class RAFT(nn.Module):
             c = self.hidden_dim
             rec.net0, rec.inp, rec.states = cnet[:, :c], cnet[:, c:], states
             rec.pyr, self._pyr = self._pyr, None
-        if stages == 'corr':
+        if stages in ('corr', 'encoders'):
             rec.fmap1, rec.fmap2 = fmaps                      # (what the pass correlated)
+        if sources is not None:
+            rec.sources = tuple((images, lo, hi) for images, lo, hi in sources)
         return r, rec
 
     def check_grad(self, stages, upsample=True):
@@ -1219,8 +1229,11 @@ class RAFT(nn.Module):
         if stages not in raft_grad.STAGES:
             raise ValueError(f'RAFT: stages must be one of {raft_grad.STAGES}, got {stages!r}')
         self.check_grad_heads(upsample)
-        if stages == 'corr':
+        if stages in ('corr', 'encoders'):
             self.check_grad_corr()
+        if stages == 'encoders':                               # (what raft_grad.encoder_backward refuses without a tensor in hand)
+            for enc in (self.fnet, self.cnet):
+                raft_grad._check_modes('RAFT: grad_encoders', enc)
 
     def check_grad_heads(self, upsample=True):
         """The refusals of ``grad_heads`` (raised before anything is launched): the tail's backward differentiates the f32 layers; a route
@@ -1246,7 +1259,7 @@ class RAFT(nn.Module):
 
     @torch.no_grad()
     def forward(self, image1, image2, upsample=True, iters=None, all_flows=False, fmaps=None, cnet=None, flow_init=None, ret_lowres=False,
-                grad_heads=False, grad_update=False, grad_corr=False):
+                grad_heads=False, grad_update=False, grad_corr=False, grad_encoders=False):
         """image1, image2: (N,3,H,W) in 0..255.  Inference only (the reference freezes RAFT, train.yaml:51).
         ``fmaps`` / ``cnet`` accept encoder outputs computed elsewhere (both encoders normalise per sample -- instance
         norm / frozen batch norm -- so a caller may encode every distinct image once and reuse it); with both given the
@@ -1259,18 +1272,36 @@ class RAFT(nn.Module):
         the output heads / the whole update block through time / the correlation.  raft_grad's module docstring says what each stage
         saves, costs, differentiates and refuses.  ``hidden`` comes back as a leaf that requires grad (.grad = d loss / d net_N); behind
         the result grad_update appends the leaves ``net_0`` (N,128,h8,w8) and ``inp`` (a leaf copy of the context), grad_corr also
-        ``fmap1`` and ``fmap2`` (leaf copies of the maps the pass correlated)."""
-        stages = 'corr' if grad_corr else 'update' if grad_update else 'heads' if grad_heads else None
+        ``fmap1`` and ``fmap2`` (leaf copies of the maps the pass correlated).
+        ``grad_encoders`` (implies grad_corr): the node goes on through both encoders (raft_grad's depth 'encoders'), so after
+        ``loss.backward()`` EVERY parameter of the model that requires grad has its gradient; no second call (backward_encoders) is
+        needed.  It needs the images: with ``fmaps`` or ``cnet`` given it is refused before any launch -- an encoder output computed
+        elsewhere cannot be differentiated here -- as are a batch norm in training mode and an active dropout.  It returns what a
+        grad_corr call returns, with the same values, except that ``hidden`` and the context are the node's ``hidden_out`` and
+        ``context_out``: whatever a consumer differentiates of them returns into the chain (the four leaves behind still get their .grad)."""
+        stages = 'encoders' if grad_encoders else 'corr' if grad_corr else 'update' if grad_update else 'heads' if grad_heads else None
         if stages is not None:
             self.check_grad(stages, upsample)                  # (before the encoders run: a refused pass launches nothing)
+        sources = None
+        if grad_encoders:
+            if fmaps is not None or cnet is not None or image1 is None or image2 is None:
+                raise RpeError('RAFT: grad_encoders differentiates the encoders on the images -- not with fmaps= or cnet= (an encoder output '
+                               'computed elsewhere cannot be differentiated here)')
+            N = image1.shape[0]
+            sources = ((image1, 0, N), (image2, 0, N), (image1, 0, N))
         fmaps, cnet, route = self._encoded(image1, image2, fmaps, cnet)
         if stages is None:
             return self._forward_impl(route, fmaps, cnet, upsample, iters, all_flows, flow_init, ret_lowres)
-        (flows, _, context, low), rec = self.grad_pass(fmaps, cnet, stages=stages, upsample=upsample, iters=iters, all_flows=all_flows, flow_init=flow_init)
+        (flows, _, context, low), rec = self.grad_pass(fmaps, cnet, stages=stages, sources=sources, upsample=upsample, iters=iters, all_flows=all_flows,
+                                                       flow_init=flow_init)
         rec = rec.rows(0, rec.hidden.shape[0])
-        flows[-1] = raft_grad.attach([rec], self.head_params(), None if stages == 'heads' else self.update_params())[0]
+        hidden = rec.hidden
+        if grad_encoders:
+            flows[-1], hidden, context = raft_grad.attach([rec], self.head_params(), self.update_params(), (self.fnet, self.cnet))[0]
+        else:
+            flows[-1] = raft_grad.attach([rec], self.head_params(), None if stages == 'heads' else self.update_params())[0]
         leaves = tuple(t for t in (rec.net0, rec.inp, rec.fmap1, rec.fmap2) if t is not None)
-        return (flows, rec.hidden, context) + ((low,) if ret_lowres else ()) + leaves
+        return (flows, hidden, context) + ((low,) if ret_lowres else ()) + leaves
 
     def _encoded(self, image1, image2, fmaps, cnet):
         """What forward's caller did not bring of the encoder outputs -> ((fmap1, fmap2), cnet, the pass's Route)."""

@@ -1,7 +1,7 @@
 """RAFT's backward for training on the pose loss, composed on the host from the one-kernel wrappers of ops.py: the two stage functions
 (raft_tail_backward, update_step_backward), the weight packings they run on, the record of what a pass saves (GradPass) and the ONE
 autograd node over such records (attach).  The forward stays what it is -- a gradient-free pass, the launches and the bits of a
-``ret_lowres`` pass --; RAFT.grad_pass runs it and fills the record, RAFT.forward(grad_heads= / grad_update= / grad_corr=) and
+``ret_lowres`` pass --; RAFT.grad_pass runs it and fills the record, RAFT.forward(grad_heads= / grad_update= / grad_corr= / grad_encoders=) and
 PoseNet.stages attach the node.
 
 Upstream detaches coords1 at the top of every iteration.  The returned prediction therefore depends on the output heads through their
@@ -22,12 +22,26 @@ fields are present; each stage includes the ones above it:
             after step 1 the build's adjoint runs once (ops.corr_build_backward, csrc/corr_backward.hip): fmap.grad = d loss / d fmap, the
             window being linear in the pyramid and the pyramid bilinear in the maps; nothing goes into the coordinates.  Every launch
             and every gradient of 'update' keeps its bits.
+  'encoders' + (sources): where the pass's three encoder inputs came from -- for fmap1, for fmap2 and for the context a (raw 0..255 image
+            batch or tuple of batches read as one, lo, hi) each; not a tensor field.  The node takes the encoders' 94 parameters behind the
+            other 30 (attach(..., encoders=(fnet, cnet))) and gives every pass two more outputs, ``hidden_out`` (the values of hidden) and
+            ``context_out`` (those of inp): what a consumer differentiates -- PoseNet's weight heads read both -- returns into the chain.  A
+            gradient on hidden_out is added to the tail's d net_N once, before step N; one on context_out is added to d inp once, behind the
+            steps' sum; the leaves' .grad hold these full gradients.  A pass runs its tail if its flow has a gradient and its steps if its
+            flow or its hidden_out has one.  After the last pass the distinct images are collected by source identity (the same batch
+            object and row; content is never compared) in the order of first appearance -- passes in the given order, fmap1's source
+            before fmap2's, rows ascending -- and each image's d fmap is the sum of the contributing leaves' gradients in that walk order,
+            added in f64 and rounded once (ops.sum_groups; a single contribution passes through unchanged); likewise cat(d net0, d inp) per
+            distinct context image.  encoder_backward then runs ONCE per encoder, on the images something contributed to, and not at all
+            for an encoder none of whose parameters requires grad; the 94 gradients leave the node as the gradients of its inputs.
+            Every launch and every gradient of 'corr' keeps its bits.  This is what the reference's freeze_flow(False) trains.
 Refused before any launch (RAFT.check_grad_heads): update_fp16, CONV_BF16X3, mixed_precision -- a route that rounds the heads' operands
-has no honest gradient here -- and upsample=False; for 'corr' also alternate_corr (no pyramid) and CORR_BF16X3 (RAFT.check_grad_corr).
+has no honest gradient here -- and upsample=False; for 'corr' also alternate_corr (no pyramid) and CORR_BF16X3 (RAFT.check_grad_corr); for
+'encoders' also a batch norm in training mode and an active dropout in an encoder (_check_modes).
 
-The two encoders have their backward as stage functions of their own (encoder_params, residual_block_backward, encoder_backward;
-csrc/encoder_backward.hip), not yet as a depth of the record: RAFT.backward_encoders hands them the .grad of a 'corr' pass's leaves
-(fmap1, fmap2, net0, inp) and adds the results into the encoders' parameters."""
+The encoders' backward is a stage function of its own (encoder_params, residual_block_backward, encoder_backward;
+csrc/encoder_backward.hip).  Beside the depth above, RAFT.backward_encoders still hands it the .grad of a 'corr' pass's leaves (fmap1,
+fmap2, net0, inp) by hand and adds the results into the encoders' parameters."""
 import dataclasses
 from typing import Any, List, Optional, Tuple
 
@@ -50,6 +64,7 @@ UPDATE_GROUP_3X3, UPDATE_GROUP_5TAP, UPDATE_GROUP_1X1 = 16, 32, 64
 # the encoders' backward: input channels per launch of a 3x3 layer's forward recomputation (144 terms), of its data gradient (288) and of
 # the 1x1 output layer (64); a stride-2 layer's recomputation runs ops.conv_direct on groups of at most ENC_CHAIN terms
 ENC_GROUP_3X3_FWD, ENC_GROUP_3X3_BWD, ENC_GROUP_1X1, ENC_CHAIN = 16, 32, 64, 288
+ENC_WGRAD_CHAIN = 1024                                                   # pixels rpe_conv_bwd_weight keeps in one chunk (include/rpe.h: its chunk rule)
 
 
 # ------------------------------------------------------------------------------------------------- weight packings
@@ -358,6 +373,21 @@ def _norm_adjoint(conv, norm, dy, z):
     return instnorm_backward(dy, z, eps=norm.eps, dz=dy), [torch.zeros_like(conv.bias)]
 
 
+def _bwd_weight(x, dy, kernel, bias=True):
+    """ops.conv_bwd_weight for the encoders' stride-1 layers.  rpe_conv_bwd_weight splits K = b h w into chunks only above ENC_WGRAD_CHAIN
+    pixels; a batch of several small maps below that would be ONE f32 chain across the images (at K = 512, two 16 x 16 maps, 2.6 times the
+    error of a blocked float32 sum on the output layer's weight).  There each image's GEMM runs alone and the images are added in f64
+    (sum_groups); one image, or a batch the kernel chunks itself, is the one launch it was."""
+    b, _, hh, ww = x.shape
+    if b == 1 or b * hh * ww > ENC_WGRAD_CHAIN:
+        return conv_bwd_weight(x, dy, kernel, bias=bias)
+    per = [conv_bwd_weight(x[i:i + 1], dy[i:i + 1], kernel, bias=bias) for i in range(b)]
+    dw0 = per[0][0]
+    dw = sum_groups(torch.stack([p[0] for p in per]).view(b, 1, dw0.shape[0], -1, dw0.shape[3])).view_as(dw0)
+    db = sum_groups(torch.stack([p[1] for p in per]).view(b, 1, -1, 1, 1)).view(-1) if bias else None
+    return dw, db
+
+
 def _block_forward(block, x, P, name):
     """One ResidualBlock again, every intermediate kept: out = relu(skip + relu(norm2(conv2(relu(norm1(conv1 x)))))), skip = x or
     norm3(conv1x1(x)) -> the record _block_backward reads."""
@@ -382,12 +412,12 @@ def _block_backward(block, r, d_out, P, name):
     g = relu_backward(d_out, r['out'], out=torch.empty_like(d_out))          # behind the block's last ReLU: ONE mask, the gradient of both paths
     gy = relu_backward(g, r['y'], out=torch.empty_like(g))
     dz2, gn2 = _norm_adjoint(block.conv2, block.norm2, gy, r['z2'])
-    dw2 = conv_bwd_weight(r['a1'], dz2, (3, 3), bias=False)[0]
+    dw2 = _bwd_weight(r['a1'], dz2, (3, 3), bias=False)[0]
     da1 = P.conv_split(f'{name}.conv2.t', dz2, P.tr(f'{name}.conv2', block.conv2.weight), None, False, ENC_GROUP_3X3_BWD)
     relu_backward(da1, r['a1'])
     dz1, gn1 = _norm_adjoint(block.conv1, block.norm1, da1, r['z1'])
     if not s2:
-        dw1 = conv_bwd_weight(x, dz1, (3, 3), bias=False)[0]
+        dw1 = _bwd_weight(x, dz1, (3, 3), bias=False)[0]
         # d x = conv1's data gradient + the shortcut's g, one more term of the same f64 sum
         d_x = P.conv_split(f'{name}.conv1.t', dz1, P.tr(f'{name}.conv1', block.conv1.weight), None, False, ENC_GROUP_3X3_BWD, extra=1,
                            fill=lambda terms: copy_planes(g, terms[0]))
@@ -495,7 +525,7 @@ def encoder_backward(enc, images, d_out, raw255=True, split_act=False, route=Non
         else:
             d = d_out
         # the adjoints, last layer first
-        grads = list(conv_bwd_weight(x, d, (1, 1)))
+        grads = list(_bwd_weight(x, d, (1, 1)))
         d = P.conv_split('conv2.t', d, P.tr('conv2', w2), None, False, ENC_GROUP_1X1)
         for (name, blk), r in zip(reversed(blocks), reversed(recs)):
             d, g = _block_backward(blk, r, d, P, name)
@@ -507,7 +537,17 @@ def encoder_backward(enc, images, d_out, raw255=True, split_act=False, route=Non
 
 
 # ------------------------------------------------------------------------------------------------- a pass's record and the node
-STAGES =('heads', 'update', 'corr')
+STAGES = ('heads', 'update', 'corr', 'encoders')
+
+
+def _source_rows(source):
+    """A record's source (images, lo, hi) -- ``images`` one raw image batch or a tuple of batches read as one -- -> [(batch, row in it)] of
+    its rows lo .. hi - 1: the identity of each image."""
+    images, lo, hi = source
+    flat = [(im, r) for im in (images if isinstance(images, (list, tuple)) else (images,)) for r in range(im.shape[0])]
+    if not 0 <= lo <= hi <= len(flat):
+        raise _lib.RpeError(f'raft_grad: a source\'s rows {lo}:{hi} are not rows of its {len(flat)} images')
+    return flat[lo:hi]
 
 
 @dataclasses.dataclass(eq=False)
@@ -526,13 +566,14 @@ class GradPass:
     fmap2: Optional[torch.Tensor] = None
     whole: Optional[tuple] = None                            # rows(): (the whole pass's coords1_k, lo, hi) -- the pyramid holds every row
     _last: tuple = (None, None)                              # corr's memo: (k, the whole pass's window of iteration k + 1)
+    sources: Optional[tuple] = None                          # 'encoders': ((images, lo, hi) of fmap1, of fmap2, of the context): _source_rows
 
     TENSORS = ('flow_up', 'hidden', 'flow_low', 'net0', 'inp', 'fmap1', 'fmap2')        # the node's tensor inputs, in this order
     LEAVES = ('hidden', 'net0', 'inp', 'fmap1', 'fmap2')                                # ... of which a backward fills the .grad
 
     @property
     def depth(self):
-        return STAGES[(self.net0 is not None) + (self.fmap1 is not None)]
+        return STAGES[(self.net0 is not None) + (self.fmap1 is not None) + (self.fmap1 is not None and self.sources is not None)]
 
     def tensors(self):
         """{field: tensor} of the tensor fields that are present, in field order."""
@@ -540,7 +581,8 @@ class GradPass:
 
     def rows(self, lo, hi):
         """The record of rows [lo, hi) of the batch: tensors and states sliced, ``hidden`` a detached leaf that requires grad, ``net0``,
-        ``inp``, ``fmap1`` and ``fmap2`` cloned into fresh leaves.  The pyramid stays whole: ``corr`` slices the window."""
+        ``inp``, ``fmap1`` and ``fmap2`` cloned into fresh leaves, the sources' row ranges narrowed.  The pyramid stays whole: ``corr``
+        slices the window."""
         leaf = lambda t: None if t is None else t[lo:hi].clone().requires_grad_(True)
         fleaf = lambda t: None if t is None else t[lo:hi].float().clone(memory_format=torch.contiguous_format).requires_grad_(True)
         states, whole = None, None
@@ -548,8 +590,9 @@ class GradPass:
             states = [(st[lo:hi], co[lo:hi]) for st, co in self.states]
             coords, base = ([co for _, co in self.states], 0) if self.whole is None else self.whole[:2]
             whole = (coords, base + lo, base + hi)
+        sources = None if self.sources is None else tuple((images, base + lo, base + hi) for images, base, _ in self.sources)
         return GradPass(self.flow_up[lo:hi].contiguous(), self.hidden[lo:hi].detach().requires_grad_(True), self.flow_low[lo:hi],
-                        leaf(self.net0), leaf(self.inp), states, self.pyr, fleaf(self.fmap1), fleaf(self.fmap2), whole)
+                        leaf(self.net0), leaf(self.inp), states, self.pyr, fleaf(self.fmap1), fleaf(self.fmap2), whole, sources=sources)
 
     def corr(self, k):
         """The window iteration k + 1 looked up (``states[k]`` = its (hx, coords1)): the pass's lookup on the saved coordinates against
@@ -568,10 +611,10 @@ def _by_field(passes, tensors):
 
 
 def _through_time(rec, t, upd, grads):
-    """The steps k = N .. 1 of one pass behind its tail's grads['hidden'] = d net_N; at 'corr' depth every step's lookup adjoint and, after
-    step 1, the build's.  ``t``: the pass's tensor inputs by field.  Fills ``grads`` (field -> gradient); -> the 22 update gradients
-    summed in descending k (zeros for a pass without states)."""
-    with_corr = rec.depth == 'corr'
+    """The steps k = N .. 1 of one pass behind grads['hidden'] = d net_N (the tail's, at 'encoders' plus what arrived on hidden_out); from
+    'corr' on every step's lookup adjoint and, after step 1, the build's.  ``t``: the pass's tensor inputs by field.  Fills ``grads``
+    (field -> gradient); -> the 22 update gradients summed in descending k (zeros for a pass without states)."""
+    with_corr = rec.fmap1 is not None
     inp, d = t['inp'].detach(), grads['hidden']
     d_inp, ug, vol, levels = None, None, None, None
     for k in reversed(range(len(rec.states))):
@@ -590,48 +633,132 @@ def _through_time(rec, t, upd, grads):
     return ug if ug is not None else [torch.zeros_like(p) for p in upd]
 
 
+def _plus(a, b):
+    """a + b of two gradients either of which may be absent."""
+    return b if a is None else a if b is None else a + b
+
+
+def _per_image(contributions):
+    """[(source, gradient (n,C,h8,w8) or None)] in walk order -> (the distinct images [(batch, row)] in the order of first appearance, their
+    gradients as one batch): every image's contributions added in f64 and rounded once (sum_groups), a single one passed through.  An
+    absent gradient contributes nothing, and an image nothing contributed to is left out."""
+    order, terms = [], {}
+    for source, g in contributions:
+        if g is None:
+            continue
+        for i, (im, r) in enumerate(_source_rows(source)):
+            key = (id(im), r)
+            if key not in terms:
+                order.append((im, r))
+                terms[key] = []
+            terms[key].append(g[i:i + 1])
+    if not order:
+        return [], None
+    rows = [terms[id(im), r] for im, r in order]
+    return order, torch.cat([ts[0] if len(ts) == 1 else sum_groups(torch.stack(ts).contiguous()) for ts in rows], dim=0)
+
+
+def _image_batches(order):
+    """[(batch, row)] -> the list of image batches encoder_backward takes: runs of consecutive rows of one batch stay one slice."""
+    runs = []
+    for im, r in order:
+        if runs and runs[-1][0] is im and runs[-1][2] == r:
+            runs[-1][2] = r + 1
+        else:
+            runs.append([im, r, r + 1])
+    return [im if (lo, hi) == (0, im.shape[0]) else im[lo:hi] for im, lo, hi in runs]
+
+
+def _encoders_backward(passes, all_grads, encoders, need):
+    """The encoders behind the last pass of an 'encoders' node: ``all_grads`` = every pass's {field: gradient}; ``need`` = (does a parameter
+    of fnet, of cnet require grad) -> fnet's gradients + cnet's in encoder_params' order, None for an encoder that is not run."""
+    fnet, cnet = encoders
+    out = []
+    walk_f = [(rec.sources[i], g[name]) for rec, g in zip(passes, all_grads) for i, name in ((0, 'fmap1'), (1, 'fmap2'))]
+    walk_c = []
+    for rec, g in zip(passes, all_grads):
+        d0, di = g['net0'], g['inp']
+        if d0 is None and di is None:
+            continue
+        d0, di = (torch.zeros_like(di) if d0 is None else d0), (torch.zeros_like(d0) if di is None else di)
+        walk_c.append((rec.sources[2], torch.cat((d0, di), dim=1)))
+    for enc, walk, split, wanted in ((fnet, walk_f, False, need[0]), (cnet, walk_c, True, need[1])):
+        order, d = _per_image(walk) if wanted else ([], None)
+        n = len(encoder_params(enc))
+        out += [None] * n if d is None else list(encoder_backward(enc, _image_batches(order), d.contiguous(), raw255=True, split_act=split))
+    return out
+
+
 class _RaftGradFn(torch.autograd.Function):
     """Gradient-free RAFT passes as ONE autograd node: inputs the records' tensor fields, pass by pass in field order, then the eight head
-    parameters and, below 'heads', the 22 of UPDATE_PARAMS; outputs the up-sampled flows unchanged.  ``passes`` (the records) stay on the
-    node.  Backward, per pass in the order given: the tail, then the steps (_through_time).  The parameter gradients are summed over the
-    steps in descending k, concatenated (heads | update) per pass, then summed over the passes in the given order; a pass whose flow
-    nothing differentiates is skipped and launches nothing: the sum's bits do not depend on the autograd engine's scheduling."""
+    parameters, below 'heads' the 22 of UPDATE_PARAMS and at 'encoders' encoder_params(fnet) + encoder_params(cnet); outputs the
+    up-sampled flows unchanged and, at 'encoders', behind them every pass's hidden_out and then every pass's context_out.  ``passes`` (the
+    records) stay on the node.  Backward, per pass in the order given: the tail, then the steps (_through_time); at 'encoders' the two
+    encoders once, behind the last pass (_encoders_backward).  The parameter gradients are summed over the steps in descending k,
+    concatenated (heads | update) per pass, then summed over the passes in the given order; a pass none of whose outputs anything
+    differentiates is skipped and launches nothing: the sum's bits do not depend on the autograd engine's scheduling."""
 
     @staticmethod
-    def forward(ctx, passes, *tensors):
-        ctx.passes = passes
+    def forward(ctx, passes, encoders, *tensors):
+        ctx.passes, ctx.encoders = passes, encoders
         ctx.save_for_backward(*tensors)
         ctx.set_materialize_grads(False)
-        return tuple(t['flow_up'].view_as(t['flow_up']) for t in _by_field(passes, tensors)[0])
+        fields = _by_field(passes, tensors)[0]
+        flows = tuple(t['flow_up'].view_as(t['flow_up']) for t in fields)
+        if encoders is None:
+            return flows
+        return flows + tuple(t['hidden'].detach() for t in fields) + tuple(t['inp'].detach() for t in fields)
 
     @staticmethod
-    def backward(ctx, *grads_up):
+    def backward(ctx, *grads_out):
         fields, params = _by_field(ctx.passes, ctx.saved_tensors)
-        heads, upd = params[:8], params[8:]
-        totals, flat = None, []
-        for rec, t, g in zip(ctx.passes, fields, grads_up):
+        heads, upd, n = params[:8], params[8:30], len(ctx.passes)
+        deep = ctx.encoders is not None
+        totals, flat, all_grads = None, [], []
+        for i, (rec, t) in enumerate(zip(ctx.passes, fields)):
+            g, g_hid, g_ctx = grads_out[i], (grads_out[n + i] if deep else None), (grads_out[2 * n + i] if deep else None)
             grads = dict.fromkeys(t)
+            both = None
             if g is not None:
                 grads['hidden'], both = raft_tail_backward(t['hidden'].detach(), t['flow_low'], g.contiguous(), heads[:4], heads[4:])
                 both = list(both)
-                if rec.depth != 'heads':
-                    both += _through_time(rec, t, upd, grads)
-                totals = both if totals is None else [a + b for a, b in zip(totals, both)]
+            if g_hid is not None:                                  # (once, before step N)
+                grads['hidden'] = _plus(grads['hidden'], g_hid)
+            if grads['hidden'] is not None and rec.depth != 'heads':
+                ug = _through_time(rec, t, upd, grads)
+                both = [None] * 8 + ug if both is None else both + ug
+            if g_ctx is not None:                                  # (once, behind the steps' sum)
+                grads['inp'] = _plus(grads['inp'], g_ctx)
+            if both is not None:
+                totals = both if totals is None else [_plus(a, b) for a, b in zip(totals, both)]
             flat += grads.values()
-        return (None, *flat, *(totals if totals is not None else [None] * len(params)))
+            all_grads.append(grads)
+        totals = list(totals) if totals is not None else [None] * 30
+        if deep:
+            need = ctx.needs_input_grad[2 + len(flat) + 30:]
+            n_f = len(encoder_params(ctx.encoders[0]))
+            totals += _encoders_backward(ctx.passes, all_grads, ctx.encoders, (any(need[:n_f]), any(need[n_f:])))
+        return (None, None, *flat, *totals[:len(params)])
 
 
-def attach(passes, head_params, update_params=None):
+def attach(passes, head_params, update_params=None, encoders=None):
     """Attach the backward to the results of gradient-free RAFT passes: ``passes`` = GradPass records of ONE depth whose ``hidden`` -- and,
     below 'heads', ``net0``, ``inp``, ``fmap1``, ``fmap2`` -- are leaves that require grad (GradPass.rows); ``head_params`` = RAFT.head_params(),
-    ``update_params`` = RAFT.update_params() (needed below 'heads') -> the list of up-sampled flows (the same values), outputs of one
-    _RaftGradFn node.  After a backward the leaves' and the parameters' .grad are what the module docstring says of the passes' depth."""
+    ``update_params`` = RAFT.update_params() (needed below 'heads'), ``encoders`` = (fnet, cnet), the modules (needed at 'encoders', refused
+    at every other depth) -> the list of up-sampled flows (the same values), outputs of one _RaftGradFn node; at 'encoders' the list of
+    every pass's (flow, hidden_out, context_out).  After a backward the leaves' and the parameters' .grad are what the module docstring
+    says of the passes' depth."""
     depth = {p.depth for p in passes}
     if len(depth) != 1:
         raise _lib.RpeError(f'raft_grad.attach: every pass must carry the same stages, got {sorted(depth)}')
     if (update_params is None) != (depth == {'heads'}):
-        raise _lib.RpeError("raft_grad.attach: update_params goes with passes of depth 'update' or 'corr', and only with them")
+        raise _lib.RpeError("raft_grad.attach: update_params goes with passes of depth 'update', 'corr' or 'encoders', and only with them")
+    if (encoders is None) != (depth != {'encoders'}):
+        raise _lib.RpeError("raft_grad.attach: encoders = (fnet, cnet) goes with passes of depth 'encoders', and only with them")
     fh, mk = head_params
     flat = [t for p in passes for t in p.tensors().values()]
+    enc_params = [] if encoders is None else encoder_params(encoders[0]) + encoder_params(encoders[1])
     with torch.enable_grad():
-        return list(_RaftGradFn.apply(list(passes), *flat, *fh, *mk, *(update_params or ())))
+        outs = list(_RaftGradFn.apply(list(passes), None if encoders is None else tuple(encoders), *flat, *fh, *mk, *(update_params or ()), *enc_params))
+    n = len(passes)
+    return outs if encoders is None else [(outs[i], outs[n + i], outs[2 * n + i]) for i in range(n)]
