@@ -77,6 +77,8 @@ const char *rpe_version(void);
  *   rpe_corr_build_backward;
  *   and the backward of the encoders: rpe_conv_s2_bwd_weight, rpe_conv_s2_bwd_weight_workspace_bytes, rpe_conv_s2_bwd_data,
  *   rpe_bn_frozen_backward, rpe_bn_frozen_backward_workspace_bytes, rpe_instnorm_backward, rpe_split_act_backward;
+ *   and the training step's update: rpe_optim_chunk_floats, rpe_optim_chunk_offsets, rpe_optim_workspace_bytes, rpe_grad_norm,
+ *   rpe_adamw_step (structs rpe_optim_row, rpe_optim_chunk, rpe_optim_record);
  *   the next RPE_ABI_MINOR bump counts them and rpe_conv_wino24*. */
 #define RPE_ABI_VERSION 5
 #define RPE_ABI_MINOR 4
@@ -1177,6 +1179,42 @@ int rpe_surfel_fuse_many(int nmaps, const rpe_surfel_map *src, const int64_t *n_
                          const int32_t *rows, int batch, const float *depth, const float *img, const uint8_t *mask, int h, int w,
                          const float *const *kmat, const float *const *kinv, const float *pose, float d_thresh, int average_pts, int upscale,
                          float conf_thr, int t_max, void *workspace, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * The training step's update (csrc/optim.hip): the global gradient norm and a clipped AdamW step over ANY number of float32 tensors,
+ * one launch each -- what torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW.step (amsgrad = False, maximize = False) do in a chain of
+ * per-tensor-list launches and, behind a GradScaler, one host synchronisation.  Neither call synchronises the host.
+ *
+ * table: DEVICE array of n_rows rpe_optim_row, one per tensor (any numel >= 1, < 2^31; the four pointers 4-byte aligned, nothing more).
+ * chunks: DEVICE array of n_chunks rpe_optim_chunk, the tensors cut into pieces of RPE_OPTIM_CHUNK elements in table order -- exactly what
+ *   rpe_optim_chunk_offsets writes (into HOST memory: the caller uploads it beside the table).  It returns the number of chunks (with
+ *   out = NULL: only that), RPE_E_BADARG for a numel < 1, a negative n_rows or cap < the count, RPE_E_UNSUPPORTED for a numel >= 2^31: this
+ *   is where sizes are checked, since the calls below see device memory only.  The split is a function of the sizes alone.
+ * workspace: rpe_optim_workspace_bytes(n_chunks) bytes, 16-byte aligned, ZEROED ONCE by the caller before its first use (the two tickets in
+ *   its head are counted back to zero by every launch); not shared between streams.
+ * rpe_grad_norm: record <- {sqrt(sum of squares of every gradient element) in f64, the same rounded to f32, the number of non-finite
+ *   gradient elements}.  One f64 partial per chunk (products of floats are exact in f64), the partials added in index order in f64 by
+ *   the launch's last workgroup: no float atomics, the same bits on every run.
+ * rpe_adamw_step: reads the record on the device.  skip_nonfinite != 0 and record->nonfinite != 0: nothing is written but state[1]
+ *   (skipped steps) += 1.  Otherwise state[0] (the step counter t) += 1 and per element, in f32 with the scalars evaluated in f64,
+ *     g' = c g, c = min(1, max_norm / (norm + 1e-6)) (max_norm <= 0: c = 1);   p *= 1 - lr weight_decay;
+ *     m += (1 - beta1)(g' - m);   v = beta2 v + (1 - beta2) g' g';   p -= (lr / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 - beta2^t) + eps).
+ *   The gradients are only read.  state: DEVICE long long[2], zero at first.
+ * n_rows == 0 (or n_chunks == 0): RPE_OK, nothing launched.  NULL table / chunks / workspace / record / state, negative counts, n_chunks <
+ * n_rows: RPE_E_BADARG.
+ * --------------------------------------------------------------------------------------------------------- */
+#define RPE_OPTIM_CHUNK 4096
+typedef struct rpe_optim_row { float *param; const float *grad; float *exp_avg; float *exp_avg_sq; long long numel; } rpe_optim_row;
+typedef struct rpe_optim_chunk { int row; int offset; } rpe_optim_chunk;          /* elements [offset, offset + RPE_OPTIM_CHUNK) of tensor `row` */
+typedef struct rpe_optim_record { double norm; float norm_f32; int reserved; long long nonfinite; long long reserved2; } rpe_optim_record;
+size_t rpe_optim_chunk_floats(void);                                              /* RPE_OPTIM_CHUNK of the loaded library */
+int rpe_optim_chunk_offsets(const long long *numel, int n_rows, rpe_optim_chunk *out, int cap);
+size_t rpe_optim_workspace_bytes(int n_chunks);
+int rpe_grad_norm(const rpe_optim_row *table, int n_rows, const rpe_optim_chunk *chunks, int n_chunks, void *workspace,
+                  rpe_optim_record *record, void *stream);
+int rpe_adamw_step(const rpe_optim_row *table, int n_rows, const rpe_optim_chunk *chunks, int n_chunks, void *workspace,
+                   const rpe_optim_record *record, long long *state, double lr, double beta1, double beta2, double eps, double weight_decay,
+                   double max_norm, int skip_nonfinite, void *stream);
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,8 @@ Layout:
   raft.py, unet.py    RAFT / TinyUNet host mirrors (convolutions on PyTorch-ROCm, correlation / gates /
                       up-sampling in HIP)
   raft_grad.py        RAFT's training backward: the stage functions, a pass's record (GradPass) and the one autograd node over them
-  pose_head.py        DPoseSE3Head / DeclarativeLayerLie mirrors on rpe_pose_solve
+  optim.py, train.py  ClippedAdamW (clip + AdamW as two launches of csrc/optim.hip) and the reference's training script as a module
+  pose_head.py       DPoseSE3Head / DeclarativeLayerLie mirrors on rpe_pose_solve
   pose_net.py         PoseNet.infer / flow2depth mirror
   pose_estimator.py   frame-to-frame tracker mirror (+ Frame), SurfelPoseEstimator (frame to model), MultiSurfelPoseEstimator (K sequences), from_config
   surfel_map.py       SurfelMap mirror on the rpe_surfel_* kernels

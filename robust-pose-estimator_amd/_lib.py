@@ -207,6 +207,16 @@ class SurfelMapDesc(_c.Structure):
     _fields_ = [('opts', _vp), ('rgb', _vp), ('conf', _vp), ('t_created', _vp), ('cap', _i64), ('count', _vp), ('overflow', _vp)]
 
 
+class OptimRow(_c.Structure):
+    """struct rpe_optim_row (include/rpe.h): one tensor of the training step's update."""
+    _fields_ = [('param', _vp), ('grad', _vp), ('exp_avg', _vp), ('exp_avg_sq', _vp), ('numel', _ll)]
+
+
+class OptimChunk(_c.Structure):
+    """struct rpe_optim_chunk (include/rpe.h)."""
+    _fields_ = [('row', _i), ('offset', _i)]
+
+
 _SMP = _c.POINTER(SurfelMapDesc)
 _P64, _P32, _PVP = _c.POINTER(_i64), _c.POINTER(_c.c_int32), _c.POINTER(_vp)
 
@@ -260,6 +270,11 @@ SIGNATURES = {
     'rpe_bn_frozen_backward': (_i, [_vp, _ll, _vp, _ll, _vp, _vp, _vp, _vp, _d, _i, _i, _i, _vp, _vp, _vp, _vp, _ll, _vp, _vp]),
     'rpe_instnorm_backward': (_i, [_vp, _ll, _vp, _ll, _i, _i, _i, _d, _vp, _ll, _vp]),
     'rpe_split_act_backward': (_i, [_vp, _ll, _vp, _ll, _i, _i, _i, _i, _vp, _ll, _vp]),
+    'rpe_optim_chunk_floats': (_sz, []),
+    'rpe_optim_chunk_offsets': (_i, [_c.POINTER(_ll), _i, _c.POINTER(OptimChunk), _i]),
+    'rpe_optim_workspace_bytes': (_sz, [_i]),
+    'rpe_grad_norm': (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp]),
+    'rpe_adamw_step': (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _d, _d, _d, _d, _d, _d, _i, _vp]),
     'rpe_flow_forward_interpolate': (_i, [_vp, _i, _i, _i, _vp, _vp]),
     'rpe_corr_pyramid_bytes': (_sz, [_i, _i, _i, _i]),
     'rpe_corr_pyramid_bytes_ex': (_sz, [_i, _i, _i, _i, _i]),

@@ -1791,3 +1791,109 @@ def split_act_backward(grad, act, half, out=None):
         raise _lib.RpeError('split_act_backward: grad, act and out must have one shape, and 0 <= half <= channels')
     check(lib().rpe_split_act_backward(gp, gbs, ap, abs_, b, c, half, hh * ww, op, obs, stream_ptr()), 'rpe_split_act_backward')
     return out
+
+
+# ------------------------------------------------------------------------------------------------ the training step's update (csrc/optim.hip)
+def optim_chunk():
+    """RPE_OPTIM_CHUNK of the loaded library: the elements of one chunk (one workgroup) of rpe_grad_norm / rpe_adamw_step."""
+    return int(lib().rpe_optim_chunk_floats())
+
+
+def optim_chunk_offsets(numels):
+    """rpe_optim_chunk_offsets: the chunk list of tensors of ``numels`` elements as a ctypes array of _lib.OptimChunk (host memory); sizes
+    below 1 or from 2^31 on are refused there."""
+    n = len(numels)
+    sizes = (ctypes.c_longlong * max(1, n))(*numels)
+    count = lib().rpe_optim_chunk_offsets(sizes, n, None, 0)
+    if count < 0:
+        check(count, 'rpe_optim_chunk_offsets')
+    out = (_lib.OptimChunk * max(1, count))()
+    check(min(0, lib().rpe_optim_chunk_offsets(sizes, n, out, count)), 'rpe_optim_chunk_offsets')
+    return out, count
+
+
+class OptimTable:
+    """The device-resident table and chunk list of rpe_grad_norm / rpe_adamw_step with their workspace.  ``set(rows)`` takes the step's
+    (param, grad, exp_avg, exp_avg_sq) tensors -- float32, contiguous, on the current device -- and uploads table and chunk list only when a
+    pointer or a size differs from what the device holds: from a pinned staging buffer of its own per upload, asynchronously on the current
+    stream (torch's pinned allocator keeps a staging buffer from being handed out again before its copy has run, so the host never waits
+    and never rewrites bytes in flight).  One table serves one stream."""
+
+    def __init__(self):
+        self.key, self.n_rows, self.n_chunks, self.numels = None, 0, 0, None
+        self.buf = self.workspace = None
+        self.chunks_at = 0
+        self._host_chunks = None
+        self.uploads = 0
+
+    def set(self, rows):
+        key = tuple((p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()) for p, g, m, v in rows)
+        if key == self.key:
+            return self
+        for p, g, m, v in rows:
+            for t in (g, m, v):
+                if not (_is_f32(t) and t.numel() == p.numel()):
+                    raise _lib.RpeError('OptimTable: gradients and moments must be contiguous float32 GPU tensors of their parameter\'s size')
+            if not _is_f32(p):
+                raise _lib.RpeError('OptimTable: parameters must be contiguous float32 GPU tensors')
+            _on_current_device(p, 'OptimTable: parameter')
+        numels = tuple(k[4] for k in key)
+        if numels != self.numels:
+            self._host_chunks, self.n_chunks = optim_chunk_offsets(numels)
+            self.numels = numels
+        n = len(rows)
+        table = (_lib.OptimRow * max(1, n))(*[_lib.OptimRow(*k) for k in key])
+        row_bytes, chunk_bytes = n * ctypes.sizeof(_lib.OptimRow), self.n_chunks * ctypes.sizeof(_lib.OptimChunk)
+        self.chunks_at = (row_bytes + 15) // 16 * 16
+        total = self.chunks_at + chunk_bytes
+        if n:
+            device = rows[0][0].device
+            host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+            ctypes.memmove(host.data_ptr(), table, row_bytes)
+            ctypes.memmove(host.data_ptr() + self.chunks_at, self._host_chunks, chunk_bytes)
+            if self.buf is None or self.buf.numel() < total or self.buf.device != device:
+                self.buf = torch.empty(total, dtype=torch.uint8, device=device)
+            self.buf[:total].copy_(host, non_blocking=True)
+            need = int(lib().rpe_optim_workspace_bytes(self.n_chunks))
+            if self.workspace is None or self.workspace.numel() < need or self.workspace.device != device:
+                self.workspace = torch.zeros(need, dtype=torch.uint8, device=device)      # (the tickets start at zero; the kernels count them back)
+            self.uploads += 1
+        self.key, self.n_rows = key, n
+        return self
+
+    def _args(self):
+        return (ctypes.c_void_p(self.buf.data_ptr()), self.n_rows, ctypes.c_void_p(self.buf.data_ptr() + self.chunks_at), self.n_chunks,
+                ptr(self.workspace))
+
+
+def optim_record(device):
+    """A zeroed struct rpe_optim_record as a (4,) float64 tensor: [0] is the norm; optim_record_fields names the rest."""
+    return torch.zeros(4, dtype=torch.float64, device=device)
+
+
+def optim_record_fields(record):
+    """Views of a record: norm (1,) f64, norm_f32 (1,) f32, nonfinite (1,) int64."""
+    return dict(norm=record[0:1], norm_f32=record.view(torch.float32)[2:3], nonfinite=record.view(torch.int64)[2:3])
+
+
+def grad_norm(table, record):
+    """rpe_grad_norm over an OptimTable: ``record`` (optim_record) <- the global L2 norm of the gradients (f64, f32) and the count of
+    non-finite elements.  One launch, none for an empty table; no host synchronisation."""
+    if table.n_rows == 0:
+        return record
+    if not (record.is_cuda and record.dtype == torch.float64 and record.numel() == 4 and record.is_contiguous()):
+        raise _lib.RpeError('grad_norm: record must be ops.optim_record(device)')
+    check(lib().rpe_grad_norm(*table._args(), ptr(record), stream_ptr()), 'rpe_grad_norm')
+    return record
+
+
+def adamw_step(table, record, state, lr, beta1, beta2, eps, weight_decay, max_norm=None, skip_nonfinite=True):
+    """rpe_adamw_step over an OptimTable, behind grad_norm on the same stream: the clipped AdamW update of every row, or -- with a non-finite
+    gradient and ``skip_nonfinite`` -- no write but ``state[1] += 1``.  ``state``: (2,) int64 on the device, [step counter, skipped steps].
+    ``max_norm`` None or <= 0: no clipping.  One launch, none for an empty table; no host synchronisation."""
+    if table.n_rows == 0:
+        return
+    if not (state.is_cuda and state.dtype == torch.int64 and state.numel() == 2 and state.is_contiguous()):
+        raise _lib.RpeError('adamw_step: state must be a (2,) int64 GPU tensor')
+    check(lib().rpe_adamw_step(*table._args(), ptr(record), ptr(state), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
+                               float(max_norm) if max_norm is not None else 0.0, int(bool(skip_nonfinite)), stream_ptr()), 'rpe_adamw_step')

@@ -91,6 +91,56 @@ def ground_truth_flows(seed, n, h, w, bf=7.2, occluders=3):
     return torch.stack(tf).contiguous(), torch.stack(sf).contiguous()
 
 
+def _se3_exp(xi):
+    """(R (3,3), t (3,), [t | quaternion xyzw] (7,)) of exp(xi), xi = [tau, phi], in float64 (closed form; the host's ground truth)."""
+    tau, phi = np.asarray(xi[:3], dtype=np.float64), np.asarray(xi[3:], dtype=np.float64)
+    th = float(np.linalg.norm(phi))
+    Kx = np.array([[0.0, -phi[2], phi[1]], [phi[2], 0.0, -phi[0]], [-phi[1], phi[0], 0.0]])
+    if th < 1e-8:
+        a, b, c = 1.0 - th * th / 6.0, 0.5 - th * th / 24.0, 1.0 / 6.0 - th * th / 120.0
+    else:
+        a, b, c = np.sin(th) / th, (1.0 - np.cos(th)) / (th * th), (th - np.sin(th)) / (th ** 3)
+    R = np.eye(3) + a * Kx + b * Kx @ Kx
+    t = (np.eye(3) + b * Kx + c * Kx @ Kx) @ tau
+    half = 0.5 * th
+    q = np.concatenate(((0.5 - th * th / 48.0 if th < 1e-8 else np.sin(half) / th) * phi, [np.cos(half)]))
+    return R, t, np.concatenate((t, q))
+
+
+def training_pairs(seed, count, h, w, bf=7.2, batch=1):
+    """``count`` training batches in the reference's format (dataset/train_datasets.py as scripts/train_posenet.py:99-101 unpacks it):
+    tuples (ref_img, trg_img, ref_img_r, trg_img_r, ref_mask, trg_mask, gt_pose, intrinsics, baseline) of CPU tensors with ``batch`` rows
+    -- images (b,3,h,w) 0..255, masks (b,1,h,w) bool, gt_pose (b,7) [t | quaternion], intrinsics (b,3,3), baseline (b,).  A rigid scene
+    in front of a moving stereo camera, rendered like ``stereo_frames`` but with the EXACT rigid motion X' = R X + t of exp(xi), so gt_pose
+    = exp(xi) is the ground truth of the flow the target image was warped with: the model sees trg as image 1 and ref as image 2, and
+    gt_pose moves points of the target camera into the reference camera.  Seeded; tests and benches need no dataset."""
+    rng = np.random.default_rng(seed)
+    K = intrinsics(h, w)
+    ys, xs = torch.meshgrid(torch.arange(h, dtype=torch.float32) + 0.5, torch.arange(w, dtype=torch.float32) + 0.5, indexing='ij')
+    for _ in range(count):
+        rows = []
+        for _ in range(batch):
+            depth = 0.2 + 0.7 * _smooth(rng, 1, h, w, 5)[0]
+            tex = 255.0 * (0.6 * _smooth(rng, 3, h, w, 24) + 0.4 * _smooth(rng, 3, h, w, 96))
+            xi = np.concatenate((rng.normal(0, 0.005, 3), rng.normal(0, 0.01, 3)))
+            R, t, pose = _se3_exp(xi)
+            X = torch.stack(((xs - K[0, 2]) / K[0, 0] * depth, (ys - K[1, 2]) / K[1, 1] * depth, depth))
+            Xp = torch.einsum('ij,jhw->ihw', torch.from_numpy(R).float(), X) + torch.from_numpy(t).float()[:, None, None]
+            fx, fy = K[0, 0] * Xp[0] / Xp[2] + K[0, 2] - xs, K[1, 1] * Xp[1] / Xp[2] + K[1, 2] - ys
+            disp = (bf / depth)[None]
+            trg = tex[None]
+            ref = _warp(trg, -fx[None], -fy[None])
+            trg_r, ref_r = _warp(trg, disp, torch.zeros_like(disp)), _warp(ref, disp, torch.zeros_like(disp))
+            masks = []
+            for _ in range(2):
+                m = torch.ones(1, h, w, dtype=torch.bool)
+                y0, x0 = int(rng.integers(0, h - h // 5)), int(rng.integers(0, w - w // 4))
+                m[:, y0:y0 + h // 5, x0:x0 + w // 4] = False
+                masks.append(m)
+            rows.append((ref[0], trg[0], ref_r[0], trg_r[0], masks[0], masks[1], torch.from_numpy(pose).float(), K, torch.tensor(bf, dtype=torch.float32)))
+        yield tuple(torch.stack(col).contiguous() for col in zip(*rows))
+
+
 def infer_args(s):
     return dict(image1l=s['image1l'], image2l=s['image2l'], intrinsics=s['K'], baseline=s['baseline'], depth1=s['depth1'],
                 image2r=s['image2r'], mask1=s['mask1'], mask2=s['mask2'], stereo_flow1=s['stereo_flow1'])
