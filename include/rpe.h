@@ -79,6 +79,8 @@ const char *rpe_version(void);
  *   rpe_bn_frozen_backward, rpe_bn_frozen_backward_workspace_bytes, rpe_instnorm_backward, rpe_split_act_backward;
  *   and the training step's update: rpe_optim_chunk_floats, rpe_optim_chunk_offsets, rpe_optim_workspace_bytes, rpe_grad_norm,
  *   rpe_adamw_step (structs rpe_optim_row, rpe_optim_chunk, rpe_optim_record);
+ *   and RAFT's sequence loss on ground-truth flow: rpe_flow_sequence_loss_workspace_bytes, rpe_flow_sequence_loss,
+ *   rpe_flow_sequence_loss_backward;
  *   the next RPE_ABI_MINOR bump counts them and rpe_conv_wino24*. */
 #define RPE_ABI_VERSION 5
 #define RPE_ABI_MINOR 4
@@ -1215,6 +1217,43 @@ int rpe_grad_norm(const rpe_optim_row *table, int n_rows, const rpe_optim_chunk 
 int rpe_adamw_step(const rpe_optim_row *table, int n_rows, const rpe_optim_chunk *chunks, int n_chunks, void *workspace,
                    const rpe_optim_record *record, long long *state, double lr, double beta1, double beta2, double eps, double weight_decay,
                    double max_norm, int skip_nonfinite, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * RAFT's sequence loss on ground-truth flow and its gradient (csrc/flow_loss.hip): what trains the flow network as RAFT itself is trained.
+ *     mask   = valid & !(|gt| >= max_flow)             |gt| = the per-pixel Euclidean norm, formed in f64
+ *     term_k = (1 / M) sum_{b,c,y,x} mask |pred_k - gt|,   M = b 2 h w: the mean runs over ALL elements, not over the valid ones
+ *     loss   = sum_k weights[k] term_k,  k = 0 .. n_preds - 1   (RAFT: weights[k] = gamma^(n_preds - 1 - k), computed by the caller)
+ *   and, on the LAST prediction over the mask pixels, the mean end-point error and the fractions with an error below 1, 3 and 5 px.
+ * One deliberate departure from upstream RAFT: a masked pixel contributes EXACTLY ZERO to the loss and to the gradient, whatever pred
+ * and gt hold there, NaN and inf included (upstream's valid * i_loss makes 0 * NaN = NaN of such a pixel).  A NaN in gt under a valid
+ * pixel is not masked (it fails |gt| >= max_flow): loss and that pixel's gradient are NaN, and rpe_adamw_step's non-finite test skips.
+ *
+ * preds: DEVICE array of n_preds pointers (1 <= n_preds <= 1024), each a contiguous f32 (b,2,h,w) tensor; gt f32 (b,2,h,w); valid uint8
+ * (b,h,w), non-zero = valid; weights: DEVICE array of n_preds doubles; any h and w; pointers need the alignment of their element only.
+ * rpe_flow_sequence_loss: two launches, no host synchronisation.  The first reads gt and valid once per pixel and every prediction
+ *   once, forms differences and magnitudes in f64 and writes one f64 partial per quantity and workgroup (RPE_FLOW_LOSS_TILE pixels each)
+ *   into workspace (rpe_flow_sequence_loss_workspace_bytes, 8-byte aligned, no initial state); the second adds the partials in workgroup
+ *   order: no float atomics, the same bits on every run.  record: DEVICE double[RPE_FLOW_LOSS_TERMS + n_preds] -- [RPE_FLOW_LOSS_LOSS]
+ *   the loss, [_EPE], [_1PX], [_3PX], [_5PX] the metrics (NaN when no pixel is in the mask), [_COUNT] the number of mask pixels as a
+ *   long long in that slot, [_TERMS + k] = term_k (unweighted); loss_f32: the loss rounded to f32.
+ * rpe_flow_sequence_loss_backward: one launch; g: DEVICE float, d L / d loss.  grads: DEVICE array of n_preds pointers to f32 (b,2,h,w)
+ *   buffers, every element of which is written:  grads[k] = float32(weights[k] g / M) sign(pred_k - gt)  on mask pixels (NaN where the
+ *   difference is NaN), exact 0 on masked pixels and where pred_k == gt.  The mask is formed again: nothing but the inputs is kept.
+ * NULL pointers, n_preds < 1, b, h or w < 1, max_flow not > 0: RPE_E_BADARG; n_preds > 1024 or h w >= 2^30: RPE_E_UNSUPPORTED.
+ * --------------------------------------------------------------------------------------------------------- */
+#define RPE_FLOW_LOSS_TILE 1024
+#define RPE_FLOW_LOSS_LOSS 0
+#define RPE_FLOW_LOSS_EPE 1
+#define RPE_FLOW_LOSS_1PX 2
+#define RPE_FLOW_LOSS_3PX 3
+#define RPE_FLOW_LOSS_5PX 4
+#define RPE_FLOW_LOSS_COUNT 5
+#define RPE_FLOW_LOSS_TERMS 6
+size_t rpe_flow_sequence_loss_workspace_bytes(int n_preds, int b, int h, int w);
+int rpe_flow_sequence_loss(const float *const *preds, int n_preds, const float *gt, const uint8_t *valid, const double *weights, int b, int h,
+                           int w, double max_flow, void *workspace, double *record, float *loss_f32, void *stream);
+int rpe_flow_sequence_loss_backward(const float *const *preds, int n_preds, const float *gt, const uint8_t *valid, const double *weights,
+                                    const float *g, int b, int h, int w, double max_flow, float *const *grads, void *stream);
 
 #ifdef __cplusplus
 }

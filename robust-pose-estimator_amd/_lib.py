@@ -275,6 +275,9 @@ SIGNATURES = {
     'rpe_optim_workspace_bytes': (_sz, [_i]),
     'rpe_grad_norm': (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp]),
     'rpe_adamw_step': (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _d, _d, _d, _d, _d, _d, _i, _vp]),
+    'rpe_flow_sequence_loss_workspace_bytes': (_sz, [_i, _i, _i, _i]),
+    'rpe_flow_sequence_loss': (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _d, _vp, _vp, _vp, _vp]),
+    'rpe_flow_sequence_loss_backward': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _d, _vp, _vp]),
     'rpe_flow_forward_interpolate': (_i, [_vp, _i, _i, _i, _vp, _vp]),
     'rpe_corr_pyramid_bytes': (_sz, [_i, _i, _i, _i]),
     'rpe_corr_pyramid_bytes_ex': (_sz, [_i, _i, _i, _i, _i]),

@@ -1897,3 +1897,98 @@ def adamw_step(table, record, state, lr, beta1, beta2, eps, weight_decay, max_no
         raise _lib.RpeError('adamw_step: state must be a (2,) int64 GPU tensor')
     check(lib().rpe_adamw_step(*table._args(), ptr(record), ptr(state), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
                                float(max_norm) if max_norm is not None else 0.0, int(bool(skip_nonfinite)), stream_ptr()), 'rpe_adamw_step')
+
+
+# ------------------------------------------------------------------------------------------------- RAFT's sequence loss
+FLOW_LOSS_FIELDS = dict(loss=0, epe=1, px1=2, px3=3, px5=4, count=5)       # RPE_FLOW_LOSS_* of include/rpe.h; the N terms follow at 6
+
+
+def _flow_loss_check(flow_preds, flow_gt, valid, gamma, max_flow):
+    """Every refusal of flow_sequence_loss, before any launch (shapes and types first, so they are raised without a GPU too) -> (the
+    predictions, gt contiguous, valid as a contiguous uint8 (b,H,W))."""
+    who = 'flow_sequence_loss'
+    if not isinstance(flow_preds, (list, tuple)) or len(flow_preds) == 0:
+        raise _lib.RpeError(f'{who}: flow_preds must be a non-empty list of (b,2,H,W) predictions')
+    preds = list(flow_preds)
+    if not isinstance(flow_gt, torch.Tensor) or flow_gt.dim() != 4 or flow_gt.shape[1] != 2 or flow_gt.dtype != torch.float32:
+        raise _lib.RpeError(f'{who}: flow_gt must be a float32 (b,2,H,W) tensor')
+    b, _, hh, ww = flow_gt.shape
+    for k, p in enumerate(preds):
+        if not isinstance(p, torch.Tensor) or p.dtype != torch.float32:
+            raise _lib.RpeError(f'{who}: prediction {k} must be a float32 tensor')
+        if tuple(p.shape) != (b, 2, hh, ww):
+            raise _lib.RpeError(f'{who}: prediction {k} has shape {tuple(p.shape)}, flow_gt {tuple(flow_gt.shape)}')
+        if not p.is_contiguous():
+            raise _lib.RpeError(f'{who}: prediction {k} must be contiguous (the kernel reads it where it lies)')
+    if not isinstance(valid, torch.Tensor) or valid.dtype not in (torch.bool, torch.uint8) or tuple(valid.shape) not in ((b, hh, ww), (b, 1, hh, ww)):
+        raise _lib.RpeError(f'{who}: valid must be a bool or uint8 ({b},{hh},{ww}) or ({b},1,{hh},{ww}) tensor')
+    if not (0.0 < float(gamma) and float(max_flow) > 0.0):
+        raise _lib.RpeError(f'{who}: gamma and max_flow must be positive, got {gamma} and {max_flow}')
+    for name, t in [(f'prediction {k}', p) for k, p in enumerate(preds)] + [('flow_gt', flow_gt), ('valid', valid)]:
+        if not t.is_cuda:
+            raise _lib.RpeError(f'{who}: {name}: expected a tensor on the GPU (the HIP path has no CPU fallback)')
+        _on_current_device(t, f'{who}: {name}')
+    v = valid.reshape(b, hh, ww).contiguous()
+    return preds, flow_gt.contiguous(), v.view(torch.uint8) if v.dtype == torch.bool else v
+
+
+def _device_table(pointers, device):
+    """Device pointers as a device int64 tensor, uploaded from pinned memory on the current stream without a host synchronisation
+    (OptimTable's way)."""
+    return torch.tensor(pointers, dtype=torch.int64).pin_memory().to(device, non_blocking=True)
+
+
+class _FlowSequenceLossFn(torch.autograd.Function):
+    """(gt, valid, weights table, max_flow, the N predictions) -> (loss 0-d f32, the record); the record is not differentiable."""
+
+    @staticmethod
+    def forward(ctx, gt, valid, weights, max_flow, *preds):
+        n, (b, _, hh, ww), dev = len(preds), gt.shape, gt.device
+        table = _device_table([p.data_ptr() for p in preds], dev)
+        ws = torch.empty(int(lib().rpe_flow_sequence_loss_workspace_bytes(n, b, hh, ww)) // 8, dtype=torch.float64, device=dev)
+        record = torch.empty(FLOW_LOSS_FIELDS['count'] + 1 + n, dtype=torch.float64, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        check(lib().rpe_flow_sequence_loss(ptr(table), n, ptr(gt), ptr(valid), ptr(weights), b, hh, ww, float(max_flow), ptr(ws), ptr(record),
+                                           ptr(loss), stream_ptr()), 'rpe_flow_sequence_loss')
+        ctx.save_for_backward(gt, valid, weights, table, *preds)
+        ctx.max_flow = float(max_flow)
+        ctx.mark_non_differentiable(record)
+        return loss, record
+
+    @staticmethod
+    def backward(ctx, g, _g_record):
+        gt, valid, weights, table, *preds = ctx.saved_tensors
+        n, (b, _, hh, ww) = len(preds), gt.shape
+        g = _f32(g.contiguous(), 'flow_sequence_loss: the gradient of the loss', numel=1)
+        grads = [torch.empty_like(p) for p in preds]
+        out = _device_table([t.data_ptr() for t in grads], gt.device)
+        check(lib().rpe_flow_sequence_loss_backward(ptr(table), n, ptr(gt), ptr(valid), ptr(weights), ptr(g), b, hh, ww, ctx.max_flow, ptr(out),
+                                                    stream_ptr()), 'rpe_flow_sequence_loss_backward')
+        return (None, None, None, None, *grads)
+
+
+def flow_sequence_loss(flow_preds, flow_gt, valid, gamma=0.8, max_flow=400.0):
+    """RAFT's sequence loss on ground-truth flow (csrc/flow_loss.hip), from its published definition:
+        mask = valid & (|flow_gt| < max_flow), |.| the per-pixel Euclidean norm;   w_k = gamma^(N-1-k), k = 0 .. N-1;
+        loss = sum_k w_k (1/M) sum_{b,c,y,x} mask |pred_k - flow_gt|,   M = b 2 H W: the mean runs over all elements, not the valid ones.
+    flow_preds: the N predictions, each a contiguous f32 (b,2,H,W) GPU tensor (RAFT.forward(all_flows=True, grad_all_flows=True) returns
+    such a list); flow_gt f32 (b,2,H,W); valid bool or uint8 (b,H,W) or (b,1,H,W).
+    -> (loss, metrics): ``loss`` a 0-d f32 tensor, the output of one autograd node over the N predictions, whose backward writes
+    d pred_k = float32(w_k g / M) sign(pred_k - flow_gt) on mask pixels and exact 0 on masked pixels and where pred_k == flow_gt, in one
+    launch from a g read on the device; ``metrics`` a dict of device tensors without gradient: 'epe', '1px', '3px', '5px' (the last
+    prediction's mean end-point error over mask pixels and the fractions below 1, 3, 5 px; NaN when the mask is empty), 'count' (mask
+    pixels, int64), 'loss_f64', 'terms' ((N,) f64, the unweighted per-iteration means).  Differences and sums in f64, partials per
+    workgroup added in a fixed order: bit-identical from run to run.  Two launches forward, one backward, no host synchronisation.
+    One deliberate departure from upstream RAFT: a masked pixel contributes EXACTLY ZERO to the loss and to the gradient, whatever the
+    prediction or flow_gt hold there, NaN and inf included (upstream's ``valid * i_loss`` gives NaN).  A NaN in flow_gt under a valid pixel
+    is not masked: it makes the loss and that pixel's gradient NaN, which optim.ClippedAdamW answers by skipping the step.
+    Refused before any launch: an empty list, predictions that are not f32, not contiguous or not of flow_gt's shape, a ``valid`` of
+    another shape or type."""
+    preds, gt, v = _flow_loss_check(flow_preds, flow_gt, valid, gamma, max_flow)
+    n = len(preds)
+    weights = torch.tensor([float(gamma) ** (n - 1 - k) for k in range(n)], dtype=torch.float64).pin_memory().to(gt.device, non_blocking=True)
+    loss, record = _FlowSequenceLossFn.apply(gt, v, weights, float(max_flow), *preds)
+    F = FLOW_LOSS_FIELDS
+    metrics = {'epe': record[F['epe']], '1px': record[F['px1']], '3px': record[F['px3']], '5px': record[F['px5']],
+               'count': record.view(torch.int64)[F['count']], 'loss_f64': record[F['loss']], 'terms': record[F['count'] + 1:]}
+    return loss, metrics

@@ -1196,26 +1196,35 @@ class RAFT(nn.Module):
         states.append((st, ops.copy_planes(co, torch.empty_like(co))))
 
     @torch.no_grad()
-    def grad_pass(self, fmaps, cnet, *, stages, sources=None, **kw):
+    def grad_pass(self, fmaps, cnet, *, stages, sources=None, grad_all_flows=False, **kw):
         """One gradient-free ``ret_lowres`` pass on given encoder outputs (``kw``: upsample, iters, all_flows, flow_init), run so that
         raft_grad can differentiate it as far as ``stages`` -- 'heads', 'update', 'corr' or 'encoders' (raft_grad's module docstring) ->
         (forward's result with the 1/8 flow as its 4th element, the raft_grad.GradPass of the whole batch; GradPass.rows makes its
         leaves).  ``sources`` (with 'encoders', and only then): where fmaps[0], fmaps[1] and cnet came from, an (images, lo, hi) each --
         one raw 0..255 image batch, or a tuple of batches that were encoded as one, and the rows of it.  The refusals are raised before
         any launch.  Below 'heads' the pass runs iteration by iteration and saves every iteration's entry state, and its pyramid is the
-        record's from here on, no longer the model's."""
+        record's from here on, no longer the model's.  ``grad_all_flows`` (needs all_flows=True): the record also carries the N - 1 earlier
+        up-sampled predictions, which the node then differentiates too (raft_grad's module docstring); at 'heads' such a pass runs
+        iteration by iteration as well and keeps every earlier iteration's (net_k, 1/8 flow_k), 130 h8 w8 4 bytes per pair each."""
         self.check_grad(stages, kw.get('upsample', True))
+        if grad_all_flows:
+            self.check_grad_all_flows(kw.get('all_flows', False), stages, kw.get('upsample', True))
         if (sources is None) != (stages != 'encoders'):
             raise RpeError("RAFT.grad_pass: sources goes with stages='encoders', and only with it")
         if sources is not None:
             for (_, lo, hi), t in zip(sources, (*fmaps, cnet)):
                 if hi - lo != t.shape[0]:
                     raise RpeError(f'RAFT.grad_pass: a source names {hi - lo} images for {t.shape[0]} rows of encoder output')
-        states = None if stages == 'heads' else []
+        states = None if stages == 'heads' and not grad_all_flows else []
         r = self._forward_impl(self._route(map_size=tuple(fmaps[0].shape[-2:])), fmaps, cnet, ret_lowres=True, states=states, **kw)
         rec = raft_grad.GradPass(r[0][-1], r[1], r[3])
-        if states is not None:
-            c = self.hidden_dim
+        c = self.hidden_dim
+        if grad_all_flows:
+            rec.earlier = list(r[0][:-1])
+            if stages == 'heads':                              # (the states' h_k and flow_k alone: the 258-channel copies are dropped)
+                fresh = lambda t: ops.copy_planes(t, torch.empty(t.shape, dtype=torch.float32, device=t.device))
+                rec.tail_states = [(fresh(st[:, :c]), fresh(st[:, st.shape[1] - 2:])) for st, _ in states[1:]]
+        if stages != 'heads':
             rec.net0, rec.inp, rec.states = cnet[:, :c], cnet[:, c:], states
             rec.pyr, self._pyr = self._pyr, None
         if stages in ('corr', 'encoders'):
@@ -1234,6 +1243,17 @@ class RAFT(nn.Module):
         if stages == 'encoders':                               # (what raft_grad.encoder_backward refuses without a tensor in hand)
             for enc in (self.fnet, self.cnet):
                 raft_grad._check_modes('RAFT: grad_encoders', enc)
+
+    @staticmethod
+    def check_grad_all_flows(all_flows, stages, upsample=True):
+        """The refusals of ``grad_all_flows`` (raised before anything is launched): it differentiates the predictions all_flows returns,
+        through a node of some depth, and those are the up-sampled ones."""
+        if not all_flows:
+            raise RpeError('RAFT: grad_all_flows differentiates every returned prediction: it needs all_flows=True')
+        if stages is None:
+            raise RpeError('RAFT: grad_all_flows needs a gradient stage: one of grad_heads, grad_update, grad_corr, grad_encoders')
+        if not upsample:
+            raise RpeError('RAFT: grad_all_flows attaches to the up-sampled predictions: it needs upsample=True')
 
     def check_grad_heads(self, upsample=True):
         """The refusals of ``grad_heads`` (raised before anything is launched): the tail's backward differentiates the f32 layers; a route
@@ -1259,7 +1279,7 @@ class RAFT(nn.Module):
 
     @torch.no_grad()
     def forward(self, image1, image2, upsample=True, iters=None, all_flows=False, fmaps=None, cnet=None, flow_init=None, ret_lowres=False,
-                grad_heads=False, grad_update=False, grad_corr=False, grad_encoders=False):
+                grad_heads=False, grad_update=False, grad_corr=False, grad_encoders=False, grad_all_flows=False):
         """image1, image2: (N,3,H,W) in 0..255.  Inference only (the reference freezes RAFT, train.yaml:51).
         ``fmaps`` / ``cnet`` accept encoder outputs computed elsewhere (both encoders normalise per sample -- instance
         norm / frozen batch norm -- so a caller may encode every distinct image once and reuse it); with both given the
@@ -1278,8 +1298,14 @@ class RAFT(nn.Module):
         needed.  It needs the images: with ``fmaps`` or ``cnet`` given it is refused before any launch -- an encoder output computed
         elsewhere cannot be differentiated here -- as are a batch norm in training mode and an active dropout.  It returns what a
         grad_corr call returns, with the same values, except that ``hidden`` and the context are the node's ``hidden_out`` and
-        ``context_out``: whatever a consumer differentiates of them returns into the chain (the four leaves behind still get their .grad)."""
+        ``context_out``: whatever a consumer differentiates of them returns into the chain (the four leaves behind still get their .grad).
+        ``grad_all_flows`` (with ``all_flows=True`` and one of the four stages): EVERY element of the returned ``flows`` is an output of
+        the one node, so a loss over all N predictions -- RAFT's sequence loss, ops.flow_sequence_loss -- trains the model as far as the
+        stage goes; values, launches of the forward and the other return elements are those of the call without it.  Refused before any
+        launch without all_flows, without a stage, or with upsample=False."""
         stages = 'encoders' if grad_encoders else 'corr' if grad_corr else 'update' if grad_update else 'heads' if grad_heads else None
+        if grad_all_flows:
+            self.check_grad_all_flows(all_flows, stages, upsample)
         if stages is not None:
             self.check_grad(stages, upsample)                  # (before the encoders run: a refused pass launches nothing)
         sources = None
@@ -1293,13 +1319,16 @@ class RAFT(nn.Module):
         if stages is None:
             return self._forward_impl(route, fmaps, cnet, upsample, iters, all_flows, flow_init, ret_lowres)
         (flows, _, context, low), rec = self.grad_pass(fmaps, cnet, stages=stages, sources=sources, upsample=upsample, iters=iters, all_flows=all_flows,
-                                                       flow_init=flow_init)
+                                                       flow_init=flow_init, grad_all_flows=grad_all_flows)
         rec = rec.rows(0, rec.hidden.shape[0])
         hidden = rec.hidden
+        outs, earlier = raft_grad.attach([rec], self.head_params(), None if stages == 'heads' else self.update_params(),
+                                         (self.fnet, self.cnet) if grad_encoders else None, ret_earlier=True)
         if grad_encoders:
-            flows[-1], hidden, context = raft_grad.attach([rec], self.head_params(), self.update_params(), (self.fnet, self.cnet))[0]
+            flows[-1], hidden, context = outs[0]
         else:
-            flows[-1] = raft_grad.attach([rec], self.head_params(), None if stages == 'heads' else self.update_params())[0]
+            flows[-1] = outs[0]
+        flows[:-1] = earlier[0] if grad_all_flows else flows[:-1]
         leaves = tuple(t for t in (rec.net0, rec.inp, rec.fmap1, rec.fmap2) if t is not None)
         return (flows, hidden, context) + ((low,) if ret_lowres else ()) + leaves
 

@@ -35,6 +35,14 @@ fields are present; each stage includes the ones above it:
             distinct context image.  encoder_backward then runs ONCE per encoder, on the images something contributed to, and not at all
             for an encoder none of whose parameters requires grad; the 94 gradients leave the node as the gradients of its inputs.
             Every launch and every gradient of 'corr' keeps its bits.  This is what the reference's freeze_flow(False) trains.
+A gradient per iteration (``grad_all_flows``, any depth): a record may carry ``earlier``, the N - 1 earlier up-sampled predictions, and the
+node then has them as further outputs, behind the ones above (flows, hidden_out, context_out; then pass by pass the earlier predictions)
+so that those keep their positions.  Prediction k depends on the parameters through net_k only -- coords1 is detached --, so the gradient
+of a loss over all predictions (RAFT's sequence loss, ops.flow_sequence_loss) is the same walk with one more tail per iteration: in front
+of the step that takes d net_k on, a prediction k that received a gradient runs raft_tail_backward on (net_k, flow_low_k, g_k)
+(GradPass.tail_inputs: both lie in the saved entry state of iteration k + 1), its d_net is added to the carried d net_k and its eight head
+gradients to the heads' sum, which runs k = N, N - 1, .. 1, one term at a time, at every depth.  A prediction without a gradient costs no
+tail; with a gradient on the last prediction alone launches and bits are those of a record without ``earlier``.
 Refused before any launch (RAFT.check_grad_heads): update_fp16, CONV_BF16X3, mixed_precision -- a route that rounds the heads' operands
 has no honest gradient here -- and upsample=False; for 'corr' also alternate_corr (no pyramid) and CORR_BF16X3 (RAFT.check_grad_corr); for
 'encoders' also a batch norm in training mode and an active dropout in an encoder (_check_modes).
@@ -65,6 +73,12 @@ UPDATE_GROUP_3X3, UPDATE_GROUP_5TAP, UPDATE_GROUP_1X1 = 16, 32, 64
 # the 1x1 output layer (64); a stride-2 layer's recomputation runs ops.conv_direct on groups of at most ENC_CHAIN terms
 ENC_GROUP_3X3_FWD, ENC_GROUP_3X3_BWD, ENC_GROUP_1X1, ENC_CHAIN = 16, 32, 64, 288
 ENC_WGRAD_CHAIN = 1024                                                   # pixels rpe_conv_bwd_weight keeps in one chunk (include/rpe.h: its chunk rule)
+# a step's weight gradients under a gradient per iteration (update_step_backward(wgrad_bands=True)): on a map rpe_conv_bwd_weight keeps in
+# one chunk, the pixels one GEMM sums -- row bands of the map, the bands' results added in f64
+UPDATE_WGRAD_BAND = 64
+# likewise the encoders' stride-1 layers (encoder_backward(wgrad_bands=True)): maps of ENC_WGRAD_CHAIN < b h w <= ENC_BAND_CAP pixels, which
+# the kernel sums in chains of ENC_WGRAD_CHAIN, in bands of ENC_WGRAD_BAND pixels
+ENC_WGRAD_BAND, ENC_BAND_CAP = 256, 4096
 
 
 # ------------------------------------------------------------------------------------------------- weight packings
@@ -191,7 +205,26 @@ def raft_tail_backward(net, flow_low, grad_up, fh_params, mask_params):
     return d_net, (dw1[:hid], db1[:hid], dw_fh2, db_fh2, dw1[hid:], db1[hid:], dw_m2, db_m2)
 
 
-def update_step_backward(hx, inp, corr, d_net, params, ret_d_corr=False):
+def _banded_bwd_weight(x, dy, kernel, bias=True, band=UPDATE_WGRAD_BAND, cap=ENC_WGRAD_CHAIN):
+    """ops.conv_bwd_weight on a map of at most ``cap`` pixels, where the kernel adds up to ENC_WGRAD_CHAIN products of an output element in
+    ONE f32 chain: the gradient is formed per band of rows -- dy zero outside the band, so the other pixels' products are exact zeros and
+    add nothing to the chain -- of about ``band`` pixels, and the bands are added in f64 and rounded once (sum_groups).  Every band costs
+    the whole map's GEMM, hence the cap; a larger map, or one that is a single band, is the one launch it always was."""
+    b, _, hh, ww = dy.shape
+    rows = max(1, band // (b * ww))
+    if b * hh * ww > cap or rows >= hh:
+        return conv_bwd_weight(x, dy, kernel, bias=bias)
+    per = []
+    for lo in range(0, hh, rows):
+        part = torch.zeros(dy.shape, dtype=torch.float32, device=dy.device)
+        part[:, :, lo:lo + rows] = dy[:, :, lo:lo + rows]
+        per.append(conv_bwd_weight(x, part, kernel, bias=bias))
+    dw0, n = per[0][0], len(per)
+    dw = sum_groups(torch.stack([p[0] for p in per]).view(n, 1, dw0.shape[0], -1, dw0.shape[3])).view_as(dw0)
+    return dw, (sum_groups(torch.stack([p[1] for p in per]).view(n, 1, -1, 1, 1)).view(-1) if bias else None)
+
+
+def update_step_backward(hx, inp, corr, d_net, params, ret_d_corr=False, wgrad_bands=False):
     """Backward of ONE application of RAFT's update block without its heads (csrc/update_backward.hip):
         cor = relu(convc2(relu(convc1(corr)))); flo = relu(convf2(relu(convf1(flow)))); m = relu(conv([cor | flo])); x = [inp | m | flow]
         per half (1x5, then 5x1): z = s(convz([h | x])), r = s(convr([h | x])), q = tanh(convq([r h | x])), h <- (1 - z) h + z q
@@ -203,7 +236,9 @@ def update_step_backward(hx, inp, corr, d_net, params, ret_d_corr=False):
     convc1's transposed 1x1 weight applied to the gradient in front of convc1's ReLU (conv_split, groups of UPDATE_GROUP_1X1 channels added
     in f64): what ops.corr_lookup_backward accumulates.  Without the flag the launches and the results are those of a call without it.  Every intermediate is recomputed here with the forward's kernels on
     groups of input channels added in f64 (conv_split), which also compute the data gradients; the gradients that reach a tensor by several
-    paths are added in that same f64 sum.  f32 throughout, bit-identical from run to run, a row's result independent of its batch."""
+    paths are added in that same f64 sum.  ``wgrad_bands``: the eleven weight gradients through _banded_bwd_weight (small maps: row bands
+    added in f64 instead of one f32 chain over the map); without it the launches and the bits are those of before.  f32 throughout,
+    bit-identical from run to run, a row's result independent of its batch."""
     who = 'update_step_backward'
     hx, inp, corr, d_net = _nchw(hx, f'{who}: hx'), _nchw(inp, f'{who}: inp'), _nchw(corr, f'{who}: corr'), _nchw(d_net, f'{who}: d_net')
     params = tuple(params)
@@ -217,6 +252,7 @@ def update_step_backward(hx, inp, corr, d_net, params, ret_d_corr=False):
     if tuple(inp.shape) != (b, c, hh, ww) or tuple(d_net.shape) != (b, c, hh, ww) or tuple(corr.shape[::2]) != (b, hh) or corr.shape[3] != ww:
         raise _lib.RpeError(f'{who}: inp and d_net must be ({b},{c},{hh},{ww}) and corr (b,324,h8,w8) for hx {tuple(hx.shape)}')
     P = _packed(_UpdatePacked, params)
+    wgrad = _banded_bwd_weight if wgrad_bands else conv_bwd_weight
     G3, G5, G1 = UPDATE_GROUP_3X3, UPDATE_GROUP_5TAP, UPDATE_GROUP_1X1
     new = lambda ch: torch.empty(b, ch, hh, ww, dtype=torch.float32, device=hx.device)
     with torch.no_grad():
@@ -251,10 +287,10 @@ def update_step_backward(hx, inp, corr, d_net, params, ret_d_corr=False):
             kernel = (1, 5) if i == 0 else (5, 1)
             dzr, dq, dh = new(2 * c), new(c), new(c)
             gru_gates_zq_backward(d, A[:, :c], z[i], q[i], dzr[:, :c], dq, dh)
-            grads['q' + hf] = conv_bwd_weight(R, dq, kernel)
+            grads['q' + hf] = wgrad(R, dq, kernel)
             T = P.conv_split('q' + hf + 't', dq, P.w['q' + hf + 't'], None, False, G5)
             gru_gates_r_backward(T[:, :c], A[:, :c], r[i], dh, dzr[:, c:], T[:, :c])
-            dw, db = conv_bwd_weight(A, dzr, kernel)                     # convz | convr read the same input: one GEMM of 2 c output channels
+            dw, db = wgrad(A, dzr, kernel)                     # convz | convr read the same input: one GEMM of 2 c output channels
             grads['z' + hf], grads['r' + hf] = (dw[:c], db[:c]), (dw[c:], db[c:])
 
             def fill(terms, T=T, carry=carry):
@@ -270,17 +306,17 @@ def update_step_backward(hx, inp, corr, d_net, params, ret_d_corr=False):
         # the motion encoder's adjoint (nothing into flow or corr)
         m = A1[:, 2 * c:3 * c - 2]
         dm = relu_backward(carry[:, 2 * c:3 * c - 2], m)
-        grads['cv'] = conv_bwd_weight(cat, dm, (3, 3))
+        grads['cv'] = wgrad(cat, dm, (3, 3))
         dcat = P.conv_split('cvt', dm, P.w['cvt'], None, False, G3)
         relu_backward(dcat, cat)
-        grads['c2'] = conv_bwd_weight(c1, dcat[:, :192], (3, 3))
-        grads['f2'] = conv_bwd_weight(f1, dcat[:, 192:], (3, 3))
+        grads['c2'] = wgrad(c1, dcat[:, :192], (3, 3))
+        grads['f2'] = wgrad(f1, dcat[:, 192:], (3, 3))
         dc1 = P.conv_split('c2t', dcat[:, :192], P.w['c2t'], None, False, G3)
         relu_backward(dc1, c1)
-        grads['c1'] = conv_bwd_weight(corr, dc1, (1, 1))
+        grads['c1'] = wgrad(corr, dc1, (1, 1))
         df1 = P.conv_split('f2t', dcat[:, 192:], P.w['f2t'], None, False, G3)
         relu_backward(df1, f1)
-        grads['f1'] = conv_bwd_weight(flow, df1, (7, 7))
+        grads['f1'] = wgrad(flow, df1, (7, 7))
         d_corr = P.conv_split('c1t', dc1, P.w['c1t'], None, False, G1) if ret_d_corr else None
     order = ('z1', 'r1', 'q1', 'z2', 'r2', 'q2', 'c1', 'c2', 'f1', 'f2', 'cv')
     out = (d_net_prev, d_inp, tuple(t for name in order for t in grads[name]))
@@ -373,12 +409,14 @@ def _norm_adjoint(conv, norm, dy, z):
     return instnorm_backward(dy, z, eps=norm.eps, dz=dy), [torch.zeros_like(conv.bias)]
 
 
-def _bwd_weight(x, dy, kernel, bias=True):
+def _bwd_weight(x, dy, kernel, bias=True, bands=False):
     """ops.conv_bwd_weight for the encoders' stride-1 layers.  rpe_conv_bwd_weight splits K = b h w into chunks only above ENC_WGRAD_CHAIN
     pixels; a batch of several small maps below that would be ONE f32 chain across the images (at K = 512, two 16 x 16 maps, 2.6 times the
     error of a blocked float32 sum on the output layer's weight).  There each image's GEMM runs alone and the images are added in f64
     (sum_groups); one image, or a batch the kernel chunks itself, is the one launch it was."""
     b, _, hh, ww = x.shape
+    if bands and b * hh * ww > ENC_WGRAD_CHAIN:                  # (``bands``: a gradient per iteration; without it the launches of before)
+        return _banded_bwd_weight(x, dy, kernel, bias, ENC_WGRAD_BAND, ENC_BAND_CAP)
     if b == 1 or b * hh * ww > ENC_WGRAD_CHAIN:
         return conv_bwd_weight(x, dy, kernel, bias=bias)
     per = [conv_bwd_weight(x[i:i + 1], dy[i:i + 1], kernel, bias=bias) for i in range(b)]
@@ -406,18 +444,18 @@ def _block_forward(block, x, P, name):
     return r
 
 
-def _block_backward(block, r, d_out, P, name):
+def _block_backward(block, r, d_out, P, name, bands=False):
     """-> (d_x, the block's gradients in block_params' order) from the record of _block_forward."""
     x, s2 = r['x'], block.downsample is not None
     g = relu_backward(d_out, r['out'], out=torch.empty_like(d_out))          # behind the block's last ReLU: ONE mask, the gradient of both paths
     gy = relu_backward(g, r['y'], out=torch.empty_like(g))
     dz2, gn2 = _norm_adjoint(block.conv2, block.norm2, gy, r['z2'])
-    dw2 = _bwd_weight(r['a1'], dz2, (3, 3), bias=False)[0]
+    dw2 = _bwd_weight(r['a1'], dz2, (3, 3), bias=False, bands=bands)[0]
     da1 = P.conv_split(f'{name}.conv2.t', dz2, P.tr(f'{name}.conv2', block.conv2.weight), None, False, ENC_GROUP_3X3_BWD)
     relu_backward(da1, r['a1'])
     dz1, gn1 = _norm_adjoint(block.conv1, block.norm1, da1, r['z1'])
     if not s2:
-        dw1 = _bwd_weight(x, dz1, (3, 3), bias=False)[0]
+        dw1 = _bwd_weight(x, dz1, (3, 3), bias=False, bands=bands)[0]
         # d x = conv1's data gradient + the shortcut's g, one more term of the same f64 sum
         d_x = P.conv_split(f'{name}.conv1.t', dz1, P.tr(f'{name}.conv1', block.conv1.weight), None, False, ENC_GROUP_3X3_BWD, extra=1,
                            fill=lambda terms: copy_planes(g, terms[0]))
@@ -472,7 +510,7 @@ def _encoder_out_shape(enc, n, hh, ww):
     return (n, enc.conv2.out_channels, hh, ww)
 
 
-def encoder_backward(enc, images, d_out, raw255=True, split_act=False, route=None):
+def encoder_backward(enc, images, d_out, raw255=True, split_act=False, route=None, wgrad_bands=False):
     """Backward of a BasicEncoder (fnet: instance norm; cnet: frozen batch norm) for one batch: ``images`` as BasicEncoder.forward takes them
     (one batch or a list of batches, raw 0..255 with ``raw255``), d_out = d loss / d (the encoder's output), behind the tanh | ReLU of
     ``split_act`` when that is set -> the list of parameter gradients in encoder_params' order.  Nothing goes into the images.
@@ -481,7 +519,8 @@ def encoder_backward(enc, images, d_out, raw255=True, split_act=False, route=Non
     and block inputs live during the call only.  ``route``: the pass's raft.Route (RAFT hands its own; else the encoder's own flags under
     the module switches).  Refused before any launch: a batch norm in training mode, dropout > 0 in training mode, update_fp16,
     CONV_BF16X3, mixed_precision, tensors that are not float32, a d_out that is not the encoder's output shape.  f32, bit-identical
-    from run to run."""
+    from run to run.  ``wgrad_bands`` (the node sets it under a gradient per iteration): the stride-1 layers' weight gradients on maps of
+    ENC_WGRAD_CHAIN < b h w <= ENC_BAND_CAP pixels in row bands added in f64 (_banded_bwd_weight); without it the launches of before."""
     from . import raft
     who = 'encoder_backward'
     _check_modes(who, enc)
@@ -525,10 +564,10 @@ def encoder_backward(enc, images, d_out, raw255=True, split_act=False, route=Non
         else:
             d = d_out
         # the adjoints, last layer first
-        grads = list(_bwd_weight(x, d, (1, 1)))
+        grads = list(_bwd_weight(x, d, (1, 1), bands=wgrad_bands))
         d = P.conv_split('conv2.t', d, P.tr('conv2', w2), None, False, ENC_GROUP_1X1)
         for (name, blk), r in zip(reversed(blocks), reversed(recs)):
-            d, g = _block_backward(blk, r, d, P, name)
+            d, g = _block_backward(blk, r, d, P, name, wgrad_bands)
             grads = g + grads
             r.clear()
         relu_backward(d, a0)
@@ -567,6 +606,8 @@ class GradPass:
     whole: Optional[tuple] = None                            # rows(): (the whole pass's coords1_k, lo, hi) -- the pyramid holds every row
     _last: tuple = (None, None)                              # corr's memo: (k, the whole pass's window of iteration k + 1)
     sources: Optional[tuple] = None                          # 'encoders': ((images, lo, hi) of fmap1, of fmap2, of the context): _source_rows
+    earlier: Optional[List[torch.Tensor]] = None             # ``grad_all_flows``, any depth: the N - 1 earlier up-sampled predictions, k = 1 .. N - 1
+    tail_states: Optional[List[Tuple[torch.Tensor, torch.Tensor]]] = None      # ... at 'heads', which has no states: [(net_k, flow_low_k)], k = 1 .. N - 1
 
     TENSORS = ('flow_up', 'hidden', 'flow_low', 'net0', 'inp', 'fmap1', 'fmap2')        # the node's tensor inputs, in this order
     LEAVES = ('hidden', 'net0', 'inp', 'fmap1', 'fmap2')                                # ... of which a backward fills the .grad
@@ -591,8 +632,26 @@ class GradPass:
             coords, base = ([co for _, co in self.states], 0) if self.whole is None else self.whole[:2]
             whole = (coords, base + lo, base + hi)
         sources = None if self.sources is None else tuple((images, base + lo, base + hi) for images, base, _ in self.sources)
+        earlier = None if self.earlier is None else [e[lo:hi].contiguous() for e in self.earlier]
+        tails = None if self.tail_states is None else [(n[lo:hi], f[lo:hi]) for n, f in self.tail_states]
         return GradPass(self.flow_up[lo:hi].contiguous(), self.hidden[lo:hi].detach().requires_grad_(True), self.flow_low[lo:hi],
-                        leaf(self.net0), leaf(self.inp), states, self.pyr, fleaf(self.fmap1), fleaf(self.fmap2), whole, sources=sources)
+                        leaf(self.net0), leaf(self.inp), states, self.pyr, fleaf(self.fmap1), fleaf(self.fmap2), whole, sources=sources,
+                        earlier=earlier, tail_states=tails)
+
+    def tail_inputs(self, k):
+        """(net_k, flow_low_k) of the earlier prediction k, 1 <= k < N, as contiguous tensors: what the heads read when they formed it.
+        Below 'heads' both lie in the saved entry state of iteration k + 1 (``states[k]``): its first 128 channels (h_k, which the next
+        step is about to update in place) and its last two (the flow the next motion encoder reads -- on the fused route the flow
+        head's own output slot, on the generic route the same coords1 - coords0 the prediction was formed from; under pad_maps the
+        content of the padded maps, as the returned hidden state and 1/8 flow are).  At 'heads' the pass kept copies of just these."""
+        if self.tail_states is not None:
+            net, flow = self.tail_states[k - 1]
+        else:
+            st = self.states[k][0]
+            c = self.hidden.shape[1]
+            net, flow = st[:, :c], st[:, st.shape[1] - 2:]
+        fresh = lambda t: t if t.is_contiguous() else copy_planes(t, torch.empty(t.shape, dtype=torch.float32, device=t.device))
+        return fresh(net), fresh(flow)
 
     def corr(self, k):
         """The window iteration k + 1 looked up (``states[k]`` = its (hx, coords1)): the pass's lookup on the saved coordinates against
@@ -610,15 +669,32 @@ def _by_field(passes, tensors):
     return [{name: next(it) for name in p.tensors()} for p in passes], list(it)
 
 
-def _through_time(rec, t, upd, grads):
+def _through_time(rec, t, upd, grads, heads=None, g_early=(), hg=None):
     """The steps k = N .. 1 of one pass behind grads['hidden'] = d net_N (the tail's, at 'encoders' plus what arrived on hidden_out); from
-    'corr' on every step's lookup adjoint and, after step 1, the build's.  ``t``: the pass's tensor inputs by field.  Fills ``grads``
-    (field -> gradient); -> the 22 update gradients summed in descending k (zeros for a pass without states)."""
+    'corr' on every step's lookup adjoint and, after step 1, the build's.  ``t``: the pass's tensor inputs by field.  ``g_early``
+    (``grad_all_flows``): the gradients that arrived on the earlier predictions k = 1 .. N - 1, None where none did.  In front of step
+    k + 1 -- the step that takes d net_k on to d net_{k-1} runs next -- a prediction k that received one runs its own tail
+    (raft_tail_backward on GradPass.tail_inputs(k)) under ``heads``, whose d_net is ADDED to the carried d net_k; one that received none
+    costs nothing.  While nothing has arrived yet (no gradient on the last prediction, nor on hidden_out) the carried gradient is absent
+    and the steps above the first such prediction are not run: they would carry zeros.  ``hg``: the eight head gradients of the pass's
+    last tail, or None; the earlier tails' are added to it one by one, so the heads' sum runs ((N + (N - 1)) + ...) + 1 at every depth.
+    Fills ``grads`` (field -> gradient); -> (the 22 update gradients summed in descending k, zeros for a pass without a step; the
+    heads' sum, None without a tail).  The steps' sum: without a gradient on an earlier prediction the float32 chain it always was (its
+    bits are kept); with one, every step's 22 gradients are kept and added in f64, rounded once (sum_groups) -- N - 1 roundings fewer
+    on the weights every step contributes to -- and every step forms its weight gradients in row bands on small maps
+    (update_step_backward(wgrad_bands=True))."""
     with_corr = rec.fmap1 is not None
     inp, d = t['inp'].detach(), grads['hidden']
     d_inp, ug, vol, levels = None, None, None, None
+    early, per_step = any(g is not None for g in g_early), []
     for k in reversed(range(len(rec.states))):
-        r = update_step_backward(rec.states[k][0], inp, rec.corr(k), d, upd, ret_d_corr=with_corr)
+        if k + 1 <= len(g_early) and g_early[k] is not None:           # prediction k + 1 < N, formed from net_{k+1}: states[k + 1]
+            dn, tg = raft_tail_backward(*rec.tail_inputs(k + 1), g_early[k].contiguous(), heads[:4], heads[4:])
+            d = _plus(d, dn)
+            hg = list(tg) if hg is None else [a + b for a, b in zip(hg, tg)]
+        if d is None:
+            continue
+        r = update_step_backward(rec.states[k][0], inp, rec.corr(k), d, upd, ret_d_corr=with_corr, **({'wgrad_bands': True} if early else {}))
         d, di, sg = r[:3]
         if with_corr:
             if vol is None:
@@ -626,11 +702,18 @@ def _through_time(rec, t, upd, grads):
                 vol = ops.corr_grad_volume(r[3].shape[0], *r[3].shape[2:], levels, device=r[3].device)
             ops.corr_lookup_backward(rec.states[k][1], r[3], vol)
         d_inp = di if d_inp is None else d_inp + di
-        ug = list(sg) if ug is None else [a + b for a, b in zip(ug, sg)]
+        if early:
+            per_step.append(sg)
+        else:
+            ug = list(sg) if ug is None else [a + b for a, b in zip(ug, sg)]
+    if len(per_step) == 1:
+        ug = list(per_step[0])
+    elif per_step:                                              # (a weight as (steps,1,cout,rest,1), a bias as (steps,1,c,1,1): _bwd_weight's views)
+        ug = [sum_groups(torch.stack(ts).view(len(ts), 1, ts[0].shape[0], -1, 1)).view_as(ts[0]) for ts in zip(*per_step)]
     grads['net0'], grads['inp'] = d, d_inp
     if vol is not None:                                         # (S h8 w8 4 bytes per pair: freed on return, before the next pass)
         grads['fmap1'], grads['fmap2'] = ops.corr_build_backward(vol, t['fmap1'].detach(), t['fmap2'].detach(), levels)
-    return ug if ug is not None else [torch.zeros_like(p) for p in upd]
+    return (ug if ug is not None else [torch.zeros_like(p) for p in upd]), hg
 
 
 def _plus(a, b):
@@ -669,7 +752,7 @@ def _image_batches(order):
     return [im if (lo, hi) == (0, im.shape[0]) else im[lo:hi] for im, lo, hi in runs]
 
 
-def _encoders_backward(passes, all_grads, encoders, need):
+def _encoders_backward(passes, all_grads, encoders, need, bands=False):
     """The encoders behind the last pass of an 'encoders' node: ``all_grads`` = every pass's {field: gradient}; ``need`` = (does a parameter
     of fnet, of cnet require grad) -> fnet's gradients + cnet's in encoder_params' order, None for an encoder that is not run."""
     fnet, cnet = encoders
@@ -685,7 +768,8 @@ def _encoders_backward(passes, all_grads, encoders, need):
     for enc, walk, split, wanted in ((fnet, walk_f, False, need[0]), (cnet, walk_c, True, need[1])):
         order, d = _per_image(walk) if wanted else ([], None)
         n = len(encoder_params(enc))
-        out += [None] * n if d is None else list(encoder_backward(enc, _image_batches(order), d.contiguous(), raw255=True, split_act=split))
+        out += [None] * n if d is None else list(encoder_backward(enc, _image_batches(order), d.contiguous(), raw255=True, split_act=split,
+                                                                        **({'wgrad_bands': True} if bands else {})))
     return out
 
 
@@ -705,9 +789,10 @@ class _RaftGradFn(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         fields = _by_field(passes, tensors)[0]
         flows = tuple(t['flow_up'].view_as(t['flow_up']) for t in fields)
+        early = tuple(e.detach() for p in passes for e in (p.earlier or ()))
         if encoders is None:
-            return flows
-        return flows + tuple(t['hidden'].detach() for t in fields) + tuple(t['inp'].detach() for t in fields)
+            return flows + early
+        return flows + tuple(t['hidden'].detach() for t in fields) + tuple(t['inp'].detach() for t in fields) + early
 
     @staticmethod
     def backward(ctx, *grads_out):
@@ -715,8 +800,14 @@ class _RaftGradFn(torch.autograd.Function):
         heads, upd, n = params[:8], params[8:30], len(ctx.passes)
         deep = ctx.encoders is not None
         totals, flat, all_grads = None, [], []
+        any_early = False
+        at = 3 * n if deep else n                                  # the earlier predictions' gradients: behind the existing outputs, pass by pass
         for i, (rec, t) in enumerate(zip(ctx.passes, fields)):
             g, g_hid, g_ctx = grads_out[i], (grads_out[n + i] if deep else None), (grads_out[2 * n + i] if deep else None)
+            g_early = grads_out[at:at + len(rec.earlier or ())]
+            at += len(g_early)
+            early = any(x is not None for x in g_early)
+            any_early = any_early or early
             grads = dict.fromkeys(t)
             both = None
             if g is not None:
@@ -724,8 +815,13 @@ class _RaftGradFn(torch.autograd.Function):
                 both = list(both)
             if g_hid is not None:                                  # (once, before step N)
                 grads['hidden'] = _plus(grads['hidden'], g_hid)
-            if grads['hidden'] is not None and rec.depth != 'heads':
-                ug = _through_time(rec, t, upd, grads)
+            if rec.depth == 'heads':                               # no path through time: the earlier tails' head gradients alone, k descending
+                for k in reversed(range(len(g_early))):
+                    if g_early[k] is not None:
+                        tg = raft_tail_backward(*rec.tail_inputs(k + 1), g_early[k].contiguous(), heads[:4], heads[4:])[1]
+                        both = list(tg) if both is None else [a + b for a, b in zip(both, tg)]
+            elif grads['hidden'] is not None or early:
+                ug, both = _through_time(rec, t, upd, grads, heads, g_early, both)
                 both = [None] * 8 + ug if both is None else both + ug
             if g_ctx is not None:                                  # (once, behind the steps' sum)
                 grads['inp'] = _plus(grads['inp'], g_ctx)
@@ -737,17 +833,18 @@ class _RaftGradFn(torch.autograd.Function):
         if deep:
             need = ctx.needs_input_grad[2 + len(flat) + 30:]
             n_f = len(encoder_params(ctx.encoders[0]))
-            totals += _encoders_backward(ctx.passes, all_grads, ctx.encoders, (any(need[:n_f]), any(need[n_f:])))
+            totals += _encoders_backward(ctx.passes, all_grads, ctx.encoders, (any(need[:n_f]), any(need[n_f:])), any_early)
         return (None, None, *flat, *totals[:len(params)])
 
 
-def attach(passes, head_params, update_params=None, encoders=None):
+def attach(passes, head_params, update_params=None, encoders=None, ret_earlier=False):
     """Attach the backward to the results of gradient-free RAFT passes: ``passes`` = GradPass records of ONE depth whose ``hidden`` -- and,
     below 'heads', ``net0``, ``inp``, ``fmap1``, ``fmap2`` -- are leaves that require grad (GradPass.rows); ``head_params`` = RAFT.head_params(),
     ``update_params`` = RAFT.update_params() (needed below 'heads'), ``encoders`` = (fnet, cnet), the modules (needed at 'encoders', refused
     at every other depth) -> the list of up-sampled flows (the same values), outputs of one _RaftGradFn node; at 'encoders' the list of
     every pass's (flow, hidden_out, context_out).  After a backward the leaves' and the parameters' .grad are what the module docstring
-    says of the passes' depth."""
+    says of the passes' depth.  ``ret_earlier``: -> (that result, per pass the list of its ``earlier`` predictions as outputs of the same
+    node -- empty for a pass that carries none)."""
     depth = {p.depth for p in passes}
     if len(depth) != 1:
         raise _lib.RpeError(f'raft_grad.attach: every pass must carry the same stages, got {sorted(depth)}')
@@ -761,4 +858,8 @@ def attach(passes, head_params, update_params=None, encoders=None):
     with torch.enable_grad():
         outs = list(_RaftGradFn.apply(list(passes), None if encoders is None else tuple(encoders), *flat, *fh, *mk, *(update_params or ()), *enc_params))
     n = len(passes)
-    return outs if encoders is None else [(outs[i], outs[n + i], outs[2 * n + i]) for i in range(n)]
+    res = outs[:n] if encoders is None else [(outs[i], outs[n + i], outs[2 * n + i]) for i in range(n)]
+    if not ret_earlier:
+        return res
+    it = iter(outs[n if encoders is None else 3 * n:])
+    return res, [[next(it) for _ in (p.earlier or ())] for p in passes]

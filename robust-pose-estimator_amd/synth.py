@@ -141,6 +141,33 @@ def training_pairs(seed, count, h, w, bf=7.2, batch=1):
         yield tuple(torch.stack(col).contiguous() for col in zip(*rows))
 
 
+def flow_pairs(seed, count, h, w, batch=1):
+    """``count`` batches for training RAFT on ground-truth flow (train.flow_train_step): tuples (image1, image2, flow_gt, valid) of CPU
+    tensors with ``batch`` rows -- images (b,3,h,w) 0..255, flow_gt (b,2,h,w) f32 in pixels, valid (b,h,w) bool, true everywhere but one
+    rectangle.  Rendered as ``training_pairs`` renders its target / reference pair: a rigid scene under the exact motion X' = R X + t of
+    exp(xi), image2 = image1 warped with the flow that motion induces, which is flow_gt from image1 to image2.  Seeded."""
+    rng = np.random.default_rng(seed)
+    K = intrinsics(h, w)
+    ys, xs = torch.meshgrid(torch.arange(h, dtype=torch.float32) + 0.5, torch.arange(w, dtype=torch.float32) + 0.5, indexing='ij')
+    for _ in range(count):
+        rows = []
+        for _ in range(batch):
+            depth = 0.2 + 0.7 * _smooth(rng, 1, h, w, 5)[0]
+            tex = 255.0 * (0.6 * _smooth(rng, 3, h, w, 24) + 0.4 * _smooth(rng, 3, h, w, 96))
+            xi = np.concatenate((rng.normal(0, 0.005, 3), rng.normal(0, 0.01, 3)))
+            R, t, _ = _se3_exp(xi)
+            X = torch.stack(((xs - K[0, 2]) / K[0, 0] * depth, (ys - K[1, 2]) / K[1, 1] * depth, depth))
+            Xp = torch.einsum('ij,jhw->ihw', torch.from_numpy(R).float(), X) + torch.from_numpy(t).float()[:, None, None]
+            fx, fy = K[0, 0] * Xp[0] / Xp[2] + K[0, 2] - xs, K[1, 1] * Xp[1] / Xp[2] + K[1, 2] - ys
+            image1 = tex[None]
+            image2 = _warp(image1, -fx[None], -fy[None])
+            valid = torch.ones(h, w, dtype=torch.bool)
+            y0, x0 = int(rng.integers(0, h - h // 5)), int(rng.integers(0, w - w // 4))
+            valid[y0:y0 + h // 5, x0:x0 + w // 4] = False
+            rows.append((image1[0], image2[0], torch.stack((fx, fy)), valid))
+        yield tuple(torch.stack(col).contiguous() for col in zip(*rows))
+
+
 def infer_args(s):
     return dict(image1l=s['image1l'], image2l=s['image2l'], intrinsics=s['K'], baseline=s['baseline'], depth1=s['depth1'],
                 image2r=s['image2r'], mask1=s['mask1'], mask2=s['mask2'], stereo_flow1=s['stereo_flow1'])

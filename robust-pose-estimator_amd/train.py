@@ -13,6 +13,7 @@ import os
 
 import torch
 
+from . import ops
 from .optim import ClippedAdamW
 from .se3 import SE3
 
@@ -47,6 +48,30 @@ def train_step(model, optimizer, batch):
     torch.mean(loss_pose).backward()
     optimizer.step()
     return loss_pose.detach()
+
+
+def sequence_loss(flow_preds, flow_gt, valid, gamma=0.8, max_flow=400.0):
+    """Upstream RAFT's ``sequence_loss`` (train.py of RAFT: the exponentially weighted L1 distance of every iteration's prediction to the
+    ground-truth flow) -> (loss, metrics with 'epe', '1px', '3px', '5px'): ops.flow_sequence_loss under the name its users look for; its
+    docstring states the definition and the one departure (a masked pixel contributes exactly zero, NaN or not)."""
+    return ops.flow_sequence_loss(flow_preds, flow_gt, valid, gamma=gamma, max_flow=max_flow)
+
+
+def flow_train_step(raft, optimizer, batch, gamma=0.8, max_flow=400.0, iters=None):
+    """One step of training RAFT as RAFT itself is trained, on ground-truth flow: ``batch`` = (image1, image2, flow_gt, valid) -- images
+    (b,3,H,W) 0..255, flow_gt (b,2,H,W) f32, valid (b,H,W) or (b,1,H,W) bool -- as synth.flow_pairs yields it.  zero_grad, one
+    ``grad_encoders`` + ``grad_all_flows`` pass (every prediction an output of the one node, every parameter reached), the sequence loss,
+    backward, ``optimizer.step()`` (a ClippedAdamW skips it on the device when a gradient is not finite).  The batch norms must be frozen
+    (RAFT.freeze_bn / eval mode), as upstream freezes them outside its first stage.  Returns the metrics dict with the loss under 'loss',
+    detached, on the device: nothing here reads a value back."""
+    device = next(raft.parameters()).device
+    image1, image2, flow_gt, valid = [x.to(device) for x in batch]
+    optimizer.zero_grad()
+    flows = raft(image1, image2, iters=iters, all_flows=True, grad_encoders=True, grad_all_flows=True)[0]
+    loss, metrics = sequence_loss(flows, flow_gt, valid, gamma=gamma, max_flow=max_flow)
+    loss.backward()
+    optimizer.step()
+    return dict(metrics, loss=loss.detach())
 
 
 def _metrics(loss_pose, key, mean):
