@@ -1547,16 +1547,23 @@ def conv3x3_to2_bwd_data(dy, weight, act=None, out=None):
     return out
 
 
+def _same_slices(who, **named):
+    """[pointer, batch stride, ...] of equally shaped channel slices -> (flat list, (b, c, h, w))."""
+    shape, sl = None, []
+    for name, t in named.items():
+        sl += _chan_slice(t, f'{who}: {name}')
+        if shape is None:
+            shape = tuple(t.shape)
+        elif tuple(t.shape) != shape:
+            raise _lib.RpeError(f'{who}: {name} has shape {tuple(t.shape)}, expected {shape}')
+    return sl, shape
+
+
 def relu_backward(grad, act, out=None):
     """rpe_relu_backward: out = act > 0 ? grad : 0 on channel slices (default: in place on ``grad``)."""
     out = grad if out is None else out
-    gp, gbs = _chan_slice(grad, 'relu_backward: grad')
-    ap, abs_ = _chan_slice(act, 'relu_backward: act')
-    op, obs = _chan_slice(out, 'relu_backward: out')
-    b, c, hh, ww = grad.shape
-    if tuple(act.shape) != (b, c, hh, ww) or tuple(out.shape) != (b, c, hh, ww):
-        raise _lib.RpeError('relu_backward: grad, act and out must have one shape')
-    check(lib().rpe_relu_backward(gp, gbs, ap, abs_, b, c, hh * ww, op, obs, stream_ptr()), 'rpe_relu_backward')
+    sl, (b, c, hh, ww) = _same_slices('relu_backward', grad=grad, act=act, out=out)
+    check(lib().rpe_relu_backward(*sl[:4], b, c, hh * ww, *sl[4:], stream_ptr()), 'rpe_relu_backward')
     return out
 
 
@@ -1579,23 +1586,11 @@ def sum_groups(parts, bias=None, relu=False, out=None):
 
 
 # ------------------------------------------------------------------------------------------------- backward of RAFT's update block
-def _gate_slices(who, **named):
-    """[pointer, batch stride, ...] of equally shaped channel slices -> (flat list, (b, c, h, w))."""
-    shape, sl = None, []
-    for name, t in named.items():
-        sl += _chan_slice(t, f'{who}: {name}')
-        if shape is None:
-            shape = tuple(t.shape)
-        elif tuple(t.shape) != shape:
-            raise _lib.RpeError(f'{who}: {name} has shape {tuple(t.shape)}, expected {shape}')
-    return sl, shape
-
-
 def gru_gates_zr_recompute(zr_pre, h, z, r, rh):
     """rpe_gru_gates_zr_recompute: z = s(zr_pre[:, :c]), r = s(zr_pre[:, c:]), rh = r h from the pre-activations (b,2c,h,w; bias added) -- the
     gates with everything their adjoints read kept.  Channel slices."""
     zp, zbs = _chan_slice(zr_pre, 'gru_gates_zr_recompute: zr_pre')
-    sl, (b, c, hh, ww) = _gate_slices('gru_gates_zr_recompute', h=h, z=z, r=r, rh=rh)
+    sl, (b, c, hh, ww) = _same_slices('gru_gates_zr_recompute', h=h, z=z, r=r, rh=rh)
     if tuple(zr_pre.shape) != (b, 2 * c, hh, ww):
         raise _lib.RpeError(f'gru_gates_zr_recompute: zr_pre must be ({b},{2 * c},{hh},{ww})')
     check(lib().rpe_gru_gates_zr_recompute(zp, zbs, *sl[:2], b, c, hh * ww, *sl[2:], stream_ptr()), 'rpe_gru_gates_zr_recompute')
@@ -1604,7 +1599,7 @@ def gru_gates_zr_recompute(zr_pre, h, z, r, rh):
 
 def gru_gates_h_recompute(q_pre, z, h, q, h_new):
     """rpe_gru_gates_h_recompute: q = tanh(q_pre), h_new = (1 - z) h + z q.  Channel slices."""
-    sl, (b, c, hh, ww) = _gate_slices('gru_gates_h_recompute', q_pre=q_pre, z=z, h=h, q=q, h_new=h_new)
+    sl, (b, c, hh, ww) = _same_slices('gru_gates_h_recompute', q_pre=q_pre, z=z, h=h, q=q, h_new=h_new)
     check(lib().rpe_gru_gates_h_recompute(*sl[:6], b, c, hh * ww, *sl[6:], stream_ptr()), 'rpe_gru_gates_h_recompute')
     return q, h_new
 
@@ -1613,7 +1608,7 @@ def gru_gates_zq_backward(d_h_new, h, z, q, d_z_pre, d_q_pre, d_h):
     """rpe_gru_gates_zq_backward, the adjoint of one GRU half's blend h' = (1 - z) h + z q from d_h_new and the post-activation z, q:
     d_z_pre = d (q - h) z (1 - z), d_q_pre = d z (1 - q^2), d_h = d (1 - z) (the direct term).  Channel slices (d_z_pre: e.g. the first half of
     the stacked z | r buffer); the outputs must not overlap the inputs."""
-    sl, (b, c, hh, ww) = _gate_slices('gru_gates_zq_backward', d_h_new=d_h_new, h=h, z=z, q=q, d_z_pre=d_z_pre, d_q_pre=d_q_pre, d_h=d_h)
+    sl, (b, c, hh, ww) = _same_slices('gru_gates_zq_backward', d_h_new=d_h_new, h=h, z=z, q=q, d_z_pre=d_z_pre, d_q_pre=d_q_pre, d_h=d_h)
     check(lib().rpe_gru_gates_zq_backward(*sl[:8], b, c, hh * ww, *sl[8:], stream_ptr()), 'rpe_gru_gates_zq_backward')
     return d_z_pre, d_q_pre, d_h
 
@@ -1621,7 +1616,7 @@ def gru_gates_zq_backward(d_h_new, h, z, q, d_z_pre, d_q_pre, d_h):
 def gru_gates_r_backward(d_rh, h, r, d_h_in, d_r_pre, d_h_out):
     """rpe_gru_gates_r_backward, once convq's data gradient d_rh = d loss / d (r h) is known: d_r_pre = d_rh h r (1 - r), d_h_out = d_h_in +
     d_rh r.  d_h_out may be d_h_in or d_rh."""
-    sl, (b, c, hh, ww) = _gate_slices('gru_gates_r_backward', d_rh=d_rh, h=h, r=r, d_h_in=d_h_in, d_r_pre=d_r_pre, d_h_out=d_h_out)
+    sl, (b, c, hh, ww) = _same_slices('gru_gates_r_backward', d_rh=d_rh, h=h, r=r, d_h_in=d_h_in, d_r_pre=d_r_pre, d_h_out=d_h_out)
     check(lib().rpe_gru_gates_r_backward(*sl[:8], b, c, hh * ww, *sl[8:], stream_ptr()), 'rpe_gru_gates_r_backward')
     return d_r_pre, d_h_out
 
@@ -1744,38 +1739,26 @@ def bn_frozen_backward(dy, z, gamma, conv_bias, mean, var, eps, dz=None):
     (behind the ReLU mask) and the raw convolution output z -> (dz = s dy, d_gamma, d_beta, d_conv_bias); ``dz`` may be given (dy itself: in
     place).  The per-channel sums run in f64 under a fixed tree."""
     who = 'bn_frozen_backward'
-    dp, dbs = _chan_slice(dy, f'{who}: dy')
-    zp, zbs = _chan_slice(z, f'{who}: z')
-    b, c, hh, ww = dy.shape
-    if tuple(z.shape) != (b, c, hh, ww):
-        raise _lib.RpeError(f'{who}: dy and z must have one shape')
+    dz = torch.empty(dy.shape, dtype=torch.float32, device=dy.device) if dz is None else dz
+    sl, (b, c, hh, ww) = _same_slices(who, dy=dy, z=z, dz=dz)
     for name, t in (('gamma', gamma), ('mean', mean), ('var', var)) + ((('conv_bias', conv_bias),) if conv_bias is not None else ()):
         _f32(t, f'{who}: {name}', numel=c)
-    dz = torch.empty(b, c, hh, ww, dtype=torch.float32, device=dy.device) if dz is None else dz
-    if tuple(dz.shape) != (b, c, hh, ww):
-        raise _lib.RpeError(f'{who}: dz must be ({b},{c},{hh},{ww})')
-    op, obs = _chan_slice(dz, f'{who}: dz')
     nws = lib().rpe_bn_frozen_backward_workspace_bytes(b, c, hh * ww)
     if nws == 0:
         raise _lib.RpeError(f'{who}: empty tensors')
     ws = torch.empty(nws, dtype=torch.uint8, device=dy.device)
     dg, dbeta, dcb = (torch.empty(c, dtype=torch.float32, device=dy.device) for _ in range(3))
-    check(lib().rpe_bn_frozen_backward(dp, dbs, zp, zbs, ptr(gamma), ptr(conv_bias), ptr(mean), ptr(var), float(eps), b, c, hh * ww, ptr(dg),
-                                       ptr(dbeta), ptr(dcb), op, obs, ptr(ws), stream_ptr()), 'rpe_bn_frozen_backward')
+    check(lib().rpe_bn_frozen_backward(*sl[:4], ptr(gamma), ptr(conv_bias), ptr(mean), ptr(var), float(eps), b, c, hh * ww, ptr(dg),
+                                       ptr(dbeta), ptr(dcb), *sl[4:], ptr(ws), stream_ptr()), 'rpe_bn_frozen_backward')
     return dz, dg, dbeta, dcb
 
 
 def instnorm_backward(dy, z, eps=1e-5, dz=None):
     """rpe_instnorm_backward: dz = (dy - mean(dy) - xh mean(dy xh)) / sigma per plane of an instance norm without affine parameters, from dy
     (behind the ReLU mask) and the norm's input z; plane moments in f64.  ``dz`` defaults to a new tensor (dy itself: in place)."""
-    dp, dbs = _chan_slice(dy, 'instnorm_backward: dy')
-    zp, zbs = _chan_slice(z, 'instnorm_backward: z')
-    b, c, hh, ww = dy.shape
-    dz = torch.empty(b, c, hh, ww, dtype=torch.float32, device=dy.device) if dz is None else dz
-    if tuple(z.shape) != (b, c, hh, ww) or tuple(dz.shape) != (b, c, hh, ww):
-        raise _lib.RpeError('instnorm_backward: dy, z and dz must have one shape')
-    op, obs = _chan_slice(dz, 'instnorm_backward: dz')
-    check(lib().rpe_instnorm_backward(dp, dbs, zp, zbs, b, c, hh * ww, float(eps), op, obs, stream_ptr()), 'rpe_instnorm_backward')
+    dz = torch.empty(dy.shape, dtype=torch.float32, device=dy.device) if dz is None else dz
+    sl, (b, c, hh, ww) = _same_slices('instnorm_backward', dy=dy, z=z, dz=dz)
+    check(lib().rpe_instnorm_backward(*sl[:4], b, c, hh * ww, float(eps), *sl[4:], stream_ptr()), 'rpe_instnorm_backward')
     return dz
 
 
@@ -1783,13 +1766,10 @@ def split_act_backward(grad, act, half, out=None):
     """rpe_split_act_backward: grad (1 - act^2) on channels [0, half) and act > 0 ? grad : 0 on the rest, ``act`` = the activated output
     (tanh | ReLU: the context encoder's net | inp); default in place on ``grad``."""
     out = grad if out is None else out
-    gp, gbs = _chan_slice(grad, 'split_act_backward: grad')
-    ap, abs_ = _chan_slice(act, 'split_act_backward: act')
-    op, obs = _chan_slice(out, 'split_act_backward: out')
-    b, c, hh, ww = grad.shape
-    if tuple(act.shape) != (b, c, hh, ww) or tuple(out.shape) != (b, c, hh, ww) or not 0 <= half <= c:
-        raise _lib.RpeError('split_act_backward: grad, act and out must have one shape, and 0 <= half <= channels')
-    check(lib().rpe_split_act_backward(gp, gbs, ap, abs_, b, c, half, hh * ww, op, obs, stream_ptr()), 'rpe_split_act_backward')
+    sl, (b, c, hh, ww) = _same_slices('split_act_backward', grad=grad, act=act, out=out)
+    if not 0 <= half <= c:
+        raise _lib.RpeError('split_act_backward: 0 <= half <= channels expected')
+    check(lib().rpe_split_act_backward(*sl[:4], b, c, half, hh * ww, *sl[4:], stream_ptr()), 'rpe_split_act_backward')
     return out
 
 

@@ -36,13 +36,12 @@ fields are present; each stage includes the ones above it:
             for an encoder none of whose parameters requires grad; the 94 gradients leave the node as the gradients of its inputs.
             Every launch and every gradient of 'corr' keeps its bits.  This is what the reference's freeze_flow(False) trains.
 A gradient per iteration (``grad_all_flows``, any depth): a record may carry ``earlier``, the N - 1 earlier up-sampled predictions, and the
-node then has them as further outputs, behind the ones above (flows, hidden_out, context_out; then pass by pass the earlier predictions)
-so that those keep their positions.  Prediction k depends on the parameters through net_k only -- coords1 is detached --, so the gradient
-of a loss over all predictions (RAFT's sequence loss, ops.flow_sequence_loss) is the same walk with one more tail per iteration: in front
-of the step that takes d net_k on, a prediction k that received a gradient runs raft_tail_backward on (net_k, flow_low_k, g_k)
-(GradPass.tail_inputs: both lie in the saved entry state of iteration k + 1), its d_net is added to the carried d net_k and its eight head
-gradients to the heads' sum, which runs k = N, N - 1, .. 1, one term at a time, at every depth.  A prediction without a gradient costs no
+node then has them as further outputs, behind the ones above (flows, hidden_out, context_out; then pass by pass the earlier predictions).
+Prediction k depends on the parameters through net_k only -- coords1 is detached --, so the gradient of a loss over all predictions
+(RAFT's sequence loss, ops.flow_sequence_loss) is the same walk with one more tail per iteration, on (net_k, flow_low_k, g_k) in front of
+the step that takes d net_k on: _through_time, the one walk at every depth, says the rest.  A prediction without a gradient costs no
 tail; with a gradient on the last prediction alone launches and bits are those of a record without ``earlier``.
+Gradients added in f64 and rounded once go through _sum_f64; _split_bwd_weight forms a stride-1 weight gradient on pieces of a small map.
 Refused before any launch (RAFT.check_grad_heads): update_fp16, CONV_BF16X3, mixed_precision -- a route that rounds the heads' operands
 has no honest gradient here -- and upsample=False; for 'corr' also alternate_corr (no pyramid) and CORR_BF16X3 (RAFT.check_grad_corr); for
 'encoders' also a batch norm in training mode and an active dropout in an encoder (_check_modes).
@@ -73,12 +72,11 @@ UPDATE_GROUP_3X3, UPDATE_GROUP_5TAP, UPDATE_GROUP_1X1 = 16, 32, 64
 # the 1x1 output layer (64); a stride-2 layer's recomputation runs ops.conv_direct on groups of at most ENC_CHAIN terms
 ENC_GROUP_3X3_FWD, ENC_GROUP_3X3_BWD, ENC_GROUP_1X1, ENC_CHAIN = 16, 32, 64, 288
 ENC_WGRAD_CHAIN = 1024                                                   # pixels rpe_conv_bwd_weight keeps in one chunk (include/rpe.h: its chunk rule)
-# a step's weight gradients under a gradient per iteration (update_step_backward(wgrad_bands=True)): on a map rpe_conv_bwd_weight keeps in
-# one chunk, the pixels one GEMM sums -- row bands of the map, the bands' results added in f64
-UPDATE_WGRAD_BAND = 64
-# likewise the encoders' stride-1 layers (encoder_backward(wgrad_bands=True)): maps of ENC_WGRAD_CHAIN < b h w <= ENC_BAND_CAP pixels, which
-# the kernel sums in chains of ENC_WGRAD_CHAIN, in bands of ENC_WGRAD_BAND pixels
-ENC_WGRAD_BAND, ENC_BAND_CAP = 256, 4096
+# _split_bwd_weight's policies (its keywords; none: one launch).  Under ``wgrad_bands`` (a gradient per iteration) an update step's layers
+# and an encoder's stride-1 layers; with or without it an encoder's run small batches one image each
+UPDATE_WGRAD_BAND, ENC_WGRAD_BAND, ENC_BAND_CAP = 64, 256, 4096
+_UPDATE_BANDS = dict(band=UPDATE_WGRAD_BAND, cap=ENC_WGRAD_CHAIN)
+_ENCODER, _ENCODER_BANDS = dict(per_image=True), dict(per_image=True, band=ENC_WGRAD_BAND, over=ENC_WGRAD_CHAIN, cap=ENC_BAND_CAP)
 
 
 # ------------------------------------------------------------------------------------------------- weight packings
@@ -205,23 +203,37 @@ def raft_tail_backward(net, flow_low, grad_up, fh_params, mask_params):
     return d_net, (dw1[:hid], db1[:hid], dw_fh2, db_fh2, dw1[hid:], db1[hid:], dw_m2, db_m2)
 
 
-def _banded_bwd_weight(x, dy, kernel, bias=True, band=UPDATE_WGRAD_BAND, cap=ENC_WGRAD_CHAIN):
-    """ops.conv_bwd_weight on a map of at most ``cap`` pixels, where the kernel adds up to ENC_WGRAD_CHAIN products of an output element in
-    ONE f32 chain: the gradient is formed per band of rows -- dy zero outside the band, so the other pixels' products are exact zeros and
-    add nothing to the chain -- of about ``band`` pixels, and the bands are added in f64 and rounded once (sum_groups).  Every band costs
-    the whole map's GEMM, hence the cap; a larger map, or one that is a single band, is the one launch it always was."""
+def _sum_f64(terms):
+    """The sum of a list of equally shaped gradients, added in list order in f64 and rounded once (sum_groups); of a list of tuples of
+    gradients, the list of the sums position by position.  A single term passes through unchanged, and so does an absent (None) gradient.
+    The view sum_groups gets: n terms of shape (c, ...) as (n, 1, c, rest, 1) -- a weight's output channels, a bias's elements."""
+    if isinstance(terms[0], (tuple, list)):
+        return [_sum_f64(ts) for ts in zip(*terms)]
+    if len(terms) == 1 or terms[0] is None:
+        return terms[0]
+    return sum_groups(torch.stack(terms).view(len(terms), 1, terms[0].shape[0], -1, 1)).view_as(terms[0])
+
+
+def _split_bwd_weight(x, dy, kernel, bias=True, band=0, over=0, cap=0, per_image=False):
+    """ops.conv_bwd_weight on pieces of the map, their results added in f64 and rounded once (_sum_f64).  rpe_conv_bwd_weight splits
+    K = b h w into chunks only above ENC_WGRAD_CHAIN pixels; below that an output element's products are ONE f32 chain over the map and
+    across the images of the batch (at K = 512, two 16 x 16 maps, 2.6 times the error of a blocked float32 sum).  The pieces: with
+    ``band``, on a map of over < b h w <= cap pixels, row bands of about ``band`` pixels -- dy zero outside the band, so the other
+    pixels' products are exact zeros and add nothing to the chain; every band costs the whole map's GEMM, hence the cap --; else, with
+    ``per_image``, one image each of a batch of several with at most ENC_WGRAD_CHAIN pixels in all; else the whole map, one launch."""
     b, _, hh, ww = dy.shape
     rows = max(1, band // (b * ww))
-    if b * hh * ww > cap or rows >= hh:
+    if band and over < b * hh * ww <= cap and rows < hh:
+        per = []
+        for lo in range(0, hh, rows):
+            part = torch.zeros(dy.shape, dtype=torch.float32, device=dy.device)
+            part[:, :, lo:lo + rows] = dy[:, :, lo:lo + rows]
+            per.append(conv_bwd_weight(x, part, kernel, bias=bias))
+    elif per_image and b > 1 and b * hh * ww <= ENC_WGRAD_CHAIN:
+        per = [conv_bwd_weight(x[i:i + 1], dy[i:i + 1], kernel, bias=bias) for i in range(b)]
+    else:
         return conv_bwd_weight(x, dy, kernel, bias=bias)
-    per = []
-    for lo in range(0, hh, rows):
-        part = torch.zeros(dy.shape, dtype=torch.float32, device=dy.device)
-        part[:, :, lo:lo + rows] = dy[:, :, lo:lo + rows]
-        per.append(conv_bwd_weight(x, part, kernel, bias=bias))
-    dw0, n = per[0][0], len(per)
-    dw = sum_groups(torch.stack([p[0] for p in per]).view(n, 1, dw0.shape[0], -1, dw0.shape[3])).view_as(dw0)
-    return dw, (sum_groups(torch.stack([p[1] for p in per]).view(n, 1, -1, 1, 1)).view(-1) if bias else None)
+    return tuple(_sum_f64(per))
 
 
 def update_step_backward(hx, inp, corr, d_net, params, ret_d_corr=False, wgrad_bands=False):
@@ -236,8 +248,8 @@ def update_step_backward(hx, inp, corr, d_net, params, ret_d_corr=False, wgrad_b
     convc1's transposed 1x1 weight applied to the gradient in front of convc1's ReLU (conv_split, groups of UPDATE_GROUP_1X1 channels added
     in f64): what ops.corr_lookup_backward accumulates.  Without the flag the launches and the results are those of a call without it.  Every intermediate is recomputed here with the forward's kernels on
     groups of input channels added in f64 (conv_split), which also compute the data gradients; the gradients that reach a tensor by several
-    paths are added in that same f64 sum.  ``wgrad_bands``: the eleven weight gradients through _banded_bwd_weight (small maps: row bands
-    added in f64 instead of one f32 chain over the map); without it the launches and the bits are those of before.  f32 throughout,
+    paths are added in that same f64 sum.  ``wgrad_bands``: the eleven weight gradients under _split_bwd_weight's banded policy (small maps: row
+    bands added in f64 instead of one f32 chain over the map); without it one launch each.  f32 throughout,
     bit-identical from run to run, a row's result independent of its batch."""
     who = 'update_step_backward'
     hx, inp, corr, d_net = _nchw(hx, f'{who}: hx'), _nchw(inp, f'{who}: inp'), _nchw(corr, f'{who}: corr'), _nchw(d_net, f'{who}: d_net')
@@ -252,7 +264,7 @@ def update_step_backward(hx, inp, corr, d_net, params, ret_d_corr=False, wgrad_b
     if tuple(inp.shape) != (b, c, hh, ww) or tuple(d_net.shape) != (b, c, hh, ww) or tuple(corr.shape[::2]) != (b, hh) or corr.shape[3] != ww:
         raise _lib.RpeError(f'{who}: inp and d_net must be ({b},{c},{hh},{ww}) and corr (b,324,h8,w8) for hx {tuple(hx.shape)}')
     P = _packed(_UpdatePacked, params)
-    wgrad = _banded_bwd_weight if wgrad_bands else conv_bwd_weight
+    wgrad = lambda x, dy, kernel: _split_bwd_weight(x, dy, kernel, **(_UPDATE_BANDS if wgrad_bands else {}))
     G3, G5, G1 = UPDATE_GROUP_3X3, UPDATE_GROUP_5TAP, UPDATE_GROUP_1X1
     new = lambda ch: torch.empty(b, ch, hh, ww, dtype=torch.float32, device=hx.device)
     with torch.no_grad():
@@ -409,23 +421,6 @@ def _norm_adjoint(conv, norm, dy, z):
     return instnorm_backward(dy, z, eps=norm.eps, dz=dy), [torch.zeros_like(conv.bias)]
 
 
-def _bwd_weight(x, dy, kernel, bias=True, bands=False):
-    """ops.conv_bwd_weight for the encoders' stride-1 layers.  rpe_conv_bwd_weight splits K = b h w into chunks only above ENC_WGRAD_CHAIN
-    pixels; a batch of several small maps below that would be ONE f32 chain across the images (at K = 512, two 16 x 16 maps, 2.6 times the
-    error of a blocked float32 sum on the output layer's weight).  There each image's GEMM runs alone and the images are added in f64
-    (sum_groups); one image, or a batch the kernel chunks itself, is the one launch it was."""
-    b, _, hh, ww = x.shape
-    if bands and b * hh * ww > ENC_WGRAD_CHAIN:                  # (``bands``: a gradient per iteration; without it the launches of before)
-        return _banded_bwd_weight(x, dy, kernel, bias, ENC_WGRAD_BAND, ENC_BAND_CAP)
-    if b == 1 or b * hh * ww > ENC_WGRAD_CHAIN:
-        return conv_bwd_weight(x, dy, kernel, bias=bias)
-    per = [conv_bwd_weight(x[i:i + 1], dy[i:i + 1], kernel, bias=bias) for i in range(b)]
-    dw0 = per[0][0]
-    dw = sum_groups(torch.stack([p[0] for p in per]).view(b, 1, dw0.shape[0], -1, dw0.shape[3])).view_as(dw0)
-    db = sum_groups(torch.stack([p[1] for p in per]).view(b, 1, -1, 1, 1)).view(-1) if bias else None
-    return dw, db
-
-
 def _block_forward(block, x, P, name):
     """One ResidualBlock again, every intermediate kept: out = relu(skip + relu(norm2(conv2(relu(norm1(conv1 x)))))), skip = x or
     norm3(conv1x1(x)) -> the record _block_backward reads."""
@@ -444,18 +439,18 @@ def _block_forward(block, x, P, name):
     return r
 
 
-def _block_backward(block, r, d_out, P, name, bands=False):
-    """-> (d_x, the block's gradients in block_params' order) from the record of _block_forward."""
+def _block_backward(block, r, d_out, P, name, wgrad=_ENCODER):
+    """-> (d_x, the block's gradients in block_params' order) from the record of _block_forward; ``wgrad``: _split_bwd_weight's keywords."""
     x, s2 = r['x'], block.downsample is not None
     g = relu_backward(d_out, r['out'], out=torch.empty_like(d_out))          # behind the block's last ReLU: ONE mask, the gradient of both paths
     gy = relu_backward(g, r['y'], out=torch.empty_like(g))
     dz2, gn2 = _norm_adjoint(block.conv2, block.norm2, gy, r['z2'])
-    dw2 = _bwd_weight(r['a1'], dz2, (3, 3), bias=False, bands=bands)[0]
+    dw2 = _split_bwd_weight(r['a1'], dz2, (3, 3), False, **wgrad)[0]
     da1 = P.conv_split(f'{name}.conv2.t', dz2, P.tr(f'{name}.conv2', block.conv2.weight), None, False, ENC_GROUP_3X3_BWD)
     relu_backward(da1, r['a1'])
     dz1, gn1 = _norm_adjoint(block.conv1, block.norm1, da1, r['z1'])
     if not s2:
-        dw1 = _bwd_weight(x, dz1, (3, 3), bias=False, bands=bands)[0]
+        dw1 = _split_bwd_weight(x, dz1, (3, 3), False, **wgrad)[0]
         # d x = conv1's data gradient + the shortcut's g, one more term of the same f64 sum
         d_x = P.conv_split(f'{name}.conv1.t', dz1, P.tr(f'{name}.conv1', block.conv1.weight), None, False, ENC_GROUP_3X3_BWD, extra=1,
                            fill=lambda terms: copy_planes(g, terms[0]))
@@ -520,7 +515,8 @@ def encoder_backward(enc, images, d_out, raw255=True, split_act=False, route=Non
     the module switches).  Refused before any launch: a batch norm in training mode, dropout > 0 in training mode, update_fp16,
     CONV_BF16X3, mixed_precision, tensors that are not float32, a d_out that is not the encoder's output shape.  f32, bit-identical
     from run to run.  ``wgrad_bands`` (the node sets it under a gradient per iteration): the stride-1 layers' weight gradients on maps of
-    ENC_WGRAD_CHAIN < b h w <= ENC_BAND_CAP pixels in row bands added in f64 (_banded_bwd_weight); without it the launches of before."""
+    ENC_WGRAD_CHAIN < b h w <= ENC_BAND_CAP pixels in row bands added in f64; with it or without, a batch of several images of at most
+    ENC_WGRAD_CHAIN pixels in all one image each, added in f64 (_split_bwd_weight's two encoder policies)."""
     from . import raft
     who = 'encoder_backward'
     _check_modes(who, enc)
@@ -564,10 +560,11 @@ def encoder_backward(enc, images, d_out, raw255=True, split_act=False, route=Non
         else:
             d = d_out
         # the adjoints, last layer first
-        grads = list(_bwd_weight(x, d, (1, 1), bands=wgrad_bands))
+        wgrad = _ENCODER_BANDS if wgrad_bands else _ENCODER
+        grads = list(_split_bwd_weight(x, d, (1, 1), **wgrad))
         d = P.conv_split('conv2.t', d, P.tr('conv2', w2), None, False, ENC_GROUP_1X1)
         for (name, blk), r in zip(reversed(blocks), reversed(recs)):
-            d, g = _block_backward(blk, r, d, P, name, wgrad_bands)
+            d, g = _block_backward(blk, r, d, P, name, wgrad)
             grads = g + grads
             r.clear()
         relu_backward(d, a0)
@@ -669,55 +666,56 @@ def _by_field(passes, tensors):
     return [{name: next(it) for name in p.tensors()} for p in passes], list(it)
 
 
-def _through_time(rec, t, upd, grads, heads=None, g_early=(), hg=None):
-    """The steps k = N .. 1 of one pass behind grads['hidden'] = d net_N (the tail's, at 'encoders' plus what arrived on hidden_out); from
-    'corr' on every step's lookup adjoint and, after step 1, the build's.  ``t``: the pass's tensor inputs by field.  ``g_early``
-    (``grad_all_flows``): the gradients that arrived on the earlier predictions k = 1 .. N - 1, None where none did.  In front of step
-    k + 1 -- the step that takes d net_k on to d net_{k-1} runs next -- a prediction k that received one runs its own tail
-    (raft_tail_backward on GradPass.tail_inputs(k)) under ``heads``, whose d_net is ADDED to the carried d net_k; one that received none
-    costs nothing.  While nothing has arrived yet (no gradient on the last prediction, nor on hidden_out) the carried gradient is absent
-    and the steps above the first such prediction are not run: they would carry zeros.  ``hg``: the eight head gradients of the pass's
-    last tail, or None; the earlier tails' are added to it one by one, so the heads' sum runs ((N + (N - 1)) + ...) + 1 at every depth.
-    Fills ``grads`` (field -> gradient); -> (the 22 update gradients summed in descending k, zeros for a pass without a step; the
-    heads' sum, None without a tail).  The steps' sum: without a gradient on an earlier prediction the float32 chain it always was (its
-    bits are kept); with one, every step's 22 gradients are kept and added in f64, rounded once (sum_groups) -- N - 1 roundings fewer
-    on the weights every step contributes to -- and every step forms its weight gradients in row bands on small maps
-    (update_step_backward(wgrad_bands=True))."""
-    with_corr = rec.fmap1 is not None
-    inp, d = t['inp'].detach(), grads['hidden']
+def _through_time(rec, t, heads, upd, grads, g_early=(), hg=None):
+    """The walk over one pass's predictions k = N .. 1, at every depth, behind grads['hidden'] = d net_N (the last tail's, at 'encoders'
+    plus what arrived on hidden_out): the steps and, from 'corr' on, every step's lookup adjoint and, after step 1, the build's.  ``t``:
+    the pass's tensor inputs by field; ``heads``: (the flow head's four parameters, the mask head's).  ``g_early`` (``grad_all_flows``):
+    the gradients that arrived on the earlier predictions k = 1 .. N - 1, None where none did.  In front of step k + 1 -- the step that
+    takes d net_k on to d net_{k-1} runs next -- a prediction k that received one runs its own tail (GradPass.tail_inputs(k)), whose d_net
+    is ADDED to the carried d net_k.  While nothing has arrived yet the carried gradient is absent and the steps above the first such
+    prediction are not run: they would carry zeros.  A record of depth 'heads' has no steps: the same walk runs its tails alone.
+    ``hg``: the eight head gradients of the pass's last tail, or None; the earlier tails' are added to it one by one, so the heads' sum
+    runs ((N + (N - 1)) + ...) + 1 at every depth.  Fills ``grads`` (field -> gradient); -> the heads' sum (None each without a tail),
+    then the 22 update gradients summed in descending k (zeros for a pass without a step; none at 'heads'): without a gradient on an
+    earlier prediction the float32 chain it always was; with one, every step forms its weight gradients in row bands on small maps
+    (wgrad_bands) and the steps' 22 gradients are kept and added in f64, rounded once (_sum_f64)."""
+    steps, with_corr = rec.states is not None, rec.fmap1 is not None
+    inp, d = (t['inp'].detach() if steps else None), grads['hidden']
     d_inp, ug, vol, levels = None, None, None, None
     early, per_step = any(g is not None for g in g_early), []
-    for k in reversed(range(len(rec.states))):
-        if k + 1 <= len(g_early) and g_early[k] is not None:           # prediction k + 1 < N, formed from net_{k+1}: states[k + 1]
-            dn, tg = raft_tail_backward(*rec.tail_inputs(k + 1), g_early[k].contiguous(), heads[:4], heads[4:])
-            d = _plus(d, dn)
-            hg = list(tg) if hg is None else [a + b for a, b in zip(hg, tg)]
-        if d is None:
+    bands = {'wgrad_bands': True} if early else {}             # (absent without a gradient per iteration: the call of before)
+    for k in reversed(range(len(rec.states) if steps else len(g_early))):
+        if k < len(g_early) and g_early[k] is not None:                # prediction k + 1 < N, formed from net_{k+1}: states[k + 1]
+            dn, tg = raft_tail_backward(*rec.tail_inputs(k + 1), g_early[k].contiguous(), *heads)
+            hg = _plus(hg, tg)
+            if steps:
+                d = _plus(d, dn)
+        if not steps or d is None:
             continue
-        r = update_step_backward(rec.states[k][0], inp, rec.corr(k), d, upd, ret_d_corr=with_corr, **({'wgrad_bands': True} if early else {}))
+        r = update_step_backward(rec.states[k][0], inp, rec.corr(k), d, upd, ret_d_corr=with_corr, **bands)
         d, di, sg = r[:3]
         if with_corr:
             if vol is None:
                 levels = r[3].shape[1] // 81
                 vol = ops.corr_grad_volume(r[3].shape[0], *r[3].shape[2:], levels, device=r[3].device)
             ops.corr_lookup_backward(rec.states[k][1], r[3], vol)
-        d_inp = di if d_inp is None else d_inp + di
+        d_inp = _plus(d_inp, di)
         if early:
             per_step.append(sg)
         else:
-            ug = list(sg) if ug is None else [a + b for a, b in zip(ug, sg)]
-    if len(per_step) == 1:
-        ug = list(per_step[0])
-    elif per_step:                                              # (a weight as (steps,1,cout,rest,1), a bias as (steps,1,c,1,1): _bwd_weight's views)
-        ug = [sum_groups(torch.stack(ts).view(len(ts), 1, ts[0].shape[0], -1, 1)).view_as(ts[0]) for ts in zip(*per_step)]
-    grads['net0'], grads['inp'] = d, d_inp
+            ug = _plus(ug, sg)
+    ug = _sum_f64(per_step) if per_step else ug if ug is not None else [torch.zeros_like(p) for p in upd]
+    if steps:
+        grads['net0'], grads['inp'] = d, d_inp
     if vol is not None:                                         # (S h8 w8 4 bytes per pair: freed on return, before the next pass)
         grads['fmap1'], grads['fmap2'] = ops.corr_build_backward(vol, t['fmap1'].detach(), t['fmap2'].detach(), levels)
-    return (ug if ug is not None else [torch.zeros_like(p) for p in upd]), hg
+    return [*(hg or [None] * 8), *ug]
 
 
 def _plus(a, b):
-    """a + b of two gradients either of which may be absent."""
+    """a + b of two gradients, or of two lists of gradients element by element (-> a list); a, or an element of either, may be absent."""
+    if isinstance(b, (list, tuple)):
+        return list(b) if a is None else [_plus(x, y) for x, y in zip(a, b)]
     return b if a is None else a if b is None else a + b
 
 
@@ -777,7 +775,7 @@ class _RaftGradFn(torch.autograd.Function):
     """Gradient-free RAFT passes as ONE autograd node: inputs the records' tensor fields, pass by pass in field order, then the eight head
     parameters, below 'heads' the 22 of UPDATE_PARAMS and at 'encoders' encoder_params(fnet) + encoder_params(cnet); outputs the
     up-sampled flows unchanged and, at 'encoders', behind them every pass's hidden_out and then every pass's context_out.  ``passes`` (the
-    records) stay on the node.  Backward, per pass in the order given: the tail, then the steps (_through_time); at 'encoders' the two
+    records) stay on the node.  Backward, per pass in the order given: the last tail, then the walk (_through_time); at 'encoders' the two
     encoders once, behind the last pass (_encoders_backward).  The parameter gradients are summed over the steps in descending k,
     concatenated (heads | update) per pass, then summed over the passes in the given order; a pass none of whose outputs anything
     differentiates is skipped and launches nothing: the sum's bits do not depend on the autograd engine's scheduling."""
@@ -797,10 +795,8 @@ class _RaftGradFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *grads_out):
         fields, params = _by_field(ctx.passes, ctx.saved_tensors)
-        heads, upd, n = params[:8], params[8:30], len(ctx.passes)
-        deep = ctx.encoders is not None
-        totals, flat, all_grads = None, [], []
-        any_early = False
+        heads, upd, n, deep = (params[:4], params[4:8]), params[8:30], len(ctx.passes), ctx.encoders is not None
+        totals, flat, all_grads, any_early = None, [], [], False
         at = 3 * n if deep else n                                  # the earlier predictions' gradients: behind the existing outputs, pass by pass
         for i, (rec, t) in enumerate(zip(ctx.passes, fields)):
             g, g_hid, g_ctx = grads_out[i], (grads_out[n + i] if deep else None), (grads_out[2 * n + i] if deep else None)
@@ -808,28 +804,18 @@ class _RaftGradFn(torch.autograd.Function):
             at += len(g_early)
             early = any(x is not None for x in g_early)
             any_early = any_early or early
-            grads = dict.fromkeys(t)
-            both = None
+            grads, both = dict.fromkeys(t), None
             if g is not None:
-                grads['hidden'], both = raft_tail_backward(t['hidden'].detach(), t['flow_low'], g.contiguous(), heads[:4], heads[4:])
-                both = list(both)
-            if g_hid is not None:                                  # (once, before step N)
-                grads['hidden'] = _plus(grads['hidden'], g_hid)
-            if rec.depth == 'heads':                               # no path through time: the earlier tails' head gradients alone, k descending
-                for k in reversed(range(len(g_early))):
-                    if g_early[k] is not None:
-                        tg = raft_tail_backward(*rec.tail_inputs(k + 1), g_early[k].contiguous(), heads[:4], heads[4:])[1]
-                        both = list(tg) if both is None else [a + b for a, b in zip(both, tg)]
-            elif grads['hidden'] is not None or early:
-                ug, both = _through_time(rec, t, upd, grads, heads, g_early, both)
-                both = [None] * 8 + ug if both is None else both + ug
+                grads['hidden'], both = raft_tail_backward(t['hidden'].detach(), t['flow_low'], g.contiguous(), *heads)
+            grads['hidden'] = _plus(grads['hidden'], g_hid)        # (once, before step N)
+            if grads['hidden'] is not None or early:
+                both = _through_time(rec, t, heads, upd, grads, g_early, both)
             if g_ctx is not None:                                  # (once, behind the steps' sum)
                 grads['inp'] = _plus(grads['inp'], g_ctx)
-            if both is not None:
-                totals = both if totals is None else [_plus(a, b) for a, b in zip(totals, both)]
+            totals = _plus(totals, both)
             flat += grads.values()
             all_grads.append(grads)
-        totals = list(totals) if totals is not None else [None] * 30
+        totals = totals if totals is not None else [None] * 30
         if deep:
             need = ctx.needs_input_grad[2 + len(flat) + 30:]
             n_f = len(encoder_params(ctx.encoders[0]))
@@ -856,9 +842,9 @@ def attach(passes, head_params, update_params=None, encoders=None, ret_earlier=F
     flat = [t for p in passes for t in p.tensors().values()]
     enc_params = [] if encoders is None else encoder_params(encoders[0]) + encoder_params(encoders[1])
     with torch.enable_grad():
-        outs = list(_RaftGradFn.apply(list(passes), None if encoders is None else tuple(encoders), *flat, *fh, *mk, *(update_params or ()), *enc_params))
+        outs = _RaftGradFn.apply(list(passes), None if encoders is None else tuple(encoders), *flat, *fh, *mk, *(update_params or ()), *enc_params)
     n = len(passes)
-    res = outs[:n] if encoders is None else [(outs[i], outs[n + i], outs[2 * n + i]) for i in range(n)]
+    res = list(outs[:n]) if encoders is None else [(outs[i], outs[n + i], outs[2 * n + i]) for i in range(n)]
     if not ret_earlier:
         return res
     it = iter(outs[n if encoders is None else 3 * n:])
